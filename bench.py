@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- env-steps/sec of the batched rollout engine (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python bench.py --gpus 8 --workload pursuit_c5        # BASELINE configs[4]: 32x32, 16 v 60, 262 144 envs over 8 GPUs
 
 One "step" = one pass of the hot path over one batch: a single launch of the fused step kernel (pre-move reward, moves,
@@ -19,13 +19,16 @@ exchanged over RCCL in chunks that overlap with the stepping and waited for at t
 (all-gather), `stats` exchanges per-episode returns only.  At N = 1 `workloads.pursuit_collective` runs that code path in a
 one-rank group (the headline config with recording + exchange in the timed region; `over_headline` = its step time / the headline's).
 
-Timing: W untimed warm-up steps, then REPEATS regions of EXACTLY K steps, each bracketed by barrier + synchronize on both
-sides, max over ranks; `value` / `ms_per_step` are the MEDIAN region, `config.region_ms_per_step` lists all of them.
+Timing: W untimed warm-up steps, then ONE region of EXACTLY K steps, bracketed by barrier + synchronize on both sides, max over
+ranks; `value` / `ms_per_step` are that region.  A plain run does nothing else: set-up, warm-up, the K timed steps, the outputs
+(--dump-outputs DIR: what the last timed step returned, DIR/<name>.npy, float32 / float64, a fixed seeded sample of env instances
+when the whole would pass 48 MB) and the line with `roofline`.
 
-Rank 0 prints ONE JSON line (contract in the task description) with `roofline` and `cpu_baseline`; at N = 1 the same line
-carries `workloads`: the other BASELINE configs (Waterworld configs[2], MultiWalker configs[3], the per-GPU shard of
-configs[4]), the survey's secondary Pursuit mode and Waterworld under StandardizedEnv, timed the same way for a bounded
-number of steps, each with its own roofline and its own bounded cpu_baseline.
+--full adds everything else this script measures: REPEATS regions of K steps (`value` / `ms_per_step` = the MEDIAN region,
+`config.region_ms_per_step` lists all of them), the one-launch-per-step and Python-API passes, `cpu_baseline`, and at N = 1
+`workloads`: the other BASELINE configs (Waterworld configs[2], MultiWalker configs[3], the per-GPU shard of configs[4]), the
+survey's secondary Pursuit mode and Waterworld under StandardizedEnv, timed the same way for a bounded number of steps, each with
+its own roofline and its own bounded cpu_baseline.
 
 cpu_baseline = the C restatement of the reference algorithm (oracle/, kind "port") timed LIVE on this box's host cores;
 when MADRL_REFERENCE_ROOT names a checkout of the reference (never the case on the GPU box, where the tree does not
@@ -51,7 +54,8 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec (/opt/skills/guides/MI355X_MICROARCH.md)
 HBM_COPY_GBPS = 6290.0  # the same guide's measured copy rate (MI355X_MICROARCH.md:34-35): what a pure streaming kernel reaches
 VALU_PEAK_TFLOPS = 157.3  # FP32 vector peak, same guide
-REPEATS = 3             # timed K-step regions per workload (each bracketed by barrier + synchronize); the line reports the median
+REPEATS = 3             # --full: timed K-step regions per workload (each bracketed by barrier + synchronize); the line reports the median
+DUMP_BYTES = 48 << 20   # --dump-outputs: above this, a fixed seeded sample of env instances is written
 
 
 def algorithmic_bytes_per_env_step(P, E, D, rec_bytes):
@@ -247,10 +251,46 @@ class Timer(object):
         return dt, kernel_ms, [r[0] / K * 1e3 for r in regions]
 
 
+def n_regions(args):
+    """timed K-step regions per workload: one in a plain run, REPEATS with --full"""
+    return REPEATS if args.full else 1
+
+
 def region_stats(region_ms):
     s = sorted(region_ms)
     return {"timed_regions": len(s), "region_ms_per_step": [round(x, 6) for x in region_ms], "region_ms_per_step_min": s[0],
-            "region_ms_per_step_median": s[len(s) // 2], "value_is": "median region"}
+            "region_ms_per_step_median": s[len(s) // 2], "value_is": "median region" if len(s) > 1 else "the timed region"}
+
+
+def take_outputs(named):
+    """{name: (device tensor, env axis)} -> {name: host array}: what the last timed step returned, for --dump-outputs.  Floating
+    tensors keep float32 / float64, int32 / int64 become float64, narrower integers float32.  When the whole passes DUMP_BYTES, every
+    array is cut to the same fixed, seeded sample of env instances, written as `env_index`."""
+    import numpy as np
+    import torch
+    wide = (torch.float64, torch.int32, torch.int64)
+    n = {t.shape[ax] for t, ax in named.values()}
+    assert len(n) == 1, n
+    n = n.pop()
+    per_env = sum(t.numel() // n * (8 if t.dtype in wide else 4) for t, _ in named.values())
+    idx = None
+    if per_env * n > DUMP_BYTES:
+        idx = np.sort(np.random.RandomState(0).choice(n, max(1, DUMP_BYTES // per_env), replace=False))
+    out = {}
+    for name, (t, ax) in named.items():
+        if idx is not None:
+            t = t.index_select(ax, torch.as_tensor(idx, device=t.device))
+        out[name] = t.to(torch.float64 if t.dtype in wide else torch.float32).cpu().numpy()
+    if idx is not None:
+        out["env_index"] = idx.astype(np.float64)
+    return out
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def roofline(bytes_per, N, kernel_ms, wall_ms, traffic, kernel, streams=1, **more):
@@ -316,7 +356,7 @@ def ensure_group(dev):
     return True
 
 
-def bench_pursuit(args, variant, K, W, rank, world, dev, cpu_budget, streams=None, reference_pass=True, api_leg=None, coll=None):
+def bench_pursuit(args, variant, K, W, rank, world, dev, cpu_budget, streams=None, reference_pass=True, api_leg=None, coll=None, dump=None):
     import numpy as np
     import torch
     from madrl_amd.maps import rectangle_map
@@ -423,7 +463,12 @@ def bench_pursuit(args, variant, K, W, rank, world, dev, cpu_budget, streams=Non
     for i in range(args.prep):
         one_step(i, False)
     torch.cuda.synchronize()
-    dt, kernel_ms, region_ms = Timer(world, dev, hip_streams, coll=coll).run(one_step, K, W, tail, prepare)
+    dt, kernel_ms, region_ms = Timer(world, dev, hip_streams, coll=coll).run(one_step, K, W, tail, prepare, repeats=n_regions(args))
+    if dump is not None:   # what BatchedPursuitEvade.step() hands back (with N > 1 rewards / dones went to the trajectory slot of step K - 1)
+        rew, dn = (traj[(K - 1) // CH]["rewards"][(K - 1) % CH], traj[(K - 1) // CH]["dones"][(K - 1) % CH]) if coll else \
+                  (torch.cat([e._rew for e in envs]), torch.cat([e._done for e in envs]))
+        dump.update(take_outputs({"observations": (torch.cat([e._obs for e in envs]), 0), "rewards": (rew, 0), "dones": (dn, 0),
+                                  "removed": (torch.cat([e._removed for e in envs]), 0)}))
     kernel_kind = envs[0].kernel_kind
     api = None
     if (bool(cpu_budget) if api_leg is None else api_leg) and not coll:
@@ -445,7 +490,7 @@ def bench_pursuit(args, variant, K, W, rank, world, dev, cpu_budget, streams=Non
         del sh
     del envs, outs, hs
     one = None
-    if reference_pass and S > 1 and not coll:
+    if reference_pass and args.full and S > 1 and not coll:
         # the same batch as ONE launch per step on one stream, in the same process: what the sub-batch streams are compared with
         one = bench_pursuit(args, variant, K, min(W, 20), rank, world, dev, 0, streams=1, reference_pass=False, api_leg=bool(cpu_budget))
     if rank != 0:
@@ -499,7 +544,7 @@ def bench_pursuit(args, variant, K, W, rank, world, dev, cpu_budget, streams=Non
     return out
 
 
-def bench_rollout(args, K, W, rank, world, dev, cpu_budget=0):
+def bench_rollout(args, K, W, rank, world, dev, cpu_budget=0, dump=None):
     """Policy in the loop (the sampler loop the reference's runners drive, runners/rurllab.py:298-305; in-tree instance heuristics/pursuit.py:71-85):
     BASELINE configs[1]'s batch, the device chase policy (madrl_amd/heuristics.py) choosing every action from the observation the step
     kernel just wrote, trajectory tensors filled in place, returns scanned at the end of each horizon -- ShardedRolloutCollector over
@@ -531,9 +576,14 @@ def bench_rollout(args, K, W, rank, world, dev, cpu_budget=0):
     for _ in range(max(3, W // T)):   # the first call allocates, the second captures the graphs
         col.collect()
 
+    last = [None]
+
     def step(i, record):
-        col.collect()
-    dt, kernel_ms, region_ms = Timer(world, dev, None).run(step, calls, 0)
+        last[0] = col.collect()
+    dt, kernel_ms, region_ms = Timer(world, dev, None).run(step, calls, 0, repeats=n_regions(args))
+    if dump is not None:   # the Trajectory list of the last collect() call, time-major, sub-batches joined along the env axis
+        dump.update(take_outputs({k: (torch.cat([getattr(tr, k) for tr in last[0]], 1), 1) for k in ("actions", "rewards", "dones", "returns", "advantages")
+                                  if getattr(last[0][0], k, None) is not None}))
     steps = calls * T
     if rank != 0:
         return None
@@ -562,7 +612,7 @@ def C_void(v):
     return ctypes.c_void_p(v)
 
 
-def bench_other(args, workload, K, W, rank, world, dev, cpu_budget, streams=None, reference_pass=True, api_leg=None):
+def bench_other(args, workload, K, W, rank, world, dev, cpu_budget, streams=None, reference_pass=True, api_leg=None, dump=None):
     """Waterworld (BASELINE configs[2]; `waterworld_std` = the same env under StandardizedEnv, which is how every reference run
     wraps it, runners/run_waterworld.py / run_pursuit.py:57-58), MultiWalker (configs[3]) and the hostage world on the same contract."""
     import numpy as np
@@ -601,11 +651,12 @@ def bench_other(args, workload, K, W, rank, world, dev, cpu_budget, streams=None
         else:
             from madrl_amd.wrappers import StandardizedEnv
             wenvs = [StandardizedEnv(e, scale_reward=0.5, enable_obsnorm=True, enable_rewnorm=True, fused=args.std_fused) for e in envs]
+            last = [None] * S
 
             def step(i, rec):
                 for j in range(S):
                     with torch.cuda.stream(hip_streams[j]):
-                        wenvs[j].step(acts[j][i % 8])
+                        last[j] = wenvs[j].step(acts[j][i % 8])
             if wenvs[0]._fused:
                 # per observation element: float64 mean + var read and written (32 B) + the normalised float32 out (4 B); the raw row never
                 # reaches HBM.  Per agent: the reward statistics (32 B) + normalised reward (4 B).  DESIGN.md 4e
@@ -743,7 +794,15 @@ def bench_other(args, workload, K, W, rank, world, dev, cpu_budget, streams=None
             (wenvs[j] if workload == "waterworld_std" else e).reset()
     torch.cuda.synchronize()
     age()
-    dt, kernel_ms, region_ms = Timer(world, dev, hip_streams).run(step, K, W)
+    dt, kernel_ms, region_ms = Timer(world, dev, hip_streams).run(step, K, W, repeats=n_regions(args))
+    if dump is not None:   # what Batched*.step() (StandardizedEnv.step()) hands back after the last timed step
+        if workload == "waterworld_std":
+            named = {"observations": [r[0] for r in last], "rewards": [r[1] for r in last]}
+        elif workload.startswith("multiwalker"):
+            named = {"observations": [e._obs for e in envs], "rewards": [e._rew for e in envs], "dones": [done_rows[K - 1]]}
+        else:
+            named = {"observations": [e._obs for e in envs], "rewards": [e._rew for e in envs], "dones": [e._done for e in envs], "info": [e._info for e in envs]}
+        dump.update(take_outputs({k: (torch.cat(v), 0) for k, v in named.items()}))
     n_ended = float((done_rows[:K] != 0).sum().item()) / N if workload.startswith("multiwalker") else None
     api = None
     if (bool(cpu_budget) if api_leg is None else api_leg) and workload in ("waterworld", "hostage") and not collective_on(world):
@@ -762,7 +821,7 @@ def bench_other(args, workload, K, W, rank, world, dev, cpu_budget, streams=None
         del sh
     del envs
     one = None
-    if reference_pass and S > 1 and world == 1:
+    if reference_pass and args.full and S > 1 and world == 1:
         one = bench_other(args, workload, K, min(W, 20), rank, world, dev, 0, streams=1, reference_pass=False, api_leg=bool(cpu_budget))
     if rank != 0:
         return None
@@ -817,7 +876,7 @@ def compact_roofline(r, side=False):
 def compact_line(out):
     """The ONE JSON line rank 0 prints: the contract's fields, short enough (a few KB) that a log tail holds every workload.  What the
     fields mean is in DESIGN.md "Measurement"; the long form of this record (every key of the rounds before, prose included) goes to
-    --full-record / gpurun_out/bench_full.json."""
+    --full-record PATH (--long-record prints it instead)."""
     line = {k: _r(out[k]) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype")}
     line["data"] = "synthetic"
     c = out["config"]
@@ -893,9 +952,13 @@ def main():
                     help="N > 1: who receives the compact trajectory (actions, rewards, dones) of the timed region, exchanged in chunks that overlap with the "
                          "stepping -- root = rank 0 only (default: north_star's gather at episode end, the sampler workers returning their paths to one learner), "
                          "all = every rank (all-gather: a learner data-parallel over the same ranks), stats = nobody (per-episode returns only)")
-    ap.add_argument("--full", action="store_true", help="print the long record (every key, prose included) instead of the compact line")
-    ap.add_argument("--full-record", default="", help="also write the long record to this file (default: gpurun_out/bench_full.json when that directory exists)")
-    ap.add_argument("--no-workloads", action="store_true", help="headline only: do not time the other BASELINE configs")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: REPEATS timed regions (median reported), the one-launch-per-step "
+                                                         "and Python-API passes, cpu_baseline, and at N = 1 the other BASELINE configs under `workloads`")
+    ap.add_argument("--long-record", action="store_true", help="print the long record (every key, prose included) instead of the compact line")
+    ap.add_argument("--full-record", default="", help="also write the long record to this file")
+    ap.add_argument("--no-workloads", action="store_true", help="--full without the other BASELINE configs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step returned to DIR/<name>.npy (float32 / float64; "
+                                                                      "a fixed seeded sample of env instances when the whole passes 48 MB)")
     ap.add_argument("--horizon", type=int, default=500, help="max_path_length (runners/__init__.py:88)")
     ap.add_argument("--prep", type=int, default=2000, help="Pursuit: untimed steps before the warm-up that bring the stale-zero masks of the observation "
                                                             "rows to their equilibrium (a rollout's steady state, like the spread episode ages)")
@@ -924,18 +987,21 @@ def main():
         ensure_group(dev)   # the launcher's group, or (MADRL_BENCH_FORCE_COLLECTIVE with one rank) a one-rank group with its own rendezvous
 
     K, W = args.steps, args.warmup
-    cpu = (not args.no_cpu_baseline) and not collective_on(world)   # the CPU baselines are reported with the plain 1-GPU line only
+    cpu = args.full and (not args.no_cpu_baseline) and not collective_on(world)   # the CPU baselines are reported with the 1-GPU --full line only
     scale = float(os.environ.get("MADRL_BENCH_CPU_BUDGET", "1"))   # tests shorten the CPU samples
     head_cpu, side_cpu = (10.0 * scale, 3.0 * scale) if cpu else (0, 0)
+    dump = {} if args.dump_outputs else None
     if args.workload == "pursuit_rollout":
-        out = bench_rollout(args, K, W, rank, world, dev, head_cpu)
+        out = bench_rollout(args, K, W, rank, world, dev, head_cpu, dump=dump)
     elif args.workload.startswith("pursuit"):
-        out = bench_pursuit(args, args.workload, K, W, rank, world, dev, head_cpu)
+        out = bench_pursuit(args, args.workload, K, W, rank, world, dev, head_cpu, dump=dump)
     else:
-        out = bench_other(args, args.workload, K, W, rank, world, dev, head_cpu)
+        out = bench_other(args, args.workload, K, W, rank, world, dev, head_cpu, dump=dump)
+    if dump is not None and rank == 0:
+        write_outputs(args.dump_outputs, dump)
     # The same driver run times every other BASELINE config (N = 1, default workload, default batch): bounded steps and a bounded
     # CPU sample (3 s) each
-    if args.workload == "pursuit" and not collective_on(world) and not args.no_workloads and not args.envs:
+    if args.full and args.workload == "pursuit" and not collective_on(world) and not args.no_workloads and not args.envs:
         wl = {}
         # (their own step counts, whatever --steps says: the contract's K is the headline's; a 20-step region of a two-stream pipeline is a third
         # fill and drain -- Waterworld reads 51 us per step at K = 20 and 42 at K = 200)
@@ -963,14 +1029,13 @@ def main():
             wl["pursuit_collective"] = {"error": repr(e)}
         out["workloads"] = wl
     if rank == 0:
-        full_path = args.full_record or (os.path.join(ROOT, "gpurun_out", "bench_full.json") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else None)
-        if full_path:
+        if args.full_record:
             try:
-                with open(full_path, "w") as f:
+                with open(args.full_record, "w") as f:
                     json.dump(out, f, indent=1)
             except OSError:
                 pass
-        json_out.write(json.dumps(out if args.full else compact_line(out), separators=(",", ":")) + "\n")
+        json_out.write(json.dumps(out if args.long_record else compact_line(out), separators=(",", ":")) + "\n")
         json_out.flush()
     if collective_on(world):
         import torch.distributed as dist

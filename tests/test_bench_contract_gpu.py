@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -34,7 +35,7 @@ def test_two_ranks_gather_path():
     env = dict(os.environ, MADRL_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "70", "--warmup", "5", "--envs", "2048",
-                        "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=400, env=env)
+                        "--no-cpu-baseline", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=400, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     j = _last_json(r.stdout)
     assert j["n_gpus"] == 2 and j["steps"] == 70 and j["config"]["parallelism"] == "env-sharded x2" and "cpu_baseline" not in j
@@ -60,22 +61,55 @@ def test_one_rank_takes_the_rccl_path():
     (two ranks on one device are refused by RCCL, so the two-rank tests above run over gloo)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "MADRL_BENCH_BACKEND")}
     env.update(MADRL_BENCH_FORCE_COLLECTIVE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, "bench.py", "--envs", "8192", "--steps", "120", "--warmup", "5", "--prep", "50"], cwd=ROOT,
+    r = subprocess.run([sys.executable, "bench.py", "--envs", "8192", "--steps", "120", "--warmup", "5", "--prep", "50", "--full"], cwd=ROOT,
                        capture_output=True, text=True, timeout=400, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     j = _last_json(r.stdout)
     assert KEYS <= set(j) and j["n_gpus"] == 1 and j["steps"] == 120 and j["config"]["rccl_ranks"] == 1
     assert j["config"]["collective_backend"] == "nccl" and j["config"]["trajectory_gather_in_timed_region"] is True
-    assert j["value"] > 1e7 and "workloads" not in j and "cpu_baseline" not in j
+    assert j["value"] > 1e7 and "workloads" not in j and "cpu_baseline" not in j   # (--full: the collective path leaves them out itself)
+    assert len(j["config"]["region_ms_per_step"]) == 3
 
 
-def test_default_batch_line_carries_every_baseline_config():
-    """the default invocation (BASELINE batch sizes) times Waterworld, MultiWalker and the configs[4] shard in the same run and
-    reports them under `workloads`; every launch of the headline carries fused resets (steady-state episode ages)"""
+def test_plain_line_times_exactly_k_steps_and_dumps_the_same_outputs(tmp_path):
+    """a plain run (no --full) times ONE region of exactly --steps steps and nothing besides the headline; --dump-outputs writes what
+    the last timed step returned (float32 / float64, at most 64 MB), the same arrays from run to run -- and other arrays when one more
+    step is timed (so they are the last TIMED step's, not a warm-up or prep step's)"""
+    dumps = []
+    for run, steps in enumerate((40, 40, 41)):
+        d = tmp_path / ("out%d" % run)
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "5", "--dump-outputs", str(d)], cwd=ROOT,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _last_json(r.stdout)
+        assert KEYS <= set(j) and j["steps"] == steps and j["warmup"] == 5 and j["config"]["envs_per_gpu"] == 65536
+        assert len(j["config"]["region_ms_per_step"]) == 1 and abs(j["config"]["region_ms_per_step"][0] - j["ms_per_step"]) < 1e-3 * j["ms_per_step"]
+        assert not {"workloads", "cpu_baseline", "python_api_ms_per_step"} & set(j) and "one_launch_ms" not in j["roofline"]
+        files = sorted(os.listdir(str(d)))
+        assert {"observations.npy", "rewards.npy", "dones.npy", "removed.npy"} <= set(files), files
+        arrays = {f: np.load(str(d / f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["rewards.npy"].shape[1:] == (8,) and arrays["observations.npy"].shape[0] == arrays["rewards.npy"].shape[0]
+        # 65 536 envs of observations pass the byte cap: a sample of env instances, named by env_index (sorted, no repeats, in range)
+        idx = arrays["env_index.npy"]
+        assert idx.shape == (arrays["rewards.npy"].shape[0],) and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 65536
+        # a real step of a steady rollout: rewards are not all zero, and with episode ages spread over the horizon some envs of the sample
+        # ran their fused reset in this very step (done bit set)
+        assert np.any(arrays["rewards.npy"] != 0) and np.any(arrays["dones.npy"] != 0) and np.any(arrays["observations.npy"] != 0)
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+    assert np.array_equal(dumps[0]["env_index.npy"], dumps[2]["env_index.npy"])
+    assert not np.array_equal(dumps[0]["observations.npy"], dumps[2]["observations.npy"])
+    assert not np.array_equal(dumps[0]["dones.npy"], dumps[2]["dones.npy"])   # another share of the envs reaches the horizon each step
+
+
+def test_default_batch_line_carries_every_baseline_config(tmp_path):
+    """the default invocation with --full (BASELINE batch sizes) times Waterworld, MultiWalker and the configs[4] shard in the same run
+    and reports them under `workloads`; every launch of the headline carries fused resets (steady-state episode ages)"""
     env = dict(os.environ, MADRL_BENCH_CPU_BUDGET="0.5")   # every workload still runs its CPU sample, just a short one
-    full = os.path.join(ROOT, "gpurun_out", "bench_full_test.json")
-    os.makedirs(os.path.dirname(full), exist_ok=True)
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "8", "--warmup", "2", "--full-record", full], cwd=ROOT, env=env,
+    full = str(tmp_path / "bench_full_test.json")
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "8", "--warmup", "2", "--full", "--full-record", full], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][0]
