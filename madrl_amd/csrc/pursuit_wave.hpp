@@ -216,24 +216,28 @@ __device__ __forceinline__ void static_for(F &&f) {
         static_for<I + 1, N>(f);
     }
 }
+// One observation slot: the four elements under their own lane masks as plain (L2-merged) dword stores, then the float4 under its
+// mask as one non-temporal store.  Each mask is the result of one v_cmp (inactive lanes compare to 0, so a mask never enables a lane
+// that exec had off) and goes into exec with one s_mov: 7 scalar instructions per slot, no mask algebra on the scalar unit.
 template <int OFF>
-__device__ __forceinline__ void store4_nt_masked(const void *base, uint32_t voff, v4f_t val, uint64_t mask) {
-    uint64_t sv;
-    asm volatile("s_mov_b64 %0, exec\n\ts_and_b64 exec, exec, %1\n\tglobal_store_dwordx4 %2, %3, %4 offset:%5 nt\n\ts_mov_b64 exec, %0\n\ts_nop 0"
-                 : "=&s"(sv) : "s"(mask), "v"(voff), "v"(val), "s"(base), "n"(OFF) : "scc");  // s_and_b64 writes SCC
-}
-// the four elements of one float4 slot, each under its own lane mask, as plain (L2-merged) dword stores
-template <int OFF>
-__device__ __forceinline__ void store1x4_masked(const void *base, uint32_t voff, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3,
-                                                uint64_t m0, uint64_t m1, uint64_t m2, uint64_t m3) {
+__device__ __forceinline__ void store_slot_masked(const void *base, uint32_t voff, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3,
+                                                  v4f_t val, uint64_t m0, uint64_t m1, uint64_t m2, uint64_t m3, uint64_t m_nt) {
     uint64_t sv;
     asm volatile("s_mov_b64 %0, exec\n\t"
-                 "s_and_b64 exec, %0, %1\n\tglobal_store_dword %5, %6, %10 offset:%11\n\t"
-                 "s_and_b64 exec, %0, %2\n\tglobal_store_dword %5, %7, %10 offset:%11+4\n\t"
-                 "s_and_b64 exec, %0, %3\n\tglobal_store_dword %5, %8, %10 offset:%11+8\n\t"
-                 "s_and_b64 exec, %0, %4\n\tglobal_store_dword %5, %9, %10 offset:%11+12\n\t"
-                 "s_mov_b64 exec, %0"
-                 : "=&s"(sv) : "s"(m0), "s"(m1), "s"(m2), "s"(m3), "v"(voff), "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(base), "n"(OFF) : "scc");
+                 "s_mov_b64 exec, %1\n\tglobal_store_dword %6, %7, %12 offset:%13\n\t"
+                 "s_mov_b64 exec, %2\n\tglobal_store_dword %6, %8, %12 offset:%13+4\n\t"
+                 "s_mov_b64 exec, %3\n\tglobal_store_dword %6, %9, %12 offset:%13+8\n\t"
+                 "s_mov_b64 exec, %4\n\tglobal_store_dword %6, %10, %12 offset:%13+12\n\t"
+                 "s_mov_b64 exec, %5\n\tglobal_store_dwordx4 %6, %11, %12 offset:%13 nt\n\t"
+                 "s_mov_b64 exec, %0\n\ts_nop 0"
+                 : "=&s"(sv) : "s"(m0), "s"(m1), "s"(m2), "s"(m3), "s"(m_nt), "v"(voff), "v"(v0), "v"(v1), "v"(v2), "v"(v3), "v"(val),
+                   "s"(base), "n"(OFF));
+}
+// OR of a lane value over its aligned group of four lanes (a DPP quad): two quad_perm moves, no scalar instruction
+__device__ __forceinline__ uint32_t quad_or(uint32_t v) {
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);  // quad_perm [1,0,3,2]
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);  // quad_perm [2,3,0,1]
+    return v;
 }
 
 // Record prefetch with an exact wait (step kernel).  vmcnt counts loads and stores alike and retires them in issue order, and the
@@ -271,7 +275,7 @@ __device__ __forceinline__ void put_zero_from(uint32_t &w) {
 // Profiling aid (scripts/variants.sh builds one library per value, never the shipped one):
 //   1 no observation stores   2 store stale cells too (all float4 full, nt)   4 no Philox
 //   8 no observation pass at all   16 no record / reward stores
-//   64 no record prefetch (timing only, wrong results)
+//   64 no record prefetch (timing only, wrong results)   128 20 dependent SALU more per observation slot (results unchanged)
 #ifndef MADRL_ABLATE
 #define MADRL_ABLATE 0
 #endif
@@ -686,6 +690,10 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
 #if MADRL_ABLATE & 2
                         clean = true;
 #endif
+                        // The lane's part of the slot as one integer, so that every store mask below is ONE vector compare (a lane mask
+                        // built from two compares would be an s_and_b64 on the scalar unit, which all four SIMDs of a CU share):
+                        //   0 = one float4 (clean), 1 .. 0x01010101 = dword stores of the inside cells (dirty), 0x80000000 = nothing (past the row)
+                        const uint32_t st = valid ? (clean ? 0u : dirty) : 0x80000000u;
 #if MADRL_ABLATE & 32
                         // what a scheme that REMEMBERS small stale values (two bits per cell: 0, 0.1, 0.2, other) and rebuilds them would add to
                         // this pass: about twenty vector instructions per slot (second byte of the four values, two flag planes, byte-to-float
@@ -701,32 +709,42 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                             acc = burn;   // (an even number of XORs with the same value: unchanged)
                         }
 #endif
-                        // An outside cell with a non-zero stale value: leave it alone (Q2), store the inside cells one by one.  Plain
-                        // (L2-cached) stores: partial lines must merge in L2 -- nontemporal partial writes cost a read-modify-write
-                        // at the memory side (3x slower).  They are issued BEFORE the non-temporal store of the slot's other lanes: the
-                        // line is then in L2 when the streaming store arrives and leaves as one write (the other order: 175 us, not 77).
+#if MADRL_ABLATE & 128
+                        // the price of one scalar instruction per env: 20 dependent SALU per slot (100 per env at NS = 5) on a dummy SGPR
+                        // that feeds nothing observable ("what a SALU costs")
+                        {
+                            uint32_t sburn = fresh_s(0u);
+                            asm volatile("s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n"
+                                         "s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n"
+                                         "s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n"
+                                         "s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1"
+                                         : "+s"(sburn) : : "scc");
+                        }
+#endif
                         const void *sb = orow_u + 4096 * (s / 4);
-                        const uint64_t md = __builtin_amdgcn_ballot_w64(valid && !clean);
-                        store1x4_masked<1024 * (s % 4)>(sb, voff, v0, v1, v2, v3, md & __builtin_amdgcn_ballot_w64(v0 != SENT),
-                                                        md & __builtin_amdgcn_ballot_w64(v1 != SENT), md & __builtin_amdgcn_ballot_w64(v2 != SENT),
-                                                        md & __builtin_amdgcn_ballot_w64(v3 != SENT));
+                        // dirty: element k is stored iff it is inside the map, i.e. v_k != SENT, i.e. v_k < lim (unsigned); other lanes: lim = 0.
+                        // (fresh(): kept as a value, or the compiler splits `v_k < select` back into two lane masks and an s_and_b64)
+                        const uint32_t lim = (uint32_t)fresh((st - 1u < 0x01010101u) ? (int)SENT : 0);
                         // One non-temporal float4 unless a cell must stay untouched; nothing if all four are outside and known zero.
                         // Outside cells (SENT = -1 as an integer) are written as the +0.0f they already hold.
-                        uint64_t m_nt = __builtin_amdgcn_ballot_w64(valid && clean && out4 != 0x01010101u);
                         // Whole 64-byte chunks: a slot that lies ENTIRELY outside the map and whose cells are known to hold zero normally
                         // stores nothing -- but when another slot of its aligned group of four lanes is written, it is written too (as the
                         // zeros it already holds), so that the group's 64 bytes leave the CU as one full chunk instead of a partial one the
                         // memory side has to merge.  Round 4, mask equilibrium, 65 536 envs: 80.0 -> 71.6 us per launch (groups of two:
                         // 74.0, of eight: 75.8; scripts/zmask_drift.py).  (The two-wavefront kernel, whose 32 x 32 map leaves far fewer cells outside, loses
                         // with the same rule -- 86.5 against 80.4 us per 32 768-env launch -- and does not apply it.)
-                        {
-                            constexpr uint64_t lo4 = 0x1111111111111111ull;
-                            const uint64_t grp = (m_nt | (m_nt >> 1) | (m_nt >> 2) | (m_nt >> 3)) & lo4;   // bit 4g: group g stores something
-                            m_nt |= (grp * 0xFull) & __builtin_amdgcn_ballot_w64(valid && clean && out4 == 0x01010101u);
-                        }
+                        // The group of four lanes is a DPP quad: a clean lane stores iff a clean lane of its quad has a cell inside the map.
+                        const uint32_t grp = quad_or(st == 0u ? (out4 ^ 0x01010101u) : 0u);
+                        const uint32_t nt = (uint32_t)fresh(st == 0u ? (int)grp : 0);
                         const v4f_t val = {__uint_as_float((uint32_t)max((int)v0, 0)), __uint_as_float((uint32_t)max((int)v1, 0)),
                                            __uint_as_float((uint32_t)max((int)v2, 0)), __uint_as_float((uint32_t)max((int)v3, 0))};
-                        store4_nt_masked<1024 * (s % 4)>(sb, voff, val, m_nt);
+                        // An outside cell with a non-zero stale value: leave it alone (Q2), store the inside cells one by one.  Plain
+                        // (L2-cached) stores: partial lines must merge in L2 -- nontemporal partial writes cost a read-modify-write
+                        // at the memory side (3x slower).  They are issued BEFORE the non-temporal store of the slot's other lanes: the
+                        // line is then in L2 when the streaming store arrives and leaves as one write (the other order: 175 us, not 77).
+                        store_slot_masked<1024 * (s % 4)>(sb, voff, v0, v1, v2, v3, val, __builtin_amdgcn_ballot_w64(v0 < lim),
+                                                          __builtin_amdgcn_ballot_w64(v1 < lim), __builtin_amdgcn_ballot_w64(v2 < lim),
+                                                          __builtin_amdgcn_ballot_w64(v3 < lim), __builtin_amdgcn_ballot_w64(nt != 0u));
                     });
                     zm = acc;
                 }
