@@ -2,9 +2,12 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <new>
+#include <vector>
 
 #include "../../include/madrl_hip.h"
 
@@ -126,6 +129,148 @@ __device__ __forceinline__ EnvWalk env_walk(int64_t n_envs) {
     }
     return w;
 }
+
+// ---------------------------------------------------------------- wavefront helpers of the env kernels
+// Launch parameters that a phase only reads now and then are not held in SGPRs across the env loop: the loop's scalar live set
+// (broadcast masks, reach sets, counters) is already at the SGPR limit, and what does not fit is parked in VGPR lanes -- one
+// v_readlane_b32 (a VALU issue slot) per value and use.  The kernel reads them from its kernel-argument segment (scalar loads) where
+// they are needed, through a view A = struct {Dev d; IO io;} of its two by-value arguments.
+template <class A>
+__device__ __forceinline__ const __attribute__((address_space(4))) A *kernargs() {
+    auto p = (const __attribute__((address_space(4))) A *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));  // a fresh pointer at every call: the loads cannot be merged with the ones at kernel entry or hoisted
+    return p;
+}
+
+// A wave-uniform pointer pinned to an SGPR pair at this point of the program.  Per-lane accesses written as
+// uniform_ptr(base + env * stride)[lane] then select the "SGPR base + 32-bit VGPR offset" addressing form; without the pin the
+// compiler reassociates to (base + lane * 4) + env * stride, keeps one 64-bit VGPR pair per array live across the env loop and,
+// at 96 VGPRs, spills them -- and a scratch reload in the loop waits (in-order vmcnt) for the previous env's observation stores.
+template <class T>
+__device__ __forceinline__ __attribute__((address_space(1))) T *uniform_ptr(T *p) {
+    const uint64_t v = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return (__attribute__((address_space(1))) T *)(((uint64_t)hi << 32) | lo);  // global address space: global_*, not flat_*, instructions
+}
+
+// Register-pressure control.  The compiler hoists every loop-invariant lane compare (lane < P, lane == k, ...)
+// out of the env loop as an SGPR-pair mask and, with ~100 uniform values already live there, spills them to
+// VGPR lanes: each use then costs two v_readlane_b32 (VALU issue slots, the resource these kernels are bound by).
+// fresh(lane) hides the invariance, so a predicate is one v_cmp at its use site and dies there.
+__device__ __forceinline__ int fresh(int v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+__device__ __forceinline__ uint32_t fresh_s(uint32_t v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+
+// The same for the SPECIALISED shapes, one instruction cheaper: fresh() costs a v_mov before its v_cmp; here the compare is written
+// out (volatile: it stays where it is used and its mask dies there), its right-hand side an inline constant of the shape (<= 64), and the
+// wave-uniform mask becomes the lane predicate without an instruction (inverse ballot).
+__device__ __forceinline__ bool lane_lt_imm(int lane, int n) {   // lane < n; n must fold to a constant in -16 .. 64
+    unsigned long long m;
+    asm volatile("v_cmp_gt_i32_e64 %0, %1, %2" : "=s"(m) : "i"(n), "v"(lane));
+    return __builtin_amdgcn_inverse_ballot_w64(m);
+}
+__device__ __forceinline__ bool lane_eq_imm(int lane, int n) {
+    unsigned long long m;
+    asm volatile("v_cmp_eq_i32_e64 %0, %1, %2" : "=s"(m) : "i"(n), "v"(lane));
+    return __builtin_amdgcn_inverse_ballot_w64(m);
+}
+
+// Wave-local synchronisation.  A workgroup (or an env's group of lanes) is one wavefront, its DS (LDS) instructions are
+// executed in issue order, so cross-lane LDS hand-offs only need the COMPILER to keep the order; unlike __syncthreads()
+// this emits no s_waitcnt vmcnt(0), i.e. the wave never waits for its observation stores to reach HBM.
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// uniform float in [0,1) from the top 24 bits
+__device__ __forceinline__ float u24(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
+
+__device__ __forceinline__ float dist2d(float ax, float ay, float bx, float by) {
+    const float dx = ax - bx, dy = ay - by;
+    return sqrtf(dx * dx + dy * dy);  // scipy cdist 'euclidean'
+}
+
+// dist2d(a, b) <= thr, with sq = sq_threshold(thr) (host side): same truth value, no square root
+__device__ __forceinline__ bool dist2_le(float ax, float ay, float bx, float by, float sq) {
+    const float dx = ax - bx, dy = ay - by;
+    return dx * dx + dy * dy <= sq;
+}
 #endif
+
+// ---------------------------------------------------------------- host side of the env handles
+// The global env index (env_id_base + env) is a 32-bit word of the RNG counter.
+inline int check_env_ids(int64_t n_envs, int64_t env_id_base) {
+    if (n_envs + env_id_base > 0xFFFFFFFFll) return fail(MADRL_EINVAL, "global env index must fit 32 bits");
+    return MADRL_OK;
+}
+
+// The largest float32 x with sqrtf(x) <= thr (thr >= 0 finite), so that "distance <= thr" is the single compare
+// "dx*dx + dy*dy <= x" with the same truth value for every input (sqrtf is monotonic and correctly rounded); the correctly
+// rounded sqrtf itself is a 20-instruction sequence.
+inline float sq_threshold(float thr) {
+    float x = thr * thr;
+    while (x > 0.0f && sqrtf(x) > thr) x = nextafterf(x, 0.0f);
+    for (;;) {
+        const float up = nextafterf(x, INFINITY);
+        if (!(sqrtf(up) <= thr)) break;
+        x = up;
+    }
+    return x;
+}
+
+// The launch grid of the particle worlds (waterworld.hip, hostage.hip): persistent one-wavefront workgroups, max_blocks of them
+// (madrl_*_set_launch; 0 = 256 * 64), never more than one per env.
+inline dim3 particle_grid(int64_t max_blocks, int64_t n_envs) {
+    int64_t blocks = max_blocks > 0 ? max_blocks : 256 * 64;
+    if (blocks > n_envs) blocks = n_envs;
+    return dim3((unsigned)blocks);
+}
+
+// madrl_waterworld_create / madrl_hostage_create after the world's own validation of cfg: H is the handle (cfg, dev, device,
+// max_blocks, lds_bytes, tables), layout() and lds_bytes() the world's functions of its configuration.
+template <class H, class C, class Dev>
+int particle_create(const C *cfg, const double *sensors_host, int64_t n_envs, int32_t device, void *state_dev, H **out,
+                    void (*layout)(const C *, Dev *), size_t (*lds_bytes)(const Dev &)) {
+    if (!sensors_host || !state_dev || !out || n_envs < 1) return fail(MADRL_EINVAL, "create: NULL argument or n_envs < 1");
+    if (n_envs >= 0x7FF00000ll)  // the kernels index envs with 32-bit integers (index + workgroup count must stay below 2^31)
+        return fail(MADRL_EINVAL, "n_envs=%lld is too large for one handle (limit 2146435071); shard the batch", (long long)n_envs);
+    const int rc = check_env_ids(n_envs, cfg->env_id_base);
+    if (rc) return rc;
+    MADRL_HIP_TRY(hipSetDevice(device));
+    H *h = new (std::nothrow) H();
+    if (!h) return fail(MADRL_ENOMEM, "out of host memory");
+    h->cfg = *cfg;
+    h->device = device;
+    layout(cfg, &h->dev);
+    h->dev.n_envs = n_envs;
+    h->dev.state = (float *)state_dev;
+    h->lds_bytes = lds_bytes(h->dev);
+    h->max_blocks = 0;
+    if (h->lds_bytes > 64 * 1024) {
+        const size_t need = h->lds_bytes;
+        delete h;
+        return fail(MADRL_EINVAL, "configuration needs %zu B of LDS (> 64 KiB)", need);
+    }
+    std::vector<float> sens(2 * (size_t)cfg->n_sensors);
+    for (size_t k = 0; k < sens.size(); ++k) sens[k] = (float)sensors_host[k];  // float64 cos/sin rounded once
+    hipError_t e = hipMalloc(&h->tables, sens.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(h->tables, sens.data(), sens.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (h->tables) (void)hipFree(h->tables);
+        delete h;
+        return fail(MADRL_EHIP, "sensor table upload failed: %s", hipGetErrorString(e));
+    }
+    h->dev.sensors = (const float *)h->tables;
+    *out = h;
+    return MADRL_OK;
+}
 
 }  // namespace madrl

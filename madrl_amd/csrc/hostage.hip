@@ -15,9 +15,7 @@
 #include "common.hpp"
 
 #include <math.h>
-#include <new>
 #include <string.h>
-#include <vector>
 
 // Profiling aid (scripts/variants.sh builds one library per value, never the shipped one):
 //   1 no observation store   2 non-temporal observation store   4 no record store   8 no reward / done / info stores
@@ -44,8 +42,7 @@ struct HwDev {
     float radius, r_ho, bad_speed, sensor_range, action_scale, gate_lo;
     float save_reward, hit_reward, encounter_reward, not_saved_reward, bomb_reward, bomb_radius, key_radius, control_penalty;
     float key_x, key_y;
-    // sq_*: largest float32 x with sqrtf(x) <= threshold ("distance <= threshold" as one compare of the squared distance, same truth
-    // value for every input; waterworld.hip): rescuer-hostage / rescuer-criminal contact, bomb and key radii
+    // sq_*: sq_threshold() (common.hpp) of the distance thresholds: rescuer-hostage / rescuer-criminal contact, bomb and key radii
     float sq_hit_ho, sq_hit_cr, sq_bomb, sq_key;
     int64_t n_envs;
     const float *sensors;  // [K][2]
@@ -62,46 +59,13 @@ struct HwIO {
     int32_t *info;          // [N][2]  ho_saved, cr_encs
 };
 
-// Same register discipline as waterworld.hip: launch parameters are read from the kernel-argument segment (scalar loads) where a
-// phase needs them instead of being held in SGPRs across the env loop (what does not fit in SGPRs is parked in VGPR lanes at two
-// VALU issue slots per value and use); per-lane global accesses go through an SGPR base + 32-bit VGPR offset; a lane predicate
-// is recomputed at its use (fresh) instead of being hoisted out of the env loop as an SGPR pair.
+// Same register discipline as waterworld.hip (helpers in common.hpp): launch parameters are read from the kernel-argument segment
+// where a phase needs them (kernargs), per-lane global accesses go through an SGPR base + 32-bit VGPR offset (uniform_ptr), a lane
+// predicate is recomputed at its use (fresh) instead of being hoisted out of the env loop as an SGPR pair.
 struct HwKArgs {
     HwDev d;
     HwIO io;
 };
-typedef const __attribute__((address_space(4))) HwKArgs *HwKArgsPtr;
-__device__ __forceinline__ HwKArgsPtr hw_args() {
-    HwKArgsPtr p = (HwKArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return p;
-}
-template <class T>
-__device__ __forceinline__ __attribute__((address_space(1))) T *uniform_ptr(T *p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-    return (__attribute__((address_space(1))) T *)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ int fresh(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ float u24(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
-__device__ __forceinline__ float dist2d(float ax, float ay, float bx, float by) {
-    const float dx = ax - bx, dy = ay - by;
-    return sqrtf(dx * dx + dy * dy);  // scipy cdist 'euclidean'
-}
-__device__ __forceinline__ bool dist2_le(float ax, float ay, float bx, float by, float sq) {  // dist2d(a, b) <= thr with sq = sq_threshold(thr)
-    const float dx = ax - bx, dy = ay - by;
-    return dx * dx + dy * dy <= sq;
-}
 __device__ __forceinline__ float clipf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ float bcast(float v, int src_lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src_lane)); }
 
@@ -118,8 +82,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TNr > 0 ? MA
     float *const smem = TNr > 0 ? smem_static : smem_dyn;
     const int lane = threadIdx.x;
     const uint32_t ulane = threadIdx.x;
-#define DA (hw_args()->d)
-#define IOA (hw_args()->io)
+#define DA (kernargs<HwKArgs>()->d)
+#define IOA (kernargs<HwKArgs>()->io)
     const int Nr = TNr > 0 ? TNr : d.Nr, Nh = TNr > 0 ? TNh : d.Nh, Nc = TNr > 0 ? TNc : d.Nc, K = TNr > 0 ? TK : d.K;
     const int NP = Nr + Nh + Nc, D = TD > 0 ? TD : d.D;
     float *S = smem;                                   // packed record
@@ -589,18 +553,6 @@ int hw_validate(const madrl_hostage_config *c) {
 
 int hw_obs_dim_of(const madrl_hostage_config *c) { return c->n_sensors * 5 + 5 + (c->addid ? 1 : 0); }  // CircAgent.__init__ :19-23
 
-// largest float32 x with sqrtf(x) <= thr (thr >= 0 finite); see HwDev::sq_*
-float hw_sq_threshold(float thr) {
-    float x = thr * thr;
-    while (x > 0.0f && sqrtf(x) > thr) x = nextafterf(x, 0.0f);
-    for (;;) {
-        const float up = nextafterf(x, INFINITY);
-        if (!(sqrtf(up) <= thr)) break;
-        x = up;
-    }
-    return x;
-}
-
 void hw_layout(const madrl_hostage_config *c, HwDev *d) {
     memset(d, 0, sizeof(*d));
     d->Nr = c->n_good; d->Nh = c->n_hostages; d->Nc = c->n_bad; d->NP = d->Nr + d->Nh + d->Nc;
@@ -616,8 +568,8 @@ void hw_layout(const madrl_hostage_config *c, HwDev *d) {
     d->key_radius = (float)c->key_radius; d->control_penalty = (float)c->control_penalty;
     d->key_x = (float)c->key_loc[0]; d->key_y = (float)c->key_loc[1];
     // the float32 sums the kernel used to form before comparing
-    d->sq_hit_ho = hw_sq_threshold(d->radius + d->r_ho); d->sq_hit_cr = hw_sq_threshold(d->radius + d->radius);
-    d->sq_bomb = hw_sq_threshold(d->radius + d->bomb_radius); d->sq_key = hw_sq_threshold(d->radius + d->key_radius);
+    d->sq_hit_ho = sq_threshold(d->radius + d->r_ho); d->sq_hit_cr = sq_threshold(d->radius + d->radius);
+    d->sq_bomb = sq_threshold(d->radius + d->bomb_radius); d->sq_key = sq_threshold(d->radius + d->key_radius);
 }
 
 size_t hw_lds_bytes(const HwDev &d) {
@@ -627,17 +579,16 @@ size_t hw_lds_bytes(const HwDev &d) {
 }
 
 int hw_launch(const madrl_hostage *h, const HwIO &io, int mode, void *stream) {
-    int64_t blocks = h->max_blocks > 0 ? h->max_blocks : 256 * 64;
-    if (blocks > h->dev.n_envs) blocks = h->dev.n_envs;
     hipStream_t s = (hipStream_t)stream;
     const HwDev &d = h->dev;
+    const dim3 g = particle_grid(h->max_blocks, d.n_envs);
     const bool ex = d.Nr == 3 && d.Nh == 10 && d.Nc == 5 && d.K == 30 && d.D == 156;  // the module's own configuration (hostage.py:483), 30 sensors, agent id
     if (mode == 0) {
-        if (ex) hipLaunchKernelGGL((hostage_kernel<0, 3, 10, 5, 30, 156>), dim3((unsigned)blocks), dim3(64), 0, s, h->dev, io);
-        else hipLaunchKernelGGL((hostage_kernel<0, 0, 0, 0, 0>), dim3((unsigned)blocks), dim3(64), h->lds_bytes, s, h->dev, io);
+        if (ex) hipLaunchKernelGGL((hostage_kernel<0, 3, 10, 5, 30, 156>), g, dim3(64), 0, s, h->dev, io);
+        else hipLaunchKernelGGL((hostage_kernel<0, 0, 0, 0, 0>), g, dim3(64), h->lds_bytes, s, h->dev, io);
     } else {
-        if (ex) hipLaunchKernelGGL((hostage_kernel<1, 3, 10, 5, 30, 156>), dim3((unsigned)blocks), dim3(64), 0, s, h->dev, io);
-        else hipLaunchKernelGGL((hostage_kernel<1, 0, 0, 0, 0>), dim3((unsigned)blocks), dim3(64), h->lds_bytes, s, h->dev, io);
+        if (ex) hipLaunchKernelGGL((hostage_kernel<1, 3, 10, 5, 30, 156>), g, dim3(64), 0, s, h->dev, io);
+        else hipLaunchKernelGGL((hostage_kernel<1, 0, 0, 0, 0>), g, dim3(64), h->lds_bytes, s, h->dev, io);
     }
     MADRL_HIP_TRY(hipGetLastError());
     return MADRL_OK;
@@ -693,37 +644,7 @@ int madrl_hostage_create(const madrl_hostage_config *cfg, const double *sensors_
                          madrl_hostage **out) {
     int rc = hw_validate(cfg);
     if (rc) return rc;
-    if (!sensors_host || !state_dev || !out || n_envs < 1) return fail(MADRL_EINVAL, "create: NULL argument or n_envs < 1");
-    if (n_envs >= 0x7FF00000ll)  // the kernel indexes envs with 32-bit integers (index + workgroup count must stay below 2^31)
-        return fail(MADRL_EINVAL, "n_envs=%lld is too large for one handle (limit 2146435071); shard the batch", (long long)n_envs);
-    if (n_envs + cfg->env_id_base > 0xFFFFFFFFll) return fail(MADRL_EINVAL, "global env index must fit 32 bits");
-    MADRL_HIP_TRY(hipSetDevice(device));
-    madrl_hostage *h = new (std::nothrow) madrl_hostage();
-    if (!h) return fail(MADRL_ENOMEM, "out of host memory");
-    h->cfg = *cfg;
-    h->device = device;
-    hw_layout(cfg, &h->dev);
-    h->dev.n_envs = n_envs;
-    h->dev.state = (float *)state_dev;
-    h->lds_bytes = hw_lds_bytes(h->dev);
-    h->max_blocks = 0;
-    if (h->lds_bytes > 64 * 1024) {
-        const size_t need = h->lds_bytes;
-        delete h;
-        return fail(MADRL_EINVAL, "configuration needs %zu B of LDS (> 64 KiB)", need);
-    }
-    std::vector<float> sens(2 * (size_t)cfg->n_sensors);
-    for (size_t k = 0; k < sens.size(); ++k) sens[k] = (float)sensors_host[k];  // float64 cos/sin rounded once
-    hipError_t e = hipMalloc(&h->tables, sens.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->tables, sens.data(), sens.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (h->tables) (void)hipFree(h->tables);
-        delete h;
-        return fail(MADRL_EHIP, "sensor table upload failed: %s", hipGetErrorString(e));
-    }
-    h->dev.sensors = (const float *)h->tables;
-    *out = h;
-    return MADRL_OK;
+    return particle_create(cfg, sensors_host, n_envs, device, state_dev, out, hw_layout, hw_lds_bytes);
 }
 
 void madrl_hostage_destroy(madrl_hostage *h) {

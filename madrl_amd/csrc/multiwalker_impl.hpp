@@ -121,12 +121,6 @@ constexpr int SOLVE_HDR_BYTES = (int)((offsetof(mw::Scratch, m_bA) + 15) / 16 * 
 constexpr int TOI_WORK_BYTES = (int)((sizeof(mw::ToiWork) + 15) / 16 * 16);
 constexpr int TOI_LANE_BYTES = (mw::EDGE_SLOTS_HULL * 5 + 15) / 16 * 16;   // time-of-impact cache of a walker's body: 4 + 1 bytes per contact slot
 
-__device__ __forceinline__ void lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // the cooperating lanes of multiwalker_core.hpp's `Par` = one group of NL (4, 8 or 16) neighbouring lanes of the wavefront
 template <int MREG_>
 struct GroupPar {
@@ -158,7 +152,7 @@ struct GroupPar {
     __device__ __forceinline__ int solve_lane(int) const { return l; }
     __device__ __forceinline__ int lane() const { return l; }
     __device__ __forceinline__ int n() const { return NL; }
-    __device__ __forceinline__ void sync() const { lds_sync(); }
+    __device__ __forceinline__ void sync() const { wave_sync(); }
     __device__ __forceinline__ int alloc(int *counter) const { return atomicAdd(counter, 1); }
     __device__ __forceinline__ void or_bits(uint32_t *p, uint32_t v) const { atomicOr(p, v); }
     __device__ __forceinline__ void or_bits(mw::Bits32 *p, mw::Bits32 v) const { atomicOr(&p->v, v.v); }
@@ -264,7 +258,7 @@ void mw_step_kernel(const MwDev d, const MwIO io, const int mode, const int pend
         uint32_t *sd = reinterpret_cast<uint32_t *>(&S);
         for (int k = lane; k < SOLVE_HDR_BYTES / 4; k += NL) sd[k] = sched_g[k];
     }
-    lds_sync();
+    wave_sync();
     if ((PH & PH_COLLIDE) && fresh) {
         if (lane == 0) {
             if (spare) {   // the episode the live env will start next
@@ -279,7 +273,7 @@ void mw_step_kernel(const MwDev d, const MwIO io, const int mode, const int pend
                 }
             }
         }
-        lds_sync();
+        wave_sync();
     }
     if (TERRAIN) {   // read over and over by the narrow phase, the root finder, the lidar
         for (int k = lane; k < M.NT; k += NL) ty_l[k] = cold_g->ty[k];
@@ -288,13 +282,13 @@ void mw_step_kernel(const MwDev d, const MwIO io, const int mode, const int pend
     if (PH & PH_COLLIDE) {
         float *s_act = reinterpret_cast<float *>(work + SCR_HDR_BYTES - SOLVE_HDR_BYTES);
         for (int k = lane; k < 4 * mw::MAX_WALKERS; k += NL) s_act[k] = (!fresh && k < 4 * W) ? io.actions[env * 4 * W + k] : 0.0f;
-        lds_sync();
+        wave_sync();
         mw::env_apply_actions(M, Wd, Cd, par, s_act);
         mw::step_collide(M, Wd, Cd, S, pool, par);
-        lds_sync();
+        wave_sync();
     }
     // every lane copies the manifolds it owns from the pool into registers (and LDS: the bytes the collide phase's summaries were in)
-    if (PH & PH_SOLVE) { mw::step_solve(M, Wd, Cd, S, pool, reinterpret_cast<mw::Manifold *>(work), overflow_of(PH), par); lds_sync(); }
+    if (PH & PH_SOLVE) { mw::step_solve(M, Wd, Cd, S, pool, reinterpret_cast<mw::Manifold *>(work), overflow_of(PH), par); wave_sync(); }
     if constexpr (NL >= 16 && PH == PH_ALL) {   // the record found again from the lane id: nothing of the above stays live over the solver (GroupPar)
         env = par.env_again();
         rec = par.rec_again();
@@ -353,7 +347,7 @@ void mw_step_kernel(const MwDev d, const MwIO io, const int mode, const int pend
             else d.pending[env] = 0;
         }
     }
-    lds_sync();
+    wave_sync();
     if (!fresh) {
         if (lane < W) io.rew[env * W + lane] = s_rew[lane];
         if (lane == 0) io.done[env] = (uint8_t)(*s_done | (Wd.overflow ? 0x80u : 0u));   // bit 7: this episode ran out of a capacity (sticky, Hot::overflow)
@@ -372,7 +366,7 @@ void mw_step_kernel(const MwDev d, const MwIO io, const int mode, const int pend
             }
         }
     }
-    lds_sync();
+    wave_sync();
     {
         const uint32_t *src = reinterpret_cast<const uint32_t *>(&Wd);
         for (int k = lane; k < (int)(sizeof(mw::Hot) / 4); k += NL) rec[k] = src[k];
@@ -547,7 +541,8 @@ int k_create(const madrl_multiwalker_config *cfg, int64_t n_envs, int32_t device
     int rc = mw_validate(cfg);
     if (rc) return rc;
     if (!state_dev || !out || n_envs < 1) return fail(MADRL_EINVAL, "create: NULL argument or n_envs < 1");
-    if (n_envs + cfg->env_id_base > 0xFFFFFFFFll) return fail(MADRL_EINVAL, "global env index must fit 32 bits");
+    rc = check_env_ids(n_envs, cfg->env_id_base);
+    if (rc) return rc;
     MADRL_HIP_TRY(hipSetDevice(device));
     MwHandle *h = new (std::nothrow) MwHandle();
     if (!h) return fail(MADRL_ENOMEM, "out of host memory");

@@ -917,8 +917,8 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
     if (rc) return rc;
     if (!map_pool_host || !state_dev || !out || n_envs < 1)
         return fail(MADRL_EINVAL, "create: NULL argument or n_envs < 1");
-    if (n_envs + cfg->env_id_base > 0xFFFFFFFFll)
-        return fail(MADRL_EINVAL, "global env index must fit 32 bits");
+    rc = check_env_ids(n_envs, cfg->env_id_base);
+    if (rc) return rc;
     MADRL_HIP_TRY(hipSetDevice(device));
     madrl_pursuit *h = new (std::nothrow) madrl_pursuit();
     if (!h) return fail(MADRL_ENOMEM, "out of host memory");

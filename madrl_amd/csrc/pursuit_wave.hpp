@@ -88,19 +88,14 @@ __device__ __forceinline__ double sload_f64(const double *p, int64_t index) {
     return ((const __attribute__((address_space(4))) double *)(uint64_t)p)[index];
 }
 
-// Launch parameters that only the rare paths read (episode reset, a change of map) are not kept in SGPRs across the env loop: the
-// kernel reads them from its kernel-argument segment (scalar loads) where they are needed.  The loop otherwise runs out of SGPRs
-// and the compiler parks the excess in VGPR lanes -- one v_readlane_b32 (a VALU issue slot) per use.
+// Launch parameters that only the rare paths read (episode reset, a change of map) come from the kernel-argument segment
+// (kernargs, common.hpp) instead of SGPRs held across the env loop.
 struct KArgs {
     WaveDev d;
     WaveIO io;
 };
 typedef const __attribute__((address_space(4))) KArgs *KArgsPtr;
-__device__ __forceinline__ KArgsPtr cold_args() {
-    KArgsPtr p = (KArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));  // a fresh pointer at every call: the loads cannot be merged with the ones at kernel entry or hoisted
-    return p;
-}
+__device__ __forceinline__ KArgsPtr cold_args() { return kernargs<KArgs>(); }
 
 template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
 struct Shape {
@@ -166,41 +161,6 @@ __device__ __forceinline__ double np_sum_regs(const double (&a)[P]) {
         for (int i = LIM; i < P; ++i) res += a[i];
         return res;
     }
-}
-
-// Wave-local synchronisation.  A workgroup is one wavefront, its DS (LDS) instructions are
-// executed in issue order, so cross-lane LDS hand-offs only need the COMPILER to keep the
-// order; unlike __syncthreads() this emits no s_waitcnt vmcnt(0), i.e. the wave never waits
-// for its observation stores to reach HBM.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Register-pressure control.  The compiler hoists every loop-invariant lane compare (lane < P, lane == k, ...)
-// out of the env loop as an SGPR-pair mask and, with ~100 uniform values already live there, spills them to
-// VGPR lanes: each use then costs two v_readlane_b32 (VALU issue slots, the resource this kernel is bound by).
-// fresh(lane) hides the invariance, so a predicate is one v_cmp at its use site and dies there.
-__device__ __forceinline__ int fresh(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-__device__ __forceinline__ uint32_t fresh_s(uint32_t v) {
-    asm volatile("" : "+s"(v));
-    return v;
-}
-
-// A wave-uniform pointer pinned to an SGPR pair at this point of the program.  Per-lane accesses written as
-// uniform_ptr(base + env * stride)[lane] then select the "SGPR base + 32-bit VGPR offset" addressing form; without the pin the
-// compiler reassociates to (base + lane * 4) + env * stride, keeps one 64-bit VGPR pair per array live across the env loop and,
-// at 96 VGPRs, spills them -- and a scratch reload in the loop waits (in-order vmcnt) for the previous env's observation stores.
-template <class T>
-__device__ __forceinline__ __attribute__((address_space(1))) T *uniform_ptr(T *p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-    return (__attribute__((address_space(1))) T *)(((uint64_t)hi << 32) | lo);  // global address space: global_*, not flat_*, instructions
 }
 
 // Masked global stores that are ALWAYS issued (exec narrowed inside the asm, no compiler-made skip branch around them): the

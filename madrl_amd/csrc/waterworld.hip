@@ -25,9 +25,7 @@
 #include "common.hpp"
 
 #include <math.h>
-#include <new>
 #include <string.h>
-#include <vector>
 
 namespace {
 
@@ -43,9 +41,8 @@ struct WwDev {
     float r_pu, r_ev, r_po, obst_r, ev_speed, poison_speed, sensor_range, action_scale;
     float poison_reward, food_reward, encounter_reward, control_penalty;
     float obst_x, obst_y;
-    // sq_*: the largest float32 x with sqrtf(x) <= threshold, so that "distance <= threshold" is the single compare "dx*dx + dy*dy <= sq"
-    // with the same truth value for every input (sqrtf is monotonic and correctly rounded); the correctly rounded sqrtf itself is a
-    // 20-instruction sequence.  Thresholds: obstacle rebound per particle kind (:247-270), pursuer-evader / pursuer-poison contact (:272-293).
+    // sq_*: sq_threshold() (common.hpp) of the distance thresholds: obstacle rebound per particle kind (:247-270), pursuer-evader /
+    // pursuer-poison contact (:272-293)
     float sq_obst_pu, sq_obst_ev, sq_obst_po, sq_hit_ev, sq_hit_po;
     int64_t n_envs;
     const float *sensors;  // [K][2]
@@ -76,69 +73,11 @@ struct WwIO {
     const WwStd *st;        // device copy of the fused-wrapper arguments, or NULL
 };
 
-// Launch parameters are read from the kernel-argument segment (scalar loads) at the phase that needs them instead of being held in
-// SGPRs across the whole env loop: the loop's scalar live set (broadcast masks, reach sets, counters) is already at the SGPR limit,
-// and what does not fit is parked in VGPR lanes at two VALU issue slots (v_writelane / v_readlane) per value and use.
+// The launch parameters as read from the kernel-argument segment (kernargs(), common.hpp) at the phase that needs them.
 struct WwKArgs {
     WwDev d;
     WwIO io;
 };
-typedef const __attribute__((address_space(4))) WwKArgs *WwKArgsPtr;
-__device__ __forceinline__ WwKArgsPtr ww_args() {
-    WwKArgsPtr p = (WwKArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));  // a fresh pointer at every call: loads are neither merged with earlier ones nor hoisted out of the loop
-    return p;
-}
-
-// A wave-uniform pointer pinned to an SGPR pair (global address space): per-lane accesses become "SGPR base + 32-bit VGPR offset"
-// instead of a 64-bit VGPR address pair per array kept live across the env loop.
-template <class T>
-__device__ __forceinline__ __attribute__((address_space(1))) T *uniform_ptr(T *p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-    return (__attribute__((address_space(1))) T *)(((uint64_t)hi << 32) | lo);
-}
-
-// Hides the loop-invariance of a lane predicate: fresh(lane) < n is one v_cmp where it is used and dies there, instead of an SGPR
-// pair hoisted out of the env loop (and, past the SGPR budget, parked in a VGPR lane).
-__device__ __forceinline__ int fresh(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
-// The same for the SPECIALISED shapes, one instruction cheaper (round 6): fresh() costs a v_mov before its v_cmp; here the compare is written
-// out (volatile: it stays where it is used and its mask dies there), its right-hand side an inline constant of the shape (<= 64), and the
-// wave-uniform mask becomes the lane predicate without an instruction (inverse ballot).
-__device__ __forceinline__ bool lane_lt_imm(int lane, int n) {   // lane < n; n must fold to a constant in -16 .. 64
-    unsigned long long m;
-    asm volatile("v_cmp_gt_i32_e64 %0, %1, %2" : "=s"(m) : "i"(n), "v"(lane));
-    return __builtin_amdgcn_inverse_ballot_w64(m);
-}
-__device__ __forceinline__ bool lane_eq_imm(int lane, int n) {
-    unsigned long long m;
-    asm volatile("v_cmp_eq_i32_e64 %0, %1, %2" : "=s"(m) : "i"(n), "v"(lane));
-    return __builtin_amdgcn_inverse_ballot_w64(m);
-}
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float u24(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
-
-__device__ __forceinline__ float dist2d(float ax, float ay, float bx, float by) {
-    const float dx = ax - bx, dy = ay - by;
-    return sqrtf(dx * dx + dy * dy);  // scipy cdist 'euclidean'
-}
-
-// dist2d(a, b) <= thr, with sq = sq_threshold(thr) (host side): same truth value, no square root
-__device__ __forceinline__ bool dist2_le(float ax, float ay, float bx, float by, float sq) {
-    const float dx = ax - bx, dy = ay - by;
-    return dx * dx + dy * dy <= sq;
-}
 
 // Profiling aid (scripts/variants.sh, never the shipped library): 1 no sensing loop, 2 no observation store, 4 no collisions
 #ifndef MADRL_WW_ABLATE
@@ -172,8 +111,8 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
     float *const smem = TNp > 0 ? smem_static : smem_dyn;
     const int lane = threadIdx.x;
     const uint32_t ulane = threadIdx.x;
-#define DA (ww_args()->d)
-#define IOA (ww_args()->io)
+#define DA (kernargs<WwKArgs>()->d)
+#define IOA (kernargs<WwKArgs>()->io)
     static_assert(TNp == 0 || TNp + TNe + TNpo + 1 <= 64, "lane predicates of a specialised shape compare against inline constants");
 #define LANE_LT(n) (TNp > 0 ? lane_lt_imm(lane, (n)) : (fresh(lane) < (n)))
 #define LANE_EQ(n) (TNp > 0 ? lane_eq_imm(lane, (n)) : (fresh(lane) == (n)))
@@ -753,18 +692,6 @@ int ww_obs_dim_of(const madrl_waterworld_config *c) {
     return c->n_sensors * (c->speed_features ? 7 : 4) + 2 + (c->addid ? 1 : 0);  // Archea.__init__ :18-24
 }
 
-// largest float32 x with sqrtf(x) <= thr (thr >= 0 finite); see WwDev::sq_*
-float sq_threshold(float thr) {
-    float x = thr * thr;
-    while (x > 0.0f && sqrtf(x) > thr) x = nextafterf(x, 0.0f);
-    for (;;) {
-        const float up = nextafterf(x, INFINITY);
-        if (!(sqrtf(up) <= thr)) break;
-        x = up;
-    }
-    return x;
-}
-
 void ww_layout(const madrl_waterworld_config *c, WwDev *d) {
     memset(d, 0, sizeof(*d));
     d->Np = c->n_pursuers; d->Ne = c->n_evaders; d->Npo = c->n_poison; d->NP = d->Np + d->Ne + d->Npo;
@@ -820,11 +747,9 @@ const WwSpec WW_SPECS[] = {
 #undef X
 
 int ww_launch(const madrl_waterworld *h, const WwIO &io, int mode, void *stream) {
-    int64_t blocks = h->max_blocks > 0 ? h->max_blocks : 256 * 64;
-    if (blocks > h->dev.n_envs) blocks = h->dev.n_envs;
     hipStream_t s = (hipStream_t)stream;
     const WwDev &d = h->dev;
-    const dim3 g((unsigned)blocks), b(64);
+    const dim3 g = particle_grid(h->max_blocks, d.n_envs), b(64);
     const bool fused = io.st != nullptr;
     const WwSpec *spec = nullptr;
     for (const WwSpec &w : WW_SPECS)
@@ -886,36 +811,7 @@ int madrl_waterworld_create(const madrl_waterworld_config *cfg, const double *se
                             int32_t device, void *state_dev, madrl_waterworld **out) {
     int rc = ww_validate(cfg);
     if (rc) return rc;
-    if (!sensors_host || !state_dev || !out || n_envs < 1) return fail(MADRL_EINVAL, "create: NULL argument or n_envs < 1");
-    if (n_envs >= 0x7FF00000ll)  // the kernel indexes envs with 32-bit integers (index + workgroup count must stay below 2^31)
-        return fail(MADRL_EINVAL, "n_envs=%lld is too large for one handle (limit 2146435071); shard the batch", (long long)n_envs);
-    if (n_envs + cfg->env_id_base > 0xFFFFFFFFll) return fail(MADRL_EINVAL, "global env index must fit 32 bits");
-    MADRL_HIP_TRY(hipSetDevice(device));
-    madrl_waterworld *h = new (std::nothrow) madrl_waterworld();
-    if (!h) return fail(MADRL_ENOMEM, "out of host memory");
-    h->cfg = *cfg;
-    h->device = device;
-    ww_layout(cfg, &h->dev);
-    h->dev.n_envs = n_envs;
-    h->dev.state = (float *)state_dev;
-    h->lds_bytes = ww_lds_bytes(h->dev);
-    h->max_blocks = 0;
-    if (h->lds_bytes > 64 * 1024) {
-        delete h;
-        return fail(MADRL_EINVAL, "configuration needs %zu B of LDS (> 64 KiB)", h->lds_bytes);
-    }
-    std::vector<float> sens(2 * (size_t)cfg->n_sensors);
-    for (size_t k = 0; k < sens.size(); ++k) sens[k] = (float)sensors_host[k];  // float64 cos/sin rounded once
-    hipError_t e = hipMalloc(&h->tables, sens.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->tables, sens.data(), sens.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (h->tables) (void)hipFree(h->tables);
-        delete h;
-        return fail(MADRL_EHIP, "sensor table upload failed: %s", hipGetErrorString(e));
-    }
-    h->dev.sensors = (const float *)h->tables;
-    *out = h;
-    return MADRL_OK;
+    return particle_create(cfg, sensors_host, n_envs, device, state_dev, out, ww_layout, ww_lds_bytes);
 }
 
 void madrl_waterworld_destroy(madrl_waterworld *h) {

@@ -4,7 +4,7 @@
   s_waitcnt (pursuit_wave.hpp, "exact-wait prefetch").  The compiler does not know those registers are in flight, so it must never
   spill or reload them: the kernels must have NO scratch and no VGPR spills.
 * pursuit_wave / pursuit_group / waterworld / hostage kernels read launch parameters from the kernel-argument segment through a
-  struct {Dev d; IO io;} view (cold_args(), ww_args(), hw_args()): the second by-value argument must start where that view says.
+  struct {Dev d; IO io;} view (kernargs<A>() in common.hpp): the second by-value argument must start where that view says.
 * The specialised Waterworld / hostage instantiations were tuned to an occupancy at which they do not spill (spill stores reach HBM).
 """
 import os
