@@ -216,6 +216,24 @@ int madrl_pursuit_declare_obs_zero(madrl_pursuit *h, const float *obs_dev, void 
 int madrl_pursuit_set_params(madrl_pursuit *h, double catchr, double constraint_window);
 int madrl_pursuit_set_curriculum(madrl_pursuit *h, const double *constraint_window_dev, const double *catchr_dev);
 
+/* Per-env agent counts (the remove-agents rule of update_curriculum, pursuit_evade.py:268-270, per env and without re-creating the
+ * handle).  set_agent_counts binds a caller-owned int32 [n_envs][2] device array of PENDING counts (pursuers, evaders); NULL turns the
+ * mode off.  The config's n_pursuers / n_evaders are then a CAPACITY (Pcap, Ecap): every env has LIVE counts 1 <= p <= Pcap,
+ * 0 <= e <= Ecap (at first the capacity), and each reset of an env -- reset() or the fused auto-reset of a step -- takes its pending
+ * counts (clamped to those ranges); the running episode keeps its agents.  An env at live (p, e) computes bit for bit what env n of
+ * a fixed-shape (p, e) batch with the same seed and env_id_base + n computes.  Layouts stay at capacity: observation rows k >= p are
+ * not written (like the rows of absent observers with control_evaders), rewards k >= p are 0, actions k >= p are ignored; evader
+ * slots >= e count as gone.  The record layout and madrl_pursuit_state_bytes do not change: a slot that does not exist holds
+ * position byte 0xFF.  The one-wavefront kernel runs the capacities listed in madrl_amd/csrc/pursuit_live_specializations.def, every
+ * other capacity the generic kernel (set_kernel(WAVE) refuses it).  Not with control_evaders = 1 (MADRL_EINVAL).  Turning the
+ * mode off is only meaningful while every env is at its capacity.
+ * get_live_counts writes the live counts int32 [n_envs][2]; set_live_counts sets them (a checkpoint restored): slots past them stop
+ * existing, a slot that exists again is at (0, 0) and, for an evader, gone until the next reset.  With the mode on, get_state
+ * reports (-1, -1) for pursuers that do not exist, and set_state writes (-1, -1) as "does not exist". */
+int madrl_pursuit_set_agent_counts(madrl_pursuit *h, const int32_t *pending_dev);
+int madrl_pursuit_get_live_counts(madrl_pursuit *h, int32_t *live_dev, void *stream);
+int madrl_pursuit_set_live_counts(madrl_pursuit *h, const int32_t *live_dev, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * MAWaterWorld  (reference: madrl_environments/pursuit/waterworld.py), float32 arithmetic
  * ---------------------------------------------------------------------------------------- */

@@ -95,6 +95,9 @@ SIGNATURES = {
     "madrl_pursuit_declare_obs_zero": (C.c_int, [_vp, _vp, _vp]),
     "madrl_pursuit_set_params": (C.c_int, [_vp, C.c_double, C.c_double]),
     "madrl_pursuit_set_curriculum": (C.c_int, [_vp, _vp, _vp]),
+    "madrl_pursuit_set_agent_counts": (C.c_int, [_vp, _vp]),
+    "madrl_pursuit_get_live_counts": (C.c_int, [_vp, _vp, _vp]),
+    "madrl_pursuit_set_live_counts": (C.c_int, [_vp, _vp, _vp]),
     "madrl_pursuit_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp]),
     "madrl_pursuit_destroy": (None, [_vp]),
     "madrl_pursuit_set_launch": (C.c_int, [_vp, C.c_int32, C.c_int64]),

@@ -36,6 +36,7 @@ enum : uint32_t { K_GRID = 0, K_ID = 1, K_FILL = 2, K_SKIP = 3 };
 constexpr uint32_t PAD_MAP = 0xFEu;  // map layer outside the map  -> vtab[0xFE] = 1/layer_norm
 constexpr uint32_t PAD_CNT = 0xFFu;  // count layers outside the map -> "do not store" (Q2)
 constexpr int MAX_CELL_COUNT = 253;  // byte grids: the agents of one layer on ONE cell must stay < PAD_MAP (checked where they are counted)
+constexpr int NOT_HERE = 0xFF;       // position byte of a slot that does not exist (per-env agent counts; no coordinate is 255)
 constexpr int MAX_COUNT = 1023;      // agents per layer.  The authors' largest launch line runs 100 pursuers / 300 evaders
                                      // (runners/old/rllab/pursuit_cnn.sh:1); more than 253 of one kind on one cell raises the overflow bit
 
@@ -123,402 +124,21 @@ __device__ __forceinline__ double np_pairwise_sum(const double *a, int n) { retu
 static_assert(MAX_COUNT <= 1024, "np_pairwise_sum: four levels of numpy's split");
 
 // mode 0: reset(mask)   mode 1: step (+ fused auto-reset)
+// LIVE (pursuit_live_kernel) = per-env agent counts (madrl_pursuit_set_agent_counts): d.P / d.E are a capacity, the env's live
+// (np, ne) are its leading slots whose position byte is not NOT_HERE; a reset takes them from pending [n_envs][2].  Pursuers >= np
+// do not move, are not counted and get no observation row and a 0 reward; evader slots >= ne are gone; draws number the agents in
+// the live layout (evader i = agent np + i), as a fixed (np, ne) batch does.
 template <int NT>
 __global__ void pursuit_kernel(const PursuitDev d, const PursuitIO io, const int mode) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const int tid = threadIdx.x;
-    const int nthr = blockDim.x;
+    constexpr bool LIVE = false;
+    const int32_t *const pending = nullptr;
+#include "pursuit_generic.inc"
+}
 
-    // ---- LDS carve (all offsets multiples of 16)
-    float *s_vtab = reinterpret_cast<float *>(smem);                   // 256 floats
-    uint8_t *g_map = smem + 1024;                                      // 3 layers, contiguous:
-    uint8_t *g_pc = g_map + d.GSZ;                                     //   map | pursuers | evaders
-    uint8_t *g_ec = g_pc + d.GSZ;
-    uint8_t *g_cr = g_ec + d.GSZ;                                      // credit layer (purs_sur)
-    const int A16 = (d.A + 15) & ~15;
-    uint8_t *s_ax = g_cr + d.GSZ;
-    uint8_t *s_ay = s_ax + A16;
-    uint32_t *s_gone = reinterpret_cast<uint32_t *>(s_ay + A16);       // ngw words
-    uint32_t *s_term = s_gone + ((d.ngw + 3) & ~3);                    // ntw words
-    uint32_t *s_misc = s_term + ((d.ntw + 3) & ~3);                    // [0..3] header, [4] removed
-    int32_t *s_kpre = reinterpret_cast<int32_t *>(s_misc + 8);         // P ints (pre-move counts)
-    double *s_rew = reinterpret_cast<double *>(s_kpre + ((d.P + 3) & ~3));  // P doubles
-    uint32_t *s_code = reinterpret_cast<uint32_t *>(s_rew + ((d.P + 1) & ~1));  // D slot codes (float4 observation path)
-    // observers: whose windows the P observation rows show.  train_pursuit: pursuer p.  Evader control (:204-207, :251 with
-    // agent_layer = evader_layer): row k = the k-th remaining evader among slots 0..P-1 (collect_obs :418-428 walks
-    // range(n_agents()) = range(n_pursuers) over evaders_gone and indexes the compacted layer); s_misc[5] = number of rows
-    uint8_t *s_ox = reinterpret_cast<uint8_t *>(s_code + ((d.D + 3) & ~3));
-    uint8_t *s_oy = s_ox + ((d.P + 15) & ~15);
-
-    // ---- once per workgroup: value table and this thread's observation slot codes
-    for (int k = tid; k < 256; k += nthr) s_vtab[k] = d.vtab[k];
-    const bool vec4 = (d.D & 3) == 0;  // rows are whole float4s (always for odd obs_range)
-    if (vec4) for (int k = tid; k < d.D; k += nthr) s_code[k] = d.codes[k];
-    uint32_t code[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int r = tid + t * nthr;
-        code[t] = (r < d.D) ? d.codes[r] : (K_SKIP << 24);
-    }
-    const int GW = d.GW, pad = d.pad, GSZ = d.GSZ;
-    const int obs_off = (d.R - 1) / 2;  // pursuit_evade.py:65
-    const int gsz_words = GSZ >> 2;
-    int cached_map = -1;
-
-    for (int64_t env = blockIdx.x; env < d.n_envs; env += gridDim.x) {
-        if (mode == 0 && io.mask != nullptr && io.mask[env] == 0) continue;  // block-uniform
-        uint8_t *rec = d.state + env * (int64_t)d.rec_bytes;
-        __syncthreads();  // previous env's LDS reads are finished
-        // ------------------------------------------------------------ load state record
-        if (tid < 4) s_misc[tid] = reinterpret_cast<const uint32_t *>(rec)[tid];
-        if (tid == 4) s_misc[4] = 0;
-        for (int a = tid; a < d.A; a += nthr) {
-            const uint32_t xy = reinterpret_cast<const uint16_t *>(rec + HDR_BYTES)[a];
-            s_ax[a] = (uint8_t)(xy & 0xFF);
-            s_ay[a] = (uint8_t)(xy >> 8);
-        }
-        for (int w = tid; w < d.ngw; w += nthr)
-            s_gone[w] = reinterpret_cast<const uint32_t *>(rec + d.off_gone)[w];
-        for (int w = tid; w < d.ntw; w += nthr)
-            s_term[w] = reinterpret_cast<const uint32_t *>(rec + d.off_term)[w];
-        __syncthreads();
-        uint32_t tick = s_misc[0];
-        int32_t tstep = (int32_t)s_misc[1];
-        int32_t map_id = (int32_t)s_misc[2];
-        const uint32_t gid = d.gid_base + (uint32_t)env;
-        bool do_reset = (mode == 0);
-        uint32_t done_bits = 0;
-
-        // -------------------------------------------------------------- observations (:418-461)
-        // Element r of pursuer p's row: code[] says which padded-grid byte (relative to the
-        // window origin) feeds it.  Stores are lane-contiguous dwords; cells of the count
-        // layers outside the map read 0xFF and are NOT stored (reference leaves them stale).
-        auto write_obs = [&]() {
-#if defined(MADRL_ABLATE) && (MADRL_ABLATE & 8)
-            if (d.n_envs >= 0) return;
-#endif
-            float *orow = io.obs + env * (int64_t)d.P * d.D;
-            int n_rows = d.P;
-            if (!d.train_pursuit) {  // observers = the remaining evaders of slots 0..P-1, in slot order
-                __syncthreads();
-                if (tid == 0) {
-                    int k = 0;
-                    for (int i = 0; i < d.P && i < d.E; ++i)
-                        if (!((s_gone[i >> 5] >> (i & 31)) & 1u)) { s_ox[k] = s_ax[d.P + i]; s_oy[k] = s_ay[d.P + i]; ++k; }
-                    s_misc[5] = (uint32_t)k;
-                }
-                __syncthreads();
-                n_rows = (int)s_misc[5];
-            }
-            const uint8_t *obx = d.train_pursuit ? s_ax : s_ox, *oby = d.train_pursuit ? s_ay : s_oy;
-            if (vec4) {
-                // float4 path (same scheme as the wave kernel): the P*D/4 float4 slots of the env are spread over the threads;
-                // a slot without stale cells is ONE non-temporal 16-byte store, a slot with stale cells falls back to masked
-                // dword stores (plain, merged in L2).  One float4 instruction touches each 64-byte chunk once, where the
-                // per-pursuer dword rows re-touch the row tails (scripts/ubench/vmem_issue.hip).
-                typedef float v4f __attribute__((ext_vector_type(4)));
-                const int DV = d.D >> 2, NQ = d.P * DV;
-                int p = tid / DV, f = tid - p * DV;
-                const int dp = nthr / DV, df = nthr - dp * DV;
-                for (int q = tid; q < NQ; q += nthr) {
-                    if (p >= n_rows) break;  // rows of absent observers keep their old contents
-                    const int base = (obx[p] - obs_off + pad) * GW + (oby[p] - obs_off + pad);
-                    float val[4];
-                    bool keep[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const uint32_t c = s_code[4 * f + k];
-                        const uint32_t kind = c >> 24;
-                        keep[k] = true;
-                        val[k] = 0.0f;
-                        if (kind == K_GRID) {
-                            const uint32_t v = g_map[base + (int)(c & 0xFFFFFFu)];
-                            keep[k] = v != PAD_CNT;
-                            val[k] = s_vtab[v];
-                        } else if (kind == K_ID) {
-                            val[k] = (float)((double)p / (double)d.P);  // :440-445
-                        } else if (kind == K_FILL) {
-                            val[k] = d.fill32;  // even obs_range: never-copied channel-0 cells
-                        } else {
-                            keep[k] = false;
-                        }
-                    }
-                    float *o = orow + 4 * (int64_t)q;
-                    if (keep[0] & keep[1] & keep[2] & keep[3]) {
-                        const v4f v = {val[0], val[1], val[2], val[3]};
-                        __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(o));
-                    } else {
-                        if (keep[0]) o[0] = val[0];
-                        if (keep[1]) o[1] = val[1];
-                        if (keep[2]) o[2] = val[2];
-                        if (keep[3]) o[3] = val[3];
-                    }
-                    f += df; p += dp;
-                    if (f >= DV) { f -= DV; ++p; }
-                }
-                return;
-            }
-            // dword path (rows that are not whole float4s: even obs_range with flatten)
-            for (int p = 0; p < n_rows; ++p) {
-                const int base = (obx[p] - obs_off + pad) * GW + (oby[p] - obs_off + pad);
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const int r = tid + t * nthr;
-                    const uint32_t kind = code[t] >> 24;
-                    if (kind == K_GRID) {
-                        const uint32_t v = g_map[base + (int)(code[t] & 0xFFFFFFu)];
-                        if (v != PAD_CNT) orow[p * d.D + r] = s_vtab[v];
-                    } else if (kind == K_ID) {
-                        orow[p * d.D + r] = (float)((double)p / (double)d.P);  // :440-445
-                    } else if (kind == K_FILL) {
-                        orow[p * d.D + r] = d.fill32;  // even obs_range: never-copied channel-0 cells
-                    }
-                }
-            }
-        };
-
-
-        if (mode == 1) {
-            // -------------------------------------------------------- grids for this env
-            {
-                const uint32_t *mt = reinterpret_cast<const uint32_t *>(d.maps + (int64_t)map_id * d.map_stride);
-                const uint32_t *ct = reinterpret_cast<const uint32_t *>(d.cnt_tmpl);
-                for (int k = tid; k < gsz_words; k += nthr) {
-                    if (cached_map != map_id) reinterpret_cast<uint32_t *>(g_map)[k] = mt[k];
-                    const uint32_t c = ct[k];
-                    reinterpret_cast<uint32_t *>(g_pc)[k] = c;
-                    reinterpret_cast<uint32_t *>(g_ec)[k] = c;
-                    reinterpret_cast<uint32_t *>(g_cr)[k] = 0u;
-                }
-                cached_map = map_id;
-            }
-            __syncthreads();
-            // -------------------------------------------------------- pre-move evader counts (:364-365)
-            for (int i = tid; i < d.E; i += nthr) {
-                if (!((s_gone[i >> 5] >> (i & 31)) & 1u))
-                    lds_byte_add(g_ec, (s_ax[d.P + i] + pad) * GW + s_ay[d.P + i] + pad, &s_misc[3]);
-            }
-            __syncthreads();
-            // proximity reward on the PRE-move state, np.clip keeps border pursuers on their
-            // own cell (pursuit_evade.py:374-380)
-            for (int p = tid; p < d.P; p += nthr) {
-                const int x = s_ax[p], y = s_ay[p];
-                const int xm = max(x - 1, 0), xp = min(x + 1, d.xs - 1);
-                const int ym = max(y - 1, 0), yp = min(y + 1, d.ys - 1);
-                s_kpre[p] = (int)g_ec[(xm + pad) * GW + y + pad] + (int)g_ec[(xp + pad) * GW + y + pad] +
-                            (int)g_ec[(x + pad) * GW + yp + pad] + (int)g_ec[(x + pad) * GW + ym + pad];
-            }
-            __syncthreads();
-            // -------------------------------------------------------- moves (:229-241)
-            for (int a = tid; a < d.A; a += nthr) {
-                const bool is_p = a < d.P;
-                const int i = a - d.P;
-                if (!is_p && ((s_gone[i >> 5] >> (i & 31)) & 1u)) continue;
-                int x = s_ax[a], y = s_ay[a];
-                int act;
-                int k = 0;  // evaders: index in the evader LAYER = alive evaders in slots below i
-                if (!is_p) {
-                    lds_byte_sub(g_ec, (x + pad) * GW + y + pad);  // undo the pre-move count
-                    for (int w = 0; w < (i >> 5); ++w) k += 32 - __popc(s_gone[w]);
-                    k += (i & 31) - __popc(s_gone[i >> 5] & ((1u << (i & 31)) - 1u));
-                }
-                if (d.train_pursuit) {
-                    if (is_p) {
-                        act = io.actions[env * d.P + a];
-                    } else if (io.inj_eact != nullptr) {
-                        act = io.inj_eact[env * d.E + k];
-                    } else {
-                        const u32x4 r = philox4x32_10(gid, tick, (uint32_t)k, TAG_EVADER_ACT, d.k0, d.k1);
-                        act = (int)__umulhi(r.x, 5u);  // RandomPolicy.act, Controllers.py:15-16
-                    }
-                } else {
-                    // evader control (:215-224): action k moves the k-th agent of the evader layer (`for i, a in enumerate(actions):
-                    // agent_layer.move_agent(i, a)`, :229-230; the caller passes one action per env.agents entry = n_pursuers of
-                    // them, so evaders past the first n_pursuers of the layer never move); every pursuer moves by one
-                    // pursuer_controller.act() draw (:238-241), injected as entry a of inj_eact [n_envs][P]
-                    if (!is_p) {
-                        act = k < d.P ? io.actions[env * d.P + k] : 4;
-                    } else if (io.inj_eact != nullptr) {
-                        act = io.inj_eact[env * d.P + a];
-                    } else {
-                        const u32x4 r = philox4x32_10(gid, tick, (uint32_t)a, TAG_PURSUER_ACT, d.k0, d.k1);
-                        act = (int)__umulhi(r.x, 5u);
-                    }
-                }
-                // DiscreteAgent.step, DiscreteAgent.py:69-97
-                const bool term = (s_term[a >> 5] >> (a & 31)) & 1u;
-                if (!term) {
-                    if (g_map[(x + pad) * GW + y + pad] == 1) {
-                        atomicOr(&s_term[a >> 5], 1u << (a & 31));  // standing in a building
-                    } else {
-                        int nx = x, ny = y;
-                        if (act == 0) nx = x - 1;
-                        else if (act == 1) nx = x + 1;
-                        else if (act == 2) ny = y + 1;
-                        else if (act == 3) ny = y - 1;
-                        // padded map layer: 0 = free, 1 = building, 0xFE = outside the map
-                        if (g_map[(nx + pad) * GW + ny + pad] == 0) {
-                            x = nx;
-                            y = ny;
-                        }
-                    }
-                }
-                s_ax[a] = (uint8_t)x;
-                s_ay[a] = (uint8_t)y;
-                lds_byte_add(is_p ? g_pc : g_ec, (x + pad) * GW + y + pad, &s_misc[3]);  // :244-246
-            }
-            __syncthreads();
-            // -------------------------------------------------------- catch resolution (:463-521)
-            const uint8_t *need_tab = d.maps + (int64_t)map_id * d.map_stride + GSZ;
-            for (int i = tid; i < d.E; i += nthr) {
-                if ((s_gone[i >> 5] >> (i & 31)) & 1u) continue;
-                const int x = s_ax[d.P + i], y = s_ay[d.P + i];
-                const int c0 = (x + pad) * GW + y + pad;
-                bool caught;
-                if (d.surround) {
-                    // neighbour order of surround_mask (:150); pad cells hold 0xFF => never a hit
-                    const bool h0 = (uint8_t)(g_pc[c0 - GW] - 1) < 0xFEu;
-                    const bool h1 = (uint8_t)(g_pc[c0 + GW] - 1) < 0xFEu;
-                    const bool h2 = (uint8_t)(g_pc[c0 + 1] - 1) < 0xFEu;
-                    const bool h3 = (uint8_t)(g_pc[c0 - 1] - 1) < 0xFEu;
-                    const int cnt = (int)h0 + (int)h1 + (int)h2 + (int)h3;
-                    caught = (cnt == (int)need_tab[x * d.ys + y]);  // need_to_surround :523-540
-                    if (caught) {  // pursuers standing on a matched neighbour get credit (:489-495)
-                        if (h0) g_cr[c0 - GW] = 1;
-                        if (h1) g_cr[c0 + GW] = 1;
-                        if (h2) g_cr[c0 + 1] = 1;
-                        if (h3) g_cr[c0 - 1] = 1;
-                    }
-                } else {
-                    caught = (int)g_pc[c0] >= d.n_catch;  // :498
-                    if (caught) g_cr[c0] = 1;             // :503-506
-                }
-                if (caught) {
-                    atomicOr(&s_gone[i >> 5], 1u << (i & 31));
-                    atomicAdd(&s_misc[4], 1u);
-                }
-            }
-            __syncthreads();
-            // -------------------------------------------------------- rewards (:254-262)
-            int n_alive = d.E;
-            for (int w = 0; w < d.ngw; ++w) n_alive -= __popc(s_gone[w]);
-            for (int p = tid; p < d.P; p += nthr) {
-                const int sur = g_cr[(s_ax[p] + pad) * GW + s_ay[p] + pad];
-                const double catchr = d.catchr_env ? d.catchr_env[env] : d.catchr;
-                double r = catchr * (double)s_kpre[p];
-                r += d.term_pursuit * (sur ? 1.0 : 0.0);
-                r += d.urgency;
-                if (d.reward_global) s_rew[p] = r;
-                else io.rew[env * d.P + p] = (float)r;
-            }
-            if (d.reward_global) {
-                __syncthreads();
-                if (tid < d.P) {
-                    const double m = np_pairwise_sum(s_rew, d.P) / (double)d.P;
-                    for (int p = tid; p < d.P; p += nthr) io.rew[env * d.P + p] = (float)m;
-                }
-            }
-            tick += 1;
-            tstep += 1;
-            if (n_alive == 0) done_bits |= 1u;                               // :383-389
-            if (d.max_steps > 0 && tstep >= d.max_steps) done_bits |= 2u;
-            const uint32_t overflow = s_misc[3] ? 0x80u : 0u;                // a cell's count left the byte range: results void
-            if (tid == 0) {
-                io.done[env] = (uint8_t)(done_bits | overflow);
-                io.removed[env] = (int32_t)s_misc[4];
-                d.flags[env] = done_flag_word(done_bits | overflow);
-            }
-            do_reset = d.auto_reset && done_bits != 0;
-        }
-
-        if (mode == 1 && do_reset) {
-            // auto-reset: the reference sequence is step() then reset(); both write the persistent
-            // observation buffer, and cells the second write skips keep the first one's values
-            write_obs();
-            __syncthreads();
-        }
-        if (do_reset) {
-            // ---------------------------------------------------------- reset (:173-207)
-            __syncthreads();
-            if (tid == 0) s_misc[3] = 0u;                            // a new episode: the overflow mark goes
-            for (int w = tid; w < d.ngw; w += nthr) s_gone[w] = 0u;  // :175-176
-            for (int w = tid; w < d.ntw; w += nthr) s_term[w] = 0u;  // fresh agents
-            if (io.inj_map != nullptr && mode == 0) {
-                map_id = io.inj_map[env];
-            } else if (d.sample_maps) {  // :182-183
-                const u32x4 r = philox4x32_10(gid, tick, 0u, TAG_RESET_ENV, d.k0, d.k1);
-                map_id = (int)__umulhi(r.x, (uint32_t)d.n_maps);
-            }
-            {
-                const uint32_t *mt = reinterpret_cast<const uint32_t *>(d.maps + (int64_t)map_id * d.map_stride);
-                const uint32_t *ct = reinterpret_cast<const uint32_t *>(d.cnt_tmpl);
-                for (int k = tid; k < gsz_words; k += nthr) {
-                    if (cached_map != map_id) reinterpret_cast<uint32_t *>(g_map)[k] = mt[k];
-                    const uint32_t c = ct[k];
-                    reinterpret_cast<uint32_t *>(g_pc)[k] = c;
-                    reinterpret_cast<uint32_t *>(g_ec)[k] = c;
-                }
-                cached_map = map_id;
-            }
-            // constraint window (:185-191), float64 like the reference
-            const u32x4 rw = philox4x32_10(gid, tick, 1u, TAG_RESET_ENV, d.k0, d.k1);
-            const double cw = d.cw_env ? d.cw_env[env] : d.cw;
-            const double sx = u53(rw.x, rw.y) * (1.0 - cw);
-            const double sy = u53(rw.z, rw.w) * (1.0 - cw);
-            const int xlb = (int)(d.xs * sx), xub = (int)(d.xs * (sx + cw));
-            const int ylb = (int)(d.ys * sy), yub = (int)(d.ys * (sy + cw));
-            // random_opponents (train_pursuit, :177-181): this episode has n_create <= E evaders; the slots above are not
-            // created and count as gone.  An injected position with x < 0 marks a slot that is not created.
-            const bool inj = io.inj_pos != nullptr && mode == 0;
-            int n_create = d.E;
-            if (d.max_opponents > 0 && !inj) {
-                const u32x4 r3 = philox4x32_10(gid, tick, 2u, TAG_RESET_ENV, d.k0, d.k1);
-                n_create = min(1 + (int)__umulhi(r3.x, (uint32_t)(d.max_opponents - 1)), d.E);
-            }
-            __syncthreads();
-            for (int a = tid; a < d.A; a += nthr) {  // create_agents, agent_utils.py:12-28
-                int x = 0, y = 0;
-                if (a >= d.P && (a - d.P >= n_create || (inj && io.inj_pos[(env * d.A + a) * 2] < 0))) {
-                    atomicOr(&s_gone[(a - d.P) >> 5], 1u << ((a - d.P) & 31));
-                    s_ax[a] = 0;
-                    s_ay[a] = 0;
-                    continue;
-                }
-                if (io.inj_pos != nullptr && mode == 0) {
-                    x = io.inj_pos[(env * d.A + a) * 2];
-                    y = io.inj_pos[(env * d.A + a) * 2 + 1];
-                } else {
-                    // feasible_position: rejection sampling (agent_utils.py:37-47); bounded
-                    for (uint32_t att = 0; att < 1024u; ++att) {
-                        const u32x4 r = philox4x32_10(gid, tick, (uint32_t)a, TAG_RESET_POS | (att << 8), d.k0, d.k1);
-                        x = xlb + (int)__umulhi(r.x, (uint32_t)(xub - xlb));
-                        y = ylb + (int)__umulhi(r.y, (uint32_t)(yub - ylb));
-                        if (g_map[(x + pad) * GW + y + pad] != 1) break;
-                    }
-                }
-                s_ax[a] = (uint8_t)x;
-                s_ay[a] = (uint8_t)y;
-                lds_byte_add(a < d.P ? g_pc : g_ec, (x + pad) * GW + y + pad, &s_misc[3]);  // :201-203
-            }
-            tick += 1;
-            tstep = 0;
-            __syncthreads();
-        }
-
-        write_obs();
-        // -------------------------------------------------------------- store state record
-        for (int a = tid; a < d.A; a += nthr)
-            reinterpret_cast<uint16_t *>(rec + HDR_BYTES)[a] = (uint16_t)(s_ax[a] | (s_ay[a] << 8));
-        for (int w = tid; w < d.ngw; w += nthr) reinterpret_cast<uint32_t *>(rec + d.off_gone)[w] = s_gone[w];
-        for (int w = tid; w < d.ntw; w += nthr) reinterpret_cast<uint32_t *>(rec + d.off_term)[w] = s_term[w];
-        if (tid == 0) {
-            uint32_t *h = reinterpret_cast<uint32_t *>(rec);
-            h[0] = tick;
-            h[1] = (uint32_t)tstep;
-            h[2] = (uint32_t)map_id;
-            h[3] = s_misc[3];   // sticky count-overflow mark of the episode (0 in every run that stays inside the byte grids)
-        }
-    }
+template <int NT>
+__global__ void pursuit_live_kernel(const PursuitDev d, const PursuitIO io, const int mode, const int32_t *pending) {
+    constexpr bool LIVE = true;
+#include "pursuit_generic.inc"
 }
 
 // ------------------------------------------------------------------ state (un)packing
@@ -596,6 +216,43 @@ __global__ void pursuit_set_state_kernel(const PursuitDev d, const int32_t *pos_
     }
 }
 
+// Per-env agent counts in the records (madrl_pursuit_get_live_counts / set_live_counts, madrl_pursuit_get_state).  in != nullptr: env n gets
+// live counts (in[n][0], in[n][1]) -- slots past them do not exist (NOT_HERE, evaders gone), a slot that exists again is at (0, 0) and,
+// for an evader, gone (not created) until the next reset.  out: the live counts; pos_p: pursuers that do not exist read (-1, -1).
+__global__ void pursuit_live_counts_kernel(const PursuitDev d, int32_t *pos_p, int32_t *out, const int32_t *in) {
+    const int64_t env = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (env >= d.n_envs) return;
+    uint8_t *rec = d.state + env * (int64_t)d.rec_bytes;
+    uint8_t *xy = rec + HDR_BYTES;
+    uint32_t *gw = reinterpret_cast<uint32_t *>(rec + d.off_gone);
+    uint32_t *tw = reinterpret_cast<uint32_t *>(rec + d.off_term);
+    if (in) {
+        const int np = min(max(in[2 * env], 1), d.P), ne = min(max(in[2 * env + 1], 0), d.E);
+        for (int a = 0; a < d.A; ++a) {
+            const bool is_p = a < d.P;
+            const int i = a - d.P;
+            if (is_p ? a >= np : i >= ne) {
+                xy[2 * a] = xy[2 * a + 1] = (uint8_t)NOT_HERE;
+                tw[a >> 5] &= ~(1u << (a & 31));
+                if (!is_p) gw[i >> 5] |= 1u << (i & 31);
+            } else if (xy[2 * a] == NOT_HERE) {
+                xy[2 * a] = xy[2 * a + 1] = 0;
+                if (!is_p) gw[i >> 5] |= 1u << (i & 31);
+            }
+        }
+    }
+    int np = 0, ne = 0;
+    while (np < d.P && xy[2 * np] != NOT_HERE) ++np;
+    while (ne < d.E && xy[2 * (d.P + ne)] != NOT_HERE) ++ne;
+    if (out) {
+        out[2 * env] = np;
+        out[2 * env + 1] = ne;
+    }
+    if (pos_p)
+        for (int p = 0; p < d.P; ++p)
+            if (xy[2 * p] == NOT_HERE) pos_p[(env * d.P + p) * 2] = pos_p[(env * d.P + p) * 2 + 1] = -1;
+}
+
 }  // namespace
 
 // =================================================================== host side / C ABI
@@ -621,6 +278,8 @@ struct madrl_pursuit {
     int walk_mode = 0;        // 0 auto (alternate above ~375 MB per launch), 1 always alternate, 2 always forward; fixed at create
     void *wtables;
     int kernel_kind;  // MADRL_KERNEL_AUTO / _GENERIC / _WAVE (requested)
+    const int32_t *pending = nullptr;      // per-env agent counts (madrl_pursuit_set_agent_counts): caller-owned int32 [n_envs][2], or off
+    const WaveEntry *wave_live = nullptr;  // the live-count instantiation of this shape (pursuit_live_specializations.def), if compiled
     hipEvent_t ev_fork = nullptr, ev_done = nullptr;   // madrl_pursuit_step_sharded: made by madrl_pursuit_create on the handle's device, destroyed with the handle
 };
 
@@ -646,7 +305,7 @@ namespace {
 
 template <class S>
 void wave_launch(const pw::WaveDev &d, const pw::WaveIO &io, int mode, int64_t blocks, hipStream_t s) {
-    if constexpr (S::E >= S::P) {
+    if constexpr (S::E >= S::P && !S::LIVE) {
         if (io.control_evaders) {   // train_pursuit=False: the evader-control instantiations (reset, flexible step)
             if (mode == 0) hipLaunchKernelGGL((pw::pursuit_wave_kernel<S, 0, false, true>), dim3((unsigned)blocks), dim3(64), 0, s, d, io);
             else hipLaunchKernelGGL((pw::pursuit_wave_kernel<S, 1, true, true>), dim3((unsigned)blocks), dim3(64), 0, s, d, io);
@@ -708,6 +367,24 @@ const WaveEntry *find_wave(const madrl_pursuit_config *c) {
     return nullptr;
 }
 
+// (wave_launch of an LShape: no evader-control instantiations, madrl_pursuit_set_agent_counts refuses control_evaders)
+#define XL(XS, YS, NP, NE, R, FL) {wave_geom<pw::LShape<XS, YS, NP, NE, R, FL>>(1, pw::LShape<XS, YS, NP, NE, R, FL>::OCC), wave_launch<pw::LShape<XS, YS, NP, NE, R, FL>>},
+const WaveEntry LIVE_TABLE[] = {
+#include "pursuit_live_specializations.def"
+};
+#undef XL
+
+// the live-count instantiation matching a shape whose fixed-shape entry `w` the handle uses (same geometry, same tables)
+const WaveEntry *find_live(const WaveEntry *w) {
+    if (!w) return nullptr;
+    for (const WaveEntry &e : LIVE_TABLE) {
+        const WaveGeom &g = e.g, &f = w->g;
+        if (g.xs == f.xs && g.ys == f.ys && g.P == f.P && g.E == f.E && g.R == f.R && g.flatten == f.flatten && g.waves == f.waves &&
+            g.rec_bytes == f.rec_bytes && g.GSZ == f.GSZ && g.D == f.D && g.X_ID == f.X_ID && g.mwords == f.mwords)
+            return &e;
+    }
+    return nullptr;
+}
 
 int validate(const madrl_pursuit_config *c) {
     if (!c) return fail(MADRL_EINVAL, "config is NULL");
@@ -795,12 +472,21 @@ template <int NT>
 void launch_nt(const madrl_pursuit *h, const PursuitIO &io, int mode, hipStream_t s) {
     int64_t blocks = h->dev.n_envs;
     if (h->max_blocks > 0 && blocks > h->max_blocks) blocks = h->max_blocks;
-    hipLaunchKernelGGL(pursuit_kernel<NT>, dim3((unsigned)blocks), dim3((unsigned)h->threads), h->lds_bytes, s,
-                       h->dev, io, mode);
+    if (h->pending)
+        hipLaunchKernelGGL(pursuit_live_kernel<NT>, dim3((unsigned)blocks), dim3((unsigned)h->threads), h->lds_bytes, s,
+                           h->dev, io, mode, h->pending);
+    else
+        hipLaunchKernelGGL(pursuit_kernel<NT>, dim3((unsigned)blocks), dim3((unsigned)h->threads), h->lds_bytes, s,
+                           h->dev, io, mode);
+}
+
+// the fast path this handle can use in its current mode (per-env agent counts: the live-count instantiation)
+bool has_wave(const madrl_pursuit *h) {
+    return h->pending ? h->wave_live != nullptr : h->wave != nullptr;
 }
 
 bool use_wave(const madrl_pursuit *h) {
-    return h->wave != nullptr && h->kernel_kind != MADRL_KERNEL_GENERIC;
+    return has_wave(h) && h->kernel_kind != MADRL_KERNEL_GENERIC;
 }
 
 int launch(madrl_pursuit *h, const PursuitIO &io, int mode, void *stream) {
@@ -829,7 +515,8 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, void *stream) {
             if (h->walk_mode != 0) alternate = h->walk_mode == 1;
             if (alternate) wd.reverse = (int32_t)(h->step_count++ & 1);
         }
-        h->wave->launch(wd, w, mode, blocks, s);
+        wd.pending = h->pending;
+        (h->pending ? h->wave_live : h->wave)->launch(wd, w, mode, blocks, s);
         MADRL_HIP_TRY(hipGetLastError());
         return MADRL_OK;
     }
@@ -1113,7 +800,6 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
             w.n_envs = d.n_envs;
             w.fmaps = reinterpret_cast<const uint32_t *>(h->wtables);
             w.vtab = d.vtab;
-            w.codes = reinterpret_cast<const uint32_t *>(h->wtables) + w_codes;
             w.cnt_tmpl = reinterpret_cast<const uint32_t *>(h->wtables) + w_tmpl;
             w.slot_tab = reinterpret_cast<const uint32_t *>(h->wtables) + w_slots;
             w.state = d.state;
@@ -1124,6 +810,7 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
             h->wave = nullptr;
         }
     }
+    h->wave_live = find_live(h->wave);
 
     h->walk_mode = 0;
     h->max_blocks = 0;
@@ -1171,6 +858,10 @@ int madrl_pursuit_set_launch(madrl_pursuit *h, int32_t threads, int64_t max_bloc
         (void)MADRL_SET_LDS(1); (void)MADRL_SET_LDS(2); (void)MADRL_SET_LDS(3); (void)MADRL_SET_LDS(4);
         (void)MADRL_SET_LDS(5); (void)MADRL_SET_LDS(6); (void)MADRL_SET_LDS(7); (void)MADRL_SET_LDS(8);
 #undef MADRL_SET_LDS
+#define MADRL_SET_LDS(NT) hipFuncSetAttribute((const void *)pursuit_live_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
+        (void)MADRL_SET_LDS(1); (void)MADRL_SET_LDS(2); (void)MADRL_SET_LDS(3); (void)MADRL_SET_LDS(4);
+        (void)MADRL_SET_LDS(5); (void)MADRL_SET_LDS(6); (void)MADRL_SET_LDS(7); (void)MADRL_SET_LDS(8);
+#undef MADRL_SET_LDS
     }
     return MADRL_OK;
 }
@@ -1188,6 +879,9 @@ int madrl_pursuit_set_kernel(madrl_pursuit *h, int32_t kind) {
     if (!h) return fail(MADRL_EINVAL, "handle is NULL");
     if (kind != MADRL_KERNEL_AUTO && kind != MADRL_KERNEL_GENERIC && kind != MADRL_KERNEL_WAVE)
         return fail(MADRL_EINVAL, "unknown kernel kind %d", kind);
+    if (kind == MADRL_KERNEL_WAVE && h->pending && !h->wave_live)
+        return fail(MADRL_EINVAL, "per-env agent counts: no live-count specialisation was compiled for this capacity "
+                    "(see madrl_amd/csrc/pursuit_live_specializations.def)");
     if (kind == MADRL_KERNEL_WAVE && !h->wave)
         return fail(MADRL_EINVAL, "no one-wavefront-per-env specialisation was compiled for this configuration "
                     "(see madrl_amd/csrc/pursuit_specializations.def)");
@@ -1268,6 +962,10 @@ int madrl_pursuit_get_state(madrl_pursuit *h, int32_t *pos_p, int32_t *pos_e, ui
     hipLaunchKernelGGL(pursuit_get_state_kernel, dim3(blocks), dim3(128), 0, (hipStream_t)stream, h->dev, pos_p,
                        pos_e, gone, term_p, term_e, map_id, tick, t);
     MADRL_HIP_TRY(hipGetLastError());
+    if (h->pending && pos_p) {  // pursuer slots that do not exist: (-1, -1)
+        hipLaunchKernelGGL(pursuit_live_counts_kernel, dim3(blocks), dim3(128), 0, (hipStream_t)stream, h->dev, pos_p, nullptr, nullptr);
+        MADRL_HIP_TRY(hipGetLastError());
+    }
     return MADRL_OK;
 }
 
@@ -1312,6 +1010,34 @@ int madrl_pursuit_set_curriculum(madrl_pursuit *h, const double *constraint_wind
     if (!h) return fail(MADRL_EINVAL, "handle is NULL");
     h->dev.cw_env = constraint_window_dev;
     h->dev.catchr_env = catchr_dev;
+    return MADRL_OK;
+}
+
+int madrl_pursuit_set_agent_counts(madrl_pursuit *h, const int32_t *pending_dev) {
+    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
+    if (pending_dev && !h->dev.train_pursuit)
+        return fail(MADRL_EINVAL, "per-env agent counts with control_evaders=1 (train_pursuit=False) are not supported");
+    if (pending_dev && h->kernel_kind == MADRL_KERNEL_WAVE && !h->wave_live)
+        return fail(MADRL_EINVAL, "per-env agent counts: kernel WAVE was requested and no live-count specialisation was compiled for this "
+                    "capacity (see madrl_amd/csrc/pursuit_live_specializations.def)");
+    h->pending = pending_dev;
+    return MADRL_OK;
+}
+
+int madrl_pursuit_get_live_counts(madrl_pursuit *h, int32_t *live_dev, void *stream) {
+    if (!h || !live_dev) return fail(MADRL_EINVAL, "get_live_counts: NULL argument");
+    const unsigned blocks = (unsigned)((h->dev.n_envs + 127) / 128);
+    hipLaunchKernelGGL(pursuit_live_counts_kernel, dim3(blocks), dim3(128), 0, (hipStream_t)stream, h->dev, nullptr, live_dev, nullptr);
+    MADRL_HIP_TRY(hipGetLastError());
+    return MADRL_OK;
+}
+
+int madrl_pursuit_set_live_counts(madrl_pursuit *h, const int32_t *live_dev, void *stream) {
+    if (!h || !live_dev) return fail(MADRL_EINVAL, "set_live_counts: NULL argument");
+    if (!h->pending) return fail(MADRL_EINVAL, "set_live_counts: the handle has no per-env agent counts (madrl_pursuit_set_agent_counts)");
+    const unsigned blocks = (unsigned)((h->dev.n_envs + 127) / 128);
+    hipLaunchKernelGGL(pursuit_live_counts_kernel, dim3(blocks), dim3(128), 0, (hipStream_t)stream, h->dev, nullptr, nullptr, live_dev);
+    MADRL_HIP_TRY(hipGetLastError());
     return MADRL_OK;
 }
 

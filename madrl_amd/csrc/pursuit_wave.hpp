@@ -56,7 +56,7 @@ struct WaveDev {
     int64_t n_envs;
     const uint32_t *fmaps;   // per map: padded float layer [GSZ] then need_to_surround [XS*YS] as u32
     const float *vtab;       // fl32(k / layer_norm), k = 0..255
-    const uint32_t *codes;   // D entries: bit31 = relative to window origin, low bits = dword offset
+    const int32_t *pending;  // LShape kernels: the caller's pending agent counts [n_envs][2], read by resets (pending_count); unused otherwise
     // Host-built launch constants, so that the per-workgroup preamble is loads, not index arithmetic (every resident wavefront
     // runs it at the same moment, 2.8 us of a 78 us launch when it was computed in the kernel):
     const uint32_t *cnt_tmpl;  // [GSZ] an empty count layer: 0 inside the map, SENT outside
@@ -96,6 +96,11 @@ struct KArgs {
 };
 typedef const __attribute__((address_space(4))) KArgs *KArgsPtr;
 __device__ __forceinline__ KArgsPtr cold_args() { return kernargs<KArgs>(); }
+// pending count k (0 pursuers, 1 evaders) of an env (LShape kernels, resets only): a scalar load, like sload_f64
+__device__ __forceinline__ int32_t pending_count(int64_t env, int k) {
+    const int32_t *pend = cold_args()->d.pending;
+    return ((const __attribute__((address_space(4))) int32_t *)(uint64_t)pend)[2 * env + k];
+}
 
 template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
 struct Shape {
@@ -132,7 +137,18 @@ struct Shape {
     static_assert(D % 4 == 0, "observation row must be a whole number of float4");
     static_assert(LDS_DWORDS * 4 <= 64 * 1024, "LDS budget");
     static_assert(NS <= 8, "stale-zero mask: one bit per slot in each byte of the lane's mask dword");
+    static constexpr bool LIVE = false;
 };
+
+// Per-env agent counts (madrl_pursuit_set_agent_counts): the same geometry, with P and E as a CAPACITY.  An env runs LIVE p <= P
+// pursuers and e <= E evader slots; a slot that does not exist holds position byte 0xFF in the record (no coordinate is 255), so p
+// and e are the numbers of leading slots without it.  pursuit_wave_kernel<LShape<...>, ...> is a kernel of its own (the fixed-shape
+// instantiations keep their code and names); the shapes are listed in pursuit_live_specializations.def.
+template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
+struct LShape : Shape<XS_, YS_, P_, E_, R_, FLATTEN_> {
+    static constexpr bool LIVE = true;
+};
+constexpr int NOT_HERE = 0xFF;   // position byte of a slot that does not exist (live-count records)
 
 __device__ __forceinline__ double pairwise8(const double *r) {
     return ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
@@ -161,6 +177,36 @@ __device__ __forceinline__ double np_sum_regs(const double (&a)[P]) {
         for (int i = LIM; i < P; ++i) res += a[i];
         return res;
     }
+}
+
+// numpy's add.reduce order (np_sum_regs) over the first n <= P of P values in registers: the live-count kernel's global reward
+template <int P>
+__device__ __forceinline__ double np_sum_first(const double (&a)[P], int n) {
+    double res = 0.0;
+    if (n < 8) {
+#pragma unroll
+        for (int i = 0; i < (P < 8 ? P : 7); ++i)
+            if (i < n) res += a[i];
+        return res;
+    }
+    if constexpr (P >= 8) {
+        double r[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) r[i] = a[i];
+        const int lim = n - (n % 8);
+#pragma unroll
+        for (int i = 8; i + 8 <= P; i += 8) {
+            if (i < lim) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) r[k] += a[i + k];
+            }
+        }
+        res = pairwise8(r);
+#pragma unroll
+        for (int i = 8; i < P; ++i)
+            if (i >= lim && i < n) res += a[i];
+    }
+    return res;
 }
 
 // Masked global stores that are ALWAYS issued (exec narrowed inside the asm, no compiler-made skip branch around them): the
@@ -263,9 +309,14 @@ __device__ __forceinline__ void put_zero_from(uint32_t &w) {
 // evaders of the layer, the pursuers move by their controller (io.inj_eact [n_envs][P] or Philox, TAG_PURSUER_ACT), observation row k
 // shows the window of the k-th remaining evader among slots 0..P-1 and the rows past the last one stay untouched; rewards stay the
 // pursuers'.  Only instantiated for the FLEX step kernel and the reset kernel of shapes with E >= P.
+// S::LIVE (LShape) = per-env agent counts: the env's live (np, ne) come from its record (NOT_HERE slots);
+// pursuer lanes >= np do not move, are not counted, write no observation row (their stores stay issued, exec-masked, so that
+// VM_PER_ENV holds) and a 0 reward; evader slots >= ne are gone; a reset takes (np, ne) from the caller's pending counts and
+// numbers its draws in the live layout (evader i is agent np + i), so that the env is bit for bit env n of a fixed (np, ne) batch.
 template <class S, int MODE, bool INJECT, bool CTRL = false>
 __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const WaveDev d, const WaveIO io) {
     static_assert(!CTRL || (S::E >= S::P && (MODE == 0 || INJECT)), "evader control: n_evaders >= n_pursuers, flexible instantiation");
+    static_assert(!CTRL || !S::LIVE, "evader control has no per-env agent counts");
     constexpr int P = S::P, E = S::E, A = S::A, GW = S::GW, PAD = S::PAD, GSZ = S::GSZ, NS = S::NS;
     __shared__ __attribute__((aligned(16))) uint32_t L[S::LDS_DWORDS];
     const int lane = threadIdx.x;
@@ -306,6 +357,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
     for (int k = lane; k < GSZ; k += 64) L[k] = d.fmaps[k];
     for (int k = lane; k < (S::XS * S::YS + 3) / 4; k += 64) L[S::X_NEED + k] = d.fmaps[GSZ + k];
     int cached_map = 0;
+    int cached_np = P;  // live-count kernel: the pursuer count the id cells X_ID.. hold (k / np, :440-445)
     const uint8_t *need_tab = reinterpret_cast<const uint8_t *>(&L[S::X_NEED]);
     uint32_t *const layer = &L[is_p ? GSZ : 2 * GSZ];  // this lane's count layer
     // which lanes feed my dword of the packed state record (agents 2j and 2j+1 for dword 4+j)
@@ -387,11 +439,26 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
             if constexpr (S::NTW > 1) term |= (uint64_t)(uint32_t)__builtin_amdgcn_readlane(cur_rec, S::OFF_TERM / 4 + 1) << 32;
             const uint32_t gid = d.gid_base + (uint32_t)env;
             const uint32_t k0 = fresh_s(d.k0), k1 = fresh_s(d.k1);  // round keys recomputed on the SALU, not kept live
+            int np = P, ne = E;  // live pursuers / evader slots (LIVE; the capacity otherwise)
+            if constexpr (S::LIVE) {
+                const bool here = x != NOT_HERE;
+                np = __popcll(__builtin_amdgcn_ballot_w64(isP() && here));
+                ne = __popcll(__builtin_amdgcn_ballot_w64(isE() && here));
+                if (!here) {  // a slot that does not exist computes on cell (0, 0) and never stores there
+                    x = 0;
+                    y = 0;
+                }
+            }
+            // a pursuer of the running episode (LIVE: lane < np)
+            auto isLP = [&]() {
+                if constexpr (S::LIVE) return fresh(lane) < np;
+                else return isP();
+            };
             bool do_reset = (MODE == 0);
             uint32_t done_bits = 0;
             float rew_out = 0.0f;
             int n_removed = 0;
-            bool alive = isP() || (isE() && !((gone >> eslot) & 1ull));
+            bool alive = isLP() || (isE() && !((gone >> eslot) & 1ull));
             int cell = (x + PAD) * GW + y + PAD;
 
             auto load_map = [&](int mid) {
@@ -479,7 +546,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                 wave_sync();
                 // ---------------------------------------------------- rewards (:254-262)
                 double r = 0.0;
-                if (isP()) {
+                if (isLP()) {
                     const uint32_t *ec = &L[2 * GSZ];
                     bool sur;
                     if (d.surround) {  // a caught evader on one of my four neighbour cells (:489-495)
@@ -499,7 +566,8 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                     double all[P];
 #pragma unroll
                     for (int k = 0; k < P; ++k) all[k] = __shfl(r, k);
-                    r = np_sum_regs<P>(all) / (double)P;
+                    if constexpr (S::LIVE) r = isLP() ? np_sum_first<P>(all, np) / (double)np : 0.0;
+                    else r = np_sum_regs<P>(all) / (double)P;
                 }
                 tick += 1;
                 tstep += 1;
@@ -553,20 +621,28 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                     // random_opponents (train_pursuit, :177-181): n_create <= E evaders this episode, the slots above are not
                     // created and count as gone; an injected position with x < 0 marks a slot that is not created
                     int n_create = E;
+                    if constexpr (S::LIVE) {  // the pending counts take effect (clamped: the caller's array is not trusted with lanes)
+                        np = min(max(pending_count(env, 0), 1), P);
+                        ne = min(max(pending_count(env, 1), 0), E);
+                        n_create = ne;
+                    }
                     if (max_opponents > 0 && !inj_pos) {
                         const u32x4 r3 = philox4x32_10(gid, tick, 2u, TAG_RESET_ENV, k0, k1);
-                        n_create = min(1 + (int)__umulhi(r3.x, (uint32_t)(max_opponents - 1)), E);
+                        n_create = min(1 + (int)__umulhi(r3.x, (uint32_t)(max_opponents - 1)), S::LIVE ? ne : E);
                     }
                     bool exists = false;
                     if (isAgent()) {  // create_agents / feasible_position, agent_utils.py:12-47
-                        exists = isP() || eslot < n_create;
+                        if constexpr (S::LIVE) exists = isLP() || (!isP() && eslot < n_create);
+                        else exists = isP() || eslot < n_create;
                         if (inj_pos) {
                             x = io.inj_pos[(env * A + lane) * 2];
                             y = io.inj_pos[(env * A + lane) * 2 + 1];
                             if (!isP() && x < 0) exists = false;
                         } else {
                             for (uint32_t att = 0; att < 1024u; ++att) {
-                                const u32x4 rp = philox4x32_10(gid, tick, (uint32_t)lane, TAG_RESET_POS | (att << 8), k0, k1);
+                                // (LIVE: the agent's index in the live layout, evader i = agent np + i)
+                                const uint32_t aidx = S::LIVE ? (uint32_t)(isP() ? lane : np + eslot) : (uint32_t)lane;
+                                const u32x4 rp = philox4x32_10(gid, tick, aidx, TAG_RESET_POS | (att << 8), k0, k1);
                                 x = xlb + (int)__umulhi(rp.x, (uint32_t)(xub - xlb));
                                 y = ylb + (int)__umulhi(rp.y, (uint32_t)(yub - ylb));
                                 // building cells hold fl32(1/norm) != 0; window cells are inside the map
@@ -590,6 +666,13 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                 // ------------------------------------------------------ observations (:418-461)
                 // integer counts -> float32 observation values, in place (a wave executes the
                 // ds_read of every lane before the ds_write of any lane)
+                if constexpr (S::LIVE) {  // the id values k / np of this pass's pursuer count
+                    if (np != cached_np) {
+                        if (lane < P) L[S::X_ID + lane] = __float_as_uint((float)((double)lane / (double)np));
+                        cached_np = np;
+                        wave_sync();
+                    }
+                }
                 uint32_t cnt = 0;
                 if (alive) cnt = layer[cell] & 0xFFFFu;
                 wave_sync();
@@ -612,6 +695,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                         wave_sync();
                         origin = (isP() && lane < n_rows) ? (int)L[S::X_OBSV + lane] : 0;
                     }
+                    if constexpr (S::LIVE) n_rows = np;
                     // SGPR base + one loop-invariant 32-bit VGPR offset (+ immediate) for every store of the row
                     const char *orow_u = (const char *)uniform_ptr(io.obs + env * (int64_t)(P * S::D));
                     // if that base came through v_readfirstlane (a VALU write of an SGPR), a vector-memory instruction may read it as its
@@ -636,7 +720,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                         const uint32_t old4 = (zm >> (NS - 1 - s)) & 0x01010101u;          // holds a value not known to be zero
                         const uint32_t dirty = out4 & old4;                                 // outside AND possibly non-zero: must stay untouched
                         bool valid = (64 * (s + 1) <= S::NQ) ? true : (fresh(lane) + 64 * s < S::NQ);
-                        if constexpr (CTRL) {
+                        if constexpr (CTRL || S::LIVE) {
                             const bool row_live = (s_src[s] >> 2) < n_rows;   // rows of absent observers keep their contents -- and their flags
                             acc = (acc << 1) | (row_live ? ((out4 & old4) | (~out4 & nz4)) : old4);
                             valid = valid && row_live;
@@ -726,7 +810,10 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
             // ---------------------------------------------------------- registers -> state record
             // one coalesced dword store: lane k writes dword k of the record
             {
-                const int myxy = x | (y << 8);
+                int myxy = x | (y << 8);
+                if constexpr (S::LIVE) {
+                    if (!(isP() ? isLP() : eslot < ne)) myxy = NOT_HERE | (NOT_HERE << 8);
+                }
                 const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(rec_src0, myxy);
                 const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(rec_src1, myxy);
                 uint32_t w = (lo & 0xFFFFu) | (hi << 16);

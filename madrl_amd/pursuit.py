@@ -54,11 +54,15 @@ class PursuitAgent(Agent):
 class BatchedPursuitEvade(AbstractMAEnv):
 
     def __init__(self, map_pool, n_envs=1, device="cuda:0", seed=0, env_id_base=0, max_steps=0,
-                 auto_reset=False, threads=0, max_blocks=0, kernel="auto", **kwargs):
+                 auto_reset=False, threads=0, max_blocks=0, kernel="auto", per_env_counts=False, **kwargs):
         self._ctor = dict(map_pool=map_pool, n_envs=n_envs, device=str(device), seed=seed,
                           env_id_base=env_id_base, max_steps=max_steps, auto_reset=auto_reset,
                           threads=threads, max_blocks=max_blocks, kernel=kernel, kwargs=dict(kwargs))
+        if per_env_counts:   # (only when set: the pickles of fixed-shape batches stay what they were)
+            self._ctor["per_env_counts"] = True
         self._kernel = kernel
+        # per-env agent counts: n_pursuers / n_evaders are a capacity, each env runs its own live counts (set_agent_counts)
+        self.per_env_counts = bool(per_env_counts)
         kw = dict(_DEFAULTS)
         for k in list(kwargs):
             if k in ("ally_layer", "opponent_layer", "evader_controller", "pursuer_controller"):
@@ -75,6 +79,8 @@ class BatchedPursuitEvade(AbstractMAEnv):
             if int(kw["n_evaders"]) < int(kw["n_pursuers"]):
                 raise ValueError("train_pursuit=False: collect_obs indexes evaders_gone[i] for i < n_pursuers (:418-428); "
                                  "the reference raises IndexError in reset() when n_evaders < n_pursuers")
+            if per_env_counts:
+                raise NotImplementedError("per_env_counts=True with train_pursuit=False (evader control) is not supported")
         for k, v in kw.items():
             if k == "reward_mech":
                 self._reward_mech = v
@@ -159,6 +165,11 @@ class BatchedPursuitEvade(AbstractMAEnv):
         if getattr(self, "_obs_is_fresh", False):   # nothing has written the buffer yet: tell the fast path (no cell "unknown" at the start)
             _lib.check(L.madrl_pursuit_declare_obs_zero(h, _lib.ptr(self._obs), _lib.current_stream(self.device)))
         self.handle_generation = getattr(self, "handle_generation", 0) + 1   # how many times the native handle was (re-)created
+        if self.per_env_counts:   # pending counts [N, 2]: kept across re-created handles of the same capacity, at the capacity otherwise
+            if getattr(self, "_pending", None) is None or self._pending.shape[0] != N or self._pending_cap != (P, E):
+                self._pending = torch.tensor([P, E], dtype=torch.int32, device=self.device).repeat(N, 1).contiguous()
+                self._pending_cap = (P, E)
+            _lib.check(L.madrl_pursuit_set_agent_counts(h, _lib.ptr(self._pending)))
         if getattr(self, "_cw_env", None) is not None and self._cw_env.shape[0] == N:   # per-env curriculum follows the new handle
             _lib.check(L.madrl_pursuit_set_curriculum(h, _lib.ptr(self._cw_env), _lib.ptr(self._catchr_env)))
         else:
@@ -183,6 +194,14 @@ class BatchedPursuitEvade(AbstractMAEnv):
         from . import build as _build
         shape = (self.xs, self.ys, int(self.n_pursuers), int(self.n_evaders), int(self.obs_range), int(bool(self.flatten)))
         if shape in BatchedPursuitEvade._hinted or self.kernel_kind != "generic" or not self.train_pursuit and shape[2] + shape[3] > 64:
+            return
+        if self.per_env_counts:   # a capacity without a live-count instantiation
+            if _build.pursuit_fast_path(*shape, include_id=bool(self.include_id))[0] == "X":
+                import warnings
+                BatchedPursuitEvade._hinted.add(shape)
+                warnings.warn("PursuitEvade per-env agent counts at capacity %d v %d (%dx%d, obs_range %d) run on the generic kernel; an "
+                              "XL%s line in madrl_amd/csrc/pursuit_live_specializations.def (and a rebuild) gives them the one-wavefront "
+                              "kernel" % (shape[2], shape[3], shape[0], shape[1], shape[4], str(shape).replace(" ", "")), stacklevel=3)
             return
         kind, _ = _build.pursuit_fast_path(*shape, include_id=bool(self.include_id))
         if kind is not None:
@@ -361,8 +380,10 @@ class BatchedPursuitEvade(AbstractMAEnv):
     def obs_rows_valid(self):
         """bool [N, P]: which observation rows the last reset / step wrote.  All of them with train_pursuit; in evader control
         row k is the k-th remaining evader among slots 0..P-1 (pursuit_evade.py:418-428) and the rows past the last one are
-        stale."""
+        stale; with per-env agent counts the rows of the env's live pursuers (live_agents())."""
         N, P = self.n_envs, int(self.n_pursuers)
+        if self.per_env_counts:
+            return self.live_agents()
         if self.train_pursuit:
             return torch.ones((N, P), dtype=torch.bool, device=self.device)
         left = (self.get_state()["gone"][:, :P] == 0).sum(dim=1, keepdim=True)
@@ -422,7 +443,23 @@ class BatchedPursuitEvade(AbstractMAEnv):
         """pursuit_evade.py:264-272.  Without `mask`: the whole batch moves one curriculum iteration, like the reference object
         (the handle is re-created only when the agent counts change).  With `mask` (bool / uint8 [N]): only those env
         instances advance -- constraint_window and catchr become PER-ENV device arrays (`curriculum_state()`), read by the
-        kernels in place; the agent counts of a batch cannot differ per env, so the remove-agents rule is not applied then."""
+        kernels in place; the agent counts of a batch cannot differ per env, so the remove-agents rule is not applied then.
+        With per_env_counts=True the remove-agents rule (:268-270) applies per env to the PENDING counts of the env instances it
+        advances (every one without `mask`): they take effect at each env's next reset, and the handle is never re-created."""
+        if self.per_env_counts:
+            if mask is None and self._cw_env is None:   # constraint_window / catchr stay batch-wide scalars (set_params)
+                cw, _, _, cr = self.curriculum_next(itr, self.constraint_window, 0, 0, self.catchr, self.curriculum_constrain_rate,
+                                                    self.curriculum_remove_every, self.curriculum_turn_off_shaping)
+                self.constraint_window, self.catchr = cw, cr
+                self._apply_params()
+            else:
+                self._curriculum_env(itr, mask)
+            if itr != 0 and itr % self.curriculum_remove_every == 0:
+                m = self._env_mask(mask)
+                sel = (m & (self._pending[:, 0] > 4)).to(torch.int32)
+                self._pending[:, 0] -= sel
+                self._pending[:, 1] = (self._pending[:, 1] - sel).clamp_(min=0)
+            return
         if mask is None and self._cw_env is None:
             cw, ne, np_, cr = self.curriculum_next(itr, self.constraint_window, self.n_evaders, self.n_pursuers, self.catchr,
                                                    self.curriculum_constrain_rate, self.curriculum_remove_every,
@@ -430,9 +467,16 @@ class BatchedPursuitEvade(AbstractMAEnv):
             self.constraint_window, self.n_evaders, self.n_pursuers, self.catchr = cw, ne, np_, cr
             self._apply_params()
             return
-        self._bind_curriculum()
-        m = torch.ones(self.n_envs, dtype=torch.bool, device=self.device) if mask is None else \
+        self._curriculum_env(itr, mask)
+
+    def _env_mask(self, mask):
+        return torch.ones(self.n_envs, dtype=torch.bool, device=self.device) if mask is None else \
             torch.as_tensor(mask, device=self.device).reshape(self.n_envs).bool()
+
+    def _curriculum_env(self, itr, mask):
+        """constraint_window / catchr of :265-266 / :271-272 on the per-env arrays, for the env instances in `mask` (all: None)"""
+        self._bind_curriculum()
+        m = self._env_mask(mask)
         # the same float64 operations as :265-266 / :271-272, on the masked elements
         cw = torch.clamp(self._cw_env + float(self.curriculum_constrain_rate), 0.0, 1.0)
         self._cw_env.copy_(torch.where(m, cw, self._cw_env))
@@ -474,6 +518,39 @@ class BatchedPursuitEvade(AbstractMAEnv):
         _lib.check(_lib.lib().madrl_pursuit_invalidate_obs(self._handle))
         self._obs_is_fresh = False   # a re-created handle must not declare this buffer all-zero
 
+    # ------------------------------------------------------------------ per-env agent counts (per_env_counts=True)
+    def _require_counts(self, what):
+        if not self.per_env_counts:
+            raise RuntimeError("%s: this batch has one agent count for all envs; construct it with per_env_counts=True" % what)
+
+    def set_agent_counts(self, n_pursuers=None, n_evaders=None, mask=None):
+        """PENDING agent counts of the env instances in `mask` (all: None): an int or an int [N] per count.  Each env takes them at
+        its next reset (reset(mask=) or the auto-reset of a step); its running episode keeps its agents.  1 <= n_pursuers <=
+        the capacity self.n_pursuers, 0 <= n_evaders <= self.n_evaders."""
+        self._require_counts("set_agent_counts")
+        N, m = self.n_envs, self._env_mask(mask)
+        for col, v, lo, hi, name in ((0, n_pursuers, 1, int(self.n_pursuers), "n_pursuers"), (1, n_evaders, 0, int(self.n_evaders), "n_evaders")):
+            if v is None:
+                continue
+            t = torch.as_tensor(v, device=self.device).to(torch.int32)
+            t = t.expand(N) if t.dim() == 0 else t.reshape(N)
+            if bool((m & ((t < lo) | (t > hi))).any()):
+                raise ValueError("%s must be in %d..%d (the batch's capacity)" % (name, lo, hi))
+            self._pending[:, col] = torch.where(m, t, self._pending[:, col])
+
+    def agent_counts(self):
+        """(pending, live): int32 [N, 2] tensors of (pursuers, evaders) per env -- the counts the next reset takes, and those of the
+        running episode"""
+        self._require_counts("agent_counts")
+        live = torch.zeros((self.n_envs, 2), dtype=torch.int32, device=self.device)
+        _lib.check(_lib.lib().madrl_pursuit_get_live_counts(self._handle, _lib.ptr(live), self._stream()))
+        return self._pending.clone(), live
+
+    def live_agents(self):
+        """bool [N, P]: the pursuers of each env's running episode (rows / rewards / actions k >= its live count are not used)"""
+        live = self.agent_counts()[1]
+        return torch.arange(int(self.n_pursuers), device=self.device)[None, :] < live[:, :1]
+
     # ------------------------------------------------------------------ state exchange
     def get_state(self):
         N, P, E, dev = self.n_envs, int(self.n_pursuers), int(self.n_evaders), self.device
@@ -488,6 +565,8 @@ class BatchedPursuitEvade(AbstractMAEnv):
         _lib.check(_lib.lib().madrl_pursuit_get_state(
             self._handle, *[_lib.ptr(st[k]) for k in ("pos_p", "pos_e", "gone", "term_p", "term_e", "map_id", "tick", "t")],
             self._stream()))
+        if self.per_env_counts:   # pos_p of a pursuer that does not exist: (-1, -1)
+            st["pending"], st["live"] = self.agent_counts()
         return st
 
     def set_state(self, st):
@@ -507,6 +586,15 @@ class BatchedPursuitEvade(AbstractMAEnv):
             args.append(v)
         self._keepalive = args
         _lib.check(_lib.lib().madrl_pursuit_set_state(self._handle, *[_lib.ptr(a) for a in args], self._stream()))
+        if st.get("live") is not None or st.get("pending") is not None:
+            self._require_counts("set_state(live= / pending=)")
+        if st.get("live") is not None:   # after the positions: slots past the live counts stop existing
+            live = self._i32(st["live"], (N, 2), "live")
+            self._keepalive.append(live)
+            _lib.check(_lib.lib().madrl_pursuit_set_live_counts(self._handle, _lib.ptr(live), self._stream()))
+        if st.get("pending") is not None:
+            pend = self._i32(st["pending"], (N, 2), "pending")
+            self.set_agent_counts(pend[:, 0], pend[:, 1])
         self._obs_is_fresh = False
 
     @property
@@ -524,16 +612,21 @@ class BatchedPursuitEvade(AbstractMAEnv):
                                n_pursuers=self.n_pursuers, catchr=self.catchr)
         if self._cw_env is not None:   # the per-env curriculum (update_curriculum(itr, mask=) / set_curriculum) travels too
             d["curriculum_env"] = dict(constraint_window=self._cw_env.cpu().numpy(), catchr=self._catchr_env.cpu().numpy())
+        if self.per_env_counts:   # ... and the pending agent counts
+            d["agent_counts"] = self._pending.cpu().numpy()
         return d
 
     def __setstate__(self, d):
         cur = d.pop("curriculum", {})
         cur_env = d.pop("curriculum_env", None)
+        counts = d.pop("agent_counts", None)
         kwargs = d.pop("kwargs")
         kwargs.update(cur)
         self.__init__(d.pop("map_pool"), **d, **kwargs)
         if cur_env is not None:
             self.set_curriculum(**cur_env)
+        if counts is not None:
+            self.set_agent_counts(counts[:, 0], counts[:, 1])
 
 
 class PursuitEvade(SingleEnvDelegate, AbstractMAEnv):
