@@ -2,11 +2,12 @@
 
     python -m madrl_amd.build [--force]
     python -m madrl_amd.build --pursuit-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN      # give this shape the fast path, rebuild
+    python -m madrl_amd.build --pursuit-live-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN # ... and per-env agent counts at this capacity
     python -m madrl_amd.build --waterworld-shape N_PURSUERS N_EVADERS N_POISON N_SENSORS [OBS_DIM]
 
 The fast paths (one wavefront -- or a group of wavefronts -- per env, everything about the shape a compile-time constant) exist for the
 shapes listed in csrc/*_specializations.def: the BASELINE configurations, the reference's own runner / script defaults, the test shapes.
-Any other shape runs on the generic kernels, at about half the speed.  The two options above append a line to
+Any other shape runs on the generic kernels, at about half the speed.  The options above append a line to
 csrc/*_specializations.local.def (git-ignored, included after the committed list) and rebuild the one object that changed (~30 s).
 
 -ffp-contract=off: reward arithmetic and the reset window are float64 expressions that must
@@ -83,6 +84,30 @@ def add_pursuit_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
                          "XG(%s, %d)   // added by madrl_amd.build" % (args, nw))
 
 
+def pursuit_live_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True):
+    """-> (live line, fixed line) that give a per-env-counts capacity its fast path: XL(...) over an X(...) shape, XLG(..., NW) over an
+    XG(..., NW) shape -- or None when the capacity has no fast path at all (pursuit_fast_path says why).  Pure: nothing is written."""
+    kind, nw = pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
+    if kind is None:
+        return None
+    args = "%d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)))
+    if kind == "X":
+        return "XL(%s)" % args, "X(%s)" % args
+    return "XLG(%s, %d)" % (args, nw), "XG(%s, %d)" % (args, nw)
+
+
+def add_pursuit_live_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
+    """per-env agent counts at this capacity on the fast path: the live line in the local live list, and the fixed-shape line it stands on
+    in the local fixed list if it is missing"""
+    lines = pursuit_live_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten)
+    if lines is None:
+        raise ValueError("no fast path for this PursuitEvade capacity: %s (per-env agent counts run on the generic kernel)"
+                         % pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten)[1])
+    live, fixed = lines
+    added_fixed = _append_local("pursuit_specializations.def", fixed + "   // added by madrl_amd.build")
+    return _append_local("pursuit_live_specializations.def", live + "   // added by madrl_amd.build") or added_fixed
+
+
 def add_waterworld_shape(n_pursuers, n_evaders, n_poison, n_sensors, obs_dim=None):
     if obs_dim is None:
         obs_dim = n_sensors * 7 + 2 + 1          # speed features and the agent id (the reference's defaults)
@@ -156,7 +181,8 @@ def build(force=False, verbose=False):
 
 if __name__ == "__main__":
     argv = sys.argv[1:]
-    for flag, fn, lo, hi in (("--pursuit-shape", add_pursuit_shape, 6, 6), ("--waterworld-shape", add_waterworld_shape, 4, 5)):
+    for flag, fn, lo, hi in (("--pursuit-shape", add_pursuit_shape, 6, 6), ("--pursuit-live-shape", add_pursuit_live_shape, 6, 6),
+                             ("--waterworld-shape", add_waterworld_shape, 4, 5)):
         while flag in argv:
             i = argv.index(flag)
             vals = []

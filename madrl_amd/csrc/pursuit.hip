@@ -367,12 +367,18 @@ const WaveEntry *find_wave(const madrl_pursuit_config *c) {
     return nullptr;
 }
 
-// (wave_launch of an LShape: no evader-control instantiations, madrl_pursuit_set_agent_counts refuses control_evaders)
+// (wave_launch of an LShape: no evader-control instantiations, madrl_pursuit_set_agent_counts refuses control_evaders; the group kernels
+// of the XLG lines are compiled in pursuit_live_group.hip)
 #define XL(XS, YS, NP, NE, R, FL) {wave_geom<pw::LShape<XS, YS, NP, NE, R, FL>>(1, pw::LShape<XS, YS, NP, NE, R, FL>::OCC), wave_launch<pw::LShape<XS, YS, NP, NE, R, FL>>},
+#define XLG(XS, YS, NP, NE, R, FL, NW) {wave_geom<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>(NW, pw::LGShape<XS, YS, NP, NE, R, FL, NW>::OCC), pw::live_group_launch<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>},
 const WaveEntry LIVE_TABLE[] = {
 #include "pursuit_live_specializations.def"
+#if __has_include("pursuit_live_specializations.local.def")   // capacities added on this machine by `python -m madrl_amd.build --pursuit-live-shape ...` (git-ignored)
+#include "pursuit_live_specializations.local.def"
+#endif
 };
 #undef XL
+#undef XLG
 
 // the live-count instantiation matching a shape whose fixed-shape entry `w` the handle uses (same geometry, same tables)
 const WaveEntry *find_live(const WaveEntry *w) {

@@ -24,6 +24,11 @@
 // 64-byte chunks), but its constants come from a table in LDS indexed by the float4's position f = q mod DV inside its row -- four
 // 15-bit dword offsets relative to the window origin, packed in two dwords, identical for every pursuer -- and (pursuer, f) advance
 // from slot to slot by constants.  The stale-zero mask grows to MWORDS = ceil(NS / 8) dwords per thread (one bit per slot in each byte).
+//
+// PER-ENV AGENT COUNTS (LGShape, pursuit_live_specializations.def XLG lines): the LShape contract of pursuit_wave.hpp carried over.  The
+// agents span wavefronts, so the live (np, ne) are counted from the record that EVERY wavefront holds whole (dword k in lane k), not from
+// a ballot of the agent lanes: all NW wavefronts agree on them without a barrier.  Rows k >= np are not stored (their store branches stay,
+// taken by no lane), and their stale-zero mask bits are kept.
 #pragma once
 
 #include "pursuit_wave.hpp"
@@ -82,7 +87,20 @@ struct GShape {
     static constexpr int OCC = OCC_LDS < MADRL_PG_WAVES ? (OCC_LDS < 1 ? 1 : OCC_LDS) : MADRL_PG_WAVES;
     static_assert(MWORDS <= 4, "at most 32 float4 slots per thread");
     static_assert(!TABLED || 3 * GSZ + 2 + P < 32768, "TABLED: dword offsets of the layers must fit 15 bits");
+    static constexpr bool LIVE = false;
 };
+
+// Per-env agent counts on the group kernel: the same geometry with P and E as a capacity (see LShape in pursuit_wave.hpp).
+// pursuit_group_kernel<LGShape<...>, ...> is a kernel of its own, instantiated in pursuit_live_group.hip.
+template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_, int NW_>
+struct LGShape : GShape<XS_, YS_, P_, E_, R_, FLATTEN_, NW_> {
+    static constexpr bool LIVE = true;
+};
+
+// host launcher of an LGShape kernel: explicitly instantiated in pursuit_live_group.hip, one per XLG line, so that these kernels
+// compile in a translation unit of their own
+template <class S>
+void live_group_launch(const WaveDev &d, const WaveIO &io, int mode, int64_t blocks, hipStream_t s);
 
 // LDS-only workgroup barrier: the DS queue of this wavefront is drained, global stores stay in flight.
 __device__ __forceinline__ void group_sync() {
@@ -135,6 +153,7 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
     for (int k = tid; k < GSZ; k += NT) L[k] = d.fmaps[k];
     for (int k = tid; k < (S::XS * S::YS + 3) / 4; k += NT) L[S::X_NEED + k] = d.fmaps[GSZ + k];
     int cached_map = 0;
+    int cached_np = P;  // LIVE: the pursuer count the id cells X_ID.. hold (k / np, :440-445)
     const uint8_t *need_tab = reinterpret_cast<const uint8_t *>(&L[S::X_NEED]);
     uint32_t *const layer = &L[is_p ? GSZ : 2 * GSZ];
     // record dword k (held by lane k of every wavefront) is STORED by one wavefront: the agent-pair dwords by the
@@ -234,11 +253,30 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
             }
             const uint32_t gid = d.gid_base + (uint32_t)env;
             const uint32_t k0 = fresh_s(d.k0), k1 = fresh_s(d.k1);
+            int np = P, ne = E;  // live pursuers / evader slots (LIVE; the capacity otherwise)
+            if constexpr (S::LIVE) {
+                // from the record, which every wavefront holds whole: dword 4 + j = agents 2j (low half) and 2j + 1 (high half)
+                const int a0 = 2 * (lane - 4);
+                const bool in_xy = lane >= 4 && lane < XY_END;
+                const bool h0 = in_xy && (cur_rec & 0xFFu) != (uint32_t)NOT_HERE;
+                const bool h1 = in_xy && a0 + 1 < A && ((cur_rec >> 16) & 0xFFu) != (uint32_t)NOT_HERE;
+                np = __popcll(__builtin_amdgcn_ballot_w64(h0 && a0 < P)) + __popcll(__builtin_amdgcn_ballot_w64(h1 && a0 + 1 < P));
+                ne = __popcll(__builtin_amdgcn_ballot_w64(h0 && a0 >= P)) + __popcll(__builtin_amdgcn_ballot_w64(h1 && a0 + 1 >= P));
+                if (x == NOT_HERE) {  // a slot that does not exist computes on cell (0, 0) and never stores there
+                    x = 0;
+                    y = 0;
+                }
+            }
+            // a pursuer of the running episode (LIVE: tid < np)
+            auto isLP = [&]() {
+                if constexpr (S::LIVE) return fresh(tid) < np;
+                else return isP();
+            };
             bool do_reset = (MODE == 0);
             uint32_t done_bits = 0;
             float rew_out = 0.0f;
             int n_removed = 0;
-            bool alive = isP() || (isE() && !((gone >> (eslot & 63)) & 1ull));
+            bool alive = isLP() || (isE() && !((gone >> (eslot & 63)) & 1ull));
             int cell = (x + PAD) * GW + y + PAD;
 
             auto load_map = [&](int mid) {
@@ -310,7 +348,7 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                 if constexpr (S::NAW == 1) group_sync();
                 // ---------------------------------------------------- rewards (:254-262)
                 double r = 0.0;
-                if (isP()) {
+                if (isLP()) {
                     const uint32_t *ec = &L[2 * GSZ];
                     bool sur;
                     if (d.surround) {
@@ -330,7 +368,8 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                     double all[P];
 #pragma unroll
                     for (int k = 0; k < P; ++k) all[k] = __shfl(r, k);
-                    r = np_sum_regs<P>(all) / (double)P;
+                    if constexpr (S::LIVE) r = isLP() ? np_sum_first<P>(all, np) / (double)np : 0.0;
+                    else r = np_sum_regs<P>(all) / (double)P;
                 }
                 tick += 1;
                 tstep += 1;
@@ -377,20 +416,28 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                     const int xlb = (int)(S::XS * sx), xub = (int)(S::XS * (sx + cw));
                     const int ylb = (int)(S::YS * sy), yub = (int)(S::YS * (sy + cw));
                     int n_create = E;
+                    if constexpr (S::LIVE) {  // the pending counts take effect, clamped as in the wave kernel
+                        np = min(max(pending_count(env, 0), 1), P);
+                        ne = min(max(pending_count(env, 1), 0), E);
+                        n_create = ne;
+                    }
                     if (max_opponents > 0 && !inj_pos) {
                         const u32x4 r3 = philox4x32_10(gid, tick, 2u, TAG_RESET_ENV, k0, k1);
-                        n_create = min(1 + (int)__umulhi(r3.x, (uint32_t)(max_opponents - 1)), E);
+                        n_create = min(1 + (int)__umulhi(r3.x, (uint32_t)(max_opponents - 1)), S::LIVE ? ne : E);
                     }
                     bool exists = false;
                     if (isAgent()) {
-                        exists = isP() || eslot < n_create;
+                        if constexpr (S::LIVE) exists = isLP() || (!isP() && eslot < n_create);
+                        else exists = isP() || eslot < n_create;
                         if (inj_pos) {
                             x = io.inj_pos[(env * A + tid) * 2];
                             y = io.inj_pos[(env * A + tid) * 2 + 1];
                             if (!isP() && x < 0) exists = false;
                         } else {
                             for (uint32_t att = 0; att < 1024u; ++att) {
-                                const u32x4 rp = philox4x32_10(gid, tick, (uint32_t)tid, TAG_RESET_POS | (att << 8), k0, k1);
+                                // (LIVE: the agent's index in the live layout, evader i = agent np + i)
+                                const uint32_t aidx = S::LIVE ? (uint32_t)(isP() ? tid : np + eslot) : (uint32_t)tid;
+                                const u32x4 rp = philox4x32_10(gid, tick, aidx, TAG_RESET_POS | (att << 8), k0, k1);
                                 x = xlb + (int)__umulhi(rp.x, (uint32_t)(xub - xlb));
                                 y = ylb + (int)__umulhi(rp.y, (uint32_t)(yub - ylb));
                                 if (L[(x + PAD) * GW + y + PAD] == 0u) break;
@@ -411,6 +458,12 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                     if constexpr (S::NAW == 1) group_sync();
                 }
                 // ------------------------------------------------------ observations (:418-461)
+                if constexpr (S::LIVE) {  // the id values k / np of this pass's pursuer count (np is the same in every wavefront; the
+                    if (np != cached_np) {  // two barriers below publish the cells before the row pass reads them)
+                        if (tid < P) L[S::X_ID + tid] = __float_as_uint((float)((double)tid / (double)np));
+                        cached_np = np;
+                    }
+                }
                 uint32_t cnt = 0;
                 if (alive) cnt = layer[cell] & 0xFFFFu;
                 group_sync();
@@ -426,14 +479,20 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                     for (int w = 0; w < MW; ++w) acc[w] = 0u;
                     // what happens to the four cells of one slot (stale-zero mask: see pursuit_wave.hpp).  Slot s = bit (slots of its word - 1 - s % 8)
                     // of every byte of mask word s / 8; `wc` is that word (a compile-time index: the words live in registers), `sh` the bit
-                    auto finish_slot = [&](auto wc, int sh, int q, bool valid, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3) {
+                    // row_live (LIVE): the slot's pursuer is < np.  Rows of absent pursuers keep their contents -- and their mask bits
+                    auto finish_slot = [&](auto wc, int sh, int q, bool valid, bool row_live, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3) {
                         constexpr int w = decltype(wc)::value;
                         const uint32_t top = __builtin_amdgcn_perm(v1, v0, 0x0C0C0703u) | __builtin_amdgcn_perm(v3, v2, 0x07030C0Cu);
                         const uint32_t out4 = (top >> 7) & 0x01010101u;
                         const uint32_t nz4 = ((top >> 5) | (top >> 6)) & 0x01010101u;
                         const uint32_t old4 = (zm[w] >> sh) & 0x01010101u;
                         const uint32_t dirty = out4 & old4;
-                        acc[w] = (acc[w] << 1) | (dirty | (~out4 & nz4));
+                        if constexpr (S::LIVE) {
+                            acc[w] = (acc[w] << 1) | (row_live ? (dirty | (~out4 & nz4)) : old4);
+                            valid = valid && row_live;
+                        } else {
+                            acc[w] = (acc[w] << 1) | (dirty | (~out4 & nz4));
+                        }
                         if (valid) {
                             if (dirty == 0u) {
                                 if (out4 != 0x01010101u) {
@@ -470,7 +529,7 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                                 const int b3 = ((int)t.y < 0) ? 0 : base;
                                 const int id3 = (t.y & 0x8000u) ? pp : 0;
                                 const uint32_t v3 = cell_b(b3 + (int)((((t.y >> 16) & 0x7FFFu) + (uint32_t)id3) << 2));
-                                finish_slot(wc, nsw - 1 - i, q, valid, v0, v1, v2, v3);
+                                finish_slot(wc, nsw - 1 - i, q, valid, pp < np, v0, v1, v2, v3);
                                 q += NT;
                                 fq += NT % S::DV;
                                 pq += NT / S::DV;
@@ -487,7 +546,7 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                             const uint32_t v1 = L[base + s_cst[s][1]];
                             const uint32_t v2 = L[base + s_cst[s][2]];
                             const uint32_t v3 = L[(int)__umul24((uint32_t)base, (uint32_t)s_rel3[s]) + s_cst[s][3]];
-                            finish_slot(std::integral_constant<int, 0>{}, NS - 1 - s, q, valid, v0, v1, v2, v3);
+                            finish_slot(std::integral_constant<int, 0>{}, NS - 1 - s, q, valid, s_org[s] - S::X_ORG < np, v0, v1, v2, v3);
                         });
                     }
 #pragma unroll
@@ -507,7 +566,10 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
             }
             // ---------------------------------------------------------- registers -> state record
             {
-                const int myxy = x | (y << 8);
+                int myxy = x | (y << 8);
+                if constexpr (S::LIVE) {
+                    if (!(isP() ? isLP() : eslot < ne)) myxy = NOT_HERE | (NOT_HERE << 8);
+                }
                 const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(rec_src0, myxy);
                 const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(rec_src1, myxy);
                 uint32_t w = (lo & 0xFFFFu) | (hi << 16);

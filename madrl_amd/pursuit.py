@@ -196,12 +196,15 @@ class BatchedPursuitEvade(AbstractMAEnv):
         if shape in BatchedPursuitEvade._hinted or self.kernel_kind != "generic" or not self.train_pursuit and shape[2] + shape[3] > 64:
             return
         if self.per_env_counts:   # a capacity without a live-count instantiation
-            if _build.pursuit_fast_path(*shape, include_id=bool(self.include_id))[0] == "X":
+            lines = _build.pursuit_live_lines(*shape, include_id=bool(self.include_id))
+            if lines is not None:
                 import warnings
                 BatchedPursuitEvade._hinted.add(shape)
-                warnings.warn("PursuitEvade per-env agent counts at capacity %d v %d (%dx%d, obs_range %d) run on the generic kernel; an "
-                              "XL%s line in madrl_amd/csrc/pursuit_live_specializations.def (and a rebuild) gives them the one-wavefront "
-                              "kernel" % (shape[2], shape[3], shape[0], shape[1], shape[4], str(shape).replace(" ", "")), stacklevel=3)
+                warnings.warn("PursuitEvade per-env agent counts at capacity %d v %d (%dx%d, obs_range %d) run on the generic kernel; the line "
+                              "%s in madrl_amd/csrc/pursuit_live_specializations.def (and a rebuild: `python -m madrl_amd.build "
+                              "--pursuit-live-shape %s`) gives them the %s kernel"
+                              % (shape[2], shape[3], shape[0], shape[1], shape[4], lines[0].replace(" ", ""), " ".join(str(v) for v in shape),
+                                 "one-wavefront" if lines[0].startswith("XL(") else "multi-wavefront"), stacklevel=3)
             return
         kind, _ = _build.pursuit_fast_path(*shape, include_id=bool(self.include_id))
         if kind is not None:
