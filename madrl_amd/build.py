@@ -3,6 +3,7 @@
     python -m madrl_amd.build [--force]
     python -m madrl_amd.build --pursuit-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN      # give this shape the fast path, rebuild
     python -m madrl_amd.build --pursuit-live-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN # ... and per-env agent counts at this capacity
+    python -m madrl_amd.build --pursuit-crowd-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN # more than 64 pursuers or evaders: the crowd kernel
     python -m madrl_amd.build --waterworld-shape N_PURSUERS N_EVADERS N_POISON N_SENSORS [OBS_DIM]
 
 The fast paths (one wavefront -- or a group of wavefronts -- per env, everything about the shape a compile-time constant) exist for the
@@ -64,6 +65,47 @@ def pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include
     return ("X", None) if nw == 1 else ("XG", nw)
 
 
+def pursuit_crowd_lds_bytes(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
+    """the static LDS of the crowd kernel's workgroup (CShape::LDS_DWORDS, pursuit_crowd.hpp): one dword per cell of the padded map, the value
+    table, the agents' bytes and words"""
+    P, E, R = int(n_pursuers), int(n_evaders), int(obs_range)
+    A = P + E
+    up = lambda v, a: (v + a - 1) // a * a
+    pad = max((R - 1) // 2, 1)
+    D = 3 * R * R + 1 if flatten else 4 * R * R
+    ngw, ntw = max((E + 31) // 32, 1), (A + 31) // 32
+    dwords = (up((xs + 2 * pad) * (ys + 2 * pad), 16) + 256 + (up(D, 4) if flatten else 0) + 2 * up(P, 2) + 2 * up(P, 4) + 2 * up(ngw, 4) +
+              up(ntw, 4) + 8 + 2 * up(A, 16) // 4)
+    return 4 * dwords
+
+
+def pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True):
+    """-> ("XC", NW): the crowd kernel (pursuit_crowd.hpp: agents looped over the threads of NW wavefronts, any count up to 1 023 of a kind)
+    can be compiled for this shape, or (None, why not): the static_asserts of CShape, evaluated here.  It says nothing about the X / XG fast
+    paths (pursuit_fast_path): a shape that has one of those keeps it."""
+    xs, ys, P, E, R = int(xs), int(ys), int(n_pursuers), int(n_evaders), int(obs_range)
+    if R % 2 == 0:
+        return None, "even obs_range"
+    if flatten and not include_id:
+        return None, "flatten without the id: rows are not whole float4s"
+    if not (1 <= P <= 1023 and 0 <= E <= 1023):
+        return None, "more than 1 023 pursuers or evaders"
+    if not (1 <= xs <= 255 and 1 <= ys <= 255):
+        return None, "coordinates above 255 do not fit the bytes of the state record"
+    D = 3 * R * R + 1 if flatten else 4 * R * R
+    if D % 4:
+        return None, "observation row is not a whole number of float4"
+    lds = pursuit_crowd_lds_bytes(xs, ys, P, E, R, flatten)
+    if lds > 160 * 1024:
+        return None, "map too large for the LDS cells (%d bytes, a workgroup may declare 163 840)" % lds
+    # wavefronts per env.  Short rows: one or two -- the dynamics are a chain of a dozen barriers, and many small workgroups per CU hide it
+    # better than few large ones (measured, scripts/crowd_time.py at 16 384 envs: 20 v 300 on 24 x 24 takes 207 us per step with four
+    # wavefronts, 184 with one).  Long rows: eight while three such workgroups fit a CU, sixteen when the cells of one env fill most of
+    # it (occupancy then comes from the workgroup itself)
+    slots = P * (D // 4)
+    return "XC", (1 if slots <= 2048 else 2 if slots <= 8192 else (8 if lds <= 40 * 1024 else 16))
+
+
 def _append_local(def_name, line):
     path = os.path.join(CSRC, def_name.replace(".def", ".local.def"))
     committed = open(os.path.join(CSRC, def_name)).read() + (open(path).read() if os.path.exists(path) else "")
@@ -82,6 +124,14 @@ def add_pursuit_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
     args = "%d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)))
     return _append_local("pursuit_specializations.def", "X(%s)   // added by madrl_amd.build" % args if kind == "X" else
                          "XG(%s, %d)   // added by madrl_amd.build" % (args, nw))
+
+
+def add_pursuit_crowd_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
+    kind, nw = pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten)
+    if kind is None:
+        raise ValueError("no crowd kernel for this PursuitEvade shape: %s (it runs on the generic kernel)" % nw)
+    return _append_local("pursuit_crowd_specializations.def", "XC(%d, %d, %d, %d, %d, %d, %d)   // added by madrl_amd.build"
+                         % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)), nw))
 
 
 def pursuit_live_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True):
@@ -182,6 +232,7 @@ def build(force=False, verbose=False):
 if __name__ == "__main__":
     argv = sys.argv[1:]
     for flag, fn, lo, hi in (("--pursuit-shape", add_pursuit_shape, 6, 6), ("--pursuit-live-shape", add_pursuit_live_shape, 6, 6),
+                             ("--pursuit-crowd-shape", add_pursuit_crowd_shape, 6, 6),
                              ("--waterworld-shape", add_waterworld_shape, 4, 5)):
         while flag in argv:
             i = argv.index(flag)

@@ -20,6 +20,7 @@
 #include "common.hpp"
 #include "pursuit_wave.hpp"
 #include "pursuit_group.hpp"
+#include "pursuit_crowd.hpp"
 
 #include <new>
 #include <stdlib.h>
@@ -257,6 +258,7 @@ __global__ void pursuit_live_counts_kernel(const PursuitDev d, int32_t *pos_p, i
 
 // =================================================================== host side / C ABI
 struct WaveEntry;  // one compiled specialisation of pursuit_wave_kernel
+struct CrowdEntry; // one compiled specialisation of pursuit_crowd_kernel
 
 struct madrl_pursuit {
     madrl_pursuit_config cfg;
@@ -280,6 +282,10 @@ struct madrl_pursuit {
     int kernel_kind;  // MADRL_KERNEL_AUTO / _GENERIC / _WAVE (requested)
     const int32_t *pending = nullptr;      // per-env agent counts (madrl_pursuit_set_agent_counts): caller-owned int32 [n_envs][2], or off
     const WaveEntry *wave_live = nullptr;  // the live-count instantiation of this shape (pursuit_live_specializations.def), if compiled
+    // the crowd kernel (pursuit_crowd.hpp): shapes above 64 of a kind that have an XC line and no X / XG line.  It shares the generic
+    // kernel's tables; `zmask` is then one word per env: "channel 3 of the env's rows is not known to hold +0.0"
+    const CrowdEntry *crowd = nullptr;
+    madrl::pc::CrowdDev cdev;
     hipEvent_t ev_fork = nullptr, ev_done = nullptr;   // madrl_pursuit_step_sharded: made by madrl_pursuit_create on the handle's device, destroyed with the handle
 };
 
@@ -364,6 +370,44 @@ const WaveEntry *find_wave(const madrl_pursuit_config *c) {
             g.flatten == (c->flatten ? 1 : 0))
             return &e;
     }
+    return nullptr;
+}
+
+// ------------------------------------------------------------------ crowd-kernel specialisations
+}  // namespace
+
+struct CrowdEntry {
+    int xs, ys, P, E, R, flatten;
+    int GSZ, D, rec_bytes, off_gone, off_term;
+    int nw;         // wavefronts per workgroup (= per env)
+    int lds_bytes;  // static LDS of the workgroup
+    void (*launch)(const madrl::pc::CrowdDev &, const madrl::pc::CrowdIO &, int mode, int64_t blocks, hipStream_t s);
+};
+
+namespace {
+
+template <class S>
+constexpr CrowdEntry crowd_entry() {
+    return CrowdEntry{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN, S::GSZ, S::D, S::REC_BYTES, S::OFF_GONE, S::OFF_TERM, S::NW,
+                      S::LDS_DWORDS * 4, pc::crowd_launch<S>};
+}
+
+#define XC(XS, YS, NP, NE, R, FL, NW) crowd_entry<pc::CShape<XS, YS, NP, NE, R, FL, NW>>(),
+const CrowdEntry CROWD_TABLE[] = {
+#include "pursuit_crowd_specializations.def"
+#if __has_include("pursuit_crowd_specializations.local.def")   // shapes added on this machine by `python -m madrl_amd.build --pursuit-crowd-shape ...` (git-ignored)
+#include "pursuit_crowd_specializations.local.def"
+#endif
+};
+#undef XC
+
+// looked at only for shapes without an X / XG line: a shape that has one keeps the kernel it has.  Evader control runs on the generic kernel.
+const CrowdEntry *find_crowd(const madrl_pursuit_config *c) {
+    if ((c->flatten && !c->include_id) || c->control_evaders || find_wave(c)) return nullptr;
+    for (const CrowdEntry &e : CROWD_TABLE)
+        if (e.xs == c->xs && e.ys == c->ys && e.P == c->n_pursuers && e.E == c->n_evaders && e.R == c->obs_range &&
+            e.flatten == (c->flatten ? 1 : 0))
+            return &e;
     return nullptr;
 }
 
@@ -488,7 +532,12 @@ void launch_nt(const madrl_pursuit *h, const PursuitIO &io, int mode, hipStream_
 
 // the fast path this handle can use in its current mode (per-env agent counts: the live-count instantiation)
 bool has_wave(const madrl_pursuit *h) {
-    return h->pending ? h->wave_live != nullptr : h->wave != nullptr;
+    return h->pending ? h->wave_live != nullptr : (h->wave != nullptr || h->crowd != nullptr);
+}
+
+// bytes of what the fast path remembers about the observation buffer (behind the records in the caller's state buffer)
+size_t zmask_len(const madrl_pursuit *h) {
+    return h->crowd ? (size_t)h->dev.n_envs * 4 : (size_t)h->dev.n_envs * 256 * h->wave->g.waves * h->wave->g.mwords;
 }
 
 bool use_wave(const madrl_pursuit *h) {
@@ -497,6 +546,25 @@ bool use_wave(const madrl_pursuit *h) {
 
 int launch(madrl_pursuit *h, const PursuitIO &io, int mode, void *stream) {
     hipStream_t s = (hipStream_t)stream;
+    if (use_wave(h) && h->crowd) {   // (per-env agent counts never get here: a crowd shape has no live-count instantiation)
+        pc::CrowdIO c;
+        c.mask = io.mask; c.inj_pos = io.inj_pos; c.inj_map = io.inj_map; c.actions = io.actions;
+        c.inj_eact = io.inj_eact; c.obs = io.obs; c.rew = io.rew; c.done = io.done; c.removed = io.removed;
+        // persistent workgroups, as many as are resident: the LDS of a workgroup and 24 wavefronts per CU (at most 85 registers per lane;
+        // a 16-wavefront workgroup may use 128 and is alone on its CU anyway)
+        const int by_lds = 160 * 1024 / h->crowd->lds_bytes, by_waves = 24 / h->crowd->nw > 0 ? 24 / h->crowd->nw : 1;
+        int64_t blocks = h->max_blocks > 0 ? h->max_blocks : 256 * (int64_t)(by_lds < by_waves ? by_lds : by_waves);
+        if (blocks > h->dev.n_envs) blocks = h->dev.n_envs;
+        pc::CrowdDev cd = h->cdev;
+        cd.catchr = h->dev.catchr; cd.cw = h->dev.cw; cd.cw_env = h->dev.cw_env; cd.catchr_env = h->dev.catchr_env;  // curriculum
+        if (h->zmask_obs != (const void *)io.obs) {  // unknown buffer contents: no env's channel 3 is known to be zero
+            MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0xFF, zmask_len(h), s));
+            h->zmask_obs = io.obs;
+        }
+        h->crowd->launch(cd, c, mode, blocks, s);
+        MADRL_HIP_TRY(hipGetLastError());
+        return MADRL_OK;
+    }
     if (use_wave(h)) {
         pw::WaveIO w;
         w.mask = io.mask; w.inj_pos = io.inj_pos; w.inj_map = io.inj_map; w.actions = io.actions;
@@ -547,6 +615,7 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, void *stream) {
 uint64_t zmask_offset(int rec_bytes, int64_t n_envs) { return align_up((uint64_t)rec_bytes * (uint64_t)n_envs, 256); }
 uint64_t zmask_bytes(const madrl_pursuit_config *cfg, int64_t n_envs) {
     const WaveEntry *w = find_wave(cfg);
+    if (!w && find_crowd(cfg)) return (uint64_t)n_envs * 4u;   // the crowd kernel: one word per env
     return w ? (uint64_t)n_envs * 256u * (uint64_t)w->g.waves * (uint64_t)w->g.mwords : 0u;
 }
 uint64_t flags_offset(const madrl_pursuit_config *cfg, int rec_bytes, int64_t n_envs) { return zmask_offset(rec_bytes, n_envs) + zmask_bytes(cfg, n_envs); }
@@ -817,6 +886,25 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
         }
     }
     h->wave_live = find_live(h->wave);
+    // ---- the crowd kernel: the generic kernel's tables and record, when the compiled geometry is this configuration's
+    h->crowd = find_crowd(cfg);
+    if (h->crowd && !(h->crowd->GSZ == d.GSZ && h->crowd->D == d.D && h->crowd->rec_bytes == d.rec_bytes &&
+                      h->crowd->off_gone == d.off_gone && h->crowd->off_term == d.off_term))
+        h->crowd = nullptr;
+    if (h->crowd) {
+        pc::CrowdDev &c = h->cdev;
+        memset(&c, 0, sizeof(c));
+        c.n_catch = d.n_catch; c.surround = d.surround; c.reward_global = d.reward_global; c.sample_maps = d.sample_maps;
+        c.n_maps = d.n_maps; c.max_steps = d.max_steps; c.auto_reset = d.auto_reset; c.max_opponents = d.max_opponents;
+        c.map_stride = d.map_stride;
+        c.k0 = d.k0; c.k1 = d.k1; c.gid_base = d.gid_base;
+        c.catchr = d.catchr; c.term_pursuit = d.term_pursuit; c.urgency = d.urgency; c.cw = d.cw;
+        c.n_envs = d.n_envs;
+        c.maps = d.maps; c.vtab = d.vtab;
+        c.state = d.state; c.flags = d.flags;
+        h->zmask = (uint8_t *)state_dev + zmask_offset(d.rec_bytes, n_envs);  // caller-owned, like the records
+        c.ch3 = reinterpret_cast<const uint32_t *>(h->zmask);
+    }
 
     h->walk_mode = 0;
     h->max_blocks = 0;
@@ -888,7 +976,7 @@ int madrl_pursuit_set_kernel(madrl_pursuit *h, int32_t kind) {
     if (kind == MADRL_KERNEL_WAVE && h->pending && !h->wave_live)
         return fail(MADRL_EINVAL, "per-env agent counts: no live-count specialisation was compiled for this capacity "
                     "(see madrl_amd/csrc/pursuit_live_specializations.def)");
-    if (kind == MADRL_KERNEL_WAVE && !h->wave)
+    if (kind == MADRL_KERNEL_WAVE && !h->wave && !h->crowd)
         return fail(MADRL_EINVAL, "no one-wavefront-per-env specialisation was compiled for this configuration "
                     "(see madrl_amd/csrc/pursuit_specializations.def)");
     h->kernel_kind = kind;
@@ -998,7 +1086,7 @@ int madrl_pursuit_invalidate_obs(madrl_pursuit *h) {
 int madrl_pursuit_declare_obs_zero(madrl_pursuit *h, const float *obs_dev, void *stream) {
     if (!h || !obs_dev) return fail(MADRL_EINVAL, "declare_obs_zero: NULL argument");
     if (h->zmask) {   // every cell of that buffer is known to hold +0.0f: no stale cell can need protecting
-        MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0, (size_t)h->dev.n_envs * 256 * h->wave->g.waves * h->wave->g.mwords, (hipStream_t)stream));
+        MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0, zmask_len(h), (hipStream_t)stream));
         h->zmask_obs = obs_dev;
     }
     return MADRL_OK;

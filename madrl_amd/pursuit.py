@@ -207,6 +207,13 @@ class BatchedPursuitEvade(AbstractMAEnv):
                                  "one-wavefront" if lines[0].startswith("XL(") else "multi-wavefront"), stacklevel=3)
             return
         kind, _ = _build.pursuit_fast_path(*shape, include_id=bool(self.include_id))
+        if kind is None and self.train_pursuit and _build.pursuit_crowd_path(*shape, include_id=bool(self.include_id))[0] is not None:
+            import warnings   # more than 64 of a kind: only the crowd kernel can take the shape
+            BatchedPursuitEvade._hinted.add(shape)
+            warnings.warn("PursuitEvade %dx%d, %d v %d, obs_range %d runs on the generic kernel; `python -m madrl_amd.build --pursuit-crowd-shape "
+                          "%s` compiles the crowd kernel for this shape (results are identical, a step takes less time)"
+                          % (shape[0], shape[1], shape[2], shape[3], shape[4], " ".join(str(v) for v in shape)), stacklevel=3)
+            return
         if kind is not None:
             import warnings
             BatchedPursuitEvade._hinted.add(shape)
@@ -215,7 +222,9 @@ class BatchedPursuitEvade(AbstractMAEnv):
                           % (shape[0], shape[1], shape[2], shape[3], shape[4], " ".join(str(v) for v in shape)), stacklevel=3)
 
     def set_kernel(self, kind):
-        """'auto' | 'generic' | 'wave' (one wavefront per env, compile-time specialised shapes only)"""
+        """'auto' | 'generic' | 'wave'.  'wave' is the compile-time specialised kernel of the shape: one wavefront per env, a group of
+        wavefronts, or -- above 64 pursuers or evaders -- the crowd kernel (csrc/pursuit_crowd_specializations.def); it raises for a shape
+        without one.  'auto' takes the specialised kernel where there is one."""
         k = {"auto": _lib.KERNEL_AUTO, "generic": _lib.KERNEL_GENERIC, "wave": _lib.KERNEL_WAVE}[kind]
         _lib.check(_lib.lib().madrl_pursuit_set_kernel(self._handle, k))
         self._kernel = kind
