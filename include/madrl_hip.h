@@ -117,8 +117,9 @@ void madrl_pursuit_destroy(madrl_pursuit *h);
  * per env, compile-time specialised; only for the shapes listed in
  * madrl_amd/csrc/pursuit_specializations.def -- and, for shapes with more than 64 pursuers or
  * evaders, the crowd kernel of the shapes listed in madrl_amd/csrc/pursuit_crowd_specializations.def,
- * one workgroup per env with the agents looped over its threads; not with control_evaders or
- * per-env agent counts).  AUTO = WAVE when available. */
+ * one workgroup per env with the agents looped over its threads; not with control_evaders, and
+ * with per-env agent counts only at the capacities that have an XLC line in
+ * madrl_amd/csrc/pursuit_live_specializations.def).  AUTO = WAVE when available. */
 #define MADRL_KERNEL_AUTO 0
 #define MADRL_KERNEL_GENERIC 1
 #define MADRL_KERNEL_WAVE 2
@@ -227,8 +228,9 @@ int madrl_pursuit_set_curriculum(madrl_pursuit *h, const double *constraint_wind
  * a fixed-shape (p, e) batch with the same seed and env_id_base + n computes.  Layouts stay at capacity: observation rows k >= p are
  * not written (like the rows of absent observers with control_evaders), rewards k >= p are 0, actions k >= p are ignored; evader
  * slots >= e count as gone.  The record layout and madrl_pursuit_state_bytes do not change: a slot that does not exist holds
- * position byte 0xFF.  The one-wavefront kernel runs the capacities listed in madrl_amd/csrc/pursuit_live_specializations.def, every
- * other capacity the generic kernel (set_kernel(WAVE) refuses it).  Not with control_evaders = 1 (MADRL_EINVAL).  Turning the
+ * position byte 0xFF.  The specialised kernels (one wavefront, a group of wavefronts, the crowd kernel above 64 pursuers or evaders) run
+ * the capacities listed in madrl_amd/csrc/pursuit_live_specializations.def (XL / XLG / XLC lines), every other capacity the generic
+ * kernel (set_kernel(WAVE) refuses it).  Not with control_evaders = 1 (MADRL_EINVAL).  Turning the
  * mode off is only meaningful while every env is at its capacity.
  * get_live_counts writes the live counts int32 [n_envs][2]; set_live_counts sets them (a checkpoint restored): slots past them stop
  * existing, a slot that exists again is at (0, 0) and, for an evader, gone until the next reset.  With the mode on, get_state

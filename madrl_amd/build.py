@@ -4,6 +4,7 @@
     python -m madrl_amd.build --pursuit-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN      # give this shape the fast path, rebuild
     python -m madrl_amd.build --pursuit-live-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN # ... and per-env agent counts at this capacity
     python -m madrl_amd.build --pursuit-crowd-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN # more than 64 pursuers or evaders: the crowd kernel
+    python -m madrl_amd.build --pursuit-live-crowd-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN # ... and per-env agent counts on it
     python -m madrl_amd.build --waterworld-shape N_PURSUERS N_EVADERS N_POISON N_SENSORS [OBS_DIM]
 
 The fast paths (one wavefront -- or a group of wavefronts -- per env, everything about the shape a compile-time constant) exist for the
@@ -158,6 +159,33 @@ def add_pursuit_live_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
     return _append_local("pursuit_live_specializations.def", live + "   // added by madrl_amd.build") or added_fixed
 
 
+def pursuit_live_crowd_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True):
+    """-> (live line, fixed line) that give a per-env-counts capacity above 64 pursuers or evaders the crowd kernel: XLC(..., NW) over an
+    XC(..., NW) shape -- or None when the crowd kernel cannot take the capacity (pursuit_crowd_path says why) or when it has an X / XG
+    fast path (pursuit_live_lines forms its lines).  Pure: nothing is written."""
+    if pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)[0] is not None:
+        return None
+    kind, nw = pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
+    if kind is None:
+        return None
+    args = "%d, %d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)), nw)
+    return "XLC(%s)" % args, "XC(%s)" % args
+
+
+def add_pursuit_live_crowd_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
+    """per-env agent counts at this capacity on the crowd kernel: the XLC line in the local live list, and the XC line it stands on in the
+    local crowd list if it is missing"""
+    lines = pursuit_live_crowd_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten)
+    if lines is None:
+        if pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten)[0] is not None:
+            raise ValueError("this PursuitEvade capacity has a one-wavefront / multi-wavefront fast path: use --pursuit-live-shape")
+        raise ValueError("no crowd kernel for this PursuitEvade capacity: %s (per-env agent counts run on the generic kernel)"
+                         % pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten)[1])
+    live, fixed = lines
+    added_fixed = _append_local("pursuit_crowd_specializations.def", fixed + "   // added by madrl_amd.build")
+    return _append_local("pursuit_live_specializations.def", live + "   // added by madrl_amd.build") or added_fixed
+
+
 def add_waterworld_shape(n_pursuers, n_evaders, n_poison, n_sensors, obs_dim=None):
     if obs_dim is None:
         obs_dim = n_sensors * 7 + 2 + 1          # speed features and the agent id (the reference's defaults)
@@ -233,6 +261,7 @@ if __name__ == "__main__":
     argv = sys.argv[1:]
     for flag, fn, lo, hi in (("--pursuit-shape", add_pursuit_shape, 6, 6), ("--pursuit-live-shape", add_pursuit_live_shape, 6, 6),
                              ("--pursuit-crowd-shape", add_pursuit_crowd_shape, 6, 6),
+                             ("--pursuit-live-crowd-shape", add_pursuit_live_crowd_shape, 6, 6),
                              ("--waterworld-shape", add_waterworld_shape, 4, 5)):
         while flag in argv:
             i = argv.index(flag)

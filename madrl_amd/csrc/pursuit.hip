@@ -259,6 +259,7 @@ __global__ void pursuit_live_counts_kernel(const PursuitDev d, int32_t *pos_p, i
 // =================================================================== host side / C ABI
 struct WaveEntry;  // one compiled specialisation of pursuit_wave_kernel
 struct CrowdEntry; // one compiled specialisation of pursuit_crowd_kernel
+struct LiveCrowdEntry; // ... of pursuit_live_crowd_kernel
 
 struct madrl_pursuit {
     madrl_pursuit_config cfg;
@@ -286,6 +287,7 @@ struct madrl_pursuit {
     // kernel's tables; `zmask` is then one word per env: "channel 3 of the env's rows is not known to hold +0.0"
     const CrowdEntry *crowd = nullptr;
     madrl::pc::CrowdDev cdev;
+    const LiveCrowdEntry *crowd_live = nullptr;  // the live-count instantiation of `crowd` (an XLC line of pursuit_live_specializations.def), if compiled
     hipEvent_t ev_fork = nullptr, ev_done = nullptr;   // madrl_pursuit_step_sharded: made by madrl_pursuit_create on the handle's device, destroyed with the handle
 };
 
@@ -384,6 +386,12 @@ struct CrowdEntry {
     void (*launch)(const madrl::pc::CrowdDev &, const madrl::pc::CrowdIO &, int mode, int64_t blocks, hipStream_t s);
 };
 
+// a live-count instantiation of a CrowdEntry's kernel: an XLC line of pursuit_live_specializations.def
+struct LiveCrowdEntry {
+    int xs, ys, P, E, R, flatten, nw;
+    void (*launch)(const madrl::pc::CrowdDev &, const madrl::pc::CrowdIO &, const int32_t *pending, int mode, int64_t blocks, hipStream_t s);
+};
+
 namespace {
 
 template <class S>
@@ -413,6 +421,7 @@ const CrowdEntry *find_crowd(const madrl_pursuit_config *c) {
 
 // (wave_launch of an LShape: no evader-control instantiations, madrl_pursuit_set_agent_counts refuses control_evaders; the group kernels
 // of the XLG lines are compiled in pursuit_live_group.hip)
+#define XLC(XS, YS, NP, NE, R, FL, NW)
 #define XL(XS, YS, NP, NE, R, FL) {wave_geom<pw::LShape<XS, YS, NP, NE, R, FL>>(1, pw::LShape<XS, YS, NP, NE, R, FL>::OCC), wave_launch<pw::LShape<XS, YS, NP, NE, R, FL>>},
 #define XLG(XS, YS, NP, NE, R, FL, NW) {wave_geom<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>(NW, pw::LGShape<XS, YS, NP, NE, R, FL, NW>::OCC), pw::live_group_launch<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>},
 const WaveEntry LIVE_TABLE[] = {
@@ -423,6 +432,51 @@ const WaveEntry LIVE_TABLE[] = {
 };
 #undef XL
 #undef XLG
+#undef XLC
+
+// An XLC line is reached through the XC line of the same capacity (find_live_crowd), so it needs one with the same NW: without it the
+// line would compile a kernel that no handle can use.  `python -m madrl_amd.build --pursuit-live-crowd-shape` appends both.
+#define XC(XS, YS, NP, NE, R, FL, NW) || (xs == XS && ys == YS && np == NP && ne == NE && r == R && fl == FL && nw == NW)
+constexpr bool has_crowd_line(int xs, int ys, int np, int ne, int r, int fl, int nw) {
+    return false
+#include "pursuit_crowd_specializations.def"
+#if __has_include("pursuit_crowd_specializations.local.def")
+#include "pursuit_crowd_specializations.local.def"
+#endif
+        ;
+}
+#undef XC
+#define XL(XS, YS, NP, NE, R, FL)
+#define XLG(XS, YS, NP, NE, R, FL, NW)
+#define XLC(XS, YS, NP, NE, R, FL, NW) static_assert(has_crowd_line(XS, YS, NP, NE, R, FL, NW), "an XLC line needs the XC line of the same capacity with the same NW");
+#include "pursuit_live_specializations.def"
+#if __has_include("pursuit_live_specializations.local.def")
+#include "pursuit_live_specializations.local.def"
+#endif
+#undef XLC
+
+// the live-count instantiations of the crowd kernel (compiled in pursuit_live_crowd.hip): the geometry is the XC line's
+#define XL(XS, YS, NP, NE, R, FL)
+#define XLG(XS, YS, NP, NE, R, FL, NW)
+#define XLC(XS, YS, NP, NE, R, FL, NW) {XS, YS, NP, NE, R, FL, NW, pc::live_crowd_launch<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>},
+const LiveCrowdEntry LIVE_CROWD_TABLE[] = {
+#include "pursuit_live_specializations.def"
+#if __has_include("pursuit_live_specializations.local.def")
+#include "pursuit_live_specializations.local.def"
+#endif
+};
+#undef XL
+#undef XLG
+#undef XLC
+
+// the live-count instantiation of the crowd entry `c` the handle uses (the same XC line, NW included)
+const LiveCrowdEntry *find_live_crowd(const CrowdEntry *c) {
+    if (!c) return nullptr;
+    for (const LiveCrowdEntry &e : LIVE_CROWD_TABLE)
+        if (e.xs == c->xs && e.ys == c->ys && e.P == c->P && e.E == c->E && e.R == c->R && e.flatten == c->flatten && e.nw == c->nw)
+            return &e;
+    return nullptr;
+}
 
 // the live-count instantiation matching a shape whose fixed-shape entry `w` the handle uses (same geometry, same tables)
 const WaveEntry *find_live(const WaveEntry *w) {
@@ -532,7 +586,7 @@ void launch_nt(const madrl_pursuit *h, const PursuitIO &io, int mode, hipStream_
 
 // the fast path this handle can use in its current mode (per-env agent counts: the live-count instantiation)
 bool has_wave(const madrl_pursuit *h) {
-    return h->pending ? h->wave_live != nullptr : (h->wave != nullptr || h->crowd != nullptr);
+    return h->pending ? (h->wave_live != nullptr || h->crowd_live != nullptr) : (h->wave != nullptr || h->crowd != nullptr);
 }
 
 // bytes of what the fast path remembers about the observation buffer (behind the records in the caller's state buffer)
@@ -546,7 +600,7 @@ bool use_wave(const madrl_pursuit *h) {
 
 int launch(madrl_pursuit *h, const PursuitIO &io, int mode, void *stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (use_wave(h) && h->crowd) {   // (per-env agent counts never get here: a crowd shape has no live-count instantiation)
+    if (use_wave(h) && h->crowd) {   // (per-env agent counts get here with a live-count instantiation only: has_wave)
         pc::CrowdIO c;
         c.mask = io.mask; c.inj_pos = io.inj_pos; c.inj_map = io.inj_map; c.actions = io.actions;
         c.inj_eact = io.inj_eact; c.obs = io.obs; c.rew = io.rew; c.done = io.done; c.removed = io.removed;
@@ -561,7 +615,8 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, void *stream) {
             MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0xFF, zmask_len(h), s));
             h->zmask_obs = io.obs;
         }
-        h->crowd->launch(cd, c, mode, blocks, s);
+        if (h->pending) h->crowd_live->launch(cd, c, h->pending, mode, blocks, s);
+        else h->crowd->launch(cd, c, mode, blocks, s);
         MADRL_HIP_TRY(hipGetLastError());
         return MADRL_OK;
     }
@@ -905,6 +960,7 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
         h->zmask = (uint8_t *)state_dev + zmask_offset(d.rec_bytes, n_envs);  // caller-owned, like the records
         c.ch3 = reinterpret_cast<const uint32_t *>(h->zmask);
     }
+    h->crowd_live = find_live_crowd(h->crowd);
 
     h->walk_mode = 0;
     h->max_blocks = 0;
@@ -973,7 +1029,7 @@ int madrl_pursuit_set_kernel(madrl_pursuit *h, int32_t kind) {
     if (!h) return fail(MADRL_EINVAL, "handle is NULL");
     if (kind != MADRL_KERNEL_AUTO && kind != MADRL_KERNEL_GENERIC && kind != MADRL_KERNEL_WAVE)
         return fail(MADRL_EINVAL, "unknown kernel kind %d", kind);
-    if (kind == MADRL_KERNEL_WAVE && h->pending && !h->wave_live)
+    if (kind == MADRL_KERNEL_WAVE && h->pending && !h->wave_live && !h->crowd_live)
         return fail(MADRL_EINVAL, "per-env agent counts: no live-count specialisation was compiled for this capacity "
                     "(see madrl_amd/csrc/pursuit_live_specializations.def)");
     if (kind == MADRL_KERNEL_WAVE && !h->wave && !h->crowd)
@@ -1111,7 +1167,7 @@ int madrl_pursuit_set_agent_counts(madrl_pursuit *h, const int32_t *pending_dev)
     if (!h) return fail(MADRL_EINVAL, "handle is NULL");
     if (pending_dev && !h->dev.train_pursuit)
         return fail(MADRL_EINVAL, "per-env agent counts with control_evaders=1 (train_pursuit=False) are not supported");
-    if (pending_dev && h->kernel_kind == MADRL_KERNEL_WAVE && !h->wave_live)
+    if (pending_dev && h->kernel_kind == MADRL_KERNEL_WAVE && !h->wave_live && !h->crowd_live)
         return fail(MADRL_EINVAL, "per-env agent counts: kernel WAVE was requested and no live-count specialisation was compiled for this "
                     "capacity (see madrl_amd/csrc/pursuit_live_specializations.def)");
     h->pending = pending_dev;

@@ -4,7 +4,9 @@
 // 64-bit scalar, the record in 64 dwords and three dword layers in LDS.  This kernel gives all of that up so that the shapes those two
 // refuse -- up to 1 023 agents of a kind, maps up to 128 x 128 with obs_range 21, records of any length (the authors' CNN launch line,
 // runners/old/rllab/pursuit_cnn.sh:1: 100 v 300, obs_range 21, (R, R, 4) rows, a 912-byte record) -- have a specialised kernel too.
-// The shapes are the XC lines of pursuit_crowd_specializations.def; the kernels are instantiated in pursuit_crowd.hip.
+// The shapes are the XC lines of pursuit_crowd_specializations.def; the kernels are instantiated in pursuit_crowd.hip.  Per-env agent
+// counts within such a shape as a capacity: LCShape / pursuit_live_crowd_kernel below, the XLC lines of pursuit_live_specializations.def,
+// instantiated in pursuit_live_crowd.hip.
 //
 // Design (DESIGN.md "pursuit_crowd_kernel"):
 //   * One workgroup of NW wavefronts per env, persistent over envs.  Agents are LOOPED over the threads; positions, the gone / terminal
@@ -90,7 +92,9 @@ struct CShape {
     static constexpr int X_GONE = X_KPRE + (P + 3) / 4 * 4;
     static constexpr int X_PLACED = X_GONE + (NGW + 3) / 4 * 4;              // evaders whose count is in the cells
     static constexpr int X_TERM = X_PLACED + (NGW + 3) / 4 * 4;
-    static constexpr int X_MISC = X_TERM + (NTW + 3) / 4 * 4;                // [0..3] header, [4] removed
+    // [0..3] header, [4] removed, LCShape: [5] / [6] the first pursuer / evader slot that does not exist (ds_min over the record's
+    // x bytes while it is loaded) -- they must hold (P, E) whenever a load begins: set before the env loop and by every record store
+    static constexpr int X_MISC = X_TERM + (NTW + 3) / 4 * 4;
     static constexpr int X_XY = X_MISC + 8;                                  // u8 x[A16], y[A16]
     static constexpr int A16 = (A + 15) / 16 * 16;
     static constexpr int LDS_DWORDS = X_XY + 2 * A16 / 4;
@@ -102,7 +106,19 @@ struct CShape {
     static_assert(D % 4 == 0, "observation row must be a whole number of float4");
     static_assert(LDS_DWORDS * 4 <= 160 * 1024, "LDS budget: one workgroup may declare 160 KiB");
     static_assert(X_REW % 2 == 0, "the reward doubles are 8-byte aligned");
+    static constexpr bool LIVE = false;
 };
+
+// Per-env agent counts (madrl_pursuit_set_agent_counts): the same geometry with P and E as a capacity.  The env's live (np, ne) are the
+// leading pursuer / evader slots of its record whose x byte is not NOT_HERE -- the generic kernel's marks (pursuit_generic.inc), whose
+// LIVE branches pursuit_live_crowd_kernel follows line for line.  The XLC lines of pursuit_live_specializations.def, instantiated in
+// pursuit_live_crowd.hip.
+template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_, int NW_>
+struct LCShape : CShape<XS_, YS_, P_, E_, R_, FLATTEN_, NW_> {
+    static constexpr bool LIVE = true;
+};
+
+constexpr uint32_t NOT_HERE = 0xFFu;   // position byte of a slot that does not exist (no coordinate is 255)
 
 // ds_add of one agent to byte `sh / 8` of a cell; *ovf as in the generic kernel's lds_byte_add
 __device__ __forceinline__ void cell_add(uint32_t *cell, int idx, unsigned sh, uint32_t *ovf) {
@@ -136,6 +152,43 @@ __device__ __forceinline__ double np_sum(const double *a) {
     }
 }
 
+// the same order over a run-time count (LCShape: the live pursuers): np_pairwise_sum of pursuit.hip, numpy's uneven split (n2 = n / 2 rounded
+// down to a multiple of 8) above 128 elements, four levels for every count up to 1 024.  A loop instead of the recursion (one copy of
+// np_base in the code, not sixteen): the up to sixteen leaves in order, each found by walking its path bits down from the root (a leaf
+// above the bottom level is taken on its all-zero path only), and a partial sum per level that is added when its right sibling arrives.
+__device__ __forceinline__ double np_sum_n(const double *a, int n) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    uint32_t has = 0u;
+    double v = 0.0;
+#pragma unroll 1
+    for (int leaf = 0; leaf < 16; ++leaf) {
+        int off = 0, len = n, depth = 0;
+        bool first = true;
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const bool right = (leaf >> (3 - l)) & 1;
+            if (len <= 128) {
+                if (right) first = false;
+            } else {
+                int n2 = len / 2;
+                n2 -= n2 % 8;
+                if (right) { off += n2; len -= n2; }
+                else len = n2;
+                depth = l + 1;
+            }
+        }
+        if (!first) continue;
+        v = np_base(a + off, len);
+#pragma unroll
+        for (int d = 4; d >= 1; --d) {
+            if (d != depth) continue;
+            if (has & (1u << (d - 1))) { v = acc[d - 1] + v; has &= ~(1u << (d - 1)); --depth; }
+            else { acc[d - 1] = v; has |= 1u << (d - 1); }
+        }
+    }
+    return v;
+}
+
 // workgroup barrier that waits for LDS traffic only (a wavefront does not wait for its row stores here)
 __device__ __forceinline__ void group_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -146,371 +199,27 @@ __device__ __forceinline__ void group_sync() {
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 // MODE 0: reset(mask)   MODE 1: step (+ fused auto-reset)
+// The body (pursuit_crowd_body.inc) is included in both kernels rather than called, as pursuit_generic.inc is: the fixed-shape kernels'
+// code stays what it was, and the live kernels get the caller's pending counts as an argument of their own -- CrowdDev and CrowdIO, and
+// with them the fixed kernels' argument loads, are untouched.
 template <class S, int MODE>
 __global__ __launch_bounds__(S::NT) void pursuit_crowd_kernel(const CrowdDev d, const CrowdIO io) {
-    constexpr int P = S::P, E = S::E, A = S::A, GW = S::GW, PAD = S::PAD, GSZ = S::GSZ, NT = S::NT, D = S::D, DV = S::DV, NQ = S::NQ;
-    constexpr int R = S::R, OFF = S::OFF, NGW = S::NGW, NTW = S::NTW;
-    __shared__ __attribute__((aligned(16))) uint32_t L[S::LDS_DWORDS];
-    const int tid0 = threadIdx.x;
-    uint32_t *const cell = &L[S::X_CELL];
-    float *const s_vtab = reinterpret_cast<float *>(&L[S::X_VTAB]);
-    uint32_t *const s_code = &L[S::X_CODE];
-    double *const s_rew = reinterpret_cast<double *>(&L[S::X_REW]);
-    int32_t *const s_base = reinterpret_cast<int32_t *>(&L[S::X_BASE]);
-    int32_t *const s_kpre = reinterpret_cast<int32_t *>(&L[S::X_KPRE]);
-    uint32_t *const s_gone = &L[S::X_GONE];
-    uint32_t *const s_placed = &L[S::X_PLACED];
-    uint32_t *const s_term = &L[S::X_TERM];
-    uint32_t *const s_misc = &L[S::X_MISC];
-    uint8_t *const s_ax = reinterpret_cast<uint8_t *>(&L[S::X_XY]);
-    uint8_t *const s_ay = s_ax + S::A16;
+    [[maybe_unused]] const int32_t *const pending = nullptr;
+#include "pursuit_crowd_body.inc"
+}
 
-    // ---- once per workgroup: the value table and (flatten) the element codes: channel << 24 | cell offset in the window; channel 3 = the id
-    for (int k = tid0; k < 256; k += NT) s_vtab[k] = d.vtab[k];
-    if constexpr (S::FLATTEN) {
-        for (int r = tid0; r < D; r += NT) {
-            const int c = r / (R * R), rr = r - c * (R * R), i = rr / R, j = rr - i * R;
-            s_code[r] = c == 3 ? (3u << 24) : (((uint32_t)c << 24) | (uint32_t)(i * GW + j));
-        }
-    }
-    int cached_map = -1;   // the map whose bytes the cells hold; the count and credit bytes are zero between envs
-
-    for (int64_t env = blockIdx.x; env < d.n_envs; env += gridDim.x) {
-        if (MODE == 0 && io.mask != nullptr && io.mask[env] == 0) continue;  // block-uniform
-        // (a fresh copy per env: what is derived from the thread index -- LDS addresses, lane predicates -- is then computed where it is
-        // used instead of being held in registers across the env loop, which the 128 registers of a 16-wavefront workgroup cannot afford)
-        const int tid = fresh(tid0);
-        uint8_t *rec = d.state + env * (int64_t)S::REC_BYTES;
-        group_sync();  // the previous env's LDS traffic is finished
-        // ------------------------------------------------------------ load state record
-        if (tid < 4) s_misc[tid] = reinterpret_cast<const uint32_t *>(rec)[tid];
-        if (tid == 4) s_misc[4] = 0;
-        for (int a = tid; a < A; a += NT) {
-            const uint32_t xy = reinterpret_cast<const uint16_t *>(rec + HDR_BYTES)[a];
-            s_ax[a] = (uint8_t)(xy & 0xFF);
-            s_ay[a] = (uint8_t)(xy >> 8);
-        }
-        for (int w = tid; w < NGW; w += NT) {
-            const uint32_t g = reinterpret_cast<const uint32_t *>(rec + S::OFF_GONE)[w];
-            s_gone[w] = g;
-            s_placed[w] = ~g;   // step mode: the evaders the pre-move pass counts
-        }
-        for (int w = tid; w < NTW; w += NT) s_term[w] = reinterpret_cast<const uint32_t *>(rec + S::OFF_TERM)[w];
-        const bool ch3_zero = !S::FLATTEN && d.ch3[env] == 0u;
-        group_sync();
-        uint32_t tick = s_misc[0];
-        int32_t tstep = (int32_t)s_misc[1];
-        int32_t map_id = (int32_t)s_misc[2];
-        const uint32_t gid = d.gid_base + (uint32_t)env;
-        bool do_reset = (MODE == 0);
-        uint32_t done_bits = 0;
-
-        // the cells take the map's bytes (count and credit bytes: zero).  Only called while no agent is placed.
-        auto load_map = [&](int m) {
-            if (cached_map == m) return;
-            const uint32_t *mt = reinterpret_cast<const uint32_t *>(d.maps + (int64_t)m * d.map_stride);
-            for (int k = tid; k < GSZ / 4; k += NT) {
-                const uint32_t w = mt[k];
-                reinterpret_cast<uint4 *>(cell)[k] = make_uint4(w & 0xFFu, (w >> 8) & 0xFFu, (w >> 16) & 0xFFu, w >> 24);
-            }
-            cached_map = m;
-        };
-
-        // -------------------------------------------------------------- observations (:418-461)
-        auto write_obs = [&]() {
-            // (the env's rows through a wave-uniform base and 32-bit offsets: P * D floats are far below 4 GB)
-            typedef __attribute__((address_space(1))) float gfloat;
-            typedef __attribute__((address_space(1))) v4f gv4f;
-            gfloat *const orow = uniform_ptr(io.obs + env * (int64_t)P * D);
-            int p = tid / DV, f = tid - p * DV;
-            constexpr int dp = NT / DV, df = NT - dp * DV;
-#pragma unroll 2
-            for (uint32_t q = (uint32_t)tid; q < (uint32_t)NQ; q += (uint32_t)NT) {
-                const int base = s_base[p];
-                gfloat *const o = orow + 4u * q;
-                if constexpr (S::FLATTEN) {
-                    const uint4 cd = reinterpret_cast<const uint4 *>(s_code)[f];
-                    const uint32_t code[4] = {cd.x, cd.y, cd.z, cd.w};
-                    float val[4];
-                    bool keep[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const uint32_t ch = code[k] >> 24;
-                        if (ch == 3u) {
-                            val[k] = (float)((double)p / (double)P);  // :440-445
-                            keep[k] = true;
-                        } else {
-                            const uint32_t c = cell[base + (int)(code[k] & 0xFFFFFFu)];
-                            val[k] = s_vtab[(c >> (8u * ch)) & 0xFFu];
-                            keep[k] = ch == 0u || (c & 0xFFu) != PAD_MAP;  // count cells outside the map keep their old contents
-                        }
-                    }
-                    if (keep[0] & keep[1] & keep[2] & keep[3]) {
-                        const v4f v = {val[0], val[1], val[2], val[3]};
-                        __builtin_nontemporal_store(v, reinterpret_cast<gv4f *>(o));
-                    } else {
-                        if (keep[0]) o[0] = val[0];
-                        if (keep[1]) o[1] = val[1];
-                        if (keep[2]) o[2] = val[2];
-                        if (keep[3]) o[3] = val[3];
-                    }
-                } else {
-                    const int i = f / R, j = f - i * R;
-                    const uint32_t c = cell[base + i * GW + j];
-                    const float v0 = s_vtab[c & 0xFFu];
-                    if ((c & 0xFFu) == PAD_MAP) {
-                        o[0] = v0;   // outside the map: the fill value in channel 0, the counts keep their old contents
-                    } else {
-                        const float v1 = s_vtab[(c >> 8) & 0xFFu], v2 = s_vtab[(c >> 16) & 0xFFu];
-                        if (f == S::CENTRE) {
-                            const v4f v = {v0, v1, v2, (float)((double)p / (double)P)};  // :440-445
-                            __builtin_nontemporal_store(v, reinterpret_cast<gv4f *>(o));
-                        } else if (ch3_zero) {
-                            const v4f v = {v0, v1, v2, 0.0f};
-                            __builtin_nontemporal_store(v, reinterpret_cast<gv4f *>(o));
-                        } else {   // channel 3 off the centre is never written (:440-441)
-                            o[0] = v0;
-                            o[1] = v1;
-                            o[2] = v2;
-                        }
-                    }
-                }
-                f += df; p += dp;
-                if (f >= DV) { f -= DV; ++p; }
-            }
-        };
-
-        // the placed agents leave the cells: counts first, then (behind a barrier: a count that left its byte may have carried into the
-        // credit bit) the credit of the evaders caught in this step
-        auto undo = [&]() {
-            group_sync();  // the row pass has read the cells
-            for (int a = tid; a < A; a += NT) {
-                const int idx = (s_ax[a] + PAD) * GW + s_ay[a] + PAD;
-                if (a < P) atomicSub(&cell[idx], 1u << 8);
-                else if ((s_placed[(a - P) >> 5] >> ((a - P) & 31)) & 1u) atomicSub(&cell[idx], 1u << 16);
-            }
-            group_sync();
-            for (int i = tid; i < E; i += NT) {
-                if (!((s_placed[i >> 5] & s_gone[i >> 5]) >> (i & 31) & 1u)) continue;
-                const int c0 = (s_ax[P + i] + PAD) * GW + s_ay[P + i] + PAD;
-                atomicAnd(&cell[c0], 0x00FFFFFFu);
-                atomicAnd(&cell[c0 - GW], 0x00FFFFFFu);
-                atomicAnd(&cell[c0 + GW], 0x00FFFFFFu);
-                atomicAnd(&cell[c0 + 1], 0x00FFFFFFu);
-                atomicAnd(&cell[c0 - 1], 0x00FFFFFFu);
-            }
-        };
-
-        if constexpr (MODE == 1) {
-            load_map(map_id);
-            group_sync();
-            // -------------------------------------------------------- pre-move evader counts (:364-365)
-            for (int i = tid; i < E; i += NT) {
-                if (!((s_gone[i >> 5] >> (i & 31)) & 1u)) cell_add(cell, (s_ax[P + i] + PAD) * GW + s_ay[P + i] + PAD, 16u, &s_misc[3]);
-            }
-            group_sync();
-            // proximity reward on the PRE-move state, np.clip keeps border pursuers on their own cell (:374-380)
-            for (int p = tid; p < P; p += NT) {
-                const int x = s_ax[p], y = s_ay[p];
-                const int xm = max(x - 1, 0), xp = min(x + 1, S::XS - 1);
-                const int ym = max(y - 1, 0), yp = min(y + 1, S::YS - 1);
-                s_kpre[p] = (int)((cell[(xm + PAD) * GW + y + PAD] >> 16) & 0xFFu) + (int)((cell[(xp + PAD) * GW + y + PAD] >> 16) & 0xFFu) +
-                            (int)((cell[(x + PAD) * GW + yp + PAD] >> 16) & 0xFFu) + (int)((cell[(x + PAD) * GW + ym + PAD] >> 16) & 0xFFu);
-            }
-            group_sync();
-            // -------------------------------------------------------- moves (:229-241)
-            for (int a = tid; a < A; a += NT) {
-                const bool is_p = a < P;
-                const int i = a - P;
-                if (!is_p && ((s_gone[i >> 5] >> (i & 31)) & 1u)) continue;
-                int x = s_ax[a], y = s_ay[a];
-                int act;
-                if (is_p) {
-                    act = io.actions[env * P + a];
-                } else {
-                    atomicSub(&cell[(x + PAD) * GW + y + PAD], 1u << 16);  // undo the pre-move count
-                    int k = 0;  // index in the evader LAYER = alive evaders in slots below i
-                    for (int w = 0; w < (i >> 5); ++w) k += 32 - __popc(s_gone[w]);
-                    k += (i & 31) - __popc(s_gone[i >> 5] & ((1u << (i & 31)) - 1u));
-                    if (io.inj_eact != nullptr) {
-                        act = io.inj_eact[env * E + k];
-                    } else {
-                        const u32x4 r = philox4x32_10(gid, tick, (uint32_t)k, TAG_EVADER_ACT, d.k0, d.k1);
-                        act = (int)__umulhi(r.x, 5u);  // RandomPolicy.act, Controllers.py:15-16
-                    }
-                }
-                // DiscreteAgent.step, DiscreteAgent.py:69-97
-                const bool term = (s_term[a >> 5] >> (a & 31)) & 1u;
-                if (!term) {
-                    if ((cell[(x + PAD) * GW + y + PAD] & 0xFFu) == 1u) {
-                        atomicOr(&s_term[a >> 5], 1u << (a & 31));  // standing in a building
-                    } else {
-                        int nx = x, ny = y;
-                        if (act == 0) nx = x - 1;
-                        else if (act == 1) nx = x + 1;
-                        else if (act == 2) ny = y + 1;
-                        else if (act == 3) ny = y - 1;
-                        if ((cell[(nx + PAD) * GW + ny + PAD] & 0xFFu) == 0u) {  // 0 = free, 1 = building, 0xFE = outside the map
-                            x = nx;
-                            y = ny;
-                        }
-                    }
-                }
-                s_ax[a] = (uint8_t)x;
-                s_ay[a] = (uint8_t)y;
-                if (is_p) s_base[a] = (x - OFF + PAD) * GW + (y - OFF + PAD);
-                cell_add(cell, (x + PAD) * GW + y + PAD, is_p ? 8u : 16u, &s_misc[3]);  // :244-246
-            }
-            group_sync();
-            // -------------------------------------------------------- catch resolution (:463-521)
-            const uint8_t *need_tab = d.maps + (int64_t)map_id * d.map_stride + GSZ;
-            for (int i = tid; i < E; i += NT) {
-                if ((s_gone[i >> 5] >> (i & 31)) & 1u) continue;
-                const int x = s_ax[P + i], y = s_ay[P + i];
-                const int c0 = (x + PAD) * GW + y + PAD;
-                bool caught;
-                // a neighbour holds pursuers: its count byte is 1 .. 254 (cells outside the map never hold any)
-                auto hit = [&](int c) { return (uint8_t)(((cell[c] >> 8) & 0xFFu) - 1u) < 0xFEu; };
-                if (d.surround) {
-                    const bool h0 = hit(c0 - GW), h1 = hit(c0 + GW), h2 = hit(c0 + 1), h3 = hit(c0 - 1);  // neighbour order of surround_mask (:150)
-                    const int cnt = (int)h0 + (int)h1 + (int)h2 + (int)h3;
-                    caught = (cnt == (int)need_tab[x * S::YS + y]);  // need_to_surround :523-540
-                    if (caught) {  // pursuers standing on a matched neighbour get credit (:489-495)
-                        if (h0) atomicOr(&cell[c0 - GW], 1u << 24);
-                        if (h1) atomicOr(&cell[c0 + GW], 1u << 24);
-                        if (h2) atomicOr(&cell[c0 + 1], 1u << 24);
-                        if (h3) atomicOr(&cell[c0 - 1], 1u << 24);
-                    }
-                } else {
-                    caught = (int)((cell[c0] >> 8) & 0xFFu) >= d.n_catch;  // :498
-                    if (caught) atomicOr(&cell[c0], 1u << 24);             // :503-506
-                }
-                if (caught) {
-                    atomicOr(&s_gone[i >> 5], 1u << (i & 31));
-                    atomicAdd(&s_misc[4], 1u);
-                }
-            }
-            group_sync();
-            // -------------------------------------------------------- rewards (:254-262)
-            int n_alive = E;
-            for (int w = 0; w < NGW; ++w) n_alive -= __popc(s_gone[w]);
-            const double catchr = d.catchr_env ? d.catchr_env[env] : d.catchr;
-            for (int p = tid; p < P; p += NT) {
-                const uint32_t sur = (cell[(s_ax[p] + PAD) * GW + s_ay[p] + PAD] >> 24) & 1u;
-                double r = catchr * (double)s_kpre[p];
-                r += d.term_pursuit * (sur ? 1.0 : 0.0);
-                r += d.urgency;
-                if (d.reward_global) s_rew[p] = r;
-                else io.rew[env * P + p] = (float)r;
-            }
-            if (d.reward_global) {
-                group_sync();
-                if (tid < P) {
-                    const double m = np_sum<P>(s_rew) / (double)P;
-                    for (int p = tid; p < P; p += NT) io.rew[env * P + p] = (float)m;
-                }
-            }
-            tick += 1;
-            tstep += 1;
-            if (n_alive == 0) done_bits |= 1u;                               // :383-389
-            if (d.max_steps > 0 && tstep >= d.max_steps) done_bits |= 2u;
-            const uint32_t overflow = s_misc[3] ? 0x80u : 0u;                // a cell's count left the byte range: results void
-            if (tid == 0) {
-                io.done[env] = (uint8_t)(done_bits | overflow);
-                io.removed[env] = (int32_t)s_misc[4];
-                d.flags[env] = done_flag_word(done_bits | overflow);
-            }
-            do_reset = d.auto_reset && done_bits != 0;
-        }
-        // a step: the rows of the step; with auto-reset the reference sequence is step() then reset(), both write the persistent observation
-        // buffer, and cells the second write skips keep the first one's values.  A reset launch: the reset, then its rows.
-        for (int pass = MODE == 0 ? 1 : 0;; ++pass) {
-            if (pass == 1) {
-                // ---------------------------------------------------------- reset (:173-207)
-                group_sync();
-                if (tid == 0) s_misc[3] = 0u;                         // a new episode: the overflow mark goes
-                for (int w = tid; w < NGW; w += NT) s_gone[w] = 0u;   // :175-176
-                for (int w = tid; w < NTW; w += NT) s_term[w] = 0u;   // fresh agents
-                if (io.inj_map != nullptr && MODE == 0) {
-                    map_id = io.inj_map[env];
-                } else if (d.sample_maps) {  // :182-183
-                    const u32x4 r = philox4x32_10(gid, tick, 0u, TAG_RESET_ENV, d.k0, d.k1);
-                    map_id = (int)__umulhi(r.x, (uint32_t)d.n_maps);
-                }
-                load_map(map_id);
-                // constraint window (:185-191), float64 like the reference
-                const u32x4 rw = philox4x32_10(gid, tick, 1u, TAG_RESET_ENV, d.k0, d.k1);
-                const double cw = d.cw_env ? d.cw_env[env] : d.cw;
-                const double sx = u53(rw.x, rw.y) * (1.0 - cw);
-                const double sy = u53(rw.z, rw.w) * (1.0 - cw);
-                const int xlb = (int)(S::XS * sx), xub = (int)(S::XS * (sx + cw));
-                const int ylb = (int)(S::YS * sy), yub = (int)(S::YS * (sy + cw));
-                // random_opponents (:177-181): this episode has n_create <= E evaders; the slots above are not created and count as gone.
-                // An injected position with x < 0 marks a slot that is not created.
-                const bool inj = io.inj_pos != nullptr && MODE == 0;
-                int n_create = E;
-                if (d.max_opponents > 0 && !inj) {
-                    const u32x4 r3 = philox4x32_10(gid, tick, 2u, TAG_RESET_ENV, d.k0, d.k1);
-                    n_create = min(1 + (int)__umulhi(r3.x, (uint32_t)(d.max_opponents - 1)), E);
-                }
-                group_sync();
-                for (int a = tid; a < A; a += NT) {  // create_agents, agent_utils.py:12-28
-                    int x = 0, y = 0;
-                    if (a >= P && (a - P >= n_create || (inj && io.inj_pos[(env * A + a) * 2] < 0))) {
-                        atomicOr(&s_gone[(a - P) >> 5], 1u << ((a - P) & 31));
-                        s_ax[a] = 0;
-                        s_ay[a] = 0;
-                        continue;
-                    }
-                    if (inj) {
-                        x = io.inj_pos[(env * A + a) * 2];
-                        y = io.inj_pos[(env * A + a) * 2 + 1];
-                        // (an injected position is the caller's word, as in the generic kernel; only the LDS index is kept inside the grid)
-                        x = min(max(x, 0), S::XS - 1);
-                        y = min(max(y, 0), S::YS - 1);
-                    } else {
-                        // feasible_position: rejection sampling (agent_utils.py:37-47); bounded
-                        for (uint32_t att = 0; att < 1024u; ++att) {
-                            const u32x4 r = philox4x32_10(gid, tick, (uint32_t)a, TAG_RESET_POS | (att << 8), d.k0, d.k1);
-                            x = xlb + (int)__umulhi(r.x, (uint32_t)(xub - xlb));
-                            y = ylb + (int)__umulhi(r.y, (uint32_t)(yub - ylb));
-                            if ((cell[(x + PAD) * GW + y + PAD] & 0xFFu) != 1u) break;
-                        }
-                    }
-                    s_ax[a] = (uint8_t)x;
-                    s_ay[a] = (uint8_t)y;
-                    if (a < P) s_base[a] = (x - OFF + PAD) * GW + (y - OFF + PAD);
-                    cell_add(cell, (x + PAD) * GW + y + PAD, a < P ? 8u : 16u, &s_misc[3]);  // :201-203
-                }
-                tick += 1;
-                tstep = 0;
-                group_sync();
-                for (int w = tid; w < NGW; w += NT) s_placed[w] = ~s_gone[w];
-                group_sync();
-            }
-            write_obs();   // (a step: the barrier after the catches published everything the rows read)
-            if (pass == 1 || !do_reset) break;
-            undo();
-        }
-        // -------------------------------------------------------------- store state record
-        for (int a = tid; a < A; a += NT)
-            reinterpret_cast<uint16_t *>(rec + HDR_BYTES)[a] = (uint16_t)(s_ax[a] | (s_ay[a] << 8));
-        for (int w = tid; w < NGW; w += NT) reinterpret_cast<uint32_t *>(rec + S::OFF_GONE)[w] = s_gone[w];
-        for (int w = tid; w < NTW; w += NT) reinterpret_cast<uint32_t *>(rec + S::OFF_TERM)[w] = s_term[w];
-        if (tid == 0) {
-            uint32_t *h = reinterpret_cast<uint32_t *>(rec);
-            h[0] = tick;
-            h[1] = (uint32_t)tstep;
-            h[2] = (uint32_t)map_id;
-            h[3] = s_misc[3];   // sticky count-overflow mark of the episode
-        }
-        undo();
-    }
+// S = LCShape: pending = the caller's int32 [n_envs][2] (pursuers, evaders), read by resets only
+template <class S, int MODE>
+__global__ __launch_bounds__(S::NT) void pursuit_live_crowd_kernel(const CrowdDev d, const CrowdIO io, const int32_t *const pending) {
+#include "pursuit_crowd_body.inc"
 }
 
 // host side: launches the instantiation of shape S (defined and instantiated for every XC line in pursuit_crowd.hip)
 template <class S>
 void crowd_launch(const CrowdDev &d, const CrowdIO &io, int mode, int64_t blocks, hipStream_t s);
+// ... of an LCShape (for every XLC line in pursuit_live_crowd.hip)
+template <class S>
+void live_crowd_launch(const CrowdDev &d, const CrowdIO &io, const int32_t *pending, int mode, int64_t blocks, hipStream_t s);
 
 }  // namespace pc
 }  // namespace madrl

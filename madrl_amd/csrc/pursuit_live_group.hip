@@ -18,6 +18,7 @@ void live_group_launch(const WaveDev &d, const WaveIO &io, int mode, int64_t blo
 }
 
 #define XL(XS, YS, NP, NE, R, FL)
+#define XLC(XS, YS, NP, NE, R, FL, NW)
 #define XLG(XS, YS, NP, NE, R, FL, NW) \
     template void live_group_launch<LGShape<XS, YS, NP, NE, R, FL, NW>>(const WaveDev &, const WaveIO &, int, int64_t, hipStream_t);
 #include "pursuit_live_specializations.def"
@@ -26,6 +27,7 @@ void live_group_launch(const WaveDev &d, const WaveIO &io, int mode, int64_t blo
 #endif
 #undef XL
 #undef XLG
+#undef XLC
 
 }  // namespace pw
 }  // namespace madrl

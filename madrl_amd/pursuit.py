@@ -205,6 +205,16 @@ class BatchedPursuitEvade(AbstractMAEnv):
                               "--pursuit-live-shape %s`) gives them the %s kernel"
                               % (shape[2], shape[3], shape[0], shape[1], shape[4], lines[0].replace(" ", ""), " ".join(str(v) for v in shape),
                                  "one-wavefront" if lines[0].startswith("XL(") else "multi-wavefront"), stacklevel=3)
+                return
+            lines = _build.pursuit_live_crowd_lines(*shape, include_id=bool(self.include_id))
+            if lines is not None:   # more than 64 of a kind: the crowd kernel's live-count instantiation
+                import warnings
+                BatchedPursuitEvade._hinted.add(shape)
+                warnings.warn("PursuitEvade per-env agent counts at capacity %d v %d (%dx%d, obs_range %d) run on the generic kernel; the line "
+                              "%s in madrl_amd/csrc/pursuit_live_specializations.def (and a rebuild: `python -m madrl_amd.build "
+                              "--pursuit-live-crowd-shape %s`) gives them the crowd kernel"
+                              % (shape[2], shape[3], shape[0], shape[1], shape[4], lines[0].replace(" ", ""), " ".join(str(v) for v in shape)),
+                              stacklevel=3)
             return
         kind, _ = _build.pursuit_fast_path(*shape, include_id=bool(self.include_id))
         if kind is None and self.train_pursuit and _build.pursuit_crowd_path(*shape, include_id=bool(self.include_id))[0] is not None:

@@ -2,6 +2,7 @@
 pursuit_crowd_specializations.def) against the generic kernel the same shapes ran on before.
 
     python scripts/crowd_time.py --mode {crowd,generic} [--shape {cnn,cnn48,surround24,colocate20,wide24}] [--envs 1024] [--warmup 200] [--steps 200]
+                                 [--live P E]
 
   cnn         the authors' CNN launch line (runners/old/rllab/pursuit_cnn.sh:1): 100 v 300, obs_range 21, (R, R, 4) rows, --surround
               --sample_maps, local reward, on a ten-map 128 x 128 pool.  Their map_pool128.npy is not in their tree: the pool is
@@ -10,6 +11,10 @@ pursuit_crowd_specializations.def) against the generic kernel the same shapes ra
   surround24  20 v 300, obs_range 9, flatten, open 24 x 24 map (windows at the border all the time)
   colocate20  260 v 40, obs_range 5, flatten, open 20 x 20 map, co-location catches, global reward
   wide24      70 v 90, obs_range 9, flatten, open 24 x 24 map
+
+--live P E: the batch is built with per_env_counts=True (the shape's counts are then a capacity) and every env runs P pursuers and E evaders:
+--mode crowd is then the live crowd kernel (the XLC lines of pursuit_live_specializations.def), --mode generic pursuit_live_kernel, and the
+bytes are those of the live rows.
 
 sample_maps as listed, max_steps=500, auto_reset=True; one launch per step through step_into.  Prints one JSON line: the HIP-event time per
 step, the kernel that ran, the algorithmic bytes per env-step (bench.algorithmic_bytes_per_env_step: 708 229 B at the CNN shape) and the
@@ -52,6 +57,7 @@ def main():
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--live", type=int, nargs=2, metavar=("P", "E"), default=None)
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -61,7 +67,10 @@ def main():
     mname, kw = SHAPES[a.shape]
     N, dev, P = a.envs, "cuda:0", kw["n_pursuers"]
     env = BatchedPursuitEvade(maps_of(mname), n_envs=N, device=dev, seed=0, max_steps=500, auto_reset=True,
-                              kernel="wave" if a.mode == "crowd" else "generic", **kw)   # "wave" raises where no crowd kernel was compiled
+                              kernel="wave" if a.mode == "crowd" else "generic",   # "wave" raises where no crowd kernel was compiled
+                              **(dict(kw, per_env_counts=True) if a.live else kw))
+    if a.live:
+        env.set_agent_counts(a.live[0], a.live[1])   # pending: the reset below takes them
     env.reset()
     gen = torch.Generator(device=dev)
     gen.manual_seed(0)
@@ -78,8 +87,8 @@ def main():
     t1.record()
     torch.cuda.synchronize()
     us = 1e3 * t0.elapsed_time(t1) / a.steps
-    nbytes = algorithmic_bytes_per_env_step(P, kw["n_evaders"], env.obs_dim, env.record_bytes)
-    print(json.dumps(dict(mode=a.mode, shape=a.shape, envs=N, kernel_kind=env.kernel_kind, us_per_step=round(us, 2),
+    nbytes = algorithmic_bytes_per_env_step(a.live[0] if a.live else P, kw["n_evaders"], env.obs_dim, env.record_bytes)
+    print(json.dumps(dict(mode=a.mode, shape=a.shape, envs=N, **(dict(live=a.live) if a.live else {}), kernel_kind=env.kernel_kind, us_per_step=round(us, 2),
                           algorithmic_bytes_per_env_step=nbytes, share_of_8e12=round(nbytes * N / (us * 1e-6) / 8.0e12, 4))))
 
 
