@@ -257,9 +257,9 @@ __global__ void pursuit_live_counts_kernel(const PursuitDev d, int32_t *pos_p, i
 }  // namespace
 
 // =================================================================== host side / C ABI
-struct WaveEntry;  // one compiled specialisation of pursuit_wave_kernel
-struct CrowdEntry; // one compiled specialisation of pursuit_crowd_kernel
-struct LiveCrowdEntry; // ... of pursuit_live_crowd_kernel
+namespace {
+struct FastEntry;  // one compiled specialisation: a line of the *_specializations.def lists (below)
+}
 
 struct madrl_pursuit {
     madrl_pursuit_config cfg;
@@ -270,11 +270,17 @@ struct madrl_pursuit {
     int64_t max_blocks;
     size_t lds_bytes;
     void *tables;  // one device allocation holding maps | cnt_tmpl | vtab | codes
-    // one-wavefront-per-env fast path (pursuit_wave.hpp), when a specialisation matches
-    const WaveEntry *wave;
+    // the fast path: the compile-time specialised kernel of this shape (find_fast), when there is one and the configuration is eligible
+    // for it -- one wavefront per env or a group of them (pursuit_wave.hpp, pursuit_group.hpp: wdev, wtables) or the crowd kernel
+    // (pursuit_crowd.hpp: cdev; it shares the generic kernel's tables)
+    const FastEntry *fast;
+    const FastEntry *fast_live = nullptr;  // the live-count instantiation of `fast` (pursuit_live_specializations.def), if compiled
     madrl::pw::WaveDev wdev;
-    void *zmask = nullptr;          // stale-zero masks of the fast path, [n_envs][64 * waves] dwords (pursuit_wave.hpp): the tail of
-                                    // the caller's state buffer (madrl_pursuit_state_bytes), not a library allocation
+    madrl::pc::CrowdDev cdev;
+    void *zmask = nullptr;          // what the fast path remembers about the observation buffer (zmask_len): the stale-zero masks,
+                                    // [n_envs][64 * waves] dwords per mask word (pursuit_wave.hpp), or the crowd kernel's one word per env,
+                                    // "channel 3 of the env's rows is not known to hold +0.0".  The tail of the caller's state buffer
+                                    // (madrl_pursuit_state_bytes), not a library allocation
     const void *zmask_obs = nullptr; // the observation buffer the masks describe; another buffer, a generic-kernel launch,
                                     // set_state or madrl_pursuit_invalidate_obs resets them to "nothing known"
     uint64_t step_count = 0;  // step launches so far (parity of the walk direction, see launch())
@@ -282,34 +288,35 @@ struct madrl_pursuit {
     void *wtables;
     int kernel_kind;  // MADRL_KERNEL_AUTO / _GENERIC / _WAVE (requested)
     const int32_t *pending = nullptr;      // per-env agent counts (madrl_pursuit_set_agent_counts): caller-owned int32 [n_envs][2], or off
-    const WaveEntry *wave_live = nullptr;  // the live-count instantiation of this shape (pursuit_live_specializations.def), if compiled
-    // the crowd kernel (pursuit_crowd.hpp): shapes above 64 of a kind that have an XC line and no X / XG line.  It shares the generic
-    // kernel's tables; `zmask` is then one word per env: "channel 3 of the env's rows is not known to hold +0.0"
-    const CrowdEntry *crowd = nullptr;
-    madrl::pc::CrowdDev cdev;
-    const LiveCrowdEntry *crowd_live = nullptr;  // the live-count instantiation of `crowd` (an XLC line of pursuit_live_specializations.def), if compiled
     hipEvent_t ev_fork = nullptr, ev_done = nullptr;   // madrl_pursuit_step_sharded: made by madrl_pursuit_create on the handle's device, destroyed with the handle
 };
 
 namespace {
 
-// ------------------------------------------------------------------ wave-kernel specialisations
-struct WaveGeom {
+// ------------------------------------------------------------------ fast-path dispatch (DESIGN.md §4.3 "Host dispatch")
+struct ShapeKey {
     int xs, ys, P, E, R, flatten;
-    int GW, PAD, GSZ, D, X_ID, X_SKIP;
-    int rec_bytes, off_gone, off_term;
-    int waves;  // wavefronts per env: 1 = pursuit_wave_kernel, > 1 = pursuit_group_kernel
-    int occ;    // resident wavefronts per SIMD the kernel's registers are allocated for
-    int mwords; // stale-zero mask dwords per lane (1: one bit per float4 slot in each byte, up to 8 slots per lane; the row-loop kernel: P / 8)
+    constexpr bool operator==(const ShapeKey &o) const {
+        return xs == o.xs && ys == o.ys && P == o.P && E == o.E && R == o.R && flatten == o.flatten;
+    }
 };
-}  // namespace
+ShapeKey key_of(const madrl_pursuit_config *c) { return {c->xs, c->ys, c->n_pursuers, c->n_evaders, c->obs_range, c->flatten ? 1 : 0}; }
 
-struct WaveEntry {
-    WaveGeom g;
-    void (*launch)(const madrl::pw::WaveDev &, const madrl::pw::WaveIO &, int mode, int64_t blocks, hipStream_t s);
+using WaveLaunch = void (*)(const pw::WaveDev &, const pw::WaveIO &, int mode, int64_t blocks, hipStream_t s);
+using CrowdLaunch = void (*)(const pc::CrowdDev &, const pc::CrowdIO &, const int32_t *pending, int mode, int64_t blocks, hipStream_t s);
+
+struct FastEntry {
+    ShapeKey key;
+    int nw;  // wavefronts per env: 1 = pursuit_wave_kernel, > 1 = pursuit_group_kernel; the crowd kernel's workgroup
+    int GSZ, D, rec_bytes, off_gone, off_term;  // madrl_pursuit_create holds these against layout() (GSZ: the crowd kernel only)
+    int GW, PAD, X_ID, X_SKIP;  // wave / group: what the table builder of madrl_pursuit_create reads
+    int mwords;      // wave / group: stale-zero mask dwords per lane (1: one bit per float4 slot in each byte, up to 8 slots per lane; the row-loop kernel: NS / 8)
+    int mask_bytes;  // per env, of `zmask`
+    int resident;    // workgroups of one launch: exactly the resident capacity of the 256 CUs
+    WaveLaunch launch_wave;    // the family: one of the two is set
+    CrowdLaunch launch_crowd;
+    constexpr bool crowd() const { return launch_crowd != nullptr; }
 };
-
-namespace {
 
 template <class S>
 void wave_launch(const pw::WaveDev &d, const pw::WaveIO &io, int mode, int64_t blocks, hipStream_t s) {
@@ -338,128 +345,50 @@ void group_launch(const pw::WaveDev &d, const pw::WaveIO &io, int mode, int64_t 
         hipLaunchKernelGGL((pw::pursuit_group_kernel<S, 1, false>), dim3((unsigned)blocks), dim3(S::NT), 0, s, d, io);
 }
 
+// resident: 4 SIMDs of S::OCC wavefronts (the occupancy the kernel's registers are allocated for) on each CU
 template <class S>
-constexpr WaveGeom wave_geom(int waves = 1, int occ = 4) {
-    return WaveGeom{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN, S::GW, S::PAD, S::GSZ, S::D, S::X_ID, S::X_SKIP,
-                    S::REC_BYTES, S::OFF_GONE, S::OFF_TERM, waves, occ, S::MWORDS};
+constexpr FastEntry wave_entry(int nw, WaveLaunch launch) {
+    return FastEntry{{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN}, nw, S::GSZ, S::D, S::REC_BYTES, S::OFF_GONE, S::OFF_TERM,
+                     S::GW, S::PAD, S::X_ID, S::X_SKIP, S::MWORDS, 256 * nw * S::MWORDS, 256 * 4 * S::OCC / nw, launch, nullptr};
 }
 
-#define X(XS, YS, NP, NE, R, FL) {wave_geom<pw::Shape<XS, YS, NP, NE, R, FL>>(1, pw::Shape<XS, YS, NP, NE, R, FL>::OCC), wave_launch<pw::Shape<XS, YS, NP, NE, R, FL>>},
-#define XG(XS, YS, NP, NE, R, FL, NW)
-const WaveEntry WAVE_TABLE[] = {
+// resident: what the LDS of a workgroup and 24 wavefronts per CU allow (at most 85 registers per lane; a 16-wavefront workgroup may use
+// 128 and is alone on its CU anyway)
+template <class S>
+constexpr FastEntry crowd_entry(CrowdLaunch launch) {
+    constexpr int by_lds = 160 * 1024 / (S::LDS_DWORDS * 4), by_waves = 24 / S::NW > 0 ? 24 / S::NW : 1;
+    return FastEntry{{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN}, S::NW, S::GSZ, S::D, S::REC_BYTES, S::OFF_GONE, S::OFF_TERM,
+                     0, 0, 0, 0, 0, 4, 256 * (by_lds < by_waves ? by_lds : by_waves), nullptr, launch};
+}
+
+// The fixed-shape kernels: the X / XG lines, then the XC lines -- a shape that has an X / XG line keeps the kernel of that line.  The
+// *.local.def lists are the lines added on this machine by `python -m madrl_amd.build --pursuit-shape / --pursuit-crowd-shape ...`
+// (git-ignored).
+#define X(XS, YS, NP, NE, R, FL) wave_entry<pw::Shape<XS, YS, NP, NE, R, FL>>(1, wave_launch<pw::Shape<XS, YS, NP, NE, R, FL>>),
+#define XG(XS, YS, NP, NE, R, FL, NW) wave_entry<pw::GShape<XS, YS, NP, NE, R, FL, NW>>(NW, group_launch<pw::GShape<XS, YS, NP, NE, R, FL, NW>>),
+#define XC(XS, YS, NP, NE, R, FL, NW) crowd_entry<pc::CShape<XS, YS, NP, NE, R, FL, NW>>(pc::crowd_launch<pc::CShape<XS, YS, NP, NE, R, FL, NW>>),
+constexpr FastEntry FAST_TABLE[] = {
 #include "pursuit_specializations.def"
-#if __has_include("pursuit_specializations.local.def")   // shapes added on this machine by `python -m madrl_amd.build --pursuit-shape ...` (git-ignored)
+#if __has_include("pursuit_specializations.local.def")
 #include "pursuit_specializations.local.def"
 #endif
-#undef X
-#undef XG
-#define X(XS, YS, NP, NE, R, FL)
-#define XG(XS, YS, NP, NE, R, FL, NW) {wave_geom<pw::GShape<XS, YS, NP, NE, R, FL, NW>>(NW, pw::GShape<XS, YS, NP, NE, R, FL, NW>::OCC), group_launch<pw::GShape<XS, YS, NP, NE, R, FL, NW>>},
-#include "pursuit_specializations.def"
-#if __has_include("pursuit_specializations.local.def")   // shapes added on this machine by `python -m madrl_amd.build --pursuit-shape ...` (git-ignored)
-#include "pursuit_specializations.local.def"
-#endif
-};
-#undef X
-#undef XG
-
-const WaveEntry *find_wave(const madrl_pursuit_config *c) {
-    if (c->flatten && !c->include_id) return nullptr;
-    for (const WaveEntry &e : WAVE_TABLE) {
-        const WaveGeom &g = e.g;
-        if (c->control_evaders && g.waves > 1) continue;  // evader control: the one-wavefront kernel or the generic one
-        if (g.xs == c->xs && g.ys == c->ys && g.P == c->n_pursuers && g.E == c->n_evaders && g.R == c->obs_range &&
-            g.flatten == (c->flatten ? 1 : 0))
-            return &e;
-    }
-    return nullptr;
-}
-
-// ------------------------------------------------------------------ crowd-kernel specialisations
-}  // namespace
-
-struct CrowdEntry {
-    int xs, ys, P, E, R, flatten;
-    int GSZ, D, rec_bytes, off_gone, off_term;
-    int nw;         // wavefronts per workgroup (= per env)
-    int lds_bytes;  // static LDS of the workgroup
-    void (*launch)(const madrl::pc::CrowdDev &, const madrl::pc::CrowdIO &, int mode, int64_t blocks, hipStream_t s);
-};
-
-// a live-count instantiation of a CrowdEntry's kernel: an XLC line of pursuit_live_specializations.def
-struct LiveCrowdEntry {
-    int xs, ys, P, E, R, flatten, nw;
-    void (*launch)(const madrl::pc::CrowdDev &, const madrl::pc::CrowdIO &, const int32_t *pending, int mode, int64_t blocks, hipStream_t s);
-};
-
-namespace {
-
-template <class S>
-constexpr CrowdEntry crowd_entry() {
-    return CrowdEntry{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN, S::GSZ, S::D, S::REC_BYTES, S::OFF_GONE, S::OFF_TERM, S::NW,
-                      S::LDS_DWORDS * 4, pc::crowd_launch<S>};
-}
-
-#define XC(XS, YS, NP, NE, R, FL, NW) crowd_entry<pc::CShape<XS, YS, NP, NE, R, FL, NW>>(),
-const CrowdEntry CROWD_TABLE[] = {
-#include "pursuit_crowd_specializations.def"
-#if __has_include("pursuit_crowd_specializations.local.def")   // shapes added on this machine by `python -m madrl_amd.build --pursuit-crowd-shape ...` (git-ignored)
-#include "pursuit_crowd_specializations.local.def"
-#endif
-};
-#undef XC
-
-// looked at only for shapes without an X / XG line: a shape that has one keeps the kernel it has.  Evader control runs on the generic kernel.
-const CrowdEntry *find_crowd(const madrl_pursuit_config *c) {
-    if ((c->flatten && !c->include_id) || c->control_evaders || find_wave(c)) return nullptr;
-    for (const CrowdEntry &e : CROWD_TABLE)
-        if (e.xs == c->xs && e.ys == c->ys && e.P == c->n_pursuers && e.E == c->n_evaders && e.R == c->obs_range &&
-            e.flatten == (c->flatten ? 1 : 0))
-            return &e;
-    return nullptr;
-}
-
-// (wave_launch of an LShape: no evader-control instantiations, madrl_pursuit_set_agent_counts refuses control_evaders; the group kernels
-// of the XLG lines are compiled in pursuit_live_group.hip)
-#define XLC(XS, YS, NP, NE, R, FL, NW)
-#define XL(XS, YS, NP, NE, R, FL) {wave_geom<pw::LShape<XS, YS, NP, NE, R, FL>>(1, pw::LShape<XS, YS, NP, NE, R, FL>::OCC), wave_launch<pw::LShape<XS, YS, NP, NE, R, FL>>},
-#define XLG(XS, YS, NP, NE, R, FL, NW) {wave_geom<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>(NW, pw::LGShape<XS, YS, NP, NE, R, FL, NW>::OCC), pw::live_group_launch<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>},
-const WaveEntry LIVE_TABLE[] = {
-#include "pursuit_live_specializations.def"
-#if __has_include("pursuit_live_specializations.local.def")   // capacities added on this machine by `python -m madrl_amd.build --pursuit-live-shape ...` (git-ignored)
-#include "pursuit_live_specializations.local.def"
-#endif
-};
-#undef XL
-#undef XLG
-#undef XLC
-
-// An XLC line is reached through the XC line of the same capacity (find_live_crowd), so it needs one with the same NW: without it the
-// line would compile a kernel that no handle can use.  `python -m madrl_amd.build --pursuit-live-crowd-shape` appends both.
-#define XC(XS, YS, NP, NE, R, FL, NW) || (xs == XS && ys == YS && np == NP && ne == NE && r == R && fl == FL && nw == NW)
-constexpr bool has_crowd_line(int xs, int ys, int np, int ne, int r, int fl, int nw) {
-    return false
 #include "pursuit_crowd_specializations.def"
 #if __has_include("pursuit_crowd_specializations.local.def")
 #include "pursuit_crowd_specializations.local.def"
 #endif
-        ;
-}
+};
+#undef X
+#undef XG
 #undef XC
-#define XL(XS, YS, NP, NE, R, FL)
-#define XLG(XS, YS, NP, NE, R, FL, NW)
-#define XLC(XS, YS, NP, NE, R, FL, NW) static_assert(has_crowd_line(XS, YS, NP, NE, R, FL, NW), "an XLC line needs the XC line of the same capacity with the same NW");
-#include "pursuit_live_specializations.def"
-#if __has_include("pursuit_live_specializations.local.def")
-#include "pursuit_live_specializations.local.def"
-#endif
-#undef XLC
 
-// the live-count instantiations of the crowd kernel (compiled in pursuit_live_crowd.hip): the geometry is the XC line's
-#define XL(XS, YS, NP, NE, R, FL)
-#define XLG(XS, YS, NP, NE, R, FL, NW)
-#define XLC(XS, YS, NP, NE, R, FL, NW) {XS, YS, NP, NE, R, FL, NW, pc::live_crowd_launch<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>},
-const LiveCrowdEntry LIVE_CROWD_TABLE[] = {
+// Their live-count instantiations (per-env agent counts), reached through the fixed line of the same shape and NW (find_live): same
+// geometry, same tables.  (wave_launch of an LShape: no evader-control instantiations, madrl_pursuit_set_agent_counts refuses
+// control_evaders; the XLG and XLC kernels are compiled in pursuit_live_group.hip and pursuit_live_crowd.hip.)  The .local.def list:
+// `python -m madrl_amd.build --pursuit-live-shape / --pursuit-live-crowd-shape ...`, which appends the fixed line too.
+#define XL(XS, YS, NP, NE, R, FL) wave_entry<pw::LShape<XS, YS, NP, NE, R, FL>>(1, wave_launch<pw::LShape<XS, YS, NP, NE, R, FL>>),
+#define XLG(XS, YS, NP, NE, R, FL, NW) wave_entry<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>(NW, pw::live_group_launch<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>),
+#define XLC(XS, YS, NP, NE, R, FL, NW) crowd_entry<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>(pc::live_crowd_launch<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>),
+constexpr FastEntry LIVE_TABLE[] = {
 #include "pursuit_live_specializations.def"
 #if __has_include("pursuit_live_specializations.local.def")
 #include "pursuit_live_specializations.local.def"
@@ -469,24 +398,37 @@ const LiveCrowdEntry LIVE_CROWD_TABLE[] = {
 #undef XLG
 #undef XLC
 
-// the live-count instantiation of the crowd entry `c` the handle uses (the same XC line, NW included)
-const LiveCrowdEntry *find_live_crowd(const CrowdEntry *c) {
-    if (!c) return nullptr;
-    for (const LiveCrowdEntry &e : LIVE_CROWD_TABLE)
-        if (e.xs == c->xs && e.ys == c->ys && e.P == c->P && e.E == c->E && e.R == c->R && e.flatten == c->flatten && e.nw == c->nw)
-            return &e;
+constexpr bool same_line(const FastEntry &a, const FastEntry &b) { return a.key == b.key && a.crowd() == b.crowd() && a.nw == b.nw; }
+
+// A live line without its fixed line would compile a kernel that no handle can use.
+constexpr bool live_lines_have_fixed_lines(bool crowd) {
+    for (const FastEntry &l : LIVE_TABLE) {
+        bool found = l.crowd() != crowd;
+        for (const FastEntry &f : FAST_TABLE) found = found || same_line(f, l);
+        if (!found) return false;
+    }
+    return true;
+}
+static_assert(live_lines_have_fixed_lines(false), "an XL / XLG line needs the X / XG line of the same capacity with the same NW");
+static_assert(live_lines_have_fixed_lines(true), "an XLC line needs the XC line of the same capacity with the same NW");
+
+// The line a configuration runs on, by the configuration alone (madrl_pursuit_state_bytes sizes the caller's buffer by it): the first of
+// its shape.  A flatten row without the id is not a whole number of float4; evader control has the one-wavefront kernel or the generic one.
+// A line that madrl_pursuit_create then finds not eligible leaves the handle on the generic kernel, not on a later line.
+const FastEntry *find_fast(const madrl_pursuit_config *c) {
+    if (c->flatten && !c->include_id) return nullptr;
+    const ShapeKey k = key_of(c);
+    for (const FastEntry &e : FAST_TABLE) {
+        if (c->control_evaders && (e.nw > 1 || e.crowd())) continue;
+        if (e.key == k) return &e;
+    }
     return nullptr;
 }
 
-// the live-count instantiation matching a shape whose fixed-shape entry `w` the handle uses (same geometry, same tables)
-const WaveEntry *find_live(const WaveEntry *w) {
-    if (!w) return nullptr;
-    for (const WaveEntry &e : LIVE_TABLE) {
-        const WaveGeom &g = e.g, &f = w->g;
-        if (g.xs == f.xs && g.ys == f.ys && g.P == f.P && g.E == f.E && g.R == f.R && g.flatten == f.flatten && g.waves == f.waves &&
-            g.rec_bytes == f.rec_bytes && g.GSZ == f.GSZ && g.D == f.D && g.X_ID == f.X_ID && g.mwords == f.mwords)
-            return &e;
-    }
+// the live-count instantiation of the fixed-shape entry `f` the handle uses
+const FastEntry *find_live(const FastEntry *f) {
+    for (const FastEntry &e : LIVE_TABLE)
+        if (f && same_line(e, *f)) return &e;
     return nullptr;
 }
 
@@ -585,67 +527,58 @@ void launch_nt(const madrl_pursuit *h, const PursuitIO &io, int mode, hipStream_
 }
 
 // the fast path this handle can use in its current mode (per-env agent counts: the live-count instantiation)
-bool has_wave(const madrl_pursuit *h) {
-    return h->pending ? (h->wave_live != nullptr || h->crowd_live != nullptr) : (h->wave != nullptr || h->crowd != nullptr);
+const FastEntry *fast_of(const madrl_pursuit *h) { return h->pending ? h->fast_live : h->fast; }
+bool has_wave(const madrl_pursuit *h) { return fast_of(h) != nullptr; }
+bool use_wave(const madrl_pursuit *h) { return has_wave(h) && h->kernel_kind != MADRL_KERNEL_GENERIC; }
+
+// bytes of what the fast path of line `f` remembers about the observation buffer (behind the records in the caller's state buffer)
+size_t zmask_len(const FastEntry *f, int64_t n_envs) { return f ? (size_t)n_envs * (size_t)f->mask_bytes : 0; }
+
+template <class IO>
+IO io_of(const PursuitIO &io) {
+    IO o{};
+    o.mask = io.mask; o.inj_pos = io.inj_pos; o.inj_map = io.inj_map; o.actions = io.actions;
+    o.inj_eact = io.inj_eact; o.obs = io.obs; o.rew = io.rew; o.done = io.done; o.removed = io.removed;
+    return o;
 }
 
-// bytes of what the fast path remembers about the observation buffer (behind the records in the caller's state buffer)
-size_t zmask_len(const madrl_pursuit *h) {
-    return h->crowd ? (size_t)h->dev.n_envs * 4 : (size_t)h->dev.n_envs * 256 * h->wave->g.waves * h->wave->g.mwords;
-}
-
-bool use_wave(const madrl_pursuit *h) {
-    return has_wave(h) && h->kernel_kind != MADRL_KERNEL_GENERIC;
+// the fast path's launch constants as madrl_pursuit_create made them, with the curriculum of this launch
+template <class Dev>
+Dev dev_now(Dev d, const PursuitDev &now) {
+    d.catchr = now.catchr; d.cw = now.cw; d.cw_env = now.cw_env; d.catchr_env = now.catchr_env;
+    return d;
 }
 
 int launch(madrl_pursuit *h, const PursuitIO &io, int mode, void *stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (use_wave(h) && h->crowd) {   // (per-env agent counts get here with a live-count instantiation only: has_wave)
-        pc::CrowdIO c;
-        c.mask = io.mask; c.inj_pos = io.inj_pos; c.inj_map = io.inj_map; c.actions = io.actions;
-        c.inj_eact = io.inj_eact; c.obs = io.obs; c.rew = io.rew; c.done = io.done; c.removed = io.removed;
-        // persistent workgroups, as many as are resident: the LDS of a workgroup and 24 wavefronts per CU (at most 85 registers per lane;
-        // a 16-wavefront workgroup may use 128 and is alone on its CU anyway)
-        const int by_lds = 160 * 1024 / h->crowd->lds_bytes, by_waves = 24 / h->crowd->nw > 0 ? 24 / h->crowd->nw : 1;
-        int64_t blocks = h->max_blocks > 0 ? h->max_blocks : 256 * (int64_t)(by_lds < by_waves ? by_lds : by_waves);
-        if (blocks > h->dev.n_envs) blocks = h->dev.n_envs;
-        pc::CrowdDev cd = h->cdev;
-        cd.catchr = h->dev.catchr; cd.cw = h->dev.cw; cd.cw_env = h->dev.cw_env; cd.catchr_env = h->dev.catchr_env;  // curriculum
-        if (h->zmask_obs != (const void *)io.obs) {  // unknown buffer contents: no env's channel 3 is known to be zero
-            MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0xFF, zmask_len(h), s));
-            h->zmask_obs = io.obs;
-        }
-        if (h->pending) h->crowd_live->launch(cd, c, h->pending, mode, blocks, s);
-        else h->crowd->launch(cd, c, mode, blocks, s);
-        MADRL_HIP_TRY(hipGetLastError());
-        return MADRL_OK;
-    }
     if (use_wave(h)) {
-        pw::WaveIO w;
-        w.mask = io.mask; w.inj_pos = io.inj_pos; w.inj_map = io.inj_map; w.actions = io.actions;
-        w.inj_eact = io.inj_eact; w.obs = io.obs; w.rew = io.rew; w.done = io.done; w.removed = io.removed;
-        w.flex = (io.inj_eact != nullptr || h->dev.catchr_env != nullptr) ? 1 : 0;
-        w.control_evaders = h->dev.train_pursuit ? 0 : 1;
-        int64_t blocks = h->max_blocks > 0 ? h->max_blocks : 256 * 4 * h->wave->g.occ / h->wave->g.waves;  // exactly the resident capacity
+        const FastEntry *f = fast_of(h);   // (the launcher; the geometry is the fixed line's, h->fast)
+        int64_t blocks = h->max_blocks > 0 ? h->max_blocks : h->fast->resident;   // persistent workgroups, as many as are resident
         if (blocks > h->dev.n_envs) blocks = h->dev.n_envs;
-        // Large batches: successive step launches walk the env range in opposite directions, so the rows written last by
-        // one step are the first ones touched by the next while they are still in the 256 MB memory-side cache.  Measured
-        // (scripts/sweep_wave.py, C2 shape): forward-only holds 7.2e8 env-steps/s up to 73 728 envs and collapses beyond
-        // (98 304: 4.7e8, 131 072: 4.5e8); alternating holds 6.4-6.7e8 from 81 920 to 131 072 but costs 6 % below.  Hence
-        // the switch at ~375 MB of rows + records per launch.  Env results do not depend on the processing order.
-        pw::WaveDev wd = h->wdev;
-        wd.catchr = h->dev.catchr; wd.cw = h->dev.cw; wd.cw_env = h->dev.cw_env; wd.catchr_env = h->dev.catchr_env;  // curriculum
         if (h->zmask_obs != (const void *)io.obs) {  // unknown buffer contents: every cell "not known to be zero"
-            MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0xFF, (size_t)h->dev.n_envs * 256 * h->wave->g.waves * h->wave->g.mwords, s));
+            MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0xFF, zmask_len(h->fast, h->dev.n_envs), s));
             h->zmask_obs = io.obs;
         }
-        if (mode == 1) {
-            bool alternate = (double)h->dev.n_envs * (4.0 * h->dev.P * h->dev.D + 2.0 * h->dev.rec_bytes) > 375e6;
-            if (h->walk_mode != 0) alternate = h->walk_mode == 1;
-            if (alternate) wd.reverse = (int32_t)(h->step_count++ & 1);
+        if (f->crowd()) {
+            f->launch_crowd(dev_now(h->cdev, h->dev), io_of<pc::CrowdIO>(io), h->pending, mode, blocks, s);
+        } else {
+            pw::WaveIO w = io_of<pw::WaveIO>(io);
+            w.flex = (io.inj_eact != nullptr || h->dev.catchr_env != nullptr) ? 1 : 0;
+            w.control_evaders = h->dev.train_pursuit ? 0 : 1;
+            // Large batches: successive step launches walk the env range in opposite directions, so the rows written last by
+            // one step are the first ones touched by the next while they are still in the 256 MB memory-side cache.  Measured
+            // (scripts/sweep_wave.py, C2 shape): forward-only holds 7.2e8 env-steps/s up to 73 728 envs and collapses beyond
+            // (98 304: 4.7e8, 131 072: 4.5e8); alternating holds 6.4-6.7e8 from 81 920 to 131 072 but costs 6 % below.  Hence
+            // the switch at ~375 MB of rows + records per launch.  Env results do not depend on the processing order.
+            pw::WaveDev wd = dev_now(h->wdev, h->dev);
+            if (mode == 1) {
+                bool alternate = (double)h->dev.n_envs * (4.0 * h->dev.P * h->dev.D + 2.0 * h->dev.rec_bytes) > 375e6;
+                if (h->walk_mode != 0) alternate = h->walk_mode == 1;
+                if (alternate) wd.reverse = (int32_t)(h->step_count++ & 1);
+            }
+            wd.pending = h->pending;
+            f->launch_wave(wd, w, mode, blocks, s);
         }
-        wd.pending = h->pending;
-        (h->pending ? h->wave_live : h->wave)->launch(wd, w, mode, blocks, s);
         MADRL_HIP_TRY(hipGetLastError());
         return MADRL_OK;
     }
@@ -665,15 +598,30 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, void *stream) {
     return MADRL_OK;
 }
 
-// caller-owned state buffer = [n_envs packed records][pad to 256 B][stale-zero masks of the fast path, 256 B per env, wavefront and
-// mask word][flag plane, one dword per env]
+// caller-owned state buffer = [n_envs packed records][pad to 256 B][what the configuration's fast path remembers about the observation
+// buffer (FastEntry::mask_bytes per env): stale-zero masks, 256 B per wavefront and mask word, or the crowd kernel's one word][flag plane,
+// one dword per env]
 uint64_t zmask_offset(int rec_bytes, int64_t n_envs) { return align_up((uint64_t)rec_bytes * (uint64_t)n_envs, 256); }
-uint64_t zmask_bytes(const madrl_pursuit_config *cfg, int64_t n_envs) {
-    const WaveEntry *w = find_wave(cfg);
-    if (!w && find_crowd(cfg)) return (uint64_t)n_envs * 4u;   // the crowd kernel: one word per env
-    return w ? (uint64_t)n_envs * 256u * (uint64_t)w->g.waves * (uint64_t)w->g.mwords : 0u;
+uint64_t flags_offset(const madrl_pursuit_config *cfg, int rec_bytes, int64_t n_envs) { return zmask_offset(rec_bytes, n_envs) + zmask_len(find_fast(cfg), n_envs); }
+
+// what madrl_pursuit_create holds a line's compiled geometry against: the configuration's record and row (layout())
+bool same_record(const FastEntry &f, const PursuitDev &d) {
+    return f.rec_bytes == d.rec_bytes && f.off_gone == d.off_gone && f.off_term == d.off_term && f.D == d.D;
 }
-uint64_t flags_offset(const madrl_pursuit_config *cfg, int rec_bytes, int64_t n_envs) { return zmask_offset(rec_bytes, n_envs) + zmask_bytes(cfg, n_envs); }
+
+// the launch constants WaveDev and CrowdDev share with the generic kernel's
+template <class Dev>
+void fill_common(Dev &w, const PursuitDev &d) {
+    memset(&w, 0, sizeof(w));
+    w.n_catch = d.n_catch; w.surround = d.surround; w.reward_global = d.reward_global; w.sample_maps = d.sample_maps;
+    w.n_maps = d.n_maps; w.max_steps = d.max_steps; w.auto_reset = d.auto_reset; w.max_opponents = d.max_opponents;
+    w.k0 = d.k0; w.k1 = d.k1; w.gid_base = d.gid_base;
+    w.catchr = d.catchr; w.term_pursuit = d.term_pursuit; w.urgency = d.urgency; w.cw = d.cw;
+    w.n_envs = d.n_envs;
+    w.vtab = d.vtab;
+    w.state = d.state;
+    w.flags = d.flags;
+}
 
 int pick_threads(const PursuitDev &d, int requested) {
     int thr = requested;
@@ -823,18 +771,18 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
     d.vtab = reinterpret_cast<const float *>(tb + off_vtab);
     d.codes = reinterpret_cast<const uint32_t *>(tb + off_codes);
 
-    // ---- one-wavefront-per-env fast path tables (pursuit_wave.hpp)
-    h->wave = find_wave(cfg);
+    // ---- the fast path of this shape; one wavefront or a group of them per env: its tables (pursuit_wave.hpp)
+    h->fast = find_fast(cfg);
     h->wtables = nullptr;
     h->kernel_kind = MADRL_KERNEL_AUTO;
-    if (h->wave) {
-        const WaveGeom &g = h->wave->g;
+    if (h->fast && !h->fast->crowd()) {
+        const FastEntry &g = *h->fast;
         const int need_words = ((int)cells + 3) / 4;
         const int fstride = g.GSZ + need_words;
         const size_t w_codes = (size_t)fstride * d.n_maps;
         // after the maps: slot codes [D] | empty count layer [GSZ] | per-thread slot table [NS][6][NT] -- or, for shapes with more than 8
         // slots per thread (pursuit_group.hpp, TABLED), one packed entry of two dwords per float4 of a pursuer's row [DV][2]
-        const int NT = 64 * g.waves, DV = d.D / 4, NQ = d.P * DV, NS = (NQ + NT - 1) / NT;
+        const int NT = 64 * g.nw, DV = d.D / 4, NQ = d.P * DV, NS = (NQ + NT - 1) / NT;
         const bool tabled = NS > 8;
         const size_t w_tmpl = w_codes + (size_t)d.D, w_slots = w_tmpl + (size_t)g.GSZ;
         std::vector<uint32_t> wh(w_slots + (tabled ? (size_t)2 * DV : (size_t)NS * 6 * NT), 0u);
@@ -860,8 +808,7 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
         uint32_t unit_bits;
         { const float unit = (float)1 / (float)cfg->layer_norm; memcpy(&unit_bits, &unit, 4); }
         bool eligible = (wall_bits != 0u) && (fill_bits != 0u) && (unit_bits >> 24) >= 0x20u && (unit_bits >> 24) < 0x80u &&
-                        (fill_bits >> 24) >= 0x20u && (fill_bits >> 24) < 0x80u && g.rec_bytes == d.rec_bytes &&
-                        g.off_gone == d.off_gone && g.off_term == d.off_term && g.D == d.D &&
+                        (fill_bits >> 24) >= 0x20u && (fill_bits >> 24) < 0x80u && same_record(g, d) &&
                         n_envs < 0x7FF00000ll;  // the fast kernels index envs with 32-bit integers (index + workgroup count < 2^31)
         for (int r = 0; r < d.D; ++r) {
             int c, i, j;
@@ -919,48 +866,29 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
                 delete h;
                 return fail(MADRL_EHIP, "wave tables: %s", hipGetErrorString(e));
             }
+            h->zmask = (uint8_t *)state_dev + zmask_offset(d.rec_bytes, n_envs);  // caller-owned, like the records
             pw::WaveDev &w = h->wdev;
-            memset(&w, 0, sizeof(w));
-            w.n_catch = d.n_catch; w.surround = d.surround; w.reward_global = d.reward_global;
-            w.sample_maps = d.sample_maps; w.n_maps = d.n_maps; w.max_steps = d.max_steps; w.auto_reset = d.auto_reset;
-            w.max_opponents = d.max_opponents;
+            fill_common(w, d);
             w.fmap_stride = fstride;
-            w.k0 = d.k0; w.k1 = d.k1; w.gid_base = d.gid_base;
-            w.catchr = d.catchr; w.term_pursuit = d.term_pursuit; w.urgency = d.urgency; w.cw = d.cw;
-            w.n_envs = d.n_envs;
             w.fmaps = reinterpret_cast<const uint32_t *>(h->wtables);
-            w.vtab = d.vtab;
             w.cnt_tmpl = reinterpret_cast<const uint32_t *>(h->wtables) + w_tmpl;
             w.slot_tab = reinterpret_cast<const uint32_t *>(h->wtables) + w_slots;
-            w.state = d.state;
-            w.flags = d.flags;
-            h->zmask = (uint8_t *)state_dev + zmask_offset(d.rec_bytes, n_envs);  // caller-owned, like the records
             w.zmask = reinterpret_cast<uint32_t *>(h->zmask);
         } else {
-            h->wave = nullptr;
+            h->fast = nullptr;
         }
-    }
-    h->wave_live = find_live(h->wave);
-    // ---- the crowd kernel: the generic kernel's tables and record, when the compiled geometry is this configuration's
-    h->crowd = find_crowd(cfg);
-    if (h->crowd && !(h->crowd->GSZ == d.GSZ && h->crowd->D == d.D && h->crowd->rec_bytes == d.rec_bytes &&
-                      h->crowd->off_gone == d.off_gone && h->crowd->off_term == d.off_term))
-        h->crowd = nullptr;
-    if (h->crowd) {
-        pc::CrowdDev &c = h->cdev;
-        memset(&c, 0, sizeof(c));
-        c.n_catch = d.n_catch; c.surround = d.surround; c.reward_global = d.reward_global; c.sample_maps = d.sample_maps;
-        c.n_maps = d.n_maps; c.max_steps = d.max_steps; c.auto_reset = d.auto_reset; c.max_opponents = d.max_opponents;
-        c.map_stride = d.map_stride;
-        c.k0 = d.k0; c.k1 = d.k1; c.gid_base = d.gid_base;
-        c.catchr = d.catchr; c.term_pursuit = d.term_pursuit; c.urgency = d.urgency; c.cw = d.cw;
-        c.n_envs = d.n_envs;
-        c.maps = d.maps; c.vtab = d.vtab;
-        c.state = d.state; c.flags = d.flags;
+    } else if (h->fast && h->fast->GSZ == d.GSZ && same_record(*h->fast, d)) {
+        // ---- the crowd kernel: the generic kernel's tables and record, when the compiled geometry is this configuration's
         h->zmask = (uint8_t *)state_dev + zmask_offset(d.rec_bytes, n_envs);  // caller-owned, like the records
+        pc::CrowdDev &c = h->cdev;
+        fill_common(c, d);
+        c.map_stride = d.map_stride;
+        c.maps = d.maps;
         c.ch3 = reinterpret_cast<const uint32_t *>(h->zmask);
+    } else {
+        h->fast = nullptr;
     }
-    h->crowd_live = find_live_crowd(h->crowd);
+    h->fast_live = find_live(h->fast);
 
     h->walk_mode = 0;
     h->max_blocks = 0;
@@ -1029,10 +957,10 @@ int madrl_pursuit_set_kernel(madrl_pursuit *h, int32_t kind) {
     if (!h) return fail(MADRL_EINVAL, "handle is NULL");
     if (kind != MADRL_KERNEL_AUTO && kind != MADRL_KERNEL_GENERIC && kind != MADRL_KERNEL_WAVE)
         return fail(MADRL_EINVAL, "unknown kernel kind %d", kind);
-    if (kind == MADRL_KERNEL_WAVE && h->pending && !h->wave_live && !h->crowd_live)
+    if (kind == MADRL_KERNEL_WAVE && h->pending && !h->fast_live)
         return fail(MADRL_EINVAL, "per-env agent counts: no live-count specialisation was compiled for this capacity "
                     "(see madrl_amd/csrc/pursuit_live_specializations.def)");
-    if (kind == MADRL_KERNEL_WAVE && !h->wave && !h->crowd)
+    if (kind == MADRL_KERNEL_WAVE && !h->fast)
         return fail(MADRL_EINVAL, "no one-wavefront-per-env specialisation was compiled for this configuration "
                     "(see madrl_amd/csrc/pursuit_specializations.def)");
     h->kernel_kind = kind;
@@ -1142,7 +1070,7 @@ int madrl_pursuit_invalidate_obs(madrl_pursuit *h) {
 int madrl_pursuit_declare_obs_zero(madrl_pursuit *h, const float *obs_dev, void *stream) {
     if (!h || !obs_dev) return fail(MADRL_EINVAL, "declare_obs_zero: NULL argument");
     if (h->zmask) {   // every cell of that buffer is known to hold +0.0f: no stale cell can need protecting
-        MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0, zmask_len(h), (hipStream_t)stream));
+        MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0, zmask_len(h->fast, h->dev.n_envs), (hipStream_t)stream));
         h->zmask_obs = obs_dev;
     }
     return MADRL_OK;
@@ -1167,7 +1095,7 @@ int madrl_pursuit_set_agent_counts(madrl_pursuit *h, const int32_t *pending_dev)
     if (!h) return fail(MADRL_EINVAL, "handle is NULL");
     if (pending_dev && !h->dev.train_pursuit)
         return fail(MADRL_EINVAL, "per-env agent counts with control_evaders=1 (train_pursuit=False) are not supported");
-    if (pending_dev && h->kernel_kind == MADRL_KERNEL_WAVE && !h->wave_live && !h->crowd_live)
+    if (pending_dev && h->kernel_kind == MADRL_KERNEL_WAVE && !h->fast_live)
         return fail(MADRL_EINVAL, "per-env agent counts: kernel WAVE was requested and no live-count specialisation was compiled for this "
                     "capacity (see madrl_amd/csrc/pursuit_live_specializations.def)");
     h->pending = pending_dev;
