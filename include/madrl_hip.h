@@ -171,6 +171,26 @@ int madrl_pursuit_step(madrl_pursuit *h, const int32_t *actions_dev,
                        const int32_t *inj_evader_actions_dev, float *obs_dev, float *rew_dev,
                        uint8_t *done_dev, int32_t *removed_dev, void *stream);
 
+/* madrl_pursuit_step with the observations written to ANOTHER buffer: after the call obs_next_dev holds, element for element, what
+ * obs_prev_dev would hold after madrl_pursuit_step(..., obs_prev_dev, ...) -- the cells the in-place step does not store, the rows of
+ * absent observers (evader control, per-env agent counts) and both observation passes of a fused auto-reset included.  obs_prev_dev
+ * is not written; rew / done / removed, the flag plane and the state records are those of madrl_pursuit_step, bit for bit.  A
+ * rollout that keeps its observations steps from trajectory slot t to slot t + 1 with no copy.
+ *   obs_prev_dev == obs_next_dev is madrl_pursuit_step; two buffers that overlap otherwise, a NULL pointer or a buffer that is not
+ *   16-byte aligned: MADRL_EINVAL.
+ *   What the fast path knows about the observation buffer (stale-zero masks, the crowd kernel's channel-3 word) describes
+ *   obs_next_dev after the call: a madrl_pursuit_step on it, or a step_to from it, needs no madrl_pursuit_invalidate_obs and loses
+ *   nothing.  obs_prev_dev becomes an unknown buffer to the library.
+ *   Only the float4s of obs_prev_dev that hold a kept cell not known to be zero, and the rows of absent observers, are read.
+ * Two-buffer fast kernels exist for the one-wavefront (X / XL) and crowd (XC / XLC) shapes listed in
+ * madrl_amd/csrc/pursuit_to_specializations.def.  Every other handle -- multi-wavefront (XG / XLG) shapes and control_evaders
+ * included -- runs step_to on the generic kernel (same values; a generic launch voids the fast path's knowledge, as it always does).
+ * madrl_pursuit_step_to_kernel_kind: MADRL_KERNEL_WAVE / MADRL_KERNEL_GENERIC, what a step_to of this handle launches. */
+int madrl_pursuit_step_to(madrl_pursuit *h, const int32_t *actions_dev, const int32_t *inj_evader_actions_dev,
+                          const float *obs_prev_dev, float *obs_next_dev, float *rew_dev, uint8_t *done_dev,
+                          int32_t *removed_dev, void *stream);
+int madrl_pursuit_step_to_kernel_kind(madrl_pursuit *h, int32_t *out);
+
 /* One batch stepped as n_shards independent sub-batches, each a handle of its own (created with env_id_base advanced by its offset)
  * on its own HIP stream: ONE host call issues every launch.  Env instances never interact (the reference's own parallelism is N
  * pickled env copies in sampler workers, runners/rurllab.py:259), so nothing orders sub-batch A's step t + 1 against sub-batch

@@ -105,6 +105,8 @@ SIGNATURES = {
     "madrl_pursuit_kernel_kind": (C.c_int, [_vp, _vp]),
     "madrl_pursuit_reset": (C.c_int, [_vp] * 6),
     "madrl_pursuit_step": (C.c_int, [_vp] * 8),
+    "madrl_pursuit_step_to": (C.c_int, [_vp] * 9),
+    "madrl_pursuit_step_to_kernel_kind": (C.c_int, [_vp, _vp]),
     "madrl_pursuit_get_state": (C.c_int, [_vp] * 10),
     "madrl_pursuit_set_state": (C.c_int, [_vp] * 10),
     "madrl_waterworld_obs_dim": (C.c_int, [_vp, _vp]),
@@ -187,3 +189,15 @@ def ptr(t):
 
 def current_stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def obs_destination(obs_out, like):
+    """`obs_out=` of the envs' step(): a caller's tensor a step kernel writes its observations to (a trajectory slot) instead of the env's own
+    buffer `like` -- checked (float32, contiguous, same device and size) and viewed in that buffer's shape"""
+    if type(obs_out) is not torch.Tensor:
+        raise TypeError("obs_out must be a torch.Tensor, got %s" % type(obs_out).__name__)
+    if obs_out.dtype is not torch.float32 or obs_out.device != like.device or not obs_out.is_contiguous() or obs_out.numel() != like.numel():
+        raise ValueError("obs_out must be a contiguous float32 tensor of %d elements on %s (got %s, %s, %s, contiguous=%s)"
+                         % (like.numel(), like.device, tuple(obs_out.shape), obs_out.dtype, obs_out.device, obs_out.is_contiguous()))
+    return obs_out.view(like.shape)
+

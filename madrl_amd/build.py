@@ -5,6 +5,7 @@
     python -m madrl_amd.build --pursuit-live-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN # ... and per-env agent counts at this capacity
     python -m madrl_amd.build --pursuit-crowd-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN # more than 64 pursuers or evaders: the crowd kernel
     python -m madrl_amd.build --pursuit-live-crowd-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN # ... and per-env agent counts on it
+    python -m madrl_amd.build --pursuit-to-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN   # the two-buffer step (step_to) on this shape's fast kernel
     python -m madrl_amd.build --waterworld-shape N_PURSUERS N_EVADERS N_POISON N_SENSORS [OBS_DIM]
 
 The fast paths (one wavefront -- or a group of wavefronts -- per env, everything about the shape a compile-time constant) exist for the
@@ -186,6 +187,33 @@ def add_pursuit_live_crowd_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatt
     return _append_local("pursuit_live_specializations.def", live + "   // added by madrl_amd.build") or added_fixed
 
 
+def pursuit_to_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True):
+    """-> (two-buffer line, fixed line) that give step_to() of a shape its fast kernel: X(...) over an X(...) shape, XC(..., NW) over an
+    XC(..., NW) shape -- or (None, why not): the multi-wavefront (XG) kernel has no two-buffer instantiation, and a shape without an
+    X / XC fast path has nothing to stand on.  Pure: nothing is written."""
+    kind, nw = pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
+    args = "%d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)))
+    if kind == "X":
+        return "X(%s)" % args, "X(%s)" % args
+    if kind == "XG":
+        return None, "its fast path is the multi-wavefront kernel (XG, %d wavefronts), which has no two-buffer instantiation" % nw
+    ckind, cnw = pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
+    if ckind is None:
+        return None, "the shape has no X / XC fast path (one wavefront: %s; crowd kernel: %s)" % (nw, cnw)
+    return "XC(%s, %d)" % (args, cnw), "XC(%s, %d)" % (args, cnw)
+
+
+def add_pursuit_to_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
+    """step_to() of this shape on the two-buffer instantiation of its fast kernel: the line in the local two-buffer list, and the X / XC
+    line it stands on in the local fixed list if it is missing"""
+    line, fixed = pursuit_to_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten)
+    if line is None:
+        raise ValueError("no two-buffer fast kernel for this PursuitEvade shape: %s (step_to runs on the generic kernel)" % fixed)
+    added_fixed = _append_local("pursuit_specializations.def" if fixed.startswith("X(") else "pursuit_crowd_specializations.def",
+                                fixed + "   // added by madrl_amd.build")
+    return _append_local("pursuit_to_specializations.def", line + "   // added by madrl_amd.build") or added_fixed
+
+
 def add_waterworld_shape(n_pursuers, n_evaders, n_poison, n_sensors, obs_dim=None):
     if obs_dim is None:
         obs_dim = n_sensors * 7 + 2 + 1          # speed features and the agent id (the reference's defaults)
@@ -262,6 +290,7 @@ if __name__ == "__main__":
     for flag, fn, lo, hi in (("--pursuit-shape", add_pursuit_shape, 6, 6), ("--pursuit-live-shape", add_pursuit_live_shape, 6, 6),
                              ("--pursuit-crowd-shape", add_pursuit_crowd_shape, 6, 6),
                              ("--pursuit-live-crowd-shape", add_pursuit_live_crowd_shape, 6, 6),
+                             ("--pursuit-to-shape", add_pursuit_to_shape, 6, 6),
                              ("--waterworld-shape", add_waterworld_shape, 4, 5)):
         while flag in argv:
             i = argv.index(flag)

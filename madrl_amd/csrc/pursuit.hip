@@ -132,13 +132,27 @@ static_assert(MAX_COUNT <= 1024, "np_pairwise_sum: four levels of numpy's split"
 template <int NT>
 __global__ void pursuit_kernel(const PursuitDev d, const PursuitIO io, const int mode) {
     constexpr bool LIVE = false;
+    constexpr bool TO = false;
     const int32_t *const pending = nullptr;
+    [[maybe_unused]] const float *const obs_prev = nullptr;
 #include "pursuit_generic.inc"
 }
 
 template <int NT>
 __global__ void pursuit_live_kernel(const PursuitDev d, const PursuitIO io, const int mode, const int32_t *pending) {
     constexpr bool LIVE = true;
+    constexpr bool TO = false;
+    [[maybe_unused]] const float *const obs_prev = nullptr;
+#include "pursuit_generic.inc"
+}
+
+// The two-buffer step (madrl_pursuit_step_to) of every handle that has no two-buffer fast kernel: the step's rows go to io.obs, and what
+// an in-place step leaves alone comes from obs_prev (write_obs in the body).
+template <int NT, bool LIVE_>
+__global__ void pursuit_to_kernel(const PursuitDev d, const PursuitIO io, [[maybe_unused]] const int32_t *pending, const float *const obs_prev) {
+    constexpr bool LIVE = LIVE_;
+    constexpr bool TO = true;
+    const int mode = 1;
 #include "pursuit_generic.inc"
 }
 
@@ -398,6 +412,51 @@ constexpr FastEntry LIVE_TABLE[] = {
 #undef XLG
 #undef XLC
 
+// The two-buffer step kernels (madrl_pursuit_step_to, pursuit_to.hip): reached through the fixed line of the same shape and NW, for a handle
+// with per-env agent counts through its live line.  A handle without an entry here runs step_to on the generic kernel.
+using WaveToLaunch = void (*)(const pw::WaveDev &, const pw::WaveIO &, int64_t blocks, hipStream_t s);
+using CrowdToLaunch = void (*)(const pc::CrowdDev &, const pc::CrowdIO &, const int32_t *pending, const float *obs_prev, int64_t blocks, hipStream_t s);
+struct ToEntry {
+    ShapeKey key;
+    int nw;
+    bool live;
+    WaveToLaunch launch_wave;    // one of the two is set
+    CrowdToLaunch launch_crowd;
+    constexpr bool crowd() const { return launch_crowd != nullptr; }
+};
+#define X(XS, YS, NP, NE, R, FL) ToEntry{{XS, YS, NP, NE, R, FL}, 1, false, pw::wave_to_launch<pw::TShape<XS, YS, NP, NE, R, FL>>, nullptr},
+#define XL(XS, YS, NP, NE, R, FL) ToEntry{{XS, YS, NP, NE, R, FL}, 1, true, pw::wave_to_launch<pw::TLShape<XS, YS, NP, NE, R, FL>>, nullptr},
+#define XC(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, false, nullptr, pc::crowd_to_launch<pc::CShape<XS, YS, NP, NE, R, FL, NW>>},
+#define XLC(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, true, nullptr, pc::crowd_to_launch<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>},
+constexpr ToEntry TO_TABLE[] = {
+#include "pursuit_to_specializations.def"
+#if __has_include("pursuit_to_specializations.local.def")
+#include "pursuit_to_specializations.local.def"
+#endif
+};
+#undef X
+#undef XL
+#undef XC
+#undef XLC
+
+// A two-buffer line without its fixed line would compile a kernel that no handle can use.
+constexpr bool to_lines_have_fixed_lines() {
+    for (const ToEntry &t : TO_TABLE) {
+        bool found = false;
+        for (const FastEntry &f : FAST_TABLE) found = found || (f.key == t.key && f.crowd() == t.crowd() && f.nw == t.nw);
+        if (!found) return false;
+    }
+    return true;
+}
+static_assert(to_lines_have_fixed_lines(), "a line of pursuit_to_specializations.def needs the X line (X / XL) or the XC line with the same NW (XC / XLC) of its shape");
+
+// the two-buffer kernel that stands on the fast line `f` (live: the per-env-count instantiation)
+const ToEntry *find_to(const FastEntry *f, bool live) {
+    for (const ToEntry &t : TO_TABLE)
+        if (f && t.key == f->key && t.crowd() == f->crowd() && t.nw == f->nw && t.live == live) return &t;
+    return nullptr;
+}
+
 constexpr bool same_line(const FastEntry &a, const FastEntry &b) { return a.key == b.key && a.crowd() == b.crowd() && a.nw == b.nw; }
 
 // A live line without its fixed line would compile a kernel that no handle can use.
@@ -592,6 +651,66 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, void *stream) {
         case 6: launch_nt<6>(h, io, mode, s); break;
         case 7: launch_nt<7>(h, io, mode, s); break;
         case 8: launch_nt<8>(h, io, mode, s); break;
+        default: return fail(MADRL_EINVAL, "internal: nt=%d", h->nt);
+    }
+    MADRL_HIP_TRY(hipGetLastError());
+    return MADRL_OK;
+}
+
+template <int NT>
+void launch_to_nt(const madrl_pursuit *h, const PursuitIO &io, const float *obs_prev, hipStream_t s) {
+    int64_t blocks = h->dev.n_envs;
+    if (h->max_blocks > 0 && blocks > h->max_blocks) blocks = h->max_blocks;
+    if (h->pending)
+        hipLaunchKernelGGL((pursuit_to_kernel<NT, true>), dim3((unsigned)blocks), dim3((unsigned)h->threads), h->lds_bytes, s,
+                           h->dev, io, h->pending, obs_prev);
+    else
+        hipLaunchKernelGGL((pursuit_to_kernel<NT, false>), dim3((unsigned)blocks), dim3((unsigned)h->threads), h->lds_bytes, s,
+                           h->dev, io, h->pending, obs_prev);
+}
+
+// the two-buffer fast kernel a step_to of this handle launches, or nullptr: the generic kernel (evader control, multi-wavefront lines and
+// shapes without a line in pursuit_to_specializations.def)
+const ToEntry *to_of(const madrl_pursuit *h) {
+    if (!use_wave(h) || !h->dev.train_pursuit) return nullptr;
+    return find_to(h->fast, h->pending != nullptr);
+}
+
+// madrl_pursuit_step_to: the step of launch(h, io, 1, ...) with its rows in io.obs and the kept cells from obs_prev
+int launch_to(madrl_pursuit *h, const PursuitIO &io, const float *obs_prev, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (const ToEntry *t = to_of(h)) {
+        int64_t blocks = h->max_blocks > 0 ? h->max_blocks : h->fast->resident;
+        if (blocks > h->dev.n_envs) blocks = h->dev.n_envs;
+        if (h->zmask_obs != (const void *)obs_prev)  // the masks describe the buffer the kept cells are read from
+            MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0xFF, zmask_len(h->fast, h->dev.n_envs), s));
+        h->zmask_obs = io.obs;  // ... and, after this launch, the buffer it wrote; obs_prev is an unknown buffer from here on
+        if (t->crowd()) {
+            t->launch_crowd(dev_now(h->cdev, h->dev), io_of<pc::CrowdIO>(io), h->pending, obs_prev, blocks, s);
+        } else {
+            pw::WaveIO w = io_of<pw::WaveIO>(io);
+            w.flex = 1;
+            w.obs_prev = obs_prev;
+            pw::WaveDev wd = dev_now(h->wdev, h->dev);
+            bool alternate = (double)h->dev.n_envs * (4.0 * h->dev.P * h->dev.D + 2.0 * h->dev.rec_bytes) > 375e6;   // as launch()
+            if (h->walk_mode != 0) alternate = h->walk_mode == 1;
+            if (alternate) wd.reverse = (int32_t)(h->step_count++ & 1);
+            wd.pending = h->pending;
+            t->launch_wave(wd, w, blocks, s);
+        }
+        MADRL_HIP_TRY(hipGetLastError());
+        return MADRL_OK;
+    }
+    h->zmask_obs = nullptr;  // the generic kernel does not maintain the fast path's stale-zero masks
+    switch (h->nt) {
+        case 1: launch_to_nt<1>(h, io, obs_prev, s); break;
+        case 2: launch_to_nt<2>(h, io, obs_prev, s); break;
+        case 3: launch_to_nt<3>(h, io, obs_prev, s); break;
+        case 4: launch_to_nt<4>(h, io, obs_prev, s); break;
+        case 5: launch_to_nt<5>(h, io, obs_prev, s); break;
+        case 6: launch_to_nt<6>(h, io, obs_prev, s); break;
+        case 7: launch_to_nt<7>(h, io, obs_prev, s); break;
+        case 8: launch_to_nt<8>(h, io, obs_prev, s); break;
         default: return fail(MADRL_EINVAL, "internal: nt=%d", h->nt);
     }
     MADRL_HIP_TRY(hipGetLastError());
@@ -940,6 +1059,11 @@ int madrl_pursuit_set_launch(madrl_pursuit *h, int32_t threads, int64_t max_bloc
         (void)MADRL_SET_LDS(1); (void)MADRL_SET_LDS(2); (void)MADRL_SET_LDS(3); (void)MADRL_SET_LDS(4);
         (void)MADRL_SET_LDS(5); (void)MADRL_SET_LDS(6); (void)MADRL_SET_LDS(7); (void)MADRL_SET_LDS(8);
 #undef MADRL_SET_LDS
+#define MADRL_SET_LDS(NT) ((void)hipFuncSetAttribute((const void *)pursuit_to_kernel<NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), \
+                           hipFuncSetAttribute((const void *)pursuit_to_kernel<NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))
+        (void)MADRL_SET_LDS(1); (void)MADRL_SET_LDS(2); (void)MADRL_SET_LDS(3); (void)MADRL_SET_LDS(4);
+        (void)MADRL_SET_LDS(5); (void)MADRL_SET_LDS(6); (void)MADRL_SET_LDS(7); (void)MADRL_SET_LDS(8);
+#undef MADRL_SET_LDS
     }
     return MADRL_OK;
 }
@@ -998,6 +1122,33 @@ int madrl_pursuit_step(madrl_pursuit *h, const int32_t *actions_dev, const int32
     io.done = done_dev;
     io.removed = removed_dev;
     return launch(h, io, 1, stream);
+}
+
+int madrl_pursuit_step_to(madrl_pursuit *h, const int32_t *actions_dev, const int32_t *inj_evader_actions_dev, const float *obs_prev_dev,
+                          float *obs_next_dev, float *rew_dev, uint8_t *done_dev, int32_t *removed_dev, void *stream) {
+    if (!h || !actions_dev || !obs_prev_dev || !obs_next_dev || !rew_dev || !done_dev || !removed_dev)
+        return fail(MADRL_EINVAL, "step_to: NULL argument");
+    if (obs_prev_dev == obs_next_dev)
+        return madrl_pursuit_step(h, actions_dev, inj_evader_actions_dev, obs_next_dev, rew_dev, done_dev, removed_dev, stream);
+    const uint64_t bytes = 4ull * (uint64_t)h->dev.n_envs * (uint64_t)h->dev.P * (uint64_t)h->dev.D;
+    const uint64_t a = (uint64_t)obs_prev_dev, b = (uint64_t)obs_next_dev;
+    if (a < b + bytes && b < a + bytes) return fail(MADRL_EINVAL, "step_to: obs_prev and obs_next overlap (the same buffer is madrl_pursuit_step; two buffers must be disjoint)");
+    if ((a | b) & 15u) return fail(MADRL_EINVAL, "step_to: observation buffers must be 16-byte aligned");
+    PursuitIO io;
+    memset(&io, 0, sizeof(io));
+    io.actions = actions_dev;
+    io.inj_eact = inj_evader_actions_dev;
+    io.obs = obs_next_dev;
+    io.rew = rew_dev;
+    io.done = done_dev;
+    io.removed = removed_dev;
+    return launch_to(h, io, obs_prev_dev, stream);
+}
+
+int madrl_pursuit_step_to_kernel_kind(madrl_pursuit *h, int32_t *out) {
+    if (!h || !out) return fail(MADRL_EINVAL, "NULL argument");
+    *out = to_of(h) ? MADRL_KERNEL_WAVE : MADRL_KERNEL_GENERIC;
+    return MADRL_OK;
 }
 
 int madrl_pursuit_step_sharded(madrl_pursuit *const *hs, const madrl_pursuit_shard_io *io, int32_t n_shards, void *caller_stream,

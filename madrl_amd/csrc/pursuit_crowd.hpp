@@ -205,12 +205,27 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 template <class S, int MODE>
 __global__ __launch_bounds__(S::NT) void pursuit_crowd_kernel(const CrowdDev d, const CrowdIO io) {
     [[maybe_unused]] const int32_t *const pending = nullptr;
+    constexpr bool TO = false;
+    [[maybe_unused]] const float *const obs_prev = nullptr;
 #include "pursuit_crowd_body.inc"
 }
 
 // S = LCShape: pending = the caller's int32 [n_envs][2] (pursuers, evaders), read by resets only
 template <class S, int MODE>
 __global__ __launch_bounds__(S::NT) void pursuit_live_crowd_kernel(const CrowdDev d, const CrowdIO io, const int32_t *const pending) {
+    constexpr bool TO = false;
+    [[maybe_unused]] const float *const obs_prev = nullptr;
+#include "pursuit_crowd_body.inc"
+}
+
+// The two-buffer step (madrl_pursuit_step_to) of a CShape or an LCShape: the step's rows go to io.obs, whole float4s, and what an in-place
+// step leaves alone comes from obs_prev (write_obs in the body).  The XC / XLC lines of pursuit_to_specializations.def, instantiated in
+// pursuit_to.hip.
+template <class S>
+__global__ __launch_bounds__(S::NT) void pursuit_crowd_to_kernel(const CrowdDev d, const CrowdIO io, [[maybe_unused]] const int32_t *const pending,
+                                                                 const float *const obs_prev) {
+    constexpr int MODE = 1;
+    constexpr bool TO = true;
 #include "pursuit_crowd_body.inc"
 }
 
@@ -221,6 +236,9 @@ void crowd_launch(const CrowdDev &d, const CrowdIO &io, const int32_t *pending, 
 // ... of an LCShape (for every XLC line in pursuit_live_crowd.hip)
 template <class S>
 void live_crowd_launch(const CrowdDev &d, const CrowdIO &io, const int32_t *pending, int mode, int64_t blocks, hipStream_t s);
+// ... of the two-buffer step of a CShape / LCShape (for every XC / XLC line of pursuit_to_specializations.def in pursuit_to.hip)
+template <class S>
+void crowd_to_launch(const CrowdDev &d, const CrowdIO &io, const int32_t *pending, const float *obs_prev, int64_t blocks, hipStream_t s);
 
 }  // namespace pc
 }  // namespace madrl

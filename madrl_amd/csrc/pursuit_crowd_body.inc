@@ -1,7 +1,8 @@
 // pursuit_crowd_body.inc -- the body of the crowd kernels (pursuit_crowd.hpp), included INSIDE both kernel definitions:
 //   pursuit_crowd_kernel<CShape, MODE>        (S::LIVE = false, pending = nullptr): one agent count for the whole batch
 //   pursuit_live_crowd_kernel<LCShape, MODE>  (S::LIVE = true): per-env agent counts within the capacity (P, E)
-// In scope: S, MODE, d (CrowdDev), io (CrowdIO), pending (int32 [n_envs][2] or nullptr).
+//   pursuit_crowd_to_kernel<S>                (TO = true, MODE = 1): the two-buffer step of madrl_pursuit_step_to (see write_obs)
+// In scope: S, MODE, TO, d (CrowdDev), io (CrowdIO), pending (int32 [n_envs][2] or nullptr), obs_prev (TO; nullptr otherwise).
 // S::LIVE follows the LIVE branches of pursuit_generic.inc: a slot that does not exist has position bytes NOT_HERE (an evader slot the gone
 // bit too), it is never placed in, moved over or taken from the cells, pursuers >= np get no row and a 0 reward, and a reset takes (np, ne)
 // from `pending` and numbers its draws in the live layout.
@@ -90,11 +91,78 @@
         };
 
         // -------------------------------------------------------------- observations (:418-461)
-        auto write_obs = [&]() {
+        // TO, src != nullptr: the two-buffer pass -- every float4 of the env's P rows leaves as one whole non-temporal store to io.obs; the
+        // elements the in-place pass does not store come from the same float4 of `src` (loaded only then; channel 3 of an (R, R, 4) row
+        // only while the env's word says "not known zero"), and the rows of pursuers that do not exist are copied whole.  src == nullptr:
+        // the in-place pass on io.obs (the second pass of a fused auto-reset, over the step pass's rows).
+        auto write_obs = [&]([[maybe_unused]] const float *src) {
             // (the env's rows through a wave-uniform base and 32-bit offsets: P * D floats are far below 4 GB)
             typedef __attribute__((address_space(1))) float gfloat;
             typedef __attribute__((address_space(1))) v4f gv4f;
             gfloat *const orow = uniform_ptr(io.obs + env * (int64_t)P * D);
+            if constexpr (TO) {
+                if (src != nullptr) {
+                    typedef const __attribute__((address_space(1))) v4f cgv4f;
+                    cgv4f *const prow = reinterpret_cast<cgv4f *>(uniform_ptr(src + env * (int64_t)P * D));
+                    int p = tid / DV, f = tid - p * DV;
+                    constexpr int dp = NT / DV, df = NT - dp * DV;
+                    [[maybe_unused]] const double n_id = (double)np;
+                    for (uint32_t q = (uint32_t)tid; q < (uint32_t)NQ; q += (uint32_t)NT) {
+                        gv4f *const o = reinterpret_cast<gv4f *>(orow + 4u * q);
+                        v4f v;
+                        if (S::LIVE && p >= np) {
+                            v = prow[q];
+                        } else {
+                            const int base = s_base[p];
+                            float idv;
+                            if constexpr (S::LIVE) idv = (float)((double)p / n_id);
+                            else idv = (float)((double)p / (double)P);  // :440-445
+                            if constexpr (S::FLATTEN) {
+                                const uint4 cd = reinterpret_cast<const uint4 *>(s_code)[f];
+                                const uint32_t code[4] = {cd.x, cd.y, cd.z, cd.w};
+                                float val[4];
+                                bool keep[4];
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    const uint32_t ch = code[k] >> 24;
+                                    if (ch == 3u) {
+                                        val[k] = idv;
+                                        keep[k] = true;
+                                    } else {
+                                        const uint32_t c = cell[base + (int)(code[k] & 0xFFFFFFu)];
+                                        val[k] = s_vtab[(c >> (8u * ch)) & 0xFFu];
+                                        keep[k] = ch == 0u || (c & 0xFFu) != PAD_MAP;
+                                    }
+                                }
+                                v = v4f{val[0], val[1], val[2], val[3]};
+                                if (!(keep[0] & keep[1] & keep[2] & keep[3])) {
+                                    const v4f old = prow[q];
+                                    if (!keep[0]) v.x = old.x;
+                                    if (!keep[1]) v.y = old.y;
+                                    if (!keep[2]) v.z = old.z;
+                                    if (!keep[3]) v.w = old.w;
+                                }
+                            } else {
+                                const int i = f / R, j = f - i * R;
+                                const uint32_t c = cell[base + i * GW + j];
+                                const bool outside = (c & 0xFFu) == PAD_MAP;
+                                v = v4f{s_vtab[c & 0xFFu], s_vtab[(c >> 8) & 0xFFu], s_vtab[(c >> 16) & 0xFFu], 0.0f};
+                                if (!outside && f == S::CENTRE) {
+                                    v.w = idv;
+                                } else if (outside || !ch3_zero) {
+                                    const v4f old = prow[q];
+                                    if (outside) { v.y = old.y; v.z = old.z; }
+                                    if (!ch3_zero) v.w = old.w;
+                                }
+                            }
+                        }
+                        __builtin_nontemporal_store(v, o);
+                        f += df; p += dp;
+                        if (f >= DV) { f -= DV; ++p; }
+                    }
+                    return;
+                }
+            }
             int p = tid / DV, f = tid - p * DV;
             constexpr int dp = NT / DV, df = NT - dp * DV;
             // LIVE: np * DV slots -- rows of pursuers that do not exist keep their contents.  The loop counts its iterations, so that the
@@ -402,7 +470,7 @@
                 for (int w = tid; w < NGW; w += NT) s_placed[w] = ~s_gone[w];
                 group_sync();
             }
-            write_obs();   // (a step: the barrier after the catches published everything the rows read)
+            write_obs(pass == 0 ? obs_prev : nullptr);   // (a step: the barrier after the catches published everything the rows read)
             if (pass == 1 || !do_reset) break;
             undo();
         }

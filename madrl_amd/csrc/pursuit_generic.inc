@@ -1,9 +1,11 @@
 // pursuit_generic.inc -- the body of the generic PursuitEvade kernels (pursuit.hip), included INSIDE both kernel definitions:
 //   pursuit_kernel<NT>       (LIVE = false, pending = nullptr): one agent count for the whole batch
 //   pursuit_live_kernel<NT>  (LIVE = true): per-env agent counts
+//   pursuit_to_kernel<NT, LIVE>  (TO = true): the two-buffer step of madrl_pursuit_step_to -- the step's rows go to io.obs, the cells an
+//                            in-place step leaves alone come from obs_prev (see write_obs)
 // It is included rather than called because a __device__ function between the kernel and its body changes the code the compiler
 // emits for pursuit_kernel<NT> (its passes see the body on its own before inlining it), and that kernel's code stays as it is.
-// In scope: NT, LIVE, d (PursuitDev), io (PursuitIO), mode, pending (int32 [n_envs][2] or nullptr).
+// In scope: NT, LIVE, TO, d (PursuitDev), io (PursuitIO), mode, pending (int32 [n_envs][2] or nullptr), obs_prev (TO; nullptr otherwise).
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x;
     const int nthr = blockDim.x;
@@ -79,11 +81,17 @@
         // Element r of pursuer p's row: code[] says which padded-grid byte (relative to the
         // window origin) feeds it.  Stores are lane-contiguous dwords; cells of the count
         // layers outside the map read 0xFF and are NOT stored (reference leaves them stale).
-        auto write_obs = [&]() {
+        // TO, src != nullptr: the two-buffer pass.  Every element of the env's rows is stored to io.obs; an element the in-place pass
+        // would not store (count cells outside the map, skipped cells, rows of absent observers) is loaded from the same place of `src`,
+        // and only the float4s that hold such an element are loaded.  src == nullptr is the in-place pass on io.obs: the second pass of a
+        // fused auto-reset, which sees the first pass's values there.
+        auto write_obs = [&]([[maybe_unused]] const float *src) {
 #if defined(MADRL_ABLATE) && (MADRL_ABLATE & 8)
             if (d.n_envs >= 0) return;
 #endif
             float *orow = io.obs + env * (int64_t)d.P * d.D;
+            [[maybe_unused]] const float *prow = nullptr;
+            if constexpr (TO) prow = src ? src + env * (int64_t)d.P * d.D : nullptr;
             int n_rows = LIVE ? np : d.P;
             if (!d.train_pursuit) {  // observers = the remaining evaders of slots 0..P-1, in slot order
                 __syncthreads();
@@ -107,6 +115,15 @@
                 int p = tid / DV, f = tid - p * DV;
                 const int dp = nthr / DV, df = nthr - dp * DV;
                 for (int q = tid; q < NQ; q += nthr) {
+                    if constexpr (TO) {
+                        if (prow != nullptr && p >= n_rows) {  // rows of absent observers: copied whole
+                            const v4f v = *reinterpret_cast<const v4f *>(prow + 4 * (int64_t)q);
+                            __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(orow + 4 * (int64_t)q));
+                            f += df; p += dp;
+                            if (f >= DV) { f -= DV; ++p; }
+                            continue;
+                        }
+                    }
                     if (p >= n_rows) break;  // rows of absent observers keep their old contents
                     const int base = (obx[p] - obs_off + pad) * GW + (oby[p] - obs_off + pad);
                     float val[4];
@@ -130,6 +147,22 @@
                         }
                     }
                     float *o = orow + 4 * (int64_t)q;
+                    if constexpr (TO) {
+                        if (prow != nullptr) {  // one whole store; the kept elements from the previous buffer
+                            v4f v = {val[0], val[1], val[2], val[3]};
+                            if (!(keep[0] & keep[1] & keep[2] & keep[3])) {
+                                const v4f old = *reinterpret_cast<const v4f *>(prow + 4 * (int64_t)q);
+                                if (!keep[0]) v.x = old.x;
+                                if (!keep[1]) v.y = old.y;
+                                if (!keep[2]) v.z = old.z;
+                                if (!keep[3]) v.w = old.w;
+                            }
+                            __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(o));
+                            f += df; p += dp;
+                            if (f >= DV) { f -= DV; ++p; }
+                            continue;
+                        }
+                    }
                     if (keep[0] & keep[1] & keep[2] & keep[3]) {
                         const v4f v = {val[0], val[1], val[2], val[3]};
                         __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(o));
@@ -145,6 +178,36 @@
                 return;
             }
             // dword path (rows that are not whole float4s: even obs_range with flatten)
+            if constexpr (TO) {
+                if (prow != nullptr) {  // every element of all P rows: the step's value, or the previous buffer's
+                    for (int p = 0; p < d.P; ++p) {
+                        const int base = p < n_rows ? (obx[p] - obs_off + pad) * GW + (oby[p] - obs_off + pad) : 0;
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) {
+                            const int r = tid + t * nthr;
+                            if (r >= d.D) continue;
+                            const uint32_t kind = code[t] >> 24;
+                            bool keep = false;
+                            float val = 0.0f;
+                            if (p < n_rows) {
+                                if (kind == K_GRID) {
+                                    const uint32_t v = g_map[base + (int)(code[t] & 0xFFFFFFu)];
+                                    keep = v != PAD_CNT;
+                                    val = s_vtab[v];
+                                } else if (kind == K_ID) {
+                                    keep = true;
+                                    val = (float)((double)p / (double)(LIVE ? np : d.P));
+                                } else if (kind == K_FILL) {
+                                    keep = true;
+                                    val = d.fill32;
+                                }
+                            }
+                            orow[p * d.D + r] = keep ? val : prow[p * d.D + r];
+                        }
+                    }
+                    return;
+                }
+            }
             for (int p = 0; p < n_rows; ++p) {
                 const int base = (obx[p] - obs_off + pad) * GW + (oby[p] - obs_off + pad);
 #pragma unroll
@@ -325,7 +388,7 @@
         if (mode == 1 && do_reset) {
             // auto-reset: the reference sequence is step() then reset(); both write the persistent
             // observation buffer, and cells the second write skips keep the first one's values
-            write_obs();
+            write_obs(obs_prev);
             __syncthreads();
         }
         if (do_reset) {
@@ -409,7 +472,7 @@
             __syncthreads();
         }
 
-        write_obs();
+        write_obs(mode == 1 && do_reset ? nullptr : obs_prev);  // (after a fused reset: in place, over the step pass's rows)
         // -------------------------------------------------------------- store state record
         for (int a = tid; a < d.A; a += nthr)
             reinterpret_cast<uint16_t *>(rec + HDR_BYTES)[a] = (uint16_t)(s_ax[a] | (s_ay[a] << 8));

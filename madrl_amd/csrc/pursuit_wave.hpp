@@ -80,6 +80,7 @@ struct WaveIO {
     int32_t *removed;
     int32_t flex;            // host side only: 1 = launch the FLEX instantiation (injected evader actions and / or per-env catchr)
     int32_t control_evaders; // host side only: 1 = launch the evader-control instantiations (madrl_pursuit_config::control_evaders)
+    const float *obs_prev;   // TShape / TLShape kernels (madrl_pursuit_step_to): the buffer the kept cells come from; unused otherwise
 };
 
 // a wave-uniform float64 read through the scalar cache (s_load_dwordx2, counted by lgkmcnt -- not by the vmcnt the
@@ -138,6 +139,7 @@ struct Shape {
     static_assert(LDS_DWORDS * 4 <= 64 * 1024, "LDS budget");
     static_assert(NS <= 8, "stale-zero mask: one bit per slot in each byte of the lane's mask dword");
     static constexpr bool LIVE = false;
+    static constexpr bool TO = false;
 };
 
 // Per-env agent counts (madrl_pursuit_set_agent_counts): the same geometry, with P and E as a CAPACITY.  An env runs LIVE p <= P
@@ -149,6 +151,21 @@ struct LShape : Shape<XS_, YS_, P_, E_, R_, FLATTEN_> {
     static constexpr bool LIVE = true;
 };
 constexpr int NOT_HERE = 0xFF;   // position byte of a slot that does not exist (live-count records)
+
+// The two-buffer step (madrl_pursuit_step_to): the step's observation pass stores every valid float4 of the env's rows to io.obs, whole
+// and non-temporal; the cells the in-place pass leaves alone come from the same place of io.obs_prev -- loaded only in the slots whose
+// `dirty` word is non-zero (a kept cell not known to be zero) and in the rows of absent observers, which are copied whole.  The mask bit
+// of a kept cell becomes "the loaded value is non-zero".  The second pass of a fused auto-reset is the in-place pass on io.obs.
+// Only the flexible step kernel <S, 1, true> is instantiated (to_wave_launch, pursuit_to.hip); the shapes are the X / XL lines of
+// pursuit_to_specializations.def.
+template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
+struct TShape : Shape<XS_, YS_, P_, E_, R_, FLATTEN_> {
+    static constexpr bool TO = true;
+};
+template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
+struct TLShape : LShape<XS_, YS_, P_, E_, R_, FLATTEN_> {
+    static constexpr bool TO = true;
+};
 
 __device__ __forceinline__ double pairwise8(const double *r) {
     return ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
@@ -317,6 +334,7 @@ template <class S, int MODE, bool INJECT, bool CTRL = false>
 __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const WaveDev d, const WaveIO io) {
     static_assert(!CTRL || (S::E >= S::P && (MODE == 0 || INJECT)), "evader control: n_evaders >= n_pursuers, flexible instantiation");
     static_assert(!CTRL || !S::LIVE, "evader control has no per-env agent counts");
+    static_assert(!S::TO || (MODE == 1 && INJECT && !CTRL), "the two-buffer step: the flexible step kernel only");
     constexpr int P = S::P, E = S::E, A = S::A, GW = S::GW, PAD = S::PAD, GSZ = S::GSZ, NS = S::NS;
     __shared__ __attribute__((aligned(16))) uint32_t L[S::LDS_DWORDS];
     const int lane = threadIdx.x;
@@ -702,9 +720,15 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                     // scalar address only 5 wait states later; the compiler cannot see the stores inside the asm blocks below
                     asm volatile("s_nop 4" : "+s"(orow_u));
                     const uint32_t voff = ulane * 16u;
+                    // (the two-buffer pass: both rows as global pointers of their own, its loads and stores are the compiler's)
+                    [[maybe_unused]] const auto prow_g = uniform_ptr(S::TO ? io.obs_prev + env * (int64_t)(P * S::D) : io.obs);
+                    [[maybe_unused]] const auto orow_g = uniform_ptr(io.obs + env * (int64_t)(P * S::D));
                     const char *Lb = reinterpret_cast<const char *>(L);
                     auto cell_at = [&](int off) -> uint32_t { return *reinterpret_cast<const uint32_t *>(Lb + off); };
                     uint32_t acc = 0u;  // the new mask, slot by slot
+                    // the two-buffer pass (S::TO, the step's pass): per slot the elements that come from the previous buffer (one flag per byte)
+                    // and the new mask bits
+                    [[maybe_unused]] uint32_t to_need[S::TO ? NS : 1], to_bits[S::TO ? NS : 1];
                     static_for<0, NS>([&](auto sc) {
                         constexpr int s = decltype(sc)::value;
                         const int base = __builtin_amdgcn_ds_bpermute(s_src[s], origin);
@@ -719,6 +743,17 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                         const uint32_t nz4 = ((top >> 5) | (top >> 6)) & 0x01010101u;      // value != 0 (meaningful where inside)
                         const uint32_t old4 = (zm >> (NS - 1 - s)) & 0x01010101u;          // holds a value not known to be zero
                         const uint32_t dirty = out4 & old4;                                 // outside AND possibly non-zero: must stay untouched
+                        if constexpr (S::TO) {
+                            if (pass == 0) {   // the two-buffer pass, part 1: this slot's values and which of them come from io.obs_prev
+                                bool row_live = true;
+                                if constexpr (S::LIVE) row_live = (s_src[s] >> 2) < n_rows;
+                                const bool in_row = (64 * (s + 1) <= S::NQ) ? true : (fresh(lane) + 64 * s < S::NQ);
+                                const uint32_t need4 = in_row ? (row_live ? dirty : 0x01010101u) : 0u;
+                                to_need[s] = need4;
+                                to_bits[s] = ~need4 & ~out4 & nz4;
+                                return;
+                            }
+                        }
                         bool valid = (64 * (s + 1) <= S::NQ) ? true : (fresh(lane) + 64 * s < S::NQ);
                         if constexpr (CTRL || S::LIVE) {
                             const bool row_live = (s_src[s] >> 2) < n_rows;   // rows of absent observers keep their contents -- and their flags
@@ -790,6 +825,56 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                                                           __builtin_amdgcn_ballot_w64(v1 < lim), __builtin_amdgcn_ballot_w64(v2 < lim),
                                                           __builtin_amdgcn_ballot_w64(v3 < lim), __builtin_amdgcn_ballot_w64(nt != 0u));
                     });
+                    if constexpr (S::TO) {
+                        if (pass == 0) {
+                            // part 2, in groups of up to TG slots: the group's loads, all issued before the one wait -- and none, and no wait, in
+                            // a wavefront none of whose lanes needs one (vmcnt retires in order: a wait for a load is also a wait for every
+                            // store issued before it) -- then every float4 of the group leaves whole (the values are read from LDS again:
+                            // keeping them across the loads would cost four registers per slot)
+                            typedef uint32_t v4u_t __attribute__((ext_vector_type(4)));
+                            typedef __attribute__((address_space(1))) v4u_t gv4u_t;
+                            typedef __attribute__((address_space(1))) v4f_t gv4f_t;
+                            constexpr int TG = NS <= 5 ? NS : 4;
+                            auto emit = [&](auto sc, const v4u_t oldv) {
+                                constexpr int s = decltype(sc)::value;
+                                const int base = __builtin_amdgcn_ds_bpermute(s_src[s], origin);
+                                const uint32_t need4 = to_need[s];
+                                uint32_t w0 = (uint32_t)max((int)cell_at(base + s_cst[s][0]), 0);
+                                uint32_t w1 = (uint32_t)max((int)cell_at(base + s_cst[s][1]), 0);
+                                uint32_t w2 = (uint32_t)max((int)cell_at(base + s_cst[s][2]), 0);
+                                uint32_t w3 = (uint32_t)max((int)cell_at((int)__umul24((uint32_t)base, (uint32_t)s_rel3[s]) + s_cst[s][3]), 0);
+                                if (need4 & 0x00000001u) w0 = oldv.x;
+                                if (need4 & 0x00000100u) w1 = oldv.y;
+                                if (need4 & 0x00010000u) w2 = oldv.z;
+                                if (need4 & 0x01000000u) w3 = oldv.w;
+                                const uint32_t oldnz = (oldv.x != 0u ? 0x00000001u : 0u) | (oldv.y != 0u ? 0x00000100u : 0u) |
+                                                       (oldv.z != 0u ? 0x00010000u : 0u) | (oldv.w != 0u ? 0x01000000u : 0u);
+                                acc = (acc << 1) | to_bits[s] | (need4 & oldnz);   // the mask bit of a kept cell: "the loaded value is non-zero"
+                                const bool in_row = (64 * (s + 1) <= S::NQ) ? true : (fresh(lane) + 64 * s < S::NQ);
+                                if (in_row) {
+                                    const v4f_t wv = {__uint_as_float(w0), __uint_as_float(w1), __uint_as_float(w2), __uint_as_float(w3)};
+                                    __builtin_nontemporal_store(wv, reinterpret_cast<gv4f_t *>(orow_g) + (64u * s + ulane));
+                                }
+                            };
+                            static_for<0, (NS + TG - 1) / TG>([&](auto gc) {
+                                constexpr int g0 = decltype(gc)::value * TG, g1 = g0 + TG < NS ? g0 + TG : NS;
+                                uint32_t any = 0u;
+#pragma unroll
+                                for (int s = g0; s < g1; ++s) any |= to_need[s];
+                                if (__builtin_amdgcn_ballot_w64(any != 0u) != 0ull) {
+                                    v4u_t old[TG];
+#pragma unroll
+                                    for (int s = g0; s < g1; ++s) {
+                                        old[s - g0] = v4u_t{0u, 0u, 0u, 0u};
+                                        if (to_need[s] != 0u) old[s - g0] = reinterpret_cast<const gv4u_t *>(prow_g)[64u * s + ulane];
+                                    }
+                                    static_for<g0, g1>([&](auto sc) { emit(sc, old[decltype(sc)::value - g0]); });
+                                } else {
+                                    static_for<g0, g1>([&](auto sc) { emit(sc, v4u_t{0u, 0u, 0u, 0u}); });
+                                }
+                            });
+                        }
+                    }
                     zm = acc;
                 }
                 wave_sync();
@@ -849,6 +934,11 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
         cur_zm = nxt_zm;
     }
 }
+
+// host side: launches the two-buffer step kernel <S, 1, true> of a TShape / TLShape (defined and instantiated for every X / XL line of
+// pursuit_to_specializations.def in pursuit_to.hip)
+template <class S>
+void wave_to_launch(const WaveDev &d, const WaveIO &io, int64_t blocks, hipStream_t s);
 
 }  // namespace pw
 }  // namespace madrl

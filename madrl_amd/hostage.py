@@ -148,9 +148,11 @@ class BatchedContinuousHostageWorld(AbstractMAEnv):
         _lib.check(_lib.lib().madrl_hostage_reset(self._handle, _lib.ptr(mask), _lib.ptr(self._obs), _lib.current_stream(self.device)))
         return self._obs
 
-    def step(self, action, respawn=None):
+    def step(self, action, respawn=None, obs_out=None):
         """hostage.py:228-430.  action: float [N, n_good, 2] (or anything that reshapes to it, :229-230).
-        respawn: optional float [N, n_bad, 4] injected respawn uniforms (parity hook)."""
+        respawn: optional float [N, n_bad, 4] injected respawn uniforms (parity hook).
+        obs_out: optional contiguous float32 destination of N * n_good * obs_dim elements on the env's device (e.g. a slot of a
+        trajectory tensor) the kernel writes the observations to instead of the env's own buffer; its [N, n_good, D] view is returned."""
         N, Nr = self.n_envs, self.n_good
         if not self._conforming(action):
             a = torch.as_tensor(action, device=self.device)
@@ -160,7 +162,7 @@ class BatchedContinuousHostageWorld(AbstractMAEnv):
         r = None
         if respawn is not None:
             r = torch.as_tensor(respawn, device=self.device).reshape(N, self.n_bad, 4).to(torch.float32).contiguous()
-        return self._launch_step(action, r, _lib.current_stream(self.device))
+        return self._launch_step(action, r, _lib.current_stream(self.device), obs_out)
 
     def _conforming(self, a):
         return (type(a) is torch.Tensor and a.dtype is torch.float32 and a.device == self.device and a.is_contiguous()
@@ -172,10 +174,11 @@ class BatchedContinuousHostageWorld(AbstractMAEnv):
             return None
         return self._launch_step(action, None, C.c_void_p(stream.cuda_stream))
 
-    def _launch_step(self, a, r, stream_ptr):
-        _lib.check(_lib.lib().madrl_hostage_step(self._handle, _lib.ptr(a), _lib.ptr(r), _lib.ptr(self._obs), _lib.ptr(self._rew),
+    def _launch_step(self, a, r, stream_ptr, obs_out=None):
+        obs = self._obs if obs_out is None else _lib.obs_destination(obs_out, self._obs)
+        _lib.check(_lib.lib().madrl_hostage_step(self._handle, _lib.ptr(a), _lib.ptr(r), _lib.ptr(obs), _lib.ptr(self._rew),
                                                  _lib.ptr(self._done), _lib.ptr(self._info), stream_ptr))
-        return self._obs, self._rew, self._done.view(torch.bool), {"ho_saved": self._info[:, 0], "cr_encs": self._info[:, 1], "done_bits": self._done}
+        return obs, self._rew, self._done.view(torch.bool), {"ho_saved": self._info[:, 0], "cr_encs": self._info[:, 1], "done_bits": self._done}
 
     @property
     def is_gate_open(self):

@@ -151,7 +151,7 @@ class BatchedMultiWalkerEnv(AbstractMAEnv):
                                                       _lib.current_stream(self.device)))
         return self._obs
 
-    def step(self, actions, rew_out=None, done_out=None):
+    def step(self, actions, rew_out=None, done_out=None, obs_out=None):
         """multi_walker.py:359-428.  done = bit 0 of the kernel's done byte (game over / package dropped, :404-424); bit 1 =
         the max_steps time limit.  With auto_reset either of them starts a new episode, so info carries the raw bits like
         BatchedPursuitEvade does (the rollout collector and the wrappers cut episodes on info['done_bits']).  Bit 7 (info['overflow']) =
@@ -159,7 +159,8 @@ class BatchedMultiWalkerEnv(AbstractMAEnv):
         the env's next reset, starts no episode by itself.  The pools are sized for walking and falling walkers (the largest
         manifold count seen in random and gait rollouts is about two thirds of them); every walker of eight lying in a heap with
         terminate_on_fall off exceeds them after a few hundred steps.
-        rew_out float32 [N, W] / done_out uint8 [N]: optional destinations the kernel writes instead of the env's buffers."""
+        rew_out float32 [N, W] / done_out uint8 [N]: optional destinations the kernel writes instead of the env's buffers.
+        obs_out: the same for the observations (contiguous float32, N * W * obs_dim elements); its [N, W, D] view is returned."""
         N, W = self.n_envs, int(self.n_walkers)
         a = torch.as_tensor(actions, device=self.device)
         if a.numel() != N * W * 4:
@@ -168,9 +169,10 @@ class BatchedMultiWalkerEnv(AbstractMAEnv):
         rew = self._rew if rew_out is None else rew_out
         dn = self._done if done_out is None else done_out
         assert rew.dtype == torch.float32 and rew.numel() == N * W and dn.dtype == torch.uint8 and dn.numel() == N
-        _lib.check(_lib.lib().madrl_multiwalker_step(self._handle, _lib.ptr(a), _lib.ptr(self._obs), _lib.ptr(rew),
+        obs = self._obs if obs_out is None else _lib.obs_destination(obs_out, self._obs)
+        _lib.check(_lib.lib().madrl_multiwalker_step(self._handle, _lib.ptr(a), _lib.ptr(obs), _lib.ptr(rew),
                                                      _lib.ptr(dn), _lib.current_stream(self.device)))
-        return self._obs, rew, (dn & 1).bool(), {"done_bits": dn, "truncated": (dn & 2).bool(), "overflow": (dn & 128).bool()}
+        return obs, rew, (dn & 1).bool(), {"done_bits": dn, "truncated": (dn & 2).bool(), "overflow": (dn & 128).bool()}
 
     def bodies(self):
         N, W, dev = self.n_envs, int(self.n_walkers), self.device

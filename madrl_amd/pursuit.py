@@ -375,16 +375,76 @@ class BatchedPursuitEvade(AbstractMAEnv):
                                                  self._stream()))
         return self._step_result(rew, dn)
 
-    def step_into(self, actions, rew_out, done_out):
+    def _obs_destination(self, obs_out):
+        """obs_out of step_to / step_into as the flat [N, P, D] tensor the env adopts, or None when it IS the current buffer (a plain step)"""
+        N, P, D = self.n_envs, int(self.n_pursuers), self.obs_dim
+        if type(obs_out) is not torch.Tensor:
+            raise TypeError("obs_out must be a torch.Tensor, got %s" % type(obs_out).__name__)
+        if obs_out.dtype is not torch.float32 or obs_out.device != self.device or not obs_out.is_contiguous() or obs_out.numel() != N * P * D:
+            raise ValueError("obs_out must be a contiguous float32 tensor of %d elements on %s (got %s, %s, %s, contiguous=%s)"
+                             % (N * P * D, self.device, tuple(obs_out.shape), obs_out.dtype, obs_out.device, obs_out.is_contiguous()))
+        if obs_out.data_ptr() == self._obs.data_ptr():
+            return None
+        return obs_out.view(N, P, D)
+
+    def _launch_step_to(self, act, eact, dest, rew, dn):
+        """madrl_pursuit_step_to from the current observation buffer into `dest`, which becomes the current buffer: obs_buffer, the views
+        step() returns and the in-place-edit bookkeeping (_check_obs_untouched) follow it, and so does what the fast path knows about
+        the buffer (include/madrl_hip.h).  The previous buffer is left as it was and belongs to the caller again."""
+        self._check_obs_untouched()   # (an in-place edit of the buffer the kept cells are read from)
+        self._obs_is_fresh = False
+        _lib.check(_lib.lib().madrl_pursuit_step_to(self._handle, _lib.ptr(act), _lib.ptr(eact), _lib.ptr(self._obs), _lib.ptr(dest),
+                                                    _lib.ptr(rew), _lib.ptr(dn), _lib.ptr(self._removed), self._stream()))
+        self._obs = dest
+        self._obs_version = self._version_of_obs()
+
+    def step_to(self, actions, obs_out, rew_out=None, done_out=None, evader_actions=None):
+        """step() with the observations written to `obs_out` (float32, contiguous, on the env's device, N * P * obs_dim elements: e.g.
+        slot t + 1 of a trajectory tensor) instead of the env's current observation buffer.  obs_out then holds, element for element, what
+        the current buffer would hold after step() -- the cells a step never stores (quirk Q2), the rows of absent observers and both
+        passes of a fused auto-reset included -- and BECOMES the env's current buffer; the previous one is not written.  Returns what
+        step() returns, the observation being the [N, P, D] / [N, P, R, R, 4] view of obs_out.  obs_out that is the current buffer is
+        step(); a buffer that overlaps it otherwise is refused.
+        The one-wavefront and crowd shapes of csrc/pursuit_to_specializations.def have two-buffer fast kernels; every other handle
+        (multi-wavefront shapes and train_pursuit=False included) runs this call on the generic kernel (step_to_kernel_kind)."""
+        N, P, E = self.n_envs, int(self.n_pursuers), int(self.n_evaders)
+        dest = self._obs_destination(obs_out)
+        if dest is None:
+            return self.step(actions, evader_actions=evader_actions, rew_out=rew_out, done_out=done_out)
+        if getattr(self, "_needs_reset", False):
+            raise RuntimeError("update_curriculum / set_param_values changed the agent counts -- call reset() first")
+        if type(actions) is torch.Tensor and actions.dtype is torch.int32 and actions.shape == (N, P) and actions.device == self.device and actions.is_contiguous():
+            act = actions
+        else:
+            act = self._i32(actions, (N, P), "actions")
+        eact = self._i32(evader_actions, (N, E if self.train_pursuit else P), "evader_actions")
+        rew = self._rew if rew_out is None else rew_out
+        dn = self._done if done_out is None else done_out
+        assert rew.dtype == torch.float32 and rew.numel() == N * P and dn.dtype == torch.uint8 and dn.numel() == N
+        self._launch_step_to(act, eact, dest, rew, dn)
+        return self._step_result(rew, dn)
+
+    @property
+    def step_to_kernel_kind(self):
+        """'wave' | 'generic': the kernel a step_to of this env launches ('wave': the two-buffer instantiation of its fast kernel)"""
+        out = C.c_int32()
+        _lib.check(_lib.lib().madrl_pursuit_step_to_kernel_kind(self._handle, C.byref(out)))
+        return {_lib.KERNEL_GENERIC: "generic", _lib.KERNEL_WAVE: "wave"}[out.value]
+
+    def step_into(self, actions, rew_out, done_out, obs_out=None):
         """The launch of step() alone, for a sampler loop that keeps everything on the device: rewards and done bits go to the given
         trajectory slots, the observation view is returned, and none of the small torch kernels that build step()'s `done` / `info`
         tensors run (six launches of ~5 us each: a third of a 65 536-env rollout step, profiles/r05_rollout).  actions: int32 [N, P]
-        contiguous on the env's device."""
+        contiguous on the env's device.  obs_out: the observations go there, as in step_to()."""
         N, P = self.n_envs, int(self.n_pursuers)
         if getattr(self, "_needs_reset", False):
             raise RuntimeError("update_curriculum / set_param_values changed the agent counts -- call reset() first")
         assert actions.dtype == torch.int32 and actions.is_contiguous() and actions.numel() == N * P
         assert rew_out.dtype == torch.float32 and rew_out.numel() == N * P and done_out.dtype == torch.uint8 and done_out.numel() == N
+        dest = self._obs_destination(obs_out) if obs_out is not None else None
+        if dest is not None:
+            self._launch_step_to(actions, None, dest, rew_out, done_out)
+            return self._obs_view()
         self._check_obs_untouched()
         self._obs_is_fresh = False
         _lib.check(_lib.lib().madrl_pursuit_step(self._handle, _lib.ptr(actions), None, _lib.ptr(self._obs), _lib.ptr(rew_out), _lib.ptr(done_out),

@@ -16,8 +16,10 @@ from . import _lib
 
 class Trajectory(object):
     """time-major tensors of one collect() call: actions [T,N,A(,adim)], rewards float32 [T,N,A],
-    dones uint8 [T,N] (bit0 terminal, bit1 time limit), values float32 [T+1,N,A] or None,
-    observations float32 [T,N,A,D] or None, returns / advantages float32 [T,N,A]."""
+    dones uint8 [T,N] (bit0 terminal, bit1 time limit; PursuitEvade / MultiWalker: bit 7 = a capacity overflow mark, no episode boundary),
+    values float32 [T+1,N,A] or None, observations float32 [T,N,A,D] or None (the observation each action was chosen from),
+    last_observation float32 [N,A,D] or None (the observation after the last step: observations[0] of the next collect()),
+    returns / advantages float32 [T,N,A]."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -28,7 +30,7 @@ class Trajectory(object):
         chosen env instances (default: all; meant for small N / debugging, the tensors are the product)."""
         T, N = self.dones.shape
         ids = range(N) if env_ids is None else env_ids
-        dn = self.dones.cpu().numpy() != 0
+        dn = (self.dones.cpu().numpy() & 3) != 0   # bit 0 terminal, bit 1 time limit; bit 7 (overflow mark) is no episode boundary
         host = {k: getattr(self, k).cpu().numpy() for k in ("actions", "rewards", "returns") }
         for k in ("advantages", "observations"):
             if getattr(self, k) is not None:
@@ -55,8 +57,14 @@ class RolloutCollector(object):
     State (the current observation) carries over between collect() calls, like a sampler that keeps its
     env copies alive between iterations."""
 
-    def __init__(self, env, policy, horizon, discount=0.99, gae_lambda=1.0, store_observations=False, graph=False):
-        """graph=True: from the second collect() on, the whole horizon (policy launches, step kernels, buffer copies, the
+    def __init__(self, env, policy, horizon, discount=0.99, gae_lambda=1.0, store_observations=False, graph=False, obs_slots=None):
+        """store_observations=True over an env whose step takes an observation destination (BatchedPursuitEvade.step_into / step_to,
+        `obs_out=` of the Waterworld, hostage and MultiWalker steps): the step kernel of step t writes slot t + 1 of a [T + 1]-slot
+        observation tensor itself -- observations = slots 0 .. T-1, last_observation = slot T -- and the only observation-sized copy of a
+        horizon is the one that brings the previous horizon's last observation to slot 0.  Other envs (wrappers such as ObservationBuffer
+        or StandardizedEnv, a Waterworld with a fused StandardizedEnv bound) keep the copy per step.  obs_slots: None = as described,
+        False = the copy per step for every env.
+        graph=True: from the second collect() on, the whole horizon (policy launches, step kernels, buffer copies, the
         return scan) is one captured hipGraph that is replayed -- for small batches the per-launch overhead of ~4 launches
         per step otherwise dominates.  The policy must be capturable (no host-side state that changes per call, no syncs);
         the device policies of madrl_amd.heuristics are."""
@@ -68,6 +76,13 @@ class RolloutCollector(object):
         import inspect
         self._direct = "rew_out" in inspect.signature(env.step).parameters   # envs whose step() can write into caller buffers
         self._into = hasattr(env, "step_into")                               # ... and that offer the launch alone (no done / info tensors built)
+        # ... and whose step kernel can write its observations into a trajectory slot (store_observations)
+        self._slots = False
+        if store_observations and (obs_slots is None or obs_slots) and getattr(env, "_std", None) is None:
+            self._slots = ("obs_out" in inspect.signature(env.step_into).parameters if self._into
+                           else "obs_out" in inspect.signature(env.step).parameters)
+        if obs_slots and store_observations and not self._slots:
+            raise ValueError("obs_slots=True: %s has no observation destination (obs_out=) in its step" % type(env).__name__)
         try:
             self._policy_out = "out" in inspect.signature(policy).parameters   # policies that write into a trajectory slot
         except (TypeError, ValueError):
@@ -81,7 +96,17 @@ class RolloutCollector(object):
                  returns=torch.empty((T,) + tuple(obs.shape[:2]), dtype=torch.float32, device=dev))
         b["values"] = torch.empty((T + 1,) + tuple(obs.shape[:2]), dtype=torch.float32, device=dev) if val is not None else None
         b["advantages"] = torch.empty_like(b["returns"]) if val is not None else None
-        b["observations"] = torch.empty((T,) + tuple(obs.shape), dtype=torch.float32, device=dev) if self.store_observations else None
+        b["observations"] = b["last_observation"] = None
+        if self.store_observations and self._slots:   # [T + 1] slots: the step kernel of step t writes slot t + 1
+            self._obs_slots = torch.empty((T + 1,) + tuple(obs.shape), dtype=torch.float32, device=dev)
+            b["observations"], b["last_observation"] = self._obs_slots[:T], self._obs_slots[T]
+            # The env gets its destinations through a second handle on the same memory with an in-place-operation counter of its own
+            # (`.data`): the copy into slot 0 below must not look to BatchedPursuitEvade like an edit of its current buffer, slot T
+            # (_check_obs_untouched would forget what the fast path knows about it at every horizon).  An in-place edit of
+            # Trajectory.last_observation by the caller is therefore not noticed by the env: call env.invalidate_obs() after one.
+            self._env_slots = self._obs_slots.data
+        elif self.store_observations:
+            b["observations"] = torch.empty((T,) + tuple(obs.shape), dtype=torch.float32, device=dev)
         return b
 
     def _act(self, obs):
@@ -98,7 +123,9 @@ class RolloutCollector(object):
             self._obs_in = self._obs
             with torch.cuda.graph(self._graph):  # records, does not execute
                 self._collect_eager()
-                self._obs_in.copy_(self._obs)    # the env returns the same persistent tensor; keep it explicit
+                if not self._slots:
+                    self._obs_in.copy_(self._obs)    # the env returns the same persistent tensor; keep it explicit
+                # (slots: every horizon starts from slot T, where the previous one ended -- the eager first call has brought the env there)
         self._graph.replay()
         return Trajectory(**self._buf)
 
@@ -126,11 +153,28 @@ class RolloutCollector(object):
                 self._buf = self._alloc(obs, act, val)
             self._buf["actions"][t].copy_(act)
         b = self._buf
-        if b["observations"] is not None:
+        if self._slots:
+            # slot 0 takes the observation the horizon starts from (the previous horizon's slot T, or the reset's); every other slot
+            # was written by the step before it.  PursuitEvade steps from its CURRENT buffer (slot T: what its fast path knows about the
+            # buffer stays valid across the horizon boundary) into slot 1 -- slot 0 holds the same values
+            if t == 0:
+                b["observations"][0].copy_(obs)
+            nxt = self._env_slots[t + 1]
+        elif b["observations"] is not None:
             b["observations"][t].copy_(obs)
         if val is not None:
             b["values"][t].copy_(val)
-        if self._into and act.dtype == torch.int32 and act.is_contiguous():
+        if self._slots and self._into and act.dtype == torch.int32 and act.is_contiguous():
+            obs = env.step_into(act, b["rewards"][t], b["dones"][t], obs_out=nxt)
+        elif self._slots and self._into:   # (PursuitEvade with actions that need a conversion)
+            obs = env.step_to(act, nxt, rew_out=b["rewards"][t], done_out=b["dones"][t])[0]
+        elif self._slots and self._direct:
+            obs = env.step(act, rew_out=b["rewards"][t], done_out=b["dones"][t], obs_out=nxt)[0]
+        elif self._slots:
+            obs, rew, done, info = env.step(act, obs_out=nxt)
+            b["rewards"][t].copy_(rew)
+            b["dones"][t].copy_(info["done_bits"] if isinstance(info, dict) and "done_bits" in info else done.to(torch.uint8))
+        elif self._into and act.dtype == torch.int32 and act.is_contiguous():
             obs = env.step_into(act, b["rewards"][t], b["dones"][t])
         elif self._direct:   # the step kernel writes rewards / done bits straight into their trajectory slot
             obs, rew, done, info = env.step(act, rew_out=b["rewards"][t], done_out=b["dones"][t])
@@ -142,6 +186,8 @@ class RolloutCollector(object):
 
     def _finish(self):
         obs, b = self._obs, self._buf
+        if self.store_observations and not self._slots:
+            b["last_observation"] = obs   # the env's own tensor: like every tensor of a Trajectory it holds these values until the next collect()
         if b["values"] is not None:
             b["values"][self.T].copy_(self._act(obs)[1])  # bootstrap of the unfinished tail
         N, A = b["rewards"].shape[1:]

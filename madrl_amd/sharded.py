@@ -158,6 +158,7 @@ class StreamSharded(object):
             e._check_obs_untouched()
             e._obs_is_fresh = False
             io[j].actions = _lib.ptr(a).value
+            io[j].obs = e._obs.data_ptr()   # (the env's current observation buffer: a step_to() moves it)
             if not join:
                 a.record_stream(self.streams[j])
         hs = (C.c_void_p * S)(*[e._handle.value for e in self.envs])

@@ -215,9 +215,12 @@ class BatchedMAWaterWorld(AbstractMAEnv):
         _lib.check(_lib.lib().madrl_waterworld_set_standardize(self._handle, None))
         self._std = None
 
-    def step(self, action, respawn=None):
+    def step(self, action, respawn=None, obs_out=None):
         """waterworld.py:220-436.  action: float [N, Np, 2] (or anything that reshapes to it, :221-222).
-        respawn: optional float [N, NP, 4] injected respawn outcomes (parity hook)."""
+        respawn: optional float [N, NP, 4] injected respawn outcomes (parity hook).
+        obs_out: optional contiguous float32 destination of N * Np * obs_dim elements on the env's device (e.g. a slot of a trajectory
+        tensor) the kernel writes the observations to instead of the env's own buffer; its [N, Np, D] view is returned.  Refused while a
+        fused StandardizedEnv is bound: the observation tensor the kernel writes then belongs to the wrapper."""
         N, Np = self.n_envs, self.n_pursuers
         if not self._conforming(action):
             a = torch.as_tensor(action, device=self.device)
@@ -227,7 +230,7 @@ class BatchedMAWaterWorld(AbstractMAEnv):
         r = None
         if respawn is not None:
             r = torch.as_tensor(respawn, device=self.device).reshape(N, self.n_particles, 4).to(torch.float32).contiguous()
-        return self._launch_step(action, r, _lib.current_stream(self.device))
+        return self._launch_step(action, r, _lib.current_stream(self.device), obs_out)
 
     def _conforming(self, a):
         """an action tensor the kernel can read as it is (float32, contiguous, on the device, N * Np * 2 elements): no torch kernel needed"""
@@ -242,15 +245,20 @@ class BatchedMAWaterWorld(AbstractMAEnv):
             return None
         return self._launch_step(action, None, C.c_void_p(stream.cuda_stream))
 
-    def _launch_step(self, a, r, stream_ptr):
+    def _launch_step(self, a, r, stream_ptr, obs_out=None):
         std = getattr(self, "_std", None)
-        _lib.check(_lib.lib().madrl_waterworld_step(self._handle, _lib.ptr(a), _lib.ptr(r), None if std else _lib.ptr(self._obs),
+        obs = self._obs
+        if obs_out is not None:
+            if std:
+                raise ValueError("obs_out: a fused StandardizedEnv is bound to this env, the kernel's observation output belongs to the wrapper")
+            obs = _lib.obs_destination(obs_out, self._obs)
+        _lib.check(_lib.lib().madrl_waterworld_step(self._handle, _lib.ptr(a), _lib.ptr(r), None if std else _lib.ptr(obs),
                                                     _lib.ptr(self._rew), _lib.ptr(self._done), _lib.ptr(self._info), stream_ptr))
         # `done` is a bool VIEW of the byte the kernel wrote (0 / 1): no torch kernel runs after the launch
         info = {"evcatches": self._info[:, 0], "pocatches": self._info[:, 1], "done_bits": self._done}
         if std:  # fused StandardizedEnv: standardised observations and scaled / normalised rewards straight from the kernel
             return std["obs_out"], std["rew_out"], self._done.view(torch.bool), info
-        return self._obs, self._rew, self._done.view(torch.bool), info
+        return obs, self._rew, self._done.view(torch.bool), info
 
     @property
     def is_terminal(self):
