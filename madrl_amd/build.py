@@ -6,6 +6,7 @@
     python -m madrl_amd.build --pursuit-crowd-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN # more than 64 pursuers or evaders: the crowd kernel
     python -m madrl_amd.build --pursuit-live-crowd-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN # ... and per-env agent counts on it
     python -m madrl_amd.build --pursuit-to-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN   # the two-buffer step (step_to) on this shape's fast kernel
+    python -m madrl_amd.build --pursuit-to-group-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN [LIVE] # ... of a multi-wavefront shape (LIVE 1: with per-env agent counts)
     python -m madrl_amd.build --waterworld-shape N_PURSUERS N_EVADERS N_POISON N_SENSORS [OBS_DIM]
 
 The fast paths (one wavefront -- or a group of wavefronts -- per env, everything about the shape a compile-time constant) exist for the
@@ -189,14 +190,15 @@ def add_pursuit_live_crowd_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatt
 
 def pursuit_to_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True):
     """-> (two-buffer line, fixed line) that give step_to() of a shape its fast kernel: X(...) over an X(...) shape, XC(..., NW) over an
-    XC(..., NW) shape -- or (None, why not): the multi-wavefront (XG) kernel has no two-buffer instantiation, and a shape without an
-    X / XC fast path has nothing to stand on.  Pure: nothing is written."""
+    XC(..., NW) shape -- or (None, why not): the lines of a multi-wavefront (XG) shape are formed by pursuit_to_group_lines, and a shape
+    without an X / XC fast path has nothing to stand on.  Pure: nothing is written."""
     kind, nw = pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
     args = "%d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)))
     if kind == "X":
         return "X(%s)" % args, "X(%s)" % args
     if kind == "XG":
-        return None, "its fast path is the multi-wavefront kernel (XG, %d wavefronts), which has no two-buffer instantiation" % nw
+        return None, ("its fast path is the multi-wavefront kernel (XG, %d wavefronts), whose two-buffer line --pursuit-to-group-shape adds: "
+                      "use that option" % nw)
     ckind, cnw = pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
     if ckind is None:
         return None, "the shape has no X / XC fast path (one wavefront: %s; crowd kernel: %s)" % (nw, cnw)
@@ -212,6 +214,33 @@ def add_pursuit_to_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
     added_fixed = _append_local("pursuit_specializations.def" if fixed.startswith("X(") else "pursuit_crowd_specializations.def",
                                 fixed + "   // added by madrl_amd.build")
     return _append_local("pursuit_to_specializations.def", line + "   // added by madrl_amd.build") or added_fixed
+
+
+def pursuit_to_group_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True, live=False):
+    """-> (two-buffer line, fixed line) that give step_to() of a multi-wavefront shape its fast kernel: XG(..., NW) -- live: XLG(..., NW),
+    the handles with per-env agent counts -- over an XG(..., NW) shape, or (None, why not): a one-wavefront or crowd shape has its lines
+    from pursuit_to_lines, and a shape without a fast path has nothing to stand on.  Pure: nothing is written."""
+    kind, nw = pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
+    args = "%d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)))
+    if kind == "XG":
+        return "%s(%s, %d)" % ("XLG" if live else "XG", args, nw), "XG(%s, %d)" % (args, nw)
+    if kind == "X":
+        return None, "its fast path is the one-wavefront kernel (X): use --pursuit-to-shape"
+    if pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)[0] is not None:
+        return None, "no multi-wavefront fast path (%s); the crowd kernel takes this shape: use --pursuit-to-shape" % nw
+    return None, nw
+
+
+def add_pursuit_to_group_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten, live=0):
+    """step_to() of this multi-wavefront shape on the two-buffer instantiation of the group kernel: the XG (live: XLG) line in the local
+    two-buffer list, the XG line it stands on in the local fixed list if it is missing, and with `live` the XLG line of the live list"""
+    line, fixed = pursuit_to_group_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, live=bool(live))
+    if line is None:
+        raise ValueError("no two-buffer multi-wavefront kernel for this PursuitEvade shape: %s (step_to runs on the generic kernel)" % fixed)
+    added = _append_local("pursuit_specializations.def", fixed + "   // added by madrl_amd.build")
+    if live:
+        added = _append_local("pursuit_live_specializations.def", line + "   // added by madrl_amd.build") or added
+    return _append_local("pursuit_to_specializations.def", line + "   // added by madrl_amd.build") or added
 
 
 def add_waterworld_shape(n_pursuers, n_evaders, n_poison, n_sensors, obs_dim=None):
@@ -291,6 +320,7 @@ if __name__ == "__main__":
                              ("--pursuit-crowd-shape", add_pursuit_crowd_shape, 6, 6),
                              ("--pursuit-live-crowd-shape", add_pursuit_live_crowd_shape, 6, 6),
                              ("--pursuit-to-shape", add_pursuit_to_shape, 6, 6),
+                             ("--pursuit-to-group-shape", add_pursuit_to_group_shape, 6, 7),
                              ("--waterworld-shape", add_waterworld_shape, 4, 5)):
         while flag in argv:
             i = argv.index(flag)

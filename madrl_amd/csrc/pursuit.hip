@@ -412,7 +412,7 @@ constexpr FastEntry LIVE_TABLE[] = {
 #undef XLG
 #undef XLC
 
-// The two-buffer step kernels (madrl_pursuit_step_to, pursuit_to.hip): reached through the fixed line of the same shape and NW, for a handle
+// The two-buffer step kernels (madrl_pursuit_step_to, pursuit_to.hip and pursuit_to_group.hip): reached through the fixed line of the same shape and NW, for a handle
 // with per-env agent counts through its live line.  A handle without an entry here runs step_to on the generic kernel.
 using WaveToLaunch = void (*)(const pw::WaveDev &, const pw::WaveIO &, int64_t blocks, hipStream_t s);
 using CrowdToLaunch = void (*)(const pc::CrowdDev &, const pc::CrowdIO &, const int32_t *pending, const float *obs_prev, int64_t blocks, hipStream_t s);
@@ -428,6 +428,8 @@ struct ToEntry {
 #define XL(XS, YS, NP, NE, R, FL) ToEntry{{XS, YS, NP, NE, R, FL}, 1, true, pw::wave_to_launch<pw::TLShape<XS, YS, NP, NE, R, FL>>, nullptr},
 #define XC(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, false, nullptr, pc::crowd_to_launch<pc::CShape<XS, YS, NP, NE, R, FL, NW>>},
 #define XLC(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, true, nullptr, pc::crowd_to_launch<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>},
+#define XG(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, false, pw::group_to_launch<pw::TGShape<XS, YS, NP, NE, R, FL, NW>>, nullptr},
+#define XLG(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, true, pw::group_to_launch<pw::TLGShape<XS, YS, NP, NE, R, FL, NW>>, nullptr},
 constexpr ToEntry TO_TABLE[] = {
 #include "pursuit_to_specializations.def"
 #if __has_include("pursuit_to_specializations.local.def")
@@ -438,6 +440,8 @@ constexpr ToEntry TO_TABLE[] = {
 #undef XL
 #undef XC
 #undef XLC
+#undef XG
+#undef XLG
 
 // A two-buffer line without its fixed line would compile a kernel that no handle can use.
 constexpr bool to_lines_have_fixed_lines() {
@@ -448,7 +452,7 @@ constexpr bool to_lines_have_fixed_lines() {
     }
     return true;
 }
-static_assert(to_lines_have_fixed_lines(), "a line of pursuit_to_specializations.def needs the X line (X / XL) or the XC line with the same NW (XC / XLC) of its shape");
+static_assert(to_lines_have_fixed_lines(), "a line of pursuit_to_specializations.def needs the X line (X / XL), the XG line with the same NW (XG / XLG) or the XC line with the same NW (XC / XLC) of its shape");
 
 // the two-buffer kernel that stands on the fast line `f` (live: the per-env-count instantiation)
 const ToEntry *find_to(const FastEntry *f, bool live) {
@@ -669,8 +673,8 @@ void launch_to_nt(const madrl_pursuit *h, const PursuitIO &io, const float *obs_
                            h->dev, io, h->pending, obs_prev);
 }
 
-// the two-buffer fast kernel a step_to of this handle launches, or nullptr: the generic kernel (evader control, multi-wavefront lines and
-// shapes without a line in pursuit_to_specializations.def)
+// the two-buffer fast kernel a step_to of this handle launches, or nullptr: the generic kernel (evader control and shapes without a
+// line in pursuit_to_specializations.def)
 const ToEntry *to_of(const madrl_pursuit *h) {
     if (!use_wave(h) || !h->dev.train_pursuit) return nullptr;
     return find_to(h->fast, h->pending != nullptr);

@@ -88,6 +88,7 @@ struct GShape {
     static_assert(MWORDS <= 4, "at most 32 float4 slots per thread");
     static_assert(!TABLED || 3 * GSZ + 2 + P < 32768, "TABLED: dword offsets of the layers must fit 15 bits");
     static constexpr bool LIVE = false;
+    static constexpr bool TO = false;
 };
 
 // Per-env agent counts on the group kernel: the same geometry with P and E as a capacity (see LShape in pursuit_wave.hpp).
@@ -96,6 +97,36 @@ template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_, int NW_>
 struct LGShape : GShape<XS_, YS_, P_, E_, R_, FLATTEN_, NW_> {
     static constexpr bool LIVE = true;
 };
+
+// The two-buffer step on the group kernel (madrl_pursuit_step_to; see TShape in pursuit_wave.hpp): the step's observation pass stores
+// every valid float4 of the env's rows to io.obs, whole and non-temporal; the elements the in-place pass leaves alone come from the same
+// place of io.obs_prev, loaded only by the lanes that keep one.  The second pass of a fused auto-reset is the in-place pass on io.obs.
+// Only the flexible step kernel <S, 1, true> is instantiated (group_to_launch, pursuit_to_group.hip); the shapes are the XG / XLG lines
+// of pursuit_to_specializations.def.
+template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_, int NW_>
+struct TGShape : GShape<XS_, YS_, P_, E_, R_, FLATTEN_, NW_> {
+    static constexpr bool TO = true;
+};
+template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_, int NW_>
+struct TLGShape : LGShape<XS_, YS_, P_, E_, R_, FLATTEN_, NW_> {
+    static constexpr bool TO = true;
+};
+// slots of the two-buffer pass whose old float4s are in flight together: all loads of a batch are issued before its first store (vmcnt
+// retires in order: a wait for a load is a wait for every store issued before it).  Four registers per slot and lane; the live forms
+// of the long-row shapes compile to the 128 registers of their occupancy with no room to spare (eight slots spill 76 - 80 registers).
+// Measured at the authors' 30 v 50 shape, 16 384 envs, one launch per step round a ring of nine buffers: batches of 2 slots 311 us per
+// launch, of 3 slots 295, of 4 slots 281 (profiles/r11_step_to_group): the waits bind, not the loads
+#ifndef MADRL_PG_TO_BATCH
+#define MADRL_PG_TO_BATCH 4    // long rows (the rolled loop)
+#endif
+#ifndef MADRL_PG_TO_RBATCH
+#define MADRL_PG_TO_RBATCH 2   // short rows (slot constants in registers)
+#endif
+
+// host launcher of a TGShape / TLGShape kernel: explicitly instantiated in pursuit_to_group.hip, one per XG / XLG line of
+// pursuit_to_specializations.def
+template <class S>
+void group_to_launch(const WaveDev &d, const WaveIO &io, int64_t blocks, hipStream_t s);
 
 // host launcher of an LGShape kernel: explicitly instantiated in pursuit_live_group.hip, one per XLG line, so that these kernels
 // compile in a translation unit of their own
@@ -112,6 +143,7 @@ __device__ __forceinline__ void group_sync() {
 template <class S, int MODE, bool INJECT>
 __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S::OCC))) void pursuit_group_kernel(const WaveDev d, const WaveIO io) {
     constexpr int P = S::P, E = S::E, A = S::A, GW = S::GW, PAD = S::PAD, GSZ = S::GSZ, NS = S::NS, NT = S::NT;
+    static_assert(!S::TO || (MODE == 1 && INJECT), "the two-buffer step: the flexible step kernel only");
     __shared__ __attribute__((aligned(16))) uint32_t L[S::LDS_DWORDS];
     const int tid = threadIdx.x;            // = agent index for tid < A
     const int lane = tid & 63;
@@ -471,7 +503,174 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                 // window origin of pursuer tid: a dword index into L (a byte offset for TABLED shapes)
                 if (isP()) L[S::X_ORG + tid] = (uint32_t)((x - S::OFF + PAD) * GW + (y - S::OFF + PAD)) * (S::TABLED ? 4u : 1u);
                 group_sync();
-                {
+                bool in_place = true;   // the in-place row pass; false: this pass was the two-buffer pass below
+                if constexpr (S::TO) {
+                    if (pass == 0) {
+                        // ------------------------------------------------ the two-buffer pass: every valid float4 leaves whole, into io.obs
+                        in_place = false;
+                        typedef float v4f __attribute__((ext_vector_type(4)));
+                        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+                        v4f *orow = reinterpret_cast<v4f *>(io.obs + env * (int64_t)(P * S::D));
+                        const v4u *prow = reinterpret_cast<const v4u *>(io.obs_prev + env * (int64_t)(P * S::D));
+                        uint32_t acc[MW];
+#pragma unroll
+                        for (int w = 0; w < MW; ++w) acc[w] = 0u;
+                        // the elements of a slot (one flag per byte) that come from io.obs_prev: what the in-place pass leaves alone -- outside
+                        // cells not known to be zero, and the whole row of an absent pursuer (LIVE)
+                        auto need_of = [&](auto wc, int sh, bool row_live, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3) -> uint32_t {
+                            constexpr int w = decltype(wc)::value;
+                            const uint32_t top = __builtin_amdgcn_perm(v1, v0, 0x0C0C0703u) | __builtin_amdgcn_perm(v3, v2, 0x07030C0Cu);
+                            const uint32_t dirty = (top >> 7) & (zm[w] >> sh) & 0x01010101u;
+                            if constexpr (S::LIVE) return row_live ? dirty : 0x01010101u;
+                            else return dirty;
+                        };
+                        // one slot: the kept elements from `oldv` (zeros in a lane that loaded nothing: it keeps nothing), the others from the
+                        // layers -- outside cells known to be zero as +0.0 -- and the slot's new mask bits: a stored element as in the in-place
+                        // pass, a kept one "the loaded value is non-zero"
+                        auto emit = [&](auto wc, int sh, int q, bool valid, bool row_live, const v4u oldv, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3) {
+                            constexpr int w = decltype(wc)::value;
+                            const uint32_t top = __builtin_amdgcn_perm(v1, v0, 0x0C0C0703u) | __builtin_amdgcn_perm(v3, v2, 0x07030C0Cu);
+                            const uint32_t out4 = (top >> 7) & 0x01010101u;
+                            const uint32_t nz4 = ((top >> 5) | (top >> 6)) & 0x01010101u;
+                            const uint32_t old4 = (zm[w] >> sh) & 0x01010101u;
+                            if constexpr (!S::LIVE) row_live = true;
+                            const uint32_t need4 = row_live ? (out4 & old4) : 0x01010101u;
+                            const uint32_t oldnz = (oldv.x != 0u ? 0x00000001u : 0u) | (oldv.y != 0u ? 0x00000100u : 0u) |
+                                                   (oldv.z != 0u ? 0x00010000u : 0u) | (oldv.w != 0u ? 0x01000000u : 0u);
+                            // (a thread past the end of the rows stores and loads nothing: its bits stay what the in-place pass makes them)
+                            acc[w] = (acc[w] << 1) | (row_live ? (~out4 & nz4) : 0u) | (need4 & (valid ? oldnz : old4));
+                            if (valid) {
+                                uint32_t w0 = (uint32_t)max((int)v0, 0), w1 = (uint32_t)max((int)v1, 0);
+                                uint32_t w2 = (uint32_t)max((int)v2, 0), w3 = (uint32_t)max((int)v3, 0);
+                                if (need4 & 0x00000001u) w0 = oldv.x;
+                                if (need4 & 0x00000100u) w1 = oldv.y;
+                                if (need4 & 0x00010000u) w2 = oldv.z;
+                                if (need4 & 0x01000000u) w3 = oldv.w;
+                                const v4f val = {__uint_as_float(w0), __uint_as_float(w1), __uint_as_float(w2), __uint_as_float(w3)};
+                                __builtin_nontemporal_store(val, &orow[q]);
+                            }
+                        };
+                        // Batches of slots.  Part 1: which lanes keep an element of which slot (the values are read from LDS again in part 2:
+                        // keeping them across the loads would cost four registers per slot).  Part 2: the batch's loads, all issued before
+                        // its first store -- and none, and no wait, in a wavefront none of whose lanes keeps anything -- then its stores.
+                        if constexpr (S::TABLED) {
+                            int pq = q0_p, fq = q0_f, q = tid;
+                            const char *Lb = reinterpret_cast<const char *>(L);
+                            auto cell_b = [&](int byte_off) -> uint32_t { return *reinterpret_cast<const uint32_t *>(Lb + byte_off); };
+                            auto read_slot = [&](int pp, int f, uint32_t &v0, uint32_t &v1, uint32_t &v2, uint32_t &v3) {   // as the in-place loop below
+                                const uint2 t = *reinterpret_cast<const uint2 *>(&L[S::X_TAB + 2 * f]);
+                                const int base = (int)L[S::X_ORG + pp];
+                                v0 = cell_b(base + (int)((t.x & 0xFFFFu) << 2));
+                                v1 = cell_b(base + (int)((t.x >> 16) << 2));
+                                v2 = cell_b(base + (int)((t.y & 0x7FFFu) << 2));
+                                const int b3 = ((int)t.y < 0) ? 0 : base;
+                                const int id3 = (t.y & 0x8000u) ? pp : 0;
+                                v3 = cell_b(b3 + (int)((((t.y >> 16) & 0x7FFFu) + (uint32_t)id3) << 2));
+                            };
+                            auto advance = [&](int &aq, int &af, int &ap) {
+                                aq += NT;
+                                af += NT % S::DV;
+                                ap += NT / S::DV;
+                                if (af >= S::DV) { af -= S::DV; ap += 1; }
+                            };
+                            static_for<0, MW>([&](auto wc) {
+                                constexpr int w = decltype(wc)::value, nsw = (NS - 8 * w) < 8 ? (NS - 8 * w) : 8;
+                                constexpr int B = MADRL_PG_TO_BATCH < nsw ? MADRL_PG_TO_BATCH : nsw;
+                                auto batch = [&](auto nbc, int i0) {   // slots i0 .. i0 + nb - 1 of mask word w
+                                    constexpr int nb = decltype(nbc)::value;
+                                    uint32_t need[nb], any = 0u;
+                                    {
+                                        int bq = q, bf = fq, bp = pq;
+#pragma unroll
+                                        for (int j = 0; j < nb; ++j) {
+                                            const bool valid = bq < S::NQ;
+                                            const int pp = valid ? bp : 0;
+                                            uint32_t v0, v1, v2, v3;
+                                            read_slot(pp, bf, v0, v1, v2, v3);
+                                            need[j] = valid ? need_of(wc, nsw - 1 - (i0 + j), pp < np, v0, v1, v2, v3) : 0u;
+                                            any |= need[j];
+                                            advance(bq, bf, bp);
+                                        }
+                                    }
+                                    auto stores = [&](const v4u (&old)[nb]) {
+#pragma unroll
+                                        for (int j = 0; j < nb; ++j) {
+                                            const bool valid = q < S::NQ;
+                                            const int pp = valid ? pq : 0;
+                                            uint32_t v0, v1, v2, v3;
+                                            read_slot(pp, fq, v0, v1, v2, v3);
+                                            emit(wc, nsw - 1 - (i0 + j), q, valid, pp < np, old[j], v0, v1, v2, v3);
+                                            advance(q, fq, pq);
+                                        }
+                                    };
+                                    v4u old[nb];
+#pragma unroll
+                                    for (int j = 0; j < nb; ++j) old[j] = v4u{0u, 0u, 0u, 0u};
+                                    if (__builtin_amdgcn_ballot_w64(any != 0u) != 0ull) {
+#pragma unroll
+                                        for (int j = 0; j < nb; ++j)
+                                            if (need[j] != 0u) old[j] = prow[q + NT * j];
+                                        stores(old);
+                                    } else {
+                                        stores(old);
+                                    }
+                                };
+#pragma unroll 1
+                                for (int i = 0; i + B <= nsw; i += B) batch(std::integral_constant<int, B>{}, i);
+                                if constexpr (nsw % B != 0) batch(std::integral_constant<int, nsw % B>{}, nsw - nsw % B);
+                            });
+                        } else {
+                            // (slot constants in registers: short rows.  The live form with five or more slots has no register to spare: one slot at a time)
+                            constexpr int TG = (S::LIVE && NS > 4) ? 1 : (MADRL_PG_TO_RBATCH < NS ? MADRL_PG_TO_RBATCH : NS);
+                            auto read_slot = [&](auto sc, uint32_t &v0, uint32_t &v1, uint32_t &v2, uint32_t &v3) {
+                                constexpr int s = decltype(sc)::value;
+                                const int base = (int)L[s_org[s]];
+                                v0 = L[base + s_cst[s][0]];
+                                v1 = L[base + s_cst[s][1]];
+                                v2 = L[base + s_cst[s][2]];
+                                v3 = L[(int)__umul24((uint32_t)base, (uint32_t)s_rel3[s]) + s_cst[s][3]];
+                            };
+                            auto valid_of = [&](auto sc) -> bool {
+                                constexpr int s = decltype(sc)::value;
+                                return (NT * (s + 1) <= S::NQ) ? true : (fresh(tid) + NT * s < S::NQ);
+                            };
+                            static_for<0, (NS + TG - 1) / TG>([&](auto gc) {
+                                constexpr int g0 = decltype(gc)::value * TG, g1 = g0 + TG < NS ? g0 + TG : NS;
+                                uint32_t need[TG], any = 0u;
+                                static_for<g0, g1>([&](auto sc) {
+                                    constexpr int s = decltype(sc)::value;
+                                    uint32_t v0, v1, v2, v3;
+                                    read_slot(sc, v0, v1, v2, v3);
+                                    need[s - g0] = valid_of(sc) ? need_of(std::integral_constant<int, 0>{}, NS - 1 - s, s_org[s] - S::X_ORG < np, v0, v1, v2, v3) : 0u;
+                                    any |= need[s - g0];
+                                });
+                                auto stores = [&](const v4u (&old)[TG]) {
+                                    static_for<g0, g1>([&](auto sc) {
+                                        constexpr int s = decltype(sc)::value;
+                                        uint32_t v0, v1, v2, v3;
+                                        read_slot(sc, v0, v1, v2, v3);
+                                        emit(std::integral_constant<int, 0>{}, NS - 1 - s, tid + NT * s, valid_of(sc), s_org[s] - S::X_ORG < np, old[s - g0], v0, v1, v2, v3);
+                                    });
+                                };
+                                v4u old[TG];
+#pragma unroll
+                                for (int j = 0; j < TG; ++j) old[j] = v4u{0u, 0u, 0u, 0u};
+                                if (__builtin_amdgcn_ballot_w64(any != 0u) != 0ull) {
+                                    static_for<g0, g1>([&](auto sc) {
+                                        constexpr int s = decltype(sc)::value;
+                                        if (need[s - g0] != 0u) old[s - g0] = prow[tid + NT * s];
+                                    });
+                                    stores(old);
+                                } else {
+                                    stores(old);
+                                }
+                            });
+                        }
+#pragma unroll
+                        for (int w = 0; w < MW; ++w) zm[w] = acc[w];
+                    }
+                }
+                if (in_place) {
                     typedef float v4f __attribute__((ext_vector_type(4)));
                     v4f *orow = reinterpret_cast<v4f *>(io.obs + env * (int64_t)(P * S::D));
                     uint32_t acc[MW];

@@ -405,8 +405,9 @@ class BatchedPursuitEvade(AbstractMAEnv):
         passes of a fused auto-reset included -- and BECOMES the env's current buffer; the previous one is not written.  Returns what
         step() returns, the observation being the [N, P, D] / [N, P, R, R, 4] view of obs_out.  obs_out that is the current buffer is
         step(); a buffer that overlaps it otherwise is refused.
-        The one-wavefront and crowd shapes of csrc/pursuit_to_specializations.def have two-buffer fast kernels; every other handle
-        (multi-wavefront shapes and train_pursuit=False included) runs this call on the generic kernel (step_to_kernel_kind)."""
+        The one-wavefront, multi-wavefront and crowd shapes of csrc/pursuit_to_specializations.def have two-buffer fast kernels (with
+        per-env agent counts: the XL / XLG / XLC lines); every other handle (train_pursuit=False included) runs this call on the generic
+        kernel (step_to_kernel_kind)."""
         N, P, E = self.n_envs, int(self.n_pursuers), int(self.n_evaders)
         dest = self._obs_destination(obs_out)
         if dest is None:
@@ -426,7 +427,8 @@ class BatchedPursuitEvade(AbstractMAEnv):
 
     @property
     def step_to_kernel_kind(self):
-        """'wave' | 'generic': the kernel a step_to of this env launches ('wave': the two-buffer instantiation of its fast kernel)"""
+        """'wave' | 'generic': the kernel a step_to of this env launches ('wave': the two-buffer instantiation of its fast kernel -- one
+        wavefront per env, a group of wavefronts or the crowd kernel)"""
         out = C.c_int32()
         _lib.check(_lib.lib().madrl_pursuit_step_to_kernel_kind(self._handle, C.byref(out)))
         return {_lib.KERNEL_GENERIC: "generic", _lib.KERNEL_WAVE: "wave"}[out.value]

@@ -2,7 +2,7 @@
 rollout step (policy launch + step kernel + whatever moves the observations into the trajectory), at
     c2       BASELINE configs[1]: 16 x 16, 8 v 30, obs_range 7, 65 536 envs, T = 16      (one-wavefront kernel)
     cnn      the authors' CNN line: 128 x 128 pool, 100 v 300, obs_range 21, (R, R, 4) rows, 1 024 envs, T = 8   (crowd kernel)
-    authors  the authors' 30 v 50 line: 32 x 32 pool, obs_range 11, 16 384 envs, T = 8   (multi-wavefront kernel; step_to: generic kernel)
+    authors  the authors' 30 v 50 line: 32 x 32 pool, obs_range 11, 16 384 envs, T = 8   (multi-wavefront kernel)
 each after 2 000 untimed steps, so that the stale-zero masks are at their equilibrium.
 
     python scripts/rollout_store_time.py [c2|cnn|authors ...] [--root DIR] [--reps K] [--copy]
