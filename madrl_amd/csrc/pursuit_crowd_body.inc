@@ -24,7 +24,22 @@
     uint8_t *const s_ay = s_ax + S::A16;
 
     // ---- once per workgroup: the value table and (flatten) the element codes: channel << 24 | cell offset in the window; channel 3 = the id
-    for (int k = tid0; k < 256; k += NT) s_vtab[k] = d.vtab[k];
+    // (compile-time trips, every thread loading from an index clamped to the table's end, all loads before the one wait: "table staging",
+    // pursuit_wave.hpp -- the strided loop compiled to one dependent round trip per 64 NW values)
+    {
+        constexpr int TV = (256 + NT - 1) / NT;
+        float vt[TV];
+#pragma unroll
+        for (int t = 0; t < TV; ++t) {
+            const uint32_t k = (uint32_t)tid0 + (uint32_t)(NT * t);
+            vt[t] = d.vtab[k < 256u ? k : 255u];
+        }
+#pragma unroll
+        for (int t = 0; t < TV; ++t) {
+            const uint32_t k = (uint32_t)tid0 + (uint32_t)(NT * t);
+            if (k < 256u) s_vtab[k] = vt[t];
+        }
+    }
     if constexpr (S::FLATTEN) {
         for (int r = tid0; r < D; r += NT) {
             const int c = r / (R * R), rr = r - c * (R * R), i = rr / R, j = rr - i * R;
@@ -83,9 +98,21 @@
         auto load_map = [&](int m) {
             if (cached_map == m) return;
             const uint32_t *mt = reinterpret_cast<const uint32_t *>(d.maps + (int64_t)m * d.map_stride);
-            for (int k = tid; k < GSZ / 4; k += NT) {
-                const uint32_t w = mt[k];
-                reinterpret_cast<uint4 *>(cell)[k] = make_uint4(w & 0xFFu, (w >> 8) & 0xFFu, (w >> 16) & 0xFFu, w >> 24);
+            // batches of at most 8 compile-time trips: the batch's loads (clamped to the map's last word), one wait, its LDS writes
+            constexpr int MAPW = GSZ / 4, TM = (MAPW + NT - 1) / NT;
+#pragma unroll
+            for (int t0 = 0; t0 < TM; t0 += 8) {
+                uint32_t mw[8];
+#pragma unroll
+                for (int t = t0; t < (t0 + 8 < TM ? t0 + 8 : TM); ++t) {
+                    const uint32_t k = (uint32_t)tid + (uint32_t)(NT * t);
+                    mw[t - t0] = mt[k < (uint32_t)MAPW ? k : (uint32_t)MAPW - 1u];
+                }
+#pragma unroll
+                for (int t = t0; t < (t0 + 8 < TM ? t0 + 8 : TM); ++t) {
+                    const uint32_t k = (uint32_t)tid + (uint32_t)(NT * t), w = mw[t - t0];
+                    if (k < (uint32_t)MAPW) reinterpret_cast<uint4 *>(cell)[k] = make_uint4(w & 0xFFu, (w >> 8) & 0xFFu, (w >> 16) & 0xFFu, w >> 24);
+                }
             }
             cached_map = m;
         };

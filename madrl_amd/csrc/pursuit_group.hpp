@@ -153,37 +153,71 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
     const int eslot = tid - P;
 
     // ---------------------------------------------------------------- once per workgroup
-    for (int k = tid; k < GSZ; k += NT) {  // count layers: 0 inside the map, SENT outside
-        const uint32_t v = d.cnt_tmpl[k];
-        L[GSZ + k] = v;
-        L[2 * GSZ + k] = v;
-    }
-    if (tid == 0) {
-        L[S::X_FILL] = d.fmaps[0];
-        L[S::X_SKIP] = SENT;
-    }
-    if (tid < P) L[S::X_ID + tid] = __float_as_uint((float)((double)tid / (double)P));
-    for (int k = tid; k < S::NVT; k += NT) L[S::X_VTAB + k] = __float_as_uint(d.vtab[k]);
+    // The tables, the slot constants and the first env's record, action and masks in one batch of loads with one wait ("table staging",
+    // pursuit_wave.hpp; map 0 is staged with the tables as there) -- in two where they do not fit FILL_FIRST registers.  The
+    // group_sync before the env loop publishes the LDS writes.  The per-env-counts kernels (LIVE) stage tables and slot constants the
+    // same way and fetch their first env as a batch of its own after it: with that fetch in the first batch they compile to a 36-byte
+    // stack frame at every batch size down to 4 trips (tests/test_live_counts_group_isa.py forbids one).
+    using F = Fill<S, NT>;
     constexpr int NSR = S::TABLED ? 1 : NS;   // slots whose constants live in registers
+    constexpr int NSL = S::TABLED ? 0 : NS;   // ... and are loaded here
+    constexpr int MW = S::MWORDS;
+    if (d.n_envs <= 0) return;   // (the batched start-up fetches an env unconditionally)
+    const uint32_t *const vtab_u = reinterpret_cast<const uint32_t *>(d.vtab);   // (TABLED: d.slot_tab is the [DV][2] table of packed offsets, a fill of its own)
+    constexpr int ROOM = FILL_FIRST - 6 * NSL - 2 - MW;
+    constexpr int JF = F::J_END < (ROOM > 4 ? ROOM : 4) ? F::J_END : (ROOM > 4 ? ROOM : 4);
     int s_cst[NSR][4];
     int s_rel3[NSR];
     int s_org[NSR];    // LDS index of the owning pursuer's window origin
-    if constexpr (S::TABLED) {
-        for (int k = tid; k < 2 * S::DV; k += NT) L[S::X_TAB + k] = d.slot_tab[k];   // host-built (pursuit.hip): [DV][2] packed offsets
-    } else {
+    uint32_t cur_rec = 0, cur_zm[MW];
 #pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const uint32_t *t = d.slot_tab + s * 6 * NT + tid;  // host-built (pursuit.hip), see WaveDev
+    for (int w = 0; w < MW; ++w) cur_zm[w] = 0xFFFFFFFFu;
+    int cur_act = 4;
+    {
+        uint32_t st[JF], sraw[6 * NSL + 1];
+        static_for<0, JF>([&](auto jc) { st[decltype(jc)::value] = fill_load<S, NT, decltype(jc)::value>(utid, d.cnt_tmpl, d.fmaps, vtab_u, d.slot_tab); });
 #pragma unroll
-            for (int k = 0; k < 4; ++k) s_cst[s][k] = (int)t[NT * k];
-            s_rel3[s] = (int)t[NT * 4];
-            s_org[s] = S::X_ORG + (int)t[NT * 5];
+        for (int k = 0; k < 6 * NSL; ++k) sraw[k] = d.slot_tab[(uint32_t)NT * k + utid];  // host-built (pursuit.hip), see WaveDev: [NS][6][NT]
+        // the first env of this workgroup (a workgroup without one fetches the last env's and never looks at it); every thread loads, from
+        // clamped offsets
+        __builtin_amdgcn_sched_barrier(0);  // these stay the loads issued last
+        if constexpr (!S::LIVE) {
+            const int ne0 = (int)d.n_envs, e0 = (int)blockIdx.x < ne0 ? (int)blockIdx.x : ne0 - 1;
+            const int64_t env0 = (int64_t)(d.reverse ? ne0 - 1 - e0 : e0);
+            const uint32_t rec_off = (ulane < (uint32_t)S::REC_DW ? ulane : (uint32_t)S::REC_DW - 1u) * 4u;
+            const uint32_t act_off = (utid < (uint32_t)P ? utid : (uint32_t)P - 1u) * 4u;
+            cur_rec = *reinterpret_cast<const uint32_t *>(d.state + env0 * (int64_t)S::REC_BYTES + rec_off);
+            if constexpr (MODE == 1) cur_act = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(io.actions + env0 * P) + act_off);
+#pragma unroll
+            for (int w = 0; w < MW; ++w) {
+                if (w == MW - 1) __builtin_amdgcn_sched_barrier(0);
+                cur_zm[w] = d.zmask[(env0 * MW + w) * NT + utid];
+            }
+        }
+        if constexpr (!S::LIVE) {
+            staged_wait<MW>(cur_zm);  // the loads issued last: the one wait, vmcnt(0), of the whole batch
+            asm volatile("" : "+v"(cur_rec), "+v"(cur_act));
+        }
+        staged_wait<6 * NSL>(sraw);
+        staged_wait<JF>(st);
+        static_for<0, JF>([&](auto jc) { fill_store<S, NT, decltype(jc)::value, true>(L, utid, st[decltype(jc)::value]); });
+        fill_trips<S, NT, JF, F::J_END, FILL_BATCH, true>(L, utid, d.cnt_tmpl, d.fmaps, vtab_u, d.slot_tab);
+        if (tid < P) L[S::X_ID + tid] = __float_as_uint((float)((double)tid / (double)P));
+        if constexpr (!S::LIVE) {
+            if (ulane >= (uint32_t)S::REC_DW) cur_rec = 0u;
+            if (!is_p) cur_act = 4;
+        }
+        if constexpr (!S::TABLED) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) s_cst[s][k] = (int)sraw[6 * s + k];
+                s_rel3[s] = (int)sraw[6 * s + 4];
+                s_org[s] = S::X_ORG + (int)sraw[6 * s + 5];
+            }
         }
     }
     const int q0_p = tid / S::DV, q0_f = tid % S::DV;   // TABLED: (pursuer, float4 position in its row) of this thread's slot 0
-    // map 0 is staged with the tables above (pursuit_wave.hpp); the group_sync before the env loop publishes it
-    for (int k = tid; k < GSZ; k += NT) L[k] = d.fmaps[k];
-    for (int k = tid; k < (S::XS * S::YS + 3) / 4; k += NT) L[S::X_NEED + k] = d.fmaps[GSZ + k];
     int cached_map = 0;
     int cached_np = P;  // LIVE: the pursuer count the id cells X_ID.. hold (k / np, :440-445)
     const uint8_t *need_tab = reinterpret_cast<const uint8_t *>(&L[S::X_NEED]);
@@ -227,26 +261,23 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
             return ((uint64_t)hi << 32) | lo;
         }
     };
-    constexpr int MW = S::MWORDS;
     auto fetch_zm = [&](int64_t env, uint32_t (&zmw)[MW]) {   // stale-zero masks, pursuit_wave.hpp: [env][MWORDS][NT]
 #pragma unroll
         for (int w = 0; w < MW; ++w) zmw[w] = uniform_ptr(d.zmask + (env * MW + w) * NT)[utid];
     };
-    uint32_t cur_rec = 0, cur_zm[MW];
-#pragma unroll
-    for (int w = 0; w < MW; ++w) cur_zm[w] = 0xFFFFFFFFu;
-    int cur_act = 4;
     // env indices are 32-bit (the fast path is not taken for n_envs >= 2^31 - 2^20), byte offsets 64-bit
     const int n_envs = (int)d.n_envs, stride = (int)gridDim.x;
     auto phys = [&](int e) -> int64_t { return (int64_t)(d.reverse ? n_envs - 1 - e : e); };
-    if ((int)blockIdx.x < n_envs) {
-        cur_rec = fetch_rec(phys(blockIdx.x));
-        cur_act = fetch_act(phys(blockIdx.x));
-        fetch_zm(phys(blockIdx.x), cur_zm);
-    }
-    asm volatile("" : "+v"(cur_rec), "+v"(cur_act));
+    if constexpr (S::LIVE) {   // the first env, a batch of its own (see the start-up above)
+        if ((int)blockIdx.x < n_envs) {
+            cur_rec = fetch_rec(phys(blockIdx.x));
+            cur_act = fetch_act(phys(blockIdx.x));
+            fetch_zm(phys(blockIdx.x), cur_zm);
+        }
+        asm volatile("" : "+v"(cur_rec), "+v"(cur_act));
 #pragma unroll
-    for (int w = 0; w < MW; ++w) asm volatile("" : "+v"(cur_zm[w]));
+        for (int w = 0; w < MW; ++w) asm volatile("" : "+v"(cur_zm[w]));
+    }
     group_sync();
 
     for (int e = blockIdx.x; e < n_envs; e += stride) {
@@ -314,9 +345,10 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
             auto load_map = [&](int mid) {
                 if (cached_map == mid) return;
                 const KArgsPtr ka = cold_args();  // rare-path launch parameters come from the kernarg segment (pursuit_wave.hpp)
-                const uint32_t *src = ka->d.fmaps + (int64_t)mid * ka->d.fmap_stride;
-                for (int k = tid; k < GSZ; k += NT) L[k] = src[k];
-                for (int k = tid; k < (S::XS * S::YS + 3) / 4; k += NT) L[S::X_NEED + k] = src[GSZ + k];
+                // the map layer and its need bytes in batches of at most FILL_BATCH trips (the slot constants are live here): per batch all
+                // loads, one wait to zero, then the LDS writes (table staging).  One batch up to 16 trips: 14 at C5 (32 x 32 on two
+                // wavefronts), 8 at the authors' shape
+                fill_trips<S, NT, F::J_MAP, F::J_VT, FILL_BATCH, false>(L, utid, nullptr, ka->d.fmaps + (int64_t)mid * ka->d.fmap_stride, nullptr, nullptr);
                 cached_map = mid;
                 group_sync();
             };

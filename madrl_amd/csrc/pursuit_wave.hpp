@@ -140,6 +140,8 @@ struct Shape {
     static_assert(NS <= 8, "stale-zero mask: one bit per slot in each byte of the lane's mask dword");
     static constexpr bool LIVE = false;
     static constexpr bool TO = false;
+    static constexpr bool TABLED = false;                        // (pursuit_group.hpp: slot constants from an LDS table; never here)
+    static constexpr int X_TAB = 0;
 };
 
 // Per-env agent counts (madrl_pursuit_set_agent_counts): the same geometry, with P and E as a CAPACITY.  An env runs LIVE p <= P
@@ -295,6 +297,101 @@ __device__ __forceinline__ void put_zero_from(uint32_t &w) {
     }
 }
 
+// ---------------------------------------------------------------- table staging (once per workgroup, and at a change of map)
+// The per-workgroup tables go from global memory to LDS in strided TRIPS: trip j of a table moves elements [NT j, NT j + NT), one per
+// thread.  Written as `for (k = tid; k < n; k += NT) L[k] = tab[k]` the compiler emits load -> s_waitcnt vmcnt(0) -> ds_write per
+// trip, each next load behind a branch on the bounds test: one dependent round trip to L2 per trip, about twenty before a workgroup's
+// first env, made by every workgroup of a launch at the same moment.  Here the trips have compile-time numbers, every thread loads
+// unconditionally from an index CLAMPED to the table's last element (the host sizes the tables exactly: no read may pass their end;
+// the bounds test stays on the LDS write alone), all loads of a batch are issued before its first value is used, and the batch is
+// waited for ONCE (staged_wait).  Fill<S, NT> numbers the trips of all tables of a shape:
+//   [0, J_MAP) empty count layer -> layers 1 and 2   [J_MAP, J_NEED) map layer   [J_NEED, J_VT) need_to_surround bytes
+//   [J_VT, J_TAB) count values   [J_TAB, J_END) the long-row slot table of the multi-wavefront kernel (TABLED shapes)
+template <class S, int NT>
+struct Fill {
+    static constexpr int NEEDW = (S::XS * S::YS + 3) / 4;
+    static constexpr int TABW = S::TABLED ? 2 * S::DV : 0;
+    static constexpr int J_MAP = (S::GSZ + NT - 1) / NT;
+    static constexpr int J_NEED = 2 * J_MAP;
+    static constexpr int J_VT = J_NEED + (NEEDW + NT - 1) / NT;
+    static constexpr int J_TAB = J_VT + (S::NVT + NT - 1) / NT;
+    static constexpr int J_END = J_TAB + (TABW + NT - 1) / NT;
+    static constexpr int first(int j) { return j < J_MAP ? 0 : j < J_NEED ? J_MAP : j < J_VT ? J_NEED : j < J_TAB ? J_VT : J_TAB; }
+    static constexpr int words(int j) { return j < J_NEED ? S::GSZ : j < J_VT ? NEEDW : j < J_TAB ? S::NVT : TABW; }
+};
+// (the sources: cnt = WaveDev::cnt_tmpl, map = the map's entry of WaveDev::fmaps -- layer, then the need bytes --, vtab, tab = the slot table)
+template <class S, int NT, int J>
+__device__ __forceinline__ uint32_t fill_load(uint32_t utid, const uint32_t *cnt, const uint32_t *map, const uint32_t *vtab, const uint32_t *tab) {
+    using F = Fill<S, NT>;
+    constexpr int t = J - F::first(J), n = F::words(J);
+    const uint32_t k = utid + (uint32_t)(NT * t);
+    const uint32_t kc = (NT * (t + 1) <= n) ? k : (k < (uint32_t)n ? k : (uint32_t)n - 1u);
+    if constexpr (J < F::J_MAP) return cnt[kc];
+    else if constexpr (J < F::J_NEED) return map[kc];
+    else if constexpr (J < F::J_VT) return map[(uint32_t)S::GSZ + kc];
+    else if constexpr (J < F::J_TAB) return vtab[kc];
+    else return tab[kc];
+}
+// FIRST: the workgroup's first fill also sets the two cells the slot constants of absent elements point at
+template <class S, int NT, int J, bool FIRST>
+__device__ __forceinline__ void fill_store(uint32_t *L, uint32_t utid, uint32_t v) {
+    using F = Fill<S, NT>;
+    constexpr int t = J - F::first(J), n = F::words(J);
+    const uint32_t k = utid + (uint32_t)(NT * t);
+    if ((NT * (t + 1) <= n) || k < (uint32_t)n) {
+        if constexpr (J < F::J_MAP) {
+            L[S::GSZ + k] = v;
+            L[2 * S::GSZ + k] = v;
+        } else if constexpr (J < F::J_NEED) L[k] = v;
+        else if constexpr (J < F::J_VT) L[S::X_NEED + k] = v;
+        else if constexpr (J < F::J_TAB) L[S::X_VTAB + k] = v;
+        else L[S::X_TAB + k] = v;
+    }
+    if constexpr (FIRST && J == F::J_MAP) {
+        if (utid == 0u) {
+            L[S::X_FILL] = v;   // element 0 of map 0: a corner of the padded map layer is always outside the map
+            L[S::X_SKIP] = SENT;
+        }
+    }
+}
+// The one wait of a batch of N staged registers a[0 .. N): groups of empty-asm operands from the END of the array -- the loads issued
+// last -- so that the first group makes the compiler wait with s_waitcnt vmcnt(0) and the others need no wait at all.  (Left to
+// itself it waits before each LDS write with a counted vmcnt(k); correct, but one of them is then the vmcnt(VM_PER_ENV) that
+// tests/test_wave_isa_budget.py wants to find in exactly one place.)
+template <int N>
+__device__ __forceinline__ void staged_wait(uint32_t *a) {
+    if constexpr (N >= 8) {
+        asm volatile("" : "+v"(a[N - 1]), "+v"(a[N - 2]), "+v"(a[N - 3]), "+v"(a[N - 4]), "+v"(a[N - 5]), "+v"(a[N - 6]), "+v"(a[N - 7]), "+v"(a[N - 8]));
+        staged_wait<N - 8>(a);
+    } else if constexpr (N >= 4) {
+        asm volatile("" : "+v"(a[N - 1]), "+v"(a[N - 2]), "+v"(a[N - 3]), "+v"(a[N - 4]));
+        staged_wait<N - 4>(a);
+    } else if constexpr (N >= 2) {
+        asm volatile("" : "+v"(a[N - 1]), "+v"(a[N - 2]));
+        staged_wait<N - 2>(a);
+    } else if constexpr (N == 1) {
+        asm volatile("" : "+v"(a[0]));
+    }
+}
+// trips [J0, J1) in batches of at most CAP: per batch all loads, one wait, the LDS writes
+template <class S, int NT, int J0, int J1, int CAP, bool FIRST>
+__device__ __forceinline__ void fill_trips(uint32_t *L, uint32_t utid, const uint32_t *cnt, const uint32_t *map, const uint32_t *vtab, const uint32_t *tab) {
+    if constexpr (J0 < J1) {
+        constexpr int JB = J0 + CAP < J1 ? J0 + CAP : J1;
+        uint32_t st[JB - J0];
+        static_for<J0, JB>([&](auto jc) {
+            if constexpr (decltype(jc)::value == JB - 1) __builtin_amdgcn_sched_barrier(0);  // the load staged_wait looks at first stays the last one issued
+            st[decltype(jc)::value - J0] = fill_load<S, NT, decltype(jc)::value>(utid, cnt, map, vtab, tab);
+        });
+        staged_wait<JB - J0>(st);
+        static_for<J0, JB>([&](auto jc) { fill_store<S, NT, decltype(jc)::value, FIRST>(L, utid, st[decltype(jc)::value - J0]); });
+        fill_trips<S, NT, JB, J1, CAP, FIRST>(L, utid, cnt, map, vtab, tab);
+    }
+}
+// registers a workgroup's first batch may hold in flight (table trips + slot constants + the first env's fetch), and the table trips
+// of every later batch (also of a change of map inside the env loop, where the slot constants are live as well)
+constexpr int FILL_FIRST = 56, FILL_BATCH = 16;
+
 // Profiling aid (scripts/variants.sh builds one library per value, never the shipped one):
 //   1 no observation stores   2 store stale cells too (all float4 full, nt)   4 no Philox
 //   8 no observation pass at all   16 no record / reward stores
@@ -346,34 +443,55 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
     if (d.n_envs > 0) return;
 #endif
     // ---------------------------------------------------------------- once per workgroup
-    for (int k = lane; k < GSZ; k += 64) {  // count layers: 0 inside the map, SENT outside
-        const uint32_t v = d.cnt_tmpl[k];
-        L[GSZ + k] = v;
-        L[2 * GSZ + k] = v;
+    // Everything a workgroup needs before its first env comes in ONE batch of loads with one wait (see "table staging"): the empty
+    // count layer, map 0, its need_to_surround bytes, the count values, the observation slot constants and the first env's record,
+    // action and mask.  Map 0 is staged with the tables: with a single map -- every BASELINE config -- the first env then needs no
+    // second round trip to HBM for a map chosen by its record, at a moment when every wavefront of the launch waits for the same
+    // thing.  With a map pool the first env may reload (load_map below).  (Shapes whose tables do not fit FILL_FIRST registers
+    // beside their slot constants stage the rest in further batches.)
+    using F = Fill<S, 64>;
+    const int n_envs = (int)d.n_envs, stride = (int)gridDim.x;  // env indices are 32-bit (the C ABI caps n_envs below 2^31); only byte offsets are 64-bit
+    if (n_envs <= 0) return;
+    auto phys = [&](int e) -> int64_t { return (int64_t)(d.reverse ? n_envs - 1 - e : e); };
+    const uint32_t *const vtab_u = reinterpret_cast<const uint32_t *>(d.vtab);
+    constexpr int ROOM = FILL_FIRST - 6 * NS - 3;
+    constexpr int JF = F::J_END < (ROOM > 4 ? ROOM : 4) ? F::J_END : (ROOM > 4 ? ROOM : 4);
+    const uint32_t rec_off = (ulane < (uint32_t)S::REC_DW ? ulane : (uint32_t)S::REC_DW - 1u) * 4u;
+    const uint32_t act_off = (ulane < (uint32_t)P ? ulane : (uint32_t)P - 1u) * 4u;
+    uint32_t st[JF], sraw[6 * NS];
+    static_for<0, JF>([&](auto jc) { st[decltype(jc)::value] = fill_load<S, 64, decltype(jc)::value>(ulane, d.cnt_tmpl, d.fmaps, vtab_u, nullptr); });
+#pragma unroll
+    for (int k = 0; k < 6 * NS; ++k) sraw[k] = d.slot_tab[64u * k + ulane];  // [NS][6][64]; slots past the end of the row read harmless cells and are never stored
+    // the first env of this workgroup (a workgroup without one fetches the last env's and never looks at it: every lane loads, from
+    // clamped offsets, like the prefetch of the env loop)
+    uint32_t cur_rec, cur_zm;
+    int cur_act = 4;
+    __builtin_amdgcn_sched_barrier(0);  // these three stay the loads issued last
+    {
+        const int64_t env0 = phys((int)blockIdx.x < n_envs ? (int)blockIdx.x : n_envs - 1);
+        cur_rec = *reinterpret_cast<const uint32_t *>(d.state + env0 * (int64_t)S::REC_BYTES + rec_off);
+        if constexpr (MODE == 1) cur_act = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(io.actions + env0 * P) + act_off);
+        cur_zm = d.zmask[env0 * 64 + ulane];
     }
-    if (lane == 0) {
-        L[S::X_FILL] = d.fmaps[0];  // a corner of the padded map layer is always outside the map
-        L[S::X_SKIP] = SENT;
-    }
+    asm volatile("" : "+v"(cur_rec), "+v"(cur_act), "+v"(cur_zm));  // the loads issued last: the one wait, vmcnt(0), of the whole batch
+    staged_wait<6 * NS>(sraw);
+    staged_wait<JF>(st);
+    static_for<0, JF>([&](auto jc) { fill_store<S, 64, decltype(jc)::value, true>(L, ulane, st[decltype(jc)::value]); });
+    fill_trips<S, 64, JF, F::J_END, FILL_BATCH, true>(L, ulane, d.cnt_tmpl, d.fmaps, vtab_u, nullptr);
     if (lane < P) L[S::X_ID + lane] = __float_as_uint((float)((double)lane / (double)P));  // :440-445
-    for (int k = lane; k < S::NVT; k += 64) L[S::X_VTAB + k] = __float_as_uint(d.vtab[k]);
+    if (ulane >= (uint32_t)S::REC_DW) cur_rec = 0u;
+    if (!is_p) cur_act = 4;
     // observation slot constants (registers, live across the env loop)
     int s_cst[NS][4];
     int s_rel3[NS];   // 1: element 3 is window-relative, 0: absolute (id / skip cell)
     int s_src[NS];    // ds_bpermute byte address of the owning pursuer's lane
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        const uint32_t *t = d.slot_tab + s * 6 * 64 + lane;  // slots past the end of the row read harmless cells and are never stored
 #pragma unroll
-        for (int k = 0; k < 4; ++k) s_cst[s][k] = (int)t[64 * k] * 4;  // byte offsets into L
-        s_rel3[s] = (int)t[64 * 4];
-        s_src[s] = (int)t[64 * 5] * 4;
+        for (int k = 0; k < 4; ++k) s_cst[s][k] = (int)sraw[6 * s + k] * 4;  // byte offsets into L
+        s_rel3[s] = (int)sraw[6 * s + 4];
+        s_src[s] = (int)sraw[6 * s + 5] * 4;
     }
-    // Map 0 is staged with the tables above (its loads are in flight together with theirs): with a single map -- every BASELINE
-    // config -- the first env then needs no second round trip to HBM for a map chosen by its record, at a moment when every
-    // wavefront of the launch waits for the same thing.  With a map pool the first env may reload (load_map below).
-    for (int k = lane; k < GSZ; k += 64) L[k] = d.fmaps[k];
-    for (int k = lane; k < (S::XS * S::YS + 3) / 4; k += 64) L[S::X_NEED + k] = d.fmaps[GSZ + k];
     int cached_map = 0;
     int cached_np = P;  // live-count kernel: the pursuer count the id cells X_ID.. hold (k / np, :440-445)
     const uint8_t *need_tab = reinterpret_cast<const uint8_t *>(&L[S::X_NEED]);
@@ -396,17 +514,6 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
         else return 4;
     };
     auto fetch_zm = [&](int64_t env) -> uint32_t { return uniform_ptr(d.zmask + env * 64)[ulane]; };
-    uint32_t cur_rec = 0, cur_zm = 0xFFFFFFFFu;
-    int cur_act = 4;
-    // env indices are 32-bit (the C ABI caps n_envs below 2^31); only byte offsets are 64-bit
-    const int n_envs = (int)d.n_envs, stride = (int)gridDim.x;
-    auto phys = [&](int e) -> int64_t { return (int64_t)(d.reverse ? n_envs - 1 - e : e); };
-    if ((int)blockIdx.x < n_envs) {
-        cur_rec = fetch_rec(phys(blockIdx.x));
-        cur_act = fetch_act(phys(blockIdx.x));
-        cur_zm = fetch_zm(phys(blockIdx.x));
-    }
-    asm volatile("" : "+v"(cur_rec), "+v"(cur_act), "+v"(cur_zm));  // loads complete before the loop (see hinge below)
     wave_sync();
 #if MADRL_PW_EXP & 8
     if (d.n_envs > 0) { if (s_cst[0][0] + s_cst[NS - 1][3] + s_rel3[0] + s_src[NS - 1] + (int)cur_rec == 0x12345) io.rew[0] = 1.f; return; }
@@ -417,8 +524,6 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
     constexpr bool PIPE = (MODE == 1) && !INJECT && !(MADRL_ABLATE & (1 | 8 | 16 | 64));
     constexpr int VM_PER_ENV = 5 * NS + 6;  // stores every step iteration issues: NS x (4 dword + 1 float4), reward, done, removed, flag word, record, mask
     static_assert(!PIPE || VM_PER_ENV < 64, "vmcnt range");
-    const uint32_t rec_off = (ulane < (uint32_t)S::REC_DW ? ulane : (uint32_t)S::REC_DW - 1u) * 4u;
-    const uint32_t act_off = (ulane < (uint32_t)P ? ulane : (uint32_t)P - 1u) * 4u;
     for (int e = blockIdx.x; e < n_envs; e += stride) {
         const int64_t env = phys(e);
         const bool has_next = e + stride < n_envs;  // n_envs + number of workgroups < 2^31
@@ -482,9 +587,10 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
             auto load_map = [&](int mid) {
                 if (cached_map == mid) return;
                 const KArgsPtr ka = cold_args();
-                const uint32_t *src = ka->d.fmaps + (int64_t)mid * ka->d.fmap_stride;
-                for (int k = lane; k < GSZ; k += 64) L[k] = src[k];
-                for (int k = lane; k < (S::XS * S::YS + 3) / 4; k += 64) L[S::X_NEED + k] = src[GSZ + k];
+                // the map layer and its need bytes in batches of at most FILL_BATCH trips (the slot constants are live here): per batch all
+                // loads, one wait to zero, then the LDS writes (table staging).  One batch up to 16 trips -- 9 at 16 x 16, obs_range 7;
+                // a 32 x 32 map on one wavefront has 27 and reloads in two
+                fill_trips<S, 64, F::J_MAP, F::J_VT, FILL_BATCH, false>(L, ulane, nullptr, ka->d.fmaps + (int64_t)mid * ka->d.fmap_stride, nullptr, nullptr);
                 cached_map = mid;
                 wave_sync();
             };
