@@ -272,7 +272,11 @@ typedef struct madrl_waterworld_config {
     int32_t obstacle_fixed;  /* 1: obstacle at obstacle_loc; 0: obstacle_loc=None, random per reset (:147-151) */
     int32_t max_steps;       /* 0 = the reference's timestep_limit of 1000 (:124-126) */
     int32_t auto_reset;      /* 1: an env whose step ends with done is reset in the same launch */
-    int32_t reserved0;
+    int32_t crowd;           /* 0: one wavefront per env -- at most 62 particles, 32 pursuers, and the observation rows of an env must fit
+                                LDS.  1: ww_crowd_kernel, one workgroup of several wavefronts per env with the particles looped over its
+                                threads: n_pursuers <= 128, n_pursuers + n_evaders + n_poison <= 1023, any n_sensors in 1..256; same
+                                results bit for bit on a shape both take; no fused StandardizedEnv.  Anything else: MADRL_EINVAL.
+                                (The word was reserved0, which callers zeroed.) */
     double radius, obstacle_radius, ev_speed, poison_speed, sensor_range, action_scale;
     double poison_reward, food_reward, encounter_reward, control_penalty;
     double obstacle_loc[2];
@@ -293,13 +297,16 @@ int madrl_waterworld_create(const madrl_waterworld_config *cfg, const double *se
                             int32_t device, void *state_dev, madrl_waterworld **out);
 void madrl_waterworld_destroy(madrl_waterworld *h);
 int madrl_waterworld_set_launch(madrl_waterworld *h, int64_t max_blocks);
+/* which kernel the handle runs: 0 = one wavefront per env, 1 = the crowd kernel (cfg.crowd) */
+int madrl_waterworld_kernel_kind(madrl_waterworld *h, int32_t *out);
 
 /* Fused StandardizedEnv (madrl_environments/__init__.py:204-311): bind the wrapper's state to the env handle and the step /
  * reset kernels normalise the observation row as it leaves LDS (and the rewards as they are produced) instead of storing it
  * raw for a second launch (madrl_wrap_obsnorm / _rewnorm) to read back: 36 instead of 44 bytes of HBM traffic per observation
  * element, one launch instead of three.  Same arithmetic (float64 exponential running mean / variance per env, agent and
  * element, :242-271).  All pointers are device memory that stays valid while bound; running statistics start at mean 0 /
- * var 1 (:229-232).  While bound, obs_dev of reset / step may be NULL (the raw row is then not stored).  args NULL unbinds. */
+ * var 1 (:229-232).  While bound, obs_dev of reset / step may be NULL (the raw row is then not stored).  args NULL unbinds.
+ * A crowd handle (cfg.crowd = 1) has no fused form: binding returns MADRL_EINVAL, the epilogue kernels serve it. */
 typedef struct madrl_standardize_args {
     int32_t struct_size, enable_obsnorm, enable_rewnorm, reserved0;
     double obs_alpha, rew_alpha, eps, scale_reward;

@@ -41,7 +41,7 @@ class WaterworldConfig(C.Structure):
     """mirror of madrl_waterworld_config (include/madrl_hip.h)"""
     _fields_ = [(n, C.c_int32) for n in (
         "struct_size", "n_pursuers", "n_evaders", "n_coop", "n_poison", "n_sensors", "addid",
-        "speed_features", "reward_global", "obstacle_fixed", "max_steps", "auto_reset", "reserved0")] + [
+        "speed_features", "reward_global", "obstacle_fixed", "max_steps", "auto_reset", "crowd")] + [
             (n, C.c_double) for n in (
                 "radius", "obstacle_radius", "ev_speed", "poison_speed", "sensor_range", "action_scale",
                 "poison_reward", "food_reward", "encounter_reward", "control_penalty")] + [
@@ -114,6 +114,7 @@ SIGNATURES = {
     "madrl_waterworld_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp]),
     "madrl_waterworld_destroy": (None, [_vp]),
     "madrl_waterworld_set_launch": (C.c_int, [_vp, C.c_int64]),
+    "madrl_waterworld_kernel_kind": (C.c_int, [_vp, _vp]),
     "madrl_waterworld_set_standardize": (C.c_int, [_vp, _vp]),
     "madrl_waterworld_reset": (C.c_int, [_vp] * 4),
     "madrl_waterworld_step": (C.c_int, [_vp] * 8),

@@ -20,9 +20,11 @@
 //   step phases ........ MAWaterWorld.step :220-436      sensing ...... Archea.sensed :64-72
 //   catch rule ......... _caught :180-193                 respawn ...... _respawn :139-142, :355-374
 //   reset .............. :144-172 (ends with a zero-action step, W11)
+// Envs beyond a wavefront's worth of particles (more than 62, or more than 32 pursuers) run on ww_crowd_kernel (waterworld_crowd.hip) when
+// the handle was created with cfg.crowd = 1; the handle, validation, record layout and dispatch of both kernels are in this file.
 // Arithmetic is float32 (north_star tolerance 1e-5 against the float64 reference); every
 // expression keeps the statement order of the reference's step() so that a float32 CPU restatement agrees bit for bit.
-#include "common.hpp"
+#include "waterworld_dev.hpp"   // WwDev, WwStd, WwIO, the RNG tags: shared with waterworld_crowd.hip
 
 #include <math.h>
 #include <string.h>
@@ -30,48 +32,6 @@
 namespace {
 
 using namespace madrl;
-
-enum : uint32_t { WW_TAG_RESPAWN = 16, WW_TAG_RESET = 17, WW_TAG_OBSTACLE = 18 };
-
-struct WwDev {
-    int32_t Np, Ne, Npo, NP, K, D, nfeat;
-    int32_t n_coop, addid, speed_features, reward_global, obstacle_fixed, max_steps, auto_reset;
-    int32_t rec_dw;  // dwords per packed state record: pos[NP][2] vel[NP][2] obst[2] t tick
-    uint32_t k0, k1, gid_base;
-    float r_pu, r_ev, r_po, obst_r, ev_speed, poison_speed, sensor_range, action_scale;
-    float poison_reward, food_reward, encounter_reward, control_penalty;
-    float obst_x, obst_y;
-    // sq_*: sq_threshold() (common.hpp) of the distance thresholds: obstacle rebound per particle kind (:247-270), pursuer-evader /
-    // pursuer-poison contact (:272-293)
-    float sq_obst_pu, sq_obst_ev, sq_obst_po, sq_hit_ev, sq_hit_po;
-    int64_t n_envs;
-    const float *sensors;  // [K][2]
-    float *state;
-};
-
-// Fused StandardizedEnv (madrl_environments/__init__.py:204-311): when `obs_out` is set, the observation row is normalised as
-// it leaves LDS -- per env, per agent, per element exponential running mean / variance in float64, exactly the arithmetic of the
-// stand-alone epilogue kernel (wrappers.hip obsnorm_kernel / rewnorm_kernel) -- instead of being stored raw and read back by a
-// second launch: 36 instead of 44 bytes of HBM traffic per observation element.
-struct WwStd {
-    double *obs_mean, *obs_var;   // [N][Np][D]
-    float *obs_out;               // [N][Np][D] normalised observations; NULL = not fused
-    double *rew_mean, *rew_var;   // [N][Np]
-    float *rew_out;               // [N][Np] scale * (reward / (sqrt(var) + eps)); NULL = rewards are not touched
-    double obs_alpha, rew_alpha, eps, scale;
-    int32_t enable_obsnorm, enable_rewnorm;
-};
-
-struct WwIO {
-    const uint8_t *mask;    // reset mode
-    const float *actions;   // [N][Np][2]
-    const float *inj_resp;  // [N][NP][4] or NULL
-    float *obs;             // [N][Np][D]
-    float *rew;             // [N][Np]
-    uint8_t *done;          // [N]
-    int32_t *info;          // [N][2]  evcatches, pocatches
-    const WwStd *st;        // device copy of the fused-wrapper arguments, or NULL
-};
 
 // The launch parameters as read from the kernel-argument segment (kernargs(), common.hpp) at the phase that needs them.
 struct WwKArgs {
@@ -678,11 +638,19 @@ int ww_validate(const madrl_waterworld_config *c) {
     if (c->struct_size != (int32_t)sizeof(madrl_waterworld_config))
         return fail(MADRL_EINVAL, "madrl_waterworld_config.struct_size=%d, library expects %d", c->struct_size,
                     (int)sizeof(madrl_waterworld_config));
+    if (c->crowd != 0 && c->crowd != 1) return fail(MADRL_EINVAL, "madrl_waterworld_config.crowd must be 0 or 1 (got %d)", c->crowd);
     if (c->n_pursuers < 1 || c->n_evaders < 1 || c->n_poison < 1)
         return fail(MADRL_EINVAL, "n_pursuers, n_evaders, n_poison must be >= 1");
-    if (c->n_pursuers + c->n_evaders + c->n_poison > 62)
-        return fail(MADRL_EINVAL, "at most 62 particles per env (one wavefront per env)");
-    if (2 * c->n_pursuers > 64) return fail(MADRL_EINVAL, "n_pursuers must be <= 32");
+    if (c->crowd) {  // ww_crowd_kernel (waterworld_crowd.hip): particles looped over the threads of a multi-wavefront workgroup
+        if (c->n_pursuers > 128) return fail(MADRL_EINVAL, "crowd kernel: n_pursuers must be <= 128 (got %d)", c->n_pursuers);
+        if ((int64_t)c->n_pursuers + c->n_evaders + c->n_poison > 1023)
+            return fail(MADRL_EINVAL, "crowd kernel: at most 1023 particles per env (got %lld)",
+                        (long long)c->n_pursuers + c->n_evaders + c->n_poison);
+    } else {
+        if ((int64_t)c->n_pursuers + c->n_evaders + c->n_poison > 62)
+            return fail(MADRL_EINVAL, "at most 62 particles per env (one wavefront per env); crowd=1 runs up to 1023 on the multi-wavefront kernel");
+        if (2 * c->n_pursuers > 64) return fail(MADRL_EINVAL, "n_pursuers must be <= 32");
+    }
     if (c->n_sensors < 1 || c->n_sensors > 256) return fail(MADRL_EINVAL, "n_sensors must be in 1..256");
     if (c->n_coop < 1) return fail(MADRL_EINVAL, "n_coop must be >= 1");
     return MADRL_OK;
@@ -720,6 +688,8 @@ size_t ww_lds_bytes(const WwDev &d) {
     return align_up(b, 16);
 }
 
+size_t ww_lds_bytes_crowd(const WwDev &d) { return ww_crowd_lds_bytes(d.Np, d.Ne, d.Npo, d.K, d.rec_dw); }
+
 struct WwSpec {
     int Np, Ne, Npo, K, D;
     void (*launch)(const WwDev &, const WwIO &, int mode, bool fused, dim3 g, hipStream_t s);
@@ -749,6 +719,7 @@ const WwSpec WW_SPECS[] = {
 int ww_launch(const madrl_waterworld *h, const WwIO &io, int mode, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     const WwDev &d = h->dev;
+    if (h->cfg.crowd) return ww_crowd_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, stream);
     const dim3 g = particle_grid(h->max_blocks, d.n_envs), b(64);
     const bool fused = io.st != nullptr;
     const WwSpec *spec = nullptr;
@@ -811,7 +782,13 @@ int madrl_waterworld_create(const madrl_waterworld_config *cfg, const double *se
                             int32_t device, void *state_dev, madrl_waterworld **out) {
     int rc = ww_validate(cfg);
     if (rc) return rc;
-    return particle_create(cfg, sensors_host, n_envs, device, state_dev, out, ww_layout, ww_lds_bytes);
+    return particle_create(cfg, sensors_host, n_envs, device, state_dev, out, ww_layout, cfg->crowd ? ww_lds_bytes_crowd : ww_lds_bytes);
+}
+
+int madrl_waterworld_kernel_kind(madrl_waterworld *h, int32_t *out) {
+    if (!h || !out) return fail(MADRL_EINVAL, "kernel_kind: NULL argument");
+    *out = h->cfg.crowd ? 1 : 0;
+    return MADRL_OK;
 }
 
 void madrl_waterworld_destroy(madrl_waterworld *h) {
@@ -824,6 +801,8 @@ void madrl_waterworld_destroy(madrl_waterworld *h) {
 int madrl_waterworld_set_standardize(madrl_waterworld *h, const madrl_standardize_args *a) {
     if (!h) return fail(MADRL_EINVAL, "handle is NULL");
     if (!a) { h->std_bound = false; return MADRL_OK; }
+    if (h->cfg.crowd)
+        return fail(MADRL_EINVAL, "set_standardize: the crowd kernel has no fused StandardizedEnv; use the epilogue kernels (madrl_wrap_obsnorm / madrl_wrap_rewnorm)");
     if (a->struct_size != (int32_t)sizeof(madrl_standardize_args))
         return fail(MADRL_EINVAL, "madrl_standardize_args.struct_size=%d, library expects %d", a->struct_size, (int)sizeof(madrl_standardize_args));
     if (!a->obs_out || (a->enable_obsnorm && (!a->obs_mean || !a->obs_var)) || (a->rew_out && a->enable_rewnorm && (!a->rew_mean || !a->rew_var)))

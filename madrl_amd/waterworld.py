@@ -49,10 +49,16 @@ class BatchedMAWaterWorld(AbstractMAEnv):
                  sensor_range=0.2, action_scale=0.01, poison_reward=-1., food_reward=1., encounter_reward=.05,
                  control_penalty=-.5, reward_mech='local', addid=True, speed_features=True,
                  n_envs=1, device="cuda:0", seed=0, env_id_base=0, max_steps=0, auto_reset=False, max_blocks=0,
-                 **kwargs):
+                 crowd=False, **kwargs):
+        """crowd=True: the multi-wavefront kernel (csrc/waterworld_crowd.hip) -- up to 128 pursuers and 1 023 particles per env, any
+        sensor count; same results bit for bit on a shape both kernels take.  The default keeps the one-wavefront kernel and its limits
+        (62 particles, 32 pursuers)."""
         # like the reference, unknown kwargs are swallowed (waterworld.py:81,:483 passes obs_loc=None)
         self._ctor = dict(locals())
         self._ctor.pop("self"); self._ctor.pop("kwargs"); self._ctor.pop("__class__", None)
+        if not crowd:   # only a set flag travels: pickles of the envs that existed before it stay what they were
+            self._ctor.pop("crowd")
+        self._crowd = bool(crowd)
         self.n_pursuers, self.n_evaders, self.n_coop, self.n_poison = n_pursuers, n_evaders, n_coop, n_poison
         self.radius, self.obstacle_radius, self.obstacle_loc = radius, obstacle_radius, obstacle_loc
         self.ev_speed, self.poison_speed, self.n_sensors = ev_speed, poison_speed, n_sensors
@@ -74,7 +80,7 @@ class BatchedMAWaterWorld(AbstractMAEnv):
         c.n_sensors, c.addid, c.speed_features = self.n_sensors, int(bool(self._addid)), int(bool(self._speed_features))
         c.reward_global = int(self._reward_mech == "global")
         c.obstacle_fixed = int(self.obstacle_loc is not None)
-        c.max_steps, c.auto_reset = self.max_steps, int(self.auto_reset)
+        c.max_steps, c.auto_reset, c.crowd = self.max_steps, int(self.auto_reset), int(self._crowd)
         c.radius, c.obstacle_radius = float(self.radius), float(self.obstacle_radius)
         c.ev_speed, c.poison_speed = float(self.ev_speed), float(self.poison_speed)
         c.sensor_range, c.action_scale = float(self.sensor_range[0]), float(self.action_scale)
@@ -112,7 +118,7 @@ class BatchedMAWaterWorld(AbstractMAEnv):
         self._handle = h
         if self._max_blocks:
             _lib.check(L.madrl_waterworld_set_launch(h, self._max_blocks))
-        if N >= 4096:
+        if N >= 4096 and not self._crowd:   # (the crowd kernel takes its shape at run time: there is nothing to specialise)
             self._hint_fast_path(D)
         self._pursuers = [Archea(i + 1, D) for i in range(Np)]
         # A fused StandardizedEnv binding belongs to the handle that was just replaced (seed() and set_param_values() come
@@ -141,6 +147,18 @@ class BatchedMAWaterWorld(AbstractMAEnv):
         warnings.warn("MAWaterWorld with %d pursuers / %d evaders / %d poison / %d sensors (obs_dim %d) runs on the generic kernel; `python -m madrl_amd.build "
                       "--waterworld-shape %d %d %d %d %d` compiles the specialised kernel for this shape (results are identical, a step takes about half the "
                       "time)" % (shape + shape), stacklevel=3)
+
+    @property
+    def kernel_kind(self):
+        """"wave": one wavefront per env (waterworld_kernel); "crowd": one workgroup of several wavefronts per env (ww_crowd_kernel)"""
+        kind = C.c_int32()
+        _lib.check(_lib.lib().madrl_waterworld_kernel_kind(self._handle, C.byref(kind)))
+        return ("wave", "crowd")[kind.value]
+
+    @property
+    def fused_standardize(self):
+        """whether bind_standardize() works on this env (StandardizedEnv asks): the crowd kernel has no fused form"""
+        return not self._crowd
 
     def set_launch(self, max_blocks=0):
         self._max_blocks = int(max_blocks)
@@ -193,7 +211,11 @@ class BatchedMAWaterWorld(AbstractMAEnv):
                          tensors=None):
         """The kernels normalise observations / rewards on their way out (madrl_waterworld_set_standardize): reset() and
         step() then return the standardised tensors and the raw observation row is not stored.  Returns the dict of
-        state tensors (running statistics, outputs) the wrapper owns; `tensors` re-binds an existing dict (setup())."""
+        state tensors (running statistics, outputs) the wrapper owns; `tensors` re-binds an existing dict (setup()).
+        The crowd kernel has no fused form: StandardizedEnv runs its epilogue kernels over such an env."""
+        if self._crowd:
+            raise _lib.MadrlError("bind_standardize: the crowd kernel (crowd=True) has no fused StandardizedEnv; "
+                                  "StandardizedEnv(env) or StandardizedEnv(env, fused=False) runs the epilogue kernels over it")
         N, Np, D, dev = self.n_envs, self.n_pursuers, self.obs_dim, self.device
         self._std_kwargs = dict(scale_reward=scale_reward, enable_obsnorm=enable_obsnorm, enable_rewnorm=enable_rewnorm,
                                 obs_alpha=obs_alpha, rew_alpha=rew_alpha, eps=eps)

@@ -181,13 +181,14 @@ class StandardizedEnv(_Wrapper):
         self._fused_state = None
         self._obs_out = self._rew_out = None
         self._fused = False
-        if fused is not False and not self._single and hasattr(self._unwrapped, "bind_standardize"):
+        can_bind = hasattr(self._unwrapped, "bind_standardize") and getattr(self._unwrapped, "fused_standardize", True)   # (False: Waterworld on the crowd kernel)
+        if fused is not False and not self._single and can_bind:
             st = self._unwrapped.bind_standardize(scale_reward=scale_reward, enable_obsnorm=enable_obsnorm, enable_rewnorm=enable_rewnorm,
                                                   obs_alpha=obs_alpha, rew_alpha=rew_alpha, eps=eps)
             self._fused_state = st   # the env re-fills this same dict when a shape change makes it start new statistics
             self._fused = True
         elif fused:
-            raise ValueError("fused=True needs an env with bind_standardize() directly below this wrapper")
+            raise ValueError("fused=True needs an env with bind_standardize() directly below this wrapper (a Waterworld env on the crowd kernel has none)")
 
     def _stat(name):
         def get(self):

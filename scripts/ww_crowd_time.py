@@ -1,0 +1,135 @@
+"""Step time of the Waterworld crowd kernel (csrc/waterworld_crowd.hip, `crowd=True`) at shapes beyond one wavefront's worth of particles.
+
+    python scripts/ww_crowd_time.py                      # the table of DESIGN 4.4a: every row below, three processes each, min - max
+    python scripts/ww_crowd_time.py --rows shapes,cpu    # some of: shapes, cpu, wave, nw8
+
+Rows
+  shapes  20/60/40, 33/100/100 and 128/512/383 with 30 sensors, at 4 096 envs and at the largest batch whose observations fit 16 GB:
+          us per launch, env-steps/s, ray tests/s (n_pursuers * n_sensors * particles per env-step: what the oracle's sensing loop visits)
+  cpu     the float32 C oracle (oracle/waterworld_oracle.c, OpenMP) on this box's host cores at the same shapes: bench.py's cpu_baseline
+  wave    crowd kernel against the one-wavefront generic instantiation at 12/25/25 (16 sensors), 32 768 envs
+  nw8     eight instead of four wavefronts per workgroup on the first two shapes: needs the variant library
+          `SRC=waterworld_crowd MACRO=MADRL_WWC_NW scripts/variants.sh 8` builds (scripts/_variants/, git-ignored)
+
+Steady state with auto_reset (max_steps 500), after an untimed warm-up; device events around the launches alone.  One measurement per
+process (`--one ...`, what the parent starts), one process at a time.
+"""
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = {"20/60/40": (20, 60, 40, 30), "33/100/100": (33, 100, 100, 30), "128/512/383": (128, 512, 383, 30), "12/25/25": (12, 25, 25, 16)}
+NW8_LIB = os.path.join(ROOT, "scripts", "_variants", "libmadrl_hip.waterworld_crowd.8.so")
+OBS_BYTES = 16e9
+
+
+def obs_dim(K):
+    return 7 * K + 3
+
+
+def largest_batch(shape):
+    Np, _Ne, _Npo, K = SHAPES[shape]
+    return int(OBS_BYTES // (Np * obs_dim(K) * 4)) // 1024 * 1024
+
+
+def one(shape, N, crowd):
+    """one measurement in this process -> a JSON line"""
+    import torch
+    from madrl_amd import _lib
+    from madrl_amd.waterworld import BatchedMAWaterWorld
+    Np, Ne, Npo, K = SHAPES[shape]
+    dev = torch.device("cuda:0")
+    env = BatchedMAWaterWorld(Np, Ne, n_poison=Npo, n_sensors=K, n_envs=N, device=dev, seed=0, max_steps=500, auto_reset=True, crowd=bool(crowd))
+    acts = [torch.rand(N, Np, 2, device=dev) * 2 - 1 for _ in range(8)]
+    env.reset()
+    L = _lib.lib()
+    outs = [_lib.ptr(t) for t in (env._obs, env._rew, env._done, env._info)]
+
+    def run(k):
+        for i in range(k):
+            _lib.check(L.madrl_waterworld_step(env._handle, _lib.ptr(acts[i % 8]), None, *outs, _lib.current_stream(dev)))
+
+    def timed(k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); run(k); e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / k * 1e3
+
+    run(10); torch.cuda.synchronize()
+    us = timed(10)
+    steps = int(min(300, max(20, 1.0e6 / us)))   # about a second of launches
+    us = timed(steps)
+    print(json.dumps(dict(shape=shape, n_envs=N, kernel=env.kernel_kind, us_per_launch=us, env_steps_per_s=N / us * 1e6,
+                          ray_tests_per_s=N * Np * K * (Np + Ne + Npo) / us * 1e6, steps=steps)), flush=True)
+
+
+def cpu(shape):
+    import numpy as np
+    from oracle import waterworld as ww
+    Np, Ne, Npo, K = SHAPES[shape]
+    N = 64 if Np + Ne + Npo > 500 else 512
+    orc = ww.WaterworldOracle(Np, Ne, n_poison=Npo, n_sensors=K, n_envs=N, seed=0, max_steps=500, dtype=np.float32)
+    orc.reset()
+    act = np.random.RandomState(0).uniform(-1, 1, (N, Np, 2)).astype(np.float32)
+    orc.step(act)
+    t0, n = time.time(), 0
+    while time.time() - t0 < 3.0:
+        orc.step(act); n += 1
+    dt = time.time() - t0
+    return dict(shape=shape, n_envs=N, env_steps_per_s=N * n / dt, threads=int(os.environ.get("OMP_NUM_THREADS", 0)) or os.cpu_count())
+
+
+def child(shape, N, crowd, lib=None):
+    env = dict(os.environ)
+    if lib:
+        env["MADRL_HIP_LIB"] = lib
+    rs = []
+    for _ in range(3):
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", shape, str(N), str(int(crowd))], env=env, capture_output=True,
+                             text=True, timeout=600)
+        if out.returncode != 0:
+            raise SystemExit("measurement %s N=%d crowd=%d failed (%d):\n%s" % (shape, N, crowd, out.returncode, out.stderr[-2000:]))
+        rs.append(json.loads(out.stdout.strip().splitlines()[-1]))
+    us = [r["us_per_launch"] for r in rs]
+    lo, hi = min(us), max(us)
+    r = rs[0]
+    scale = lambda key, u: r[key] * r["us_per_launch"] / u
+    print("%-12s %-5s N=%8d  %10.1f - %10.1f us/launch  %.3e - %.3e env-steps/s  %.3e - %.3e ray tests/s%s" % (
+        shape, r["kernel"], N, lo, hi, scale("env_steps_per_s", hi), scale("env_steps_per_s", lo), scale("ray_tests_per_s", hi),
+        scale("ray_tests_per_s", lo), "  [%s]" % os.path.basename(lib) if lib else ""), flush=True)
+    return lo, hi
+
+
+def main():
+    argv = sys.argv[1:]
+    if argv[:1] == ["--one"]:
+        return one(argv[1], int(argv[2]), int(argv[3]))
+    rows = argv[argv.index("--rows") + 1].split(",") if "--rows" in argv else ["shapes", "cpu", "wave", "nw8"]
+    big = ("20/60/40", "33/100/100", "128/512/383")
+    if "shapes" in rows:
+        for s in big:
+            for N in (4096, largest_batch(s)):
+                child(s, N, True)
+    if "cpu" in rows:
+        for s in big:
+            r = cpu(s)
+            print("%-12s float32 C oracle, %d threads, N=%d: %.3e env-steps/s" % (s, r["threads"], r["n_envs"], r["env_steps_per_s"]), flush=True)
+    if "wave" in rows:
+        c = child("12/25/25", 32768, True)
+        w = child("12/25/25", 32768, False)
+        print("12/25/25 at 32 768 envs: crowd / one-wavefront generic = %.2f - %.2f" % (c[0] / w[1], c[1] / w[0]), flush=True)
+    if "nw8" in rows:
+        if not os.path.exists(NW8_LIB):
+            raise SystemExit("no %s: build it with SRC=waterworld_crowd MACRO=MADRL_WWC_NW scripts/variants.sh 8" % NW8_LIB)
+        for s in big[:2]:
+            for N in (4096, largest_batch(s)):
+                child(s, N, True)
+                child(s, N, True, lib=NW8_LIB)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,244 @@
+"""GPU tests (-m gpu) of the Waterworld crowd kernel (`crowd=True`: csrc/waterworld_crowd.hip, one workgroup of several wavefronts per env,
+particles looped over its threads), at shapes beyond one wavefront's worth of particles and at shapes both kernels take:
+(1) teacher-forced against the reference recordings, 1e-5, and equal to the float32 oracle; (2) free-running against the float32 oracle,
+identical in every bit; (3) against the one-wavefront kernel, identical in every bit; (4) the rest of the env's interface;
+(5) StandardizedEnv; (6) RolloutCollector."""
+import glob
+import os
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+TOL = 1e-5  # BASELINE.json north_star: "within 1e-5 for Waterworld ... float32 state"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FILES = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "wwcrowd_*.npz"))) + sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "waterworld_*.npz")))
+gid = lambda p: os.path.basename(p)[:-4]
+
+
+def _mk(n_envs, crowd=True, **kw):
+    from madrl_amd.waterworld import BatchedMAWaterWorld
+    return BatchedMAWaterWorld(n_envs=n_envs, device=DEV, crowd=crowd, **kw)
+
+
+def _bits(t):
+    t = t.contiguous()
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+@pytest.mark.parametrize("path", FILES, ids=gid)
+def test_crowd_matches_reference_golden_teacher_forced(path):
+    """Protocol and tolerance of test_waterworld_gpu.py::test_hip_matches_reference_golden_teacher_forced (all recorded steps of a file are
+    independent under teacher forcing: one batch), no step beyond 1e-5.  The float32 oracle is within it on every file too, and the kernel
+    equals that oracle in every bit."""
+    from oracle import waterworld as ww
+    g = np.load(path)
+    T = len(g["pre_t"])
+    kw = ww.kwargs_from_golden(g)
+    env = _mk(T, **kw)
+    assert env.kernel_kind == "crowd" and env.obs_dim == g["obs"].shape[-1]
+    orc = ww.WaterworldOracle(n_envs=T, dtype=np.float32, sensors=g["sensors"], **kw)
+    for e in (env, orc):
+        e.set_state(pos=g["pre_pos"], vel=g["pre_vel"], obst=g["obst"], t=g["pre_t"])
+    obs, rew, done, info = env.step(g["act"], respawn=g["resp"])
+    oobs, orew, odone, oinfo = orc.step(g["act"], resp=g["resp"])
+    st, ost = env.get_state(), orc.get_state()
+    obs, rew = obs.cpu().numpy(), rew.cpu().numpy()
+    pos, vel = st["pos"].cpu().numpy(), st["vel"].cpu().numpy()
+    beyond = []
+    worst = oworst = 0.0
+    for t in range(T):
+        errs = [np.abs(pos[t] - g["post_pos"][t]).max(), np.abs(vel[t] - g["post_vel"][t]).max(), np.abs(obs[t] - g["obs"][t]).max()]
+        oerrs = [np.abs(ost["pos"][t] - g["post_pos"][t]).max(), np.abs(ost["vel"][t] - g["post_vel"][t]).max(), np.abs(oobs[t] - g["obs"][t]).max()]
+        if not g["is_reset_step"][t]:
+            errs.append(np.abs(rew[t] - g["rew"][t]).max())
+            oerrs.append(np.abs(orew[t] - g["rew"][t]).max())
+            assert bool(done[t]) == bool(g["done"][t])
+            assert int(info["evcatches"][t]) == int(g["evc"][t]), "evcatches, step %d" % t
+            assert int(info["pocatches"][t]) == int(g["poc"][t]), "pocatches, step %d" % t
+        assert int(st["t"][t]) == int(g["post_t"][t])
+        worst, oworst = max(worst, max(errs)), max(oworst, max(oerrs))
+        if max(errs) > TOL:
+            beyond.append((t, max(errs)))
+    print("golden %s: worst error kernel %.3g, float32 oracle %.3g" % (gid(path), worst, oworst))
+    assert oworst <= TOL, "the float32 oracle itself is %.3g off the recording" % oworst
+    assert not beyond, "%d of %d steps beyond %.0e: %s" % (len(beyond), T, TOL, beyond[:5])
+    # the kernel IS the float32 oracle (rewards of the reset records are not outputs of reset(): compared where they are)
+    live = ~g["is_reset_step"].astype(bool)
+    assert np.array_equal(obs.view(np.int32), oobs.view(np.int32)), "observations differ from the float32 oracle"
+    assert np.array_equal(rew[live].view(np.int32), orew[live].view(np.int32)), "rewards differ from the float32 oracle"
+    assert np.array_equal(pos.view(np.int32), ost["pos"].view(np.int32)) and np.array_equal(vel.view(np.int32), ost["vel"].view(np.int32))
+
+
+BEYOND = {
+    # first shape beyond one wavefront
+    "63_particles": (dict(n_pursuers=13, n_evaders=25, n_poison=25, n_coop=3, n_sensors=16, radius=0.03, ev_speed=0.03, action_scale=0.03), 65, 40),
+    # first pursuer count beyond 32, random obstacle, global reward, odd K
+    "33_pursuers_global": (dict(n_pursuers=33, n_evaders=20, n_poison=12, n_coop=2, n_sensors=7, radius=0.03, ev_speed=0.03, action_scale=0.03,
+                                obstacle_loc=None, reward_mech="global"), 33, 40),
+    # every class one past a wavefront multiple
+    "one_past_multiples": (dict(n_pursuers=65, n_evaders=65, n_poison=129, n_coop=2, n_sensors=30, ev_speed=0.04, action_scale=0.03), 17, 30),
+    # exact multiples, no speed features, no id
+    "exact_multiples_nospeed": (dict(n_pursuers=64, n_evaders=64, n_poison=64, n_coop=1, n_sensors=12, speed_features=False, addid=False,
+                                     sensor_range=0.3, radius=0.02), 16, 30),
+    # the limits
+    "limits": (dict(n_pursuers=128, n_evaders=512, n_poison=383, n_coop=4, n_sensors=30, radius=0.02, ev_speed=0.03), 3, 12),
+    # rows too long to stage
+    "long_rows": (dict(n_pursuers=40, n_evaders=30, n_poison=20, n_coop=2, n_sensors=200, sensor_range=0.5), 3, 20),
+}
+
+
+@pytest.mark.parametrize("case", sorted(BEYOND))
+def test_crowd_matches_f32_oracle_free_running(case):
+    """as test_waterworld_gpu.py::_vs_f32_oracle(teacher_forced=False): nothing is ever copied across; resets, respawns and random obstacles
+    from Philox on both sides; every output and the state identical in every bit at every step"""
+    from oracle import waterworld as ww
+    kw, N, T = BEYOND[case]
+    H = max(5, T // 3)
+    env = _mk(N, seed=77, env_id_base=500, max_steps=H, auto_reset=True, **kw)
+    orc = ww.WaterworldOracle(n_envs=N, seed=77, env_id_base=500, max_steps=H, dtype=np.float32, **kw)
+    assert env.kernel_kind == "crowd"
+    obs = env.reset()
+    oobs = orc.reset()
+    assert np.array_equal(obs.cpu().numpy().view(np.int32), oobs.view(np.int32)), "reset observations"
+    rng = np.random.RandomState(1)
+    evc = poc = resets = 0
+    for t in range(T):
+        act = rng.uniform(-1, 1, size=(N, kw["n_pursuers"], 2)).astype(np.float32)
+        obs, rew, done, info = env.step(act)
+        oobs, orew, odone, oinfo = orc.step(act)
+        assert np.array_equal(done.cpu().numpy(), odone.astype(bool)), "done step %d" % t
+        assert np.array_equal(info["evcatches"].cpu().numpy(), oinfo[:, 0]), "evcatches step %d" % t
+        assert np.array_equal(info["pocatches"].cpu().numpy(), oinfo[:, 1]), "pocatches step %d" % t
+        assert np.array_equal(rew.cpu().numpy().view(np.int32), orew.view(np.int32)), "rewards step %d" % t
+        evc += int(oinfo[:, 0].sum()); poc += int(oinfo[:, 1].sum()); resets += int(odone.sum())
+        if odone.any():
+            orc.reset(mask=odone)
+        got = obs.cpu().numpy()
+        assert np.array_equal(got.view(np.int32), orc.obs.view(np.int32)), "obs step %d: %g" % (t, np.abs(got - orc.obs).max())
+        gst, ost = env.get_state(), orc.get_state()
+        assert np.array_equal(gst["pos"].cpu().numpy().view(np.int32), ost["pos"].view(np.int32)), "pos step %d" % t
+        assert np.array_equal(gst["vel"].cpu().numpy().view(np.int32), ost["vel"].view(np.int32)), "vel step %d" % t
+        assert np.array_equal(gst["obst"].cpu().numpy().view(np.int32), ost["obst"].view(np.int32)), "obst step %d" % t
+        assert np.array_equal(gst["t"].cpu().numpy(), ost["t"])
+        assert np.array_equal(gst["tick"].cpu().numpy().view(np.uint32), ost["tick"])
+    print("%s: %d evader catches, %d poison catches, %d time-limit resets" % (case, evc, poc, resets))
+    assert evc + poc > 0, "no catches"
+    assert resets > 0, "no time-limit reset"
+
+
+@pytest.mark.parametrize("kw,N", [(dict(n_pursuers=12, n_evaders=25, n_poison=25, n_coop=3, n_sensors=16, radius=0.03), 65),
+                                  (dict(n_pursuers=1, n_evaders=1, n_poison=1, n_coop=1, n_sensors=1), 1)], ids=["62_particles", "smallest"])
+def test_crowd_equals_the_one_wavefront_kernel(kw, N):
+    """a shape both kernels run: 40 free-running steps from the same seed, everything equal in every bit"""
+    a = _mk(N, crowd=True, seed=5, env_id_base=9, max_steps=15, auto_reset=True, **kw)
+    b = _mk(N, crowd=False, seed=5, env_id_base=9, max_steps=15, auto_reset=True, **kw)
+    assert (a.kernel_kind, b.kernel_kind) == ("crowd", "wave")
+    assert torch.equal(_bits(a.reset()), _bits(b.reset()))
+    g = torch.Generator(device="cpu").manual_seed(3)
+    for t in range(40):
+        act = (torch.rand((N, kw["n_pursuers"], 2), generator=g) * 2 - 1).to(DEV)
+        oa, ra, da, ia = a.step(act)
+        ob, rb, db, ib = b.step(act)
+        assert torch.equal(_bits(oa), _bits(ob)), "obs step %d" % t
+        assert torch.equal(_bits(ra), _bits(rb)) and torch.equal(da, db), "rewards / done step %d" % t
+        assert torch.equal(ia["evcatches"], ib["evcatches"]) and torch.equal(ia["pocatches"], ib["pocatches"]), "info step %d" % t
+        sa, sb = a.get_state(), b.get_state()
+        for k in sa:
+            assert torch.equal(_bits(sa[k]), _bits(sb[k])), "state %s step %d" % (k, t)
+
+
+def test_crowd_env_interface():
+    """mask reset, set_state / get_state round trip, step(obs_out=) into a second tensor, kernel_kind, the constructor arguments it pickles by"""
+    from madrl_amd import _lib
+    from oracle import waterworld as ww
+    kw, N, _T = BEYOND["63_particles"]
+    env = _mk(N, seed=3, max_steps=1000, **kw)
+    orc = ww.WaterworldOracle(n_envs=N, seed=3, max_steps=1000, dtype=np.float32, **kw)
+    assert env.kernel_kind == "crowd" and env._ctor["crowd"] is True
+    assert "crowd" not in _mk(2, crowd=False, n_pursuers=3, n_evaders=4)._ctor      # pickles of the envs that existed before stay what they were
+    assert pickle.loads(pickle.dumps(env)).kernel_kind == "crowd"
+    with pytest.raises(_lib.MadrlError, match="crowd"):
+        env.bind_standardize(enable_obsnorm=True)
+    assert np.array_equal(env.reset().cpu().numpy(), orc.reset())
+    rng = np.random.RandomState(0)
+    act = rng.uniform(-1, 1, (N, 13, 2)).astype(np.float32)
+    # step into a second tensor: the env's own buffer keeps what it held
+    own = env._obs.clone()
+    dst = torch.full((N * 13 * env.obs_dim,), 7.0, device=DEV)
+    obs, rew, done, info = env.step(act, obs_out=dst)
+    oobs, orew, _od, _oi = orc.step(act)
+    assert obs.data_ptr() == dst.data_ptr() and torch.equal(env._obs, own)
+    assert np.array_equal(obs.cpu().numpy(), oobs) and np.array_equal(rew.cpu().numpy(), orew)
+    # mask reset: the envs outside the mask keep state and observations
+    before, st0 = env.step(act)[0].clone(), env.get_state()
+    orc.step(act)
+    m = np.zeros(N, np.uint8); m[::3] = 1
+    got = env.reset(mask=m).cpu().numpy()
+    want = orc.reset(mask=m)
+    keep = m == 0
+    assert np.array_equal(got[m == 1], want[m == 1]) and np.array_equal(got[keep], before.cpu().numpy()[keep])
+    st1 = env.get_state()
+    assert torch.equal(st1["pos"][torch.as_tensor(keep)], st0["pos"][torch.as_tensor(keep)]) and (st1["t"].cpu().numpy()[m == 1] == 1).all()
+    ost = orc.get_state()
+    assert np.array_equal(st1["pos"].cpu().numpy(), ost["pos"]) and np.array_equal(st1["tick"].cpu().numpy().view(np.uint32), ost["tick"])
+    # set_state / get_state round trip through the record the crowd kernel reads
+    pos = rng.uniform(0, 1, (N, 63, 2)).astype(np.float32); vel = rng.uniform(-.01, .01, (N, 63, 2)).astype(np.float32)
+    obst = rng.uniform(0.3, 0.7, (N, 2)).astype(np.float32); t = rng.randint(0, 50, N).astype(np.int32); tick = rng.randint(0, 1000, N).astype(np.int32)
+    env.set_state(pos=pos, vel=vel, obst=obst, t=t, tick=tick)
+    orc.set_state(pos=pos, vel=vel, obst=obst, t=t, tick=tick.view(np.uint32))
+    st = env.get_state()
+    for k, v in (("pos", pos), ("vel", vel), ("obst", obst), ("t", t), ("tick", tick)):
+        assert np.array_equal(st[k].cpu().numpy(), v), k
+    obs, rew, done, info = env.step(act)
+    oobs, orew, _od, oinfo = orc.step(act)
+    assert np.array_equal(obs.cpu().numpy(), oobs) and np.array_equal(rew.cpu().numpy(), orew)
+    assert np.array_equal(env.get_state()["t"].cpu().numpy(), t + 1) and np.array_equal(info["evcatches"].cpu().numpy(), oinfo[:, 0])
+
+
+def test_standardized_env_over_a_crowd_env_takes_the_epilogue_kernels():
+    from madrl_amd.wrappers import StandardizedEnv
+    kw, N, _T = BEYOND["63_particles"]
+    mk = lambda: _mk(N, seed=9, max_steps=6, auto_reset=True, **kw)
+    cfg = dict(enable_obsnorm=True, enable_rewnorm=True)
+    auto, plain = StandardizedEnv(mk(), **cfg), StandardizedEnv(mk(), fused=False, **cfg)
+    assert not auto._fused and not plain._fused and auto.unwrapped._std is None
+    with pytest.raises(ValueError, match="fused=True"):
+        StandardizedEnv(mk(), fused=True, **cfg)
+    assert torch.equal(_bits(auto.reset()), _bits(plain.reset()))
+    g = torch.Generator(device="cpu").manual_seed(2)
+    for t in range(10):
+        a = (torch.rand((N, 13, 2), generator=g) * 2 - 1).to(DEV)
+        oa, ra, da, _ = auto.step(a)
+        op, rp, dp, _ = plain.step(a)
+        assert torch.equal(_bits(oa), _bits(op)) and torch.equal(_bits(ra), _bits(rp)) and torch.equal(da, dp), t
+    assert torch.isfinite(oa).all() and not torch.equal(oa, auto.unwrapped._obs)   # standardised, not the raw rows
+
+
+@pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
+def test_rollout_collector_over_a_crowd_env(graph):
+    """the step kernel writes the observation slots of the trajectory itself: they equal the observations of an eager loop"""
+    from madrl_amd.heuristics import WaterworldHeuristicPolicy
+    from madrl_amd.rollout import RolloutCollector
+    kw, N, _T = BEYOND["33_pursuers_global"]
+    H = 8
+    mk = lambda: _mk(N, seed=4, max_steps=5, auto_reset=True, **kw)
+    col = RolloutCollector(mk(), WaterworldHeuristicPolicy(), horizon=H, store_observations=True, graph=graph)
+    assert col._slots
+    env, pol = mk(), WaterworldHeuristicPolicy()
+    obs = env.reset()
+    for it in range(3):   # (graph: call 1 eager, call 2 captures and replays, call 3 replays)
+        traj = col.collect()
+        torch.cuda.synchronize()
+        for t in range(H):
+            assert torch.equal(_bits(traj.observations[t]), _bits(obs)), (it, t)
+            act = pol(obs)
+            act = act[0] if isinstance(act, tuple) else act
+            assert torch.equal(_bits(traj.actions[t]), _bits(act)), (it, t)
+            obs, rew, done, _info = env.step(act)
+            assert torch.equal(_bits(traj.rewards[t]), _bits(rew)) and torch.equal(traj.dones[t] != 0, done), (it, t)
+        assert torch.equal(_bits(traj.last_observation), _bits(obs)), it
+    assert int((traj.dones != 0).sum()) >= N   # max_steps=5: episodes ended and restarted inside the horizon
