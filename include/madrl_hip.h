@@ -335,11 +335,13 @@ int madrl_waterworld_set_state(madrl_waterworld *h, const float *pos, const floa
                                const int32_t *t, const uint32_t *tick, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * ContinuousHostageWorld (reference: madrl_environments/hostage.py).  One wavefront per env, float32.
+ * ContinuousHostageWorld (reference: madrl_environments/hostage.py).  One wavefront per env, or on request (crowd) one
+ * workgroup of several wavefronts per env; float32.
  * ---------------------------------------------------------------------------------------- */
 /* Constructor arguments of ContinuousHostageWorld.__init__ (hostage.py:76-81). */
 typedef struct madrl_hostage_config {
-    int32_t struct_size;     /* = sizeof(madrl_hostage_config) */
+    int32_t struct_size;     /* = sizeof(madrl_hostage_config); the size without the two trailing words (crowd, reserved0) is
+                                accepted too and means crowd = 0: what callers compiled before those words existed pass */
     int32_t n_good, n_hostages, n_bad, n_coop_save, n_coop_avoid, n_sensors;
     int32_t addid;
     int32_t reward_global;   /* reward_mech == 'global' (the reference's default here) */
@@ -351,6 +353,12 @@ typedef struct madrl_hostage_config {
     double key_loc[2];
     uint64_t seed;
     int64_t env_id_base;
+    int32_t crowd;           /* 0: one wavefront per env -- at most 61 particles, 32 rescuers, and the observation rows of an env must fit
+                                LDS.  1: hw_crowd_kernel, one workgroup of several wavefronts per env with the particles looped over its
+                                threads: n_good <= 128, n_hostages <= 64 (the saved mask is one 64-bit word), n_good + n_hostages + n_bad
+                                <= 1023, any n_sensors in 1..256; the same state record, and the same results bit for bit on a shape
+                                both take.  Anything else: MADRL_EINVAL.  (Appended at the end: the struct had no spare word.) */
+    int32_t reserved0;       /* 0 */
 } madrl_hostage_config;
 
 typedef struct madrl_hostage madrl_hostage; /* opaque */
@@ -365,6 +373,8 @@ int madrl_hostage_create(const madrl_hostage_config *cfg, const double *sensors_
                          void *state_dev, madrl_hostage **out);
 void madrl_hostage_destroy(madrl_hostage *h);
 int madrl_hostage_set_launch(madrl_hostage *h, int64_t max_blocks);
+/* which kernel the handle runs: 0 = one wavefront per env, 1 = the crowd kernel (cfg.crowd) */
+int madrl_hostage_kernel_kind(madrl_hostage *h, int32_t *out);
 /* ContinuousHostageWorld.reset (:137-177) incl. its trailing zero-action step; obs float32 [N][n_good][obs_dim] */
 int madrl_hostage_reset(madrl_hostage *h, const uint8_t *mask_dev, float *obs_dev, void *stream);
 /* ContinuousHostageWorld.step (:228-430).  actions float32 [N][n_good][2]; inj_respawn_dev float32 [N][n_bad][4] or NULL:

@@ -55,7 +55,7 @@ class HostageConfig(C.Structure):
         "key_fixed", "max_steps", "auto_reset")] + [(n, C.c_double) for n in (
             "radius", "bad_speed", "sensor_range", "action_scale", "save_reward", "hit_reward", "encounter_reward", "not_saved_reward",
             "bomb_reward", "bomb_radius", "key_radius", "control_penalty")] + [
-                ("key_loc", C.c_double * 2), ("seed", C.c_uint64), ("env_id_base", C.c_int64)]
+                ("key_loc", C.c_double * 2), ("seed", C.c_uint64), ("env_id_base", C.c_int64), ("crowd", C.c_int32), ("reserved0", C.c_int32)]
 
 
 class MultiWalkerConfig(C.Structure):
@@ -125,6 +125,7 @@ SIGNATURES = {
     "madrl_hostage_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp]),
     "madrl_hostage_destroy": (None, [_vp]),
     "madrl_hostage_set_launch": (C.c_int, [_vp, C.c_int64]),
+    "madrl_hostage_kernel_kind": (C.c_int, [_vp, _vp]),
     "madrl_hostage_reset": (C.c_int, [_vp] * 4),
     "madrl_hostage_step": (C.c_int, [_vp] * 8),
     "madrl_hostage_get_state": (C.c_int, [_vp] * 10),

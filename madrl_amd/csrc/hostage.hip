@@ -12,9 +12,10 @@
 //   catch rule ... _caught :184-198             step ....... :228-430
 // Quirks kept (G1..G9) are listed where they occur.  Arithmetic is float32, every expression keeps the statement order of the
 // reference's step() so that a float32 CPU restatement agrees bit for bit.
-#include "common.hpp"
+#include "hostage_dev.hpp"
 
 #include <math.h>
+#include <stddef.h>
 #include <string.h>
 
 // Profiling aid (scripts/variants.sh builds one library per value, never the shipped one):
@@ -31,33 +32,6 @@
 namespace {
 
 using namespace madrl;
-
-enum : uint32_t { HW_TAG_RESPAWN = 48, HW_TAG_RESET = 49 };
-
-struct HwDev {
-    int32_t Nr, Nh, Nc, NP, K, D;
-    int32_t n_coop_save, addid, reward_global, key_fixed, max_steps, auto_reset;
-    int32_t rec_dw;  // dwords per packed state record: pos[NP][2] vel[NP][2] key[2] bomb[2] saved_lo saved_hi flags t tick
-    uint32_t k0, k1, gid_base;
-    float radius, r_ho, bad_speed, sensor_range, action_scale, gate_lo;
-    float save_reward, hit_reward, encounter_reward, not_saved_reward, bomb_reward, bomb_radius, key_radius, control_penalty;
-    float key_x, key_y;
-    // sq_*: sq_threshold() (common.hpp) of the distance thresholds: rescuer-hostage / rescuer-criminal contact, bomb and key radii
-    float sq_hit_ho, sq_hit_cr, sq_bomb, sq_key;
-    int64_t n_envs;
-    const float *sensors;  // [K][2]
-    float *state;
-};
-
-struct HwIO {
-    const uint8_t *mask;    // reset mode
-    const float *actions;   // [N][Nr][2]
-    const float *inj_resp;  // [N][Nc][4] or NULL
-    float *obs;             // [N][Nr][D]
-    float *rew;             // [N][Nr]
-    uint8_t *done;          // [N]
-    int32_t *info;          // [N][2]  ho_saved, cr_encs
-};
 
 // Same register discipline as waterworld.hip (helpers in common.hpp): launch parameters are read from the kernel-argument segment
 // where a phase needs them (kernargs), per-lane global accesses go through an SGPR base + 32-bit VGPR offset (uniform_ptr), a lane
@@ -538,14 +512,32 @@ struct madrl_hostage {
 
 namespace {
 
-int hw_validate(const madrl_hostage_config *c) {
+// The configuration grew by `crowd` (and a reserved word) at its end: a caller compiled against the struct without them passes the old
+// struct_size and means crowd = 0.  -> *full: the whole struct, zero-extended, which everything after this function reads.
+constexpr int32_t HW_CONFIG_SIZE_V1 = (int32_t)offsetof(madrl_hostage_config, crowd);
+
+int hw_validate(const madrl_hostage_config *c, madrl_hostage_config *full) {
     if (!c) return fail(MADRL_EINVAL, "config is NULL");
-    if (c->struct_size != (int32_t)sizeof(madrl_hostage_config))
-        return fail(MADRL_EINVAL, "madrl_hostage_config.struct_size=%d, library expects %d", c->struct_size, (int)sizeof(madrl_hostage_config));
+    if (c->struct_size != (int32_t)sizeof(madrl_hostage_config) && c->struct_size != HW_CONFIG_SIZE_V1)
+        return fail(MADRL_EINVAL, "madrl_hostage_config.struct_size=%d, library expects %d (or %d: the struct without crowd)", c->struct_size,
+                    (int)sizeof(madrl_hostage_config), (int)HW_CONFIG_SIZE_V1);
+    memset(full, 0, sizeof(*full));
+    memcpy(full, c, (size_t)c->struct_size);
+    full->struct_size = (int32_t)sizeof(madrl_hostage_config);
+    c = full;
+    if (c->crowd != 0 && c->crowd != 1) return fail(MADRL_EINVAL, "madrl_hostage_config.crowd must be 0 or 1 (got %d)", c->crowd);
     if (c->n_good < 1 || c->n_hostages < 1 || c->n_bad < 1) return fail(MADRL_EINVAL, "n_good, n_hostages, n_bad must be >= 1");
-    // one wavefront per env; the packed record (4 * NP + 9 dwords) is prefetched as 4 dwords per lane
-    if (c->n_good + c->n_hostages + c->n_bad > 61) return fail(MADRL_EINVAL, "at most 61 particles per env (one wavefront per env)");
-    if (2 * c->n_good > 64) return fail(MADRL_EINVAL, "n_good must be <= 32");
+    if (c->crowd) {  // hw_crowd_kernel (hostage_crowd.hip): particles looped over the threads of a multi-wavefront workgroup
+        if (c->n_good > 128) return fail(MADRL_EINVAL, "crowd kernel: n_good must be <= 128 (got %d)", c->n_good);
+        if (c->n_hostages > 64) return fail(MADRL_EINVAL, "crowd kernel: n_hostages must be <= 64, the bits of the saved mask (got %d)", c->n_hostages);
+        if ((int64_t)c->n_good + c->n_hostages + c->n_bad > 1023)
+            return fail(MADRL_EINVAL, "crowd kernel: at most 1023 particles per env (got %lld)", (long long)c->n_good + c->n_hostages + c->n_bad);
+    } else {
+        // one wavefront per env; the packed record (4 * NP + 9 dwords) is prefetched as 4 dwords per lane
+        if ((int64_t)c->n_good + c->n_hostages + c->n_bad > 61)
+            return fail(MADRL_EINVAL, "at most 61 particles per env (one wavefront per env); crowd=1 runs up to 1023 on the multi-wavefront kernel");
+        if (2 * c->n_good > 64) return fail(MADRL_EINVAL, "n_good must be <= 32");
+    }
     if (c->n_sensors < 1 || c->n_sensors > 256) return fail(MADRL_EINVAL, "n_sensors must be in 1..256");
     if (c->n_coop_save < 1) return fail(MADRL_EINVAL, "n_coop_save must be >= 1");
     return MADRL_OK;
@@ -578,9 +570,12 @@ size_t hw_lds_bytes(const HwDev &d) {
     return align_up(b, 16);
 }
 
+size_t hw_lds_bytes_crowd(const HwDev &d) { return hw_crowd_lds_bytes(d.Nr, d.Nh, d.Nc, d.K, d.rec_dw); }
+
 int hw_launch(const madrl_hostage *h, const HwIO &io, int mode, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     const HwDev &d = h->dev;
+    if (h->cfg.crowd) return hw_crowd_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, stream);
     const dim3 g = particle_grid(h->max_blocks, d.n_envs);
     const bool ex = d.Nr == 3 && d.Nh == 10 && d.Nc == 5 && d.K == 30 && d.D == 156;  // the module's own configuration (hostage.py:483), 30 sensors, agent id
     if (mode == 0) {
@@ -623,28 +618,37 @@ __global__ void hw_state_copy_kernel(const HwDev d, float *pos, float *vel, floa
 extern "C" {
 
 int madrl_hostage_obs_dim(const madrl_hostage_config *cfg, int32_t *out_dim) {
-    int rc = hw_validate(cfg);
+    madrl_hostage_config full;
+    int rc = hw_validate(cfg, &full);
     if (rc) return rc;
     if (!out_dim) return fail(MADRL_EINVAL, "out_dim is NULL");
-    *out_dim = hw_obs_dim_of(cfg);
+    *out_dim = hw_obs_dim_of(&full);
     return MADRL_OK;
 }
 
 int madrl_hostage_state_bytes(const madrl_hostage_config *cfg, int64_t n_envs, uint64_t *out_bytes) {
-    int rc = hw_validate(cfg);
+    madrl_hostage_config full;
+    int rc = hw_validate(cfg, &full);
     if (rc) return rc;
     if (n_envs < 1 || !out_bytes) return fail(MADRL_EINVAL, "n_envs must be >= 1 and out_bytes non-NULL");
     HwDev d;
-    hw_layout(cfg, &d);
+    hw_layout(&full, &d);  // (the record does not depend on the kernel)
     *out_bytes = (uint64_t)d.rec_dw * 4u * (uint64_t)n_envs;
     return MADRL_OK;
 }
 
 int madrl_hostage_create(const madrl_hostage_config *cfg, const double *sensors_host, int64_t n_envs, int32_t device, void *state_dev,
                          madrl_hostage **out) {
-    int rc = hw_validate(cfg);
+    madrl_hostage_config full;
+    int rc = hw_validate(cfg, &full);
     if (rc) return rc;
-    return particle_create(cfg, sensors_host, n_envs, device, state_dev, out, hw_layout, hw_lds_bytes);
+    return particle_create(&full, sensors_host, n_envs, device, state_dev, out, hw_layout, full.crowd ? hw_lds_bytes_crowd : hw_lds_bytes);
+}
+
+int madrl_hostage_kernel_kind(madrl_hostage *h, int32_t *out) {
+    if (!h || !out) return fail(MADRL_EINVAL, "kernel_kind: NULL argument");
+    *out = h->cfg.crowd ? 1 : 0;
+    return MADRL_OK;
 }
 
 void madrl_hostage_destroy(madrl_hostage *h) {

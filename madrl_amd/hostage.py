@@ -6,6 +6,7 @@
   `timestep_limit`, `reset()`, `step()`, `seed()`, `is_terminal`, `is_gate_open`; tensors:
       reset()       -> obs float32 [N, n_good, D]          D = 5K + 6  (K sensors)
       step(action)  -> obs, rew float32 [N, n_good], done bool [N], {'ho_saved','cr_encs': int32 [N]}
+  `crowd=True` runs envs beyond one wavefront's worth of particles (more than 61 particles or 32 rescuers) on the multi-wavefront kernel.
 * `ContinuousHostageWorld(...)`: N == 1 drop-in with the reference's return types.
 
 Arithmetic is float32 in the HIP kernel (reference: float64; tolerance 1e-5, tests/)."""
@@ -43,9 +44,15 @@ class BatchedContinuousHostageWorld(AbstractMAEnv):
     def __init__(self, n_good, n_hostages, n_bad, n_coop_save, n_coop_avoid, radius=0.015, key_loc=None, bad_speed=0.01, n_sensors=30,
                  sensor_range=0.2, action_scale=0.01, save_reward=5., hit_reward=-1., encounter_reward=0.01, not_saved_reward=-3,
                  bomb_reward=-5., bomb_radius=0.05, key_radius=0.0075, control_penalty=-.1, reward_mech='global', addid=True,
-                 n_envs=1, device="cuda:0", seed=0, env_id_base=0, max_steps=0, auto_reset=False, max_blocks=0, **kwargs):
+                 n_envs=1, device="cuda:0", seed=0, env_id_base=0, max_steps=0, auto_reset=False, max_blocks=0, crowd=False, **kwargs):
+        """crowd=True: the multi-wavefront kernel (csrc/hostage_crowd.hip) -- up to 128 rescuers, 64 hostages and 1 023 particles per env,
+        any sensor count up to 256; the same results bit for bit on a shape both kernels take.  Without it an env holds at most 61 particles
+        and 32 rescuers."""
         self._ctor = dict(locals())
         self._ctor.pop("self"); self._ctor.pop("kwargs"); self._ctor.pop("__class__", None)
+        if not crowd:   # only a set flag travels: pickles of the envs that existed before it stay what they were
+            self._ctor.pop("crowd")
+        self._crowd = bool(crowd)
         self.n_good, self.n_hostages, self.n_bad = n_good, n_hostages, n_bad
         self.n_coop_save, self.n_coop_avoid, self.radius, self.key_loc = n_coop_save, n_coop_avoid, radius, key_loc
         self.key_radius, self.bad_speed, self.n_sensors = key_radius, bad_speed, n_sensors
@@ -77,6 +84,7 @@ class BatchedContinuousHostageWorld(AbstractMAEnv):
             k = np.asarray(self.key_loc, np.float64).reshape(2)
             c.key_loc[0], c.key_loc[1] = float(k[0]), float(k[1])
         c.seed, c.env_id_base = self._seed_value, self.env_id_base
+        c.crowd = int(self._crowd)
         return c
 
     def setup(self):
@@ -110,6 +118,13 @@ class BatchedContinuousHostageWorld(AbstractMAEnv):
     def set_launch(self, max_blocks=0):
         self._max_blocks = int(max_blocks)
         _lib.check(_lib.lib().madrl_hostage_set_launch(self._handle, self._max_blocks))
+
+    @property
+    def kernel_kind(self):
+        """"wave": one wavefront per env (hostage_kernel); "crowd": one workgroup of several wavefronts per env (hw_crowd_kernel)"""
+        kind = C.c_int32()
+        _lib.check(_lib.lib().madrl_hostage_kernel_kind(self._handle, C.byref(kind)))
+        return ("wave", "crowd")[kind.value]
 
     def _destroy(self):
         if getattr(self, "_handle", None):
@@ -188,6 +203,8 @@ class BatchedContinuousHostageWorld(AbstractMAEnv):
     def is_terminal(self):
         s = self.get_state()
         allm = (1 << self.n_hostages) - 1
+        if self.n_hostages >= 64:
+            allm = -1   # the 64 bits of the mask as the int64 the state holds them in: the top one is the sign
         return ((s["flags"] & 2) != 0) | ((s["saved"] & allm) == allm) | (s["t"] >= self.timestep_limit)  # :179-182
 
     def _shapes(self):
