@@ -375,6 +375,13 @@ void madrl_hostage_destroy(madrl_hostage *h);
 int madrl_hostage_set_launch(madrl_hostage *h, int64_t max_blocks);
 /* which kernel the handle runs: 0 = one wavefront per env, 1 = the crowd kernel (cfg.crowd) */
 int madrl_hostage_kernel_kind(madrl_hostage *h, int32_t *out);
+/* Fused StandardizedEnv, as madrl_waterworld_set_standardize above (same madrl_standardize_args, A = n_good): the step / reset
+ * kernels of the one-wavefront handle standardise the observation row as it leaves LDS and write the scaled / normalised rewards
+ * themselves, bit for bit what madrl_wrap_obsnorm / madrl_wrap_rewnorm compute from the raw outputs.  reset(mask) leaves the
+ * statistics and the obs_out rows of the envs outside the mask alone.  While bound, obs_dev of reset / step may be NULL (the raw
+ * row is then not stored).  args NULL unbinds.  A crowd handle (cfg.crowd = 1) has no fused form: MADRL_EINVAL, the epilogue
+ * kernels serve it. */
+int madrl_hostage_set_standardize(madrl_hostage *h, const madrl_standardize_args *args);
 /* ContinuousHostageWorld.reset (:137-177) incl. its trailing zero-action step; obs float32 [N][n_good][obs_dim] */
 int madrl_hostage_reset(madrl_hostage *h, const uint8_t *mask_dev, float *obs_dev, void *stream);
 /* ContinuousHostageWorld.step (:228-430).  actions float32 [N][n_good][2]; inj_respawn_dev float32 [N][n_bad][4] or NULL:

@@ -126,6 +126,7 @@ SIGNATURES = {
     "madrl_hostage_destroy": (None, [_vp]),
     "madrl_hostage_set_launch": (C.c_int, [_vp, C.c_int64]),
     "madrl_hostage_kernel_kind": (C.c_int, [_vp, _vp]),
+    "madrl_hostage_set_standardize": (C.c_int, [_vp, _vp]),
     "madrl_hostage_reset": (C.c_int, [_vp] * 4),
     "madrl_hostage_step": (C.c_int, [_vp] * 8),
     "madrl_hostage_get_state": (C.c_int, [_vp] * 10),

@@ -28,6 +28,14 @@
                            // 60 B per lane and the spill stores reached HBM).  With the launch parameters out of the SGPR file
                            // and the static LDS layout: 72 VGPRs, no scratch at 7 waves.  32 768 envs: 4 waves 55.2 us, 5 50.7, 6 48.0, 7 46.9.
 #endif
+// The fused-wrapper variants of the specialised kernel hold a batch of float64 statistics: fewer resident wavefronts, the most at which
+// they have no scratch.  Step: 5 (at 6 it spills 4 VGPRs, 20 B of scratch per lane).  Reset: 6.
+#ifndef MADRL_HW_FUSED_STEP_WAVES
+#define MADRL_HW_FUSED_STEP_WAVES 5
+#endif
+#ifndef MADRL_HW_FUSED_RESET_WAVES
+#define MADRL_HW_FUSED_RESET_WAVES 6
+#endif
 
 namespace {
 
@@ -45,8 +53,11 @@ __device__ __forceinline__ float bcast(float v, int src_lane) { return __int_as_
 
 // MODE 0: reset(mask)   MODE 1: step (+ fused auto-reset)
 // TNr..TK > 0: the particle / sensor counts are compile-time constants (small loops unroll, the index divisions fold); 0: generic.
-template <int MODE, int TNr, int TNh, int TNc, int TK, int TD = 0>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TNr > 0 ? MADRL_HW_WAVES : 1, TNr > 0 ? MADRL_HW_WAVES : 8))) void hostage_kernel(const HwDev d, const HwIO io) {
+// FUSED: the StandardizedEnv epilogue (HwStd) is compiled in; a template parameter and not a run-time branch because its float64 code
+// would otherwise cost the plain kernel registers, i.e. resident wavefronts (measured on Waterworld: 96 instead of 78 us per step)
+#define MADRL_HW_OCC_N (TNr > 0 ? (FUSED ? (MODE == 1 ? MADRL_HW_FUSED_STEP_WAVES : MADRL_HW_FUSED_RESET_WAVES) : MADRL_HW_WAVES) : 0)
+template <int MODE, int TNr, int TNh, int TNc, int TK, int TD = 0, bool FUSED = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC_N > 0 ? MADRL_HW_OCC_N : 1, MADRL_HW_OCC_N > 0 ? MADRL_HW_OCC_N : 8))) void hostage_kernel(const HwDev d, const HwIO io) {
     // specialised shape: compile-time LDS layout in a static array, launched with 0 dynamic bytes (see waterworld.hip)
     constexpr int SPEC_DW = TNr > 0 ? ((4 * (TNr + TNh + TNc) + 9 + 3) / 4 * 4 + ((TNr + 1) * (TD > 0 ? TD : 1) + 3) / 4 * 4 + (2 * TK + 3) / 4 * 4) : 0;   // (TNr + 1: the spare row of the sensing phase)
     constexpr int SPEC_BYTES = TNr > 0 ? (SPEC_DW * 4 + 8 * TNr + TNr * (TNh + TNc) + 2 * TNh + TNc + 15) / 16 * 16 : 16;
@@ -450,6 +461,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TNr > 0 ? MA
 #endif
                 if (MODE == 1 && !do_init) {
                     if (fresh(lane) < Nr) uniform_ptr(IOA.rew + env * Nr)[ulane] = reward;
+                    if constexpr (FUSED) {  // StandardizedEnv.step :283-291, the operations of wrappers.hip rewnorm_kernel in its order
+                        if (IOA.st->rew_out != nullptr && fresh(lane) < Nr) {
+                            const HwStd &st = *IOA.st;
+                            const int64_t i = env * Nr + lane;
+                            double r = (double)reward;
+                            if (st.enable_rewnorm) {
+                                const double m = (1.0 - st.rew_alpha) * st.rew_mean[i] + st.rew_alpha * r;         // :253-254
+                                const double dd = r - m;
+                                const double v = (1.0 - st.rew_alpha) * st.rew_var[i] + st.rew_alpha * (dd * dd);  // :255-257
+                                st.rew_mean[i] = m;
+                                st.rew_var[i] = v;
+                                r = r / (sqrt(v) + st.eps);                                                      // :268-271
+                            }
+                            st.rew_out[i] = (float)(st.scale * r);                                              // :290
+                        }
+                    }
                     if (fresh(lane) == 0) {
                         IOA.done[env] = (uint8_t)is_done;
                         IOA.info[2 * env] = n_ho_caught;
@@ -460,6 +487,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TNr > 0 ? MA
                         do_init = true;
                     }
                 }
+                if constexpr (!FUSED) {
                 if (pass == npass - 1) {
                     const auto orow = uniform_ptr(IOA.obs + env * (int64_t)(Nr * D));
 #if MADRL_HW_ABLATE & 1
@@ -470,6 +498,51 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TNr > 0 ? MA
 #else
                     for (uint32_t e = ulane; e < (uint32_t)(Nr * D); e += 64u) orow[e] = O[e];
 #endif
+                }
+                } else if (pass == npass - 1) {  // StandardizedEnv.standardize_obs :242-263; after a fused auto-reset this is the new episode's first row, standardised once
+                    const int n_el = Nr * D;
+                    const int64_t base = env * (int64_t)n_el;
+                    float *const obs_p = IOA.obs;
+                    if (obs_p != nullptr) {  // the raw row may be dropped when the wrapper's output is all the caller reads
+                        const auto orow = uniform_ptr(obs_p + base);
+                        for (uint32_t e = ulane; e < (uint32_t)n_el; e += 64u) orow[e] = O[e];
+                    }
+                    // by value: through a reference into global memory every float64 store of the loop could have changed alpha, eps and the
+                    // pointers (type-based aliasing), and the compiler would load them again behind each one
+                    const HwStd st = *IOA.st;
+                    if (st.enable_obsnorm) {
+                        // batches of 4 elements per lane: all 8 statistics loads of a batch are in flight before the first dependent float64
+                        // operation (waterworld.hip: element by element 421, batched 357 us per wrapped step).  The operations of wrappers.hip
+                        // obsnorm_kernel / obsnorm_one in their order; every statistics byte is touched once per step: non-temporal.
+                        double *__restrict__ gm = st.obs_mean + base;
+                        double *__restrict__ gv = st.obs_var + base;
+                        float *__restrict__ go = st.obs_out + base;
+                        const double alpha = st.obs_alpha, eps = st.eps;
+                        for (int e0 = lane; e0 < n_el; e0 += 256) {
+                            double m[4], v[4];
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const int e = e0 + 64 * u;
+                                m[u] = e < n_el ? __builtin_nontemporal_load(&gm[e]) : 0.0;
+                                v[u] = e < n_el ? __builtin_nontemporal_load(&gv[e]) : 1.0;
+                            }
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const int e = e0 + 64 * u;
+                                if (e < n_el) {
+                                    const double x = (double)O[e];
+                                    const double mm = (1.0 - alpha) * m[u] + alpha * x;          // :245-246
+                                    const double dd = x - mm;
+                                    const double vv = (1.0 - alpha) * v[u] + alpha * (dd * dd);  // :247-249
+                                    __builtin_nontemporal_store(mm, &gm[e]);
+                                    __builtin_nontemporal_store(vv, &gv[e]);
+                                    __builtin_nontemporal_store((float)((x - mm) / (sqrt(vv) + eps)), &go[e]);  // :262-263
+                                }
+                            }
+                        }
+                    } else {
+                        for (int e = lane; e < n_el; e += 64) st.obs_out[base + e] = O[e];
+                    }
                 }
                 wave_sync();
             }
@@ -497,6 +570,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TNr > 0 ? MA
 }
 #undef DA
 #undef IOA
+#undef MADRL_HW_OCC_N
 
 }  // namespace
 
@@ -508,6 +582,8 @@ struct madrl_hostage {
     int64_t max_blocks;
     size_t lds_bytes;
     void *tables;
+    HwStd *std_dev;   // device copy of the bound StandardizedEnv arguments (madrl_hostage_set_standardize)
+    bool std_bound;
 };
 
 namespace {
@@ -578,7 +654,15 @@ int hw_launch(const madrl_hostage *h, const HwIO &io, int mode, void *stream) {
     if (h->cfg.crowd) return hw_crowd_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, stream);
     const dim3 g = particle_grid(h->max_blocks, d.n_envs);
     const bool ex = d.Nr == 3 && d.Nh == 10 && d.Nc == 5 && d.K == 30 && d.D == 156;  // the module's own configuration (hostage.py:483), 30 sensors, agent id
-    if (mode == 0) {
+    if (io.st != nullptr) {  // a bound StandardizedEnv: the instantiations with its epilogue
+        if (mode == 0) {
+            if (ex) hipLaunchKernelGGL((hostage_kernel<0, 3, 10, 5, 30, 156, true>), g, dim3(64), 0, s, h->dev, io);
+            else hipLaunchKernelGGL((hostage_kernel<0, 0, 0, 0, 0, 0, true>), g, dim3(64), h->lds_bytes, s, h->dev, io);
+        } else {
+            if (ex) hipLaunchKernelGGL((hostage_kernel<1, 3, 10, 5, 30, 156, true>), g, dim3(64), 0, s, h->dev, io);
+            else hipLaunchKernelGGL((hostage_kernel<1, 0, 0, 0, 0, 0, true>), g, dim3(64), h->lds_bytes, s, h->dev, io);
+        }
+    } else if (mode == 0) {
         if (ex) hipLaunchKernelGGL((hostage_kernel<0, 3, 10, 5, 30, 156>), g, dim3(64), 0, s, h->dev, io);
         else hipLaunchKernelGGL((hostage_kernel<0, 0, 0, 0, 0>), g, dim3(64), h->lds_bytes, s, h->dev, io);
     } else {
@@ -654,7 +738,29 @@ int madrl_hostage_kernel_kind(madrl_hostage *h, int32_t *out) {
 void madrl_hostage_destroy(madrl_hostage *h) {
     if (!h) return;
     if (h->tables) (void)hipFree(h->tables);
+    if (h->std_dev) (void)hipFree(h->std_dev);
     delete h;
+}
+
+int madrl_hostage_set_standardize(madrl_hostage *h, const madrl_standardize_args *a) {
+    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
+    if (!a) { h->std_bound = false; return MADRL_OK; }
+    if (h->cfg.crowd)
+        return fail(MADRL_EINVAL, "set_standardize: the crowd kernel has no fused StandardizedEnv; use the epilogue kernels (madrl_wrap_obsnorm / madrl_wrap_rewnorm)");
+    if (a->struct_size != (int32_t)sizeof(madrl_standardize_args))
+        return fail(MADRL_EINVAL, "madrl_standardize_args.struct_size=%d, library expects %d", a->struct_size, (int)sizeof(madrl_standardize_args));
+    if (!a->obs_out || (a->enable_obsnorm && (!a->obs_mean || !a->obs_var)) || (a->rew_out && a->enable_rewnorm && (!a->rew_mean || !a->rew_var)))
+        return fail(MADRL_EINVAL, "set_standardize: obs_out and the running statistics of every enabled normalisation are required");
+    HwStd st;
+    st.obs_mean = a->obs_mean; st.obs_var = a->obs_var; st.obs_out = a->obs_out;
+    st.rew_mean = a->rew_mean; st.rew_var = a->rew_var; st.rew_out = a->rew_out;
+    st.obs_alpha = a->obs_alpha; st.rew_alpha = a->rew_alpha; st.eps = a->eps; st.scale = a->scale_reward;
+    st.enable_obsnorm = a->enable_obsnorm; st.enable_rewnorm = a->enable_rewnorm;
+    MADRL_HIP_TRY(hipSetDevice(h->device));
+    if (!h->std_dev) MADRL_HIP_TRY(hipMalloc((void **)&h->std_dev, sizeof(HwStd)));
+    MADRL_HIP_TRY(hipMemcpy(h->std_dev, &st, sizeof(HwStd), hipMemcpyHostToDevice));
+    h->std_bound = true;
+    return MADRL_OK;
 }
 
 int madrl_hostage_set_launch(madrl_hostage *h, int64_t max_blocks) {
@@ -664,22 +770,24 @@ int madrl_hostage_set_launch(madrl_hostage *h, int64_t max_blocks) {
 }
 
 int madrl_hostage_reset(madrl_hostage *h, const uint8_t *mask_dev, float *obs_dev, void *stream) {
-    if (!h || !obs_dev) return fail(MADRL_EINVAL, "reset: handle/obs is NULL");
+    if (!h || (!obs_dev && !h->std_bound)) return fail(MADRL_EINVAL, "reset: handle/obs is NULL");
     HwIO io;
     memset(&io, 0, sizeof(io));
     io.mask = mask_dev;
     io.obs = obs_dev;
+    io.st = h->std_bound ? h->std_dev : nullptr;
     return hw_launch(h, io, 0, stream);
 }
 
 int madrl_hostage_step(madrl_hostage *h, const float *actions_dev, const float *inj_respawn_dev, float *obs_dev, float *rew_dev,
                        uint8_t *done_dev, int32_t *info_dev, void *stream) {
-    if (!h || !actions_dev || !obs_dev || !rew_dev || !done_dev || !info_dev) return fail(MADRL_EINVAL, "step: NULL argument");
+    if (!h || !actions_dev || (!obs_dev && !h->std_bound) || !rew_dev || !done_dev || !info_dev) return fail(MADRL_EINVAL, "step: NULL argument");
     HwIO io;
     memset(&io, 0, sizeof(io));
     io.actions = actions_dev;
     io.inj_resp = inj_respawn_dev;
     io.obs = obs_dev;
+    io.st = h->std_bound ? h->std_dev : nullptr;
     io.rew = rew_dev;
     io.done = done_dev;
     io.info = info_dev;

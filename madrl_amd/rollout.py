@@ -62,7 +62,7 @@ class RolloutCollector(object):
         `obs_out=` of the Waterworld, hostage and MultiWalker steps): the step kernel of step t writes slot t + 1 of a [T + 1]-slot
         observation tensor itself -- observations = slots 0 .. T-1, last_observation = slot T -- and the only observation-sized copy of a
         horizon is the one that brings the previous horizon's last observation to slot 0.  Other envs (wrappers such as ObservationBuffer
-        or StandardizedEnv, a Waterworld with a fused StandardizedEnv bound) keep the copy per step.  obs_slots: None = as described,
+        or StandardizedEnv, a Waterworld or hostage world with a fused StandardizedEnv bound) keep the copy per step.  obs_slots: None = as described,
         False = the copy per step for every env.
         graph=True: from the second collect() on, the whole horizon (policy launches, step kernels, buffer copies, the
         return scan) is one captured hipGraph that is replayed -- for small batches the per-launch overhead of ~4 launches

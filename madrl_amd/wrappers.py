@@ -171,9 +171,12 @@ class StandardizedEnv(_Wrapper):
 
     def __init__(self, env, scale_reward=1., enable_obsnorm=False, enable_rewnorm=False, obs_alpha=0.001, rew_alpha=0.001,
                  eps=1e-8, fused=None):
-        """fused: None = fuse into the env's step / reset kernels when the env directly below supports it
-        (`bind_standardize`, today the Waterworld engine): the observation row is normalised as it leaves LDS instead of
-        being stored raw and read back by an epilogue launch.  False = always the stand-alone epilogue kernels."""
+        """fused: None = fuse into the env's step / reset kernels when the env directly below supports it (`bind_standardize`) and its
+        fused form is the faster one for this configuration (`fused_standardize_pays`: the Waterworld engine always, the hostage-world
+        engine with enable_obsnorm -- without it its fused step measured slower than step + reward launch): the
+        observation row is normalised as it leaves LDS instead of being stored raw and read back by an epilogue launch.  False = always
+        the stand-alone epilogue kernels.  True = fuse or raise.  The results are bit-identical either way, and either way
+        reset(mask=...) standardises the rows of the envs in the mask alone: the others keep their statistics and their rows."""
         super().__init__(env)
         self._scale_reward, self._enable_obsnorm, self._enable_rewnorm = scale_reward, enable_obsnorm, enable_rewnorm
         self._obs_alpha, self._rew_alpha, self._eps = obs_alpha, rew_alpha, eps
@@ -181,14 +184,18 @@ class StandardizedEnv(_Wrapper):
         self._fused_state = None
         self._obs_out = self._rew_out = None
         self._fused = False
-        can_bind = hasattr(self._unwrapped, "bind_standardize") and getattr(self._unwrapped, "fused_standardize", True)   # (False: Waterworld on the crowd kernel)
-        if fused is not False and not self._single and can_bind:
+        can_bind = hasattr(self._unwrapped, "bind_standardize") and getattr(self._unwrapped, "fused_standardize", True)   # (False: Waterworld / the hostage world on their crowd kernels)
+        # (an env may say for which configurations its fused form is the faster one: fused_standardize_pays; elsewhere fused=True only)
+        pays = getattr(self._unwrapped, "fused_standardize_pays", None)
+        auto = bool(pays(enable_obsnorm=enable_obsnorm, enable_rewnorm=enable_rewnorm)) if callable(pays) else True
+        want = bool(fused) or (fused is None and auto)
+        if want and not self._single and can_bind:
             st = self._unwrapped.bind_standardize(scale_reward=scale_reward, enable_obsnorm=enable_obsnorm, enable_rewnorm=enable_rewnorm,
                                                   obs_alpha=obs_alpha, rew_alpha=rew_alpha, eps=eps)
             self._fused_state = st   # the env re-fills this same dict when a shape change makes it start new statistics
             self._fused = True
         elif fused:
-            raise ValueError("fused=True needs an env with bind_standardize() directly below this wrapper (a Waterworld env on the crowd kernel has none)")
+            raise ValueError("fused=True needs an env with bind_standardize() directly below this wrapper (a Waterworld or hostage-world env on the crowd kernel has none)")
 
     def _stat(name):
         def get(self):
@@ -200,17 +207,18 @@ class StandardizedEnv(_Wrapper):
     _obs_mean, _obs_var, _rew_mean, _rew_var = _stat("obs_mean"), _stat("obs_var"), _stat("rew_mean"), _stat("rew_var")
     del _stat
 
-    def _norm_obs(self, obs):
+    def _norm_obs(self, obs, mask=None):
+        """mask (uint8 [N], a partial reset): the envs outside it keep their statistics and their standardised rows, as under the fused form"""
         if not self._enable_obsnorm:
             return obs
         obs = obs.contiguous()
         if self._obs_mean is None:  # :229-230
             self._obs_mean = torch.zeros(obs.shape, dtype=torch.float64, device=obs.device)
             self._obs_var = torch.ones(obs.shape, dtype=torch.float64, device=obs.device)
-            self._obs_out = torch.empty_like(obs)
+            self._obs_out = torch.zeros_like(obs)
         n = obs.numel()
         _lib.check(_lib.lib().madrl_wrap_obsnorm(_lib.ptr(obs), _lib.ptr(self._obs_mean), _lib.ptr(self._obs_var), _lib.ptr(self._obs_out),
-                                                 n, n // self.n_envs, None, float(self._obs_alpha), float(self._eps), _stream(self)))
+                                                 n, n // self.n_envs, _lib.ptr(mask), float(self._obs_alpha), float(self._eps), _stream(self)))
         return self._obs_out
 
     def _norm_rew(self, rew):
@@ -228,7 +236,10 @@ class StandardizedEnv(_Wrapper):
     def _reset_b(self, **kw):
         if self._fused:
             return self._inner_reset(**kw)  # already standardised by the env's kernel
-        return self._norm_obs(self._inner_reset(**kw))  # :276-281
+        mask = kw.get("mask")
+        if mask is not None:   # the env below converts it the same way
+            mask = kw["mask"] = torch.as_tensor(mask, device=self.device).reshape(self.n_envs).to(torch.uint8).contiguous()
+        return self._norm_obs(self._inner_reset(**kw), mask)  # :276-281
 
     def _step_b(self, *args, **kw):
         obs, rew, done, info = self._inner_step(*args, **kw)  # :283-291
