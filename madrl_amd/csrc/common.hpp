@@ -5,6 +5,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 #include <stdarg.h>
 #include <new>
 #include <vector>
@@ -203,6 +204,14 @@ __device__ __forceinline__ bool dist2_le(float ax, float ay, float bx, float by,
     const float dx = ax - bx, dy = ay - by;
     return dx * dx + dy * dy <= sq;
 }
+
+// StandardizedEnv.update_obs_estimate / update_rew_estimate (madrl_environments/__init__.py:245-249, :253-257): one element's exponential
+// running mean m and variance v take the value x, in float64 and in the reference's order of operations.
+__device__ __forceinline__ void ema_update(double &m, double &v, double x, double alpha) {
+    m = (1.0 - alpha) * m + alpha * x;
+    const double d = x - m;
+    v = (1.0 - alpha) * v + alpha * (d * d);
+}
 #endif
 
 // ---------------------------------------------------------------- host side of the env handles
@@ -234,8 +243,35 @@ inline dim3 particle_grid(int64_t max_blocks, int64_t n_envs) {
     return dim3((unsigned)blocks);
 }
 
-// madrl_waterworld_create / madrl_hostage_create after the world's own validation of cfg: H is the handle (cfg, dev, device,
-// max_blocks, lds_bytes, tables), layout() and lds_bytes() the world's functions of its configuration.
+// Fused StandardizedEnv (madrl_environments/__init__.py:204-311) of the particle worlds, the device copy of madrl_standardize_args:
+// the kernels' FUSED instantiations normalise the observation row as it leaves LDS and scale / normalise the rewards as they are
+// produced -- per env, per agent, per element exponential running mean / variance in float64, the arithmetic of the stand-alone
+// epilogue kernels (wrappers.hip obsnorm_kernel / rewnorm_kernel) in their order -- instead of storing the row raw for a second
+// launch to read back: 36 instead of 44 bytes of HBM traffic per observation element.
+struct ParticleStd {
+    double *obs_mean, *obs_var;   // [N][agents][D]
+    float *obs_out;               // [N][agents][D] standardised observations (a copy of the row without enable_obsnorm)
+    double *rew_mean, *rew_var;   // [N][agents]
+    float *rew_out;               // [N][agents] scale * (reward / (sqrt(var) + eps)); NULL = rewards are not touched
+    double obs_alpha, rew_alpha, eps, scale;
+    int32_t enable_obsnorm, enable_rewnorm;
+};
+
+// What a particle world's handle holds: struct madrl_waterworld / madrl_hostage derive from it with their configuration and Dev types.
+template <class C, class Dev>
+struct ParticleHandle {
+    C cfg;
+    Dev dev;
+    int device;
+    int64_t max_blocks;
+    size_t lds_bytes;
+    void *tables;
+    ParticleStd *std_dev;   // device copy of the bound StandardizedEnv arguments (particle_set_standardize)
+    bool std_bound;
+};
+
+// madrl_waterworld_create / madrl_hostage_create after the world's own validation of cfg: H is the handle, layout() and lds_bytes()
+// the world's functions of its configuration.
 template <class H, class C, class Dev>
 int particle_create(const C *cfg, const double *sensors_host, int64_t n_envs, int32_t device, void *state_dev, H **out,
                     void (*layout)(const C *, Dev *), size_t (*lds_bytes)(const Dev &)) {
@@ -271,6 +307,80 @@ int particle_create(const C *cfg, const double *sensors_host, int64_t n_envs, in
     h->dev.sensors = (const float *)h->tables;
     *out = h;
     return MADRL_OK;
+}
+
+// The rest of the two worlds' C ABI (madrl_waterworld_* / madrl_hostage_*) over a handle H.
+template <class H>
+int particle_kernel_kind(H *h, int32_t *out) {
+    if (!h || !out) return fail(MADRL_EINVAL, "kernel_kind: NULL argument");
+    *out = h->cfg.crowd ? 1 : 0;
+    return MADRL_OK;
+}
+
+template <class H>
+void particle_destroy(H *h) {
+    if (!h) return;
+    if (h->tables) (void)hipFree(h->tables);
+    if (h->std_dev) (void)hipFree(h->std_dev);
+    delete h;
+}
+
+template <class H>
+int particle_set_launch(H *h, int64_t max_blocks) {
+    if (!h || max_blocks < 0) return fail(MADRL_EINVAL, "set_launch: bad argument");
+    h->max_blocks = max_blocks;
+    return MADRL_OK;
+}
+
+template <class H>
+int particle_set_standardize(H *h, const madrl_standardize_args *a) {
+    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
+    if (!a) { h->std_bound = false; return MADRL_OK; }
+    if (h->cfg.crowd)
+        return fail(MADRL_EINVAL, "set_standardize: the crowd kernel has no fused StandardizedEnv; use the epilogue kernels (madrl_wrap_obsnorm / madrl_wrap_rewnorm)");
+    if (a->struct_size != (int32_t)sizeof(madrl_standardize_args))
+        return fail(MADRL_EINVAL, "madrl_standardize_args.struct_size=%d, library expects %d", a->struct_size, (int)sizeof(madrl_standardize_args));
+    if (!a->obs_out || (a->enable_obsnorm && (!a->obs_mean || !a->obs_var)) || (a->rew_out && a->enable_rewnorm && (!a->rew_mean || !a->rew_var)))
+        return fail(MADRL_EINVAL, "set_standardize: obs_out and the running statistics of every enabled normalisation are required");
+    ParticleStd st;
+    st.obs_mean = a->obs_mean; st.obs_var = a->obs_var; st.obs_out = a->obs_out;
+    st.rew_mean = a->rew_mean; st.rew_var = a->rew_var; st.rew_out = a->rew_out;
+    st.obs_alpha = a->obs_alpha; st.rew_alpha = a->rew_alpha; st.eps = a->eps; st.scale = a->scale_reward;
+    st.enable_obsnorm = a->enable_obsnorm; st.enable_rewnorm = a->enable_rewnorm;
+    MADRL_HIP_TRY(hipSetDevice(h->device));
+    if (!h->std_dev) MADRL_HIP_TRY(hipMalloc((void **)&h->std_dev, sizeof(ParticleStd)));
+    MADRL_HIP_TRY(hipMemcpy(h->std_dev, &st, sizeof(ParticleStd), hipMemcpyHostToDevice));
+    h->std_bound = true;
+    return MADRL_OK;
+}
+
+// reset / step: the world's IO struct filled (both have these fields under these names) and handed to its launch(h, io, mode, stream),
+// mode 0 = reset, 1 = step
+template <class H, class IO>
+int particle_reset(H *h, const uint8_t *mask_dev, float *obs_dev, void *stream, int (*launch)(const H *, const IO &, int, void *)) {
+    if (!h || (!obs_dev && !h->std_bound)) return fail(MADRL_EINVAL, "reset: handle/obs is NULL");
+    IO io;
+    memset(&io, 0, sizeof(io));
+    io.mask = mask_dev;
+    io.obs = obs_dev;
+    io.st = h->std_bound ? h->std_dev : nullptr;
+    return launch(h, io, 0, stream);
+}
+
+template <class H, class IO>
+int particle_step(H *h, const float *actions_dev, const float *inj_respawn_dev, float *obs_dev, float *rew_dev, uint8_t *done_dev,
+                  int32_t *info_dev, void *stream, int (*launch)(const H *, const IO &, int, void *)) {
+    if (!h || !actions_dev || (!obs_dev && !h->std_bound) || !rew_dev || !done_dev || !info_dev) return fail(MADRL_EINVAL, "step: NULL argument");
+    IO io;
+    memset(&io, 0, sizeof(io));
+    io.actions = actions_dev;
+    io.inj_resp = inj_respawn_dev;
+    io.obs = obs_dev;
+    io.st = h->std_bound ? h->std_dev : nullptr;
+    io.rew = rew_dev;
+    io.done = done_dev;
+    io.info = info_dev;
+    return launch(h, io, 1, stream);
 }
 
 }  // namespace madrl

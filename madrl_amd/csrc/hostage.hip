@@ -53,7 +53,7 @@ __device__ __forceinline__ float bcast(float v, int src_lane) { return __int_as_
 
 // MODE 0: reset(mask)   MODE 1: step (+ fused auto-reset)
 // TNr..TK > 0: the particle / sensor counts are compile-time constants (small loops unroll, the index divisions fold); 0: generic.
-// FUSED: the StandardizedEnv epilogue (HwStd) is compiled in; a template parameter and not a run-time branch because its float64 code
+// FUSED: the StandardizedEnv epilogue (ParticleStd, common.hpp) is compiled in; a template parameter and not a run-time branch because its float64 code
 // would otherwise cost the plain kernel registers, i.e. resident wavefronts (measured on Waterworld: 96 instead of 78 us per step)
 #define MADRL_HW_OCC_N (TNr > 0 ? (FUSED ? (MODE == 1 ? MADRL_HW_FUSED_STEP_WAVES : MADRL_HW_FUSED_RESET_WAVES) : MADRL_HW_WAVES) : 0)
 template <int MODE, int TNr, int TNh, int TNc, int TK, int TD = 0, bool FUSED = false>
@@ -463,7 +463,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                     if (fresh(lane) < Nr) uniform_ptr(IOA.rew + env * Nr)[ulane] = reward;
                     if constexpr (FUSED) {  // StandardizedEnv.step :283-291, the operations of wrappers.hip rewnorm_kernel in its order
                         if (IOA.st->rew_out != nullptr && fresh(lane) < Nr) {
-                            const HwStd &st = *IOA.st;
+                            const ParticleStd &st = *IOA.st;
                             const int64_t i = env * Nr + lane;
                             double r = (double)reward;
                             if (st.enable_rewnorm) {
@@ -509,7 +509,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                     }
                     // by value: through a reference into global memory every float64 store of the loop could have changed alpha, eps and the
                     // pointers (type-based aliasing), and the compiler would load them again behind each one
-                    const HwStd st = *IOA.st;
+                    const ParticleStd st = *IOA.st;
                     if (st.enable_obsnorm) {
                         // batches of 4 elements per lane: all 8 statistics loads of a batch are in flight before the first dependent float64
                         // operation (waterworld.hip: element by element 421, batched 357 us per wrapped step).  The operations of wrappers.hip
@@ -575,16 +575,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
 }  // namespace
 
 // =================================================================== host side / C ABI
-struct madrl_hostage {
-    madrl_hostage_config cfg;
-    HwDev dev;
-    int device;
-    int64_t max_blocks;
-    size_t lds_bytes;
-    void *tables;
-    HwStd *std_dev;   // device copy of the bound StandardizedEnv arguments (madrl_hostage_set_standardize)
-    bool std_bound;
-};
+struct madrl_hostage : ParticleHandle<madrl_hostage_config, HwDev> {};
 
 namespace {
 
@@ -729,69 +720,21 @@ int madrl_hostage_create(const madrl_hostage_config *cfg, const double *sensors_
     return particle_create(&full, sensors_host, n_envs, device, state_dev, out, hw_layout, full.crowd ? hw_lds_bytes_crowd : hw_lds_bytes);
 }
 
-int madrl_hostage_kernel_kind(madrl_hostage *h, int32_t *out) {
-    if (!h || !out) return fail(MADRL_EINVAL, "kernel_kind: NULL argument");
-    *out = h->cfg.crowd ? 1 : 0;
-    return MADRL_OK;
-}
+int madrl_hostage_kernel_kind(madrl_hostage *h, int32_t *out) { return particle_kernel_kind(h, out); }
 
-void madrl_hostage_destroy(madrl_hostage *h) {
-    if (!h) return;
-    if (h->tables) (void)hipFree(h->tables);
-    if (h->std_dev) (void)hipFree(h->std_dev);
-    delete h;
-}
+void madrl_hostage_destroy(madrl_hostage *h) { particle_destroy(h); }
 
-int madrl_hostage_set_standardize(madrl_hostage *h, const madrl_standardize_args *a) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    if (!a) { h->std_bound = false; return MADRL_OK; }
-    if (h->cfg.crowd)
-        return fail(MADRL_EINVAL, "set_standardize: the crowd kernel has no fused StandardizedEnv; use the epilogue kernels (madrl_wrap_obsnorm / madrl_wrap_rewnorm)");
-    if (a->struct_size != (int32_t)sizeof(madrl_standardize_args))
-        return fail(MADRL_EINVAL, "madrl_standardize_args.struct_size=%d, library expects %d", a->struct_size, (int)sizeof(madrl_standardize_args));
-    if (!a->obs_out || (a->enable_obsnorm && (!a->obs_mean || !a->obs_var)) || (a->rew_out && a->enable_rewnorm && (!a->rew_mean || !a->rew_var)))
-        return fail(MADRL_EINVAL, "set_standardize: obs_out and the running statistics of every enabled normalisation are required");
-    HwStd st;
-    st.obs_mean = a->obs_mean; st.obs_var = a->obs_var; st.obs_out = a->obs_out;
-    st.rew_mean = a->rew_mean; st.rew_var = a->rew_var; st.rew_out = a->rew_out;
-    st.obs_alpha = a->obs_alpha; st.rew_alpha = a->rew_alpha; st.eps = a->eps; st.scale = a->scale_reward;
-    st.enable_obsnorm = a->enable_obsnorm; st.enable_rewnorm = a->enable_rewnorm;
-    MADRL_HIP_TRY(hipSetDevice(h->device));
-    if (!h->std_dev) MADRL_HIP_TRY(hipMalloc((void **)&h->std_dev, sizeof(HwStd)));
-    MADRL_HIP_TRY(hipMemcpy(h->std_dev, &st, sizeof(HwStd), hipMemcpyHostToDevice));
-    h->std_bound = true;
-    return MADRL_OK;
-}
+int madrl_hostage_set_standardize(madrl_hostage *h, const madrl_standardize_args *a) { return particle_set_standardize(h, a); }
 
-int madrl_hostage_set_launch(madrl_hostage *h, int64_t max_blocks) {
-    if (!h || max_blocks < 0) return fail(MADRL_EINVAL, "set_launch: bad argument");
-    h->max_blocks = max_blocks;
-    return MADRL_OK;
-}
+int madrl_hostage_set_launch(madrl_hostage *h, int64_t max_blocks) { return particle_set_launch(h, max_blocks); }
 
 int madrl_hostage_reset(madrl_hostage *h, const uint8_t *mask_dev, float *obs_dev, void *stream) {
-    if (!h || (!obs_dev && !h->std_bound)) return fail(MADRL_EINVAL, "reset: handle/obs is NULL");
-    HwIO io;
-    memset(&io, 0, sizeof(io));
-    io.mask = mask_dev;
-    io.obs = obs_dev;
-    io.st = h->std_bound ? h->std_dev : nullptr;
-    return hw_launch(h, io, 0, stream);
+    return particle_reset(h, mask_dev, obs_dev, stream, hw_launch);
 }
 
 int madrl_hostage_step(madrl_hostage *h, const float *actions_dev, const float *inj_respawn_dev, float *obs_dev, float *rew_dev,
                        uint8_t *done_dev, int32_t *info_dev, void *stream) {
-    if (!h || !actions_dev || (!obs_dev && !h->std_bound) || !rew_dev || !done_dev || !info_dev) return fail(MADRL_EINVAL, "step: NULL argument");
-    HwIO io;
-    memset(&io, 0, sizeof(io));
-    io.actions = actions_dev;
-    io.inj_resp = inj_respawn_dev;
-    io.obs = obs_dev;
-    io.st = h->std_bound ? h->std_dev : nullptr;
-    io.rew = rew_dev;
-    io.done = done_dev;
-    io.info = info_dev;
-    return hw_launch(h, io, 1, stream);
+    return particle_step(h, actions_dev, inj_respawn_dev, obs_dev, rew_dev, done_dev, info_dev, stream, hw_launch);
 }
 
 int madrl_hostage_get_state(madrl_hostage *h, float *pos, float *vel, float *key, float *bomb, uint64_t *saved, uint8_t *flags, int32_t *t,

@@ -29,19 +29,6 @@ struct HwDev {
     float *state;
 };
 
-// Fused StandardizedEnv (madrl_environments/__init__.py:204-311), the fields of waterworld_dev.hpp's WwStd: hostage_kernel<..., FUSED>
-// normalises the observation row as it leaves LDS and scales / normalises the rewards as they are produced -- per env, per rescuer,
-// per element exponential running mean / variance in float64, the arithmetic of the stand-alone epilogue kernels (wrappers.hip
-// obsnorm_kernel / rewnorm_kernel) in their order -- instead of storing the row raw for a second launch to read back.
-struct HwStd {
-    double *obs_mean, *obs_var;   // [N][Nr][D]
-    float *obs_out;               // [N][Nr][D] standardised observations (a copy of the row without enable_obsnorm)
-    double *rew_mean, *rew_var;   // [N][Nr]
-    float *rew_out;               // [N][Nr] scale * (reward / (sqrt(var) + eps)); NULL = rewards are not touched
-    double obs_alpha, rew_alpha, eps, scale;
-    int32_t enable_obsnorm, enable_rewnorm;
-};
-
 struct HwIO {
     const uint8_t *mask;    // reset mode
     const float *actions;   // [N][Nr][2]
@@ -50,7 +37,7 @@ struct HwIO {
     float *rew;             // [N][Nr]
     uint8_t *done;          // [N]
     int32_t *info;          // [N][2]  ho_saved, cr_encs
-    const HwStd *st;        // device copy of the fused-wrapper arguments, or NULL (last: the offsets of the fields above stay)
+    const ParticleStd *st;  // device copy of the fused-wrapper arguments (common.hpp), or NULL (last: the offsets of the fields above stay)
 };
 
 }  // namespace

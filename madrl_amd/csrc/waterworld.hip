@@ -24,7 +24,7 @@
 // the handle was created with cfg.crowd = 1; the handle, validation, record layout and dispatch of both kernels are in this file.
 // Arithmetic is float32 (north_star tolerance 1e-5 against the float64 reference); every
 // expression keeps the statement order of the reference's step() so that a float32 CPU restatement agrees bit for bit.
-#include "waterworld_dev.hpp"   // WwDev, WwStd, WwIO, the RNG tags: shared with waterworld_crowd.hip
+#include "waterworld_dev.hpp"   // WwDev, WwIO, the RNG tags: shared with waterworld_crowd.hip
 
 #include <math.h>
 #include <string.h>
@@ -56,7 +56,7 @@ struct WwKArgs {
 
 // MODE 0: reset(mask)   MODE 1: step (+ fused auto-reset)
 // TNp..TK > 0: the particle / sensor counts are compile-time constants (loops unroll, the index divisions fold); 0: generic.
-// FUSED: the StandardizedEnv epilogue (WwStd) is compiled in; a template parameter because its float64 code would otherwise cost the
+// FUSED: the StandardizedEnv epilogue (ParticleStd, common.hpp) is compiled in; a template parameter because its float64 code would otherwise cost the
 // plain kernel a wavefront per SIMD (132 instead of 119 VGPRs: 96 instead of 78 us per step)
 template <int MODE, int TNp, int TNe, int TNpo, int TK, bool FUSED = false, int TD = 0>
 __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev d, const WwIO io) {
@@ -518,7 +518,7 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                 if (MODE == 1 && !do_init) {
                     if (LANE_LT(Np)) uniform_ptr(IOA.rew + env * Np)[ulane] = reward;
                     if (FUSED && IOA.st->rew_out != nullptr && LANE_LT(Np)) {  // StandardizedEnv.step :283-291
-                        const WwStd &st = *IOA.st;
+                        const ParticleStd &st = *IOA.st;
                         const int64_t i = env * Np + lane;
                         double r = (double)reward;
                         if (st.enable_rewnorm) {
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                         for (uint32_t e = 4u * n4 + ulane; e < (uint32_t)(Np * D); e += 64u) orow[e] = O[e];
                     }
                     if (FUSED) {  // StandardizedEnv.standardize_obs :242-263
-                        const WwStd &st = *IOA.st;
+                        const ParticleStd &st = *IOA.st;   // (hostage.hip reads these arguments by value and says why; this kernel keeps the reference)
                         const int64_t base = env * (int64_t)(Np * D);
                         if (st.enable_obsnorm) {
                             // batches of 4 elements per lane: all 8 statistics loads of a batch are in flight before the first
@@ -580,9 +580,8 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                                     const int e = e0 + 64 * u;
                                     if (e < n_el) {
                                         const double x = (double)O[e];
-                                        const double mm = (1.0 - st.obs_alpha) * m[u] + st.obs_alpha * x;      // :245-246
-                                        const double dd = x - mm;
-                                        const double vv = (1.0 - st.obs_alpha) * v[u] + st.obs_alpha * (dd * dd);  // :247-249
+                                        double mm = m[u], vv = v[u];
+                                        ema_update(mm, vv, x, st.obs_alpha);                                  // :245-249
                                         __builtin_nontemporal_store(mm, &st.obs_mean[base + e]);
                                         __builtin_nontemporal_store(vv, &st.obs_var[base + e]);
                                         __builtin_nontemporal_store((float)((x - mm) / (sqrt(vv) + st.eps)), &st.obs_out[base + e]);  // :262-263
@@ -620,16 +619,7 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
 
 }  // namespace
 // =================================================================== host side / C ABI
-struct madrl_waterworld {
-    madrl_waterworld_config cfg;
-    WwDev dev;
-    int device;
-    int64_t max_blocks;
-    size_t lds_bytes;
-    void *tables;
-    WwStd *std_dev;   // device copy of the bound StandardizedEnv arguments (madrl_waterworld_set_standardize)
-    bool std_bound;
-};
+struct madrl_waterworld : ParticleHandle<madrl_waterworld_config, WwDev> {};
 
 namespace {
 
@@ -785,69 +775,21 @@ int madrl_waterworld_create(const madrl_waterworld_config *cfg, const double *se
     return particle_create(cfg, sensors_host, n_envs, device, state_dev, out, ww_layout, cfg->crowd ? ww_lds_bytes_crowd : ww_lds_bytes);
 }
 
-int madrl_waterworld_kernel_kind(madrl_waterworld *h, int32_t *out) {
-    if (!h || !out) return fail(MADRL_EINVAL, "kernel_kind: NULL argument");
-    *out = h->cfg.crowd ? 1 : 0;
-    return MADRL_OK;
-}
+int madrl_waterworld_kernel_kind(madrl_waterworld *h, int32_t *out) { return particle_kernel_kind(h, out); }
 
-void madrl_waterworld_destroy(madrl_waterworld *h) {
-    if (!h) return;
-    if (h->tables) (void)hipFree(h->tables);
-    if (h->std_dev) (void)hipFree(h->std_dev);
-    delete h;
-}
+void madrl_waterworld_destroy(madrl_waterworld *h) { particle_destroy(h); }
 
-int madrl_waterworld_set_standardize(madrl_waterworld *h, const madrl_standardize_args *a) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    if (!a) { h->std_bound = false; return MADRL_OK; }
-    if (h->cfg.crowd)
-        return fail(MADRL_EINVAL, "set_standardize: the crowd kernel has no fused StandardizedEnv; use the epilogue kernels (madrl_wrap_obsnorm / madrl_wrap_rewnorm)");
-    if (a->struct_size != (int32_t)sizeof(madrl_standardize_args))
-        return fail(MADRL_EINVAL, "madrl_standardize_args.struct_size=%d, library expects %d", a->struct_size, (int)sizeof(madrl_standardize_args));
-    if (!a->obs_out || (a->enable_obsnorm && (!a->obs_mean || !a->obs_var)) || (a->rew_out && a->enable_rewnorm && (!a->rew_mean || !a->rew_var)))
-        return fail(MADRL_EINVAL, "set_standardize: obs_out and the running statistics of every enabled normalisation are required");
-    WwStd st;
-    st.obs_mean = a->obs_mean; st.obs_var = a->obs_var; st.obs_out = a->obs_out;
-    st.rew_mean = a->rew_mean; st.rew_var = a->rew_var; st.rew_out = a->rew_out;
-    st.obs_alpha = a->obs_alpha; st.rew_alpha = a->rew_alpha; st.eps = a->eps; st.scale = a->scale_reward;
-    st.enable_obsnorm = a->enable_obsnorm; st.enable_rewnorm = a->enable_rewnorm;
-    MADRL_HIP_TRY(hipSetDevice(h->device));
-    if (!h->std_dev) MADRL_HIP_TRY(hipMalloc((void **)&h->std_dev, sizeof(WwStd)));
-    MADRL_HIP_TRY(hipMemcpy(h->std_dev, &st, sizeof(WwStd), hipMemcpyHostToDevice));
-    h->std_bound = true;
-    return MADRL_OK;
-}
+int madrl_waterworld_set_standardize(madrl_waterworld *h, const madrl_standardize_args *a) { return particle_set_standardize(h, a); }
 
-int madrl_waterworld_set_launch(madrl_waterworld *h, int64_t max_blocks) {
-    if (!h || max_blocks < 0) return fail(MADRL_EINVAL, "set_launch: bad argument");
-    h->max_blocks = max_blocks;
-    return MADRL_OK;
-}
+int madrl_waterworld_set_launch(madrl_waterworld *h, int64_t max_blocks) { return particle_set_launch(h, max_blocks); }
 
 int madrl_waterworld_reset(madrl_waterworld *h, const uint8_t *mask_dev, float *obs_dev, void *stream) {
-    if (!h || (!obs_dev && !h->std_bound)) return fail(MADRL_EINVAL, "reset: handle/obs is NULL");
-    WwIO io;
-    memset(&io, 0, sizeof(io));
-    io.mask = mask_dev;
-    io.obs = obs_dev;
-    io.st = h->std_bound ? h->std_dev : nullptr;
-    return ww_launch(h, io, 0, stream);
+    return particle_reset(h, mask_dev, obs_dev, stream, ww_launch);
 }
 
 int madrl_waterworld_step(madrl_waterworld *h, const float *actions_dev, const float *inj_respawn_dev, float *obs_dev,
                           float *rew_dev, uint8_t *done_dev, int32_t *info_dev, void *stream) {
-    if (!h || !actions_dev || (!obs_dev && !h->std_bound) || !rew_dev || !done_dev || !info_dev) return fail(MADRL_EINVAL, "step: NULL argument");
-    WwIO io;
-    memset(&io, 0, sizeof(io));
-    io.actions = actions_dev;
-    io.inj_resp = inj_respawn_dev;
-    io.obs = obs_dev;
-    io.st = h->std_bound ? h->std_dev : nullptr;
-    io.rew = rew_dev;
-    io.done = done_dev;
-    io.info = info_dev;
-    return ww_launch(h, io, 1, stream);
+    return particle_step(h, actions_dev, inj_respawn_dev, obs_dev, rew_dev, done_dev, info_dev, stream, ww_launch);
 }
 
 int madrl_waterworld_get_state(madrl_waterworld *h, float *pos, float *vel, float *obst, int32_t *t, uint32_t *tick,

@@ -30,19 +30,6 @@ struct WwDev {
     float *state;
 };
 
-// Fused StandardizedEnv (madrl_environments/__init__.py:204-311): when `obs_out` is set, the observation row is normalised as
-// it leaves LDS -- per env, per agent, per element exponential running mean / variance in float64, exactly the arithmetic of the
-// stand-alone epilogue kernel (wrappers.hip obsnorm_kernel / rewnorm_kernel) -- instead of being stored raw and read back by a
-// second launch: 36 instead of 44 bytes of HBM traffic per observation element.
-struct WwStd {
-    double *obs_mean, *obs_var;   // [N][Np][D]
-    float *obs_out;               // [N][Np][D] normalised observations; NULL = not fused
-    double *rew_mean, *rew_var;   // [N][Np]
-    float *rew_out;               // [N][Np] scale * (reward / (sqrt(var) + eps)); NULL = rewards are not touched
-    double obs_alpha, rew_alpha, eps, scale;
-    int32_t enable_obsnorm, enable_rewnorm;
-};
-
 struct WwIO {
     const uint8_t *mask;    // reset mode
     const float *actions;   // [N][Np][2]
@@ -51,7 +38,7 @@ struct WwIO {
     float *rew;             // [N][Np]
     uint8_t *done;          // [N]
     int32_t *info;          // [N][2]  evcatches, pocatches
-    const WwStd *st;        // device copy of the fused-wrapper arguments, or NULL
+    const ParticleStd *st;  // device copy of the fused-wrapper arguments (common.hpp), or NULL
 };
 
 }  // namespace

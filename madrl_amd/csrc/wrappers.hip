@@ -35,9 +35,7 @@ typedef double d2_t __attribute__((ext_vector_type(2)));
 typedef float f2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void obsnorm_one(double &m, double &v, float x, float &o, double alpha, double eps) {
     const double xd = (double)x;
-    m = (1.0 - alpha) * m + alpha * xd;                                    // :245-246
-    const double d = xd - m;
-    v = (1.0 - alpha) * v + alpha * (d * d);                               // :247-249
+    ema_update(m, v, xd, alpha);                                           // :245-249
     o = (float)((xd - m) / (sqrt(v) + eps));                               // :262-263
 }
 __global__ __launch_bounds__(256) void obsnorm_pairs_kernel(const float *obs_in, double *mean, double *var, float *obs_out, int64_t n_pairs,
@@ -79,9 +77,8 @@ __global__ void rewnorm_kernel(const float *rew_in, double *mean, double *var, f
         if (mask != nullptr && mask[i / per_env] == 0) continue;
         double r = (double)rew_in[i];
         if (enable) {
-            const double m = (1.0 - alpha) * mean[i] + alpha * r;          // :253-254
-            const double d = r - m;
-            const double v = (1.0 - alpha) * var[i] + alpha * (d * d);     // :255-257
+            double m = mean[i], v = var[i];
+            ema_update(m, v, r, alpha);                                    // :253-257
             mean[i] = m;
             var[i] = v;
             r = r / (sqrt(v) + eps);                                       // :268-271 (the mean is not subtracted)

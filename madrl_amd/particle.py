@@ -1,0 +1,286 @@
+"""The host layer the two particle worlds share (madrl_amd/waterworld.py, madrl_amd/hostage.py): buffers and handle, seed / reset / step,
+the fused StandardizedEnv binding, state access, pickling -- and the N == 1 drop-in shell.  A world declares its C symbols, attribute names,
+info keys and state layout (the class attributes below) and keeps its constructor, `_config()` and what only it has."""
+import ctypes as C
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import _lib
+from .base import AbstractMAEnv, SingleEnvDelegate
+
+_CALLS = ("obs_dim", "state_bytes", "create", "destroy", "set_launch", "kernel_kind", "set_standardize", "reset", "step", "get_state",
+          "set_state")
+_API = {}   # C symbol prefix -> the world's functions under their short names (filled by setup(): nothing is kept on the instance)
+
+
+def _api(prefix):
+    L = _lib.lib()
+    if prefix not in _API:
+        _API[prefix] = SimpleNamespace(**{name: getattr(L, "%s_%s" % (prefix, name)) for name in _CALLS})
+    return _API[prefix]
+
+
+def sensor_vectors(n_sensors):
+    """Archea.__init__, waterworld.py:29-31: unit vectors of the K ray sensors (float64)."""
+    angles = np.linspace(0., 2. * np.pi, n_sensors + 1)[:-1]
+    return np.ascontiguousarray(np.c_[np.cos(angles), np.sin(angles)])
+
+
+class BatchedParticleWorld(AbstractMAEnv):
+    """A subclass's constructor assigns the reference's parameters, `_ctor`, `_crowd`, n_envs, device, `_seed_value`, env_id_base, max_steps,
+    auto_reset, `_max_blocks` and `_handle = None`, then calls setup().  Every parameter, the agent count included, is read from the live
+    attributes where it is used: nothing of them is copied here."""
+    _SYM = None         # prefix of the C symbols: "madrl_waterworld"
+    _COUNTS = None      # names of the attributes that hold the particle counts, the agents' first: ("n_pursuers", "n_evaders", "n_poison")
+    _INJECT = None      # name of the attribute that holds the row count of step(respawn=...)
+    _INFO_KEYS = None   # the two info keys of step()
+    _AGENT = None       # the agent class: _AGENT(idx, obs_dim)
+    _STATE = None       # get_state / set_state: ((name, dtype, per-env shape), ...) in the C functions' order, "NP" = n_particles
+
+    def setup(self):
+        c = _api(self._SYM)
+        if self.device.type != "cuda":
+            raise _lib.MadrlError("%s needs a ROCm device (got %s); there is no CPU path" % (type(self).__name__, self.device))
+        cfg = self._config()
+        dim, nbytes = C.c_int32(), C.c_uint64()
+        _lib.check(c.obs_dim(C.byref(cfg), C.byref(dim)))
+        _lib.check(c.state_bytes(C.byref(cfg), self.n_envs, C.byref(nbytes)))
+        counts = [getattr(self, k) for k in self._COUNTS]
+        N, Na, D, dev = self.n_envs, counts[0], dim.value, self.device
+        self.n_particles = sum(counts)
+        if getattr(self, "_shape_key", None) != (N, Na, D, nbytes.value):
+            self._state = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
+            self._obs = torch.zeros((N, Na, D), dtype=torch.float32, device=dev)
+            self._rew = torch.zeros((N, Na), dtype=torch.float32, device=dev)
+            self._done = torch.zeros(N, dtype=torch.uint8, device=dev)
+            self._info = torch.zeros((N, 2), dtype=torch.int32, device=dev)
+            self._shape_key = (N, Na, D, nbytes.value)
+        self.obs_dim = D
+        self._destroy()
+        h = C.c_void_p()
+        self._sensors = sensor_vectors(self.n_sensors)
+        dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
+        _lib.check(c.create(C.byref(cfg), self._sensors.ctypes.data_as(C.c_void_p), N, dev_index, _lib.ptr(self._state), C.byref(h)))
+        self._handle = h
+        if self._max_blocks:
+            _lib.check(c.set_launch(h, self._max_blocks))
+        if N >= 4096 and not self._crowd:   # (the crowd kernel takes its shape at run time: there is nothing to specialise)
+            self._hint_fast_path(D)
+        self._agents = [self._AGENT(i + 1, D) for i in range(Na)]
+        # A fused StandardizedEnv binding belongs to the handle that was just replaced (seed() and set_param_values() come
+        # through here): bind the new handle to the SAME statistics / output tensors, or -- when the shapes changed -- to
+        # fresh ones, so that the wrapper keeps receiving standardised rows.
+        old, self._std = getattr(self, "_std", None), None
+        if old is not None:
+            if tuple(old["obs_out"].shape) == (N, Na, D):
+                self.bind_standardize(tensors=old, **self._std_kwargs)
+            else:   # new shapes: fresh statistics, handed to the wrapper through the SAME dict object it holds
+                fresh = self.bind_standardize(tensors=None, **self._std_kwargs)
+                old.clear(); old.update(fresh)
+                self._std = old
+
+    def _hint_fast_path(self, D):
+        """a world with a list of specialised shapes says here that a large batch runs on the generic kernel (called by setup() itself)"""
+
+    @property
+    def kernel_kind(self):
+        """"wave": one wavefront per env; "crowd": one workgroup of several wavefronts per env (crowd=True)"""
+        kind = C.c_int32()
+        _lib.check(_API[self._SYM].kernel_kind(self._handle, C.byref(kind)))
+        return ("wave", "crowd")[kind.value]
+
+    @property
+    def fused_standardize(self):
+        """whether bind_standardize() works on this env (StandardizedEnv asks): the crowd kernel has no fused form"""
+        return not self._crowd
+
+    def set_launch(self, max_blocks=0):
+        self._max_blocks = int(max_blocks)
+        _lib.check(_API[self._SYM].set_launch(self._handle, self._max_blocks))
+
+    def _destroy(self):
+        if getattr(self, "_handle", None):
+            _API[self._SYM].destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self._destroy()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ reference API
+    @property
+    def reward_mech(self):
+        return self._reward_mech
+
+    @property
+    def timestep_limit(self):
+        return self.max_steps if self.max_steps > 0 else 1000  # waterworld.py:124-126, hostage.py:118-120
+
+    @property
+    def agents(self):
+        return self._agents
+
+    def seed(self, seed=None):
+        if seed is None:
+            seed = int(np.random.randint(2**31 - 1))
+        self._seed_value = int(seed)
+        self.setup()
+        return [self._seed_value]
+
+    def reset(self, mask=None):
+        if mask is not None:
+            mask = torch.as_tensor(mask, device=self.device).reshape(self.n_envs).to(torch.uint8).contiguous()
+        std = getattr(self, "_std", None)
+        _lib.check(_API[self._SYM].reset(self._handle, _lib.ptr(mask), None if std else _lib.ptr(self._obs), _lib.current_stream(self.device)))
+        return std["obs_out"] if std else self._obs
+
+    # ------------------------------------------------------------------ fused StandardizedEnv (include/madrl_hip.h)
+    def bind_standardize(self, scale_reward=1.0, enable_obsnorm=False, enable_rewnorm=False, obs_alpha=0.001, rew_alpha=0.001, eps=1e-8,
+                         tensors=None):
+        """The kernels normalise observations / rewards on their way out (madrl_*_set_standardize): reset() and
+        step() then return the standardised tensors and the raw observation row is not stored.  Returns the dict of
+        state tensors (running statistics, outputs) the wrapper owns; `tensors` re-binds an existing dict (setup()).
+        The crowd kernel has no fused form: StandardizedEnv runs its epilogue kernels over such an env."""
+        if self._crowd:
+            raise _lib.MadrlError("bind_standardize: the crowd kernel (crowd=True) has no fused StandardizedEnv; "
+                                  "StandardizedEnv(env) or StandardizedEnv(env, fused=False) runs the epilogue kernels over it")
+        N, Na, D, dev = self.n_envs, getattr(self, self._COUNTS[0]), self.obs_dim, self.device
+        self._std_kwargs = dict(scale_reward=scale_reward, enable_obsnorm=enable_obsnorm, enable_rewnorm=enable_rewnorm,
+                                obs_alpha=obs_alpha, rew_alpha=rew_alpha, eps=eps)
+        st = tensors if tensors is not None else dict(
+            obs_mean=torch.zeros((N, Na, D), dtype=torch.float64, device=dev), obs_var=torch.ones((N, Na, D), dtype=torch.float64, device=dev),
+            obs_out=torch.zeros((N, Na, D), dtype=torch.float32, device=dev),
+            rew_mean=torch.zeros((N, Na), dtype=torch.float64, device=dev), rew_var=torch.ones((N, Na), dtype=torch.float64, device=dev),
+            rew_out=torch.zeros((N, Na), dtype=torch.float32, device=dev))
+        a = _lib.StandardizeArgs()
+        a.struct_size = C.sizeof(_lib.StandardizeArgs)
+        a.enable_obsnorm, a.enable_rewnorm = int(bool(enable_obsnorm)), int(bool(enable_rewnorm))
+        a.obs_alpha, a.rew_alpha, a.eps, a.scale_reward = float(obs_alpha), float(rew_alpha), float(eps), float(scale_reward)
+        for k, v in st.items():
+            setattr(a, k, v.data_ptr())
+        _lib.check(_API[self._SYM].set_standardize(self._handle, C.byref(a)))
+        self._std = st
+        return st
+
+    def unbind_standardize(self):
+        _lib.check(_API[self._SYM].set_standardize(self._handle, None))
+        self._std = None
+
+    def step(self, action, respawn=None, obs_out=None):
+        """waterworld.py:220-436, hostage.py:228-430.  action: float [N, n_agents, 2] (or anything that reshapes to it).
+        respawn: optional float [N, rows, 4] injected respawn outcomes (parity hook; rows: every particle in Waterworld, the criminals in
+        the hostage world).
+        obs_out: optional contiguous float32 destination of N * n_agents * obs_dim elements on the env's device (e.g. a slot of a trajectory
+        tensor) the kernel writes the observations to instead of the env's own buffer; its [N, n_agents, D] view is returned.  Refused while
+        a fused StandardizedEnv is bound: the observation tensor the kernel writes then belongs to the wrapper."""
+        N, Na = self.n_envs, getattr(self, self._COUNTS[0])
+        if not self._conforming(action):
+            a = torch.as_tensor(action, device=self.device)
+            if a.numel() != N * Na * 2:
+                raise AssertionError("action has %d elements, expected %d" % (a.numel(), N * Na * 2))  # waterworld.py:227, hostage.py:234
+            action = a.reshape(N, Na, 2).to(torch.float32).contiguous()
+        r = None
+        if respawn is not None:
+            r = torch.as_tensor(respawn, device=self.device).reshape(N, getattr(self, self._INJECT), 4).to(torch.float32).contiguous()
+        return self._launch_step(action, r, _lib.current_stream(self.device), obs_out)
+
+    def _conforming(self, a):
+        """an action tensor the kernel can read as it is (float32, contiguous, on the device, N * n_agents * 2 elements): no torch kernel needed"""
+        return (type(a) is torch.Tensor and a.dtype is torch.float32 and a.device == self.device and a.is_contiguous()
+                and a.numel() == self.n_envs * getattr(self, self._COUNTS[0]) * 2)
+
+    def step_on_stream(self, action, stream):
+        """step() launched on `stream` (a torch.cuda.Stream) without making it the current stream -- for callers that drive sub-batches on
+        their own streams (madrl_amd/sharded.py): entering a `with torch.cuda.stream(...)` block costs the host more than this launch.
+        Returns None when the action needs a conversion kernel (the caller then takes step() under the stream context)."""
+        if not self._conforming(action):
+            return None
+        return self._launch_step(action, None, C.c_void_p(stream.cuda_stream))
+
+    def _launch_step(self, a, r, stream_ptr, obs_out=None):
+        std = getattr(self, "_std", None)
+        obs = self._obs
+        if obs_out is not None:
+            if std:
+                raise ValueError("obs_out: a fused StandardizedEnv is bound to this env, the kernel's observation output belongs to the wrapper")
+            obs = _lib.obs_destination(obs_out, self._obs)
+        _lib.check(_API[self._SYM].step(self._handle, _lib.ptr(a), _lib.ptr(r), None if std else _lib.ptr(obs), _lib.ptr(self._rew),
+                                _lib.ptr(self._done), _lib.ptr(self._info), stream_ptr))
+        # `done` is a bool VIEW of the byte the kernel wrote (0 / 1): no torch kernel runs after the launch
+        info = {self._INFO_KEYS[0]: self._info[:, 0], self._INFO_KEYS[1]: self._info[:, 1], "done_bits": self._done}
+        if std:  # fused StandardizedEnv: standardised observations and scaled / normalised rewards straight from the kernel
+            return std["obs_out"], std["rew_out"], self._done.view(torch.bool), info
+        return obs, self._rew, self._done.view(torch.bool), info
+
+    # ------------------------------------------------------------------ state access
+    def _state_layout(self):
+        """_STATE with the batch's shapes: [(name, dtype, shape), ...]"""
+        return [(k, dt, (self.n_envs,) + tuple(self.n_particles if s == "NP" else s for s in shape)) for k, dt, shape in self._STATE]
+
+    def get_state(self):
+        st = {k: torch.zeros(shape, dtype=dt, device=self.device) for k, dt, shape in self._state_layout()}
+        _lib.check(_API[self._SYM].get_state(self._handle, *[_lib.ptr(v) for v in st.values()], _lib.current_stream(self.device)))
+        return st
+
+    def _set_state(self, values, to_array=np.asarray):
+        """values: {name: tensor, array-like or None (that part stays)}; to_array: what makes an array of a value that is no tensor"""
+        args = []
+        for k, dt, shape in self._state_layout():
+            v = values.get(k)
+            if v is not None:
+                v = torch.as_tensor(v if torch.is_tensor(v) else to_array(v), device=self.device).reshape(shape).to(dt).contiguous()
+            args.append(v)
+        self._keepalive = args
+        _lib.check(_API[self._SYM].set_state(self._handle, *[_lib.ptr(a) for a in args], _lib.current_stream(self.device)))
+
+    def __getstate__(self):
+        return dict(self._ctor)
+
+    def __setstate__(self, d):
+        self.__init__(**d)
+
+
+class ParticleWorld(SingleEnvDelegate, AbstractMAEnv):
+    """N == 1 drop-in with the reference's return types over a one-env `_BATCHED` engine."""
+    _BATCHED = None
+
+    def __init__(self, *args, **kwargs):
+        kwargs.pop("n_envs", None)
+        self._env = self._BATCHED(*args, n_envs=1, **kwargs)
+
+    @property
+    def agents(self):
+        return self._env.agents
+
+    @property
+    def reward_mech(self):
+        return self._env.reward_mech
+
+    @property
+    def timestep_limit(self):
+        return self._env.timestep_limit
+
+    def seed(self, seed=None):
+        return self._env.seed(seed)
+
+    def _obslist(self, obs):
+        o = obs[0].detach().cpu().numpy().astype(np.float64)
+        return [o[i] for i in range(o.shape[0])]
+
+    def reset(self):
+        return self._obslist(self._env.reset())
+
+    def _step(self, action):
+        """step() of a world, which keeps the reference's parameter name"""
+        a = np.asarray(action, dtype=np.float64).reshape((len(self._env.agents), 2))  # waterworld.py:221-222, hostage.py:229-230
+        obs, rew, done, info = self._env.step(a[None])
+        return (self._obslist(obs), rew[0].detach().cpu().numpy().astype(np.float64), bool(done[0].item()),
+                {k: int(info[k][0].item()) for k in self._env._INFO_KEYS})
+
+    @property
+    def is_terminal(self):
+        return bool(self._env.is_terminal[0].item())

@@ -1,0 +1,125 @@
+"""GPU tests (-m gpu): the host layer Waterworld and the hostage world share (madrl_amd/particle.py BatchedParticleWorld, the particle_*
+templates of csrc/common.hpp) serves both worlds: the fused StandardizedEnv binding follows seed() and a change of the agent count, the
+refusals keep their exception types, pickles keep their constructor dict, and the fused step equals step + epilogue kernels bit for bit."""
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+N = 8
+ALPHA, EPS, SCALE = 0.05, 1e-8, 0.7
+
+# (2 pursuers, 3 evaders, 2 poison, 4 sensors) and (2 rescuers, 3 hostages, 2 criminals, 4 sensors, n_coop_save = n_coop_avoid = 1)
+WORLDS = {"waterworld": dict(args=(2, 3), kw=dict(n_poison=2, n_sensors=4), count="n_pursuers"),
+          "hostage": dict(args=(2, 3, 2, 1, 1), kw=dict(n_sensors=4), count="n_good")}
+world = pytest.mark.parametrize("world", sorted(WORLDS))
+
+
+def _mk(world, **over):
+    from madrl_amd.hostage import BatchedContinuousHostageWorld
+    from madrl_amd.waterworld import BatchedMAWaterWorld
+    w = WORLDS[world]
+    kw = dict(n_envs=N, device=DEV, seed=4, **w["kw"])
+    kw.update(over)
+    return (BatchedMAWaterWorld if world == "waterworld" else BatchedContinuousHostageWorld)(*w["args"], **kw)
+
+
+def _actions(n_agents, steps=3):
+    g = torch.Generator(device="cpu").manual_seed(1)
+    return (torch.rand((steps, N, n_agents, 2), generator=g) * 2 - 1).to(DEV)
+
+
+@world
+def test_binding_follows_seed_and_agent_count_and_unbinds(world):
+    env = _mk(world)
+    st = env.bind_standardize(enable_obsnorm=True, enable_rewnorm=True)
+    held = dict(st)
+    assert env.seed(7) == [7]
+    assert env._std is st and set(st) == set(held) and all(st[k] is held[k] for k in held), "seed(): the same dict with the same tensors"
+    env.reset()
+    obs, rew, _, _ = env.step(_actions(2)[0])
+    assert obs is st["obs_out"] and rew is st["rew_out"]
+    env.set_param_values({WORLDS[world]["count"]: 3})
+    D = env.obs_dim
+    assert env._std is st, "a shape change re-fills the dict the wrapper holds"
+    assert tuple(st["obs_out"].shape) == tuple(st["obs_mean"].shape) == tuple(st["obs_var"].shape) == (N, 3, D)
+    assert tuple(st["rew_out"].shape) == tuple(st["rew_mean"].shape) == (N, 3)
+    assert bool((st["obs_var"] == 1).all()) and bool((st["obs_mean"] == 0).all()), "fresh statistics"
+    assert len(env.agents) == 3
+    env.reset()
+    obs, rew, _, _ = env.step(_actions(3)[0])
+    assert obs is st["obs_out"] and rew is st["rew_out"]
+    env.unbind_standardize()
+    assert env._std is None
+    assert env.reset() is env._obs
+    obs, rew, _, _ = env.step(_actions(3)[1])
+    assert obs is env._obs and rew is env._rew
+
+
+@world
+def test_refusals_and_what_only_one_world_has(world):
+    from madrl_amd import _lib
+    env = _mk(world)
+    env.bind_standardize(enable_obsnorm=True, enable_rewnorm=True)
+    env.reset()
+    act = _actions(2)[0]
+    with pytest.raises(ValueError):
+        env.step(act, obs_out=torch.zeros((N, 2, env.obs_dim), dtype=torch.float32, device=DEV))
+    assert env.step_on_stream(act.double(), torch.cuda.current_stream(DEV)) is None
+    assert env.step_on_stream(act, torch.cuda.current_stream(DEV)) is not None
+    crowd = _mk(world, crowd=True)
+    assert crowd.kernel_kind == "crowd" and env.kernel_kind == "wave" and not crowd.fused_standardize
+    with pytest.raises(_lib.MadrlError):
+        crowd.bind_standardize(enable_obsnorm=True, enable_rewnorm=True)
+    assert hasattr(env, "fused_standardize_pays") == (world == "hostage")
+    if world == "waterworld":
+        with pytest.raises(TypeError):
+            env.set_state(flags=torch.zeros(N, dtype=torch.uint8))
+
+
+@world
+def test_pickle_keeps_the_constructor_dict(world):
+    env, crowd = _mk(world), _mk(world, crowd=True)
+    assert "crowd" not in env.__getstate__() and crowd.__getstate__()["crowd"] is True
+    for e in (env, crowd):
+        twin = pickle.loads(pickle.dumps(e))
+        a, b = twin.__getstate__(), e.__getstate__()
+        assert set(a) == set(b)
+        for k in a:
+            assert np.array_equal(a[k], b[k]) if isinstance(b[k], np.ndarray) else a[k] == b[k], k
+        assert type(twin) is type(e) and twin.kernel_kind == e.kernel_kind
+
+
+@world
+def test_fused_step_equals_step_and_epilogue_kernels(world):
+    from madrl_amd import _lib
+    L = _lib.lib()
+    fused, plain = _mk(world), _mk(world)
+    st = fused.bind_standardize(scale_reward=SCALE, enable_obsnorm=True, enable_rewnorm=True, obs_alpha=ALPHA, rew_alpha=ALPHA, eps=EPS)
+    D = plain.obs_dim
+    f64 = dict(dtype=torch.float64, device=DEV)
+    om, ov, oo = torch.zeros((N, 2, D), **f64), torch.ones((N, 2, D), **f64), torch.zeros((N, 2, D), device=DEV)
+    rm, rv, ro = torch.zeros((N, 2), **f64), torch.ones((N, 2), **f64), torch.zeros((N, 2), device=DEV)
+    stream = _lib.current_stream(torch.device(DEV))
+
+    def obsnorm(obs):
+        _lib.check(L.madrl_wrap_obsnorm(_lib.ptr(obs), _lib.ptr(om), _lib.ptr(ov), _lib.ptr(oo), obs.numel(), obs.numel() // N, None, ALPHA, EPS,
+                                        stream))
+        return oo
+
+    def rewnorm(rew):
+        _lib.check(L.madrl_wrap_rewnorm(_lib.ptr(rew), _lib.ptr(rm), _lib.ptr(rv), _lib.ptr(ro), rew.numel(), rew.numel() // N, None, ALPHA, EPS,
+                                        SCALE, 1, stream))
+        return ro
+
+    assert torch.equal(fused.reset(), obsnorm(plain.reset())), "reset"
+    for t, act in enumerate(_actions(2)):
+        of, rf, df, inf = fused.step(act)
+        op, rp, dp, inp = plain.step(act)
+        assert torch.equal(of, obsnorm(op)) and torch.equal(rf, rewnorm(rp)) and torch.equal(df, dp), "step %d" % t
+        assert sorted(inf) == sorted(inp) and all(torch.equal(inf[k], inp[k]) for k in inf), "step %d" % t
+    for k, v in dict(obs_mean=om, obs_var=ov, rew_mean=rm, rew_var=rv).items():
+        assert torch.equal(st[k], v), k
