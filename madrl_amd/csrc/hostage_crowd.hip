@@ -1,14 +1,10 @@
-// hostage_crowd.hip -- ContinuousHostageWorld for envs beyond one wavefront's worth of particles (gfx950 / CDNA4), float32.
-//
-// hostage_kernel (hostage.hip) gives every particle a lane of ONE wavefront: at most 61 particles, 32 rescuers.  Here one WORKGROUP of NW
-// wavefronts owns an env at a time (persistent, striding over the envs) and its threads loop over the particles, the scheme of
-// ww_crowd_kernel (waterworld_crowd.hip).  Reached on request only (madrl_hostage_config.crowd = 1).  Limits:
+// hostage_crowd.hip -- ContinuousHostageWorld for envs beyond one wavefront's worth of particles (gfx950 / CDNA4), float32: hw_crowd_kernel,
+// one workgroup of NW wavefronts per env.  The scheme (phases, sensing passes, the ordered reach walk) and the code it shares with
+// ww_crowd_kernel are in particle_crowd.hpp; this file is the oracle's hw_step_env in its order.  Limits:
 //   n_good <= 128            a thread owns at most one rescuer
 //   n_hostages <= 64         the saved mask is one 64-bit word in the record, in get_state and in the oracle (64 itself works: "all saved" is ~0)
 //   at most 1 023 particles, n_sensors in 1..256, n_coop_save >= 1
-// The record is the one hostage_kernel reads and writes (the two kernels are interchangeable on one state buffer), and the results are
-// those of that kernel and of the float32 C restatement of the reference the tests use ("the oracle") bit for bit: every float expression
-// keeps the oracle's statement order, and whatever the oracle does in a loop whose order matters is done in that order here.
+// The record is the one hostage_kernel reads and writes (the two kernels are interchangeable on one state buffer).
 //
 // LDS (dynamic, hw_crowd_lds_bytes; about 35 KB at the limits, 2 KB at 20 / 30 / 40):
 //   S     the packed state record  X[NP][2] | V[NP][2] | key[2] | bomb[2] | saved_lo saved_hi | flags | t | tick     (<= 16 KB)
@@ -16,27 +12,10 @@
 //   ACT   the scaled actions [Nr][2]: the global control penalty sums them row-major
 //   COL   collision bits, per rescuer one 64-bit word for the hostages and one per chunk of 64 criminals   (<= 14 KB)
 //   CAU / ENC   ho_caught | cr_caught bits per chunk / ho_enc bits;  KEB / BOB   key / bomb contact bit per rescuer
-// The observation row is NOT staged: a (rescuer, sensor) lane stores its five features straight to global memory; for a fixed rescuer and
-// feature the K sensor values are contiguous, so the lanes of a rescuer write whole runs.
-//
-// Phases of a step, a workgroup barrier between them, in the order of the oracle's hw_step_env (reference lines: hostage.py, as in hostage.hip):
-//   A   thread = rescuer: actions, integration, walls, closed gate (G3), key / bomb contact                :231-260, :281-291
-//   B1  wavefront = (rescuer, chunk of 64 objects), lane = object: contact test, ballot -> COL             :263-279 (G4: no saved mask)
-//   B2  wavefront = chunk, lane = object: column count over the rescuers -> CAU / ENC                     _caught :184-198
-//       thread = rescuer: contact flags, gate state and id of the observation row, the reward (G6, G9)    :385-396, :410-430
-//   C   wavefront = pass of (rescuer, sensor) lanes: ray tests, features to global (G1, G5)               :295-362, :398-400
-//   E   thread = criminal: respawn if caught, then motion (G7)                                            :365-383, :402-408
-// What the processing of :365-383 decides (saved mask, gate, bombed, done) is known after B2, before anything reads it.  Sensing is the
-// bulk.  A pass holds floor(64 / K) whole rescuers (K > 64: 64 sensors of one rescuer).  Per class and chunk of 64 objects the lanes test
-// which objects are within reach of a rescuer of the pass (the conservative predicate of hostage.hip), one ballot makes that a
-// wave-uniform mask, and its set bits are walked in ascending order -- the oracle's index order, so the running minimum with a strict `<`
-// is the oracle's first minimum.  The objects out of reach would yield +inf and are skipped.  Key and bomb are single objects.
-//
-// Known costs, as in ww_crowd_kernel: the next env's record is not fetched ahead, and the launch parameters are held in registers across
-// the env loop instead of being read through kernargs<>() where a phase needs them.
+// The observation row is NOT staged.  Reference lines (:n) are hostage.py's, as in hostage.hip.  What the processing of :365-383 decides
+// (saved mask, gate, bombed, done) is known after B2, before anything reads it.
+#include "particle_crowd.hpp"
 #include "hostage_dev.hpp"
-
-#include <math.h>
 
 // wavefronts per workgroup (a profiling variant builds the other value: scripts/hostage_crowd_time.py)
 #ifndef MADRL_HWC_NW
@@ -46,8 +25,6 @@
 namespace {
 
 using namespace madrl;
-
-__host__ __device__ inline int up4(int v) { return (v + 3) & ~3; }
 
 // MODE 0: reset(mask)   MODE 1: step (+ fused auto-reset)
 template <int MODE, int NW>
@@ -74,14 +51,9 @@ __global__ __launch_bounds__(64 * NW) void hw_crowd_kernel(const HwDev d, const 
 
     for (int k = tid; k < 2 * K; k += NT) SEN[k] = d.sensors[k];
 
-    // the lanes of a sensing pass: PPP whole rescuers of K sensors (K <= 64), or one chunk of 64 sensors of one rescuer
-    const int PPP = K <= 64 ? 64 / K : 1, KC = K <= 64 ? 1 : (K + 63) >> 6;
-    const int li = K <= 64 ? lane / K : 0;
-    const int n_pass = ((Nr + PPP - 1) / PPP) * KC;
+    const PassShape passes = pass_shape(K, Nr, lane);
     const float srange = d.sensor_range, rad2 = d.radius * d.radius;  // G1: the SENSING rescuer's radius
-    // a sensor of rescuer i can only return a finite value for an object with d2 <= rad2 + sv^2 <= rad2 + range^2 (plus a relative margin
-    // far above the rounding of the test itself): everything else yields +inf in the oracle and never becomes a minimum
-    const float reach2 = (rad2 + srange * srange) * 1.0001f + 1e-9f;
+    const float reach2 = sensor_reach2(rad2, srange);
     const int limit = d.max_steps > 0 ? d.max_steps : 1000;  // timestep_limit :118-120
     const uint64_t all_h = Nh >= 64 ? ~0ull : ((1ull << Nh) - 1ull);
     const int n_envs = (int)d.n_envs;
@@ -145,26 +117,11 @@ __global__ __launch_bounds__(64 * NW) void hw_crowd_kernel(const HwDev d, const 
                 bool col_bo = false, col_ke = false;
                 if (tid < Nr) {
                     const int i = tid;
-                    float r0 = 0.0f, r1 = 0.0f;
-                    if (live) {
-                        const float *a = io.actions + (env * Nr + i) * 2;
-                        r0 = a[0];
-                        r1 = a[1];
-                    }
-                    const float a0 = r0 * d.action_scale, a1 = r1 * d.action_scale;  // :231
-                    ACT[2 * i] = a0;
-                    ACT[2 * i + 1] = a1;
                     float x = X[2 * i], y = X[2 * i + 1], vx = V[2 * i], vy = V[2 * i + 1];
-                    vx = vx + a0; vy = vy + a1;  // :236-238
-                    x = x + vx; y = y + vy;
-                    float cx = x < 0.f ? 0.f : (x > 1.f ? 1.f : x);  // walls :247-252
-                    float cy = y < 0.f ? 0.f : (y > 1.f ? 1.f : y);
-                    if (x != cx) vx = 0.f;
-                    if (y != cy) vy = 0.f;
-                    x = cx; y = cy;
+                    drive_agent(live, io.actions, env * Nr + i, d.action_scale, ACT, i, x, y, vx, vy);  // :231, :236-238, walls :247-252
                     if (!gate0) {  // G3: both coordinates, velocity component flipped (:255-260)
-                        cx = x < d.gate_lo ? d.gate_lo : (x > 1.f ? 1.f : x);
-                        cy = y < d.gate_lo ? d.gate_lo : (y > 1.f ? 1.f : y);
+                        const float cx = x < d.gate_lo ? d.gate_lo : (x > 1.f ? 1.f : x);
+                        const float cy = y < d.gate_lo ? d.gate_lo : (y > 1.f ? 1.f : y);
                         if (x != cx) vx *= -1.f;
                         if (y != cy) vy *= -1.f;
                         x = cx; y = cy;
@@ -179,30 +136,11 @@ __global__ __launch_bounds__(64 * NW) void hw_crowd_kernel(const HwDev d, const 
                 }
             }
             __syncthreads();
-            // phase B1: collisions (:263-279), saved hostages included (G4).  Bits past the end of a class stay 0.
-            for (int i = wave; i < Nr; i += NW) {
-                const float pix = X[2 * i], piy = X[2 * i + 1];
-                for (int c = 0; c < W; ++c) {
-                    const bool is_ho = c == 0;
-                    const int m = (is_ho ? 0 : c - 1) * 64 + lane;
-                    const bool in = m < (is_ho ? Nh : Nc);
-                    const int j = (is_ho ? Nr : Nr + Nh) + (in ? m : 0);
-                    const uint64_t hit = __ballot(in && dist2_le(pix, piy, X[2 * j], X[2 * j + 1], is_ho ? d.sq_hit_ho : d.sq_hit_cr));
-                    if (lane == 0) COL[i * W + c] = hit;
-                }
-            }
+            // phase B1: collisions (:263-279), saved hostages included (G4)
+            contact_ballots<NW>(X, COL, Nr, W, 1, {Nr, Nh, d.sq_hit_ho}, {Nr + Nh, Nc, d.sq_hit_cr}, wave, lane);
             __syncthreads();
-            // phase B2: _caught (:184-198): an object counts its column
-            for (int c = wave; c < W; c += NW) {
-                int s = 0;
-                for (int i = 0; i < Nr; ++i) s += (int)((COL[i * W + c] >> lane) & 1ull);
-                const uint64_t cm = __ballot(s >= (c == 0 ? d.n_coop_save : 1));
-                const uint64_t em = __ballot(s >= 1);
-                if (lane == 0) {
-                    CAU[c] = cm;
-                    if (c == 0) ENC[0] = em;
-                }
-            }
+            // phase B2: _caught (:184-198)
+            column_counts<NW>(COL, CAU, ENC, Nr, W, 1, d.n_coop_save, wave, lane);
             __syncthreads();
             // what the processing of :365-383 will decide
             const uint64_t ho_caught = CAU[0];
@@ -241,13 +179,8 @@ __global__ __launch_bounds__(64 * NW) void hw_crowd_kernel(const HwDev d, const 
                 }
                 if (live) {
                     float reward;
-                    if (d.reward_global) {  // (actions**2).sum(), row-major (:241-242): summed in that order, not as a tree
-                        float s = 0.0f;
-                        for (int q = 0; q < Nr; ++q) {
-                            const float b0 = ACT[2 * q], b1 = ACT[2 * q + 1];
-                            s += b0 * b0;
-                            s += b1 * b1;
-                        }
+                    if (d.reward_global) {  // (actions**2).sum(), row-major (:241-242)
+                        const float s = control_sum(ACT, Nr);
                         reward = 0.0f + d.control_penalty * s;
                         reward += ((((float)n_ho_enc * d.encounter_reward) * gate1 + (float)n_ho_caught * d.save_reward) +
                                    (float)n_cr_caught * d.hit_reward) + bombed1 * d.bomb_reward;
@@ -265,75 +198,36 @@ __global__ __launch_bounds__(64 * NW) void hw_crowd_kernel(const HwDev d, const 
             }
             // phase C: sensing (:295-362).  Rows: [criminal dist | criminal speed | hostage dist | key dist | bomb dist] (:398-400)
             if (emit) {
-                for (int p = wave; p < n_pass; p += NW) {
-                    const int ig = KC == 1 ? p : p / KC, kc = p - ig * KC;
-                    const int i_first = ig * PPP, i_cnt = min(PPP, Nr - i_first);  // the rescuers of this pass
-                    const int k0 = K <= 64 ? lane - li * K : kc * 64 + lane;
-                    const bool okq = li < i_cnt && k0 < K;   // lanes without a (rescuer, sensor) pair compute along and store nothing
-                    const int iq = i_first + (okq ? li : 0), kq = okq ? k0 : 0;
-                    const float sxq = SEN[2 * kq], syq = SEN[2 * kq + 1];
-                    const float pxq = X[2 * iq], pyq = X[2 * iq + 1], pvx = V[2 * iq], pvy = V[2 * iq + 1];
-                    float *const o = orow_env + (int64_t)iq * D + kq;
-                    float b = INFINITY;
-                    int bi = 0;  // the first minimum of an all-inf row is 0
-                    auto visit = [&](int m, float qx, float qy) {
-                        const float rx = qx - pxq, ry = qy - pyq;
-                        const float sv = sxq * rx + syq * ry;  // sensors.dot(relpos.T) :67
-                        const float d2 = rx * rx + ry * ry;
-                        // sv < 0 || sv > srange as ONE compare: the median of (sv, 0, srange) is sv exactly when 0 <= sv <= srange (hostage.hip)
-                        const bool out = (__builtin_amdgcn_fmed3f(sv, 0.f, srange) != sv) | (d2 - sv * sv > rad2);
-                        // an excluded ray is +inf in the reference and never "better"; a kept one is when it is smaller: first minimum
-                        const bool better = !out & (sv < b);
-                        b = better ? sv : b;
-                        bi = better ? m : bi;
-                    };
-                    // cls 0: criminals; cls 1: hostages, the saved ones (mask from before this step, G5, :296) not sensed
-                    auto walk = [&](int lo, int cnt, bool hostages) {
-                        for (int base = 0; base < cnt; base += 64) {
-                            const int m = base + lane;
-                            const bool in = m < cnt;
-                            const float2 mp = *reinterpret_cast<const float2 *>(&X[2 * (lo + (in ? m : 0))]);
-                            bool near = false;
-                            for (int q = 0; q < i_cnt; ++q) {
-                                const float2 pp = *reinterpret_cast<const float2 *>(&X[2 * (i_first + q)]);
-                                const float rx = mp.x - pp.x, ry = mp.y - pp.y;
-                                near |= rx * rx + ry * ry <= reach2;
-                            }
-                            uint64_t todo = __ballot(in && near);  // wave-uniform: the objects of this chunk within reach of the pass
-                            if (hostages) todo &= ~saved0;
-#pragma nounroll
-                            while (todo != 0ull) {
-                                const int m2 = base + __builtin_ctzll(todo);
-                                todo &= todo - 1ull;
-                                const float2 qp = *reinterpret_cast<const float2 *>(&X[2 * (lo + m2)]);  // uniform address: a broadcast
-                                visit(m2, qp.x, qp.y);
-                            }
-                        }
-                    };
-                    walk(Nr + Nh, Nc, false);
+                for (int p = wave; p < passes.n_pass; p += NW) {
+                    const PassLanes L = pass_lanes(passes, p, K, Nr, lane);  // the rescuers of this pass
+                    Ray ray(SEN, X, V, L.iq, L.kq, srange, rad2);
+                    float *const o = orow_env + (int64_t)L.iq * D + L.kq;
+                    auto visit = [&](int m, float qx, float qy) { ray.visit(m, qx, qy); };
+                    reach_walk(X, Nr + Nh, Nc, L, reach2, 0ull, lane, visit);  // criminals
                     {
-                        const bool fin = b < INFINITY;
-                        const int j = Nr + Nh + bi;  // (bi = 0 without a hit: a valid particle, its value is not used)
-                        const float raw = sxq * (V[2 * j] - pvx) + syq * (V[2 * j + 1] - pvy);  // :204-226
-                        if (okq) {
-                            o[0] = fin ? b : 0.f;
+                        const bool fin = ray.b < INFINITY;
+                        const int j = Nr + Nh + ray.bi;  // (bi = 0 without a hit: a valid particle, its value is not used)
+                        const float raw = ray.speed_along(V, j);  // :204-226
+                        if (L.okq) {
+                            o[0] = fin ? ray.b : 0.f;
                             o[K] = fin ? raw : 0.f;
                         }
                     }
-                    b = INFINITY;
-                    if (gate0) walk(Nr, Nh, true);  // (workgroup-uniform: behind the closed gate the feature is 0 whatever is sensed, :320-322)
-                    if (okq) o[2 * K] = (gate0 && b < INFINITY) ? b : 0.f;
-                    b = INFINITY;
-                    if (!gate0) visit(0, kx, ky);   // :338-340
-                    if (okq) o[3 * K] = (!gate0 && b < INFINITY) ? b : 0.f;
-                    b = INFINITY;
-                    visit(0, bx, by);
-                    if (okq) o[4 * K] = (b < INFINITY) ? b : 0.f;
+                    ray.restart();
+                    // hostages: the saved ones (mask from before this step, G5, :296) are not sensed.  (gate0 is workgroup-uniform: behind
+                    // the closed gate the feature is 0 whatever is sensed, :320-322)
+                    if (gate0) reach_walk(X, Nr, Nh, L, reach2, saved0, lane, visit);
+                    if (L.okq) o[2 * K] = (gate0 && ray.b < INFINITY) ? ray.b : 0.f;
+                    ray.restart();
+                    if (!gate0) ray.visit(0, kx, ky);   // :338-340
+                    if (L.okq) o[3 * K] = (!gate0 && ray.b < INFINITY) ? ray.b : 0.f;
+                    ray.restart();
+                    ray.visit(0, bx, by);
+                    if (L.okq) o[4 * K] = (ray.b < INFINITY) ? ray.b : 0.f;
                 }
             }
             __syncthreads();  // sensing read the positions of this step: respawn and motion come after it
-            // phase E: respawn caught criminals (:371-374), then criminals move; the velocity flips only if BOTH coordinates left [0,1], no
-            // clipping (G7, :402-408)
+            // phase E: respawn caught criminals (:371-374), then criminals move (G7, :402-408)
             for (int m = tid; m < Nc; m += NT) {
                 const int j = Nr + Nh + m;
                 float x = X[2 * j], y = X[2 * j + 1], vx = V[2 * j], vy = V[2 * j + 1];
@@ -349,9 +243,7 @@ __global__ __launch_bounds__(64 * NW) void hw_crowd_kernel(const HwDev d, const 
                     vx = (u0 - 0.5f) * d.bad_speed;
                     vy = (u1 - 0.5f) * d.bad_speed;
                 }
-                x = x + vx; y = y + vy;
-                const bool outx = !(x >= 0.f && x <= 1.f), outy = !(y >= 0.f && y <= 1.f);
-                if (outx && outy) { vx = -1.0f * vx; vy = -1.0f * vy; }
+                free_motion(x, y, vx, vy);
                 X[2 * j] = x; X[2 * j + 1] = y; V[2 * j] = vx; V[2 * j + 1] = vy;
             }
             tick += 1;
@@ -390,14 +282,9 @@ size_t hw_crowd_lds_bytes(int Nr, int Nh, int Nc, int K, int rec_dw) {
     return ((size_t)up4(rec_dw) + up4(2 * K) + up4(2 * Nr)) * 4 + ((size_t)Nr * W + W + 1 + 2 + 2) * 8;
 }
 
-int hw_crowd_launch(const void *dev, const void *io_, int mode, int64_t max_blocks, size_t lds_bytes, void *stream) {
-    const HwDev &d = *static_cast<const HwDev *>(dev);
-    const HwIO &io = *static_cast<const HwIO *>(io_);
-    const dim3 g = particle_grid(max_blocks, d.n_envs), b(64 * MADRL_HWC_NW);
-    if (mode == 0) hipLaunchKernelGGL((hw_crowd_kernel<0, MADRL_HWC_NW>), g, b, lds_bytes, (hipStream_t)stream, d, io);
-    else hipLaunchKernelGGL((hw_crowd_kernel<1, MADRL_HWC_NW>), g, b, lds_bytes, (hipStream_t)stream, d, io);
-    MADRL_HIP_TRY(hipGetLastError());
-    return MADRL_OK;
+int hw_crowd_launch(const void *dev, const void *io, int mode, int64_t max_blocks, size_t lds_bytes, void *stream) {
+    return crowd_launch<HwDev, HwIO>(mode == 0 ? hw_crowd_kernel<0, MADRL_HWC_NW> : hw_crowd_kernel<1, MADRL_HWC_NW>, MADRL_HWC_NW, dev, io,
+                                     max_blocks, lds_bytes, stream);
 }
 
 }  // namespace madrl
