@@ -300,6 +300,26 @@ int madrl_waterworld_set_launch(madrl_waterworld *h, int64_t max_blocks);
 /* which kernel the handle runs: 0 = one wavefront per env, 1 = the crowd kernel (cfg.crowd) */
 int madrl_waterworld_kernel_kind(madrl_waterworld *h, int32_t *out);
 
+/* Per-env particle counts on the crowd kernel (a curriculum over agent counts without re-creating the handle; the Waterworld form of
+ * madrl_pursuit_set_agent_counts).  With both arrays bound the config's n_pursuers / n_evaders / n_poison are a CAPACITY (Pcap, Ecap,
+ * POcap) -- for madrl_waterworld_state_bytes, the LDS size and the limits of 128 pursuers and 1 023 particles as well -- and every env
+ * has LIVE counts 1 <= p <= Pcap, 1 <= e <= Ecap, 1 <= po <= POcap.  Each reset of an env -- reset(), reset(mask) for the envs in the
+ * mask, the fused auto-reset of a step -- takes its PENDING counts, clamped to those ranges, and writes them to live_dev; the running
+ * episode keeps its particles.  An env at live (p, e, po) computes bit for bit what env n of a fixed-shape (p, e, po) crowd batch with
+ * the same seed and env_id_base + n computes: observation rows and rewards < p, done, info, the particles that exist, the obstacle, t
+ * and tick (the Philox particle index is the index in the live class order).
+ * Layouts stay at the capacity, slotted by class: pursuer i at slot i, evader m at Pcap + m, poison m at Pcap + Ecap + m, in the state
+ * record, in get_state / set_state and in the rows of inj_respawn_dev.  Actions [N][Pcap][2]: rows >= p are ignored.  Rewards
+ * [N][Pcap]: rows >= p are written as 0.  Observations [N][Pcap][obs_dim]: rows >= p are written as +0.0 whenever the env's rows are
+ * written.  The record layout and madrl_waterworld_state_bytes do not change; a slot that does not exist holds position (-1, -1) and
+ * velocity (0, 0) once a launch has stored the env's record.
+ *   pending_dev  const int32 [n_envs][3] (pursuers, evaders, poison), caller-owned, read by resets
+ *   live_dev     int32 [n_envs][3], caller-owned, read and written by the kernels (values outside the ranges are read clamped); the
+ *                caller fills it before the first launch: the capacity -- or, with a restored set_state, the counts of that state
+ * Both stay valid while bound and may be rewritten between launches.  Both NULL turns the mode off (meaningful only while every env is
+ * at its capacity); one NULL: MADRL_EINVAL.  A handle with cfg.crowd == 0: MADRL_EINVAL. */
+int madrl_waterworld_set_particle_counts(madrl_waterworld *h, const int32_t *pending_dev, int32_t *live_dev);
+
 /* Fused StandardizedEnv (madrl_environments/__init__.py:204-311): bind the wrapper's state to the env handle and the step /
  * reset kernels normalise the observation row as it leaves LDS (and the rewards as they are produced) instead of storing it
  * raw for a second launch (madrl_wrap_obsnorm / _rewnorm) to read back: 36 instead of 44 bytes of HBM traffic per observation

@@ -619,7 +619,10 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
 
 }  // namespace
 // =================================================================== host side / C ABI
-struct madrl_waterworld : ParticleHandle<madrl_waterworld_config, WwDev> {};
+struct madrl_waterworld : ParticleHandle<madrl_waterworld_config, WwDev> {
+    const int32_t *pending;  // madrl_waterworld_set_particle_counts: caller-owned [n_envs][3], both NULL = one shape for all envs
+    int32_t *live;
+};
 
 namespace {
 
@@ -709,7 +712,7 @@ const WwSpec WW_SPECS[] = {
 int ww_launch(const madrl_waterworld *h, const WwIO &io, int mode, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     const WwDev &d = h->dev;
-    if (h->cfg.crowd) return ww_crowd_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, stream);
+    if (h->cfg.crowd) return ww_crowd_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, h->pending, h->live, stream);
     const dim3 g = particle_grid(h->max_blocks, d.n_envs), b(64);
     const bool fused = io.st != nullptr;
     const WwSpec *spec = nullptr;
@@ -782,6 +785,16 @@ void madrl_waterworld_destroy(madrl_waterworld *h) { particle_destroy(h); }
 int madrl_waterworld_set_standardize(madrl_waterworld *h, const madrl_standardize_args *a) { return particle_set_standardize(h, a); }
 
 int madrl_waterworld_set_launch(madrl_waterworld *h, int64_t max_blocks) { return particle_set_launch(h, max_blocks); }
+
+int madrl_waterworld_set_particle_counts(madrl_waterworld *h, const int32_t *pending_dev, int32_t *live_dev) {
+    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
+    if (!h->cfg.crowd) return fail(MADRL_EINVAL, "set_particle_counts: per-env particle counts run on the crowd kernel (cfg.crowd = 1)");
+    if ((pending_dev == nullptr) != (live_dev == nullptr))
+        return fail(MADRL_EINVAL, "set_particle_counts: pending_dev and live_dev are both arrays or both NULL");
+    h->pending = pending_dev;
+    h->live = live_dev;
+    return MADRL_OK;
+}
 
 int madrl_waterworld_reset(madrl_waterworld *h, const uint8_t *mask_dev, float *obs_dev, void *stream) {
     return particle_reset(h, mask_dev, obs_dev, stream, ww_launch);

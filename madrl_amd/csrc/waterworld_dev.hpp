@@ -45,8 +45,10 @@ struct WwIO {
 
 namespace madrl {
 
-// waterworld_crowd.hip.  dev / io: a WwDev and a WwIO (see the note at the top); mode 0 = reset, 1 = step.
-int ww_crowd_launch(const void *dev, const void *io, int mode, int64_t max_blocks, size_t lds_bytes, void *stream);
+// waterworld_crowd.hip.  dev / io: a WwDev and a WwIO (see the note at the top); mode 0 = reset, 1 = step.  live != NULL: the per-env
+// particle counts of madrl_waterworld_set_particle_counts (the kernels' live-count instantiations), the shape of dev being the capacity.
+int ww_crowd_launch(const void *dev, const void *io, int mode, int64_t max_blocks, size_t lds_bytes, const int32_t *pending, int32_t *live,
+                    void *stream);
 // the dynamic LDS of one ww_crowd_kernel workgroup
 size_t ww_crowd_lds_bytes(int n_pursuers, int n_evaders, int n_poison, int n_sensors, int rec_dw);
 

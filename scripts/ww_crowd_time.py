@@ -1,7 +1,8 @@
 """Step time of the Waterworld crowd kernel (csrc/waterworld_crowd.hip, `crowd=True`) at shapes beyond one wavefront's worth of particles.
 
     python scripts/ww_crowd_time.py                      # the table of DESIGN 4.4a: every row below, three processes each, min - max
-    python scripts/ww_crowd_time.py --rows shapes,cpu    # some of: shapes, cpu, wave, nw8
+    python scripts/ww_crowd_time.py --rows shapes,cpu    # some of: shapes, cpu, wave, nw8, live
+    python scripts/ww_crowd_time.py --live               # the table of DESIGN 4.4b: the `live` row alone
 
 Rows
   shapes  20/60/40, 33/100/100 and 128/512/383 with 30 sensors, at 4 096 envs and at the largest batch whose observations fit 16 GB:
@@ -10,6 +11,9 @@ Rows
   wave    crowd kernel against the one-wavefront generic instantiation at 12/25/25 (16 sensors), 32 768 envs
   nw8     eight instead of four wavefronts per workgroup on the first two shapes: needs the variant library
           `SRC=waterworld_crowd MACRO=MADRL_WWC_NW scripts/variants.sh 8` builds (scripts/_variants/, git-ignored)
+  live    per-env particle counts (per_env_counts=True) at the capacities 20/60/40 and 33/100/100, 4 096 envs: the fixed-shape kernel, the
+          live-count kernel with every env at the capacity, and with every env's triple drawn uniformly between (1, 1, 1) and the capacity
+          -- the three alternating, three processes each (ray tests/s of the spread row are counted at the capacity: compare its us)
 
 Steady state with auto_reset (max_steps 500), after an untimed warm-up; device events around the launches alone.  One measurement per
 process (`--one ...`, what the parent starts), one process at a time.
@@ -37,14 +41,18 @@ def largest_batch(shape):
     return int(OBS_BYTES // (Np * obs_dim(K) * 4)) // 1024 * 1024
 
 
-def one(shape, N, crowd):
-    """one measurement in this process -> a JSON line"""
+def one(shape, N, crowd, live=0):
+    """one measurement in this process -> a JSON line.  live: 0 fixed shape, 1 per-env counts at the capacity, 2 a spread of counts"""
     import torch
     from madrl_amd import _lib
     from madrl_amd.waterworld import BatchedMAWaterWorld
     Np, Ne, Npo, K = SHAPES[shape]
     dev = torch.device("cuda:0")
-    env = BatchedMAWaterWorld(Np, Ne, n_poison=Npo, n_sensors=K, n_envs=N, device=dev, seed=0, max_steps=500, auto_reset=True, crowd=bool(crowd))
+    env = BatchedMAWaterWorld(Np, Ne, n_poison=Npo, n_sensors=K, n_envs=N, device=dev, seed=0, max_steps=500, auto_reset=True, crowd=bool(crowd),
+                              per_env_counts=bool(live))
+    if live == 2:
+        g = torch.Generator().manual_seed(0)
+        env.set_particle_counts(*[torch.randint(1, c + 1, (N,), generator=g) for c in (Np, Ne, Npo)])
     acts = [torch.rand(N, Np, 2, device=dev) * 2 - 1 for _ in range(8)]
     env.reset()
     L = _lib.lib()
@@ -63,7 +71,7 @@ def one(shape, N, crowd):
     us = timed(10)
     steps = int(min(300, max(20, 1.0e6 / us)))   # about a second of launches
     us = timed(steps)
-    print(json.dumps(dict(shape=shape, n_envs=N, kernel=env.kernel_kind, us_per_launch=us, env_steps_per_s=N / us * 1e6,
+    print(json.dumps(dict(shape=shape, n_envs=N, kernel=env.kernel_kind + ("", "-live", "-live-spread")[live], us_per_launch=us, env_steps_per_s=N / us * 1e6,
                           ray_tests_per_s=N * Np * K * (Np + Ne + Npo) / us * 1e6, steps=steps)), flush=True)
 
 
@@ -83,17 +91,19 @@ def cpu(shape):
     return dict(shape=shape, n_envs=N, env_steps_per_s=N * n / dt, threads=int(os.environ.get("OMP_NUM_THREADS", 0)) or os.cpu_count())
 
 
-def child(shape, N, crowd, lib=None):
+def measure(shape, N, crowd, lib=None, live=0):
     env = dict(os.environ)
     if lib:
         env["MADRL_HIP_LIB"] = lib
-    rs = []
-    for _ in range(3):
-        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", shape, str(N), str(int(crowd))], env=env, capture_output=True,
-                             text=True, timeout=600)
-        if out.returncode != 0:
-            raise SystemExit("measurement %s N=%d crowd=%d failed (%d):\n%s" % (shape, N, crowd, out.returncode, out.stderr[-2000:]))
-        rs.append(json.loads(out.stdout.strip().splitlines()[-1]))
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", shape, str(N), str(int(crowd)), str(live)], env=env,
+                         capture_output=True, text=True, timeout=600)
+    if out.returncode != 0:
+        raise SystemExit("measurement %s N=%d crowd=%d live=%d failed (%d):\n%s" % (shape, N, crowd, live, out.returncode, out.stderr[-2000:]))
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def child(shape, N, crowd, lib=None, rs=None):
+    rs = rs or [measure(shape, N, crowd, lib) for _ in range(3)]
     us = [r["us_per_launch"] for r in rs]
     lo, hi = min(us), max(us)
     r = rs[0]
@@ -107,8 +117,8 @@ def child(shape, N, crowd, lib=None):
 def main():
     argv = sys.argv[1:]
     if argv[:1] == ["--one"]:
-        return one(argv[1], int(argv[2]), int(argv[3]))
-    rows = argv[argv.index("--rows") + 1].split(",") if "--rows" in argv else ["shapes", "cpu", "wave", "nw8"]
+        return one(argv[1], int(argv[2]), int(argv[3]), int(argv[4]) if len(argv) > 4 else 0)
+    rows = argv[argv.index("--rows") + 1].split(",") if "--rows" in argv else ["live"] if "--live" in argv else ["shapes", "cpu", "wave", "nw8"]
     big = ("20/60/40", "33/100/100", "128/512/383")
     if "shapes" in rows:
         for s in big:
@@ -129,6 +139,15 @@ def main():
             for N in (4096, largest_batch(s)):
                 child(s, N, True)
                 child(s, N, True, lib=NW8_LIB)
+    if "live" in rows:
+        for s in big[:2]:
+            runs = [[], [], []]
+            for _ in range(3):   # fixed, live at the capacity, live spread: alternating
+                for live in range(3):
+                    runs[live].append(measure(s, 4096, True, live=live))
+            (f0, f1), (l0, l1), (s0, s1) = [child(s, 4096, True, rs=r) for r in runs]
+            print("%s at 4 096 envs: live at the capacity / fixed = %.3f - %.3f, spread / live at the capacity = %.3f - %.3f" % (
+                s, l0 / f1, l1 / f0, s0 / l1, s1 / l0), flush=True)
 
 
 if __name__ == "__main__":
