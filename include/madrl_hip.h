@@ -395,6 +395,30 @@ void madrl_hostage_destroy(madrl_hostage *h);
 int madrl_hostage_set_launch(madrl_hostage *h, int64_t max_blocks);
 /* which kernel the handle runs: 0 = one wavefront per env, 1 = the crowd kernel (cfg.crowd) */
 int madrl_hostage_kernel_kind(madrl_hostage *h, int32_t *out);
+
+/* Per-env particle counts on the crowd kernel (a curriculum over n_good / n_hostages / n_bad without re-creating the handle; the hostage
+ * form of madrl_waterworld_set_particle_counts).  With both arrays bound the config's n_good / n_hostages / n_bad are a CAPACITY (Rcap,
+ * Hcap, Ccap) -- for madrl_hostage_state_bytes, the LDS size and the limits of 128 rescuers, 64 hostages and 1 023 particles as well --
+ * and every env has LIVE counts 1 <= r <= Rcap, 1 <= h <= Hcap, 1 <= c <= Ccap.  Each reset of an env -- reset(), reset(mask) for the
+ * envs in the mask, the fused auto-reset of a step -- takes its PENDING counts, clamped to those ranges, before its draws, and writes
+ * them to live_dev; the running episode keeps its particles.  An env at live (r, h, c) computes bit for bit what env n of a fixed-shape
+ * (r, h, c) crowd batch with the same seed and env_id_base + n computes: observation rows and rewards < r, done, info, the particles
+ * that exist, key, bomb, saved mask, flags, t and tick.  What depends on the counts follows the live ones: the reset's Philox indices
+ * (key 0, particle j of the live class order 1 + j, bomb 1 + r + h + c; a respawning criminal m: m), "all saved" (the low h bits of
+ * the mask; bit m is hostage m and bits >= h are never set), the not_saved_reward term (h - popcount(saved)) and the global control
+ * penalty (the r live action rows).  The key is drawn at the env's first reset and kept across count changes.  n_coop_save > r is
+ * legal, as on a fixed batch: such an env saves nobody.
+ * Layouts stay at the capacity, slotted by class: rescuer i at slot i, hostage m at Rcap + m, criminal m at Rcap + Hcap + m, in the
+ * state record and in get_state / set_state.  inj_respawn_dev stays [N][Ccap][4], criminal m at row m.  Actions [N][Rcap][2]: rows >= r
+ * are ignored.  Rewards [N][Rcap]: rows >= r are written as 0.  Observations [N][Rcap][obs_dim]: rows >= r are written as +0.0 whenever
+ * the env's rows are written.  The record layout and madrl_hostage_state_bytes do not change; a slot that does not exist holds
+ * position (-1, -1) and velocity (0, 0) once a launch has stored the env's record.
+ *   pending_dev  const int32 [n_envs][3] (good, hostages, bad), caller-owned, read by resets
+ *   live_dev     int32 [n_envs][3], caller-owned, read and written by the kernels (values outside the ranges are read clamped); the
+ *                caller fills it before the first launch: the capacity -- or, with a restored set_state, the counts of that state
+ * Both stay valid while bound and may be rewritten between launches.  Both NULL turns the mode off (meaningful only while every env is
+ * at its capacity); one NULL: MADRL_EINVAL.  A handle with cfg.crowd == 0: MADRL_EINVAL. */
+int madrl_hostage_set_particle_counts(madrl_hostage *h, const int32_t *pending_dev, int32_t *live_dev);
 /* Fused StandardizedEnv, as madrl_waterworld_set_standardize above (same madrl_standardize_args, A = n_good): the step / reset
  * kernels of the one-wavefront handle standardise the observation row as it leaves LDS and write the scaled / normalised rewards
  * themselves, bit for bit what madrl_wrap_obsnorm / madrl_wrap_rewnorm compute from the raw outputs.  reset(mask) leaves the

@@ -127,6 +127,7 @@ SIGNATURES = {
     "madrl_hostage_destroy": (None, [_vp]),
     "madrl_hostage_set_launch": (C.c_int, [_vp, C.c_int64]),
     "madrl_hostage_kernel_kind": (C.c_int, [_vp, _vp]),
+    "madrl_hostage_set_particle_counts": (C.c_int, [_vp, _vp, _vp]),
     "madrl_hostage_set_standardize": (C.c_int, [_vp, _vp]),
     "madrl_hostage_reset": (C.c_int, [_vp] * 4),
     "madrl_hostage_step": (C.c_int, [_vp] * 8),

@@ -575,7 +575,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
 }  // namespace
 
 // =================================================================== host side / C ABI
-struct madrl_hostage : ParticleHandle<madrl_hostage_config, HwDev> {};
+struct madrl_hostage : ParticleHandle<madrl_hostage_config, HwDev> {
+    const int32_t *pending;  // madrl_hostage_set_particle_counts: caller-owned [n_envs][3], both NULL = one shape for all envs
+    int32_t *live;
+};
 
 namespace {
 
@@ -642,7 +645,7 @@ size_t hw_lds_bytes_crowd(const HwDev &d) { return hw_crowd_lds_bytes(d.Nr, d.Nh
 int hw_launch(const madrl_hostage *h, const HwIO &io, int mode, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     const HwDev &d = h->dev;
-    if (h->cfg.crowd) return hw_crowd_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, stream);
+    if (h->cfg.crowd) return hw_crowd_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, h->pending, h->live, stream);
     const dim3 g = particle_grid(h->max_blocks, d.n_envs);
     const bool ex = d.Nr == 3 && d.Nh == 10 && d.Nc == 5 && d.K == 30 && d.D == 156;  // the module's own configuration (hostage.py:483), 30 sensors, agent id
     if (io.st != nullptr) {  // a bound StandardizedEnv: the instantiations with its epilogue
@@ -727,6 +730,16 @@ void madrl_hostage_destroy(madrl_hostage *h) { particle_destroy(h); }
 int madrl_hostage_set_standardize(madrl_hostage *h, const madrl_standardize_args *a) { return particle_set_standardize(h, a); }
 
 int madrl_hostage_set_launch(madrl_hostage *h, int64_t max_blocks) { return particle_set_launch(h, max_blocks); }
+
+int madrl_hostage_set_particle_counts(madrl_hostage *h, const int32_t *pending_dev, int32_t *live_dev) {
+    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
+    if (!h->cfg.crowd) return fail(MADRL_EINVAL, "set_particle_counts: per-env particle counts run on the crowd kernel (cfg.crowd = 1)");
+    if ((pending_dev == nullptr) != (live_dev == nullptr))
+        return fail(MADRL_EINVAL, "set_particle_counts: pending_dev and live_dev are both arrays or both NULL");
+    h->pending = pending_dev;
+    h->live = live_dev;
+    return MADRL_OK;
+}
 
 int madrl_hostage_reset(madrl_hostage *h, const uint8_t *mask_dev, float *obs_dev, void *stream) {
     return particle_reset(h, mask_dev, obs_dev, stream, hw_launch);

@@ -44,8 +44,10 @@ struct HwIO {
 
 namespace madrl {
 
-// hostage_crowd.hip.  dev / io: a HwDev and a HwIO (see the note at the top); mode 0 = reset, 1 = step.
-int hw_crowd_launch(const void *dev, const void *io, int mode, int64_t max_blocks, size_t lds_bytes, void *stream);
+// hostage_crowd.hip.  dev / io: a HwDev and a HwIO (see the note at the top); mode 0 = reset, 1 = step.  live != NULL: the per-env
+// particle counts of madrl_hostage_set_particle_counts (the kernels' live-count instantiations), the shape of dev being the capacity.
+int hw_crowd_launch(const void *dev, const void *io, int mode, int64_t max_blocks, size_t lds_bytes, const int32_t *pending, int32_t *live,
+                    void *stream);
 // the dynamic LDS of one hw_crowd_kernel workgroup
 size_t hw_crowd_lds_bytes(int n_good, int n_hostages, int n_bad, int n_sensors, int rec_dw);
 

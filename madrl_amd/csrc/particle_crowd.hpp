@@ -35,6 +35,15 @@ namespace madrl {
 
 __host__ __device__ inline int up4(int v) { return (v + 3) & ~3; }
 
+// Per-env particle counts (madrl_waterworld_set_particle_counts, madrl_hostage_set_particle_counts): the two caller-owned int32
+// [n_envs][3] arrays of the live-count entries (*_crowd_kernel_live), in the world's class order, the agents first
+struct ParticleCounts {
+    const int32_t *pending;  // the counts an env takes at its next reset, clamped to 1 .. capacity
+    int32_t *live;           // the counts of its running episode: read per env, written by the reset pass
+};
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 // ---- phase A.  An agent's action row (zeros unless live) is scaled and kept in ACT[i]; the agent integrates and is clipped to the
 // walls, the velocity component zeroed where it was.
 __device__ __forceinline__ void drive_agent(bool live, const float *actions, int64_t row, float action_scale, float *ACT, int i, float &x,
@@ -196,6 +205,18 @@ template <class Dev, class IO>
 int crowd_launch(void (*kernel)(Dev, IO), int nw, const void *dev, const void *io, int64_t max_blocks, size_t lds_bytes, void *stream) {
     const Dev &d = *static_cast<const Dev *>(dev);
     hipLaunchKernelGGL(kernel, particle_grid(max_blocks, d.n_envs), dim3(64 * nw), lds_bytes, (hipStream_t)stream, d, *static_cast<const IO *>(io));
+    MADRL_HIP_TRY(hipGetLastError());
+    return MADRL_OK;
+}
+
+
+// ... of a live-count entry, with the count arrays as its third argument
+template <class Dev, class IO>
+int crowd_launch(void (*kernel)(Dev, IO, ParticleCounts), int nw, const void *dev, const void *io, const ParticleCounts &cn,
+                 int64_t max_blocks, size_t lds_bytes, void *stream) {
+    const Dev &d = *static_cast<const Dev *>(dev);
+    hipLaunchKernelGGL(kernel, particle_grid(max_blocks, d.n_envs), dim3(64 * nw), lds_bytes, (hipStream_t)stream, d, *static_cast<const IO *>(io),
+                       cn);
     MADRL_HIP_TRY(hipGetLastError());
     return MADRL_OK;
 }

@@ -24,14 +24,6 @@ namespace {
 
 using namespace madrl;
 
-// Per-env particle counts (madrl_waterworld_set_particle_counts): the two caller-owned int32 [n_envs][3] arrays of the LIVE kernels
-struct WwCounts {
-    const int32_t *pending;  // (pursuers, evaders, poison) an env takes at its next reset, clamped to 1 .. capacity
-    int32_t *live;           // the counts of its running episode: read per env, written by the reset pass
-};
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // MODE 0: reset(mask)   MODE 1: step (+ fused auto-reset)
 // LIVE (ww_crowd_kernel_live): d.Np / d.Ne / d.Npo are a CAPACITY and every env runs its own counts (cn.live).  Whatever a caller sees stays at the capacity,
 // slotted by class: pursuer i at slot i, evader m at Pc + m, poison m at Pc + Ec + m -- the record, the rows of inj_resp, the action /
@@ -42,12 +34,12 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 template <int MODE, int NW>
 __global__ __launch_bounds__(64 * NW) void ww_crowd_kernel(const WwDev d, const WwIO io) {
     constexpr bool LIVE = false;
-    constexpr WwCounts cn{nullptr, nullptr};
+    constexpr ParticleCounts cn{nullptr, nullptr};
 #include "waterworld_crowd_body.inc"
 }
 
 template <int MODE, int NW>
-__global__ __launch_bounds__(64 * NW) void ww_crowd_kernel_live(const WwDev d, const WwIO io, const WwCounts cn) {
+__global__ __launch_bounds__(64 * NW) void ww_crowd_kernel_live(const WwDev d, const WwIO io, const ParticleCounts cn) {
     constexpr bool LIVE = true;
 #include "waterworld_crowd_body.inc"
 }
@@ -63,14 +55,9 @@ size_t ww_crowd_lds_bytes(int Np, int Ne, int Npo, int K, int rec_dw) {
 
 int ww_crowd_launch(const void *dev, const void *io, int mode, int64_t max_blocks, size_t lds_bytes, const int32_t *pending, int32_t *live,
                     void *stream) {
-    if (live != nullptr) {  // per-env particle counts
-        const WwDev &d = *static_cast<const WwDev *>(dev);
-        void (*const kernel)(WwDev, WwIO, WwCounts) = mode == 0 ? ww_crowd_kernel_live<0, MADRL_WWC_NW> : ww_crowd_kernel_live<1, MADRL_WWC_NW>;
-        hipLaunchKernelGGL(kernel, particle_grid(max_blocks, d.n_envs), dim3(64 * MADRL_WWC_NW), lds_bytes, (hipStream_t)stream, d,
-                           *static_cast<const WwIO *>(io), WwCounts{pending, live});
-        MADRL_HIP_TRY(hipGetLastError());
-        return MADRL_OK;
-    }
+    if (live != nullptr)  // per-env particle counts
+        return crowd_launch<WwDev, WwIO>(mode == 0 ? ww_crowd_kernel_live<0, MADRL_WWC_NW> : ww_crowd_kernel_live<1, MADRL_WWC_NW>, MADRL_WWC_NW,
+                                         dev, io, ParticleCounts{pending, live}, max_blocks, lds_bytes, stream);
     return crowd_launch<WwDev, WwIO>(mode == 0 ? ww_crowd_kernel<0, MADRL_WWC_NW> : ww_crowd_kernel<1, MADRL_WWC_NW>, MADRL_WWC_NW, dev, io,
                                      max_blocks, lds_bytes, stream);
 }

@@ -1,6 +1,6 @@
 // waterworld_crowd_body.inc -- the body of ww_crowd_kernel<MODE, NW> and ww_crowd_kernel_live<MODE, NW> (waterworld_crowd.hip), included
 // inside both __global__ entries like pursuit_crowd_body.inc: the fixed-shape entry keeps its two arguments and its code.  In scope: MODE,
-// NW, d (WwDev), io (WwIO), `constexpr bool LIVE` and, when LIVE, cn (WwCounts).
+// NW, d (WwDev), io (WwIO), `constexpr bool LIVE` and, when LIVE, cn (ParticleCounts).
     static_assert(NW >= 2 && NW <= 16, "a thread owns at most one pursuer (n_pursuers <= 128)");
     constexpr int NT = 64 * NW;
     extern __shared__ __attribute__((aligned(16))) float smem_crowd[];

@@ -6,7 +6,8 @@
   `timestep_limit`, `reset()`, `step()`, `seed()`, `is_terminal`, `is_gate_open`; tensors:
       reset()       -> obs float32 [N, n_good, D]          D = 5K + 6  (K sensors)
       step(action)  -> obs, rew float32 [N, n_good], done bool [N], {'ho_saved','cr_encs': int32 [N]}
-  `crowd=True` runs envs beyond one wavefront's worth of particles (more than 61 particles or 32 rescuers) on the multi-wavefront kernel.
+  `crowd=True` runs envs beyond one wavefront's worth of particles (more than 61 particles or 32 rescuers) on the multi-wavefront kernel;
+  with `per_env_counts=True` as well, n_good / n_hostages / n_bad are a capacity and every env runs its own counts.
 * `ContinuousHostageWorld(...)`: N == 1 drop-in with the reference's return types.
 
 Arithmetic is float32 in the HIP kernel (reference: float64; tolerance 1e-5, tests/)."""
@@ -46,15 +47,18 @@ class BatchedContinuousHostageWorld(BatchedParticleWorld):
     def __init__(self, n_good, n_hostages, n_bad, n_coop_save, n_coop_avoid, radius=0.015, key_loc=None, bad_speed=0.01, n_sensors=30,
                  sensor_range=0.2, action_scale=0.01, save_reward=5., hit_reward=-1., encounter_reward=0.01, not_saved_reward=-3,
                  bomb_reward=-5., bomb_radius=0.05, key_radius=0.0075, control_penalty=-.1, reward_mech='global', addid=True,
-                 n_envs=1, device="cuda:0", seed=0, env_id_base=0, max_steps=0, auto_reset=False, max_blocks=0, crowd=False, **kwargs):
+                 n_envs=1, device="cuda:0", seed=0, env_id_base=0, max_steps=0, auto_reset=False, max_blocks=0, crowd=False,
+                 per_env_counts=False, **kwargs):
         """crowd=True: the multi-wavefront kernel (csrc/hostage_crowd.hip) -- up to 128 rescuers, 64 hostages and 1 023 particles per env,
         any sensor count up to 256; the same results bit for bit on a shape both kernels take.  Without it an env holds at most 61 particles
-        and 32 rescuers."""
+        and 32 rescuers.
+        per_env_counts=True (with crowd=True): n_good / n_hostages / n_bad are a capacity and every env runs its own counts
+        (set_particle_counts), taken at its next reset; all tensors keep the capacity's shapes, slotted by class (rescuer i at i, hostage m
+        at n_good + m, criminal m at n_good + n_hostages + m; bit m of the saved mask is hostage m).  A pickle keeps the constructor
+        arguments only: the counts of the copy are back at the capacity."""
         self._ctor = dict(locals())
         self._ctor.pop("self"); self._ctor.pop("kwargs"); self._ctor.pop("__class__", None)
-        if not crowd:   # only a set flag travels: pickles of the envs that existed before it stay what they were
-            self._ctor.pop("crowd")
-        self._crowd = bool(crowd)
+        self._flags(crowd, per_env_counts)
         self.n_good, self.n_hostages, self.n_bad = n_good, n_hostages, n_bad
         self.n_coop_save, self.n_coop_avoid, self.radius, self.key_loc = n_coop_save, n_coop_avoid, radius, key_loc
         self.key_radius, self.bad_speed, self.n_sensors = key_radius, bad_speed, n_sensors
@@ -99,18 +103,40 @@ class BatchedContinuousHostageWorld(BatchedParticleWorld):
     def is_gate_open(self):
         return (self.get_state()["flags"] & 1).bool()
 
+    def _all_saved(self, n_hostages):
+        """the saved mask of "all saved" for hostage counts int [N], as the int64 the state holds it in"""
+        h = n_hostages.to(torch.int64)
+        return torch.where(h >= 64, torch.full_like(h, -1), (torch.ones_like(h) << h.clamp(max=63)) - 1)
+
     @property
     def is_terminal(self):
         s = self.get_state()
-        allm = (1 << self.n_hostages) - 1
-        if self.n_hostages >= 64:
-            allm = -1   # the 64 bits of the mask as the int64 the state holds them in: the top one is the sign
+        if self.per_env_counts:   # each env's live hostage count
+            allm = self._all_saved(s["counts"][:, 1])
+        else:
+            allm = (1 << self.n_hostages) - 1
+            if self.n_hostages >= 64:
+                allm = -1   # the 64 bits of the mask as the int64 the state holds them in: the top one is the sign
         return ((s["flags"] & 2) != 0) | ((s["saved"] & allm) == allm) | (s["t"] >= self.timestep_limit)  # :179-182
 
-    def set_state(self, **kw):
+    def set_particle_counts(self, n_good=None, n_hostages=None, n_bad=None, mask=None):
+        """PENDING counts of the envs in `mask` (all: None): an int or an int [N] per count, each in 1 .. the capacity.  An env takes them
+        at its next reset -- reset(), reset(mask=) or the auto-reset of a step; its running episode keeps its particles."""
+        self._set_pending((n_good, n_hostages, n_bad), mask)
+
+    def set_state(self, counts=None, **kw):
+        """counts (per_env_counts=True): live counts int [N, 3] of the state being restored; pos and vel (slotted at the capacity) must
+        come with them, and the bits of `saved` at or above an env's hostage count are cleared.  The pending counts are not touched."""
         def signed(v):   # numpy's unsigned masks and ticks as the int64 torch takes
             v = np.asarray(v)
             return v.astype(np.int64) if v.dtype in (np.uint64, np.uint32) else v
+        if counts is not None:
+            live, kw["pos"], kw["vel"] = self._restored_counts(counts, kw.get("pos"), kw.get("vel"))
+            if kw.get("saved") is not None:
+                sv = kw["saved"]
+                sv = torch.as_tensor(sv if torch.is_tensor(sv) else signed(sv), device=self.device).reshape(self.n_envs).to(torch.int64)
+                kw["saved"] = sv & self._all_saved(live[:, 1])
+            self._live.copy_(live)
         self._set_state(kw, signed)
 
 

@@ -10,8 +10,8 @@ import torch
 from . import _lib
 from .base import AbstractMAEnv, SingleEnvDelegate
 
-_CALLS = ("obs_dim", "state_bytes", "create", "destroy", "set_launch", "kernel_kind", "set_standardize", "reset", "step", "get_state",
-          "set_state")
+_CALLS = ("obs_dim", "state_bytes", "create", "destroy", "set_launch", "kernel_kind", "set_particle_counts", "set_standardize", "reset", "step",
+          "get_state", "set_state")
 _API = {}   # C symbol prefix -> the world's functions under their short names (filled by setup(): nothing is kept on the instance)
 
 
@@ -31,13 +31,27 @@ def sensor_vectors(n_sensors):
 class BatchedParticleWorld(AbstractMAEnv):
     """A subclass's constructor assigns the reference's parameters, `_ctor`, `_crowd`, n_envs, device, `_seed_value`, env_id_base, max_steps,
     auto_reset, `_max_blocks` and `_handle = None`, then calls setup().  Every parameter, the agent count included, is read from the live
-    attributes where it is used: nothing of them is copied here."""
+    attributes where it is used: nothing of them is copied here.
+    per_env_counts=True (which `_flags()` takes from the constructor, with crowd=True): the `_COUNTS` attributes are a capacity and every env
+    runs its own counts, taken at its next reset (set_particle_counts of the world, with its own keyword names); all tensors keep the
+    capacity's shapes, slotted by class."""
+    per_env_counts = False
     _SYM = None         # prefix of the C symbols: "madrl_waterworld"
     _COUNTS = None      # names of the attributes that hold the particle counts, the agents' first: ("n_pursuers", "n_evaders", "n_poison")
     _INJECT = None      # name of the attribute that holds the row count of step(respawn=...)
     _INFO_KEYS = None   # the two info keys of step()
     _AGENT = None       # the agent class: _AGENT(idx, obs_dim)
     _STATE = None       # get_state / set_state: ((name, dtype, per-env shape), ...) in the C functions' order, "NP" = n_particles
+
+    def _flags(self, crowd, per_env_counts):
+        """the two kernel flags of a constructor, after `self._ctor = dict(locals())`: only a set flag travels, so pickles of the envs that
+        existed before a flag stay what they were"""
+        for flag in ("crowd", "per_env_counts"):
+            if not self._ctor[flag]:
+                self._ctor.pop(flag)
+        if per_env_counts and not crowd:
+            raise ValueError("per_env_counts=True runs on the crowd kernel: construct the batch with crowd=True")
+        self._crowd, self.per_env_counts = bool(crowd), bool(per_env_counts)
 
     def setup(self):
         c = _api(self._SYM)
@@ -80,6 +94,13 @@ class BatchedParticleWorld(AbstractMAEnv):
                 fresh = self.bind_standardize(tensors=None, **self._std_kwargs)
                 old.clear(); old.update(fresh)
                 self._std = old
+        if self.per_env_counts:   # the count tensors outlive a re-created handle of the same capacity (seed()); otherwise: the capacity
+            cap = tuple(int(k) for k in counts)
+            if getattr(self, "_counts_key", None) != (N, cap):
+                self._pending = torch.tensor(cap, dtype=torch.int32, device=dev).repeat(N, 1).contiguous()
+                self._live = self._pending.clone()
+                self._counts_key = (N, cap)
+            _lib.check(c.set_particle_counts(h, _lib.ptr(self._pending), _lib.ptr(self._live)))
 
     def _hint_fast_path(self, D):
         """a world with a list of specialised shapes says here that a large batch runs on the generic kernel (called by setup() itself)"""
@@ -216,14 +237,72 @@ class BatchedParticleWorld(AbstractMAEnv):
             return std["obs_out"], std["rew_out"], self._done.view(torch.bool), info
         return obs, self._rew, self._done.view(torch.bool), info
 
+    # ------------------------------------------------------------------ per-env particle counts (per_env_counts=True)
+    def _require_counts(self, what):
+        if not self.per_env_counts:
+            raise RuntimeError("%s: this batch has one particle count for all envs; construct it with crowd=True, per_env_counts=True" % what)
+
+    def _checked_counts(self, v, col, name, m=None):
+        """an int or an int [N] as int32 [N] within 1 .. the capacity (where m is set)"""
+        t = torch.as_tensor(v, device=self.device).to(torch.int32)
+        t = t.expand(self.n_envs) if t.dim() == 0 else t.reshape(self.n_envs)
+        bad = (t < 1) | (t > int(getattr(self, self._COUNTS[col])))
+        if bool((bad if m is None else bad & m).any()):
+            raise ValueError("%s must be in 1..%d (the batch's capacity)" % (name, int(getattr(self, self._COUNTS[col]))))
+        return t
+
+    def _set_pending(self, values, mask):
+        """set_particle_counts of a world: `values` in the order of _COUNTS, each None (stays), an int or an int [N]"""
+        self._require_counts("set_particle_counts")
+        m = torch.ones(self.n_envs, dtype=torch.bool, device=self.device) if mask is None else \
+            torch.as_tensor(mask, device=self.device).reshape(self.n_envs) != 0
+        new = [None if v is None else self._checked_counts(v, col, name, m) for col, (v, name) in enumerate(zip(values, self._COUNTS))]
+        for col, t in enumerate(new):
+            if t is not None:
+                self._pending[:, col] = torch.where(m, t, self._pending[:, col])
+
+    def particle_counts(self):
+        """(pending, live): int32 [N, 3] copies of the counts per env, in the order of the constructor's -- what its next reset takes, and
+        what its running episode has"""
+        self._require_counts("particle_counts")
+        return self._pending.clone(), self._live.clone()
+
+    def live_agents(self):
+        """bool [N, agents of the capacity]: the agents of each env's running episode (action rows past them are ignored, their reward and
+        observation rows are zero)"""
+        self._require_counts("live_agents")
+        return torch.arange(int(getattr(self, self._COUNTS[0])), device=self.device)[None, :] < self._live[:, :1]
+
+    def _slot_exists(self, live):
+        """bool [N, NP]: the slots (the three classes at the capacity) that hold a particle under the live counts int [N, 3]"""
+        parts = [torch.arange(int(getattr(self, k)), device=self.device)[None, :] < live[:, c:c + 1] for c, k in enumerate(self._COUNTS)]
+        return torch.cat(parts, dim=1)
+
+    def _restored_counts(self, counts, pos, vel):
+        """set_state(counts=): the live counts int [N, 3] of the state being restored, checked -> (live int32 [N, 3], pos, vel) with
+        (-1, -1) / 0 in the slots that hold no particle.  pos and vel, slotted at the capacity, must come with the counts.  The caller
+        copies `live` into self._live once the rest of its arguments is checked; the pending counts are not touched."""
+        self._require_counts("set_state(counts=)")
+        if pos is None or vel is None:
+            raise ValueError("set_state(counts=) needs pos and vel in the same call: the counts say which of their slots hold a particle")
+        c = torch.as_tensor(counts if torch.is_tensor(counts) else np.asarray(counts), device=self.device).reshape(self.n_envs, 3)
+        live = torch.stack([self._checked_counts(c[:, col], col, name) for col, name in enumerate(self._COUNTS)], dim=1)
+        shape = (self.n_envs, self.n_particles, 2)
+        conv = lambda v: torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v), device=self.device).reshape(shape).to(torch.float32)
+        is_ = self._slot_exists(live)[:, :, None]
+        return live, torch.where(is_, conv(pos), -1.0), torch.where(is_, conv(vel), 0.0)
+
     # ------------------------------------------------------------------ state access
     def _state_layout(self):
         """_STATE with the batch's shapes: [(name, dtype, shape), ...]"""
         return [(k, dt, (self.n_envs,) + tuple(self.n_particles if s == "NP" else s for s in shape)) for k, dt, shape in self._STATE]
 
     def get_state(self):
+        """with per_env_counts: also "counts", the live counts int32 [N, 3]; a slot without a particle reads (-1, -1) / (0, 0)"""
         st = {k: torch.zeros(shape, dtype=dt, device=self.device) for k, dt, shape in self._state_layout()}
         _lib.check(_API[self._SYM].get_state(self._handle, *[_lib.ptr(v) for v in st.values()], _lib.current_stream(self.device)))
+        if self.per_env_counts:
+            st["counts"] = self._live.clone()
         return st
 
     def _set_state(self, values, to_array=np.asarray):

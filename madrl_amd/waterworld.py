@@ -60,12 +60,7 @@ class BatchedMAWaterWorld(BatchedParticleWorld):
         # like the reference, unknown kwargs are swallowed (waterworld.py:81,:483 passes obs_loc=None)
         self._ctor = dict(locals())
         self._ctor.pop("self"); self._ctor.pop("kwargs"); self._ctor.pop("__class__", None)
-        for flag in ("crowd", "per_env_counts"):   # only a set flag travels: pickles of the envs that existed before it stay what they were
-            if not self._ctor[flag]:
-                self._ctor.pop(flag)
-        if per_env_counts and not crowd:
-            raise ValueError("per_env_counts=True runs on the crowd kernel: construct the batch with crowd=True")
-        self._crowd, self.per_env_counts = bool(crowd), bool(per_env_counts)
+        self._flags(crowd, per_env_counts)
         self.n_pursuers, self.n_evaders, self.n_coop, self.n_poison = n_pursuers, n_evaders, n_coop, n_poison
         self.radius, self.obstacle_radius, self.obstacle_loc = radius, obstacle_radius, obstacle_loc
         self.ev_speed, self.poison_speed, self.n_sensors = ev_speed, poison_speed, n_sensors
@@ -98,16 +93,6 @@ class BatchedMAWaterWorld(BatchedParticleWorld):
         c.seed, c.env_id_base = self._seed_value, self.env_id_base
         return c
 
-    def setup(self):
-        super().setup()
-        if self.per_env_counts:   # the count tensors outlive a re-created handle of the same capacity (seed()); otherwise: the capacity
-            cap = tuple(int(getattr(self, k)) for k in self._COUNTS)
-            if getattr(self, "_counts_key", None) != (self.n_envs, cap):
-                self._pending = torch.tensor(cap, dtype=torch.int32, device=self.device).repeat(self.n_envs, 1).contiguous()
-                self._live = self._pending.clone()
-                self._counts_key = (self.n_envs, cap)
-            _lib.check(_lib.lib().madrl_waterworld_set_particle_counts(self._handle, _lib.ptr(self._pending), _lib.ptr(self._live)))
-
     _hinted = set()
 
     def _hint_fast_path(self, D):
@@ -130,69 +115,16 @@ class BatchedMAWaterWorld(BatchedParticleWorld):
     def is_terminal(self):
         return self.get_state()["t"] >= self.timestep_limit
 
-    # ------------------------------------------------------------------ per-env particle counts (per_env_counts=True)
-    def _require_counts(self, what):
-        if not self.per_env_counts:
-            raise RuntimeError("%s: this batch has one particle count for all envs; construct it with crowd=True, per_env_counts=True" % what)
-
-    def _checked_counts(self, v, col, name, m=None):
-        """an int or an int [N] as int32 [N] within 1 .. the capacity (where m is set)"""
-        t = torch.as_tensor(v, device=self.device).to(torch.int32)
-        t = t.expand(self.n_envs) if t.dim() == 0 else t.reshape(self.n_envs)
-        bad = (t < 1) | (t > int(getattr(self, self._COUNTS[col])))
-        if bool((bad if m is None else bad & m).any()):
-            raise ValueError("%s must be in 1..%d (the batch's capacity)" % (name, int(getattr(self, self._COUNTS[col]))))
-        return t
-
     def set_particle_counts(self, n_pursuers=None, n_evaders=None, n_poison=None, mask=None):
         """PENDING counts of the envs in `mask` (all: None): an int or an int [N] per count, each in 1 .. the capacity.  An env takes them
         at its next reset -- reset(), reset(mask=) or the auto-reset of a step; its running episode keeps its particles."""
-        self._require_counts("set_particle_counts")
-        m = torch.ones(self.n_envs, dtype=torch.bool, device=self.device) if mask is None else \
-            torch.as_tensor(mask, device=self.device).reshape(self.n_envs) != 0
-        new = [None if v is None else self._checked_counts(v, col, name, m) for col, (v, name) in
-               enumerate(zip((n_pursuers, n_evaders, n_poison), self._COUNTS))]
-        for col, t in enumerate(new):
-            if t is not None:
-                self._pending[:, col] = torch.where(m, t, self._pending[:, col])
-
-    def particle_counts(self):
-        """(pending, live): int32 [N, 3] copies of (pursuers, evaders, poison) per env -- what its next reset takes, and what its running
-        episode has"""
-        self._require_counts("particle_counts")
-        return self._pending.clone(), self._live.clone()
-
-    def live_agents(self):
-        """bool [N, n_pursuers]: the pursuers of each env's running episode (action rows past them are ignored, their reward and
-        observation rows are zero)"""
-        self._require_counts("live_agents")
-        return torch.arange(int(self.n_pursuers), device=self.device)[None, :] < self._live[:, :1]
-
-    def _slot_exists(self, live):
-        """bool [N, NP]: the slots (pursuers | evaders | poison at the capacity) that hold a particle under the live counts int [N, 3]"""
-        parts = [torch.arange(int(getattr(self, k)), device=self.device)[None, :] < live[:, c:c + 1] for c, k in enumerate(self._COUNTS)]
-        return torch.cat(parts, dim=1)
-
-    def get_state(self):
-        """with per_env_counts: also "counts", the live counts int32 [N, 3]; a slot without a particle reads (-1, -1) / (0, 0)"""
-        st = super().get_state()
-        if self.per_env_counts:
-            st["counts"] = self._live.clone()
-        return st
+        self._set_pending((n_pursuers, n_evaders, n_poison), mask)
 
     def set_state(self, pos=None, vel=None, obst=None, t=None, tick=None, counts=None):
         """counts (per_env_counts=True): live counts int [N, 3] of the state being restored; pos and vel (slotted at the capacity) must
         come with them.  The pending counts are not touched."""
         if counts is not None:
-            self._require_counts("set_state(counts=)")
-            if pos is None or vel is None:
-                raise ValueError("set_state(counts=) needs pos and vel in the same call: the counts say which of their slots hold a particle")
-            c = torch.as_tensor(counts if torch.is_tensor(counts) else np.asarray(counts), device=self.device).reshape(self.n_envs, 3)
-            live = torch.stack([self._checked_counts(c[:, col], col, name) for col, name in enumerate(self._COUNTS)], dim=1)
-            shape = (self.n_envs, self.n_particles, 2)
-            conv = lambda v: torch.as_tensor(v if torch.is_tensor(v) else np.asarray(v), device=self.device).reshape(shape).to(torch.float32)
-            is_ = self._slot_exists(live)[:, :, None]
-            pos, vel = torch.where(is_, conv(pos), -1.0), torch.where(is_, conv(vel), 0.0)
+            live, pos, vel = self._restored_counts(counts, pos, vel)
             self._live.copy_(live)
         self._set_state(dict(pos=pos, vel=vel, obst=obst, t=t, tick=tick))
 

@@ -1,7 +1,8 @@
 """Step time of the hostage-world crowd kernel (csrc/hostage_crowd.hip, `crowd=True`) at shapes beyond one wavefront's worth of particles.
 
     python scripts/hostage_crowd_time.py                      # the table of DESIGN 4.5a: every row below, three processes each, min - max
-    python scripts/hostage_crowd_time.py --rows shapes,cpu    # some of: shapes, cpu, wave, nw8
+    python scripts/hostage_crowd_time.py --rows shapes,cpu    # some of: shapes, cpu, wave, nw8, live
+    python scripts/hostage_crowd_time.py --live               # the table of DESIGN 4.5b: the `live` row alone
 
 Rows
   shapes  20/30/40 at 4 096 and 262 144 envs, 33/10/20 at 4 096, 128/64/831 at 4 096 and 32 768 (30 sensors, n_coop_save 2): us per launch,
@@ -12,6 +13,9 @@ Rows
   wave    3/10/5 at 32 768 envs on both kernels, alternating in one process: the cost of the crowd form on a shape both take
   nw8     eight instead of four wavefronts per workgroup on the first two shapes: needs the variant library
           `SRC=hostage_crowd MACRO=MADRL_HWC_NW scripts/variants.sh 8` builds (scripts/_variants/, git-ignored)
+  live    per-env particle counts (per_env_counts=True) at the capacities 20/30/40 and 33/10/20, 4 096 envs: the fixed-shape kernel, the
+          live-count kernel with every env at the capacity, and with every env's triple drawn uniformly between (1, 1, 1) and the capacity
+          -- the three alternating, three processes each (ray tests/s of the spread row are counted at the capacity: compare its us)
 
 Steady state with auto_reset (max_steps 500), after an untimed warm-up; device events around at least 200 launches with no synchronise
 between them.  One measurement per process (`--one ...`, what the parent starts), one process at a time.
@@ -31,6 +35,7 @@ ROWS = (("20/30/40", 4096), ("20/30/40", 262144), ("33/10/20", 4096), ("128/64/8
 NW8_LIB = os.path.join(ROOT, "scripts", "_variants", "libmadrl_hip.hostage_crowd.8.so")
 HBM_PEAK = 8e12
 STEPS = 200
+LIVE_KINDS = ("crowd", "crowd-live", "crowd-live-spread")
 
 
 def bytes_per_env_step(shape):
@@ -39,16 +44,22 @@ def bytes_per_env_step(shape):
     return Nr * 2 * 4 + Nr * (5 * K + 6) * 4 + Nr * 4 + 1 + 8 + 2 * rec
 
 
-def _env(shape, N, crowd):
+def _env(shape, N, crowd, live=0):
+    """live: 0 fixed shape, 1 per-env counts at the capacity, 2 a spread of counts"""
     import torch
     from madrl_amd.hostage import BatchedContinuousHostageWorld
     Nr, Nh, Nc = SHAPES[shape]
-    return BatchedContinuousHostageWorld(Nr, Nh, Nc, 2, 2, n_sensors=K, n_envs=N, device=torch.device("cuda:0"), seed=0, max_steps=500,
-                                         auto_reset=True, crowd=bool(crowd))
+    env = BatchedContinuousHostageWorld(Nr, Nh, Nc, 2, 2, n_sensors=K, n_envs=N, device=torch.device("cuda:0"), seed=0, max_steps=500,
+                                        auto_reset=True, crowd=bool(crowd), per_env_counts=bool(live))
+    if live == 2:
+        g = torch.Generator().manual_seed(0)
+        env.set_particle_counts(*[torch.randint(1, c + 1, (N,), generator=g) for c in (Nr, Nh, Nc)])
+    return env
 
 
 def one(shape, N, kernels):
-    """one measurement per kernel of `kernels` ("crowd", "wave" or "crowd,wave": alternating blocks) in this process -> a JSON line each"""
+    """one measurement per kernel of `kernels` ("crowd", "wave", "crowd,wave": alternating blocks; "crowd-live" / "crowd-live-spread": the
+    live-count kernel at the capacity / over a spread of counts) in this process -> a JSON line each"""
     import torch
     from madrl_amd import _lib
     Nr, Nh, Nc = SHAPES[shape]
@@ -57,8 +68,8 @@ def one(shape, N, kernels):
     acts = [torch.rand(N, Nr, 2, device=dev) * 2 - 1 for _ in range(8)]
     runs = {}
     for kind in kernels.split(","):
-        env = _env(shape, N, kind == "crowd")
-        assert env.kernel_kind == kind
+        env = _env(shape, N, kind != "wave", LIVE_KINDS.index(kind) if kind in LIVE_KINDS else 0)
+        assert env.kernel_kind == kind.split("-")[0]
         env.reset()
         outs = [_lib.ptr(t) for t in (env._obs, env._rew, env._done, env._info)]
 
@@ -104,20 +115,21 @@ def cpu(shape):
     return dict(shape=shape, n_envs=N, env_steps_per_s=N * n / dt, threads=int(os.environ.get("OMP_NUM_THREADS", 0)) or os.cpu_count())
 
 
-def child(shape, N, kernels="crowd", lib=None):
-    """three processes -> {kernel: (min, max) us per launch}"""
+def child(shape, N, kernels="crowd", lib=None, separate=False):
+    """three processes (separate: three per kernel of `kernels`, the kernels alternating) -> {kernel: (min, max) us per launch}"""
     env = dict(os.environ)
     if lib:
         env["MADRL_HIP_LIB"] = lib
     rs = {}
     for _ in range(3):
-        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", shape, str(N), kernels], env=env, capture_output=True, text=True,
-                             timeout=900)
-        if out.returncode != 0:
-            raise SystemExit("measurement %s N=%d %s failed (%d):\n%s" % (shape, N, kernels, out.returncode, out.stderr[-2000:]))
-        for line in out.stdout.strip().splitlines()[-len(kernels.split(",")):]:
-            r = json.loads(line)
-            rs.setdefault(r["kernel"], []).append(r)
+        for ks in (kernels.split(",") if separate else [kernels]):
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", shape, str(N), ks], env=env, capture_output=True, text=True,
+                                 timeout=900)
+            if out.returncode != 0:
+                raise SystemExit("measurement %s N=%d %s failed (%d):\n%s" % (shape, N, ks, out.returncode, out.stderr[-2000:]))
+            for line in out.stdout.strip().splitlines()[-len(ks.split(",")):]:
+                r = json.loads(line)
+                rs.setdefault(r["kernel"], []).append(r)
     res = {}
     for kind, rr in rs.items():
         us = [r["us_per_launch"] for r in rr]
@@ -135,7 +147,7 @@ def main():
     argv = sys.argv[1:]
     if argv[:1] == ["--one"]:
         return one(argv[1], int(argv[2]), argv[3])
-    rows = argv[argv.index("--rows") + 1].split(",") if "--rows" in argv else ["shapes", "cpu", "wave", "nw8"]
+    rows = argv[argv.index("--rows") + 1].split(",") if "--rows" in argv else ["live"] if "--live" in argv else ["shapes", "cpu", "wave", "nw8"]
     if "shapes" in rows:
         for s, N in ROWS:
             child(s, N)
@@ -153,6 +165,12 @@ def main():
         for s, N in ROWS[:3]:
             child(s, N)
             child(s, N, lib=NW8_LIB)
+    if "live" in rows:
+        for s in ("20/30/40", "33/10/20"):   # fixed, live at the capacity, live spread: alternating, a process each
+            r = child(s, 4096, ",".join(LIVE_KINDS), separate=True)
+            (f0, f1), (l0, l1), (s0, s1) = [r[k] for k in LIVE_KINDS]
+            print("%s at 4 096 envs: live at the capacity / fixed = %.3f - %.3f, spread / live at the capacity = %.3f - %.3f" % (
+                s, l0 / f1, l1 / f0, s0 / l1, s1 / l0), flush=True)
 
 
 if __name__ == "__main__":
