@@ -97,6 +97,7 @@ __host__ __device__ inline double u53(uint32_t hi, uint32_t lo) {
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+constexpr __host__ __device__ inline int up4(int v) { return (v + 3) & ~3; }
 
 // The flag plane of a step launch (include/madrl_hip.h, madrl_pursuit_flags_offset): the done byte split into one 0 / 1 byte per
 // meaning, so that the host side hands out bool views of it instead of launching kernels that mask bits.
@@ -212,6 +213,30 @@ __device__ __forceinline__ void ema_update(double &m, double &v, double x, doubl
     const double d = x - m;
     v = (1.0 - alpha) * v + alpha * (d * d);
 }
+
+// ---------------------------------------------------------------- float text the particle worlds' kernels share
+// (particle_wave.hpp: one wavefront per env; particle_crowd.hpp: a multi-wavefront workgroup per env)
+// An agent takes its scaled action (a0, a1), integrates and is clipped to the walls, the velocity component zeroed where it was.
+__device__ __forceinline__ void integrate_agent(float a0, float a1, float &x, float &y, float &vx, float &vy) {
+    vx = vx + a0; vy = vy + a1;
+    x = x + vx; y = y + vy;
+    const float cx = x < 0.f ? 0.f : (x > 1.f ? 1.f : x);
+    const float cy = y < 0.f ? 0.f : (y > 1.f ? 1.f : y);
+    if (x != cx) vx = 0.f;
+    if (y != cy) vy = 0.f;
+    x = cx; y = cy;
+}
+
+// A non-agent moves; its velocity flips only if BOTH coordinates left [0, 1], and nothing is clipped.
+__device__ __forceinline__ void free_motion(float &x, float &y, float &vx, float &vy) {
+    x = x + vx; y = y + vy;
+    const bool outx = !(x >= 0.f && x <= 1.f), outy = !(y >= 0.f && y <= 1.f);
+    if (outx && outy) { vx = -1.0f * vx; vy = -1.0f * vy; }
+}
+
+// A sensor of agent i can only return a finite value for an object with d2 <= rad2 + sv^2 <= rad2 + range^2 (plus a relative margin far
+// above the rounding of the test itself): everything else yields +inf in the oracle and never becomes a minimum.
+__device__ __forceinline__ float sensor_reach2(float rad2, float srange) { return (rad2 + srange * srange) * 1.0001f + 1e-9f; }
 #endif
 
 // ---------------------------------------------------------------- host side of the env handles
@@ -268,6 +293,8 @@ struct ParticleHandle {
     void *tables;
     ParticleStd *std_dev;   // device copy of the bound StandardizedEnv arguments (particle_set_standardize)
     bool std_bound;
+    const int32_t *pending;  // particle_set_counts: caller-owned [n_envs][3], both NULL = one shape for all envs
+    int32_t *live;
 };
 
 // madrl_waterworld_create / madrl_hostage_create after the world's own validation of cfg: H is the handle, layout() and lds_bytes()
@@ -329,6 +356,18 @@ template <class H>
 int particle_set_launch(H *h, int64_t max_blocks) {
     if (!h || max_blocks < 0) return fail(MADRL_EINVAL, "set_launch: bad argument");
     h->max_blocks = max_blocks;
+    return MADRL_OK;
+}
+
+// madrl_waterworld_set_particle_counts / madrl_hostage_set_particle_counts
+template <class H>
+int particle_set_counts(H *h, const int32_t *pending_dev, int32_t *live_dev) {
+    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
+    if (!h->cfg.crowd) return fail(MADRL_EINVAL, "set_particle_counts: per-env particle counts run on the crowd kernel (cfg.crowd = 1)");
+    if ((pending_dev == nullptr) != (live_dev == nullptr))
+        return fail(MADRL_EINVAL, "set_particle_counts: pending_dev and live_dev are both arrays or both NULL");
+    h->pending = pending_dev;
+    h->live = live_dev;
     return MADRL_OK;
 }
 

@@ -7,12 +7,17 @@
 // object) collision pairs, (rescuer, sensor) sensing pairs -- the objects a sensor is tested against are broadcast once
 // from the owning lane's registers (v_readlane -> SGPR operands) and reused by three passes of pairs held in registers.
 //
+// The device code shared with waterworld_kernel is in particle_wave.hpp (its opening comment has the scheme); this file is the hostage
+// world's step in the reference's order and what is its own: the reset draws, gate, key and bomb, the saved mask and flags, the ballot
+// form of the collision matrices (BITROWS), the row tail, rewards, respawn and done.
+//
 // Reference semantics (file:line under /root/reference/madrl_environments/hostage.py):
 //   sensing ...... CircAgent.sensed :62-71     reset ...... ContinuousHostageWorld.reset :137-177 (ends with a zero-action step)
 //   catch rule ... _caught :184-198             step ....... :228-430
 // Quirks kept (G1..G9) are listed where they occur.  Arithmetic is float32, every expression keeps the statement order of the
 // reference's step() so that a float32 CPU restatement agrees bit for bit.
 #include "hostage_dev.hpp"
+#include "particle_wave.hpp"   // the device code this kernel shares with waterworld_kernel (waterworld.hip)
 
 #include <math.h>
 #include <stddef.h>
@@ -59,8 +64,7 @@ __device__ __forceinline__ float bcast(float v, int src_lane) { return __int_as_
 template <int MODE, int TNr, int TNh, int TNc, int TK, int TD = 0, bool FUSED = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC_N > 0 ? MADRL_HW_OCC_N : 1, MADRL_HW_OCC_N > 0 ? MADRL_HW_OCC_N : 8))) void hostage_kernel(const HwDev d, const HwIO io) {
     // specialised shape: compile-time LDS layout in a static array, launched with 0 dynamic bytes (see waterworld.hip)
-    constexpr int SPEC_DW = TNr > 0 ? ((4 * (TNr + TNh + TNc) + 9 + 3) / 4 * 4 + ((TNr + 1) * (TD > 0 ? TD : 1) + 3) / 4 * 4 + (2 * TK + 3) / 4 * 4) : 0;   // (TNr + 1: the spare row of the sensing phase)
-    constexpr int SPEC_BYTES = TNr > 0 ? (SPEC_DW * 4 + 8 * TNr + TNr * (TNh + TNc) + 2 * TNh + TNc + 15) / 16 * 16 : 16;
+    constexpr int SPEC_BYTES = TNr > 0 ? (int)wave_lds_bytes(4 * (TNr + TNh + TNc) + 9, TNr, TD, TK, TNh, TNc) : 16;
     static_assert(TNr == 0 || TD > 0, "a specialised shape fixes the observation width too");
     extern __shared__ __attribute__((aligned(16))) float smem_dyn[];
     __shared__ __attribute__((aligned(16))) float smem_static[SPEC_BYTES / 4];
@@ -85,47 +89,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
     uint8_t *FLG = COLC + Nr * Nc;                     // ho_caught[Nh] | ho_enc[Nh] | cr_caught[Nc]
 
     for (int k = lane; k < 2 * K; k += 64) SEN[k] = d.sensors[k];
-    const int nreg = (rec_dw + 63) >> 6;  // <= 4
 
-    uint32_t cur[4] = {0, 0, 0, 0};
-    float cur_act = 0.0f;
-    auto fetch = [&](int64_t env, uint32_t (&r)[4], float &a) {
-        const auto src = uniform_ptr(reinterpret_cast<const uint32_t *>(DA.state) + env * (int64_t)rec_dw);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t k = ulane + 64u * q;
-            r[q] = (q < nreg && (int)k < rec_dw) ? src[k] : 0u;
-        }
-        if constexpr (MODE == 1) a = (lane < 2 * Nr) ? uniform_ptr(IOA.actions + env * 2 * Nr)[ulane] : 0.0f;
-        else a = 0.0f;
-    };
+    WaveRecord cur;  // software pipeline: the next env's record (<= 4 dwords per lane) + action row are fetched one env ahead
     const EnvWalk walk = env_walk(d.n_envs);  // XCD-aware: neighbouring envs share an L2 (common.hpp)
-    if (walk.first < walk.lim) fetch(walk.base + walk.first, cur, cur_act);
-    asm volatile("" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur_act));
+    if (walk.first < walk.lim) cur.fetch<MODE, HwKArgs>(walk.base + walk.first, rec_dw, Nr, lane, ulane);
+    cur.hinge();
     wave_sync();
 
     const int w_base = (int)walk.base, w_stride = (int)walk.stride, w_lim = (int)walk.lim;  // env indices are 32-bit, byte offsets 64-bit
     for (int li = (int)walk.first; li < w_lim; li += w_stride) {
         const int64_t env = w_base + li;
         const int64_t nenv = env + w_stride;
-        uint32_t nxt[4] = {0, 0, 0, 0};
-        float nxt_act = 0.0f;
-        if (li + w_stride < w_lim) fetch(nenv, nxt, nxt_act);
+        WaveRecord nxt;
+        if (li + w_stride < w_lim) nxt.fetch<MODE, HwKArgs>(nenv, rec_dw, Nr, lane, ulane);
         bool skip = false;
         if constexpr (MODE == 0) skip = (IOA.mask != nullptr && IOA.mask[env] == 0);
         if (!skip) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int k = lane + 64 * q;
-                if (q < nreg && k < rec_dw) SU[k] = cur[q];
-            }
+            cur.to_lds(SU, rec_dw, lane);
             wave_sync();
             int32_t tstep = (int32_t)SU[OFF_T];
             uint32_t tick = SU[OFF_TICK];
             uint32_t flags = SU[OFF_FLAGS];  // bit0 gate_open, bit1 bombed, bit2 key sampled
             uint64_t saved = (uint64_t)SU[OFF_SAVED] | ((uint64_t)SU[OFF_SAVED + 1] << 32);
             const uint32_t gid = DA.gid_base + (uint32_t)env;
-            float act_lane = cur_act;
+            float act_lane = cur.act;
 
             bool do_init = (MODE == 0);
             int npass = 1;
@@ -167,19 +154,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                 float reward = 0.0f;
                 bool col_bo = false, col_ke = false;
                 {   // phase A: rescuers (:231-260)
-                    const float a_raw0 = __shfl(act_lane, 2 * (fresh(lane) < Nr ? lane : 0));
-                    const float a_raw1 = __shfl(act_lane, 2 * (fresh(lane) < Nr ? lane : 0) + 1);
-                    const float a0 = a_raw0 * DA.action_scale, a1 = a_raw1 * DA.action_scale;
-                    float pen = DA.control_penalty * (a0 * a0 + a1 * a1);
-                    if (DA.reward_global) {  // (actions**2).sum(), row-major (:241-242)
-                        float s = 0.0f;
-                        for (int i = 0; i < Nr; ++i) {
-                            const float b0 = __shfl(a0, i), b1 = __shfl(a1, i);
-                            s += b0 * b0;
-                            s += b1 * b1;
-                        }
-                        pen = DA.control_penalty * s;
-                    }
+                    float a0, a1;  // the penalty: under the global reward (actions**2).sum(), row-major (:241-242)
+                    const float pen = agent_action<HwKArgs>(act_lane, [&]() { return fresh(lane) < Nr ? lane : 0; }, Nr, a0, a1);
                     if (fresh(lane) < Nr) {
                         float x = X[2 * lane], y = X[2 * lane + 1], vx = V[2 * lane], vy = V[2 * lane + 1];
                         vx = vx + a0; vy = vy + a1;
@@ -229,29 +205,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                         my_enc = is_ho && sc >= 1;
                     }
                 } else {
-                for (int idx = lane; idx < Nr * (Nh + Nc); idx += 64) {
-                    const bool is_ho = idx < Nr * Nh;
-                    const int r = is_ho ? idx : idx - Nr * Nh;
-                    const int n2 = is_ho ? Nh : Nc;
-                    const int i = r / n2, m = r % n2;
-                    const int j = (is_ho ? Nr : Nr + Nh) + m;
-                    (is_ho ? COLH : COLC)[r] = dist2_le(X[2 * i], X[2 * i + 1], X[2 * j], X[2 * j + 1], is_ho ? DA.sq_hit_ho : DA.sq_hit_cr);
-                }
+                contact_bytes(X, COLH, Nr, Nh, Nc, lane, [&](bool is_ho) { return is_ho ? DA.sq_hit_ho : DA.sq_hit_cr; });
                 wave_sync();
                 if (fresh(lane) >= Nr && fresh(lane) < NP) {
                     const bool is_ho = fresh(lane) < Nr + Nh;
                     const int m = is_ho ? lane - Nr : lane - Nr - Nh;
-                    const uint8_t *col = is_ho ? COLH : COLC;
-                    const int n2 = is_ho ? Nh : Nc;
-                    int s = 0;
-                    for (int i = 0; i < Nr; ++i) s += col[i * n2 + m];
+                    const int s = column_count(is_ho ? COLH : COLC, Nr, is_ho ? Nh : Nc, m);
                     my_caught = s >= (is_ho ? DA.n_coop_save : 1);
                     my_enc = is_ho && s >= 1;
-                    if (is_ho) { FLG[m] = my_caught; FLG[Nh + m] = my_enc; }
-                    else FLG[2 * Nh + m] = my_caught;
+                    column_flags(FLG, is_ho, Nh, m, my_caught, my_enc);
                 }
                 }
-                const uint64_t ho_lanes = ((Nh >= 64) ? ~0ull : ((1ull << Nh) - 1ull)) << Nr;
+                const uint64_t ho_lanes = low_bits64(Nh) << Nr;
                 const uint64_t caught_mask = __ballot(my_caught);
                 const int n_ho_caught = __popcll(caught_mask & ho_lanes);
                 const int n_cr_caught = __popcll(caught_mask & ~ho_lanes);
@@ -261,24 +226,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                 wave_sync();
                 // phase C: sensing (:295-362).  Rows: [criminal dist | criminal speed | hostage dist | key dist | bomb dist] (:398-400)
                 {
-                    // passes of 64 (rescuer, sensor) pairs held in registers at a time: no more than the specialised shape needs
-                    // ALIGNED (compile-time K <= 64): a pass holds floor(64 / K) whole rescuers, so its reach set is theirs alone (waterworld.hip)
-                    constexpr bool ALIGNED = TK > 0 && TK <= 64;
-                    constexpr int PPP = ALIGNED ? 64 / (TK > 0 ? TK : 1) : 1;
-                    const int n_pass = ALIGNED ? (Nr + PPP - 1) / PPP : (Nr * K + 63) / 64;
-                    constexpr int N_PASS_T = TNr > 0 ? (ALIGNED ? (TNr + PPP - 1) / PPP : (TNr * TK + 63) / 64) : 3;
+                    // passes of 64 (rescuer, sensor) pairs held in registers at a time (sense_pass: the lane layout of a pass)
+                    const int n_pass = sense_n_pass<TK>(Nr, K);
+                    constexpr int N_PASS_T = TNr > 0 ? sense_n_pass<TK>(TNr, TK) : 3;
                     const float srange = DA.sensor_range, rad2 = DA.radius * DA.radius;  // G1
                     const float part_x = fresh(lane) < NP ? X[2 * lane] : 0.f, part_y = fresh(lane) < NP ? X[2 * lane + 1] : 0.f;
-                    // Conservative cull (as in waterworld.hip): NEAR[i] = objects with d2 <= (rad2 + range^2) * (1 + 1e-4); all others
-                    // would yield INFINITY for every sensor of rescuer i and are skipped per pass.
+                    // Conservative cull: NEAR[i] marks the objects within rescuer i's sensing reach (the key: bit NP, the bomb: bit NP + 1); all
+                    // others would yield INFINITY for every sensor of the rescuer and are skipped per pass.
                     {
-                        const float thr2 = (rad2 + srange * srange) * 1.0001f + 1e-9f;
+                        const float thr2 = sensor_reach2(rad2, srange);
                         const float mx = fresh(lane) == NP ? kx : (fresh(lane) == NP + 1 ? bx : part_x), my = fresh(lane) == NP ? ky : (fresh(lane) == NP + 1 ? by : part_y);
-                        for (int i = 0; i < Nr; ++i) {
-                            const float rx = mx - bcast(part_x, i), ry = my - bcast(part_y, i);
-                            const uint64_t mk = __ballot((fresh(lane) <= NP + 1) && (rx * rx + ry * ry <= thr2));
-                            if (fresh(lane) == 0) NEAR[i] = mk;
-                        }
+                        reach_cull(NEAR, Nr, part_x, part_y, mx, my, thr2, [&]() { return fresh(lane) <= NP + 1; }, [&]() { return fresh(lane) == 0; });
                         wave_sync();
                     }
                     // ONE PASS AT A TIME (round 6, as in waterworld.hip): a pass walks the set bits of ITS OWN reach mask (ascending = the
@@ -287,78 +245,42 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                     // to a spare row instead of branching around the stores.
 #pragma unroll
                     for (int pass_q = 0; pass_q < (TNr > 0 ? N_PASS_T : n_pass); ++pass_q) {
-                        int i_first, i_last;  // rescuers of this pass
-                        bool okq;
-                        int iq, kq;
-                        if constexpr (ALIGNED) {
-                            const int li = lane / K;
-                            i_first = pass_q * PPP; i_last = min(i_first + PPP, Nr) - 1;
-                            okq = li < PPP && i_first + li <= i_last;
-                            iq = okq ? i_first + li : 0;
-                            kq = okq ? lane - li * K : 0;
-                        } else {
-                            const int idx = 64 * pass_q + lane;
-                            okq = idx < Nr * K;
-                            iq = okq ? idx / K : 0;
-                            kq = okq ? idx - iq * K : 0;
-                            i_first = 64 * pass_q / K; i_last = min(64 * pass_q + 63, Nr * K - 1) / K;
-                        }
+                        const SensePass sp = sense_pass<TK>(pass_q, Nr, K, lane);  // the rescuers of this pass, this lane's (rescuer, sensor)
+                        const bool okq = sp.okq;
+                        const int iq = sp.iq, kq = sp.kq;
                         const float sxq = SEN[2 * kq], syq = SEN[2 * kq + 1];
                         const float pxq = X[2 * iq], pyq = X[2 * iq + 1];
-                        uint64_t u = 0ull;
-                        for (int i = i_first; i <= i_last; ++i) u |= NEAR[i];
-                        // wave-uniform: objects in reach of any rescuer of this pass
-                        const uint64_t reach = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u)) |
-                                               ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32)) << 32);
+                        const uint64_t reach = pass_reach(NEAR, sp.i_first, sp.i_last);  // wave-uniform: objects in reach of any rescuer of this pass
                         auto sense = [&](float qx, float qy) -> float {
-                            const float rx = qx - pxq, ry = qy - pyq;
-                            const float sv = sxq * rx + syq * ry;
-                            const float d2 = rx * rx + ry * ry;
-                            // sv < 0 || sv > srange as ONE compare: the median of (sv, 0, srange) is sv exactly when 0 <= sv <= srange (waterworld.hip)
-                            const bool out = (__builtin_amdgcn_fmed3f(sv, 0.f, srange) != sv) | (d2 - sv * sv > rad2);
+                            float sv;
+                            const bool out = ray_misses(sxq, syq, pxq, pyq, qx, qy, srange, rad2, sv);
                             return out ? INFINITY : sv;
                         };
                         float b_cr = INFINITY, b_ho = INFINITY;
                         int a_cr = 0;
                         if (TNr > 0 && Nc <= 32 && Nh <= 32) {   // 32-bit class masks: half the scalar work of the walk
-                            uint32_t todo = (uint32_t)(reach >> (Nr + Nh)) & (Nc >= 32 ? 0xFFFFFFFFu : ((1u << Nc) - 1u));
-#pragma nounroll
-                            while (todo != 0u) {
-                                const int m = __builtin_ctz(todo);
-                                todo &= todo - 1u;
+                            walk_bits((uint32_t)(reach >> (Nr + Nh)) & low_bits32(Nc), [&](int m) {
                                 const float sv = sense(bcast(part_x, Nr + Nh + m), bcast(part_y, Nr + Nh + m));
                                 const bool better = sv < b_cr;
                                 b_cr = better ? sv : b_cr;
                                 a_cr = better ? m : a_cr;
-                            }
+                            });
                             // hostages: the saved ones (mask from before this step's processing, G5, :296) are not sensed
-                            todo = (uint32_t)(reach >> Nr) & (Nh >= 32 ? 0xFFFFFFFFu : ((1u << Nh) - 1u)) & ~(uint32_t)saved;
-#pragma nounroll
-                            while (todo != 0u) {
-                                const int m = __builtin_ctz(todo);
-                                todo &= todo - 1u;
+                            walk_bits((uint32_t)(reach >> Nr) & low_bits32(Nh) & ~(uint32_t)saved, [&](int m) {
                                 const float sv = sense(bcast(part_x, Nr + m), bcast(part_y, Nr + m));
                                 b_ho = sv < b_ho ? sv : b_ho;
-                            }
+                            });
                         } else {
-                            uint64_t todo = reach & ((((Nc >= 64) ? ~0ull : ((1ull << Nc) - 1ull))) << (Nr + Nh));
-#pragma nounroll
-                            while (todo != 0ull) {
-                                const int bit = __builtin_ctzll(todo);
-                                todo &= todo - 1ull;
+                            walk_bits(reach & (low_bits64(Nc) << (Nr + Nh)), [&](int bit) {
                                 const float sv = sense(bcast(part_x, bit), bcast(part_y, bit));
                                 const bool better = sv < b_cr;
                                 b_cr = better ? sv : b_cr;
                                 a_cr = better ? bit - (Nr + Nh) : a_cr;
-                            }
-                            todo = reach & (((((Nh >= 64) ? ~0ull : ((1ull << Nh) - 1ull))) & ~saved) << Nr);
-#pragma nounroll
-                            while (todo != 0ull) {
-                                const int bit = __builtin_ctzll(todo);
-                                todo &= todo - 1ull;
+                            });
+                            walk_bits(reach & ((low_bits64(Nh) & ~saved) << Nr), [&](int bit) {
                                 const float sv = sense(bcast(part_x, bit), bcast(part_y, bit));
                                 b_ho = sv < b_ho ? sv : b_ho;
-                            }
+                            });
                         }
                         const float b_ke = ((reach >> NP) & 1ull) ? sense(kx, ky) : INFINITY;
                         const float b_bo = ((reach >> (NP + 1)) & 1ull) ? sense(bx, by) : INFINITY;
@@ -366,7 +288,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                             float *o = okq ? O + iq * D : O_SPARE;
                             const bool fin = b_cr < INFINITY;
                             const int j = Nr + Nh + a_cr;   // (a_cr = 0 without a hit: a valid particle, its value is not used)
-                            const float raw = sxq * (V[2 * j] - V[2 * iq]) + syq * (V[2 * j + 1] - V[2 * iq + 1]);   // :204-226; loaded and computed unconditionally: a select, no branch
+                            const float raw = speed_along(V, sxq, syq, j, iq);   // :204-226; loaded and computed unconditionally: a select, no branch
                             o[kq] = fin ? b_cr : 0.f;
                             o[K + kq] = fin ? raw : 0.f;
                             o[2 * K + kq] = (gate0 && b_ho < INFINITY) ? b_ho : 0.f;   // :320-322
@@ -387,17 +309,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                         w_enc = (row_ho & (enc_mask >> Nr)) != 0ull;            // touches an encountered hostage
                         w_cr = (row_cr & (caught_mask >> (Nr + Nh))) != 0ull;   // touches a caught criminal
                     } else {
-                    for (int j = 0; j < Nh; ++j) {
-                        const bool c = COLH[lane * Nh + j];
-                        t_ho |= c;
-                        w_ho |= c && FLG[j];
-                        w_enc |= c && FLG[Nh + j];
-                    }
-                    for (int j = 0; j < Nc; ++j) {
-                        const bool c = COLC[lane * Nc + j];
-                        t_cr |= c;
-                        w_cr |= c && FLG[2 * Nh + j];
-                    }
+                        agent_contacts(COLH, COLC, FLG, lane, Nh, Nc, t_ho, w_ho, w_enc, t_cr, w_cr);
                     }
                 }
                 wave_sync();
@@ -436,9 +348,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                 // phase F: criminals move; velocity flips only if BOTH coordinates left [0,1], no clipping (G7, :402-408)
                 if (fresh(lane) >= Nr + Nh && fresh(lane) < NP) {
                     float x = X[2 * lane], y = X[2 * lane + 1], vx = V[2 * lane], vy = V[2 * lane + 1];
-                    x = x + vx; y = y + vy;
-                    const bool outx = !(x >= 0.f && x <= 1.f), outy = !(y >= 0.f && y <= 1.f);
-                    if (outx && outy) { vx = -1.0f * vx; vy = -1.0f * vy; }
+                    free_motion(x, y, vx, vy);
                     X[2 * lane] = x; X[2 * lane + 1] = y; V[2 * lane] = vx; V[2 * lane + 1] = vy;
                 }
                 if (fresh(lane) < Nr) {  // tail of the observation row (:410-425)
@@ -448,13 +358,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                     if (DA.addid) o[5] = (float)(lane + 1);
                 }
                 tstep += 1;  // :427
-                const uint64_t all_h = (Nh >= 64) ? ~0ull : ((1ull << Nh) - 1ull);
+                const uint64_t all_h = low_bits64(Nh);
                 const int limit = DA.max_steps > 0 ? DA.max_steps : 1000;  // timestep_limit :118-120
                 const bool is_done = (flags & 2u) || ((saved & all_h) == all_h) || tstep >= limit;  // :179-182
                 if (is_done && fresh(lane) < Nr) reward += (float)(Nh - __popcll(saved & all_h)) * DA.not_saved_reward;  // :429-430
                 wave_sync();
 
-                if (pass == 0) asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt_act));  // pipeline hinge
+                if (pass == 0) nxt.hinge();  // pipeline hinge
                 // ---------------------------------------------------- outputs
 #if MADRL_HW_ABLATE & 8
                 if (DA.n_envs < 0)
@@ -462,20 +372,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                 if (MODE == 1 && !do_init) {
                     if (fresh(lane) < Nr) uniform_ptr(IOA.rew + env * Nr)[ulane] = reward;
                     if constexpr (FUSED) {  // StandardizedEnv.step :283-291, the operations of wrappers.hip rewnorm_kernel in its order
-                        if (IOA.st->rew_out != nullptr && fresh(lane) < Nr) {
-                            const ParticleStd &st = *IOA.st;
-                            const int64_t i = env * Nr + lane;
-                            double r = (double)reward;
-                            if (st.enable_rewnorm) {
-                                const double m = (1.0 - st.rew_alpha) * st.rew_mean[i] + st.rew_alpha * r;         // :253-254
-                                const double dd = r - m;
-                                const double v = (1.0 - st.rew_alpha) * st.rew_var[i] + st.rew_alpha * (dd * dd);  // :255-257
-                                st.rew_mean[i] = m;
-                                st.rew_var[i] = v;
-                                r = r / (sqrt(v) + st.eps);                                                      // :268-271
-                            }
-                            st.rew_out[i] = (float)(st.scale * r);                                              // :290
-                        }
+                        if (IOA.st->rew_out != nullptr && fresh(lane) < Nr) std_reward(*IOA.st, env * Nr + lane, reward);
                     }
                     if (fresh(lane) == 0) {
                         IOA.done[env] = (uint8_t)is_done;
@@ -510,39 +407,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                     // by value: through a reference into global memory every float64 store of the loop could have changed alpha, eps and the
                     // pointers (type-based aliasing), and the compiler would load them again behind each one
                     const ParticleStd st = *IOA.st;
-                    if (st.enable_obsnorm) {
-                        // batches of 4 elements per lane: all 8 statistics loads of a batch are in flight before the first dependent float64
-                        // operation (waterworld.hip: element by element 421, batched 357 us per wrapped step).  The operations of wrappers.hip
-                        // obsnorm_kernel / obsnorm_one in their order; every statistics byte is touched once per step: non-temporal.
-                        double *__restrict__ gm = st.obs_mean + base;
-                        double *__restrict__ gv = st.obs_var + base;
-                        float *__restrict__ go = st.obs_out + base;
-                        const double alpha = st.obs_alpha, eps = st.eps;
-                        for (int e0 = lane; e0 < n_el; e0 += 256) {
-                            double m[4], v[4];
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) {
-                                const int e = e0 + 64 * u;
-                                m[u] = e < n_el ? __builtin_nontemporal_load(&gm[e]) : 0.0;
-                                v[u] = e < n_el ? __builtin_nontemporal_load(&gv[e]) : 1.0;
-                            }
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) {
-                                const int e = e0 + 64 * u;
-                                if (e < n_el) {
-                                    const double x = (double)O[e];
-                                    const double mm = (1.0 - alpha) * m[u] + alpha * x;          // :245-246
-                                    const double dd = x - mm;
-                                    const double vv = (1.0 - alpha) * v[u] + alpha * (dd * dd);  // :247-249
-                                    __builtin_nontemporal_store(mm, &gm[e]);
-                                    __builtin_nontemporal_store(vv, &gv[e]);
-                                    __builtin_nontemporal_store((float)((x - mm) / (sqrt(vv) + eps)), &go[e]);  // :262-263
-                                }
-                            }
-                        }
-                    } else {
-                        for (int e = lane; e < n_el; e += 64) st.obs_out[base + e] = O[e];
-                    }
+                    std_obs_row(st, O, base, n_el, lane);
                 }
                 wave_sync();
             }
@@ -554,18 +419,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
                 SU[OFF_TICK] = tick;
             }
             wave_sync();
-            {
-                const auto dst = uniform_ptr(reinterpret_cast<uint32_t *>(DA.state) + env * (int64_t)rec_dw);
 #if MADRL_HW_ABLATE & 4
-                if (DA.n_envs < 0)
+            if (DA.n_envs < 0)
 #endif
-                for (uint32_t k = ulane; k < (uint32_t)rec_dw; k += 64u) dst[k] = SU[k];
-            }
+            store_record<HwKArgs>(SU, env, rec_dw, ulane);
             wave_sync();
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
-        cur_act = nxt_act;
+        cur = nxt;
     }
 }
 #undef DA
@@ -575,10 +435,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MADRL_HW_OCC
 }  // namespace
 
 // =================================================================== host side / C ABI
-struct madrl_hostage : ParticleHandle<madrl_hostage_config, HwDev> {
-    const int32_t *pending;  // madrl_hostage_set_particle_counts: caller-owned [n_envs][3], both NULL = one shape for all envs
-    int32_t *live;
-};
+struct madrl_hostage : ParticleHandle<madrl_hostage_config, HwDev> {};
 
 namespace {
 
@@ -634,11 +491,7 @@ void hw_layout(const madrl_hostage_config *c, HwDev *d) {
     d->sq_bomb = sq_threshold(d->radius + d->bomb_radius); d->sq_key = sq_threshold(d->radius + d->key_radius);
 }
 
-size_t hw_lds_bytes(const HwDev &d) {
-    size_t f = align_up((size_t)d.rec_dw, 4) + align_up((size_t)(d.Nr + 1) * d.D, 4) + align_up((size_t)2 * d.K, 4);   // (Nr + 1: the spare row of the sensing phase)
-    size_t b = f * 4 + 8 * (size_t)d.Nr + (size_t)d.Nr * (d.Nh + d.Nc) + 2 * (size_t)d.Nh + d.Nc;
-    return align_up(b, 16);
-}
+size_t hw_lds_bytes(const HwDev &d) { return wave_lds_bytes(d.rec_dw, d.Nr, d.D, d.K, d.Nh, d.Nc); }
 
 size_t hw_lds_bytes_crowd(const HwDev &d) { return hw_crowd_lds_bytes(d.Nr, d.Nh, d.Nc, d.K, d.rec_dw); }
 
@@ -732,13 +585,7 @@ int madrl_hostage_set_standardize(madrl_hostage *h, const madrl_standardize_args
 int madrl_hostage_set_launch(madrl_hostage *h, int64_t max_blocks) { return particle_set_launch(h, max_blocks); }
 
 int madrl_hostage_set_particle_counts(madrl_hostage *h, const int32_t *pending_dev, int32_t *live_dev) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    if (!h->cfg.crowd) return fail(MADRL_EINVAL, "set_particle_counts: per-env particle counts run on the crowd kernel (cfg.crowd = 1)");
-    if ((pending_dev == nullptr) != (live_dev == nullptr))
-        return fail(MADRL_EINVAL, "set_particle_counts: pending_dev and live_dev are both arrays or both NULL");
-    h->pending = pending_dev;
-    h->live = live_dev;
-    return MADRL_OK;
+    return particle_set_counts(h, pending_dev, live_dev);
 }
 
 int madrl_hostage_reset(madrl_hostage *h, const uint8_t *mask_dev, float *obs_dev, void *stream) {
@@ -752,21 +599,13 @@ int madrl_hostage_step(madrl_hostage *h, const float *actions_dev, const float *
 
 int madrl_hostage_get_state(madrl_hostage *h, float *pos, float *vel, float *key, float *bomb, uint64_t *saved, uint8_t *flags, int32_t *t,
                             uint32_t *tick, void *stream) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    const unsigned blocks = (unsigned)((h->dev.n_envs + 127) / 128);
-    hipLaunchKernelGGL(hw_state_copy_kernel, dim3(blocks), dim3(128), 0, (hipStream_t)stream, h->dev, pos, vel, key, bomb, saved, flags, t, tick, 0);
-    MADRL_HIP_TRY(hipGetLastError());
-    return MADRL_OK;
+    return state_copy_launch(h, hw_state_copy_kernel, stream, pos, vel, key, bomb, saved, flags, t, tick, 0);
 }
 
 int madrl_hostage_set_state(madrl_hostage *h, const float *pos, const float *vel, const float *key, const float *bomb, const uint64_t *saved,
                             const uint8_t *flags, const int32_t *t, const uint32_t *tick, void *stream) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    const unsigned blocks = (unsigned)((h->dev.n_envs + 127) / 128);
-    hipLaunchKernelGGL(hw_state_copy_kernel, dim3(blocks), dim3(128), 0, (hipStream_t)stream, h->dev, (float *)pos, (float *)vel, (float *)key,
-                       (float *)bomb, (uint64_t *)saved, (uint8_t *)flags, (int32_t *)t, (uint32_t *)tick, 1);
-    MADRL_HIP_TRY(hipGetLastError());
-    return MADRL_OK;
+    return state_copy_launch(h, hw_state_copy_kernel, stream, (float *)pos, (float *)vel, (float *)key, (float *)bomb, (uint64_t *)saved,
+                             (uint8_t *)flags, (int32_t *)t, (uint32_t *)tick, 1);
 }
 
 }  // extern "C"

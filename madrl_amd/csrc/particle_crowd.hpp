@@ -6,6 +6,7 @@
 // 128 agents (pursuers / rescuers: a thread owns at most one), any sensor count.  Reached on request only (config.crowd = 1); the results
 // are those of the one-wavefront kernel and of the float32 C restatement of the reference the tests use ("the oracle") bit for bit: every
 // float expression keeps the oracle's statement order, and whatever the oracle does in a loop whose order matters is done in that order.
+// integrate_agent, free_motion and sensor_reach2, the float text the one-wavefront kernels use too, are in common.hpp.
 // The helpers below take the LDS arrays and the counts as arguments and know nothing of a world's structs; each .hip is its world's step
 // in the oracle's order and keeps what is its own (reset, obstacle / gate / key / bomb, flags and row tail, rewards, respawn draws, done).
 //
@@ -33,8 +34,6 @@
 
 namespace madrl {
 
-__host__ __device__ inline int up4(int v) { return (v + 3) & ~3; }
-
 // Per-env particle counts (madrl_waterworld_set_particle_counts, madrl_hostage_set_particle_counts): the two caller-owned int32
 // [n_envs][3] arrays of the live-count entries (*_crowd_kernel_live), in the world's class order, the agents first
 struct ParticleCounts {
@@ -57,13 +56,7 @@ __device__ __forceinline__ void drive_agent(bool live, const float *actions, int
     const float a0 = r0 * action_scale, a1 = r1 * action_scale;
     ACT[2 * i] = a0;
     ACT[2 * i + 1] = a1;
-    vx = vx + a0; vy = vy + a1;
-    x = x + vx; y = y + vy;
-    const float cx = x < 0.f ? 0.f : (x > 1.f ? 1.f : x);
-    const float cy = y < 0.f ? 0.f : (y > 1.f ? 1.f : y);
-    if (x != cx) vx = 0.f;
-    if (y != cy) vy = 0.f;
-    x = cx; y = cy;
+    integrate_agent(a0, a1, x, y, vx, vy);
 }
 
 // ---- phases B1 / B2.  A collision row is W 64-bit words per agent: `first_words` chunks of the first class, then the chunks of the second.
@@ -134,10 +127,6 @@ __device__ __forceinline__ PassLanes pass_lanes(const PassShape &s, int p, int K
     return {i_first, i_cnt, i_first + (okq ? s.li : 0), okq ? k0 : 0, okq};
 }
 
-// A sensor of agent i can only return a finite value for an object with d2 <= rad2 + sv^2 <= rad2 + range^2 (plus a relative margin far
-// above the rounding of the test itself): everything else yields +inf in the oracle and never becomes a minimum.
-__device__ __forceinline__ float sensor_reach2(float rad2, float srange) { return (rad2 + srange * srange) * 1.0001f + 1e-9f; }
-
 // One (agent, sensor) lane's ray and its running first minimum (b, bi) over the objects visited in index order.
 struct Ray {
     float sxq, syq, pxq, pyq, pvx, pvy;  // the sensor's unit vector, the sensing agent's position and velocity
@@ -191,13 +180,6 @@ __device__ __forceinline__ void reach_walk(const float *X, int lo, int cnt, cons
             visit(m2, qp.x, qp.y);
         }
     }
-}
-
-// ---- phase E.  A non-agent moves; its velocity flips only if BOTH coordinates left [0, 1], and nothing is clipped.
-__device__ __forceinline__ void free_motion(float &x, float &y, float &vx, float &vy) {
-    x = x + vx; y = y + vy;
-    const bool outx = !(x >= 0.f && x <= 1.f), outy = !(y >= 0.f && y <= 1.f);
-    if (outx && outy) { vx = -1.0f * vx; vy = -1.0f * vy; }
 }
 
 // ---- host.  `kernel`: the reset or the step instantiation; dev / io: the world's Dev and IO structs behind the untyped pointers of *_dev.hpp

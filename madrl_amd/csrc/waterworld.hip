@@ -20,11 +20,16 @@
 //   step phases ........ MAWaterWorld.step :220-436      sensing ...... Archea.sensed :64-72
 //   catch rule ......... _caught :180-193                 respawn ...... _respawn :139-142, :355-374
 //   reset .............. :144-172 (ends with a zero-action step, W11)
+// The device code this kernel has in common with hostage_kernel (hostage.hip) -- the record pipeline, the action and control penalty, the
+// generic path's collision bytes, the sensing passes, reach masks, ray test and bit walks, the fused StandardizedEnv epilogue -- is in
+// particle_wave.hpp; this file is Waterworld's step in the reference's order and what is its own: the reset draws, the obstacle, the
+// ballot form of the collision matrices (BITROWS), the row tail, rewards, respawn and done.
 // Envs beyond a wavefront's worth of particles (more than 62, or more than 32 pursuers) run on ww_crowd_kernel (waterworld_crowd.hip) when
 // the handle was created with cfg.crowd = 1; the handle, validation, record layout and dispatch of both kernels are in this file.
 // Arithmetic is float32 (north_star tolerance 1e-5 against the float64 reference); every
 // expression keeps the statement order of the reference's step() so that a float32 CPU restatement agrees bit for bit.
 #include "waterworld_dev.hpp"   // WwDev, WwIO, the RNG tags: shared with waterworld_crowd.hip
+#include "particle_wave.hpp"    // the device code this kernel shares with hostage_kernel (hostage.hip)
 
 #include <math.h>
 #include <string.h>
@@ -63,8 +68,7 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
     // The specialised shape has a compile-time LDS layout in a STATIC array (launched with 0 dynamic bytes): every LDS address is
     // "lane-dependent register + immediate offset".  With the dynamic array the base is a link-time symbol the compiler adds in
     // registers, hoists out of the env loop per access pattern and -- at 5 waves per SIMD -- spills.
-    constexpr int SPEC_DW = TNp > 0 ? ((4 * (TNp + TNe + TNpo) + 4 + 3) / 4 * 4 + ((TNp + 1) * (TD > 0 ? TD : 1) + 3) / 4 * 4 + (2 * TK + 3) / 4 * 4) : 0;   // (TNp + 1: the spare row)
-    constexpr int SPEC_BYTES = TNp > 0 ? (SPEC_DW * 4 + 8 * TNp + TNp * (TNe + TNpo) + 2 * TNe + TNpo + 15) / 16 * 16 : 16;
+    constexpr int SPEC_BYTES = TNp > 0 ? (int)wave_lds_bytes(4 * (TNp + TNe + TNpo) + 4, TNp, TD, TK, TNe, TNpo) : 16;
     static_assert(TNp == 0 || TD > 0, "a specialised shape fixes the observation width too");
     extern __shared__ __attribute__((aligned(16))) float smem_dyn[];
     __shared__ __attribute__((aligned(16))) float smem_static[SPEC_BYTES / 4];
@@ -91,47 +95,29 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
     uint8_t *FLG = COLP + Np * Npo;                     // caught_ev[Ne] | enc_ev[Ne] | caught_po[Npo]
 
     for (int k = lane; k < 2 * K; k += 64) SEN[k] = d.sensors[k];
-    const int rec_dw = TNp > 0 ? (4 * (TNp + TNe + TNpo) + 4 + 3) / 4 * 4 : d.rec_dw;
-    const int nreg = (rec_dw + 63) >> 6;  // <= 4 (NP <= 62)
+    const int rec_dw = TNp > 0 ? (4 * (TNp + TNe + TNpo) + 4 + 3) / 4 * 4 : d.rec_dw;  // <= 4 dwords per lane (NP <= 62)
 
     // ---- software pipeline: next env's record + action row are fetched one env ahead
-    uint32_t cur[4] = {0, 0, 0, 0};
-    float cur_act = 0.0f;
-    auto fetch = [&](int64_t env, uint32_t (&r)[4], float &a) {
-        const auto src = uniform_ptr(reinterpret_cast<const uint32_t *>(DA.state) + env * (int64_t)rec_dw);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t k = ulane + 64u * q;
-            r[q] = (q < nreg && (int)k < rec_dw) ? src[k] : 0u;
-        }
-        if constexpr (MODE == 1) a = (lane < 2 * Np) ? uniform_ptr(IOA.actions + env * 2 * Np)[ulane] : 0.0f;
-        else a = 0.0f;
-    };
+    WaveRecord cur;
     const int n_envs = (int)d.n_envs;
-    if ((int)blockIdx.x < n_envs) fetch(blockIdx.x, cur, cur_act);
-    asm volatile("" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur_act));
+    if ((int)blockIdx.x < n_envs) cur.fetch<MODE, WwKArgs>(blockIdx.x, rec_dw, Np, lane, ulane);
+    cur.hinge();
     wave_sync();
 
     for (int e32 = blockIdx.x; e32 < n_envs; e32 += (int)gridDim.x) {  // env indices are 32-bit (n_envs < 2^31 - grid), byte offsets 64-bit
         const int64_t env = e32;
         const int n32 = e32 + (int)gridDim.x;
-        uint32_t nxt[4] = {0, 0, 0, 0};
-        float nxt_act = 0.0f;
-        if (n32 < n_envs) fetch(n32, nxt, nxt_act);
+        WaveRecord nxt;
+        if (n32 < n_envs) nxt.fetch<MODE, WwKArgs>(n32, rec_dw, Np, lane, ulane);
         bool skip = false;
         if constexpr (MODE == 0) skip = (IOA.mask != nullptr && IOA.mask[env] == 0);
         if (!skip) {
-            // record -> LDS
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int k = lane + 64 * q;
-                if (q < nreg && k < rec_dw) reinterpret_cast<uint32_t *>(S)[k] = cur[q];
-            }
+            cur.to_lds(reinterpret_cast<uint32_t *>(S), rec_dw, lane);
             wave_sync();
             int32_t tstep = reinterpret_cast<int32_t *>(S)[4 * NP + 2];
             uint32_t tick = reinterpret_cast<uint32_t *>(S)[4 * NP + 3];
             const uint32_t gid = DA.gid_base + (uint32_t)env;
-            float act_lane = cur_act;  // lane 2i / 2i+1 hold pursuer i's action components
+            float act_lane = cur.act;  // lane 2i / 2i+1 hold pursuer i's action components
 
             bool do_init = (MODE == 0);
             int npass = 1;
@@ -176,31 +162,14 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                 // phase A: particles
                 float reward = 0.0f;
                 {
-                    const float a_raw0 = __shfl(act_lane, 2 * (LANE_LT(Np) ? lane : 0));
-                    const float a_raw1 = __shfl(act_lane, 2 * (LANE_LT(Np) ? lane : 0) + 1);
-                    const float a0 = a_raw0 * DA.action_scale, a1 = a_raw1 * DA.action_scale;  // :224
-                    float pen_local = DA.control_penalty * (a0 * a0 + a1 * a1);
-                    if (DA.reward_global) {  // (actions**2).sum(), row-major (:234-235, W12)
-                        float s = 0.0f;
-                        for (int i = 0; i < Np; ++i) {
-                            const float b0 = __shfl(a0, i), b1 = __shfl(a1, i);
-                            s += b0 * b0;
-                            s += b1 * b1;
-                        }
-                        pen_local = DA.control_penalty * s;
-                    }
+                    float a0, a1;  // :224; the penalty: :233-237, under the global reward (actions**2).sum() row-major (:234-235, W12)
+                    const float pen_local = agent_action<WwKArgs>(act_lane, [&]() { return LANE_LT(Np) ? lane : 0; }, Np, a0, a1);
                     if (LANE_LT(NP)) {
                         float x = X[2 * lane], y = X[2 * lane + 1], vx = V[2 * lane], vy = V[2 * lane + 1];
                         float sq_obst = DA.sq_obst_po, f = -1.0f;
                         if (LANE_LT(Np)) {
-                            vx = vx + a0; vy = vy + a1;  // :229-231
-                            x = x + vx; y = y + vy;
+                            integrate_agent(a0, a1, x, y, vx, vy);  // :229-231, walls :239-245
                             reward = 0.0f + pen_local;   // :233-237
-                            const float cx = x < 0.f ? 0.f : (x > 1.f ? 1.f : x);  // :239-245
-                            const float cy = y < 0.f ? 0.f : (y > 1.f ? 1.f : y);
-                            if (x != cx) vx = 0.f;
-                            if (y != cy) vy = 0.f;
-                            x = cx; y = cy;
                             sq_obst = DA.sq_obst_pu; f = -0.5f;
                         } else if (LANE_LT(Np + Ne)) {
                             sq_obst = DA.sq_obst_ev; f = -0.5f;
@@ -270,30 +239,19 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
 #if MADRL_WW_ABLATE & 4
                 if (DA.n_envs < 0)
 #endif
-                for (int idx = lane; idx < Np * (Ne + Npo); idx += 64) {
-                    const bool is_ev = idx < Np * Ne;
-                    const int r = is_ev ? idx : idx - Np * Ne;
-                    const int n2 = is_ev ? Ne : Npo;
-                    const int i = r / n2, m = r % n2;
-                    const int j = (is_ev ? Np : Np + Ne) + m;
-                    COL[idx] = dist2_le(X[2 * i], X[2 * i + 1], X[2 * j], X[2 * j + 1], is_ev ? DA.sq_hit_ev : DA.sq_hit_po);
-                }
+                contact_bytes(X, COL, Np, Ne, Npo, lane, [&](bool is_ev) { return is_ev ? DA.sq_hit_ev : DA.sq_hit_po; });
                 wave_sync();
                 // _caught (:180-193): evader lanes / poison lanes count their column
                 if ((!LANE_LT(Np) && LANE_LT(NP))) {
                     const bool is_ev = LANE_LT(Np + Ne);
                     const int m = is_ev ? lane - Np : lane - Np - Ne;
-                    const uint8_t *col = is_ev ? COL : COLP;
-                    const int n2 = is_ev ? Ne : Npo;
-                    int s = 0;
-                    for (int i = 0; i < Np; ++i) s += col[i * n2 + m];
+                    const int s = column_count(is_ev ? COL : COLP, Np, is_ev ? Ne : Npo, m);
                     my_caught = s >= (is_ev ? DA.n_coop : 1);
                     my_enc = is_ev && s >= 1;
-                    if (is_ev) { FLG[m] = my_caught; FLG[Ne + m] = my_enc; }
-                    else FLG[2 * Ne + m] = my_caught;
+                    column_flags(FLG, is_ev, Ne, m, my_caught, my_enc);
                 }
                 }
-                const uint64_t ev_lanes = ((Ne >= 64) ? ~0ull : ((1ull << Ne) - 1ull)) << Np;
+                const uint64_t ev_lanes = low_bits64(Ne) << Np;
                 const uint64_t caught_mask = __ballot(my_caught);
                 const uint64_t enc_mask = __ballot(my_enc);
                 const int n_evc = __popcll(caught_mask & ev_lanes);
@@ -306,27 +264,16 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                 // against are wave-uniform, so each object's position is broadcast ONCE from the register of the lane that
                 // owns the particle (v_readlane -> SGPR operand) and reused by all passes: the inner loop is pure VALU, no
                 // LDS round trip per (pair, object).  Arithmetic and comparison order per pair are those of the reference loop.
-                // passes of 64 (pursuer, sensor) pairs held in registers at a time: no more than the specialised shape needs
-                // Lane layout of a pass.  ALIGNED (compile-time K <= 64): a pass holds floor(64 / K) WHOLE pursuers (the last lanes idle), so
-                // the objects a pass must visit are those in reach of 2 pursuers at BASELINE C3 instead of the 2.1-3 a pass of 64
-                // consecutive (pursuer, sensor) pairs straddles: about a quarter fewer (object, pass) visits.  Otherwise: consecutive pairs.
-                constexpr bool ALIGNED = TK > 0 && TK <= 64;
-                constexpr int PPP = ALIGNED ? 64 / (TK > 0 ? TK : 1) : 1;  // pursuers per pass
-                const int n_pass = ALIGNED ? (Np + PPP - 1) / PPP : (Np * K + 63) / 64;
-                constexpr int N_PASS_T = TNp > 0 ? (ALIGNED ? (TNp + PPP - 1) / PPP : (TNp * TK + 63) / 64) : 3;
+                // passes of 64 (pursuer, sensor) pairs held in registers at a time (sense_pass: the lane layout of a pass)
+                const int n_pass = sense_n_pass<TK>(Np, K);
+                constexpr int N_PASS_T = TNp > 0 ? sense_n_pass<TK>(TNp, TK) : 3;
                 const float part_x = LANE_LT(NP) ? X[2 * lane] : 0.f, part_y = LANE_LT(NP) ? X[2 * lane + 1] : 0.f;
-                // Conservative cull: a sensor of pursuer i can only return a finite value for an object with
-                // d2 <= rad2 + sv^2 <= rad2 + range^2; NEAR[i] marks the objects within that reach plus a 1e-4 relative margin
-                // (d2 is computed exactly as in the test below), everything else would yield INFINITY and is skipped per pass.
+                // Conservative cull: NEAR[i] marks the objects within pursuer i's sensing reach (the obstacle: bit NP); everything else
+                // would yield INFINITY for every sensor of the pursuer and is skipped per pass.
                 {
-                    const float thr2 = (rad2 + srange * srange) * 1.0001f + 1e-9f;
+                    const float thr2 = sensor_reach2(rad2, srange);
                     const float mx = LANE_EQ(NP) ? ox : part_x, my = LANE_EQ(NP) ? oy : part_y;
-                    for (int i = 0; i < Np; ++i) {
-                        const float rx = mx - __int_as_float(__builtin_amdgcn_readlane(__float_as_int(part_x), i));
-                        const float ry = my - __int_as_float(__builtin_amdgcn_readlane(__float_as_int(part_y), i));
-                        const uint64_t mk = __ballot((LANE_LT(NP + 1)) && (rx * rx + ry * ry <= thr2));
-                        if (LANE_EQ(0)) NEAR[i] = mk;
-                    }
+                    reach_cull(NEAR, Np, part_x, part_y, mx, my, thr2, [&]() { return LANE_LT(NP + 1); }, [&]() { return LANE_EQ(0); });
                     wave_sync();
                 }
 #if MADRL_WW_ABLATE & 1
@@ -340,29 +287,12 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                 // one pass's lane constants and ONE running minimum are all that is live in the object loop.
 #pragma unroll
                 for (int pass_q = 0; pass_q < (TNp > 0 ? N_PASS_T : n_pass); ++pass_q) {
-                    int i_first, i_last;  // pursuers of this pass
-                    bool okq;
-                    int iq, kq;
-                    if constexpr (ALIGNED) {
-                        const int li = lane / K;
-                        i_first = pass_q * PPP; i_last = min(i_first + PPP, Np) - 1;
-                        okq = li < PPP && i_first + li <= i_last;
-                        iq = okq ? i_first + li : 0;
-                        kq = okq ? lane - li * K : 0;
-                    } else {
-                        const int idx = 64 * pass_q + lane;
-                        okq = idx < Np * K;
-                        iq = okq ? idx / K : 0;
-                        kq = okq ? idx - iq * K : 0;
-                        i_first = 64 * pass_q / K; i_last = min(64 * pass_q + 63, Np * K - 1) / K;
-                    }
+                    const SensePass sp = sense_pass<TK>(pass_q, Np, K, lane);  // the pursuers of this pass, this lane's (pursuer, sensor)
+                    const bool okq = sp.okq;
+                    const int iq = sp.iq, kq = sp.kq;
                     const float sxq = SEN[2 * kq], syq = SEN[2 * kq + 1];
                     const float pxq = X[2 * iq], pyq = X[2 * iq + 1];
-                    uint64_t u = 0ull;
-                    for (int i = i_first; i <= i_last; ++i) u |= NEAR[i];
-                    // wave-uniform: objects in reach of any pursuer of this pass
-                    const uint64_t reach = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u)) |
-                                           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32)) << 32);
+                    const uint64_t reach = pass_reach(NEAR, sp.i_first, sp.i_last);  // wave-uniform: objects in reach of any pursuer of this pass
                     // (a specialised shape fixes the row width, and with it whether the speed features are in the row: 7 K + 2 (+ 1) against 4 K + 2 (+ 1))
                     const bool speed = TNp > 0 ? (TD >= 7 * TK + 2) : (bool)DA.speed_features;
                     // lanes without a (pursuer, sensor) pair -- 4 of 64 in a pass of two pursuers, 34 in the last pass of C3 -- write their features
@@ -375,13 +305,9 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                         float b = INFINITY;
                         int bi = 0;
                         auto visit = [&](int m, float qx, float qy) {
-                            const float rx = qx - pxq, ry = qy - pyq;
-                            const float sv = sxq * rx + syq * ry;
-                            const float d2 = rx * rx + ry * ry;
-                            // branch-free (bitwise |, selects): no exec-mask round trips in the inner loop
-                            // sv < 0 || sv > srange as ONE compare: the median of (sv, 0, srange) is sv exactly when 0 <= sv <= srange (sv is finite;
-                            // -0.0 compares equal to the +0.0 the median may return, as it passes `sv < 0`)
-                            const bool out = (__builtin_amdgcn_fmed3f(sv, 0.f, srange) != sv) | (d2 - sv * sv > rad2) | ((cls == 3) & (m == iq));
+                            // branch-free (bitwise |, selects): no exec-mask round trips in the inner loop; a pursuer does not sense itself
+                            float sv;
+                            const bool out = ray_misses(sxq, syq, pxq, pyq, qx, qy, srange, rad2, sv) | ((cls == 3) & (m == iq));
                             // (the reference sets an excluded ray to +inf and takes the first minimum: an excluded ray is never "better", a kept one
                             // is when it is smaller -- the same minimum and the same first index without materialising the +inf)
                             const bool better = !out & (sv < b);
@@ -391,25 +317,17 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                         if (cls == 0) {
                             if ((reach >> NP) & 1ull) visit(0, ox, oy);
                         } else if (TNp > 0 && cnt <= 32) {
-                            uint32_t todo = (uint32_t)(reach >> lo) & (cnt >= 32 ? 0xFFFFFFFFu : ((1u << cnt) - 1u));
-#pragma nounroll
-                            while (todo != 0u) {
-                                const int m = __builtin_ctz(todo);
-                                todo &= todo - 1u;
+                            walk_bits((uint32_t)(reach >> lo) & low_bits32(cnt), [&](int m) {
                                 // the object's position: ONE uniform-address LDS read (a broadcast) instead of two v_readlane + their wait states --
                                 // the LDS pipe has room, the VALU port is what this kernel is bound by since the scalar work went
                                 const float2 qp = *reinterpret_cast<const float2 *>(&X[2 * (lo + m)]);
                                 visit(m, qp.x, qp.y);
-                            }
+                            });
                         } else {
-                            uint64_t todo = reach & ((((cnt >= 64) ? ~0ull : ((1ull << cnt) - 1ull))) << lo);
-#pragma nounroll
-                            while (todo != 0ull) {
-                                const int bit = __builtin_ctzll(todo);
-                                todo &= todo - 1ull;
+                            walk_bits(reach & (low_bits64(cnt) << lo), [&](int bit) {
                                 visit(bit - lo, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(part_x), bit)),
                                       __int_as_float(__builtin_amdgcn_readlane(__float_as_int(part_y), bit)));
-                            }
+                            });
                         }
                         // the features of (pass, class) go to the staging row now: nothing but ONE running minimum is held in registers
                         {
@@ -420,8 +338,8 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                                 o[kq] = fd;
                             } else {
                                 const int j = lo + bi;   // (bi = 0 without a hit: a valid particle, its value is not used)
-                                const float raw = sxq * (V[2 * j] - V[2 * iq]) + syq * (V[2 * j + 1] - V[2 * iq + 1]);   // loaded and computed
-                                const float fs = fin ? raw : 0.f;  // W5                                                  unconditionally: a select, no branch
+                                const float raw = speed_along(V, sxq, syq, j, iq);   // loaded and computed unconditionally: a select, no branch
+                                const float fs = fin ? raw : 0.f;  // W5
                                 if (speed) { o[(2 * cls - 1) * K + kq] = fd; o[2 * cls * K + kq] = fs; }
                                 else o[cls * K + kq] = fd;
                             }
@@ -446,17 +364,7 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                         we = (row_ev & (enc_mask >> Np)) != 0ull;              // touches an encountered evader
                         wp = (row_po & (caught_mask >> (Np + Ne))) != 0ull;    // touches a caught poison
                     } else {
-                    for (int e = 0; e < Ne; ++e) {
-                        const bool c = COL[lane * Ne + e];
-                        tev |= c;
-                        wc |= c && FLG[e];
-                        we |= c && FLG[Ne + e];
-                    }
-                    for (int p = 0; p < Npo; ++p) {
-                        const bool c = COLP[lane * Npo + p];
-                        tpo |= c;
-                        wp |= c && FLG[2 * Ne + p];
-                    }
+                        agent_contacts(COL, COLP, FLG, lane, Ne, Npo, tev, wc, we, tpo, wp);
                     }
                     float *o = O + lane * D + DA.nfeat * K;  // :411-428
                     o[0] = tev ? 1.f : 0.f;
@@ -503,9 +411,7 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                 // phase G: evaders / poisons move; velocity flips only if BOTH coordinates left [0,1] (W6)
                 if ((!LANE_LT(Np) && LANE_LT(NP))) {
                     float x = X[2 * lane], y = X[2 * lane + 1], vx = V[2 * lane], vy = V[2 * lane + 1];
-                    x = x + vx; y = y + vy;
-                    const bool outx = !(x >= 0.f && x <= 1.f), outy = !(y >= 0.f && y <= 1.f);
-                    if (outx && outy) { vx = -1.0f * vx; vy = -1.0f * vy; }
+                    free_motion(x, y, vx, vy);
                     X[2 * lane] = x; X[2 * lane + 1] = y; V[2 * lane] = vx; V[2 * lane + 1] = vy;
                 }
                 tstep += 1;  // :433
@@ -513,24 +419,11 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                 const bool is_done = tstep >= limit;                     // :174-178
                 wave_sync();
 
-                if (pass == 0) asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt_act));  // pipeline hinge
+                if (pass == 0) nxt.hinge();  // pipeline hinge
                 // ---------------------------------------------------- outputs
                 if (MODE == 1 && !do_init) {
                     if (LANE_LT(Np)) uniform_ptr(IOA.rew + env * Np)[ulane] = reward;
-                    if (FUSED && IOA.st->rew_out != nullptr && LANE_LT(Np)) {  // StandardizedEnv.step :283-291
-                        const ParticleStd &st = *IOA.st;
-                        const int64_t i = env * Np + lane;
-                        double r = (double)reward;
-                        if (st.enable_rewnorm) {
-                            const double m = (1.0 - st.rew_alpha) * st.rew_mean[i] + st.rew_alpha * r;      // :253-254
-                            const double dd = r - m;
-                            const double v = (1.0 - st.rew_alpha) * st.rew_var[i] + st.rew_alpha * (dd * dd);  // :255-257
-                            st.rew_mean[i] = m;
-                            st.rew_var[i] = v;
-                            r = r / (sqrt(v) + st.eps);                                                   // :268-271
-                        }
-                        st.rew_out[i] = (float)(st.scale * r);                                           // :290
-                    }
+                    if (FUSED && IOA.st->rew_out != nullptr && LANE_LT(Np)) std_reward(*IOA.st, env * Np + lane, reward);
                     if (LANE_EQ(0)) {
                         IOA.done[env] = (uint8_t)is_done;
                         IOA.info[2 * env] = n_evc;
@@ -557,41 +450,8 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                             *reinterpret_cast<__attribute__((address_space(1))) f4u *>(orow + 4 * e) = *reinterpret_cast<const f4a *>(O + 4 * e);
                         for (uint32_t e = 4u * n4 + ulane; e < (uint32_t)(Np * D); e += 64u) orow[e] = O[e];
                     }
-                    if (FUSED) {  // StandardizedEnv.standardize_obs :242-263
-                        const ParticleStd &st = *IOA.st;   // (hostage.hip reads these arguments by value and says why; this kernel keeps the reference)
-                        const int64_t base = env * (int64_t)(Np * D);
-                        if (st.enable_obsnorm) {
-                            // batches of 4 elements per lane: all 8 statistics loads of a batch are in flight before the first
-                            // dependent float64 operation (element by element the loop pays one HBM round trip each: 421 instead
-                            // of 357 us per wrapped step; 16-byte pair accesses on top measured no further gain)
-                            const int n_el = Np * D;
-                            const double *__restrict__ gm = st.obs_mean + base;
-                            const double *__restrict__ gv = st.obs_var + base;
-                            for (int e0 = lane; e0 < n_el; e0 += 256) {
-                                double m[4], v[4];
-#pragma unroll
-                                for (int u = 0; u < 4; ++u) {
-                                    const int e = e0 + 64 * u;
-                                    m[u] = e < n_el ? __builtin_nontemporal_load(&gm[e]) : 0.0;
-                                    v[u] = e < n_el ? __builtin_nontemporal_load(&gv[e]) : 1.0;
-                                }
-#pragma unroll
-                                for (int u = 0; u < 4; ++u) {
-                                    const int e = e0 + 64 * u;
-                                    if (e < n_el) {
-                                        const double x = (double)O[e];
-                                        double mm = m[u], vv = v[u];
-                                        ema_update(mm, vv, x, st.obs_alpha);                                  // :245-249
-                                        __builtin_nontemporal_store(mm, &st.obs_mean[base + e]);
-                                        __builtin_nontemporal_store(vv, &st.obs_var[base + e]);
-                                        __builtin_nontemporal_store((float)((x - mm) / (sqrt(vv) + st.eps)), &st.obs_out[base + e]);  // :262-263
-                                    }
-                                }
-                            }
-                        } else {
-                            for (int e = lane; e < Np * D; e += 64) st.obs_out[base + e] = O[e];
-                        }
-                    }
+                    // (hostage.hip hands the helper a copy of *IOA.st and says why; this kernel keeps the reference)
+                    if (FUSED) std_obs_row(*IOA.st, O, env * (int64_t)(Np * D), Np * D, lane);
                 }
                 wave_sync();
             }
@@ -601,15 +461,10 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
                 reinterpret_cast<uint32_t *>(S)[4 * NP + 3] = tick;
             }
             wave_sync();
-            {
-                const auto dst = uniform_ptr(reinterpret_cast<uint32_t *>(DA.state) + env * (int64_t)rec_dw);
-                for (uint32_t k = ulane; k < (uint32_t)rec_dw; k += 64u) dst[k] = reinterpret_cast<const uint32_t *>(S)[k];
-            }
+            store_record<WwKArgs>(reinterpret_cast<const uint32_t *>(S), env, rec_dw, ulane);
             wave_sync();
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
-        cur_act = nxt_act;
+        cur = nxt;
     }
 }
 #undef DA
@@ -619,10 +474,7 @@ __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev
 
 }  // namespace
 // =================================================================== host side / C ABI
-struct madrl_waterworld : ParticleHandle<madrl_waterworld_config, WwDev> {
-    const int32_t *pending;  // madrl_waterworld_set_particle_counts: caller-owned [n_envs][3], both NULL = one shape for all envs
-    int32_t *live;
-};
+struct madrl_waterworld : ParticleHandle<madrl_waterworld_config, WwDev> {};
 
 namespace {
 
@@ -675,11 +527,7 @@ void ww_layout(const madrl_waterworld_config *c, WwDev *d) {
     d->sq_hit_ev = sq_threshold(d->r_pu + d->r_ev); d->sq_hit_po = sq_threshold(d->r_pu + d->r_po);
 }
 
-size_t ww_lds_bytes(const WwDev &d) {
-    size_t f = align_up((size_t)d.rec_dw, 4) + align_up((size_t)(d.Np + 1) * d.D, 4) + align_up((size_t)2 * d.K, 4);   // (Np + 1: the spare row of the sensing phase)
-    size_t b = f * 4 + 8 * (size_t)d.Np + (size_t)d.Np * (d.Ne + d.Npo) + 2 * (size_t)d.Ne + d.Npo;
-    return align_up(b, 16);
-}
+size_t ww_lds_bytes(const WwDev &d) { return wave_lds_bytes(d.rec_dw, d.Np, d.D, d.K, d.Ne, d.Npo); }
 
 size_t ww_lds_bytes_crowd(const WwDev &d) { return ww_crowd_lds_bytes(d.Np, d.Ne, d.Npo, d.K, d.rec_dw); }
 
@@ -787,13 +635,7 @@ int madrl_waterworld_set_standardize(madrl_waterworld *h, const madrl_standardiz
 int madrl_waterworld_set_launch(madrl_waterworld *h, int64_t max_blocks) { return particle_set_launch(h, max_blocks); }
 
 int madrl_waterworld_set_particle_counts(madrl_waterworld *h, const int32_t *pending_dev, int32_t *live_dev) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    if (!h->cfg.crowd) return fail(MADRL_EINVAL, "set_particle_counts: per-env particle counts run on the crowd kernel (cfg.crowd = 1)");
-    if ((pending_dev == nullptr) != (live_dev == nullptr))
-        return fail(MADRL_EINVAL, "set_particle_counts: pending_dev and live_dev are both arrays or both NULL");
-    h->pending = pending_dev;
-    h->live = live_dev;
-    return MADRL_OK;
+    return particle_set_counts(h, pending_dev, live_dev);
 }
 
 int madrl_waterworld_reset(madrl_waterworld *h, const uint8_t *mask_dev, float *obs_dev, void *stream) {
@@ -807,22 +649,12 @@ int madrl_waterworld_step(madrl_waterworld *h, const float *actions_dev, const f
 
 int madrl_waterworld_get_state(madrl_waterworld *h, float *pos, float *vel, float *obst, int32_t *t, uint32_t *tick,
                                void *stream) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    const unsigned blocks = (unsigned)((h->dev.n_envs + 127) / 128);
-    hipLaunchKernelGGL(ww_state_copy_kernel, dim3(blocks), dim3(128), 0, (hipStream_t)stream, h->dev, pos, vel, obst, t,
-                       tick, 0);
-    MADRL_HIP_TRY(hipGetLastError());
-    return MADRL_OK;
+    return state_copy_launch(h, ww_state_copy_kernel, stream, pos, vel, obst, t, tick, 0);
 }
 
 int madrl_waterworld_set_state(madrl_waterworld *h, const float *pos, const float *vel, const float *obst,
                                const int32_t *t, const uint32_t *tick, void *stream) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    const unsigned blocks = (unsigned)((h->dev.n_envs + 127) / 128);
-    hipLaunchKernelGGL(ww_state_copy_kernel, dim3(blocks), dim3(128), 0, (hipStream_t)stream, h->dev, (float *)pos,
-                       (float *)vel, (float *)obst, (int32_t *)t, (uint32_t *)tick, 1);
-    MADRL_HIP_TRY(hipGetLastError());
-    return MADRL_OK;
+    return state_copy_launch(h, ww_state_copy_kernel, stream, (float *)pos, (float *)vel, (float *)obst, (int32_t *)t, (uint32_t *)tick, 1);
 }
 
 }  // extern "C"

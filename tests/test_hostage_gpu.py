@@ -85,6 +85,43 @@ def test_hip_matches_f32_oracle_free_running(mech, nh):
     assert n_done > N and n_resp > 50
 
 
+def _vs_f32_oracle(args, kw, N, T, H):
+    """Seeded rollout with auto-reset against the float32 oracle, their own Philox on both sides and nothing ever copied across: every
+    output and the whole state must stay identical in every bit"""
+    from madrl_amd.hostage import BatchedContinuousHostageWorld
+    from oracle import hostage as ho
+    env = BatchedContinuousHostageWorld(*args, n_envs=N, device=DEV, seed=77, env_id_base=500, max_steps=H, auto_reset=True, **kw)
+    orc = ho.HostageOracle(*args, n_envs=N, seed=77, env_id_base=500, max_steps=H, dtype=np.float32, **kw)
+    assert np.array_equal(env.reset().cpu().numpy(), orc.reset())
+    rng = np.random.RandomState(1)
+    catches = n_done = 0
+    for t in range(T):
+        act = rng.uniform(-1, 1, size=(N, args[0], 2)).astype(np.float32)
+        obs, rew, done, info = env.step(act)
+        oobs, orew, odone, oinfo = orc.step(act)
+        assert np.array_equal(done.cpu().numpy(), odone != 0), "done step %d" % t
+        assert np.array_equal(info["ho_saved"].cpu().numpy(), oinfo[:, 0]), "ho_saved step %d" % t
+        assert np.array_equal(info["cr_encs"].cpu().numpy(), oinfo[:, 1]), "cr_encs step %d" % t
+        assert np.array_equal(rew.cpu().numpy(), orew), "rewards step %d" % t
+        catches += int(oinfo.sum())
+        n_done += int((odone != 0).sum())
+        if (odone != 0).any():
+            orc.reset(mask=(odone != 0).astype(np.uint8))
+        assert np.array_equal(obs.cpu().numpy(), orc.obs), "obs step %d" % t
+        gst, ost = env.get_state(), orc.get_state()
+        for k in ("pos", "vel", "key", "bomb", "t", "tick"):
+            assert np.array_equal(gst[k].cpu().numpy(), np.asarray(ost[k]).astype(gst[k].cpu().numpy().dtype)), "%s step %d" % (k, t)
+        assert np.array_equal(gst["saved"].cpu().numpy(), ost["saved"].astype(np.int64)) and np.array_equal(gst["flags"].cpu().numpy(), ost["flags"])
+    assert catches > 0, "no catches"
+    assert n_done >= N, "no auto-reset"
+
+
+def test_generic_kernel_at_its_limits_free_running_vs_f32_oracle():
+    """61 particles (20 rescuers, 21 hostages, 20 criminals): the record is four dwords per lane; 70 sensors: the passes of 64 (rescuer,
+    sensor) pairs straddle rescuers; local reward: the who-caught loops over the byte matrices"""
+    _vs_f32_oracle((20, 21, 20, 2, 2), dict(n_sensors=70, reward_mech="local"), N=64, T=40, H=15)
+
+
 @pytest.mark.parametrize("i", range(8))
 def test_drawn_configurations_free_running_vs_f32_oracle(i):
     """configurations drawn like the recorded ones (oracle/make_golden_hostage_fuzz.py), another seed, nothing injected: every step of a

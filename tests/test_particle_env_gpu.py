@@ -12,6 +12,10 @@ DEV = "cuda:0"
 N = 8
 ALPHA, EPS, SCALE = 0.05, 1e-8, 0.7
 
+# the generic kernels at their limits (tests/test_waterworld_gpu.py LIMITS, tests/test_hostage_gpu.py): 62 / 61 particles, 70 sensors
+LIMITS = {"waterworld": dict(args=(20, 22), kw=dict(n_poison=20, n_sensors=70, obstacle_loc=None, reward_mech="global"), catches=("evcatches", "pocatches")),
+          "hostage": dict(args=(20, 21, 20, 2, 2), kw=dict(n_sensors=70, reward_mech="local"), catches=("ho_saved", "cr_encs"))}
+
 # (2 pursuers, 3 evaders, 2 poison, 4 sensors) and (2 rescuers, 3 hostages, 2 criminals, 4 sensors, n_coop_save = n_coop_avoid = 1)
 WORLDS = {"waterworld": dict(args=(2, 3), kw=dict(n_poison=2, n_sensors=4), count="n_pursuers"),
           "hostage": dict(args=(2, 3, 2, 1, 1), kw=dict(n_sensors=4), count="n_good")}
@@ -123,3 +127,49 @@ def test_fused_step_equals_step_and_epilogue_kernels(world):
         assert sorted(inf) == sorted(inp) and all(torch.equal(inf[k], inp[k]) for k in inf), "step %d" % t
     for k, v in dict(obs_mean=om, obs_var=ov, rew_mean=rm, rew_var=rv).items():
         assert torch.equal(st[k], v), k
+
+
+@world
+def test_fused_step_equals_step_and_epilogue_kernels_at_the_limits(world):
+    """the same over LIMITS, 64 envs and 40 steps under auto-reset (max_steps 15): the fused epilogue over rows of 20 x 493 / 20 x 356
+    elements, the fused reset pass included"""
+    from madrl_amd import _lib
+    from madrl_amd.hostage import BatchedContinuousHostageWorld
+    from madrl_amd.waterworld import BatchedMAWaterWorld
+    L = _lib.lib()
+    w, n, A = LIMITS[world], 64, 20
+    mk = lambda: (BatchedMAWaterWorld if world == "waterworld" else BatchedContinuousHostageWorld)(
+        *w["args"], n_envs=n, device=DEV, seed=77, env_id_base=500, max_steps=15, auto_reset=True, **w["kw"])
+    fused, plain = mk(), mk()
+    st = fused.bind_standardize(scale_reward=SCALE, enable_obsnorm=True, enable_rewnorm=True, obs_alpha=ALPHA, rew_alpha=ALPHA, eps=EPS)
+    D = plain.obs_dim
+    f64 = dict(dtype=torch.float64, device=DEV)
+    om, ov, oo = torch.zeros((n, A, D), **f64), torch.ones((n, A, D), **f64), torch.zeros((n, A, D), device=DEV)
+    rm, rv, ro = torch.zeros((n, A), **f64), torch.ones((n, A), **f64), torch.zeros((n, A), device=DEV)
+    stream = _lib.current_stream(torch.device(DEV))
+
+    def obsnorm(obs):
+        _lib.check(L.madrl_wrap_obsnorm(_lib.ptr(obs), _lib.ptr(om), _lib.ptr(ov), _lib.ptr(oo), obs.numel(), obs.numel() // n, None, ALPHA, EPS,
+                                        stream))
+        return oo
+
+    def rewnorm(rew):
+        _lib.check(L.madrl_wrap_rewnorm(_lib.ptr(rew), _lib.ptr(rm), _lib.ptr(rv), _lib.ptr(ro), rew.numel(), rew.numel() // n, None, ALPHA, EPS,
+                                        SCALE, 1, stream))
+        return ro
+
+    assert torch.equal(fused.reset(), obsnorm(plain.reset())), "reset"
+    g = torch.Generator(device="cpu").manual_seed(1)
+    catches = n_done = 0
+    for t in range(40):
+        act = (torch.rand((n, A, 2), generator=g) * 2 - 1).to(DEV)
+        of, rf, df, inf = fused.step(act)
+        op, rp, dp, inp = plain.step(act)
+        assert torch.equal(of, obsnorm(op)) and torch.equal(rf, rewnorm(rp)) and torch.equal(df, dp), "step %d" % t
+        assert sorted(inf) == sorted(inp) and all(torch.equal(inf[k], inp[k]) for k in inf), "step %d" % t
+        catches += sum(int(inp[k].sum()) for k in w["catches"])
+        n_done += int(dp.sum())
+    for k, v in dict(obs_mean=om, obs_var=ov, rew_mean=rm, rew_var=rv).items():
+        assert torch.equal(st[k], v), k
+    assert catches > 0, "no catches"
+    assert n_done >= n, "no auto-reset"

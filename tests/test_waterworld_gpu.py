@@ -70,14 +70,18 @@ CASES = {
 }
 
 
-def _vs_f32_oracle(case, teacher_forced):
+# The generic kernel at its limits: 62 particles, so the record is four dwords per lane; 70 sensors, so the passes of 64 (pursuer, sensor)
+# pairs straddle pursuers; rows of 7 * 70 + 3 = 493 floats, so the 16-byte row store has a dword tail; about 41 KB of LDS per workgroup
+LIMITS = dict(n_pursuers=20, n_evaders=22, n_poison=20, n_sensors=70, obstacle_loc=None, reward_mech="global")
+
+
+def _vs_f32_oracle(case, teacher_forced, N=256, T=60, H=20):
     """Seeded rollout with auto-reset against the float32 oracle: same statement order, their own Philox on both sides.
     teacher_forced: the kernel takes the oracle's state at the start of every step (a divergence cannot compound: the comparison of each
     step stands on its own, tolerance 1e-5 as north_star asks).  Otherwise NOTHING is ever copied across: 60 steps, resets, respawns and
     random obstacles included, must stay identical in every bit of every output and of the state -- one flipped `<=` would show."""
     from oracle import waterworld as ww
-    kw = CASES[case]
-    N, T, H = 256, 60, 20
+    kw = CASES[case] if isinstance(case, str) else case
     env = _mk(N, seed=77, env_id_base=500, max_steps=H, auto_reset=True, **kw)
     orc = ww.WaterworldOracle(n_envs=N, seed=77, env_id_base=500, max_steps=H, dtype=np.float32, **kw)
     obs = env.reset()
@@ -118,6 +122,11 @@ def _vs_f32_oracle(case, teacher_forced):
 def test_hip_matches_f32_oracle_free_running(case):
     """truly free-running: no state is ever copied from the oracle to the kernel; every output and the state bit-identical for 60 steps"""
     _vs_f32_oracle(case, teacher_forced=False)
+
+
+def test_generic_kernel_at_its_limits_free_running_vs_f32_oracle():
+    """LIMITS, free-running under auto-reset: every output and the state bit-identical to the float32 oracle"""
+    _vs_f32_oracle(LIMITS, teacher_forced=False, N=64, T=40, H=15)
 
 
 @pytest.mark.parametrize("case", sorted(CASES), ids=sorted(CASES))
