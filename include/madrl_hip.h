@@ -300,7 +300,7 @@ int madrl_waterworld_set_launch(madrl_waterworld *h, int64_t max_blocks);
 /* which kernel the handle runs: 0 = one wavefront per env, 1 = the crowd kernel (cfg.crowd) */
 int madrl_waterworld_kernel_kind(madrl_waterworld *h, int32_t *out);
 
-/* Per-env particle counts on the crowd kernel (a curriculum over agent counts without re-creating the handle; the Waterworld form of
+/* Per-env particle counts (a curriculum over agent counts without re-creating the handle; the Waterworld form of
  * madrl_pursuit_set_agent_counts).  With both arrays bound the config's n_pursuers / n_evaders / n_poison are a CAPACITY (Pcap, Ecap,
  * POcap) -- for madrl_waterworld_state_bytes, the LDS size and the limits of 128 pursuers and 1 023 particles as well -- and every env
  * has LIVE counts 1 <= p <= Pcap, 1 <= e <= Ecap, 1 <= po <= POcap.  Each reset of an env -- reset(), reset(mask) for the envs in the
@@ -317,7 +317,13 @@ int madrl_waterworld_kernel_kind(madrl_waterworld *h, int32_t *out);
  *   live_dev     int32 [n_envs][3], caller-owned, read and written by the kernels (values outside the ranges are read clamped); the
  *                caller fills it before the first launch: the capacity -- or, with a restored set_state, the counts of that state
  * Both stay valid while bound and may be rewritten between launches.  Both NULL turns the mode off (meaningful only while every env is
- * at its capacity); one NULL: MADRL_EINVAL.  A handle with cfg.crowd == 0: MADRL_EINVAL. */
+ * at its capacity); one NULL: MADRL_EINVAL.
+ * Which kernel runs: a handle with cfg.crowd == 1 launches ww_crowd_kernel_live (one workgroup of four wavefronts per env, the limits
+ * above); a handle with cfg.crowd == 0 launches waterworld_kernel_live, the generic one-wavefront kernel on per-env counts, whose
+ * capacity is within that kernel's limits (62 particles, 32 pursuers) and whose fixed-shape twin is a one-wavefront batch -- the faster
+ * of the two wherever the capacity fits it.  The one-wavefront live kernel has no fused StandardizedEnv: on such a handle
+ * madrl_waterworld_set_standardize and this call refuse each other (MADRL_EINVAL), in either order.  madrl_waterworld_kernel_kind
+ * stays 0 / 1 by cfg.crowd. */
 int madrl_waterworld_set_particle_counts(madrl_waterworld *h, const int32_t *pending_dev, int32_t *live_dev);
 
 /* Fused StandardizedEnv (madrl_environments/__init__.py:204-311): bind the wrapper's state to the env handle and the step /

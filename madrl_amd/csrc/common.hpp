@@ -237,6 +237,8 @@ __device__ __forceinline__ void free_motion(float &x, float &y, float &vx, float
 // A sensor of agent i can only return a finite value for an object with d2 <= rad2 + sv^2 <= rad2 + range^2 (plus a relative margin far
 // above the rounding of the test itself): everything else yields +inf in the oracle and never becomes a minimum.
 __device__ __forceinline__ float sensor_reach2(float rad2, float srange) { return (rad2 + srange * srange) * 1.0001f + 1e-9f; }
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 #endif
 
 // ---------------------------------------------------------------- host side of the env handles
@@ -280,6 +282,13 @@ struct ParticleStd {
     float *rew_out;               // [N][agents] scale * (reward / (sqrt(var) + eps)); NULL = rewards are not touched
     double obs_alpha, rew_alpha, eps, scale;
     int32_t enable_obsnorm, enable_rewnorm;
+};
+
+// Per-env particle counts (madrl_waterworld_set_particle_counts, madrl_hostage_set_particle_counts): the two caller-owned int32
+// [n_envs][3] arrays of the live-count entries (*_crowd_kernel_live, waterworld_kernel_live), in the world's class order, the agents first
+struct ParticleCounts {
+    const int32_t *pending;  // the counts an env takes at its next reset, clamped to 1 .. capacity
+    int32_t *live;           // the counts of its running episode: read per env, written by the reset pass
 };
 
 // What a particle world's handle holds: struct madrl_waterworld / madrl_hostage derive from it with their configuration and Dev types.
@@ -360,12 +369,16 @@ int particle_set_launch(H *h, int64_t max_blocks) {
 }
 
 // madrl_waterworld_set_particle_counts / madrl_hostage_set_particle_counts
+// wave_live: the world's one-wavefront kernel has a live-count entry too (cfg.crowd = 0); it has no fused StandardizedEnv, so a bound one
+// and the counts refuse each other (particle_set_standardize)
 template <class H>
-int particle_set_counts(H *h, const int32_t *pending_dev, int32_t *live_dev) {
+int particle_set_counts(H *h, const int32_t *pending_dev, int32_t *live_dev, bool wave_live = false) {
     if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    if (!h->cfg.crowd) return fail(MADRL_EINVAL, "set_particle_counts: per-env particle counts run on the crowd kernel (cfg.crowd = 1)");
+    if (!h->cfg.crowd && !wave_live) return fail(MADRL_EINVAL, "set_particle_counts: per-env particle counts run on the crowd kernel (cfg.crowd = 1)");
     if ((pending_dev == nullptr) != (live_dev == nullptr))
         return fail(MADRL_EINVAL, "set_particle_counts: pending_dev and live_dev are both arrays or both NULL");
+    if (live_dev != nullptr && h->std_bound)
+        return fail(MADRL_EINVAL, "set_particle_counts: a fused StandardizedEnv is bound, and the live-count kernel has none; unbind it first (set_standardize(NULL))");
     h->pending = pending_dev;
     h->live = live_dev;
     return MADRL_OK;
@@ -377,6 +390,8 @@ int particle_set_standardize(H *h, const madrl_standardize_args *a) {
     if (!a) { h->std_bound = false; return MADRL_OK; }
     if (h->cfg.crowd)
         return fail(MADRL_EINVAL, "set_standardize: the crowd kernel has no fused StandardizedEnv; use the epilogue kernels (madrl_wrap_obsnorm / madrl_wrap_rewnorm)");
+    if (h->live != nullptr)
+        return fail(MADRL_EINVAL, "set_standardize: the live-count kernel (set_particle_counts) has no fused StandardizedEnv; use the epilogue kernels (madrl_wrap_obsnorm / madrl_wrap_rewnorm)");
     if (a->struct_size != (int32_t)sizeof(madrl_standardize_args))
         return fail(MADRL_EINVAL, "madrl_standardize_args.struct_size=%d, library expects %d", a->struct_size, (int)sizeof(madrl_standardize_args));
     if (!a->obs_out || (a->enable_obsnorm && (!a->obs_mean || !a->obs_var)) || (a->rew_out && a->enable_rewnorm && (!a->rew_mean || !a->rew_var)))

@@ -34,15 +34,7 @@
 
 namespace madrl {
 
-// Per-env particle counts (madrl_waterworld_set_particle_counts, madrl_hostage_set_particle_counts): the two caller-owned int32
-// [n_envs][3] arrays of the live-count entries (*_crowd_kernel_live), in the world's class order, the agents first
-struct ParticleCounts {
-    const int32_t *pending;  // the counts an env takes at its next reset, clamped to 1 .. capacity
-    int32_t *live;           // the counts of its running episode: read per env, written by the reset pass
-};
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
+// (ParticleCounts, the third argument of the live-count entries, and clampi are in common.hpp: waterworld_kernel_live takes them too)
 // ---- phase A.  An agent's action row (zeros unless live) is scaled and kept in ACT[i]; the agent integrates and is clipped to the
 // walls, the velocity component zeroed where it was.
 __device__ __forceinline__ void drive_agent(bool live, const float *actions, int64_t row, float action_scale, float *ACT, int i, float &x,

@@ -15,6 +15,8 @@
 //               order (walk_bits) -- the reference's index order, so a running minimum with a strict `<` is np.argmin's first minimum.
 //               One ray test: ray_misses
 //   epilogue    the fused StandardizedEnv (std_reward, std_obs_row), then the record goes back (store_record)
+//   live counts a live-count entry (waterworld_kernel_live) fetches the env's counts with its record (WaveCounts) and moves the record between the
+//               capacity's slotted layout and the packed layout of the env's counts (slot_to_packed; the mapped to_lds / store_record)
 // The helpers take the LDS arrays, the counts and the lane as arguments and know nothing of a world's structs.  Two kinds of argument
 // keep the kernels' code as it was measured: a launch parameter that a kernel reads inside a branch or a loop is read there, through
 // kernargs<KA>() (common.hpp; KA is the kernel's view struct {Dev d; IO io;}, and only fields both worlds have under one name are
@@ -46,6 +48,11 @@ struct WaveRecord {
 
     template <int MODE, class KA>
     __device__ __forceinline__ void fetch(int64_t env, int rec_dw, int n_agents, int lane, uint32_t ulane) {
+        fetch_rows<MODE, KA>(env, rec_dw, n_agents, n_agents, lane, ulane);
+    }
+    // row_agents: the agents the action tensor has a row for (the stride); the first n_agents rows are read
+    template <int MODE, class KA>
+    __device__ __forceinline__ void fetch_rows(int64_t env, int rec_dw, int row_agents, int n_agents, int lane, uint32_t ulane) {
         const int nreg = (rec_dw + 63) >> 6;
         const auto src = uniform_ptr(reinterpret_cast<const uint32_t *>(kernargs<KA>()->d.state) + env * (int64_t)rec_dw);
 #pragma unroll
@@ -53,7 +60,7 @@ struct WaveRecord {
             const uint32_t k = ulane + 64u * q;
             r[q] = (q < nreg && (int)k < rec_dw) ? src[k] : 0u;
         }
-        if constexpr (MODE == 1) act = (lane < 2 * n_agents) ? uniform_ptr(kernargs<KA>()->io.actions + env * 2 * n_agents)[ulane] : 0.0f;
+        if constexpr (MODE == 1) act = (lane < 2 * n_agents) ? uniform_ptr(kernargs<KA>()->io.actions + env * 2 * row_agents)[ulane] : 0.0f;
         else act = 0.0f;
     }
     // The hinge of the software pipeline: the compiler may not move the loads of a fetch past this point, nor what follows ahead of them.
@@ -67,13 +74,74 @@ struct WaveRecord {
             if (q < nreg && k < rec_dw) SU[k] = r[q];
         }
     }
+    // slotted record -> the packed record of an env's live counts: dword k goes to packed(k), those of absent slots (packed(k) < 0) are dropped
+    template <class Packed>
+    __device__ __forceinline__ void to_lds(uint32_t *SU, int rec_dw, int lane, Packed packed) const {
+        const int nreg = (rec_dw + 63) >> 6;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = lane + 64 * q;
+            if (q < nreg && k < rec_dw) {
+                const int j = packed(k);
+                if (j >= 0) SU[j] = r[q];
+            }
+        }
+    }
 };
+
+// ---- per-env particle counts of a live-count entry (ParticleCounts, common.hpp).  An env's pending and live triples, each clamped to
+// 1 .. the capacity (c0, c1, c2 <= 62) as it is read -- nothing in the arrays leads outside the capacity's LDS or rows -- and packed into
+// one word (n0 | n1 << 8 | n2 << 16).  They are fetched with the env's record, one env ahead: the env index is wave-uniform, so these are
+// scalar loads, and the first record access of an env waits for none of them.
+struct WaveCounts {
+    uint32_t pend = 0u, live = 0u;
+
+    static __device__ __forceinline__ int n0(uint32_t pk) { return (int)(pk & 255u); }
+    static __device__ __forceinline__ int n1(uint32_t pk) { return (int)((pk >> 8) & 255u); }
+    static __device__ __forceinline__ int n2(uint32_t pk) { return (int)(pk >> 16); }
+    static __device__ __forceinline__ uint32_t pack(const int32_t *c, int c0, int c1, int c2) {
+        return (uint32_t)clampi(c[0], 1, c0) | ((uint32_t)clampi(c[1], 1, c1) << 8) | ((uint32_t)clampi(c[2], 1, c2) << 16);
+    }
+    // MODE 0 (reset) runs on the pending triple alone; a step on the live one, and on the pending one in the reset pass of an auto-reset
+    template <int MODE, class P, class L>
+    __device__ __forceinline__ void fetch(P pending, L live_arr, int64_t env, int c0, int c1, int c2) {
+        pend = pack(pending + 3 * env, c0, c1, c2);
+        live = MODE == 1 ? pack(live_arr + 3 * env, c0, c1, c2) : pend;
+    }
+    __device__ __forceinline__ void hinge() { asm volatile("" : "+s"(pend), "+s"(live)); }
+};
+
+// Dword k of a record slotted at the capacity (c0 | c1 | c2 particles by class: X[NPc][2] | V[NPc][2] | the world's own words) -> its dword
+// in the packed record of the live counts (n0, n1, n2), X[NP][2] | V[NP][2] | the same words; -1 for a dword of a slot that holds no
+// particle.  Class member m of a slot keeps its index: packed particles are in the live class order, which is the lane order of the phases.
+__device__ __forceinline__ int slot_to_packed(int k, int c0, int c1, int c2, int n0, int n1, int n2) {
+    const int NPc = c0 + c1 + c2, NP = n0 + n1 + n2;
+    if (k >= 4 * NPc) return 4 * NP + (k - 4 * NPc);
+    const bool vel = k >= 2 * NPc;
+    const int kk = vel ? k - 2 * NPc : k;
+    const int s = kk >> 1;
+    const int m = s < c0 ? s : (s < c0 + c1 ? s - c0 : s - c0 - c1);           // index within the class
+    const int lo = s < c0 ? 0 : (s < c0 + c1 ? n0 : n0 + n1);                   // where the class starts in the packed arrays
+    const bool is = m < (s < c0 ? n0 : (s < c0 + c1 ? n1 : n2));
+    return is ? (vel ? 2 * NP : 0) + 2 * (lo + m) + (kk & 1) : -1;
+}
 
 // LDS -> record
 template <class KA>
 __device__ __forceinline__ void store_record(const uint32_t *SU, int64_t env, int rec_dw, uint32_t ulane) {
     const auto dst = uniform_ptr(reinterpret_cast<uint32_t *>(kernargs<KA>()->d.state) + env * (int64_t)rec_dw);
     for (uint32_t k = ulane; k < (uint32_t)rec_dw; k += 64u) dst[k] = SU[k];
+}
+// the packed record of an env's live counts -> the slotted record: every dword of the capacity's record is written, from packed(k) or,
+// for a slot that holds no particle, -1.0f (positions: the first half of the particle words) / 0 (velocities)
+template <class KA, class Packed>
+__device__ __forceinline__ void store_record(const uint32_t *SU, int64_t env, int rec_dw, uint32_t ulane, Packed packed) {
+    const auto dst = uniform_ptr(reinterpret_cast<uint32_t *>(kernargs<KA>()->d.state) + env * (int64_t)rec_dw);
+    const uint32_t half = ((uint32_t)rec_dw - 4u) >> 1;  // rec_dw = 4 NPc + 4 here: positions below 2 NPc
+    for (uint32_t k = ulane; k < (uint32_t)rec_dw; k += 64u) {
+        const int j = packed((int)k);
+        dst[k] = j >= 0 ? SU[j] : (k < half ? __float_as_uint(-1.0f) : 0u);
+    }
 }
 
 // ---- phase A.  act_lane: the action row spread over the lanes (WaveRecord::act); agent(): the lane's agent index, 0 for a lane that is

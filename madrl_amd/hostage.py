@@ -55,7 +55,8 @@ class BatchedContinuousHostageWorld(BatchedParticleWorld):
         per_env_counts=True (with crowd=True): n_good / n_hostages / n_bad are a capacity and every env runs its own counts
         (set_particle_counts), taken at its next reset; all tensors keep the capacity's shapes, slotted by class (rescuer i at i, hostage m
         at n_good + m, criminal m at n_good + n_hostages + m; bit m of the saved mask is hostage m).  A pickle keeps the constructor
-        arguments only: the counts of the copy are back at the capacity."""
+        arguments only: the counts of the copy are back at the capacity.  per_env_counts="wave" (Waterworld's one-wavefront form) is a
+        ValueError here: hostage_kernel has no live counts."""
         self._ctor = dict(locals())
         self._ctor.pop("self"); self._ctor.pop("kwargs"); self._ctor.pop("__class__", None)
         self._flags(crowd, per_env_counts)

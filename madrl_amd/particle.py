@@ -34,8 +34,10 @@ class BatchedParticleWorld(AbstractMAEnv):
     attributes where it is used: nothing of them is copied here.
     per_env_counts=True (which `_flags()` takes from the constructor, with crowd=True): the `_COUNTS` attributes are a capacity and every env
     runs its own counts, taken at its next reset (set_particle_counts of the world, with its own keyword names); all tensors keep the
-    capacity's shapes, slotted by class."""
+    capacity's shapes, slotted by class.  per_env_counts="wave" (without crowd=True) is the same on the one-wavefront kernel, for a world
+    whose one-wavefront kernel has a live-count entry (`_WAVE_LIVE`)."""
     per_env_counts = False
+    _WAVE_LIVE = False  # the world's one-wavefront kernel takes per-env counts (per_env_counts="wave")
     _SYM = None         # prefix of the C symbols: "madrl_waterworld"
     _COUNTS = None      # names of the attributes that hold the particle counts, the agents' first: ("n_pursuers", "n_evaders", "n_poison")
     _INJECT = None      # name of the attribute that holds the row count of step(respawn=...)
@@ -49,8 +51,20 @@ class BatchedParticleWorld(AbstractMAEnv):
         for flag in ("crowd", "per_env_counts"):
             if not self._ctor[flag]:
                 self._ctor.pop(flag)
-        if per_env_counts and not crowd:
-            raise ValueError("per_env_counts=True runs on the crowd kernel: construct the batch with crowd=True")
+        if isinstance(per_env_counts, str):   # the one-wavefront form is asked for by value
+            if per_env_counts != "wave":
+                raise ValueError("per_env_counts must be False, True (the crowd kernel's form, with crowd=True) or \"wave\" (got %r)" % (per_env_counts,))
+            if not self._WAVE_LIVE:
+                raise ValueError("per_env_counts=\"wave\": the one-wavefront kernel of %s has no live counts; use crowd=True, per_env_counts=True"
+                                 % type(self).__name__)
+            if crowd:
+                raise ValueError("per_env_counts=\"wave\" is the one-wavefront kernel's form: construct the batch without crowd=True "
+                                 "(crowd=True takes per_env_counts=True)")
+        elif per_env_counts not in (False, True, 0, 1, None):
+            raise ValueError("per_env_counts must be False, True (the crowd kernel's form, with crowd=True) or \"wave\" (got %r)" % (per_env_counts,))
+        elif per_env_counts and not crowd:
+            raise ValueError("per_env_counts=True runs on the crowd kernel: construct the batch with crowd=True"
+                             + (" (or ask for the one-wavefront kernel's form with per_env_counts=\"wave\")" if self._WAVE_LIVE else ""))
         self._crowd, self.per_env_counts = bool(crowd), bool(per_env_counts)
 
     def setup(self):
@@ -80,7 +94,7 @@ class BatchedParticleWorld(AbstractMAEnv):
         self._handle = h
         if self._max_blocks:
             _lib.check(c.set_launch(h, self._max_blocks))
-        if N >= 4096 and not self._crowd:   # (the crowd kernel takes its shape at run time: there is nothing to specialise)
+        if N >= 4096 and not self._crowd and not self.per_env_counts:   # (the crowd and live-count kernels take their shape at run time: there is nothing to specialise)
             self._hint_fast_path(D)
         self._agents = [self._AGENT(i + 1, D) for i in range(Na)]
         # A fused StandardizedEnv binding belongs to the handle that was just replaced (seed() and set_param_values() come
@@ -114,8 +128,8 @@ class BatchedParticleWorld(AbstractMAEnv):
 
     @property
     def fused_standardize(self):
-        """whether bind_standardize() works on this env (StandardizedEnv asks): the crowd kernel has no fused form"""
-        return not self._crowd
+        """whether bind_standardize() works on this env (StandardizedEnv asks): the crowd and live-count kernels have no fused form"""
+        return not self._crowd and not self.per_env_counts
 
     def set_launch(self, max_blocks=0):
         self._max_blocks = int(max_blocks)
@@ -168,6 +182,9 @@ class BatchedParticleWorld(AbstractMAEnv):
         The crowd kernel has no fused form: StandardizedEnv runs its epilogue kernels over such an env."""
         if self._crowd:
             raise _lib.MadrlError("bind_standardize: the crowd kernel (crowd=True) has no fused StandardizedEnv; "
+                                  "StandardizedEnv(env) or StandardizedEnv(env, fused=False) runs the epilogue kernels over it")
+        if self.per_env_counts:
+            raise _lib.MadrlError("bind_standardize: the live-count kernel (per_env_counts=\"wave\") has no fused StandardizedEnv; "
                                   "StandardizedEnv(env) or StandardizedEnv(env, fused=False) runs the epilogue kernels over it")
         N, Na, D, dev = self.n_envs, getattr(self, self._COUNTS[0]), self.obs_dim, self.device
         self._std_kwargs = dict(scale_reward=scale_reward, enable_obsnorm=enable_obsnorm, enable_rewnorm=enable_rewnorm,
@@ -240,7 +257,8 @@ class BatchedParticleWorld(AbstractMAEnv):
     # ------------------------------------------------------------------ per-env particle counts (per_env_counts=True)
     def _require_counts(self, what):
         if not self.per_env_counts:
-            raise RuntimeError("%s: this batch has one particle count for all envs; construct it with crowd=True, per_env_counts=True" % what)
+            raise RuntimeError("%s: this batch has one particle count for all envs; construct it with crowd=True, per_env_counts=True%s"
+                               % (what, " or with per_env_counts=\"wave\"" if self._WAVE_LIVE else ""))
 
     def _checked_counts(self, v, col, name, m=None):
         """an int or an int [N] as int32 [N] within 1 .. the capacity (where m is set)"""

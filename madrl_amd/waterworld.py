@@ -41,6 +41,7 @@ class BatchedMAWaterWorld(BatchedParticleWorld):
     _SYM, _AGENT = "madrl_waterworld", Archea
     _COUNTS, _INJECT = ("n_pursuers", "n_evaders", "n_poison"), "n_particles"
     _INFO_KEYS = ("evcatches", "pocatches")
+    _WAVE_LIVE = True
     _STATE = (("pos", torch.float32, ("NP", 2)), ("vel", torch.float32, ("NP", 2)), ("obst", torch.float32, (2,)), ("t", torch.int32, ()),
               ("tick", torch.int32, ()))
 
@@ -56,7 +57,13 @@ class BatchedMAWaterWorld(BatchedParticleWorld):
         per_env_counts=True (with crowd=True): n_pursuers / n_evaders / n_poison are a capacity and every env runs its own counts
         (set_particle_counts), taken at its next reset; all tensors keep the capacity's shapes, slotted by class (pursuer i at i, evader
         m at n_pursuers + m, poison m at n_pursuers + n_evaders + m).  A pickle keeps the constructor arguments only: the counts of the
-        copy are back at the capacity."""
+        copy are back at the capacity.
+        per_env_counts="wave" (without crowd=True): the same contract on the one-wavefront kernel (waterworld_kernel_live), for a capacity
+        within its limits -- the twin of an env at (p, e, po) is then env n of a fixed-shape one-wavefront batch, which computes what the
+        crowd kernel does.  Which to choose: "wave" whenever the capacity fits 62 particles and 32 pursuers (one wavefront per env instead
+        of a workgroup of four; DESIGN.md 4.4c has the timing); crowd=True, per_env_counts=True beyond that.  The live one-wavefront kernel
+        is the generic instantiation -- there is no compile-time capacity -- and has no fused StandardizedEnv (the wrapper runs its epilogue
+        kernels)."""
         # like the reference, unknown kwargs are swallowed (waterworld.py:81,:483 passes obs_loc=None)
         self._ctor = dict(locals())
         self._ctor.pop("self"); self._ctor.pop("kwargs"); self._ctor.pop("__class__", None)

@@ -3,6 +3,7 @@
     python scripts/ww_crowd_time.py                      # the table of DESIGN 4.4a: every row below, three processes each, min - max
     python scripts/ww_crowd_time.py --rows shapes,cpu    # some of: shapes, cpu, wave, nw8, live
     python scripts/ww_crowd_time.py --live               # the table of DESIGN 4.4b: the `live` row alone
+    python scripts/ww_crowd_time.py --rows livewave      # the table of DESIGN 4.4c (not in the default set)
 
 Rows
   shapes  20/60/40, 33/100/100 and 128/512/383 with 30 sensors, at 4 096 envs and at the largest batch whose observations fit 16 GB:
@@ -14,6 +15,10 @@ Rows
   live    per-env particle counts (per_env_counts=True) at the capacities 20/60/40 and 33/100/100, 4 096 envs: the fixed-shape kernel, the
           live-count kernel with every env at the capacity, and with every env's triple drawn uniformly between (1, 1, 1) and the capacity
           -- the three alternating, three processes each (ray tests/s of the spread row are counted at the capacity: compare its us)
+  livewave  per-env particle counts on the one-wavefront kernel (per_env_counts="wave") against the crowd kernel's, at the capacities
+          5/10/10 (30 sensors) and 12/25/25 (16 sensors), 32 768 envs: the fixed-shape one-wavefront kernel (specialised at the first
+          capacity, generic at the second), the one-wavefront live kernel and the crowd live kernel with every env at the capacity, and
+          both live kernels on the same spread of triples -- the five alternating, three processes each
 
 Steady state with auto_reset (max_steps 500), after an untimed warm-up; device events around the launches alone.  One measurement per
 process (`--one ...`, what the parent starts), one process at a time.
@@ -27,7 +32,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-SHAPES = {"20/60/40": (20, 60, 40, 30), "33/100/100": (33, 100, 100, 30), "128/512/383": (128, 512, 383, 30), "12/25/25": (12, 25, 25, 16)}
+SHAPES = {"20/60/40": (20, 60, 40, 30), "33/100/100": (33, 100, 100, 30), "128/512/383": (128, 512, 383, 30), "12/25/25": (12, 25, 25, 16),
+          "5/10/10": (5, 10, 10, 30)}
 NW8_LIB = os.path.join(ROOT, "scripts", "_variants", "libmadrl_hip.waterworld_crowd.8.so")
 OBS_BYTES = 16e9
 
@@ -49,7 +55,7 @@ def one(shape, N, crowd, live=0):
     Np, Ne, Npo, K = SHAPES[shape]
     dev = torch.device("cuda:0")
     env = BatchedMAWaterWorld(Np, Ne, n_poison=Npo, n_sensors=K, n_envs=N, device=dev, seed=0, max_steps=500, auto_reset=True, crowd=bool(crowd),
-                              per_env_counts=bool(live))
+                              per_env_counts=(True if crowd else "wave") if live else False)
     if live == 2:
         g = torch.Generator().manual_seed(0)
         env.set_particle_counts(*[torch.randint(1, c + 1, (N,), generator=g) for c in (Np, Ne, Npo)])
@@ -148,6 +154,18 @@ def main():
             (f0, f1), (l0, l1), (s0, s1) = [child(s, 4096, True, rs=r) for r in runs]
             print("%s at 4 096 envs: live at the capacity / fixed = %.3f - %.3f, spread / live at the capacity = %.3f - %.3f" % (
                 s, l0 / f1, l1 / f0, s0 / l1, s1 / l0), flush=True)
+    if "livewave" in rows:
+        variants = ((False, 0), (False, 1), (True, 1), (False, 2), (True, 2))   # (crowd, live)
+        for s in ("5/10/10", "12/25/25"):
+            runs = [[] for _ in variants]
+            for _ in range(3):
+                for r, (crowd, live) in zip(runs, variants):
+                    r.append(measure(s, 32768, crowd, live=live))
+            (f0, f1), (w0, w1), (c0, c1), (ws0, ws1), (cs0, cs1) = [child(s, 32768, crowd, rs=r) for r, (crowd, _l) in zip(runs, variants)]
+            print("%s at 32 768 envs: one-wavefront live / fixed = %.3f - %.3f; crowd live / one-wavefront live = %.2f - %.2f at the capacity, "
+                  "%.2f - %.2f on the spread; gate (one-wavefront live faster than crowd live beyond the spread of the repetitions): %s" % (
+                      s, w0 / f1, w1 / f0, c0 / w1, c1 / w0, cs0 / ws1, cs1 / ws0, "holds" if w1 < c0 and ws1 < cs0 else "does NOT hold"),
+                  flush=True)
 
 
 if __name__ == "__main__":
