@@ -152,26 +152,28 @@ inline unsigned grid_for(int64_t n) {
 
 // One thread per (env, agent) column; each time row is one coalesced sweep over [N][A].  HBM-bound:
 // 4 (rew) + 4 (values) + 4 + 4 (returns, adv) bytes per element and step, the done byte is shared by A lanes.
+// The grid is capped (grid_for): a thread walks the columns in strides of the grid, one whole scan per column (up to 1 048 576
+// columns: one column per thread).
 __global__ void gae_kernel(const float *__restrict__ rew, const uint8_t *__restrict__ done, const float *__restrict__ values, int64_t T,
                            int64_t n_envs, int n_agents, double gamma, double lambda, float *__restrict__ returns,
                            float *__restrict__ adv) {
     const int64_t row = n_envs * n_agents;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= row) return;
-    const int64_t n = i / n_agents;
-    double ret = values ? (double)values[T * row + i] : 0.0, a = 0.0;
-    double vnext = ret;
-    for (int64_t t = T - 1; t >= 0; --t) {
-        const bool cut = (done[t * n_envs + n] & 0x03u) != 0;   // (bit 7 = overflow report: no episode boundary)
-        const double r = (double)rew[t * row + i];
-        ret = r + (cut ? 0.0 : gamma * ret);
-        returns[t * row + i] = (float)ret;
-        if (adv) {
-            const double v = (double)values[t * row + i];
-            const double delta = r + (cut ? 0.0 : gamma * vnext) - v;
-            a = delta + (cut ? 0.0 : gamma * lambda * a);
-            adv[t * row + i] = (float)a;
-            vnext = v;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < row; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t n = i / n_agents;
+        double ret = values ? (double)values[T * row + i] : 0.0, a = 0.0;
+        double vnext = ret;
+        for (int64_t t = T - 1; t >= 0; --t) {
+            const bool cut = (done[t * n_envs + n] & 0x03u) != 0;   // (bit 7 = overflow report: no episode boundary)
+            const double r = (double)rew[t * row + i];
+            ret = r + (cut ? 0.0 : gamma * ret);
+            returns[t * row + i] = (float)ret;
+            if (adv) {
+                const double v = (double)values[t * row + i];
+                const double delta = r + (cut ? 0.0 : gamma * vnext) - v;
+                a = delta + (cut ? 0.0 : gamma * lambda * a);
+                adv[t * row + i] = (float)a;
+                vnext = v;
+            }
         }
     }
 }

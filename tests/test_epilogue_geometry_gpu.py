@@ -1,0 +1,388 @@
+"""GPU tests (-m gpu): the epilogue kernels of wrappers.hip / heuristics.hip past their grid caps, at their tails and on their alignment
+fall-backs, through the C ABI, against the float64 NumPy oracles (oracle/rollout_oracle.py, wrappers_oracle.py, heuristics_oracle.py).
+
+All of these kernels launch a capped grid (at most 4 096 blocks of 256 threads; obsnorm_pairs_kernel 8 192 blocks of two elements per
+lane) and walk the rest in strides of the grid, so the sizes here sit just above the caps: 1 048 576 elements, 2 097 152 pairs.  Every
+output buffer is filled with NaN (integers: -7) before a launch, so an element the kernel never wrote cannot pass by luck, and shifted or
+odd-sized buffers carry a guard element on either side that must keep its fill.
+
+Tolerances.  Statistics (float64 + - * only, -ffp-contract=off) and copies are compared exactly; the returns / advantages scan applies
+the oracle's float64 operations in the oracle's order and is compared exactly after the oracle's result is rounded to float32; float32
+outputs behind a sqrt and a division use the project's bound, 1e-5 (rewards: 1e-5 * max(1, |ref|.max()))."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import heuristics_oracle as ho
+from oracle import rollout_oracle as ro
+from oracle import wrappers_oracle as wo
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+NAN = float("nan")
+
+
+# ---------------------------------------------------------------- NumPy side (tests/test_oracle_wrappers.py pins the two helpers on the CPU)
+def masked_obs(so, x, mask):
+    """StdOracle.obs on the elements where `mask` (bool, the shape of x) is set: the oracle is applied to everything, then the statistics
+    are np.where(mask, new, old).  Returns the standardised x (meaningful where mask is set)."""
+    om, ov = so.om, so.ov
+    out = so.obs(x)
+    so.om, so.ov = np.where(mask, so.om, om), np.where(mask, so.ov, ov)
+    return out
+
+
+def masked_rew(so, r, mask):
+    """StdOracle.rew on the elements where `mask` is set, like masked_obs"""
+    rm, rv = so.rm, so.rv
+    out = so.rew(r)
+    so.rm, so.rv = np.where(mask, so.rm, rm), np.where(mask, so.rv, rv)
+    return out
+
+
+def _bits(a):
+    """float arrays as integers: a bit-for-bit comparison that also holds for NaN"""
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
+
+
+def _same_bits(a, b):
+    return a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
+
+
+# ---------------------------------------------------------------- device side
+def _d(x):
+    return torch.as_tensor(np.ascontiguousarray(x), device=DEV)
+
+
+class _Buf(object):
+    """n elements at an offset of `off` (0 or 1) elements inside an allocation of n + 2, everything set to `fill`: .t is what the kernel
+    gets, the elements around it are guards"""
+
+    def __init__(self, n, dtype, fill, off=0):
+        self.full = torch.full((n + 2,), fill, dtype=dtype, device=DEV)
+        assert self.full.data_ptr() % 16 == 0, "the allocator's blocks are expected to be 16-byte aligned"
+        self.n, self.off, self.fill = n, off, fill
+        self.t = self.full[off:off + n]
+
+    def np(self):
+        return self.t.cpu().numpy()
+
+    def guards_intact(self):
+        g = torch.cat([self.full[:self.off], self.full[self.off + self.n:]]).cpu().numpy()
+        return len(g) == 2 and _same_bits(g, np.full(2, self.fill, g.dtype))
+
+
+def _L():
+    from madrl_amd import _lib
+    return _lib, _lib.lib(), _lib.ptr, _lib.current_stream(torch.device(DEV))
+
+
+# ---------------------------------------------------------------- a. the returns / GAE scan
+GAE_DONE = np.array([0, 0, 0, 1, 2, 3, 0x80, 0x81], np.uint8)   # bit 7 (a capacity overflow mark) is no episode boundary
+
+
+def _gae_device(rew, done, val, gamma, lam):
+    _lib, L, P, st = _L()
+    T, N, A = rew.shape
+    r_d, dn_d = _d(rew), _d(done)
+    v_d = _d(val) if val is not None else None
+    ret_d = torch.full_like(r_d, NAN)
+    adv_d = torch.full_like(r_d, NAN) if val is not None else None
+    _lib.check(L.madrl_rollout_gae(P(r_d), P(dn_d), P(v_d), T, N, A, gamma, lam, P(ret_d), P(adv_d), st))
+    return ret_d.cpu().numpy(), adv_d.cpu().numpy() if val is not None else None
+
+
+def _first_bad(got, want):
+    bad = np.flatnonzero(_bits(got).reshape(-1) != _bits(want).reshape(-1))
+    cols = int(np.prod(got.shape[1:]))
+    return "no difference" if len(bad) == 0 else "%d of %d elements differ, first at column %d (got %r, want %r)" % (
+        len(bad), got.size, bad[0] % cols, got.reshape(-1)[bad[0]], want.reshape(-1)[bad[0]])
+
+
+@pytest.mark.parametrize("use_values", [True, False], ids=["adv", "returns_only"])
+@pytest.mark.parametrize("T,N,A", [(3, 131072, 8),     # exactly 1 048 576 columns: one column per thread of the capped grid
+                                   (3, 131073, 8),     # the cap + 8
+                                   (2, 1048577, 1),    # the cap + 1
+                                   (2, 299593, 7),     # 2 097 151: one short of two sweeps
+                                   (1, 2097153, 1)])   # two sweeps + 1
+def test_gae_every_column_beyond_the_grid_cap(T, N, A, use_values):
+    """gae_kernel once had no stride loop: the columns from 1 048 576 on were never written.  Exact against the oracle: the kernel and
+    rollout_oracle.gae apply the same float64 operations in the same order, and contraction is off."""
+    rng = np.random.RandomState(1000 * T + A)
+    rew = rng.randn(T, N, A).astype(np.float32)
+    val = rng.randn(T + 1, N, A).astype(np.float32) if use_values else None
+    done = GAE_DONE[rng.randint(0, len(GAE_DONE), (T, N))]
+    ret, adv = _gae_device(rew, done, val, 0.99, 0.95)
+    ref_ret, ref_adv = ro.gae(rew, done & 3, val, 0.99, 0.95)
+    assert np.array_equal(ret, ref_ret.astype(np.float32)), "returns: " + _first_bad(ret, ref_ret.astype(np.float32))
+    if use_values:
+        assert np.array_equal(adv, ref_adv.astype(np.float32)), "advantages: " + _first_bad(adv, ref_adv.astype(np.float32))
+
+
+# ---------------------------------------------------------------- b. ... through RolloutCollector
+class _SeededEnv(object):
+    """a batched env that plays seeded observation / reward / done tensors back (cf. ReplayEnv of tests/test_wrappers_gpu.py)"""
+
+    def __init__(self, n_envs, n_agents, n_steps, seed):
+        rng = np.random.RandomState(seed)
+        self.n_envs, self.device, self.t = n_envs, torch.device(DEV), 0
+        self.obs = _d(rng.randn(n_steps + 1, n_envs, n_agents, 1).astype(np.float32))
+        self.rew = _d(rng.randn(n_steps, n_envs, n_agents).astype(np.float32))
+        self.done_bits = _d(GAE_DONE[rng.randint(0, len(GAE_DONE), (n_steps, n_envs))])
+
+    def reset(self):
+        return self.obs[0]
+
+    def step(self, action):
+        t = self.t
+        self.t += 1
+        bits = self.done_bits[t]
+        return self.obs[t + 1], self.rew[t], (bits & 3) != 0, {"done_bits": bits}
+
+
+def test_collector_returns_and_advantages_for_more_columns_than_the_grid_cap():
+    """RolloutCollector._finish over 262 145 envs x 4 agents = 1 048 580 columns.  Two horizons: the trajectory tensors are allocated
+    once (torch.empty) and reused, so before the second horizon returns and advantages are filled with NaN."""
+    from madrl_amd.rollout import RolloutCollector
+    N, A, T = 262145, 4, 3
+    env = _SeededEnv(N, A, 2 * T, seed=7)
+
+    def policy(obs):
+        return torch.zeros(obs.shape[:2], dtype=torch.int32, device=obs.device), obs[..., 0] * 0.5
+
+    col = RolloutCollector(env, policy, T, discount=0.97, gae_lambda=0.9)
+    for it in range(2):
+        tr = col.collect()
+        rew, done, val = tr.rewards.cpu().numpy(), tr.dones.cpu().numpy(), tr.values.cpu().numpy()
+        assert np.array_equal(rew, env.rew[it * T:(it + 1) * T].cpu().numpy())
+        assert np.array_equal(done, env.done_bits[it * T:(it + 1) * T].cpu().numpy()) and (done & 0x80).any() and (done & 3).any()
+        assert np.array_equal(val, 0.5 * env.obs[it * T:(it + 1) * T + 1, ..., 0].cpu().numpy())
+        ref_ret, ref_adv = ro.gae(rew, done & 3, val, 0.97, 0.9)
+        ret, adv = tr.returns.cpu().numpy(), tr.advantages.cpu().numpy()
+        assert ret.shape == adv.shape == (T, N, A)
+        assert np.array_equal(ret, ref_ret.astype(np.float32)), "horizon %d returns: " % it + _first_bad(ret, ref_ret.astype(np.float32))
+        assert np.array_equal(adv, ref_adv.astype(np.float32)), "horizon %d advantages: " % it + _first_bad(adv, ref_adv.astype(np.float32))
+        tr.returns.fill_(NAN)
+        tr.advantages.fill_(NAN)
+
+
+# ---------------------------------------------------------------- c. obsnorm without a mask: the pairs kernel, its odd tail, the scalar fall-back
+def _obs_inputs(rng, calls, n):
+    """normal inputs around per-element offsets; the noise of call t is one seeded draw rotated by a different prime"""
+    offs, z = 3.0 * rng.randn(n), rng.randn(n)
+    return np.stack([(offs + 2.0 * np.roll(z, 977 * t)) for t in range(calls)]).astype(np.float32)
+
+
+def _obsnorm_unmasked(n, shift=None):
+    _lib, L, P, st = _L()
+    alpha, eps = 0.05, 1e-8
+    x = _obs_inputs(np.random.RandomState(n % 100003), 3, n)
+    off = lambda name: 1 if shift == name else 0
+    xin = _Buf(n, torch.float32, 0.0, off("obs_in"))
+    out = _Buf(n, torch.float32, NAN, off("obs_out"))
+    mean, var = _Buf(n, torch.float64, -7.0, off("mean")), _Buf(n, torch.float64, -7.0, off("var"))
+    mean.t.zero_()
+    var.t.fill_(1.0)
+    so = wo.StdOracle((n,), (1,), enable_obsnorm=True, obs_alpha=alpha, eps=eps)
+    for t in range(3):
+        xin.t.copy_(_d(x[t]))
+        out.t.fill_(NAN)
+        _lib.check(L.madrl_wrap_obsnorm(P(xin.t), P(mean.t), P(var.t), P(out.t), n, n, None, alpha, eps, st))
+        ref = so.obs(x[t])
+        assert np.array_equal(mean.np(), so.om), "call %d: mean (an element skipped or updated twice?)" % t
+        assert np.array_equal(var.np(), so.ov), "call %d: variance" % t
+        err = np.abs(out.np() - ref).max()
+        assert err < 1e-5, "call %d: standardised observations, max error %r" % (t, err)   # NaN (unwritten) fails too
+    assert mean.guards_intact() and var.guards_intact() and out.guards_intact()
+    assert np.array_equal(xin.np(), x[2])
+
+
+@pytest.mark.parametrize("n", [4195859,    # 2 * 2 097 152 + 2 * 777 + 1: a second trip of the pipelined loop for 777 lanes, and the odd tail
+                               4194304,    # exactly one trip everywhere
+                               1, 2, 3])   # scalar kernel alone; one pair; one pair + the odd tail
+def test_obsnorm_pairs_kernel_second_trip_and_tails(n):
+    _obsnorm_unmasked(n)
+
+
+@pytest.mark.parametrize("shift", ["obs_in", "obs_out", "mean", "var"])
+def test_obsnorm_scalar_fallback_for_each_misaligned_pointer_beyond_the_cap(shift):
+    """obs_in / obs_out off 8-byte alignment by one float, mean / var off 16-byte alignment by one double: the scalar kernel, 513 elements
+    beyond one sweep of its capped grid"""
+    _obsnorm_unmasked(1049089, shift)
+
+
+# ---------------------------------------------------------------- d. obsnorm under an env mask (partial reset)
+def _env_mask(rng, N, p=0.5):
+    m = (rng.rand(N) < p).astype(np.uint8)
+    m[0] = m[N - 1] = 1
+    return m
+
+
+def test_obsnorm_masked_beyond_the_cap_leaves_other_envs_bit_for_bit():
+    _lib, L, P, st = _L()
+    N, E, alpha, eps = 4099, 257, 0.05, 1e-8
+    n = N * E
+    rng = np.random.RandomState(41)
+    x = _obs_inputs(rng, 2, n)
+    mean, var = _Buf(n, torch.float64, -7.0), _Buf(n, torch.float64, -7.0)
+    out, xin = _Buf(n, torch.float32, NAN), _Buf(n, torch.float32, 0.0)
+    mean.t.zero_()
+    var.t.fill_(1.0)
+    so = wo.StdOracle((n,), (1,), enable_obsnorm=True, obs_alpha=alpha, eps=eps)
+    masks = [_env_mask(rng, N), _env_mask(rng, N)]
+    assert not np.array_equal(masks[0], masks[1]) and 0.4 < masks[0].mean() < 0.6
+    prev = out.np()
+    for t in range(2):
+        m_d, me = _d(masks[t]), np.repeat(masks[t] != 0, E)
+        xin.t.copy_(_d(x[t]))
+        _lib.check(L.madrl_wrap_obsnorm(P(xin.t), P(mean.t), P(var.t), P(out.t), n, E, P(m_d), alpha, eps, st))
+        ref = masked_obs(so, x[t], me)
+        assert np.array_equal(mean.np(), so.om) and np.array_equal(var.np(), so.ov), "call %d: statistics" % t
+        got = out.np()
+        assert np.abs(got[me] - ref[me]).max() < 1e-5, t
+        assert _same_bits(got[~me], prev[~me]), "call %d: an env outside the mask was written" % t
+        prev = got
+    assert np.isnan(prev[~(np.repeat(masks[0] != 0, E) | np.repeat(masks[1] != 0, E))]).all()   # in neither mask: never written
+    assert mean.guards_intact() and var.guards_intact() and out.guards_intact()
+
+
+# ---------------------------------------------------------------- e. rewnorm
+@pytest.mark.parametrize("mode", ["plain", "masked", "no_norm"])
+def test_rewnorm_beyond_the_cap(mode):
+    _lib, L, P, st = _L()
+    N, per, alpha, eps, scale = 349569, 3, 0.05, 1e-8, 0.7
+    n = N * per   # 1 048 707
+    rng = np.random.RandomState(len(mode))
+    offs = 2.0 * rng.randn(n)
+    r = np.stack([(offs + 3.0 * rng.randn(n)) for _ in range(3)]).astype(np.float32)
+    norm = mode != "no_norm"
+    mean, var = _Buf(n, torch.float64, -7.0), _Buf(n, torch.float64, -7.0)
+    out, rin = _Buf(n, torch.float32, NAN), _Buf(n, torch.float32, 0.0)
+    mean.t.zero_()
+    var.t.fill_(1.0)
+    so = wo.StdOracle((1,), (n,), scale_reward=scale, enable_rewnorm=norm, rew_alpha=alpha, eps=eps)
+    prev = out.np()
+    for t in range(3):
+        mask = _env_mask(rng, N) if mode == "masked" else None
+        me = np.repeat(mask != 0, per) if mask is not None else np.ones(n, bool)
+        rin.t.copy_(_d(r[t]))
+        m_d = _d(mask) if mask is not None else None
+        _lib.check(L.madrl_wrap_rewnorm(P(rin.t), P(mean.t) if norm else None, P(var.t) if norm else None, P(out.t), n, per,
+                                        P(m_d), alpha, eps, scale, int(norm), st))
+        ref = masked_rew(so, r[t], me)
+        assert np.array_equal(mean.np(), so.rm) and np.array_equal(var.np(), so.rv), "call %d: statistics" % t
+        got = out.np()
+        err = np.abs(got[me] - ref[me]).max()
+        assert err < 1e-5 * max(1.0, np.abs(ref[me]).max()), "call %d: max error %r" % (t, err)
+        assert _same_bits(got[~me], prev[~me]), "call %d: an env outside the mask was written" % t
+        prev = got
+    if not norm:   # null statistics: the oracle's stay at their initial values, and so does the memory the test did not pass
+        assert not so.rm.any() and (so.rv == 1.0).all()
+    assert mean.guards_intact() and var.guards_intact() and out.guards_intact()
+
+
+# ---------------------------------------------------------------- f. observation buffer (frame stack)
+@pytest.mark.parametrize("k,off", [(1, 0), (3, 0), (4, 0), (4, 1)], ids=["k1", "k3", "k4_float4", "k4_shifted_scalar"])
+def test_obsbuffer_beyond_the_cap_with_reset_bytes_and_active_mask(k, off):
+    """k = 4 on a 16-byte aligned buffer moves one float4 per element (obsbuffer4_kernel); shifted by one float it takes the scalar kernel.
+    Copies only: exact."""
+    _lib, L, P, st = _L()
+    N, E = 4099, 257
+    n = N * E   # 1 053 443
+    rng = np.random.RandomState(10 * k + off)
+    obs = rng.randn(4, N, E).astype(np.float32)
+    full = torch.full((n * k + 8,), NAN, dtype=torch.float32, device=DEV)
+    assert full.data_ptr() % 16 == 0
+    buf = full[4 + off:4 + off + n * k]
+    bo = wo.BufOracle((N, E), k)
+    reset_bytes = np.array([0, 1, 2, 0x80, 0x81], np.uint8)   # bit 7 alone (an overflow mark) resets nothing
+    pushes = [(np.ones(N, np.uint8), None),                                   # 1. all reset
+              (None, None),                                                   # 2. plain push
+              (reset_bytes[rng.randint(0, 5, N)], None),                      # 3. reset bytes
+              (reset_bytes[rng.randint(0, 5, N)], _env_mask(rng, N))]         # 4. reset bytes under an active mask
+    for t, (rm, am) in enumerate(pushes):
+        o_d, rm_d, am_d = _d(obs[t]), _d(rm) if rm is not None else None, _d(am) if am is not None else None   # (alive across the launch)
+        _lib.check(L.madrl_wrap_obsbuffer(P(o_d), P(buf), n, E, k, P(rm_d), P(am_d), st))
+        old = bo.buf.copy()
+        new = bo.step(obs[t], reset_mask=(rm & 0x7F) != 0 if rm is not None else None)
+        if am is not None:
+            bo.buf = np.where((am != 0)[:, None, None], new, old)   # inactive envs keep their history
+        assert np.array_equal(buf.cpu().numpy().reshape(N, E, k), bo.buf.astype(np.float32)), "push %d" % (t + 1)
+    g = torch.cat([full[:4 + off], full[4 + off + n * k:]]).cpu().numpy()
+    assert np.isnan(g).all(), "written outside the buffer"
+
+
+# ---------------------------------------------------------------- g. diagnostics: the tail of its 128-thread blocks
+@pytest.mark.parametrize("N,A", [(1, 1), (130, 7), (257, 1)])
+def test_diagnostics_block_tail_and_untouched_slots_of_unfinished_envs(N, A):
+    _lib, L, P, st = _L()
+    steps, discount, mtl = 14, 0.9, 5
+    rng = np.random.RandomState(N + A)
+    done_set = np.array([0, 0, 0, 1, 2, 0x80, 0x83], np.uint8)
+    f64 = dict(dtype=torch.float64, device=DEV)
+    ep_rew, disc_ret, disc_pow = torch.zeros((N, A), **f64), torch.zeros(N, **f64), torch.zeros(N, **f64)
+    ep_len = torch.zeros(N, dtype=torch.int32, device=DEV)
+    o_rew, o_disc = torch.full((N, A), NAN, **f64), torch.full((N,), NAN, **f64)
+    o_len = torch.full((N,), -7, dtype=torch.int32, device=DEV)
+    o_fin = torch.full((N,), 7, dtype=torch.uint8, device=DEV)
+    do = wo.DiagOracle(N, A, discount, mtl)
+    e_rew, e_disc, e_len = np.full((N, A), NAN), np.full(N, NAN), np.full(N, -7, np.int32)   # what the output slots must hold
+    n_fin = 0
+    for t in range(steps):
+        rew = rng.randn(N, A).astype(np.float32)
+        done = done_set[rng.randint(0, len(done_set), N)]
+        o_fin.fill_(7)
+        rew_d, done_d = _d(rew), _d(done)   # (alive across the launch)
+        _lib.check(L.madrl_wrap_diagnostics(P(rew_d), P(done_d), P(ep_rew), P(ep_len), P(disc_ret), P(disc_pow), N, A, discount, mtl,
+                                            P(o_rew), P(o_disc), P(o_len), P(o_fin), st))
+        ref = do.step(rew, (done & 3) != 0)
+        fin = ref["finished"]
+        n_fin += int(fin.sum())
+        assert np.array_equal(o_fin.cpu().numpy(), fin.astype(np.uint8)), t
+        prev_disc = e_disc.copy()
+        e_rew[fin], e_disc[fin], e_len[fin] = ref["reward"][fin], ref["disc"][fin], ref["length"][fin]
+        assert np.array_equal(o_len.cpu().numpy(), e_len), t
+        assert _same_bits(o_rew.cpu().numpy(), e_rew), t            # sequential float64 sums of float32 values: exact
+        got_disc = o_disc.cpu().numpy()
+        assert (np.abs(got_disc[fin] - e_disc[fin]) <= 1e-12 * np.maximum(1.0, np.abs(e_disc[fin]))).all(), t
+        assert _same_bits(got_disc[~fin], prev_disc[~fin]), "step %d: the slot of an unfinished env changed" % t
+        e_disc[fin] = got_disc[fin]                                 # (carried bit for bit from here on)
+        assert np.array_equal(ep_len.cpu().numpy(), do.ep_len) and np.array_equal(ep_rew.cpu().numpy(), do.ep_rew), t
+    assert n_fin >= 2 * N   # max_traj_len 5 over 14 steps: every env finishes at least twice
+
+
+# ---------------------------------------------------------------- h. the chase policy at obs_range 3
+@pytest.mark.parametrize("n_rows", [5, 70001])
+def test_pursuit_policy_rows_kernel_obs_range_3(n_rows):
+    """9 cells: lanes 0 and 1 of a row's 16 load cells 0-3 and 4-7, the other 14 step back onto cells 5-8.  Windows are built as in
+    test_pursuit_policy_rows_kernel_any_row_count_and_its_own_draw_counter, with the evader density raised from 0.04 to 0.15 so that
+    with 9 cells instead of 49 about three windows in four still hold an evader."""
+    from madrl_amd import _lib
+    from madrl_amd.heuristics import PursuitHeuristicPolicy
+    R = 3
+    rng = np.random.RandomState(n_rows)
+    win = np.zeros((n_rows, R, R, 4), np.float32)
+    win[..., 2] = (rng.rand(n_rows, R, R) < 0.15) * rng.randint(1, 4, (n_rows, R, R))
+    win[..., 0] = rng.rand(n_rows, R, R) < 0.2
+    win[..., 1] = rng.randint(0, 3, (n_rows, R, R))
+    ref = ho.pursuit_actions(win[:20000])
+    det = ref >= 0
+    assert det.any() and not det.all()
+    rows = np.concatenate([np.transpose(win[..., :3], (0, 3, 1, 2)).reshape(n_rows, -1), np.full((n_rows, 1), 0.5, np.float32)], axis=1)
+    assert rows.shape[1] == 3 * R * R + 1
+    pol = PursuitHeuristicPolicy(R, flatten=True, seed=11)
+    obs = torch.as_tensor(rows, device=DEV).view(n_rows, 1, -1)
+    act = torch.full((n_rows, 1), -7, dtype=torch.int32, device=DEV)
+    a = pol(obs, out=act).cpu().numpy()[:, 0]
+    assert a.min() >= 0 and a.max() <= 4, "a row without an action"
+    assert np.array_equal(a[:len(ref)][det], ref[det])
+    # the (R, R, 4) layout takes the generic kernel: same actions everywhere, the drawn ones included (same seed, row ids and tick)
+    act_b = torch.full((n_rows, 1), -7, dtype=torch.int32, device=DEV)
+    b = PursuitHeuristicPolicy(R, flatten=False, seed=11)(torch.as_tensor(win, device=DEV).view(n_rows, 1, R, R, 4), out=act_b).cpu().numpy()[:, 0]
+    assert np.array_equal(a, b)
+    for _ in range(4):
+        pol(obs)
+    torch.cuda.synchronize()
+    t = pol._tick.cpu().numpy()
+    assert len(t) == _lib.POLICY_COUNTER_WORDS and t[0] == 5 and not t[1:].any()

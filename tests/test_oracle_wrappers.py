@@ -22,6 +22,39 @@ def test_standardized_env_oracle_matches_reference():
             assert np.abs(o.rew(g["rew"][t]) - g["std_rew"][t]).max() < 1e-12
 
 
+def test_masked_statistics_helpers_are_the_oracle_under_a_full_mask_and_the_identity_under_an_empty_one():
+    """masked_obs / masked_rew of tests/test_epilogue_geometry_gpu.py (the oracle, then np.where(mask, new, old) on the statistics) are
+    what the GPU tests of partial resets compare the kernels with"""
+    from test_epilogue_geometry_gpu import masked_obs, masked_rew
+    rng = np.random.RandomState(3)
+    shape = (6, 5)
+    cfg = dict(scale_reward=0.7, enable_obsnorm=True, enable_rewnorm=True, obs_alpha=0.05, rew_alpha=0.05)
+    plain, full, none = (wo.StdOracle(shape, shape, **cfg) for _ in range(3))
+    stats = lambda o: (o.om, o.ov, o.rm, o.rv)
+    for t in range(4):
+        x, r = (3 * rng.randn(*shape)).astype(np.float32), rng.randn(*shape).astype(np.float32)
+        if t == 0:   # something other than the initial statistics for the identity to keep
+            for o in (plain, full, none):
+                o.obs(x), o.rew(r)
+            continue
+        before = [s.copy() for s in stats(none)]
+        want_o, want_r = plain.obs(x), plain.rew(r)
+        assert np.array_equal(masked_obs(full, x, np.ones(shape, bool)), want_o)
+        assert np.array_equal(masked_rew(full, r, np.ones(shape, bool)), want_r)
+        masked_obs(none, x, np.zeros(shape, bool)), masked_rew(none, r, np.zeros(shape, bool))
+        assert all(np.array_equal(a, b) for a, b in zip(stats(full), stats(plain)))
+        assert all(np.array_equal(a, b) for a, b in zip(stats(none), before))
+    assert not np.array_equal(plain.om, none.om) and not np.array_equal(plain.rv, none.rv)
+    # a mixed mask: each element follows the one or the other
+    m = rng.rand(*shape) < 0.5
+    om, rv = none.om.copy(), none.rv.copy()
+    ref = wo.StdOracle(shape, shape, **cfg)
+    ref.om, ref.ov, ref.rm, ref.rv = (s.copy() for s in stats(none))
+    ref.obs(x), ref.rew(r)
+    masked_obs(none, x, m), masked_rew(none, r, m)
+    assert np.array_equal(none.om, np.where(m, ref.om, om)) and np.array_equal(none.rv, np.where(m, ref.rv, rv)) and m.any() and not m.all()
+
+
 def test_observation_buffer_oracle_matches_reference():
     g = np.load(G)
     T, P, D = g["obs"].shape
