@@ -326,6 +326,20 @@ int madrl_waterworld_kernel_kind(madrl_waterworld *h, int32_t *out);
  * stays 0 / 1 by cfg.crowd. */
 int madrl_waterworld_set_particle_counts(madrl_waterworld *h, const int32_t *pending_dev, int32_t *live_dev);
 
+/* Per-pursuer sensor ranges (the array form of MAWaterWorld's sensor_range, waterworld.py:96, :109): pursuer i senses with ranges[i]
+ * instead of cfg.sensor_range.  The range enters the ray test of Archea.sensed (:68) alone, so positions, rewards, done and info are those
+ * of the uniform handle, and observation row i is bit for bit row i of a uniform handle created with sensor_range = ranges[i].
+ *   ranges_host  float64 [n_pursuers] in HOST memory, like sensors_host of create; each value is rounded to float32 once, the way
+ *                cfg.sensor_range is, and must be finite and > 0 (MADRL_EINVAL).  The handle owns the device copy (destroy frees it);
+ *                the array may be freed after the call.  Not to be called while a launch of this handle is in flight.
+ *                NULL: back to the uniform cfg.sensor_range and the dispatch the handle had (a specialised instantiation included).
+ * Works on cfg.crowd == 0 and == 1 handles: while ranges are bound, reset / step launch waterworld_kernel_ranges (the generic
+ * one-wavefront kernel, whatever the shape) or ww_crowd_kernel_ranges; madrl_waterworld_kernel_kind stays 0 / 1 by cfg.crowd.
+ * Out of scope, and refused with MADRL_EINVAL in either order: ranges together with madrl_waterworld_set_particle_counts, and ranges
+ * together with a fused madrl_waterworld_set_standardize (the epilogue kernels madrl_wrap_obsnorm / madrl_wrap_rewnorm serve such a
+ * handle).  The hostage world has no such call: it senses with one range. */
+int madrl_waterworld_set_sensor_ranges(madrl_waterworld *h, const double *ranges_host);
+
 /* Fused StandardizedEnv (madrl_environments/__init__.py:204-311): bind the wrapper's state to the env handle and the step /
  * reset kernels normalise the observation row as it leaves LDS (and the rewards as they are produced) instead of storing it
  * raw for a second launch (madrl_wrap_obsnorm / _rewnorm) to read back: 36 instead of 44 bytes of HBM traffic per observation

@@ -116,6 +116,7 @@ SIGNATURES = {
     "madrl_waterworld_set_launch": (C.c_int, [_vp, C.c_int64]),
     "madrl_waterworld_kernel_kind": (C.c_int, [_vp, _vp]),
     "madrl_waterworld_set_particle_counts": (C.c_int, [_vp, _vp, _vp]),
+    "madrl_waterworld_set_sensor_ranges": (C.c_int, [_vp, _vp]),
     "madrl_waterworld_set_standardize": (C.c_int, [_vp, _vp]),
     "madrl_waterworld_reset": (C.c_int, [_vp] * 4),
     "madrl_waterworld_step": (C.c_int, [_vp] * 8),

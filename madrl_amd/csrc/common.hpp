@@ -304,6 +304,8 @@ struct ParticleHandle {
     bool std_bound;
     const int32_t *pending;  // particle_set_counts: caller-owned [n_envs][3], both NULL = one shape for all envs
     int32_t *live;
+    void *range_tables;      // madrl_waterworld_set_sensor_ranges: the handle's copy of `tables` with the per-agent sensor ranges behind it
+    bool ranged;             // ... is bound: dev.sensors points to it, dev.sensor_range is its maximum, lds_bytes holds the ranges too
 };
 
 // madrl_waterworld_create / madrl_hostage_create after the world's own validation of cfg: H is the handle, layout() and lds_bytes()
@@ -357,6 +359,7 @@ template <class H>
 void particle_destroy(H *h) {
     if (!h) return;
     if (h->tables) (void)hipFree(h->tables);
+    if (h->range_tables) (void)hipFree(h->range_tables);
     if (h->std_dev) (void)hipFree(h->std_dev);
     delete h;
 }
@@ -377,6 +380,8 @@ int particle_set_counts(H *h, const int32_t *pending_dev, int32_t *live_dev, boo
     if (!h->cfg.crowd && !wave_live) return fail(MADRL_EINVAL, "set_particle_counts: per-env particle counts run on the crowd kernel (cfg.crowd = 1)");
     if ((pending_dev == nullptr) != (live_dev == nullptr))
         return fail(MADRL_EINVAL, "set_particle_counts: pending_dev and live_dev are both arrays or both NULL");
+    if (live_dev != nullptr && h->ranged)
+        return fail(MADRL_EINVAL, "set_particle_counts: per-pursuer sensor ranges are bound (set_sensor_ranges), and the live-count kernels take one range; unbind them first (set_sensor_ranges(NULL))");
     if (live_dev != nullptr && h->std_bound)
         return fail(MADRL_EINVAL, "set_particle_counts: a fused StandardizedEnv is bound, and the live-count kernel has none; unbind it first (set_standardize(NULL))");
     h->pending = pending_dev;
@@ -388,6 +393,8 @@ template <class H>
 int particle_set_standardize(H *h, const madrl_standardize_args *a) {
     if (!h) return fail(MADRL_EINVAL, "handle is NULL");
     if (!a) { h->std_bound = false; return MADRL_OK; }
+    if (h->ranged)
+        return fail(MADRL_EINVAL, "set_standardize: the ranged kernel (set_sensor_ranges) has no fused StandardizedEnv; use the epilogue kernels (madrl_wrap_obsnorm / madrl_wrap_rewnorm)");
     if (h->cfg.crowd)
         return fail(MADRL_EINVAL, "set_standardize: the crowd kernel has no fused StandardizedEnv; use the epilogue kernels (madrl_wrap_obsnorm / madrl_wrap_rewnorm)");
     if (h->live != nullptr)

@@ -17,6 +17,9 @@
 //   epilogue    the fused StandardizedEnv (std_reward, std_obs_row), then the record goes back (store_record)
 //   live counts a live-count entry (waterworld_kernel_live) fetches the env's counts with its record (WaveCounts) and moves the record between the
 //               capacity's slotted layout and the packed layout of the env's counts (slot_to_packed; the mapped to_lds / store_record)
+//   ranges      a ranged entry (waterworld_kernel_ranges) keeps phase C's helpers as they are: ray_misses takes srange per lane -- there the
+//               range of the lane's own agent, from a table next to the sensor vectors in LDS -- and reach_cull / pass_reach run on the
+//               table's maximum, which keeps the cull conservative for every agent (it only skips what the ray test would reject)
 // The helpers take the LDS arrays, the counts and the lane as arguments and know nothing of a world's structs.  Two kinds of argument
 // keep the kernels' code as it was measured: a launch parameter that a kernel reads inside a branch or a loop is read there, through
 // kernargs<KA>() (common.hpp; KA is the kernel's view struct {Dev d; IO io;}, and only fields both worlds have under one name are

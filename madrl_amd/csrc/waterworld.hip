@@ -28,7 +28,9 @@
 // the handle was created with cfg.crowd = 1; the handle, validation, record layout and dispatch of both kernels are in this file.
 // The kernel's text is waterworld_wave_body.inc, included inside two __global__ entries: waterworld_kernel<...> (one shape for all envs, the
 // instantiations as they were) and waterworld_kernel_live<MODE> (per-env particle counts within the handle's capacity,
-// madrl_waterworld_set_particle_counts on a handle with cfg.crowd = 0: the generic body, the count arrays as a third argument).
+// madrl_waterworld_set_particle_counts on a handle with cfg.crowd = 0: the generic body, the count arrays as a third argument) and
+// waterworld_kernel_ranges<MODE> (a sensor range per pursuer, madrl_waterworld_set_sensor_ranges: the generic body, the ranges behind
+// the sensor table).
 // Arithmetic is float32 (north_star tolerance 1e-5 against the float64 reference); every
 // expression keeps the statement order of the reference's step() so that a float32 CPU restatement agrees bit for bit.
 #include "waterworld_dev.hpp"   // WwDev, WwIO, the RNG tags: shared with waterworld_crowd.hip
@@ -76,7 +78,9 @@ static_assert(sizeof(WwKArgs) % 8 == 0 && sizeof(WwKArgsLive) == sizeof(WwKArgs)
 template <int MODE, int TNp, int TNe, int TNpo, int TK, bool FUSED = false, int TD = 0>
 __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev d, const WwIO io) {
 #define MADRL_WW_BODY_LIVE 0
+#define MADRL_WW_BODY_RANGES 0
 #include "waterworld_wave_body.inc"
+#undef MADRL_WW_BODY_RANGES
 #undef MADRL_WW_BODY_LIVE
 }
 
@@ -87,7 +91,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void
     constexpr int TNp = 0, TNe = 0, TNpo = 0, TK = 0, TD = 0;
     constexpr bool FUSED = false;
 #define MADRL_WW_BODY_LIVE 1
+#define MADRL_WW_BODY_RANGES 0
 #include "waterworld_wave_body.inc"
+#undef MADRL_WW_BODY_RANGES
+#undef MADRL_WW_BODY_LIVE
+}
+
+// The ranged entry: the generic body (run-time counts, dynamic LDS, registers left to the compiler) with a sensor range per pursuer
+// (madrl_waterworld_set_sensor_ranges on a handle with cfg.crowd = 0).  d.sensors holds the ranges [Np] behind the sensor vectors, the
+// workgroup's LDS up4(Np) floats more, and d.sensor_range their maximum.  Whatever the shape: no specialised form, no fused StandardizedEnv.
+template <int MODE>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void waterworld_kernel_ranges(const WwDev d, const WwIO io) {
+    constexpr int TNp = 0, TNe = 0, TNpo = 0, TK = 0, TD = 0;
+    constexpr bool FUSED = false;
+#define MADRL_WW_BODY_LIVE 0
+#define MADRL_WW_BODY_RANGES 1
+#include "waterworld_wave_body.inc"
+#undef MADRL_WW_BODY_RANGES
 #undef MADRL_WW_BODY_LIVE
 }
 #undef DA
@@ -183,7 +203,7 @@ const WwSpec WW_SPECS[] = {
 int ww_launch(const madrl_waterworld *h, const WwIO &io, int mode, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     const WwDev &d = h->dev;
-    if (h->cfg.crowd) return ww_crowd_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, h->pending, h->live, stream);
+    if (h->cfg.crowd) return ww_crowd_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, h->pending, h->live, h->ranged, stream);
     const dim3 g = particle_grid(h->max_blocks, d.n_envs), b(64);
     const bool fused = io.st != nullptr;
     if (h->live != nullptr) {  // per-env particle counts: the generic body at the capacity's LDS bytes, whatever the shape
@@ -191,6 +211,13 @@ int ww_launch(const madrl_waterworld *h, const WwIO &io, int mode, void *stream)
         const ParticleCounts cn{h->pending, h->live};
         if (mode == 0) hipLaunchKernelGGL(waterworld_kernel_live<0>, g, b, h->lds_bytes, s, h->dev, io, cn);
         else hipLaunchKernelGGL(waterworld_kernel_live<1>, g, b, h->lds_bytes, s, h->dev, io, cn);
+        MADRL_HIP_TRY(hipGetLastError());
+        return MADRL_OK;
+    }
+    if (h->ranged) {  // per-pursuer sensor ranges: the generic body with the ranges in LDS, whatever the shape
+        if (fused) return fail(MADRL_EINVAL, "the ranged kernel has no fused StandardizedEnv");
+        if (mode == 0) hipLaunchKernelGGL(waterworld_kernel_ranges<0>, g, b, h->lds_bytes, s, h->dev, io);
+        else hipLaunchKernelGGL(waterworld_kernel_ranges<1>, g, b, h->lds_bytes, s, h->dev, io);
         MADRL_HIP_TRY(hipGetLastError());
         return MADRL_OK;
     }
@@ -267,6 +294,44 @@ int madrl_waterworld_set_launch(madrl_waterworld *h, int64_t max_blocks) { retur
 
 int madrl_waterworld_set_particle_counts(madrl_waterworld *h, const int32_t *pending_dev, int32_t *live_dev) {
     return particle_set_counts(h, pending_dev, live_dev, /*wave_live=*/true);
+}
+
+int madrl_waterworld_set_sensor_ranges(madrl_waterworld *h, const double *ranges_host) {
+    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
+    const size_t base_lds = h->cfg.crowd ? ww_lds_bytes_crowd(h->dev) : ww_lds_bytes(h->dev);
+    if (!ranges_host) {  // back to cfg.sensor_range and the dispatch the handle had
+        h->ranged = false;
+        h->dev.sensors = (const float *)h->tables;
+        h->dev.sensor_range = (float)h->cfg.sensor_range;
+        h->lds_bytes = base_lds;
+        return MADRL_OK;
+    }
+    if (h->live != nullptr)
+        return fail(MADRL_EINVAL, "set_sensor_ranges: per-env particle counts are bound (set_particle_counts), and the live-count kernels take one range; unbind them first (set_particle_counts(NULL, NULL))");
+    if (h->std_bound)
+        return fail(MADRL_EINVAL, "set_sensor_ranges: a fused StandardizedEnv is bound (set_standardize), and the ranged kernel has none; unbind it first (set_standardize(NULL))");
+    const int Np = h->dev.Np, sen = up4(2 * h->dev.K);  // the ranges lie behind the sensor vectors [K][2], on a 16-byte boundary
+    std::vector<float> tab((size_t)sen + up4(Np), 0.0f);
+    float top = 0.0f;
+    for (int i = 0; i < Np; ++i) {
+        if (!(ranges_host[i] > 0.0) || !isfinite(ranges_host[i]))
+            return fail(MADRL_EINVAL, "set_sensor_ranges: ranges[%d]=%g must be finite and > 0", i, ranges_host[i]);
+        const float r = (float)ranges_host[i];  // rounded once, like cfg.sensor_range (ww_layout)
+        if (!(r > 0.0f) || !isfinite(r)) return fail(MADRL_EINVAL, "set_sensor_ranges: ranges[%d]=%g is no positive finite float32", i, ranges_host[i]);
+        tab[sen + i] = r;
+        top = r > top ? r : top;
+    }
+    const size_t lds = base_lds + (size_t)up4(Np) * 4;
+    if (lds > 64 * 1024) return fail(MADRL_EINVAL, "set_sensor_ranges: configuration needs %zu B of LDS (> 64 KiB)", lds);
+    MADRL_HIP_TRY(hipSetDevice(h->device));
+    MADRL_HIP_TRY(hipMemcpy(tab.data(), h->tables, (size_t)2 * h->dev.K * sizeof(float), hipMemcpyDeviceToHost));
+    if (!h->range_tables) MADRL_HIP_TRY(hipMalloc(&h->range_tables, tab.size() * sizeof(float)));
+    MADRL_HIP_TRY(hipMemcpy(h->range_tables, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    h->dev.sensors = (const float *)h->range_tables;
+    h->dev.sensor_range = top;  // the reach cull runs on it: conservative for every pursuer; the ray test takes the pursuer's own
+    h->lds_bytes = lds;
+    h->ranged = true;
+    return MADRL_OK;
 }
 
 int madrl_waterworld_reset(madrl_waterworld *h, const uint8_t *mask_dev, float *obs_dev, void *stream) {

@@ -33,14 +33,23 @@ using namespace madrl;
 // the workgroup.  The LDS parts keep their offsets at the capacity (ww_crowd_lds_bytes of the capacity bounds every live triple).
 template <int MODE, int NW>
 __global__ __launch_bounds__(64 * NW) void ww_crowd_kernel(const WwDev d, const WwIO io) {
-    constexpr bool LIVE = false;
+    constexpr bool LIVE = false, RANGES = false;
     constexpr ParticleCounts cn{nullptr, nullptr};
 #include "waterworld_crowd_body.inc"
 }
 
 template <int MODE, int NW>
 __global__ __launch_bounds__(64 * NW) void ww_crowd_kernel_live(const WwDev d, const WwIO io, const ParticleCounts cn) {
-    constexpr bool LIVE = true;
+    constexpr bool LIVE = true, RANGES = false;
+#include "waterworld_crowd_body.inc"
+}
+
+// The ranged entry (madrl_waterworld_set_sensor_ranges): the fixed-shape text with a sensor range per pursuer; d.sensors holds the ranges
+// behind the sensor vectors and the workgroup's LDS up4(Np) floats more.
+template <int MODE, int NW>
+__global__ __launch_bounds__(64 * NW) void ww_crowd_kernel_ranges(const WwDev d, const WwIO io) {
+    constexpr bool LIVE = false, RANGES = true;
+    constexpr ParticleCounts cn{nullptr, nullptr};
 #include "waterworld_crowd_body.inc"
 }
 
@@ -54,7 +63,10 @@ size_t ww_crowd_lds_bytes(int Np, int Ne, int Npo, int K, int rec_dw) {
 }
 
 int ww_crowd_launch(const void *dev, const void *io, int mode, int64_t max_blocks, size_t lds_bytes, const int32_t *pending, int32_t *live,
-                    void *stream) {
+                    bool ranged, void *stream) {
+    if (ranged)  // per-pursuer sensor ranges (never together with per-env counts: the two calls refuse each other)
+        return crowd_launch<WwDev, WwIO>(mode == 0 ? ww_crowd_kernel_ranges<0, MADRL_WWC_NW> : ww_crowd_kernel_ranges<1, MADRL_WWC_NW>, MADRL_WWC_NW,
+                                         dev, io, max_blocks, lds_bytes, stream);
     if (live != nullptr)  // per-env particle counts
         return crowd_launch<WwDev, WwIO>(mode == 0 ? ww_crowd_kernel_live<0, MADRL_WWC_NW> : ww_crowd_kernel_live<1, MADRL_WWC_NW>, MADRL_WWC_NW,
                                          dev, io, ParticleCounts{pending, live}, max_blocks, lds_bytes, stream);

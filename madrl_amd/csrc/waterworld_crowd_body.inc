@@ -1,6 +1,9 @@
 // waterworld_crowd_body.inc -- the body of ww_crowd_kernel<MODE, NW> and ww_crowd_kernel_live<MODE, NW> (waterworld_crowd.hip), included
 // inside both __global__ entries like pursuit_crowd_body.inc: the fixed-shape entry keeps its two arguments and its code.  In scope: MODE,
-// NW, d (WwDev), io (WwIO), `constexpr bool LIVE` and, when LIVE, cn (ParticleCounts).
+// NW, d (WwDev), io (WwIO), `constexpr bool LIVE` and, when LIVE, cn (ParticleCounts); `constexpr bool RANGES` (ww_crowd_kernel_ranges,
+// madrl_waterworld_set_sensor_ranges): every pursuer senses with its own range, from the table RNG [Np] behind the sensor vectors (in
+// global memory at d.sensors + up4(2 K)); d.sensor_range is then the table's maximum, which keeps the reach walk conservative for every
+// pursuer of a pass, and a ray takes the range of its own pursuer.
     static_assert(NW >= 2 && NW <= 16, "a thread owns at most one pursuer (n_pursuers <= 128)");
     constexpr int NT = 64 * NW;
     extern __shared__ __attribute__((aligned(16))) float smem_crowd[];
@@ -14,12 +17,15 @@
     float *S = smem_crowd;
     float *X = S, *V = S + 2 * NPc, *OB = S + 4 * NPc;
     float *SEN = S + up4(rec_dw);
-    float *ACT = SEN + up4(2 * K);
+    [[maybe_unused]] float *RNG = SEN + up4(2 * K);  // RANGES only
+    float *ACT = SEN + up4(2 * K) + (RANGES ? up4(Pc) : 0);
     uint64_t *COL = reinterpret_cast<uint64_t *>(ACT + up4(2 * Np));  // [Np][W]
     uint64_t *CAU = COL + Np * W;                                     // [W]   caught evaders | caught poisons
     uint64_t *ENC = CAU + W;                                          // [WE]  evaders touched by at least one pursuer
 
     for (int k = tid; k < 2 * K; k += NT) SEN[k] = d.sensors[k];
+    if constexpr (RANGES)
+        for (int k = tid; k < Pc; k += NT) RNG[k] = d.sensors[up4(2 * K) + k];
 
     PassShape passes = pass_shape(K, Np, lane);
     // LIVE: an env's counts and what follows from them
@@ -178,7 +184,7 @@
                 const bool speed = (bool)d.speed_features;
                 for (int p = wave; p < passes.n_pass; p += NW) {
                     const PassLanes L = pass_lanes(passes, p, K, Np, lane);  // the pursuers of this pass
-                    Ray ray(SEN, X, V, L.iq, L.kq, srange, rad2);
+                    Ray ray(SEN, X, V, L.iq, L.kq, RANGES ? RNG[L.iq] : srange, rad2);  // (L.iq < Np)
                     float *const o = orow_env + (int64_t)L.iq * D + L.kq;
 #pragma unroll
                     for (int cls = 0; cls < 4; ++cls) {  // 0 obstacle, 1 evaders, 2 poison, 3 allies

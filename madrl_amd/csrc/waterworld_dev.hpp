@@ -47,8 +47,9 @@ namespace madrl {
 
 // waterworld_crowd.hip.  dev / io: a WwDev and a WwIO (see the note at the top); mode 0 = reset, 1 = step.  live != NULL: the per-env
 // particle counts of madrl_waterworld_set_particle_counts (the kernels' live-count instantiations), the shape of dev being the capacity.
+// ranged: the per-pursuer sensor ranges of madrl_waterworld_set_sensor_ranges lie behind dev's sensor table and lds_bytes has room for them.
 int ww_crowd_launch(const void *dev, const void *io, int mode, int64_t max_blocks, size_t lds_bytes, const int32_t *pending, int32_t *live,
-                    void *stream);
+                    bool ranged, void *stream);
 // the dynamic LDS of one ww_crowd_kernel workgroup
 size_t ww_crowd_lds_bytes(int n_pursuers, int n_evaders, int n_poison, int n_sensors, int rec_dw);
 

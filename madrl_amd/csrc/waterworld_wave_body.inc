@@ -1,7 +1,7 @@
 // waterworld_wave_body.inc -- the body of waterworld_kernel<MODE, TNp, TNe, TNpo, TK, FUSED, TD> and waterworld_kernel_live<MODE>
 // (waterworld.hip), included inside both __global__ entries like waterworld_crowd_body.inc: the fixed-shape entry keeps its two arguments,
 // its name and its code.  In scope: MODE, TNp .. TD, FUSED, d (WwDev), io (WwIO) and the macro MADRL_WW_BODY_LIVE (0 / 1); the live entry's third
-// argument (ParticleCounts) is read through kernargs<WwKArgsLive>().
+// argument (ParticleCounts) is read through kernargs<WwKArgsLive>().  MADRL_WW_BODY_RANGES (0 / 1): the ranged entry, see RNG below.
 // LIVE: d.Np / d.Ne / d.Npo are a CAPACITY (Pc, Ec, POc) and every env runs its own counts.  Whatever a caller sees stays at the capacity,
 // slotted by class: the record, the rows of inj_resp, the action / reward / observation rows (stride Pc).  The env's counts travel with the
 // record prefetch (WaveCounts); the slotted record is packed to the live counts on its way into LDS and scattered back on its way out
@@ -39,7 +39,15 @@
     float *O = S + (((TNp > 0 ? 4 * (TNp + TNe + TNpo) + 4 : d.rec_dw) + 3) & ~3);  // observation staging [Np][D]
     float *const O_SPARE = O + Pc * D;                  // one more row: where the sensing lanes without a (pursuer, sensor) pair write
     float *SEN = O + (((Pc + 1) * D + 3) & ~3);         // sensor unit vectors [K][2]
+    // RANGES (waterworld_kernel_ranges, madrl_waterworld_set_sensor_ranges): every pursuer senses with its own range.  The table [Pc] lies
+    // behind the sensor vectors, in global memory (d.sensors + up4(2 K)) as in LDS; a sensing pass reads its lane's pursuer's range from it
+    // for the ray test, and d.sensor_range is the table's maximum: the reach cull, which runs on it, is conservative for every pursuer.
+#if MADRL_WW_BODY_RANGES
+    float *RNG = SEN + ((2 * K + 3) & ~3);
+    uint64_t *NEAR = reinterpret_cast<uint64_t *>(RNG + ((Pc + 3) & ~3));
+#else
     uint64_t *NEAR = reinterpret_cast<uint64_t *>(SEN + ((2 * K + 3) & ~3));  // per pursuer: particles (bit j) / obstacle (bit NP) in sensing reach
+#endif
     uint8_t *COL = reinterpret_cast<uint8_t *>(NEAR + Pc);  // col_ev[Np][Ne] | col_po[Np][Npo]
     uint8_t *COLP = COL + Np * Ne;
     uint8_t *FLG = COLP + Np * Npo;                     // caught_ev[Ne] | enc_ev[Ne] | caught_po[Npo]
@@ -56,6 +64,9 @@
 #endif
 
     for (int k = lane; k < 2 * K; k += 64) SEN[k] = d.sensors[k];
+#if MADRL_WW_BODY_RANGES
+    for (int k = lane; k < Pc; k += 64) RNG[k] = d.sensors[up4(2 * K) + k];
+#endif
     const int rec_dw = TNp > 0 ? (4 * (TNp + TNe + TNpo) + 4 + 3) / 4 * 4 : d.rec_dw;  // <= 4 dwords per lane (NP <= 62)
 
     // ---- software pipeline: next env's record + action row (LIVE: and its counts) are fetched one env ahead
@@ -279,6 +290,11 @@
                     const int iq = sp.iq, kq = sp.kq;
                     const float sxq = SEN[2 * kq], syq = SEN[2 * kq + 1];
                     const float pxq = X[2 * iq], pyq = X[2 * iq + 1];
+#if MADRL_WW_BODY_RANGES
+                    const float srange_q = RNG[iq];  // the range of this lane's pursuer (iq < Np <= Pc, 0 in a lane without a pair)
+#else
+                    const float srange_q = srange;
+#endif
                     const uint64_t reach = pass_reach(NEAR, sp.i_first, sp.i_last);  // wave-uniform: objects in reach of any pursuer of this pass
                     // (a specialised shape fixes the row width, and with it whether the speed features are in the row: 7 K + 2 (+ 1) against 4 K + 2 (+ 1))
                     const bool speed = TNp > 0 ? (TD >= 7 * TK + 2) : (bool)DA.speed_features;
@@ -294,7 +310,7 @@
                         auto visit = [&](int m, float qx, float qy) {
                             // branch-free (bitwise |, selects): no exec-mask round trips in the inner loop; a pursuer does not sense itself
                             float sv;
-                            const bool out = ray_misses(sxq, syq, pxq, pyq, qx, qy, srange, rad2, sv) | ((cls == 3) & (m == iq));
+                            const bool out = ray_misses(sxq, syq, pxq, pyq, qx, qy, srange_q, rad2, sv) | ((cls == 3) & (m == iq));
                             // (the reference sets an excluded ray to +inf and takes the first minimum: an excluded ray is never "better", a kept one
                             // is when it is smaller -- the same minimum and the same first index without materialising the +inf)
                             const bool better = !out & (sv < b);

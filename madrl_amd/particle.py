@@ -92,6 +92,7 @@ class BatchedParticleWorld(AbstractMAEnv):
         dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
         _lib.check(c.create(C.byref(cfg), self._sensors.ctypes.data_as(C.c_void_p), N, dev_index, _lib.ptr(self._state), C.byref(h)))
         self._handle = h
+        self._bind_handle(h)
         if self._max_blocks:
             _lib.check(c.set_launch(h, self._max_blocks))
         if N >= 4096 and not self._crowd and not self.per_env_counts:   # (the crowd and live-count kernels take their shape at run time: there is nothing to specialise)
@@ -115,6 +116,9 @@ class BatchedParticleWorld(AbstractMAEnv):
                 self._live = self._pending.clone()
                 self._counts_key = (N, cap)
             _lib.check(c.set_particle_counts(h, _lib.ptr(self._pending), _lib.ptr(self._live)))
+
+    def _bind_handle(self, h):
+        """what a world binds to every handle it creates, before anything else is (called by setup() itself)"""
 
     def _hint_fast_path(self, D):
         """a world with a list of specialised shapes says here that a large batch runs on the generic kernel (called by setup() itself)"""

@@ -63,7 +63,12 @@ class BatchedMAWaterWorld(BatchedParticleWorld):
         crowd kernel does.  Which to choose: "wave" whenever the capacity fits 62 particles and 32 pursuers (one wavefront per env instead
         of a workgroup of four; DESIGN.md 4.4c has the timing); crowd=True, per_env_counts=True beyond that.  The live one-wavefront kernel
         is the generic instantiation -- there is no compile-time capacity -- and has no fused StandardizedEnv (the wrapper runs its epilogue
-        kernels)."""
+        kernels).
+        sensor_range: a float or, as in the reference (waterworld.py:96, :109), one value per pursuer.  An array whose elements differ
+        runs on the ranged kernels (madrl_waterworld_set_sensor_ranges; crowd=True or not): observation row i is bit for bit row i of a
+        batch with sensor_range=sensor_range[i], everything else is unchanged.  Such a batch runs the generic one-wavefront kernel whatever
+        its shape, has no fused StandardizedEnv (the wrapper runs its epilogue kernels) and does not combine with per_env_counts
+        (ValueError).  An all-equal array is the float."""
         # like the reference, unknown kwargs are swallowed (waterworld.py:81,:483 passes obs_loc=None)
         self._ctor = dict(locals())
         self._ctor.pop("self"); self._ctor.pop("kwargs"); self._ctor.pop("__class__", None)
@@ -72,6 +77,12 @@ class BatchedMAWaterWorld(BatchedParticleWorld):
         self.radius, self.obstacle_radius, self.obstacle_loc = radius, obstacle_radius, obstacle_loc
         self.ev_speed, self.poison_speed, self.n_sensors = ev_speed, poison_speed, n_sensors
         self.sensor_range = np.ones(n_pursuers) * sensor_range
+        if self._ranged:   # checked here, before a device is touched
+            if not (np.isfinite(self.sensor_range).all() and (self.sensor_range > 0).all()):
+                raise ValueError("sensor_range: every element of a per-pursuer array must be finite and > 0 (got %r)" % (self.sensor_range,))
+            if self.per_env_counts:
+                raise ValueError("per-pursuer sensor ranges do not combine with per_env_counts: the live-count kernels take one range "
+                                 "(pass a float, or an array of equal elements)")
         self.action_scale, self.poison_reward, self.food_reward = action_scale, poison_reward, food_reward
         self.control_penalty, self.encounter_reward = control_penalty, encounter_reward
         self.n_obstacles = 1
@@ -100,11 +111,36 @@ class BatchedMAWaterWorld(BatchedParticleWorld):
         c.seed, c.env_id_base = self._seed_value, self.env_id_base
         return c
 
+    @property
+    def _ranged(self):
+        """the elements of sensor_range differ: the batch runs on the ranged kernels (read from the live attribute, like every parameter)"""
+        r = np.asarray(self.sensor_range, dtype=np.float64).reshape(-1)
+        return bool((r != r[0]).any())
+
+    def _bind_handle(self, h):
+        if self._ranged:   # every handle the batch creates: the constructor's, seed()'s, set_param_values()'s, an unpickled copy's
+            r = np.ascontiguousarray(self.sensor_range, dtype=np.float64).reshape(-1)
+            if r.shape != (int(self.n_pursuers),):
+                raise ValueError("sensor_range has %d elements for %d pursuers" % (r.size, int(self.n_pursuers)))
+            _lib.check(_lib.lib().madrl_waterworld_set_sensor_ranges(h, r.ctypes.data_as(C.c_void_p)))
+
+    @property
+    def fused_standardize(self):
+        return not self._ranged and super().fused_standardize
+
+    def bind_standardize(self, *args, **kwargs):
+        if self._ranged:
+            raise _lib.MadrlError("bind_standardize: the ranged kernel (per-pursuer sensor_range) has no fused StandardizedEnv; "
+                                  "StandardizedEnv(env) or StandardizedEnv(env, fused=False) runs the epilogue kernels over it")
+        return super().bind_standardize(*args, **kwargs)
+
     _hinted = set()
 
     def _hint_fast_path(self, D):
         """A large batch of a shape that is not in csrc/waterworld_specializations.def runs on the generic instantiation (dynamic LDS layout,
         run-time loop bounds: about half the speed): say once per shape how to give it its own kernel.  Results are identical either way."""
+        if self._ranged:   # the ranged kernel takes its shape at run time: there is nothing to specialise
+            return
         from . import build as _build
         shape = (int(self.n_pursuers), int(self.n_evaders), int(self.n_poison), int(self.n_sensors), int(D))
         if shape in BatchedMAWaterWorld._hinted or _build.waterworld_is_specialised(*shape):

@@ -4,6 +4,7 @@
     python scripts/ww_crowd_time.py --rows shapes,cpu    # some of: shapes, cpu, wave, nw8, live
     python scripts/ww_crowd_time.py --live               # the table of DESIGN 4.4b: the `live` row alone
     python scripts/ww_crowd_time.py --rows livewave      # the table of DESIGN 4.4c (not in the default set)
+    python scripts/ww_crowd_time.py --rows ranges        # the table of DESIGN 4.4d (not in the default set)
 
 Rows
   shapes  20/60/40, 33/100/100 and 128/512/383 with 30 sensors, at 4 096 envs and at the largest batch whose observations fit 16 GB:
@@ -19,6 +20,10 @@ Rows
           5/10/10 (30 sensors) and 12/25/25 (16 sensors), 32 768 envs: the fixed-shape one-wavefront kernel (specialised at the first
           capacity, generic at the second), the one-wavefront live kernel and the crowd live kernel with every env at the capacity, and
           both live kernels on the same spread of triples -- the five alternating, three processes each
+  ranges  per-pursuer sensor ranges (madrl_waterworld_set_sensor_ranges) against the fixed-shape kernel of the same handle kind: one-wavefront
+          at 12/25/25 (16 sensors; generic) and 5/10/10 (30 sensors; specialised), 32 768 envs, and crowd at 20/60/40, 4 096 envs.  Three
+          variants alternating, three processes each: fixed shape, the ranged entry with every range at 0.2 (the same ray tests and the same
+          cull as the fixed kernel: the cost of the entry itself), and with the ranges cycling over 0.1 / 0.2 / 0.3 (the cull runs on 0.3)
 
 Steady state with auto_reset (max_steps 500), after an untimed warm-up; device events around the launches alone.  One measurement per
 process (`--one ...`, what the parent starts), one process at a time.
@@ -48,14 +53,20 @@ def largest_batch(shape):
 
 
 def one(shape, N, crowd, live=0):
-    """one measurement in this process -> a JSON line.  live: 0 fixed shape, 1 per-env counts at the capacity, 2 a spread of counts"""
+    """one measurement in this process -> a JSON line.  live: 0 fixed shape, 1 per-env counts at the capacity, 2 a spread of counts,
+    3 per-pursuer sensor ranges all at 0.2, 4 ranges cycling over 0.1 / 0.2 / 0.3"""
+    import ctypes
+    import numpy as np
     import torch
     from madrl_amd import _lib
     from madrl_amd.waterworld import BatchedMAWaterWorld
     Np, Ne, Npo, K = SHAPES[shape]
     dev = torch.device("cuda:0")
     env = BatchedMAWaterWorld(Np, Ne, n_poison=Npo, n_sensors=K, n_envs=N, device=dev, seed=0, max_steps=500, auto_reset=True, crowd=bool(crowd),
-                              per_env_counts=(True if crowd else "wave") if live else False)
+                              per_env_counts=(True if crowd else "wave") if live in (1, 2) else False)
+    if live >= 3:   # through the C function: it takes equal values too, which the constructor would hand to the uniform kernel
+        r = np.full(Np, 0.2) if live == 3 else np.asarray([(0.1, 0.2, 0.3)[i % 3] for i in range(Np)])
+        _lib.check(_lib.lib().madrl_waterworld_set_sensor_ranges(env._handle, r.ctypes.data_as(ctypes.c_void_p)))
     if live == 2:
         g = torch.Generator().manual_seed(0)
         env.set_particle_counts(*[torch.randint(1, c + 1, (N,), generator=g) for c in (Np, Ne, Npo)])
@@ -77,7 +88,7 @@ def one(shape, N, crowd, live=0):
     us = timed(10)
     steps = int(min(300, max(20, 1.0e6 / us)))   # about a second of launches
     us = timed(steps)
-    print(json.dumps(dict(shape=shape, n_envs=N, kernel=env.kernel_kind + ("", "-live", "-live-spread")[live], us_per_launch=us, env_steps_per_s=N / us * 1e6,
+    print(json.dumps(dict(shape=shape, n_envs=N, kernel=env.kernel_kind + ("", "-live", "-live-spread", "-ranges", "-ranges-spread")[live], us_per_launch=us, env_steps_per_s=N / us * 1e6,
                           ray_tests_per_s=N * Np * K * (Np + Ne + Npo) / us * 1e6, steps=steps)), flush=True)
 
 
@@ -114,7 +125,7 @@ def child(shape, N, crowd, lib=None, rs=None):
     lo, hi = min(us), max(us)
     r = rs[0]
     scale = lambda key, u: r[key] * r["us_per_launch"] / u
-    print("%-12s %-5s N=%8d  %10.1f - %10.1f us/launch  %.3e - %.3e env-steps/s  %.3e - %.3e ray tests/s%s" % (
+    print("%-12s %-19s N=%8d  %10.1f - %10.1f us/launch  %.3e - %.3e env-steps/s  %.3e - %.3e ray tests/s%s" % (
         shape, r["kernel"], N, lo, hi, scale("env_steps_per_s", hi), scale("env_steps_per_s", lo), scale("ray_tests_per_s", hi),
         scale("ray_tests_per_s", lo), "  [%s]" % os.path.basename(lib) if lib else ""), flush=True)
     return lo, hi
@@ -166,6 +177,15 @@ def main():
                   "%.2f - %.2f on the spread; gate (one-wavefront live faster than crowd live beyond the spread of the repetitions): %s" % (
                       s, w0 / f1, w1 / f0, c0 / w1, c1 / w0, cs0 / ws1, cs1 / ws0, "holds" if w1 < c0 and ws1 < cs0 else "does NOT hold"),
                   flush=True)
+    if "ranges" in rows:
+        for s, N, crowd in (("12/25/25", 32768, False), ("5/10/10", 32768, False), ("20/60/40", 4096, True)):
+            runs = [[], [], []]
+            for _ in range(3):   # fixed, ranged at one value, ranged spread: alternating
+                for r, live in zip(runs, (0, 3, 4)):
+                    r.append(measure(s, N, crowd, live=live))
+            (f0, f1), (r0, r1), (s0, s1) = [child(s, N, crowd, rs=r) for r in runs]
+            print("%s at %d envs (%s): ranged at one value / fixed = %.3f - %.3f, ranged spread / fixed = %.3f - %.3f" % (
+                s, N, "crowd" if crowd else "one wavefront", r0 / f1, r1 / f0, s0 / f1, s1 / f0), flush=True)
 
 
 if __name__ == "__main__":

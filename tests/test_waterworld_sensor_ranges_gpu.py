@@ -1,0 +1,360 @@
+"""GPU tests (-m gpu) of per-pursuer sensor ranges in Waterworld (`sensor_range=array`: madrl_waterworld_set_sensor_ranges,
+waterworld_kernel_ranges in csrc/waterworld.hip and ww_crowd_kernel_ranges in csrc/waterworld_crowd.hip).  The definition of right: the
+range enters the ray test alone, so state, rewards, done and info are those of any uniform batch, and observation row i is row i of a
+uniform batch at sensor_range = ranges[i] -- bit for bit, free-running, nothing copied across.  The uniform kernels are pinned to the
+float32 oracle and to the reference elsewhere (test_waterworld_gpu.py, test_waterworld_crowd_gpu.py); the recordings of the unmodified
+reference with an array sensor_range (tests/golden/wwrange_*.npz) are replayed teacher-forced on top."""
+import ctypes as C
+import functools
+import os
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+TOL = 1e-5   # TOL of tests/test_waterworld_gpu.py
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = lambda name: os.path.join(ROOT, "tests", "golden", "wwrange_%s.npz" % name)
+FAST = dict(radius=0.03, ev_speed=0.03, action_scale=0.03)   # moving fast enough for catches inside short episodes
+
+
+def _mk(n_envs, crowd=False, **kw):
+    from madrl_amd.waterworld import BatchedMAWaterWorld
+    env = BatchedMAWaterWorld(n_envs=n_envs, device=DEV, **(dict(kw, crowd=True) if crowd else kw))
+    assert env.kernel_kind == ("crowd" if crowd else "wave")
+    r = np.asarray(kw.get("sensor_range", 0.2), dtype=np.float64).reshape(-1)
+    assert env._ranged == bool((r != r[0]).any()) and np.array_equal(env.sensor_range, np.ones(env.n_pursuers) * kw.get("sensor_range", 0.2))
+    return env
+
+
+def _bits(t):
+    t = t.contiguous()
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+def _same_bits(a, b):
+    return torch.equal(_bits(a), _bits(b))
+
+
+def _cycle(values, n):
+    return np.asarray([values[i % len(values)] for i in range(n)], dtype=np.float64)
+
+
+# ------------------------------------------------------------------ the reference's recordings, teacher-forced
+@pytest.mark.parametrize("name,crowd", [("4_8_6_k12", False), ("4_8_6_k12", True), ("33_12_8_k8", True)],
+                         ids=["4_8_6_k12-wave", "4_8_6_k12-crowd", "33_12_8_k8-crowd"])
+def test_hip_matches_reference_recording_teacher_forced(name, crowd):
+    """the protocol of test_waterworld_gpu.py::test_hip_matches_reference_golden_teacher_forced: all recorded steps are one batch"""
+    from oracle import waterworld as ww
+    g = np.load(GOLD(name))
+    T, ranges = len(g["pre_t"]), g["cfg_sensor_ranges"]
+    env = _mk(T, crowd=crowd, **dict(ww.kwargs_from_golden(g), sensor_range=ranges))
+    assert env._ranged and env.obs_dim == g["obs"].shape[-1]
+    env.set_state(pos=g["pre_pos"], vel=g["pre_vel"], obst=g["obst"], t=g["pre_t"])
+    obs, rew, done, info = env.step(g["act"], respawn=g["resp"])
+    st = {k: v.cpu().numpy() for k, v in env.get_state().items()}
+    obs, rew, done = obs.cpu().numpy(), rew.cpu().numpy(), done.cpu().numpy()
+    live = g["is_reset_step"] == 0
+    errs = dict(pos=np.abs(st["pos"] - g["post_pos"]).max(), vel=np.abs(st["vel"] - g["post_vel"]).max(), obs=np.abs(obs - g["obs"]).max(),
+                rew=np.abs(rew[live] - g["rew"][live]).max())
+    per_row = np.abs(obs - g["obs"]).max(axis=(0, 2))
+    print("%s %s: %s; worst row error %.3g" % (name, env.kernel_kind, {k: "%.3g" % v for k, v in errs.items()}, per_row.max()))
+    assert np.array_equal(st["t"], g["post_t"]) and np.array_equal(done[live], g["done"][live].astype(bool))
+    assert np.array_equal(info["evcatches"].cpu().numpy()[live], g["evc"][live].astype(np.int64))
+    assert np.array_equal(info["pocatches"].cpu().numpy()[live], g["poc"][live].astype(np.int64))
+    assert max(errs.values()) <= TOL, errs
+
+
+def test_n1_dropin_with_a_range_array_reproduces_the_recordings_opening_steps():
+    """MAWaterWorld(sensor_range=array), the reference's own call: the first eight recorded steps after the reset, each from its recorded
+    pre-state (observations and rewards are formed before a caught particle respawns: no respawn outcome is needed)"""
+    from madrl_amd.waterworld import MAWaterWorld
+    from oracle import waterworld as ww
+    g = np.load(GOLD("4_8_6_k12"))
+    one = MAWaterWorld(device=DEV, **dict(ww.kwargs_from_golden(g), sensor_range=g["cfg_sensor_ranges"]))
+    assert one._env.kernel_kind == "wave" and one._env._ranged and len(one.reset()) == 4
+    for t in range(1, 9):
+        assert not g["is_reset_step"][t]
+        one._env.set_state(pos=g["pre_pos"][t][None], vel=g["pre_vel"][t][None], obst=g["obst"][t][None], t=g["pre_t"][t:t + 1])
+        obs, rew, done, info = one.step(g["act"][t])
+        assert isinstance(obs, list) and len(obs) == 4 and obs[0].dtype == np.float64 and isinstance(done, bool)
+        assert np.abs(np.stack(obs) - g["obs"][t]).max() <= TOL and np.abs(rew - g["rew"][t]).max() <= TOL, t
+        assert done == bool(g["done"][t]) and info == dict(evcatches=int(g["evc"][t]), pocatches=int(g["poc"][t]))
+
+
+# ------------------------------------------------------------------ row identity, free-running, bit for bit
+SHAPES = {
+    # the twins run the specialised instantiation (csrc/waterworld_specializations.def), the ranged batch leaves it
+    "5_10_10_k30": (dict(n_pursuers=5, n_evaders=10, n_poison=10, n_coop=2, n_sensors=30, **FAST), np.array([0.2, 0.1, 0.35, 0.2, 0.5])),
+    # 62 particles, 32 pursuers: 16 pursuers per pass of 64 (pursuer, sensor) pairs
+    "32_15_15_k4": (dict(n_pursuers=32, n_evaders=15, n_poison=15, n_coop=2, n_sensors=4, **FAST), _cycle((0.3, 0.1, 0.2), 32)),
+    # several passes per pursuer
+    "3_4_4_k200": (dict(n_pursuers=3, n_evaders=4, n_poison=4, n_coop=1, n_sensors=200, **FAST), np.array([0.5, 0.15, 0.3])),
+    # 84 pairs: a pass of 64 starts and ends inside a pursuer; the other row layout, random obstacle, global reward
+    "7_9_9_k12": (dict(n_pursuers=7, n_evaders=9, n_poison=9, n_coop=2, n_sensors=12, obstacle_loc=None, reward_mech="global",
+                       speed_features=False, addid=False, **FAST), _cycle((0.25, 0.1, 0.4), 7)),
+    # more than 32 pursuers: the crowd kernel alone
+    "33_12_8_k8": (dict(n_pursuers=33, n_evaders=12, n_poison=8, n_coop=2, n_sensors=8, **FAST), _cycle((0.15, 0.45, 0.3), 33)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _row_identity(shape, crowd, N=13, T=60, H=20, max_blocks=3):
+    """one ranged batch and one uniform twin per distinct range, same seed and env_id_base, the same random actions: at every step the
+    state, rewards, done and info of all batches are equal and row i of the ranged batch is row i of the twin at ranges[i].
+    -> the ranged batch's observations of every step (on the host), for the comparison of the two kernel families"""
+    kw, ranges = SHAPES[shape]
+    common = dict(kw, seed=41, env_id_base=700, max_steps=H, auto_reset=True, max_blocks=max_blocks)
+    ranged = _mk(N, crowd=crowd, sensor_range=ranges, **common)
+    values = sorted(set(ranges.tolist()))
+    twins = [_mk(N, crowd=crowd, sensor_range=v, **common) for v in values]
+    assert ranged._ranged and len(values) >= 3 and not any(t._ranged for t in twins)
+    rows = [torch.as_tensor(np.flatnonzero(ranges == v), device=DEV) for v in values]
+    others = torch.as_tensor(np.flatnonzero(ranges != ranges[0]), device=DEV)
+
+    def check(obs, tobs, tag):
+        st = ranged.get_state()
+        for v, tw, o, idx in zip(values, twins, tobs, rows):
+            for k, s in tw.get_state().items():
+                assert _same_bits(st[k], s), "state %s, twin %g, %s" % (k, v, tag)
+            assert _same_bits(obs[:, idx], o[:, idx]), "rows of range %g, %s: %g" % (v, tag, (obs[:, idx] - o[:, idx]).abs().max())
+        return int((_bits(obs[:, others]) != _bits(tobs[values.index(ranges[0])][:, others])).any(dim=-1).sum())
+
+    differ = check(ranged.reset(), [t.reset() for t in twins], "reset")
+    g = torch.Generator(device="cpu").manual_seed(6)
+    out, catches, resets = [], 0, 0
+    for t in range(T):
+        act = (torch.rand((N, kw["n_pursuers"], 2), generator=g) * 2 - 1).to(DEV)
+        obs, rew, done, info = ranged.step(act)
+        tobs = []
+        for v, tw in zip(values, twins):
+            o, r, d, i = tw.step(act)
+            assert _same_bits(rew, r) and torch.equal(done, d), "rewards / done, twin %g, step %d" % (v, t)
+            assert torch.equal(info["evcatches"], i["evcatches"]) and torch.equal(info["pocatches"], i["pocatches"]), "info, twin %g, step %d" % (v, t)
+            tobs.append(o)
+        differ += check(obs, tobs, "step %d" % t)
+        catches += int(info["evcatches"].sum() + info["pocatches"].sum()); resets += int(done.sum())
+        out.append(obs.cpu())
+    print("%s %s: %d catches, %d time-limit resets; %d of %d rows of the other ranges differ from the twin at ranges[0]"
+          % (shape, ranged.kernel_kind, catches, resets, differ, (T + 1) * N * len(others)))
+    assert catches > 0 and resets >= 2 * N
+    assert differ > 0, "the run does not tell the ranges apart"   # (what the batch computed before: every pursuer at ranges[0])
+    return out
+
+
+@pytest.mark.parametrize("shape", ["5_10_10_k30", "32_15_15_k4", "3_4_4_k200", "7_9_9_k12"])
+def test_rows_are_those_of_uniform_twins_one_wavefront(shape):
+    from madrl_amd import build as B
+    kw, _ranges = SHAPES[shape]
+    if shape == "5_10_10_k30":   # the twins' shape has its own kernel; a ranged batch runs the generic body whatever the shape
+        assert B.waterworld_is_specialised(kw["n_pursuers"], kw["n_evaders"], kw["n_poison"], kw["n_sensors"], 7 * kw["n_sensors"] + 3)
+    assert len(_row_identity(shape, False)) == 60
+
+
+@pytest.mark.parametrize("shape", ["7_9_9_k12", "33_12_8_k8"])
+def test_rows_are_those_of_uniform_twins_crowd(shape):
+    crowd = _row_identity(shape, True)
+    assert len(crowd) == 60
+    if shape == "7_9_9_k12":   # a shape both families take: the two ranged kernels agree in every bit
+        wave = _row_identity(shape, False)
+        assert all(_same_bits(a, b) for a, b in zip(wave, crowd))
+
+
+# ------------------------------------------------------------------ switching
+def _run_same(a, b, N, Np, T, seed=3):
+    assert _same_bits(a.reset(), b.reset())
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    for t in range(T):
+        act = (torch.rand((N, Np, 2), generator=g) * 2 - 1).to(DEV)
+        oa, ra, da, ia = a.step(act)
+        ob, rb, db, ib = b.step(act)
+        assert _same_bits(oa, ob) and _same_bits(ra, rb) and torch.equal(da, db), "step %d" % t
+        assert torch.equal(ia["evcatches"], ib["evcatches"]) and torch.equal(ia["pocatches"], ib["pocatches"]), "info step %d" % t
+        sa, sb = a.get_state(), b.get_state()
+        assert all(_same_bits(sa[k], sb[k]) for k in sb), "state step %d" % t
+
+
+def test_an_all_equal_array_is_the_float():
+    from madrl_amd import build as B
+    kw = dict(SHAPES["5_10_10_k30"][0], seed=8, env_id_base=3, max_steps=9, auto_reset=True)
+    a, b = _mk(17, sensor_range=np.full(5, 0.2), **kw), _mk(17, sensor_range=0.2, **kw)
+    assert not a._ranged and a.fused_standardize and B.waterworld_is_specialised(5, 10, 10, 30, 213)   # today's path: the specialised kernel
+    st = a.bind_standardize(enable_obsnorm=True)   # ... and the fused StandardizedEnv binds
+    assert st["obs_out"].shape == (17, 5, 213)
+    a.unbind_standardize()
+    _run_same(a, b, 17, 5, 20)
+
+
+@pytest.mark.parametrize("crowd", [False, True], ids=["wave", "crowd"])
+def test_null_returns_the_handle_to_the_uniform_range(crowd):
+    from madrl_amd import _lib
+    L = _lib.lib()
+    kw, ranges = SHAPES["5_10_10_k30"]
+    kw = dict(kw, seed=8, env_id_base=3, max_steps=9, auto_reset=True)
+    N = 11
+    a, u = _mk(N, crowd=crowd, sensor_range=ranges, **kw), _mk(N, crowd=crowd, sensor_range=float(ranges[0]), **kw)
+    oa, ou = a.reset(), u.reset()
+    g = torch.Generator(device="cpu").manual_seed(9)
+    act = lambda: (torch.rand((N, 5, 2), generator=g) * 2 - 1).to(DEV)
+    differed = 0
+    for t in range(6):
+        x = act()
+        (oa, ra, da, _), (ou, ru, du, _) = a.step(x), u.step(x)
+        assert _same_bits(ra, ru) and torch.equal(da, du) and _same_bits(oa[:, 0], ou[:, 0]) and _same_bits(oa[:, 3], ou[:, 3])
+        differed += int(not _same_bits(oa, ou))
+    assert differed >= 3   # the ranges were in force
+    _lib.check(L.madrl_waterworld_set_sensor_ranges(a._handle, None))
+    for t in range(12):
+        x = act()
+        (oa, ra, da, _), (ou, ru, du, _) = a.step(x), u.step(x)
+        assert _same_bits(oa, ou) and _same_bits(ra, ru) and torch.equal(da, du), "after NULL, step %d" % t
+    assert _same_bits(a.reset(), u.reset())
+    r = np.ascontiguousarray(ranges)   # ... and bound again (the handle's table is reused)
+    _lib.check(L.madrl_waterworld_set_sensor_ranges(a._handle, r.ctypes.data_as(C.c_void_p)))
+    x = act()
+    assert not _same_bits(a.step(x)[0][:, 4], u.step(x)[0][:, 4])
+
+
+# ------------------------------------------------------------------ refusals in C
+@pytest.mark.parametrize("crowd", [False, True], ids=["wave", "crowd"])
+def test_ranges_and_particle_counts_refuse_each_other_in_c(crowd):
+    from madrl_amd import _lib
+    L = _lib.lib()
+    env = _mk(4, crowd=crowd, n_pursuers=3, n_evaders=4, n_poison=5)
+    r = np.array([0.2, 0.1, 0.3])
+    rp = r.ctypes.data_as(C.c_void_p)
+    counts = torch.tensor((3, 4, 5), dtype=torch.int32, device=DEV).repeat(4, 1).contiguous()
+    live = counts.clone()
+    _lib.check(L.madrl_waterworld_set_sensor_ranges(env._handle, rp))                     # ranges first: the counts are refused
+    assert L.madrl_waterworld_set_particle_counts(env._handle, _lib.ptr(counts), _lib.ptr(live)) == -1
+    assert b"set_sensor_ranges" in L.madrl_last_error()
+    _lib.check(L.madrl_waterworld_set_sensor_ranges(env._handle, None))
+    _lib.check(L.madrl_waterworld_set_particle_counts(env._handle, _lib.ptr(counts), _lib.ptr(live)))   # counts first: the ranges are refused
+    assert L.madrl_waterworld_set_sensor_ranges(env._handle, rp) == -1 and b"set_particle_counts" in L.madrl_last_error()
+    _lib.check(L.madrl_waterworld_set_particle_counts(env._handle, None, None))
+    for bad in (np.nan, np.inf, 0.0, -0.2):                                              # values: finite and > 0
+        b = np.array([0.2, bad, 0.3])
+        assert L.madrl_waterworld_set_sensor_ranges(env._handle, b.ctypes.data_as(C.c_void_p)) == -1 and b"finite and > 0" in L.madrl_last_error()
+    _lib.check(L.madrl_waterworld_set_sensor_ranges(env._handle, rp))
+    assert torch.isfinite(env.reset()).all()
+
+
+def test_ranges_and_a_fused_standardize_refuse_each_other_in_c():
+    from madrl_amd import _lib
+    L = _lib.lib()
+    env = _mk(4, n_pursuers=3, n_evaders=4, n_poison=5)
+    r = np.array([0.2, 0.1, 0.3])
+    rp = r.ctypes.data_as(C.c_void_p)
+    st = env.bind_standardize(enable_obsnorm=True)                                        # a fused StandardizedEnv first: the ranges are refused
+    assert L.madrl_waterworld_set_sensor_ranges(env._handle, rp) == -1 and b"set_standardize" in L.madrl_last_error()
+    env.unbind_standardize()
+    _lib.check(L.madrl_waterworld_set_sensor_ranges(env._handle, rp))                     # ranges first: the fused StandardizedEnv is refused
+    a = _lib.StandardizeArgs()
+    a.struct_size = C.sizeof(_lib.StandardizeArgs)
+    a.enable_obsnorm, a.obs_alpha, a.rew_alpha, a.eps, a.scale_reward = 1, 0.001, 0.001, 1e-8, 1.0
+    for k, v in st.items():
+        setattr(a, k, v.data_ptr())
+    assert L.madrl_waterworld_set_standardize(env._handle, C.byref(a)) == -1 and b"set_sensor_ranges" in L.madrl_last_error()
+    _lib.check(L.madrl_waterworld_set_standardize(env._handle, None))                     # unbinding is always allowed
+    _lib.check(L.madrl_waterworld_set_sensor_ranges(env._handle, None))
+    _lib.check(L.madrl_waterworld_set_standardize(env._handle, C.byref(a)))
+    _lib.check(L.madrl_waterworld_set_standardize(env._handle, None))
+
+
+# ------------------------------------------------------------------ handle lifecycle and API
+RANGES5 = SHAPES["5_10_10_k30"][1]
+
+
+def _ranged5(N=8, crowd=False, **kw):
+    return _mk(N, crowd=crowd, sensor_range=RANGES5, **dict(SHAPES["5_10_10_k30"][0], max_steps=6, auto_reset=True, **kw))
+
+
+@pytest.mark.parametrize("crowd", [False, True], ids=["wave", "crowd"])
+def test_ranges_survive_seed_and_a_pickle_round_trip(crowd):
+    import warnings
+    env = _ranged5(crowd=crowd, seed=4)
+    env.seed(23)                                        # a new handle (over the same state buffer: nothing has run on it yet, every tick is 0)
+    fresh = _ranged5(crowd=crowd, seed=23)
+    assert env._ranged and env.kernel_kind == fresh.kernel_kind
+    uniform = _mk(8, crowd=crowd, sensor_range=float(RANGES5[0]), seed=23, **dict(SHAPES["5_10_10_k30"][0], max_steps=6, auto_reset=True))
+    first = env.reset()
+    assert _same_bits(first[:, 0], uniform.reset()[:, 0]) and not _same_bits(first, uniform._obs)   # the ranges are in force on the new handle
+    assert _same_bits(first, fresh.reset())             # (both have been reset once: the ticks stay in step)
+    _run_same(env, fresh, 8, 5, 8)
+    again = pickle.loads(pickle.dumps(env))             # the constructor arguments: the array travels
+    assert again._ranged and np.array_equal(again.sensor_range, RANGES5) and again.kernel_kind == env.kernel_kind
+    _run_same(again, _ranged5(crowd=crowd, seed=4), 8, 5, 8)   # (a pickle restores the constructor's seed)
+    if not crowd:
+        with warnings.catch_warnings(record=True) as caught:   # a large ranged batch: no hint at a specialised kernel, there is none
+            warnings.simplefilter("always")
+            big = _mk(4096, sensor_range=np.array([0.2, 0.3, 0.1]), n_pursuers=3, n_evaders=6, n_poison=7, n_sensors=9)
+        assert big._ranged and not [w for w in caught if "generic kernel" in str(w.message)]
+        assert torch.isfinite(big.reset()).all()
+
+
+def test_masked_reset_leaves_the_other_envs_rows_alone():
+    env = _ranged5(N=9, seed=5)
+    env.reset()
+    for _ in range(3):
+        obs, _r, _d, _i = env.step(torch.rand((9, 5, 2), device=DEV) * 2 - 1)
+    before, t0 = obs.clone(), env.get_state()["t"].clone()
+    m = torch.arange(9, device=DEV) % 3 == 1
+    after = env.reset(mask=m)
+    t1 = env.get_state()["t"]
+    assert _same_bits(after[~m], before[~m]) and torch.equal(t1[~m], t0[~m])
+    assert (t1[m] == 1).all() and not _same_bits(after[m], before[m])
+
+
+def test_obs_out_leaves_no_nan_in_an_uninitialised_destination():
+    for crowd in (False, True):
+        env = _ranged5(crowd=crowd, seed=6)
+        env.reset()
+        dst = torch.empty(8 * 5 * env.obs_dim, device=DEV).fill_(float("nan"))
+        obs, _rew, _done, _info = env.step(torch.rand((8, 5, 2), device=DEV) * 2 - 1, obs_out=dst)
+        assert obs.data_ptr() == dst.data_ptr() and not torch.isnan(dst).any()
+
+
+def test_standardized_env_runs_its_epilogue_kernels():
+    from madrl_amd import _lib
+    from madrl_amd.wrappers import StandardizedEnv
+    env = _ranged5(seed=7)
+    assert env.fused_standardize is False
+    with pytest.raises(_lib.MadrlError, match="no fused StandardizedEnv"):
+        env.bind_standardize()
+    kws = dict(scale_reward=2.0, enable_obsnorm=True, enable_rewnorm=True)
+    auto, unfused = StandardizedEnv(env, **kws), StandardizedEnv(_ranged5(seed=7), fused=False, **kws)
+    assert not auto._fused and not unfused._fused
+    with pytest.raises(ValueError, match="fused=True"):
+        StandardizedEnv(_ranged5(seed=7), fused=True, **kws)
+    assert _same_bits(auto.reset(), unfused.reset())
+    g = torch.Generator(device="cpu").manual_seed(2)
+    for t in range(8):
+        a = (torch.rand((8, 5, 2), generator=g) * 2 - 1).to(DEV)
+        o1, r1, d1, _ = auto.step(a)
+        o2, r2, d2, _ = unfused.step(a)
+        assert _same_bits(o1, o2) and _same_bits(r1, r2) and torch.equal(d1, d2), t
+    assert torch.isfinite(o1).all() and torch.isfinite(r1).all()
+
+
+def test_rollout_collector_over_a_ranged_batch_equals_stepping_by_hand():
+    from madrl_amd.heuristics import WaterworldHeuristicPolicy
+    from madrl_amd.rollout import RolloutCollector
+    H = 8
+    col = RolloutCollector(_ranged5(seed=9), WaterworldHeuristicPolicy(), horizon=H, store_observations=True)
+    env, pol = _ranged5(seed=9), WaterworldHeuristicPolicy()
+    obs = env.reset()
+    for it in range(2):
+        traj = col.collect()
+        torch.cuda.synchronize()
+        for t in range(H):
+            assert _same_bits(traj.observations[t], obs), (it, t)
+            act = pol(obs)
+            act = act[0] if isinstance(act, tuple) else act
+            assert _same_bits(traj.actions[t], act), (it, t)
+            obs, rew, done, _info = env.step(act)
+            assert _same_bits(traj.rewards[t], rew) and torch.equal(traj.dones[t] != 0, done), (it, t)
+        assert _same_bits(traj.last_observation, obs), it
+    assert not torch.isnan(traj.observations).any() and int((traj.dones != 0).sum()) >= 8
