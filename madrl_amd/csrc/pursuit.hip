@@ -17,51 +17,29 @@
 //   observations ............. pursuit_evade.py:418-461 (stale out-of-map cells kept: the
 //                              obs buffer is IN/OUT and those cells are simply not stored)
 //   reset .................... pursuit_evade.py:173-207, utils/agent_utils.py:12-47
+//
+// Host side: the configuration's layout(), PursuitDev and the host-built tables (both formats, and the rules that make a configuration
+// eligible for its fast line) are pure functions in pursuit_tables.hpp; this file holds the handle, the dispatch tables and the one launch().
 #include "common.hpp"
+#include "pursuit_tables.hpp"
 #include "pursuit_wave.hpp"
 #include "pursuit_group.hpp"
 #include "pursuit_crowd.hpp"
 
+#include <memory>
 #include <new>
 #include <stdlib.h>
 #include <string.h>
-#include <vector>
+#include <type_traits>
 
 namespace {
 
 using namespace madrl;
 
-// slot-code kinds (one code per element of an agent's observation row, built on the host)
-enum : uint32_t { K_GRID = 0, K_ID = 1, K_FILL = 2, K_SKIP = 3 };
-
-constexpr uint32_t PAD_MAP = 0xFEu;  // map layer outside the map  -> vtab[0xFE] = 1/layer_norm
-constexpr uint32_t PAD_CNT = 0xFFu;  // count layers outside the map -> "do not store" (Q2)
 constexpr int MAX_CELL_COUNT = 253;  // byte grids: the agents of one layer on ONE cell must stay < PAD_MAP (checked where they are counted)
 constexpr int NOT_HERE = 0xFF;       // position byte of a slot that does not exist (per-env agent counts; no coordinate is 255)
 constexpr int MAX_COUNT = 1023;      // agents per layer.  The authors' largest launch line runs 100 pursuers / 300 evaders
                                      // (runners/old/rllab/pursuit_cnn.sh:1); more than 253 of one kind on one cell raises the overflow bit
-
-struct PursuitDev {
-    int32_t xs, ys, P, E, A, R, D;
-    int32_t pad, GW, GSZ;  // padded grid: width (y extent), bytes per layer (multiple of 16)
-    int32_t n_catch, surround, reward_global, sample_maps, n_maps, max_steps, auto_reset;
-    int32_t max_opponents;  // > 0: random_opponents (pursuit_evade.py:177-181)
-    int32_t train_pursuit;  // 0: the ACTIONS drive the evaders, the pursuers move by their controller (pursuit_evade.py:215-224)
-    int32_t rec_bytes, off_gone, off_term, ngw, ntw;  // state record layout (byte offsets)
-    int32_t map_stride;                               // bytes per map entry in `maps`
-    uint32_t k0, k1, gid_base;
-    float fill32;
-    double catchr, term_pursuit, urgency, cw;
-    int64_t n_envs;
-    const uint8_t *maps;     // per map: padded wall layer [GSZ] then need_to_surround [xs*ys]
-    const uint8_t *cnt_tmpl; // padded count-layer template [GSZ]: 0 inside, 0xFF outside
-    const float *vtab;       // 256 floats: fl32(k / layer_norm), [0xFE] = fl32(1.0 / layer_norm)
-    const uint32_t *codes;   // D slot codes
-    const double *cw_env;     // per-env constraint_window / catchr (curriculum, pursuit_evade.py:264-272) or nullptr: the scalars above
-    const double *catchr_env;
-    uint8_t *state;
-    uint32_t *flags;         // [n_envs] flag words (done_flag_word, common.hpp): in the caller's state buffer, behind the stale-zero masks
-};
 
 struct PursuitIO {
     const uint8_t *mask;       // reset mode
@@ -75,8 +53,7 @@ struct PursuitIO {
     int32_t *removed;
 };
 
-// state record: [u32 tick][u32 t][u32 map_id][u32 spare][u8 xy[2A]][u32 gone[ngw]][u32 term[ntw]]
-constexpr int HDR_BYTES = 16;
+static_assert(SENT == pw::SENT, "pursuit_tables.hpp builds the count template the wave / group kernels read");
 
 // `ovf`: set when the cell already held MAX_CELL_COUNT agents -- its count leaves the byte's usable range (254 / 255 are the padding
 // sentinels, one more would carry into the neighbouring cell).  The env's results are void from there on: sticky word 3 of its
@@ -276,21 +253,21 @@ struct FastEntry;  // one compiled specialisation: a line of the *_specializatio
 }
 
 struct madrl_pursuit {
-    madrl_pursuit_config cfg;
-    PursuitDev dev;
-    int device;
-    int threads;
-    int nt;
-    int64_t max_blocks;
-    size_t lds_bytes;
-    void *tables;  // one device allocation holding maps | cnt_tmpl | vtab | codes
+    madrl_pursuit_config cfg{};
+    PursuitDev dev{};
+    int device = 0;
+    int threads = 0;
+    int nt = 0;
+    int64_t max_blocks = 0;
+    size_t lds_bytes = 0;
+    void *tables = nullptr;  // one device allocation holding maps | cnt_tmpl | vtab | codes
     // the fast path: the compile-time specialised kernel of this shape (find_fast), when there is one and the configuration is eligible
     // for it -- one wavefront per env or a group of them (pursuit_wave.hpp, pursuit_group.hpp: wdev, wtables) or the crowd kernel
     // (pursuit_crowd.hpp: cdev; it shares the generic kernel's tables)
-    const FastEntry *fast;
+    const FastEntry *fast = nullptr;
     const FastEntry *fast_live = nullptr;  // the live-count instantiation of `fast` (pursuit_live_specializations.def), if compiled
-    madrl::pw::WaveDev wdev;
-    madrl::pc::CrowdDev cdev;
+    madrl::pw::WaveDev wdev{};
+    madrl::pc::CrowdDev cdev{};
     void *zmask = nullptr;          // what the fast path remembers about the observation buffer (zmask_len): the stale-zero masks,
                                     // [n_envs][64 * waves] dwords per mask word (pursuit_wave.hpp), or the crowd kernel's one word per env,
                                     // "channel 3 of the env's rows is not known to hold +0.0".  The tail of the caller's state buffer
@@ -299,10 +276,20 @@ struct madrl_pursuit {
                                     // set_state or madrl_pursuit_invalidate_obs resets them to "nothing known"
     uint64_t step_count = 0;  // step launches so far (parity of the walk direction, see launch())
     int walk_mode = 0;        // 0 auto (alternate above ~375 MB per launch), 1 always alternate, 2 always forward; fixed at create
-    void *wtables;
-    int kernel_kind;  // MADRL_KERNEL_AUTO / _GENERIC / _WAVE (requested)
+    void *wtables = nullptr;  // the wave / group kernels' device allocation (build_wave_tables)
+    int kernel_kind = MADRL_KERNEL_AUTO;  // MADRL_KERNEL_AUTO / _GENERIC / _WAVE (requested)
     const int32_t *pending = nullptr;      // per-env agent counts (madrl_pursuit_set_agent_counts): caller-owned int32 [n_envs][2], or off
     hipEvent_t ev_fork = nullptr, ev_done = nullptr;   // madrl_pursuit_step_sharded: made by madrl_pursuit_create on the handle's device, destroyed with the handle
+
+    madrl_pursuit() = default;
+    madrl_pursuit(const madrl_pursuit &) = delete;
+    madrl_pursuit &operator=(const madrl_pursuit &) = delete;
+    ~madrl_pursuit() {   // the one place that frees: madrl_pursuit_destroy, and every error path of madrl_pursuit_create
+        if (tables) (void)hipFree(tables);
+        if (wtables) (void)hipFree(wtables);
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (ev_done) (void)hipEventDestroy(ev_done);
+    }
 };
 
 namespace {
@@ -321,10 +308,8 @@ using CrowdLaunch = void (*)(const pc::CrowdDev &, const pc::CrowdIO &, const in
 
 struct FastEntry {
     ShapeKey key;
-    int nw;  // wavefronts per env: 1 = pursuit_wave_kernel, > 1 = pursuit_group_kernel; the crowd kernel's workgroup
-    int GSZ, D, rec_bytes, off_gone, off_term;  // madrl_pursuit_create holds these against layout() (GSZ: the crowd kernel only)
-    int GW, PAD, X_ID, X_SKIP;  // wave / group: what the table builder of madrl_pursuit_create reads
-    int mwords;      // wave / group: stale-zero mask dwords per lane (1: one bit per float4 slot in each byte, up to 8 slots per lane; the row-loop kernel: NS / 8)
+    WaveGeom g;      // the compiled geometry (pursuit_tables.hpp).  g.nw, wavefronts per env: 1 = pursuit_wave_kernel, > 1 = pursuit_group_kernel; the
+                     // crowd kernel's workgroup.  g.mwords: 1 = one bit per float4 slot in each byte, up to 8 slots per lane; the row-loop kernel: NS / 8
     int mask_bytes;  // per env, of `zmask`
     int resident;    // workgroups of one launch: exactly the resident capacity of the 256 CUs
     WaveLaunch launch_wave;    // the family: one of the two is set
@@ -360,10 +345,11 @@ void group_launch(const pw::WaveDev &d, const pw::WaveIO &io, int mode, int64_t 
 }
 
 // resident: 4 SIMDs of S::OCC wavefronts (the occupancy the kernel's registers are allocated for) on each CU
-template <class S>
-constexpr FastEntry wave_entry(int nw, WaveLaunch launch) {
-    return FastEntry{{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN}, nw, S::GSZ, S::D, S::REC_BYTES, S::OFF_GONE, S::OFF_TERM,
-                     S::GW, S::PAD, S::X_ID, S::X_SKIP, S::MWORDS, 256 * nw * S::MWORDS, 256 * 4 * S::OCC / nw, launch, nullptr};
+template <class S, int NW>
+constexpr FastEntry wave_entry(WaveLaunch launch) {
+    constexpr WaveGeom g{NW, S::GSZ, S::GW, S::PAD, S::X_ID, S::X_SKIP, S::MWORDS, S::D, S::REC_BYTES, S::OFF_GONE, S::OFF_TERM};
+    static_assert(g == wave_geom(S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN, NW), "wave_geom() of pursuit_tables.hpp is not this kernel's geometry");
+    return FastEntry{{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN}, g, 256 * NW * S::MWORDS, 256 * 4 * S::OCC / NW, launch, nullptr};
 }
 
 // resident: what the LDS of a workgroup and 24 wavefronts per CU allow (at most 85 registers per lane; a 16-wavefront workgroup may use
@@ -371,15 +357,15 @@ constexpr FastEntry wave_entry(int nw, WaveLaunch launch) {
 template <class S>
 constexpr FastEntry crowd_entry(CrowdLaunch launch) {
     constexpr int by_lds = 160 * 1024 / (S::LDS_DWORDS * 4), by_waves = 24 / S::NW > 0 ? 24 / S::NW : 1;
-    return FastEntry{{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN}, S::NW, S::GSZ, S::D, S::REC_BYTES, S::OFF_GONE, S::OFF_TERM,
-                     0, 0, 0, 0, 0, 4, 256 * (by_lds < by_waves ? by_lds : by_waves), nullptr, launch};
+    return FastEntry{{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN}, WaveGeom{S::NW, S::GSZ, 0, 0, 0, 0, 0, S::D, S::REC_BYTES, S::OFF_GONE, S::OFF_TERM},
+                     4, 256 * (by_lds < by_waves ? by_lds : by_waves), nullptr, launch};
 }
 
 // The fixed-shape kernels: the X / XG lines, then the XC lines -- a shape that has an X / XG line keeps the kernel of that line.  The
 // *.local.def lists are the lines added on this machine by `python -m madrl_amd.build --pursuit-shape / --pursuit-crowd-shape ...`
 // (git-ignored).
-#define X(XS, YS, NP, NE, R, FL) wave_entry<pw::Shape<XS, YS, NP, NE, R, FL>>(1, wave_launch<pw::Shape<XS, YS, NP, NE, R, FL>>),
-#define XG(XS, YS, NP, NE, R, FL, NW) wave_entry<pw::GShape<XS, YS, NP, NE, R, FL, NW>>(NW, group_launch<pw::GShape<XS, YS, NP, NE, R, FL, NW>>),
+#define X(XS, YS, NP, NE, R, FL) wave_entry<pw::Shape<XS, YS, NP, NE, R, FL>, 1>(wave_launch<pw::Shape<XS, YS, NP, NE, R, FL>>),
+#define XG(XS, YS, NP, NE, R, FL, NW) wave_entry<pw::GShape<XS, YS, NP, NE, R, FL, NW>, NW>(group_launch<pw::GShape<XS, YS, NP, NE, R, FL, NW>>),
 #define XC(XS, YS, NP, NE, R, FL, NW) crowd_entry<pc::CShape<XS, YS, NP, NE, R, FL, NW>>(pc::crowd_launch<pc::CShape<XS, YS, NP, NE, R, FL, NW>>),
 constexpr FastEntry FAST_TABLE[] = {
 #include "pursuit_specializations.def"
@@ -399,8 +385,8 @@ constexpr FastEntry FAST_TABLE[] = {
 // geometry, same tables.  (wave_launch of an LShape: no evader-control instantiations, madrl_pursuit_set_agent_counts refuses
 // control_evaders; the XLG and XLC kernels are compiled in pursuit_live_group.hip and pursuit_live_crowd.hip.)  The .local.def list:
 // `python -m madrl_amd.build --pursuit-live-shape / --pursuit-live-crowd-shape ...`, which appends the fixed line too.
-#define XL(XS, YS, NP, NE, R, FL) wave_entry<pw::LShape<XS, YS, NP, NE, R, FL>>(1, wave_launch<pw::LShape<XS, YS, NP, NE, R, FL>>),
-#define XLG(XS, YS, NP, NE, R, FL, NW) wave_entry<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>(NW, pw::live_group_launch<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>),
+#define XL(XS, YS, NP, NE, R, FL) wave_entry<pw::LShape<XS, YS, NP, NE, R, FL>, 1>(wave_launch<pw::LShape<XS, YS, NP, NE, R, FL>>),
+#define XLG(XS, YS, NP, NE, R, FL, NW) wave_entry<pw::LGShape<XS, YS, NP, NE, R, FL, NW>, NW>(pw::live_group_launch<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>),
 #define XLC(XS, YS, NP, NE, R, FL, NW) crowd_entry<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>(pc::live_crowd_launch<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>),
 constexpr FastEntry LIVE_TABLE[] = {
 #include "pursuit_live_specializations.def"
@@ -447,7 +433,7 @@ constexpr ToEntry TO_TABLE[] = {
 constexpr bool to_lines_have_fixed_lines() {
     for (const ToEntry &t : TO_TABLE) {
         bool found = false;
-        for (const FastEntry &f : FAST_TABLE) found = found || (f.key == t.key && f.crowd() == t.crowd() && f.nw == t.nw);
+        for (const FastEntry &f : FAST_TABLE) found = found || (f.key == t.key && f.crowd() == t.crowd() && f.g.nw == t.nw);
         if (!found) return false;
     }
     return true;
@@ -457,11 +443,11 @@ static_assert(to_lines_have_fixed_lines(), "a line of pursuit_to_specializations
 // the two-buffer kernel that stands on the fast line `f` (live: the per-env-count instantiation)
 const ToEntry *find_to(const FastEntry *f, bool live) {
     for (const ToEntry &t : TO_TABLE)
-        if (f && t.key == f->key && t.crowd() == f->crowd() && t.nw == f->nw && t.live == live) return &t;
+        if (f && t.key == f->key && t.crowd() == f->crowd() && t.nw == f->g.nw && t.live == live) return &t;
     return nullptr;
 }
 
-constexpr bool same_line(const FastEntry &a, const FastEntry &b) { return a.key == b.key && a.crowd() == b.crowd() && a.nw == b.nw; }
+constexpr bool same_line(const FastEntry &a, const FastEntry &b) { return a.key == b.key && a.crowd() == b.crowd() && a.g.nw == b.g.nw; }
 
 // A live line without its fixed line would compile a kernel that no handle can use.
 constexpr bool live_lines_have_fixed_lines(bool crowd) {
@@ -482,7 +468,7 @@ const FastEntry *find_fast(const madrl_pursuit_config *c) {
     if (c->flatten && !c->include_id) return nullptr;
     const ShapeKey k = key_of(c);
     for (const FastEntry &e : FAST_TABLE) {
-        if (c->control_evaders && (e.nw > 1 || e.crowd())) continue;
+        if (c->control_evaders && (e.g.nw > 1 || e.crowd())) continue;
         if (e.key == k) return &e;
     }
     return nullptr;
@@ -520,51 +506,6 @@ int validate(const madrl_pursuit_config *c) {
     return MADRL_OK;
 }
 
-int obs_dim_of(const madrl_pursuit_config *c) {
-    const int R = c->obs_range;
-    return c->flatten ? 3 * R * R + (c->include_id ? 1 : 0) : 4 * R * R;
-}
-
-void layout(const madrl_pursuit_config *c, PursuitDev *d) {
-    memset(d, 0, sizeof(*d));
-    d->xs = c->xs; d->ys = c->ys; d->P = c->n_pursuers; d->E = c->n_evaders; d->A = d->P + d->E;
-    d->R = c->obs_range; d->D = obs_dim_of(c);
-    const int off = (c->obs_range - 1) / 2;
-    d->pad = off > 1 ? off : 1;
-    d->GW = c->ys + 2 * d->pad;
-    d->GSZ = (int)align_up((size_t)(c->xs + 2 * d->pad) * d->GW, 16);
-    d->n_catch = c->n_catch; d->surround = c->surround; d->reward_global = c->reward_global;
-    d->sample_maps = c->sample_maps; d->n_maps = c->n_maps; d->max_steps = c->max_steps;
-    d->auto_reset = c->auto_reset;
-    d->max_opponents = c->max_opponents;
-    d->train_pursuit = !c->control_evaders;
-    d->ngw = (d->E + 31) / 32; if (d->ngw < 1) d->ngw = 1;
-    d->ntw = (d->A + 31) / 32;
-    d->off_gone = (int)align_up(HDR_BYTES + 2 * (size_t)d->A, 4);
-    d->off_term = d->off_gone + 4 * d->ngw;
-    d->rec_bytes = (int)align_up((size_t)d->off_term + 4 * d->ntw, 16);
-    d->map_stride = (int)align_up((size_t)d->GSZ + (size_t)c->xs * c->ys, 16);
-    d->k0 = (uint32_t)c->seed; d->k1 = (uint32_t)(c->seed >> 32);
-    d->gid_base = (uint32_t)c->env_id_base;
-    d->catchr = c->catchr; d->term_pursuit = c->term_pursuit; d->urgency = c->urgency_reward;
-    d->cw = c->constraint_window;
-    d->fill32 = (float)(1.0 / c->layer_norm);  // local_obs[..][0].fill(1.0 / layer_norm), :433
-}
-
-// need_to_surround(x, y), pursuit_evade.py:523-540, tabulated per map cell
-int need_to_surround(const int8_t *map, int xs, int ys, int x, int y) {
-    static const int mx[4] = {-1, 1, 0, 0}, my[4] = {0, 0, 1, -1};
-    int tosur = 4;
-    if (x == 0 || x == xs - 1) tosur -= 1;
-    if (y == 0 || y == ys - 1) tosur -= 1;
-    for (int m = 0; m < 4; ++m) {
-        const int xn = x + mx[m], yn = y + my[m];
-        if (!(0 < xn && xn < xs) || !(0 < yn && yn < ys)) continue;  // sic: row/col 0 skipped
-        if (map[xn * ys + yn] == -1) tosur -= 1;
-    }
-    return tosur;
-}
-
 size_t lds_bytes_for(const PursuitDev &d) {
     size_t b = 1024 + 4 * (size_t)d.GSZ;
     b += 2 * align_up((size_t)d.A, 16);
@@ -577,16 +518,16 @@ size_t lds_bytes_for(const PursuitDev &d) {
     return align_up(b, 16);
 }
 
-template <int NT>
-void launch_nt(const madrl_pursuit *h, const PursuitIO &io, int mode, hipStream_t s) {
-    int64_t blocks = h->dev.n_envs;
-    if (h->max_blocks > 0 && blocks > h->max_blocks) blocks = h->max_blocks;
-    if (h->pending)
-        hipLaunchKernelGGL(pursuit_live_kernel<NT>, dim3((unsigned)blocks), dim3((unsigned)h->threads), h->lds_bytes, s,
-                           h->dev, io, mode, h->pending);
-    else
-        hipLaunchKernelGGL(pursuit_kernel<NT>, dim3((unsigned)blocks), dim3((unsigned)h->threads), h->lds_bytes, s,
-                           h->dev, io, mode);
+// The generic kernels' slots per thread, a template argument NT in 1..8, from the handle's nt: fn(std::integral_constant<int, NT>) is called
+// for NT == nt -- the one place that spells the instantiations out.
+template <int NT = 1, class F>
+int with_nt(int nt, F &&fn) {
+    if constexpr (NT > 8) return fail(MADRL_EINVAL, "internal: nt=%d", nt);
+    else {
+        if (nt != NT) return with_nt<NT + 1>(nt, fn);
+        fn(std::integral_constant<int, NT>{});
+        return MADRL_OK;
+    }
 }
 
 // the fast path this handle can use in its current mode (per-env agent counts: the live-count instantiation)
@@ -605,6 +546,13 @@ IO io_of(const PursuitIO &io) {
     return o;
 }
 
+// the arguments of a step launch (madrl_pursuit_step, _step_to, _step_sharded)
+PursuitIO step_io(const int32_t *actions, const int32_t *inj_eact, float *obs, float *rew, uint8_t *done, int32_t *removed) {
+    PursuitIO io{};
+    io.actions = actions; io.inj_eact = inj_eact; io.obs = obs; io.rew = rew; io.done = done; io.removed = removed;
+    return io;
+}
+
 // the fast path's launch constants as madrl_pursuit_create made them, with the curriculum of this launch
 template <class Dev>
 Dev dev_now(Dev d, const PursuitDev &now) {
@@ -612,22 +560,36 @@ Dev dev_now(Dev d, const PursuitDev &now) {
     return d;
 }
 
-int launch(madrl_pursuit *h, const PursuitIO &io, int mode, void *stream) {
+// the two-buffer fast kernel a step_to of this handle launches, or nullptr: the generic kernel (evader control and shapes without a
+// line in pursuit_to_specializations.def)
+const ToEntry *to_of(const madrl_pursuit *h) {
+    if (!use_wave(h) || !h->dev.train_pursuit) return nullptr;
+    return find_to(h->fast, h->pending != nullptr);
+}
+
+// mode 0: reset, 1: step.  obs_prev == nullptr: in place, io.obs is read and written.  Otherwise madrl_pursuit_step_to: the step's rows go to
+// io.obs and the kept cells come from obs_prev.
+int launch(madrl_pursuit *h, const PursuitIO &io, int mode, const float *obs_prev, void *stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (use_wave(h)) {
+    const ToEntry *t = obs_prev ? to_of(h) : nullptr;
+    if (obs_prev ? t != nullptr : use_wave(h)) {
         const FastEntry *f = fast_of(h);   // (the launcher; the geometry is the fixed line's, h->fast)
         int64_t blocks = h->max_blocks > 0 ? h->max_blocks : h->fast->resident;   // persistent workgroups, as many as are resident
         if (blocks > h->dev.n_envs) blocks = h->dev.n_envs;
-        if (h->zmask_obs != (const void *)io.obs) {  // unknown buffer contents: every cell "not known to be zero"
+        // The masks describe the buffer the kept cells are read from; another one has unknown contents: every cell "not known to be zero".
+        // After this launch they describe the buffer it wrote (two buffers: obs_prev is an unknown buffer from here on).
+        if (h->zmask_obs != (obs_prev ? (const void *)obs_prev : (const void *)io.obs))
             MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0xFF, zmask_len(h->fast, h->dev.n_envs), s));
-            h->zmask_obs = io.obs;
-        }
+        h->zmask_obs = io.obs;
         if (f->crowd()) {
-            f->launch_crowd(dev_now(h->cdev, h->dev), io_of<pc::CrowdIO>(io), h->pending, mode, blocks, s);
+            const pc::CrowdDev cd = dev_now(h->cdev, h->dev);
+            if (t) t->launch_crowd(cd, io_of<pc::CrowdIO>(io), h->pending, obs_prev, blocks, s);
+            else f->launch_crowd(cd, io_of<pc::CrowdIO>(io), h->pending, mode, blocks, s);
         } else {
             pw::WaveIO w = io_of<pw::WaveIO>(io);
-            w.flex = (io.inj_eact != nullptr || h->dev.catchr_env != nullptr) ? 1 : 0;
-            w.control_evaders = h->dev.train_pursuit ? 0 : 1;
+            w.flex = (t || io.inj_eact != nullptr || h->dev.catchr_env != nullptr) ? 1 : 0;
+            w.control_evaders = (t || h->dev.train_pursuit) ? 0 : 1;   // (in place only: to_of)
+            w.obs_prev = obs_prev;
             // Large batches: successive step launches walk the env range in opposite directions, so the rows written last by
             // one step are the first ones touched by the next while they are still in the 256 MB memory-side cache.  Measured
             // (scripts/sweep_wave.py, C2 shape): forward-only holds 7.2e8 env-steps/s up to 73 728 envs and collapses beyond
@@ -640,83 +602,24 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, void *stream) {
                 if (alternate) wd.reverse = (int32_t)(h->step_count++ & 1);
             }
             wd.pending = h->pending;
-            f->launch_wave(wd, w, mode, blocks, s);
+            if (t) t->launch_wave(wd, w, blocks, s);
+            else f->launch_wave(wd, w, mode, blocks, s);
         }
         MADRL_HIP_TRY(hipGetLastError());
         return MADRL_OK;
     }
     h->zmask_obs = nullptr;  // the generic kernel does not maintain the fast path's stale-zero masks
-    switch (h->nt) {
-        case 1: launch_nt<1>(h, io, mode, s); break;
-        case 2: launch_nt<2>(h, io, mode, s); break;
-        case 3: launch_nt<3>(h, io, mode, s); break;
-        case 4: launch_nt<4>(h, io, mode, s); break;
-        case 5: launch_nt<5>(h, io, mode, s); break;
-        case 6: launch_nt<6>(h, io, mode, s); break;
-        case 7: launch_nt<7>(h, io, mode, s); break;
-        case 8: launch_nt<8>(h, io, mode, s); break;
-        default: return fail(MADRL_EINVAL, "internal: nt=%d", h->nt);
-    }
-    MADRL_HIP_TRY(hipGetLastError());
-    return MADRL_OK;
-}
-
-template <int NT>
-void launch_to_nt(const madrl_pursuit *h, const PursuitIO &io, const float *obs_prev, hipStream_t s) {
     int64_t blocks = h->dev.n_envs;
     if (h->max_blocks > 0 && blocks > h->max_blocks) blocks = h->max_blocks;
-    if (h->pending)
-        hipLaunchKernelGGL((pursuit_to_kernel<NT, true>), dim3((unsigned)blocks), dim3((unsigned)h->threads), h->lds_bytes, s,
-                           h->dev, io, h->pending, obs_prev);
-    else
-        hipLaunchKernelGGL((pursuit_to_kernel<NT, false>), dim3((unsigned)blocks), dim3((unsigned)h->threads), h->lds_bytes, s,
-                           h->dev, io, h->pending, obs_prev);
-}
-
-// the two-buffer fast kernel a step_to of this handle launches, or nullptr: the generic kernel (evader control and shapes without a
-// line in pursuit_to_specializations.def)
-const ToEntry *to_of(const madrl_pursuit *h) {
-    if (!use_wave(h) || !h->dev.train_pursuit) return nullptr;
-    return find_to(h->fast, h->pending != nullptr);
-}
-
-// madrl_pursuit_step_to: the step of launch(h, io, 1, ...) with its rows in io.obs and the kept cells from obs_prev
-int launch_to(madrl_pursuit *h, const PursuitIO &io, const float *obs_prev, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (const ToEntry *t = to_of(h)) {
-        int64_t blocks = h->max_blocks > 0 ? h->max_blocks : h->fast->resident;
-        if (blocks > h->dev.n_envs) blocks = h->dev.n_envs;
-        if (h->zmask_obs != (const void *)obs_prev)  // the masks describe the buffer the kept cells are read from
-            MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0xFF, zmask_len(h->fast, h->dev.n_envs), s));
-        h->zmask_obs = io.obs;  // ... and, after this launch, the buffer it wrote; obs_prev is an unknown buffer from here on
-        if (t->crowd()) {
-            t->launch_crowd(dev_now(h->cdev, h->dev), io_of<pc::CrowdIO>(io), h->pending, obs_prev, blocks, s);
-        } else {
-            pw::WaveIO w = io_of<pw::WaveIO>(io);
-            w.flex = 1;
-            w.obs_prev = obs_prev;
-            pw::WaveDev wd = dev_now(h->wdev, h->dev);
-            bool alternate = (double)h->dev.n_envs * (4.0 * h->dev.P * h->dev.D + 2.0 * h->dev.rec_bytes) > 375e6;   // as launch()
-            if (h->walk_mode != 0) alternate = h->walk_mode == 1;
-            if (alternate) wd.reverse = (int32_t)(h->step_count++ & 1);
-            wd.pending = h->pending;
-            t->launch_wave(wd, w, blocks, s);
-        }
-        MADRL_HIP_TRY(hipGetLastError());
-        return MADRL_OK;
-    }
-    h->zmask_obs = nullptr;  // the generic kernel does not maintain the fast path's stale-zero masks
-    switch (h->nt) {
-        case 1: launch_to_nt<1>(h, io, obs_prev, s); break;
-        case 2: launch_to_nt<2>(h, io, obs_prev, s); break;
-        case 3: launch_to_nt<3>(h, io, obs_prev, s); break;
-        case 4: launch_to_nt<4>(h, io, obs_prev, s); break;
-        case 5: launch_to_nt<5>(h, io, obs_prev, s); break;
-        case 6: launch_to_nt<6>(h, io, obs_prev, s); break;
-        case 7: launch_to_nt<7>(h, io, obs_prev, s); break;
-        case 8: launch_to_nt<8>(h, io, obs_prev, s); break;
-        default: return fail(MADRL_EINVAL, "internal: nt=%d", h->nt);
-    }
+    const dim3 grid((unsigned)blocks), block((unsigned)h->threads);
+    const int rc = with_nt(h->nt, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        if (obs_prev && h->pending) hipLaunchKernelGGL((pursuit_to_kernel<NT, true>), grid, block, h->lds_bytes, s, h->dev, io, h->pending, obs_prev);
+        else if (obs_prev) hipLaunchKernelGGL((pursuit_to_kernel<NT, false>), grid, block, h->lds_bytes, s, h->dev, io, h->pending, obs_prev);
+        else if (h->pending) hipLaunchKernelGGL(pursuit_live_kernel<NT>, grid, block, h->lds_bytes, s, h->dev, io, mode, h->pending);
+        else hipLaunchKernelGGL(pursuit_kernel<NT>, grid, block, h->lds_bytes, s, h->dev, io, mode);
+    });
+    if (rc) return rc;
     MADRL_HIP_TRY(hipGetLastError());
     return MADRL_OK;
 }
@@ -726,11 +629,6 @@ int launch_to(madrl_pursuit *h, const PursuitIO &io, const float *obs_prev, void
 // one dword per env]
 uint64_t zmask_offset(int rec_bytes, int64_t n_envs) { return align_up((uint64_t)rec_bytes * (uint64_t)n_envs, 256); }
 uint64_t flags_offset(const madrl_pursuit_config *cfg, int rec_bytes, int64_t n_envs) { return zmask_offset(rec_bytes, n_envs) + zmask_len(find_fast(cfg), n_envs); }
-
-// what madrl_pursuit_create holds a line's compiled geometry against: the configuration's record and row (layout())
-bool same_record(const FastEntry &f, const PursuitDev &d) {
-    return f.rec_bytes == d.rec_bytes && f.off_gone == d.off_gone && f.off_term == d.off_term && f.D == d.D;
-}
 
 // the launch constants WaveDev and CrowdDev share with the generic kernel's
 template <class Dev>
@@ -808,7 +706,7 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
     rc = check_env_ids(n_envs, cfg->env_id_base);
     if (rc) return rc;
     MADRL_HIP_TRY(hipSetDevice(device));
-    madrl_pursuit *h = new (std::nothrow) madrl_pursuit();
+    std::unique_ptr<madrl_pursuit> h(new (std::nothrow) madrl_pursuit());   // ~madrl_pursuit frees whatever an early return leaves behind
     if (!h) return fail(MADRL_ENOMEM, "out of host memory");
     h->cfg = *cfg;
     h->device = device;
@@ -817,219 +715,63 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
     d.n_envs = n_envs;
     d.state = (uint8_t *)state_dev;
     d.flags = reinterpret_cast<uint32_t *>((uint8_t *)state_dev + flags_offset(cfg, d.rec_bytes, n_envs));
-    const int xs = d.xs, ys = d.ys, pad = d.pad, GW = d.GW;
-    const size_t cells = (size_t)xs * ys;
 
-    // ---- host-side tables
-    const size_t maps_bytes = (size_t)d.map_stride * d.n_maps;
-    const size_t off_cnt = align_up(maps_bytes, 16);
-    const size_t off_vtab = align_up(off_cnt + d.GSZ, 16);
-    const size_t off_codes = off_vtab + 256 * sizeof(float);
-    const size_t total = align_up(off_codes + sizeof(uint32_t) * d.D, 16);
-    std::vector<uint8_t> host(total, 0);
-    for (int m = 0; m < d.n_maps; ++m) {
-        const int8_t *map = map_pool_host + (size_t)m * cells;
-        uint8_t *wall = host.data() + (size_t)m * d.map_stride;
-        uint8_t *need = wall + d.GSZ;
-        memset(wall, PAD_MAP, d.GSZ);
-        for (int x = 0; x < xs; ++x)
-            for (int y = 0; y < ys; ++y) {
-                const int8_t v = map[x * ys + y];
-                if (v != 0 && v != -1) {
-                    delete h;
-                    return fail(MADRL_EINVAL, "map %d cell (%d,%d) = %d, expected 0 or -1", m, x, y, (int)v);
-                }
-                wall[(x + pad) * GW + y + pad] = (v == -1) ? 1 : 0;
-                need[x * ys + y] = (uint8_t)need_to_surround(map, xs, ys, x, y);
-            }
-    }
-    {
-        uint8_t *ct = host.data() + off_cnt;
-        memset(ct, PAD_CNT, d.GSZ);
-        for (int x = 0; x < xs; ++x)
-            for (int y = 0; y < ys; ++y) ct[(x + pad) * GW + y + pad] = 0;
-    }
-    {
-        // np.abs(model_state) / layer_norm is float32 / weak python scalar -> float32 (:438-439)
-        float *vt = reinterpret_cast<float *>(host.data() + off_vtab);
-        const float norm32 = (float)cfg->layer_norm;
-        for (int k = 0; k < 256; ++k) vt[k] = (float)k / norm32;
-        vt[PAD_MAP] = d.fill32;
-        vt[PAD_CNT] = 0.0f;
-    }
-    {
-        // slot codes: which padded-grid byte (relative to the window origin) feeds element r
-        uint32_t *codes = reinterpret_cast<uint32_t *>(host.data() + off_codes);
-        const int R = d.R, off = (R - 1) / 2, W = 2 * off + 1;  // W: copied window width (:451-461)
-        for (int r = 0; r < d.D; ++r) {
-            int c, i, j;
-            if (cfg->flatten) {
-                if (r == 3 * R * R) { codes[r] = K_ID << 24; continue; }  // :444-445
-                c = r / (R * R); i = (r % (R * R)) / R; j = r % R;
-            } else {
-                c = r % 4; i = (r / 4) / R; j = (r / 4) % R;  // rollaxis -> (R,R,4), :449
-                if (c == 3) {  // :440-441: only the centre of channel 3 is ever written
-                    codes[r] = ((i == R / 2 && j == R / 2) ? K_ID : K_SKIP) << 24;
-                    continue;
-                }
-            }
-            if (i < W && j < W) codes[r] = (K_GRID << 24) | (uint32_t)(c * d.GSZ + i * GW + j);
-            else codes[r] = (c == 0 ? K_FILL : K_SKIP) << 24;  // even obs_range (Q11)
-        }
-    }
+    // ---- the generic kernel's tables
+    const GenericTables gt = build_generic_tables(cfg, d, map_pool_host);
+    if (gt.bad_map >= 0) return fail(MADRL_EINVAL, "map %d cell (%d,%d) = %d, expected 0 or -1", gt.bad_map, gt.bad_x, gt.bad_y, gt.bad_v);
+    const size_t total = gt.host.size();
     hipError_t e = hipMalloc(&h->tables, total);
-    if (e != hipSuccess) {
-        delete h;
-        return fail(MADRL_EHIP, "hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
-    }
-    e = hipMemcpy(h->tables, host.data(), total, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(h->tables);
-        delete h;
-        return fail(MADRL_EHIP, "hipMemcpy tables failed: %s", hipGetErrorString(e));
-    }
-    uint8_t *tb = (uint8_t *)h->tables;
-    d.maps = tb;
-    d.cnt_tmpl = tb + off_cnt;
-    d.vtab = reinterpret_cast<const float *>(tb + off_vtab);
-    d.codes = reinterpret_cast<const uint32_t *>(tb + off_codes);
+    if (e != hipSuccess) return fail(MADRL_EHIP, "hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
+    e = hipMemcpy(h->tables, gt.host.data(), total, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(MADRL_EHIP, "hipMemcpy tables failed: %s", hipGetErrorString(e));
+    const uint8_t *tb = (const uint8_t *)h->tables;
+    d.maps = tb + gt.maps;
+    d.cnt_tmpl = tb + gt.cnt;
+    d.vtab = reinterpret_cast<const float *>(tb + gt.vtab);
+    d.codes = reinterpret_cast<const uint32_t *>(tb + gt.codes);
 
-    // ---- the fast path of this shape; one wavefront or a group of them per env: its tables (pursuit_wave.hpp)
+    // ---- the fast path of this shape, if the configuration is eligible for its line
     h->fast = find_fast(cfg);
-    h->wtables = nullptr;
-    h->kernel_kind = MADRL_KERNEL_AUTO;
+    void *const zmask = (uint8_t *)state_dev + zmask_offset(d.rec_bytes, n_envs);  // caller-owned, like the records
     if (h->fast && !h->fast->crowd()) {
-        const FastEntry &g = *h->fast;
-        const int need_words = ((int)cells + 3) / 4;
-        const int fstride = g.GSZ + need_words;
-        const size_t w_codes = (size_t)fstride * d.n_maps;
-        // after the maps: slot codes [D] | empty count layer [GSZ] | per-thread slot table [NS][6][NT] -- or, for shapes with more than 8
-        // slots per thread (pursuit_group.hpp, TABLED), one packed entry of two dwords per float4 of a pursuer's row [DV][2]
-        const int NT = 64 * g.nw, DV = d.D / 4, NQ = d.P * DV, NS = (NQ + NT - 1) / NT;
-        const bool tabled = NS > 8;
-        const size_t w_tmpl = w_codes + (size_t)d.D, w_slots = w_tmpl + (size_t)g.GSZ;
-        std::vector<uint32_t> wh(w_slots + (tabled ? (size_t)2 * DV : (size_t)NS * 6 * NT), 0u);
-        const float wallv = (float)1 / (float)cfg->layer_norm;  // |-1| / layer_norm in float32
-        uint32_t wall_bits, fill_bits;
-        memcpy(&wall_bits, &wallv, 4);
-        memcpy(&fill_bits, &d.fill32, 4);
-        for (int m = 0; m < d.n_maps; ++m) {
-            const int8_t *map = map_pool_host + (size_t)m * cells;
-            uint32_t *fm = wh.data() + (size_t)m * fstride;
-            uint8_t *need = reinterpret_cast<uint8_t *>(fm + g.GSZ);
-            for (int k = 0; k < g.GSZ; ++k) fm[k] = fill_bits;
-            for (int x = 0; x < xs; ++x)
-                for (int y = 0; y < ys; ++y) {
-                    fm[(x + g.PAD) * g.GW + y + g.PAD] = (map[x * ys + y] == -1) ? wall_bits : 0u;
-                    need[x * ys + y] = (uint8_t)need_to_surround(map, xs, ys, x, y);
-                }
-        }
-        uint32_t *wc = wh.data() + w_codes;
-        const int R = d.R;
-        // the fast path tells 0.0f, observation values and its "outside the map" marker apart by the top byte of the value:
-        // every non-zero observation value must be a positive float >= 2^-63 (top byte 0x20..0x7F)
-        uint32_t unit_bits;
-        { const float unit = (float)1 / (float)cfg->layer_norm; memcpy(&unit_bits, &unit, 4); }
-        bool eligible = (wall_bits != 0u) && (fill_bits != 0u) && (unit_bits >> 24) >= 0x20u && (unit_bits >> 24) < 0x80u &&
-                        (fill_bits >> 24) >= 0x20u && (fill_bits >> 24) < 0x80u && same_record(g, d) &&
-                        n_envs < 0x7FF00000ll;  // the fast kernels index envs with 32-bit integers (index + workgroup count < 2^31)
-        for (int r = 0; r < d.D; ++r) {
-            int c, i, j;
-            if (cfg->flatten) {
-                if (r == 3 * R * R) { wc[r] = (uint32_t)g.X_ID; continue; }
-                c = r / (R * R); i = (r % (R * R)) / R; j = r % R;
-            } else {
-                c = r % 4; i = (r / 4) / R; j = (r / 4) % R;
-                if (c == 3) { wc[r] = (uint32_t)((i == R / 2 && j == R / 2) ? g.X_ID : g.X_SKIP); continue; }
-            }
-            wc[r] = 0x80000000u | (uint32_t)(c * g.GSZ + i * g.GW + j);
-        }
-        for (int r = 0; r < d.D; ++r)  // the kernel assumes only element 3 of a float4 can be absolute
-            if ((r & 3) != 3 && !(wc[r] >> 31)) eligible = false;
-        for (int k = 0; k < g.GSZ; ++k) {
-            const int gx = k / g.GW - g.PAD, gy = k % g.GW - g.PAD;
-            wh[w_tmpl + k] = (gx >= 0 && gx < xs && gy >= 0 && gy < ys) ? 0u : pw::SENT;
-        }
-        if (tabled) {
-            // entry f: dword 0 = off0 | off1 << 16, dword 1 = off2 | id3 << 15 | off3 << 16 | abs3 << 31 -- dword offsets into the LDS array,
-            // relative to the window origin unless abs3 (element 3 only: the skip cell, or with id3 the id cell of pursuer 0 + pursuer)
-            if (3 * g.GSZ + 2 + d.P >= 32768 || g.mwords != (NS + 7) / 8) eligible = false;
-            for (int f = 0; f < DV && eligible; ++f) {
-                uint32_t off[4], abs3 = 0u, id3 = 0u;
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t c = wc[4 * f + k];
-                    off[k] = c & 0x7FFFFFFFu;
-                    if (k == 3 && !(c >> 31)) { abs3 = 1u; id3 = ((int)off[k] == g.X_ID) ? 1u : 0u; }
-                    if (off[k] >= 32768u) eligible = false;
-                }
-                wh[w_slots + 2 * (size_t)f] = off[0] | (off[1] << 16);
-                wh[w_slots + 2 * (size_t)f + 1] = off[2] | (id3 << 15) | (off[3] << 16) | (abs3 << 31);
-            }
-        }
-        for (int sl = 0; sl < (tabled ? 0 : NS); ++sl)
-            for (int t = 0; t < NT; ++t) {
-                const int q = t + NT * sl, pidx = q / DV, f = q % DV;
-                uint32_t *row = wh.data() + w_slots + (size_t)sl * 6 * NT + t;
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t c = (q < NQ) ? wc[4 * f + k] : (k == 3 ? (uint32_t)g.X_SKIP : 0u);
-                    uint32_t cst = c & 0x7FFFFFFFu;
-                    if ((int)cst >= g.X_ID && (int)cst < g.X_ID + d.P) cst = (uint32_t)(g.X_ID + pidx);  // this pursuer's id cell
-                    row[(size_t)NT * k] = cst;
-                    if (k == 3) row[(size_t)NT * 4] = c >> 31;
-                }
-                row[(size_t)NT * 5] = (uint32_t)(q < NQ ? pidx : 0);
-            }
-        if (eligible) {
-            const size_t wbytes = wh.size() * sizeof(uint32_t);
+        // one wavefront or a group of them per env: its own tables (pursuit_wave.hpp)
+        const WaveTables wt = build_wave_tables(cfg, d, h->fast->g, n_envs, map_pool_host);
+        if (wt.eligible) {
+            const size_t wbytes = wt.host.size() * sizeof(uint32_t);
             e = hipMalloc(&h->wtables, wbytes);
-            if (e == hipSuccess) e = hipMemcpy(h->wtables, wh.data(), wbytes, hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                if (h->wtables) (void)hipFree(h->wtables);
-                (void)hipFree(h->tables);
-                delete h;
-                return fail(MADRL_EHIP, "wave tables: %s", hipGetErrorString(e));
-            }
-            h->zmask = (uint8_t *)state_dev + zmask_offset(d.rec_bytes, n_envs);  // caller-owned, like the records
+            if (e == hipSuccess) e = hipMemcpy(h->wtables, wt.host.data(), wbytes, hipMemcpyHostToDevice);
+            if (e != hipSuccess) return fail(MADRL_EHIP, "wave tables: %s", hipGetErrorString(e));
+            h->zmask = zmask;
             pw::WaveDev &w = h->wdev;
             fill_common(w, d);
-            w.fmap_stride = fstride;
+            w.fmap_stride = wt.fstride;
             w.fmaps = reinterpret_cast<const uint32_t *>(h->wtables);
-            w.cnt_tmpl = reinterpret_cast<const uint32_t *>(h->wtables) + w_tmpl;
-            w.slot_tab = reinterpret_cast<const uint32_t *>(h->wtables) + w_slots;
-            w.zmask = reinterpret_cast<uint32_t *>(h->zmask);
+            w.cnt_tmpl = w.fmaps + wt.w_tmpl;
+            w.slot_tab = w.fmaps + wt.w_slots;
+            w.zmask = reinterpret_cast<uint32_t *>(zmask);
         } else {
             h->fast = nullptr;
         }
-    } else if (h->fast && h->fast->GSZ == d.GSZ && same_record(*h->fast, d)) {
-        // ---- the crowd kernel: the generic kernel's tables and record, when the compiled geometry is this configuration's
-        h->zmask = (uint8_t *)state_dev + zmask_offset(d.rec_bytes, n_envs);  // caller-owned, like the records
+    } else if (h->fast && h->fast->g.GSZ == d.GSZ && same_record(h->fast->g, d)) {
+        // the crowd kernel: the generic kernel's tables and record, when the compiled geometry is this configuration's
+        h->zmask = zmask;
         pc::CrowdDev &c = h->cdev;
         fill_common(c, d);
         c.map_stride = d.map_stride;
         c.maps = d.maps;
-        c.ch3 = reinterpret_cast<const uint32_t *>(h->zmask);
+        c.ch3 = reinterpret_cast<const uint32_t *>(zmask);
     } else {
         h->fast = nullptr;
     }
     h->fast_live = find_live(h->fast);
 
-    h->walk_mode = 0;
-    h->max_blocks = 0;
-    rc = madrl_pursuit_set_launch(h, 0, 0);
+    rc = madrl_pursuit_set_launch(h.get(), 0, 0);
+    if (rc) return rc;
     // the fork / join events of madrl_pursuit_step_sharded, on this handle's device (hipSetDevice above), each checked on its own
-    if (!rc && (hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess)) {
-        if (h->ev_done) (void)hipEventDestroy(h->ev_done);
-        if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-        rc = fail(MADRL_EHIP, "create: hipEventCreateWithFlags failed");
-    }
-    if (rc) {
-        if (h->wtables) (void)hipFree(h->wtables);
-        (void)hipFree(h->tables);
-        delete h;
-        return rc;
-    }
-    *out = h;
+    if (hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess)
+        return fail(MADRL_EHIP, "create: hipEventCreateWithFlags failed");
+    *out = h.release();
     return MADRL_OK;
 }
 
@@ -1055,31 +797,19 @@ int madrl_pursuit_set_launch(madrl_pursuit *h, int32_t threads, int64_t max_bloc
     if (lds > 64 * 1024) {
         // opt in to large dynamic LDS for every instantiation we may launch
         const int bytes = (int)lds;
-#define MADRL_SET_LDS(NT) hipFuncSetAttribute((const void *)pursuit_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
-        (void)MADRL_SET_LDS(1); (void)MADRL_SET_LDS(2); (void)MADRL_SET_LDS(3); (void)MADRL_SET_LDS(4);
-        (void)MADRL_SET_LDS(5); (void)MADRL_SET_LDS(6); (void)MADRL_SET_LDS(7); (void)MADRL_SET_LDS(8);
-#undef MADRL_SET_LDS
-#define MADRL_SET_LDS(NT) hipFuncSetAttribute((const void *)pursuit_live_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
-        (void)MADRL_SET_LDS(1); (void)MADRL_SET_LDS(2); (void)MADRL_SET_LDS(3); (void)MADRL_SET_LDS(4);
-        (void)MADRL_SET_LDS(5); (void)MADRL_SET_LDS(6); (void)MADRL_SET_LDS(7); (void)MADRL_SET_LDS(8);
-#undef MADRL_SET_LDS
-#define MADRL_SET_LDS(NT) ((void)hipFuncSetAttribute((const void *)pursuit_to_kernel<NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), \
-                           hipFuncSetAttribute((const void *)pursuit_to_kernel<NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))
-        (void)MADRL_SET_LDS(1); (void)MADRL_SET_LDS(2); (void)MADRL_SET_LDS(3); (void)MADRL_SET_LDS(4);
-        (void)MADRL_SET_LDS(5); (void)MADRL_SET_LDS(6); (void)MADRL_SET_LDS(7); (void)MADRL_SET_LDS(8);
-#undef MADRL_SET_LDS
+        for (int k = 1; k <= 8; ++k)
+            (void)with_nt(k, [&](auto nt_c) {
+                constexpr int NT = decltype(nt_c)::value;
+                (void)hipFuncSetAttribute((const void *)pursuit_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+                (void)hipFuncSetAttribute((const void *)pursuit_live_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+                (void)hipFuncSetAttribute((const void *)pursuit_to_kernel<NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+                (void)hipFuncSetAttribute((const void *)pursuit_to_kernel<NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+            });
     }
     return MADRL_OK;
 }
 
-void madrl_pursuit_destroy(madrl_pursuit *h) {
-    if (!h) return;
-    if (h->tables) (void)hipFree(h->tables);
-    if (h->wtables) (void)hipFree(h->wtables);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_done) (void)hipEventDestroy(h->ev_done);
-    delete h;
-}
+void madrl_pursuit_destroy(madrl_pursuit *h) { delete h; }   // (~madrl_pursuit)
 
 int madrl_pursuit_set_kernel(madrl_pursuit *h, int32_t kind) {
     if (!h) return fail(MADRL_EINVAL, "handle is NULL");
@@ -1110,22 +840,14 @@ int madrl_pursuit_reset(madrl_pursuit *h, const uint8_t *mask_dev, const int32_t
     io.inj_pos = inj_pos_dev;
     io.inj_map = inj_map_dev;
     io.obs = obs_dev;
-    return launch(h, io, 0, stream);
+    return launch(h, io, 0, nullptr, stream);
 }
 
 int madrl_pursuit_step(madrl_pursuit *h, const int32_t *actions_dev, const int32_t *inj_evader_actions_dev,
                        float *obs_dev, float *rew_dev, uint8_t *done_dev, int32_t *removed_dev, void *stream) {
     if (!h || !actions_dev || !obs_dev || !rew_dev || !done_dev || !removed_dev)
         return fail(MADRL_EINVAL, "step: NULL argument");
-    PursuitIO io;
-    memset(&io, 0, sizeof(io));
-    io.actions = actions_dev;
-    io.inj_eact = inj_evader_actions_dev;
-    io.obs = obs_dev;
-    io.rew = rew_dev;
-    io.done = done_dev;
-    io.removed = removed_dev;
-    return launch(h, io, 1, stream);
+    return launch(h, step_io(actions_dev, inj_evader_actions_dev, obs_dev, rew_dev, done_dev, removed_dev), 1, nullptr, stream);
 }
 
 int madrl_pursuit_step_to(madrl_pursuit *h, const int32_t *actions_dev, const int32_t *inj_evader_actions_dev, const float *obs_prev_dev,
@@ -1138,15 +860,7 @@ int madrl_pursuit_step_to(madrl_pursuit *h, const int32_t *actions_dev, const in
     const uint64_t a = (uint64_t)obs_prev_dev, b = (uint64_t)obs_next_dev;
     if (a < b + bytes && b < a + bytes) return fail(MADRL_EINVAL, "step_to: obs_prev and obs_next overlap (the same buffer is madrl_pursuit_step; two buffers must be disjoint)");
     if ((a | b) & 15u) return fail(MADRL_EINVAL, "step_to: observation buffers must be 16-byte aligned");
-    PursuitIO io;
-    memset(&io, 0, sizeof(io));
-    io.actions = actions_dev;
-    io.inj_eact = inj_evader_actions_dev;
-    io.obs = obs_next_dev;
-    io.rew = rew_dev;
-    io.done = done_dev;
-    io.removed = removed_dev;
-    return launch_to(h, io, obs_prev_dev, stream);
+    return launch(h, step_io(actions_dev, inj_evader_actions_dev, obs_next_dev, rew_dev, done_dev, removed_dev), 1, obs_prev_dev, stream);
 }
 
 int madrl_pursuit_step_to_kernel_kind(madrl_pursuit *h, int32_t *out) {
@@ -1170,10 +884,7 @@ int madrl_pursuit_step_sharded(madrl_pursuit *const *hs, const madrl_pursuit_sha
     int rc = MADRL_OK, launched = 0;
     for (; launched < n_shards && rc == MADRL_OK; ++launched) {
         const int j = launched;
-        PursuitIO p;
-        memset(&p, 0, sizeof(p));
-        p.actions = io[j].actions; p.inj_eact = io[j].inj_evader_actions; p.obs = io[j].obs; p.rew = io[j].rew; p.done = io[j].done; p.removed = io[j].removed;
-        rc = launch(hs[j], p, 1, io[j].stream);
+        rc = launch(hs[j], step_io(io[j].actions, io[j].inj_evader_actions, io[j].obs, io[j].rew, io[j].done, io[j].removed), 1, nullptr, io[j].stream);
         if (rc) break;
     }
     // ... and the caller's stream waits for every sub-batch -- also when a launch failed half way: the shards launched before it are

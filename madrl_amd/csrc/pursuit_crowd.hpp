@@ -76,7 +76,7 @@ struct CShape {
     static constexpr int D = FLATTEN ? 3 * R * R + 1 : 4 * R * R;  // include_id is implied
     static constexpr int DV = D / 4;                               // float4 per pursuer row
     static constexpr int NQ = P * DV;                              // float4 slots per env
-    // packed state record, identical to the generic kernel's layout() in pursuit.hip
+    // packed state record, identical to the generic kernel's layout() (pursuit_tables.hpp)
     static constexpr int NGW = (E + 31) / 32 > 0 ? (E + 31) / 32 : 1;
     static constexpr int NTW = (A + 31) / 32;
     static constexpr int OFF_GONE = (HDR_BYTES + 2 * A + 3) / 4 * 4;

@@ -125,7 +125,7 @@ struct Shape {
     static constexpr int X_NEED = X_VTAB + NVT;                  // XS*YS bytes, as dwords
     static constexpr int X_OBSV = X_NEED + (XS * YS + 3) / 4;    // evader control: window origin of the observer of row p (P dwords)
     static constexpr int LDS_DWORDS = X_OBSV + (P + 3) / 4 * 4;
-    // packed state record, identical to the generic kernel's layout() in pursuit.hip
+    // packed state record, identical to the generic kernel's layout() (pursuit_tables.hpp)
     static constexpr int NGW = (E + 31) / 32 > 0 ? (E + 31) / 32 : 1;
     static constexpr int NTW = (A + 31) / 32;
     static constexpr int OFF_GONE = (16 + 2 * A + 3) / 4 * 4;
