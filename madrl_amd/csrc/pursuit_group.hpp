@@ -19,11 +19,14 @@
 // Requirements: n_pursuers <= 64, n_evaders <= 64, record <= 64 dwords, odd obs_range, row length % 4 == 0.
 //
 // LONG ROWS (round 6; the authors' own training shapes, runners/old/rllab/pursuit.sh:1 -- 30 pursuers, obs_range 11: 2 730 float4 per
-// env, 22 slots per thread): with more than 8 slots per thread the per-slot constants no longer live in registers (6 VGPRs per slot).
+// env, 11 slots per thread of four wavefronts, two mask words): with more than 8 slots per thread of two wavefronts the per-slot
+// constants no longer live in registers (6 VGPRs per slot), and four wavefronts carry the rows.
 // Such a shape is TABLED: slot q = tid + NT s still belongs to thread tid (every store instruction writes NT consecutive float4, whole
 // 64-byte chunks), but its constants come from a table in LDS indexed by the float4's position f = q mod DV inside its row -- four
 // 15-bit dword offsets relative to the window origin, packed in two dwords, identical for every pursuer -- and (pursuer, f) advance
 // from slot to slot by constants.  The stale-zero mask grows to MWORDS = ceil(NS / 8) dwords per thread (one bit per slot in each byte).
+// The authors' shapes have two mask words; three and four (17 to 32 slots), words that hold 1, 5 and 7 slots and the 9-slot threshold
+// run in the `// tests:` lines of pursuit_specializations.def.
 //
 // PER-ENV AGENT COUNTS (LGShape, pursuit_live_specializations.def XLG lines): the LShape contract of pursuit_wave.hpp carried over.  The
 // agents span wavefronts, so the live (np, ne) are counted from the record that EVERY wavefront holds whole (dword k in lane k), not from
@@ -243,23 +246,23 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
         if constexpr (MODE == 1) return isP() ? uniform_ptr(io.actions + env * P)[utid] : 4;
         else return 4;
     };
-    // evader-slot mask of a wave-wide predicate, combined over the wavefronts that hold agents
+    // evader-slot mask of a wave-wide predicate, combined over the wavefronts that hold agents and handed to EVERY wavefront of the group
+    // -- also when one wavefront holds all agents (NAW == 1, long rows: 30 v 30 on four wavefronts): the others must learn of this step's
+    // catches too, or they miss an episode that ends by its last catch, skip the fused reset's second pass and leave the group's barriers
     auto evader_mask = [&](bool pred) -> uint64_t {
+        static_assert(S::NW >= 2 && S::NAW <= 2, "the exchange reads the words of wavefronts 0 and 1");
         const uint64_t b = __ballot(pred);
-        if constexpr (S::NAW == 1) {
-            return b >> P;
-        } else {
-            const uint64_t mine = (wv == 0) ? (b >> P) : ((wv == 1) ? (b << (64 - P)) : 0ull);
-            if (lane == 0) {
-                L[S::X_XCH + 2 * wv] = (uint32_t)mine;
-                L[S::X_XCH + 2 * wv + 1] = (uint32_t)(mine >> 32);
-            }
-            group_sync();
-            const uint32_t a0 = L[S::X_XCH], a1 = L[S::X_XCH + 1], b0 = L[S::X_XCH + 2], b1 = L[S::X_XCH + 3];
-            const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a0 | b0));
-            const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a1 | b1));
-            return ((uint64_t)hi << 32) | lo;
+        // (64 pursuers: wavefront 0 holds no evader -- and a 64-bit shift by 64 is not defined)
+        const uint64_t mine = (wv == 0) ? (P < 64 ? (b >> (P & 63)) : 0ull) : ((wv == 1) ? (b << ((64 - P) & 63)) : 0ull);
+        if (lane == 0) {
+            L[S::X_XCH + 2 * wv] = (uint32_t)mine;
+            L[S::X_XCH + 2 * wv + 1] = (uint32_t)(mine >> 32);
         }
+        group_sync();
+        const uint32_t a0 = L[S::X_XCH], a1 = L[S::X_XCH + 1], b0 = L[S::X_XCH + 2], b1 = L[S::X_XCH + 3];
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a0 | b0));
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a1 | b1));
+        return ((uint64_t)hi << 32) | lo;
     };
     auto fetch_zm = [&](int64_t env, uint32_t (&zmw)[MW]) {   // stale-zero masks, pursuit_wave.hpp: [env][MWORDS][NT]
 #pragma unroll
@@ -407,9 +410,8 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                     }
                     if (caught) atomicAdd(&layer[cell], CAUGHT);
                 }
-                const uint64_t caught_mask = evader_mask(caught);  // contains the barrier for the CAUGHT marks when NAW > 1
+                const uint64_t caught_mask = evader_mask(caught);  // contains the barrier for the CAUGHT marks
                 gone |= caught_mask;
-                if constexpr (S::NAW == 1) group_sync();
                 // ---------------------------------------------------- rewards (:254-262)
                 double r = 0.0;
                 if (isLP()) {
@@ -519,7 +521,6 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                     alive = exists;
                     tick += 1;
                     tstep = 0;
-                    if constexpr (S::NAW == 1) group_sync();
                 }
                 // ------------------------------------------------------ observations (:418-461)
                 if constexpr (S::LIVE) {  // the id values k / np of this pass's pursuer count (np is the same in every wavefront; the
@@ -741,7 +742,7 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                         }
                     };
                     if constexpr (S::TABLED) {
-                        // a ROLLED loop per mask word (fully unrolled, the 22 slots of the authors' shape cost 241 VGPRs: two wavefronts per SIMD)
+                        // a ROLLED loop per mask word (fully unrolled, the 22 slots the authors' shape had on two wavefronts cost 241 VGPRs: two wavefronts per SIMD)
                         int pq = q0_p, fq = q0_f, q = tid;   // (pursuer, position in its row) and index of the slot, advanced by constants
                         const char *Lb = reinterpret_cast<const char *>(L);
                         auto cell_b = [&](int byte_off) -> uint32_t { return *reinterpret_cast<const uint32_t *>(Lb + byte_off); };

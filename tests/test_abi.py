@@ -159,8 +159,8 @@ def test_which_shapes_can_have_a_fast_path_and_how_they_are_added(tmp_path, monk
     from madrl_amd import build as b
     assert b.pursuit_fast_path(16, 16, 8, 30, 7, 1) == ("X", None) and b.pursuit_fast_path(32, 32, 16, 60, 7, 1) == ("XG", 2)
     assert b.pursuit_fast_path(16, 16, 8, 30, 7, 0) == ("X", None) and b.pursuit_fast_path(20, 8, 7, 1, 3, 0) == ("X", None)
-    # the authors' own training shapes (runners/old/rllab/pursuit.sh:1, runners/old/rltools/pursuit.sh:1): 22 float4 slots per thread on two
-    # wavefronts -- also at 30 v 30, where the agents alone would fit one
+    # the authors' own training shapes (runners/old/rllab/pursuit.sh:1, runners/old/rltools/pursuit.sh:1): 22 float4 slots per thread of two
+    # wavefronts, so four carry the rows, 11 slots and two mask words each -- also at 30 v 30, where the agents alone would fit one
     assert b.pursuit_fast_path(32, 32, 30, 50, 11, 1) == ("XG", 4) and b.pursuit_fast_path(32, 32, 30, 30, 11, 1) == ("XG", 4)   # long rows: four wavefronts
     assert b.pursuit_fast_path(5, 10, 16, 7, 7, 1) == ("XG", 2)   # 23 agents, but 10 slots per lane of one wavefront: two wavefronts, 5 each
     for shape, why in (((10, 10, 4, 4, 4, 1), "even"), ((128, 128, 100, 300, 21, 0), "more than 64"), ((16, 16, 64, 10, 21, 0), "slots"),
@@ -168,6 +168,13 @@ def test_which_shapes_can_have_a_fast_path_and_how_they_are_added(tmp_path, monk
         kind, reason = b.pursuit_fast_path(*shape)
         assert kind is None and why in reason, (shape, reason)
     assert b.pursuit_fast_path(16, 16, 8, 30, 7, 1, include_id=False)[0] is None
+    # the limits themselves are accepted (each has its `// tests:` line in the committed list), one step past each is refused with its reason
+    assert b.pursuit_fast_path(16, 16, 64, 40, 3, 1) == ("XG", 2) and b.pursuit_fast_path(16, 16, 44, 64, 3, 1) == ("XG", 2)
+    assert b.pursuit_fast_path(12, 12, 64, 20, 13, 1) == ("XG", 4) and b.pursuit_fast_path(16, 16, 13, 51, 7, 1) == ("X", None)
+    for shape, why in (((16, 16, 65, 10, 3, 1), "more than 64 pursuers"), ((16, 16, 46, 64, 3, 1), "state record above 256 bytes"),
+                       ((12, 12, 64, 20, 15, 1), "more than 32 float4 slots")):
+        kind, reason = b.pursuit_fast_path(*shape)
+        assert kind is None and why in reason, (shape, reason)
     # every committed line passes its own check
     for line in open(os.path.join(ROOT, "madrl_amd", "csrc", "pursuit_specializations.def")):
         m = re.match(r"\s*(XG?)\(([^)]*)\)", line)

@@ -93,7 +93,7 @@ def test_long_rollout_into_the_mask_equilibrium_is_bit_exact(mode, start):
     maps = [rectangle_map(16, 16)]
     kw = dict(n_pursuers=P, n_evaders=E, obs_range=7, reward_mech="local")
     kw.update(dict(n_catch=2, surround=True, flatten=True) if mode == "headline" else dict(n_catch=2, surround=False, flatten=False))
-    if mode == "authors_long_rows":   # the two-wavefront kernel with the LDS slot table: three stale-zero mask words per thread
+    if mode == "authors_long_rows":   # the four-wavefront kernel with the LDS slot table: 11 slots and two stale-zero mask words per thread
         import os
         from conftest import GOLDEN
         N, P, E, T = 192, 30, 50, 500

@@ -31,7 +31,7 @@ WAVE_GOLDEN = {"pursuit_c1_surround_local", "pursuit_c1_surround_global", "pursu
                "pursuit_pool16_sample_maps", "pursuit_tiny5_dense", "pursuit_in_building",
                "pursuit_nonsquare_12x20", "pursuit_window_gt_map", "pursuit_random_opponents",
                "pursuit_c5_32x32",  # two wavefronts per env (pursuit_group.hpp)
-               "pursuit_authors_30v50_obs11", "pursuit_authors_30v30_obs11",   # ... with 22 float4 slots per thread (the LDS slot table, round 6)
+               "pursuit_authors_30v50_obs11", "pursuit_authors_30v30_obs11",   # four wavefronts per env, 11 float4 slots per thread (the LDS slot table, round 6)
                "pursuit_fuzz_13", "pursuit_fuzz_20"}  # the drawn configurations whose shape the one-wavefront kernel can take (odd obs_range, <= 8 float4 slots per lane)
 
 
@@ -94,24 +94,52 @@ CASES = {
     "authors_cnn_100v300": dict(maps="rect128", n_pursuers=100, n_evaders=300, obs_range=21, n_catch=2, surround=True, flatten=False,
                                 reward_mech="local", n_envs=6, steps=20, expect_catches=False),   # (random pursuers surround nobody on a 128 x 128 map in 20 steps)
     # the authors' own training shapes (runners/old/rllab/pursuit.sh:1, runners/old/rltools/pursuit.sh:1) on resize(2, map_pool16): the
-    # two-wavefront kernel with the LDS slot table (22 slots per thread, three stale-zero mask words)
+    # four-wavefront kernel with the LDS slot table (11 slots per thread, two stale-zero mask words)
     "authors_30v50_obs11": dict(maps="pool32", n_pursuers=30, n_evaders=50, obs_range=11, n_catch=2, surround=True, flatten=True,
                                 reward_mech="local", sample_maps=True, n_envs=192, steps=90),
     "authors_30v30_obs11": dict(maps="pool32", n_pursuers=30, n_evaders=30, obs_range=11, n_catch=2, surround=True, flatten=True,
                                 reward_mech="local", sample_maps=True, catchr=0.0, term_pursuit=5.0, n_envs=192, steps=60),
+    # the 30 v 30 shape with ONE evader per episode (max_opponents 2 creates 1 + floor(u) = 1): episodes end by their last catch while
+    # the other envs of the workgroup run on.  All agents sit in wavefront 0 of the four: the other three learn of the catch -- and of
+    # the 29 evaders a reset does not create -- only through the group's mask exchange, and must take the fused reset's second pass too
+    "authors_30v30_one_opponent": dict(maps="pool32", n_pursuers=30, n_evaders=30, obs_range=11, n_catch=1, surround=False, flatten=True,
+                                       reward_mech="local", sample_maps=True, random_opponents=True, max_opponents=2,
+                                       n_envs=40, steps=60, max_blocks=3, expect_lone_done=True),
     "tiny_window": dict(maps="open6", n_pursuers=5, n_evaders=4, obs_range=5, n_catch=2, surround=True, flatten=True,
                         reward_mech="global", constraint_window=0.5),
 }
 
+# The fast path at the limits madrl_amd.build.pursuit_fast_path accepts (the last `// tests:` lines of csrc/pursuit_specializations.def):
+# name -> (map side, n_pursuers, n_evaders, obs_range, surround, reward_mech, what the shape pins)
+LIMIT_SHAPES = {
+    "limit_09_slots_36v10": (10, 36, 10, 9, True, "local", "9 slots per thread, the first TABLED count: the second mask word holds one slot"),
+    "limit_13_slots_36v12": (10, 36, 12, 11, False, "local", "13 slots: the second mask word holds 5 (remainder batch of 1, odd tail of the unroll by 2)"),
+    "limit_17_slots_46v18": (12, 46, 18, 11, True, "local", "17 slots: three mask words, the third holds one slot; 64 agents in one agent wavefront of four"),
+    "limit_23_slots_46v10": (12, 46, 10, 13, False, "local", "23 slots: the third mask word holds 7 (remainder batch of 3)"),
+    "limit_32_slots_64v20": (12, 64, 20, 13, False, "global", "32 slots, four mask words; 64 pursuers (the pairwise mean over 64), agents in two wavefronts"),
+    "limit_64_pursuers_64v40": (16, 64, 40, 3, False, "local", "64 pursuers on the register path; a record of exactly 64 dwords"),
+    "limit_64_evaders_44v64": (16, 44, 64, 3, False, "local", "64 evaders (bit 63 of the alive mask); 108 agents, the most a 256-byte record holds"),
+    "limit_wave_8_slots_13v51": (16, 13, 51, 7, False, "local", "one wavefront: 8 slots per lane, 64 agents, evader slot 50 in lane 63"),
+}
+
+
+def _limit_kw(name):
+    side, P, E, R, surround, mech, _what = LIMIT_SHAPES[name]
+    return dict(maps="rect%d" % side, n_pursuers=P, n_evaders=E, obs_range=R, n_catch=2, surround=surround, flatten=True, reward_mech=mech)
+
+
+# 40 envs on 3 workgroups: a workgroup walks 13 - 14 envs, so the loop-carried prefetch of record, action and mask words runs with a ragged tail
+for _name in LIMIT_SHAPES:
+    CASES[_name] = dict(_limit_kw(_name), n_envs=40, steps=60, max_blocks=3)
+# (these two also end episodes by their last catch at steps where the other envs run on -- with 56 agents in one wavefront of four, and
+# with 84 in two of four)
+CASES["limit_23_slots_46v10"]["expect_lone_done"] = CASES["limit_32_slots_64v20"]["expect_lone_done"] = True
+
 
 def _maps(name):
     from madrl_amd.maps import rectangle_map
-    if name == "rect16":
-        return [rectangle_map(16, 16)]
-    if name == "rect32":
-        return [rectangle_map(32, 32)]
-    if name == "rect128":
-        return [rectangle_map(128, 128)]
+    if name.startswith("rect"):
+        return [rectangle_map(int(name[4:]), int(name[4:]))]
     if name == "open6":
         return [np.zeros((6, 6), np.int32)]
     if name == "pool32":   # TwoDMaps.resize(2, map_pool16), as recorded in the authors' shape goldens
@@ -131,10 +159,11 @@ def test_hip_matches_oracle_free_running(case, kernel):
     kw = dict(CASES[case])
     maps = _maps(kw.pop("maps"))
     N, T = kw.pop("n_envs", 512), kw.pop("steps", 120)
-    expect_catches = kw.pop("expect_catches", True)
+    expect_catches, max_blocks, expect_lone_done = kw.pop("expect_catches", True), kw.pop("max_blocks", 0), kw.pop("expect_lone_done", False)
     if kernel == "auto" and kw["n_pursuers"] + kw["n_evaders"] > 128:
         pytest.skip("no fast path above two wavefronts of agents: the generic kernel is what runs")
-    _free_run(maps, kw, kernel, N, T, expect_catches, want_kind="wave" if kernel == "auto" else None)
+    _free_run(maps, kw, kernel, N, T, expect_catches, want_kind="wave" if kernel == "auto" else None, max_blocks=max_blocks,
+              expect_lone_done=expect_lone_done)
 
 
 def _drawn_cases(n=16, seed=20260927):
@@ -158,9 +187,11 @@ def test_drawn_configurations_free_running_vs_oracle(i):
     _free_run(maps, cfg, "auto", 96 if big else 256, 50, expect_catches=False)
 
 
-def _free_run(maps, kw, kernel, N, T, expect_catches, want_kind=None, H=25):
+def _free_run(maps, kw, kernel, N, T, expect_catches, want_kind=None, H=25, max_blocks=0, expect_lone_done=False):
     from oracle import pursuit as po
     env = _mk(maps, N, seed=2024, env_id_base=1000, max_steps=H, auto_reset=True, kernel=kernel, **kw)
+    if max_blocks:
+        env.set_launch(max_blocks=max_blocks)   # a workgroup walks several envs: the loop-carried prefetch is exercised
     if want_kind:
         assert env.kernel_kind == want_kind  # one wavefront per env, or a wavefront group for more than 64 agents
     orc = po.PursuitOracle(maps, n_envs=N, seed=2024, env_id_base=1000, **kw)
@@ -170,7 +201,8 @@ def _free_run(maps, kw, kernel, N, T, expect_catches, want_kind=None, H=25):
     _cmp_state(env.get_state(), orc.get_state(), "after reset")
     rng = np.random.RandomState(5)
     tstep = np.zeros(N, np.int64)
-    n_done = n_removed = 0
+    n_done = n_removed = n_lone_done = 0
+    n_resets = np.zeros(N, np.int64)
     for t in range(T):
         act = rng.randint(5, size=(N, env.n_pursuers))
         obs, rew, done, info = env.step(torch.as_tensor(act, device=DEV))
@@ -184,7 +216,9 @@ def _free_run(maps, kw, kernel, N, T, expect_catches, want_kind=None, H=25):
         if mask.any():
             orc.reset(mask=mask)  # rewrites the masked rows of orc.obs (shared persistent buffer)
             tstep[mask != 0] = 0
+            n_resets += mask
         n_done += int((bits & 1).sum())
+        n_lone_done += int((bits & 1).any() and not (bits != 0).all())   # an episode ended by its last catch while other envs ran on
         n_removed += int(orem.sum())
         got = obs.reshape(orc.obs.shape).cpu().numpy()
         assert np.array_equal(got, orc.obs), "step %d obs: %d cells differ" % (t, int((got != orc.obs).sum()))
@@ -192,32 +226,126 @@ def _free_run(maps, kw, kernel, N, T, expect_catches, want_kind=None, H=25):
             _cmp_state(env.get_state(), orc.get_state(), "step %d" % t)
             assert np.array_equal(env.get_state()["t"].cpu().numpy(), tstep), "episode step counter"
     assert n_removed > 0 or not expect_catches
+    assert T < H or bool((n_resets > 0).all()), "every env went through the fused reset at least once"
+    assert n_lone_done > 0 or not expect_lone_done
 
 
-@pytest.mark.parametrize("shape", ["c2_wave", "c5_group"])
+@pytest.mark.parametrize("start", ["nothing_known", "known_zero"])
+@pytest.mark.parametrize("case", sorted(LIMIT_SHAPES), ids=sorted(LIMIT_SHAPES))
+def test_limit_shapes_keep_and_store_cells_of_a_buffer_that_is_not_zero(case, start):
+    """The fast path of the limit shapes on a buffer whose never-stored cells hold something: after reset(), channels 1 and 2 of every
+    row hold 7.0 where the window indices have (i + j) % 2 == 0 -- every float4 then mixes cells a step keeps with cells it stores --
+    on both sides (the tensor in place, set_local_obs on the oracle), and the env is told so (invalidate_obs: "nothing known").  The
+    whole persistent buffer, rewards, done bits and `removed` equal the C oracle's at every one of 30 steps; two workgroups walk the 24
+    envs, and max_steps 11 puts two fused resets into every env's run.  The oracle's own buffer says the run is not empty: 7.0 cells
+    remain after step 10 on every shape, and on the six shapes with obs_range >= 7 after step 30 too, some of them in a float4 with
+    another value (with obs_range 3 every window cell has been inside the map once by then).
+    known_zero: the same cells are zeroed again on both sides and the env is NOT told: what the create call declared and the reset
+    learned about the buffer stays in force -- still true, a zero where the masks say "zero or stored" -- so the whole-store path runs
+    where the first start state takes the masked stores."""
+    from oracle import pursuit as po
+    kw = _limit_kw(case)
+    maps = _maps(kw.pop("maps"))
+    N, T, H, R, P = 24, 30, 11, kw["obs_range"], kw["n_pursuers"]
+    env = _mk(maps, N, seed=7, env_id_base=300, max_steps=H, auto_reset=True, kernel="auto", **kw)
+    env.set_launch(max_blocks=2)
+    assert env.kernel_kind == "wave"
+    orc = po.PursuitOracle(maps, n_envs=N, seed=7, env_id_base=300, **kw)
+    obs, oobs = env.reset(), orc.reset()
+    assert np.array_equal(obs.cpu().numpy(), oobs), "reset obs"
+    i, j = np.meshgrid(np.arange(R), np.arange(R), indexing="ij")
+    board = (i + j) % 2 == 0
+    fill = 7.0 if start == "nothing_known" else 0.0
+    lo = orc.local_obs()
+    lo[:, :, 1:3, board] = 7.0
+    lo[:, :, 1:3, board] = fill
+    orc.set_local_obs(lo)
+    # .data: a write PyTorch's version counter does not see (include/madrl_hip.h, the obs_dev contract), so that nothing but the
+    # invalidate_obs() below tells the env -- and nothing at all in the known_zero start
+    version = obs._version
+    win = obs.data.view(N, P, -1)[:, :, :3 * R * R].view(N, P, 3, R, R)
+    sel = torch.as_tensor(board, device=DEV)
+    win[:, :, 1:3, sel] = 7.0
+    win[:, :, 1:3, sel] = fill
+    assert obs._version == version
+    if start == "nothing_known":
+        env.invalidate_obs()
+    rng = np.random.RandomState(5)
+    tstep = np.zeros(N, np.int64)
+    n_resets = np.zeros(N, np.int64)
+    sevens = {}
+    for t in range(T):
+        act = rng.randint(5, size=(N, P))
+        obs, rew, done, info = env.step(torch.as_tensor(act, device=DEV))
+        oobs, orew, odone, orem = orc.step(act)
+        tstep += 1
+        bits = odone.astype(np.uint8) | ((tstep >= H).astype(np.uint8) << 1)
+        assert np.array_equal(info["done_bits"].cpu().numpy(), bits), "step %d done bits" % t
+        assert np.array_equal(info["removed"].cpu().numpy(), orem), "step %d removed" % t
+        assert np.array_equal(rew.cpu().numpy(), orew.astype(np.float32)), "step %d rewards" % t
+        mask = (bits != 0).astype(np.uint8)
+        if mask.any():
+            orc.reset(mask=mask)
+            tstep[mask != 0] = 0
+            n_resets += mask
+        got = obs.reshape(orc.obs.shape).cpu().numpy()
+        assert np.array_equal(got, orc.obs), "step %d obs: %d cells differ" % (t, int((got != orc.obs).sum()))
+        sevens[t + 1] = int((orc.obs == 7.0).sum())
+    _cmp_state(env.get_state(), orc.get_state(), "end")
+    assert bool((n_resets >= 2).all())
+    if start == "nothing_known":
+        assert sevens[10] > 0, sevens
+        if R >= 7:
+            quads = orc.obs.reshape(N, P, -1, 4)
+            mixed = int(((quads == 7.0).any(-1) & (quads != 7.0).any(-1)).sum())
+            assert sevens[T] > 0 and mixed > 0, (sevens, mixed)
+    else:
+        assert sevens[T] == 0
+
+
+@pytest.mark.parametrize("shape", ["c2_wave", "c5_group", "group_44v64", "group_64v40"])
 def test_bit31_of_the_alive_and_terminal_masks(shape):
     """Evader slot 31 gone / agent 31 terminal: bit 31 of a record word must not leak into the upper half of the
-    64-bit wave masks (v_readlane returns a signed int).  Fast path against the generic kernel from the same state."""
+    64-bit wave masks (v_readlane returns a signed int).  Fast path against the generic kernel from the same state.
+    group_44v64 / group_64v40: the same at the top of the masks and of the record -- the last evader slot gone and terminal (44 v 64:
+    slot 63, bit 63 of the alive mask), agents 63 and 64 (the last lane of wavefront 0, the first of wavefront 1) and the last agent
+    terminal; with 108 and 104 agents the terminal words sit in the record's last dwords (lanes 60 - 63 and 58 - 61 of the 64 the record
+    load fills).  set_state keeps no terminal flag for an evader that is gone, so the last slot is gone in the even envs and terminal in
+    the odd ones."""
     from madrl_amd.maps import rectangle_map
+    R = 7
     if shape == "c2_wave":
         maps, P, E = [rectangle_map(16, 16)], 8, 30
-    else:
+    elif shape == "c5_group":
         maps, P, E = [rectangle_map(32, 32)], 16, 60
+    else:
+        maps, (P, E), R = [rectangle_map(16, 16)], ((44, 64) if shape == "group_44v64" else (64, 40)), 3
     N = 64
-    kw = dict(n_pursuers=P, n_evaders=E, obs_range=7, n_catch=2, surround=True, flatten=True, seed=4)
+    kw = dict(n_pursuers=P, n_evaders=E, obs_range=R, n_catch=2, surround=True, flatten=True, seed=4)
     envs = [_mk(maps, N, kernel=k, **kw) for k in ("generic", "wave")]
     for env in envs:
         env.reset()
         st = env.get_state()
         gone = torch.zeros((N, E), dtype=torch.uint8)
         term_e = torch.zeros((N, E), dtype=torch.uint8)
+        term_p = torch.zeros((N, P), dtype=torch.uint8)
         if E > 31:
             gone[:, 31] = 1
-        term_e[:, 31 - P] = 1            # agent index 31
+        if P > 31:
+            term_p[:, 31] = 1            # agent index 31
+        else:
+            term_e[:, 31 - P] = 1
         if P + E > 64:
             term_e[:, 95 - P if 95 - P < E else E - 1] = 1
             gone[:, E - 1] = 1
-        env.set_state(dict(gone=gone, term_e=term_e))
+        if shape.startswith("group_"):
+            gone[1::2, E - 1] = 0        # the last slot: gone in the even envs, terminal in the odd ones
+            for a in (63, 64, P + E - 1):   # agents 63, 64 and the last one
+                if a < P:
+                    term_p[:, a] = 1
+                else:
+                    term_e[:, a - P] = 1
+        env.set_state(dict(gone=gone, term_e=term_e, term_p=term_p))
     g = torch.Generator(device="cpu").manual_seed(3)
     for t in range(12):
         act = torch.randint(0, 5, (N, P), generator=g, dtype=torch.int32).to(DEV)
@@ -226,7 +354,11 @@ def test_bit31_of_the_alive_and_terminal_masks(shape):
         sa, sb = envs[0].get_state(), envs[1].get_state()
         for k in sa:
             assert torch.equal(sa[k], sb[k]), "step %d state[%s]" % (t, k)
-    assert bool(sa["term_e"][:, 31 - P].all()) and (E <= 31 or bool(sa["gone"][:, 31].all()))
+    assert bool((sa["term_e"][:, 31 - P] if P <= 31 else sa["term_p"][:, 31]).all()) and (E <= 31 or bool(sa["gone"][:, 31].all()))
+    if shape.startswith("group_"):   # (a terminal evader stands still and may be caught: gone then, and its flag reads 0)
+        held = lambda k: sa["term_e"][:, k] | sa["gone"][:, k]
+        assert bool(sa["gone"][::2, E - 1].all()) and bool(held(E - 1)[1::2].all()) and bool(sa["term_e"][1::2, E - 1].any())
+        assert bool(held(64 - P).all()) and bool((sa["term_p"][:, 63] if P == 64 else held(63 - P)).all())
 
 
 def test_launch_shape_does_not_change_results():

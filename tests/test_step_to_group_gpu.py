@@ -35,6 +35,13 @@ CASES = {
     "XLG_authors_30v30": ((32, 32), True, dict(n_pursuers=30, n_evaders=30, per_env_counts=True, **AUTHORS), _counts(30, 30), {}),
     "XLG_20v50": ((16, 16), False, dict(n_pursuers=20, n_evaders=50, obs_range=5, flatten=True, per_env_counts=True), _counts(20, 50), {}),
 }
+# long rows past the authors' two mask words, on rectangle_map (the last XG lines of csrc/pursuit_to_specializations.def): a mask word of
+# 5 slots (a remainder batch of 1 after one batch of MADRL_PG_TO_BATCH = 4), one of 7 (a remainder batch of 3), and the limit: 32 slots,
+# four mask words, 64 pursuers
+CASES["XG_13_slots_36v12"] = ((10, 10), False, dict(n_pursuers=36, n_evaders=12, obs_range=11, flatten=True, surround=False, n_catch=2), None, {})
+CASES["XG_23_slots_46v10"] = ((12, 12), False, dict(n_pursuers=46, n_evaders=10, obs_range=13, flatten=True, surround=False, n_catch=2), None, {})
+CASES["XG_32_slots_64v20"] = ((12, 12), False, dict(n_pursuers=64, n_evaders=20, obs_range=13, flatten=True, surround=False, n_catch=2,
+                                                    reward_mech="global"), None, {})
 CASES["XG_authors_30v50_global"] = CASES["XG_authors_30v50"][:2] + (dict(CASES["XG_authors_30v50"][2], reward_mech="global"), None, {})
 CASES["XLG_20v50_global"] = CASES["XLG_20v50"][:2] + (dict(CASES["XLG_20v50"][2], reward_mech="global"), _counts(20, 50), {})
 CASES["XG_c5_16v60_evader_actions"] = CASES["XG_c5_16v60"][:4] + (dict(evader_actions=True),)
