@@ -93,7 +93,9 @@ int madrl_pursuit_obs_dim(const madrl_pursuit_config *cfg, int32_t *out_dim);
  * reference's constructor state -- every agent at (0,0) on map 0, pursuit_evade.py:69-75).
  * Layout: n_envs packed records of madrl_pursuit_record_bytes() each, padding to 256 bytes, then -- for shapes with a
  * compiled fast path -- the stale-zero masks of that path (256 bytes per env, wavefront and mask word, see obs_dev below), then the
- * flag plane (one dword per env, madrl_pursuit_flags_offset).
+ * flag plane (one dword per env, madrl_pursuit_flags_offset).  A one-wavefront flatten shape whose lanes each own at most four float4
+ * slots with a channel-1 / 2 cell (and at most five slots) keeps 16 mask bits per lane: its kernels use the first n_envs * 128 bytes of
+ * the mask region and never touch the rest; the region's size and the flag plane's offset are the same either way.
  * Everything the library knows about an env lives in this buffer and in the observation buffer: copying both clones it. */
 int madrl_pursuit_state_bytes(const madrl_pursuit_config *cfg, int64_t n_envs, uint64_t *out_bytes);
 /* Byte offset, inside the state buffer, of the FLAG PLANE: uint32 [n_envs], written by every step launch next to done_dev.

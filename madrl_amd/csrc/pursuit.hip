@@ -626,7 +626,9 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, const float *obs_pre
 
 // caller-owned state buffer = [n_envs packed records][pad to 256 B][what the configuration's fast path remembers about the observation
 // buffer (FastEntry::mask_bytes per env): stale-zero masks, 256 B per wavefront and mask word, or the crowd kernel's one word][flag plane,
-// one dword per env]
+// one dword per env].  The one-wavefront kernels of a pw::Shape with ZM16 (pursuit_zm16.hpp: 16 mask bits per lane) read and write only the
+// first n_envs * 128 bytes of the mask region, [n_envs][32] dwords; the region keeps its 256 B per env -- sizes and offsets are part of the
+// ABI -- and the memsets below (0xFF = nothing known, 0 = known zero: the same polarity in both forms) keep covering all of it.
 uint64_t zmask_offset(int rec_bytes, int64_t n_envs) { return align_up((uint64_t)rec_bytes * (uint64_t)n_envs, 256); }
 uint64_t flags_offset(const madrl_pursuit_config *cfg, int rec_bytes, int64_t n_envs) { return zmask_offset(rec_bytes, n_envs) + zmask_len(find_fast(cfg), n_envs); }
 

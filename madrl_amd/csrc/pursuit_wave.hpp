@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "pursuit_zm16.hpp"
 
 namespace madrl {
 namespace pw {
@@ -65,7 +66,8 @@ struct WaveDev {
     const double *catchr_env;  // (constant address space): written by the host or an earlier launch, never by these kernels
     uint8_t *state;
     uint32_t *flags;         // [n_envs] flag words of the step launches (done_flag_word, common.hpp)
-    uint32_t *zmask;         // [n_envs][64]: per lane, which of its observation cells hold a NON-ZERO stale value (see "stale-zero mask")
+    uint32_t *zmask;         // [n_envs][64]: per lane, which of its observation cells hold a NON-ZERO stale value (see "stale-zero mask");
+                             // S::ZM16 shapes: [n_envs][32], 16 bits per lane (pursuit_zm16.hpp), the first half of the same region
 };
 
 struct WaveIO {
@@ -116,6 +118,8 @@ struct Shape {
     static constexpr int NQ = P * DV;                            // float4 slots per env
     static constexpr int NS = (NQ + 63) / 64;                    // slots per lane
     static constexpr int MWORDS = 1;                             // stale-zero mask dwords per lane
+    static constexpr bool ZM16 = zm16::eligible(P, R, FLATTEN);  // the masks are kept as 16 bits per lane (pursuit_zm16.hpp)
+    static constexpr int ZMW = ZM16 ? 32 : 64;                   // mask dwords per env
     static constexpr int OCC = NS <= 5 ? MADRL_PW_WAVES : (MADRL_PW_WAVES < 4 ? MADRL_PW_WAVES : 4);  // resident wavefronts per SIMD aimed at
     static constexpr int X_FILL = 3 * GSZ;                       // extras after the layers
     static constexpr int X_SKIP = 3 * GSZ + 1;
@@ -396,6 +400,9 @@ constexpr int FILL_FIRST = 56, FILL_BATCH = 16;
 //   1 no observation stores   2 store stale cells too (all float4 full, nt)   4 no Philox
 //   8 no observation pass at all   16 no record / reward stores
 //   64 no record prefetch (timing only, wrong results)   128 20 dependent SALU more per observation slot (results unchanged)
+//   256 every env's stale-zero mask at the address of env & 255: the mask traffic stays in L2 (timing only, wrong results)
+//   512 no mask traffic: the masks are read at env & 255 (never written: they stay in L2) and not stored, every float4 stored whole as
+//       with 2 -- against 2 this prices the mask bytes alone (timing only, wrong results)
 #ifndef MADRL_ABLATE
 #define MADRL_ABLATE 0
 #endif
@@ -413,6 +420,8 @@ constexpr int FILL_FIRST = 56, FILL_BATCH = 16;
 // (value != 0), a cell outside keeps it.  A slot is stored as ONE non-temporal float4, zeros in its outside cells, unless an
 // outside cell's bit is set; only those slots (about 3 % instead of 19 %) fall back to masked dword stores.  All bits set =
 // "nothing known" is always correct: the library starts there and returns there whenever the caller hands it another buffer.
+// S::ZM16 shapes keep the same dword in registers but 16 bits per lane in memory (pursuit_zm16.hpp): [env][32] dwords, lane l < 32 stores
+// its own half and lane l + 32's, every lane loads dword l & 31 and unpacks its half -- 128 B read and written per env instead of 256 B.
 //
 // MODE 0: reset(mask)      MODE 1: step (+ fused auto-reset)
 // INJECT (step only) = the FLEXIBLE instantiation: evader actions come from io.inj_eact when it is given (parity harness)
@@ -453,6 +462,11 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
     const int n_envs = (int)d.n_envs, stride = (int)gridDim.x;  // env indices are 32-bit (the C ABI caps n_envs below 2^31); only byte offsets are 64-bit
     if (n_envs <= 0) return;
     auto phys = [&](int e) -> int64_t { return (int64_t)(d.reverse ? n_envs - 1 - e : e); };
+    // the env whose mask words an env reads and writes: its own
+    auto zm_env = [](int64_t env) -> int64_t { return (MADRL_ABLATE & (256 | 512)) ? (env & 255) : env; };
+    // the dword of an env's masks a lane loads: its own -- or, 16 bits per lane, the one it shares with lane +- 32
+    const uint32_t zm_lane = S::ZM16 ? (ulane & 31u) : ulane;
+    [[maybe_unused]] const uint32_t zm_keep = S::ZM16 ? zm16::keep_low(P, S::R, lane) : 0u;   // which bit position the lane's 16 bits leave out
     const uint32_t *const vtab_u = reinterpret_cast<const uint32_t *>(d.vtab);
     constexpr int ROOM = FILL_FIRST - 6 * NS - 3;
     constexpr int JF = F::J_END < (ROOM > 4 ? ROOM : 4) ? F::J_END : (ROOM > 4 ? ROOM : 4);
@@ -471,7 +485,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
         const int64_t env0 = phys((int)blockIdx.x < n_envs ? (int)blockIdx.x : n_envs - 1);
         cur_rec = *reinterpret_cast<const uint32_t *>(d.state + env0 * (int64_t)S::REC_BYTES + rec_off);
         if constexpr (MODE == 1) cur_act = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(io.actions + env0 * P) + act_off);
-        cur_zm = d.zmask[env0 * 64 + ulane];
+        cur_zm = d.zmask[zm_env(env0) * S::ZMW + zm_lane];
     }
     asm volatile("" : "+v"(cur_rec), "+v"(cur_act), "+v"(cur_zm));  // the loads issued last: the one wait, vmcnt(0), of the whole batch
     staged_wait<6 * NS>(sraw);
@@ -513,7 +527,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
         if constexpr (MODE == 1) return isP() ? uniform_ptr(io.actions + env * P)[ulane] : 4;
         else return 4;
     };
-    auto fetch_zm = [&](int64_t env) -> uint32_t { return uniform_ptr(d.zmask + env * 64)[ulane]; };
+    auto fetch_zm = [&](int64_t env) -> uint32_t { return uniform_ptr(d.zmask + zm_env(env) * S::ZMW)[zm_lane]; };
     wave_sync();
 #if MADRL_PW_EXP & 8
     if (d.n_envs > 0) { if (s_cst[0][0] + s_cst[NS - 1][3] + s_rel3[0] + s_src[NS - 1] + (int)cur_rec == 0x12345) io.rew[0] = 1.f; return; }
@@ -522,7 +536,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
     // PIPE: the exact-wait prefetch above (production step kernel); the reset kernel (envs may be skipped) and the parity
     // harness variant keep compiler-managed loads and the mid-iteration hinge.
     constexpr bool PIPE = (MODE == 1) && !INJECT && !(MADRL_ABLATE & (1 | 8 | 16 | 64));
-    constexpr int VM_PER_ENV = 5 * NS + 6;  // stores every step iteration issues: NS x (4 dword + 1 float4), reward, done, removed, flag word, record, mask
+    constexpr int VM_PER_ENV = 5 * NS + 6 - ((MADRL_ABLATE & 512) ? 1 : 0);  // stores every step iteration issues: NS x (4 dword + 1 float4), reward, done, removed, flag word, record, mask
     static_assert(!PIPE || VM_PER_ENV < 64, "vmcnt range");
     for (int e = blockIdx.x; e < n_envs; e += stride) {
         const int64_t env = phys(e);
@@ -533,7 +547,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
         uint32_t pf_rec, pf_act, pf_zm;
         if constexpr (PIPE) {
             prefetch3(pf_rec, pf_act, pf_zm, d.state + nenv * (int64_t)S::REC_BYTES, rec_off, io.actions + nenv * P, act_off,
-                      d.zmask + nenv * 64, ulane * 4u);
+                      d.zmask + zm_env(nenv) * S::ZMW, zm_lane * 4u);
         } else {
 #if MADRL_ABLATE & 64
             nxt_rec = cur_rec ^ (uint32_t)(fresh(lane) == 0);  // no loads in the loop: is the in-order vmcnt drain what serialises a wave?
@@ -710,6 +724,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
             // vmcnt(0) would also wait for this env's observation stores to reach HBM.
             if constexpr (!PIPE) asm volatile("" : "+v"(nxt_rec), "+v"(nxt_act), "+v"(nxt_zm));
             uint32_t zm = cur_zm;  // stale-zero mask of this env: byte k, bit (4 - s) = cell k of slot s
+            if constexpr (S::ZM16) zm = zm16::unpack(fresh(lane) < 32 ? cur_zm : cur_zm >> 16, zm_keep);  // (cur_zm: as loaded, two lanes' halves)
 
             // One observation pass normally.  On auto-reset two: the reference sequence is step()
             // then reset(), both write the persistent observation buffer and the cells the second
@@ -872,7 +887,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
 #if MADRL_ABLATE & 1
                         valid = d.n_envs < 0;
 #endif
-#if MADRL_ABLATE & 2
+#if MADRL_ABLATE & (2 | 512)
                         clean = true;
 #endif
                         // The lane's part of the slot as one integer, so that every store mask below is ONE vector compare (a lane mask
@@ -1026,7 +1041,16 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
 #if MADRL_ABLATE & 16
                 if (d.n_envs < 0)
 #endif
-                uniform_ptr(d.zmask + env * 64)[ulane] = zm;
+#if !(MADRL_ABLATE & 512)
+                if constexpr (S::ZM16) {
+                    // 16 bits per lane: lane l < 32 stores its own half and lane l + 32's, ONE 128-byte line per env
+                    const uint32_t h = zm16::pack(zm, zm_keep);
+                    const uint32_t other = __builtin_amdgcn_permlane32_swap(h, h, false, false)[1];   // lanes 0..31: lane + 32's h
+                    if (fresh(lane) < 32) uniform_ptr(d.zmask + zm_env(env) * S::ZMW)[ulane] = h | (other << 16);
+                } else {
+                    uniform_ptr(d.zmask + zm_env(env) * 64)[ulane] = zm;
+                }
+#endif
             }
         }
         if constexpr (PIPE) {
