@@ -29,6 +29,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "pursuit_rules.hpp"
 
 namespace madrl {
 namespace pc {

@@ -3,9 +3,8 @@
 //   pursuit_live_crowd_kernel<LCShape, MODE>  (S::LIVE = true): per-env agent counts within the capacity (P, E)
 //   pursuit_crowd_to_kernel<S>                (TO = true, MODE = 1): the two-buffer step of madrl_pursuit_step_to (see write_obs)
 // In scope: S, MODE, TO, d (CrowdDev), io (CrowdIO), pending (int32 [n_envs][2] or nullptr), obs_prev (TO; nullptr otherwise).
-// S::LIVE follows the LIVE branches of pursuit_generic.inc: a slot that does not exist has position bytes NOT_HERE (an evader slot the gone
-// bit too), it is never placed in, moved over or taken from the cells, pursuers >= np get no row and a 0 reward, and a reset takes (np, ne)
-// from `pending` and numbers its draws in the live layout.
+// The environment's rules are pursuit_rules.hpp's.  S::LIVE follows pursuit_generic.inc: a slot that does not exist has position bytes NOT_HERE
+// (an evader slot the gone bit too), is never placed in, moved over or taken from the cells, and pursuers >= np get no row and a 0 reward.
     constexpr int P = S::P, E = S::E, A = S::A, GW = S::GW, PAD = S::PAD, GSZ = S::GSZ, NT = S::NT, D = S::D, DV = S::DV, NQ = S::NQ;
     constexpr int R = S::R, OFF = S::OFF, NGW = S::NGW, NTW = S::NTW;
     __shared__ __attribute__((aligned(16))) uint32_t L[S::LDS_DWORDS];
@@ -317,10 +316,7 @@
                     k += (i & 31) - __popc(s_gone[i >> 5] & ((1u << (i & 31)) - 1u));
                     if (io.inj_eact != nullptr) {
                         act = io.inj_eact[env * E + k];
-                    } else {
-                        const u32x4 r = philox4x32_10(gid, tick, (uint32_t)k, TAG_EVADER_ACT, d.k0, d.k1);
-                        act = (int)__umulhi(r.x, 5u);  // RandomPolicy.act, Controllers.py:15-16
-                    }
+                    } else act = pr::evader_action(gid, tick, (uint32_t)k, d.k0, d.k1);
                 }
                 // DiscreteAgent.step, DiscreteAgent.py:69-97
                 const bool term = (s_term[a >> 5] >> (a & 31)) & 1u;
@@ -386,9 +382,7 @@
                     }
                 }
                 const uint32_t sur = (cell[(s_ax[p] + PAD) * GW + s_ay[p] + PAD] >> 24) & 1u;
-                double r = catchr * (double)s_kpre[p];
-                r += d.term_pursuit * (sur ? 1.0 : 0.0);
-                r += d.urgency;
+                const double r = pr::pursuer_reward(catchr, s_kpre[p], d.term_pursuit, sur, d.urgency);
                 if (d.reward_global) s_rew[p] = r;
                 else io.rew[env * P + p] = (float)r;
             }
@@ -406,8 +400,7 @@
             }
             tick += 1;
             tstep += 1;
-            if (n_alive == 0) done_bits |= 1u;                               // :383-389
-            if (d.max_steps > 0 && tstep >= d.max_steps) done_bits |= 2u;
+            done_bits = pr::done_bits(n_alive == 0, d.max_steps, tstep);
             const uint32_t overflow = s_misc[3] ? 0x80u : 0u;                // a cell's count left the byte range: results void
             if (tid == 0) {
                 io.done[env] = (uint8_t)(done_bits | overflow);
@@ -425,33 +418,17 @@
                 if (tid == 0) s_misc[3] = 0u;                         // a new episode: the overflow mark goes
                 for (int w = tid; w < NGW; w += NT) s_gone[w] = 0u;   // :175-176
                 for (int w = tid; w < NTW; w += NT) s_term[w] = 0u;   // fresh agents
-                if (io.inj_map != nullptr && MODE == 0) {
-                    map_id = io.inj_map[env];
-                } else if (d.sample_maps) {  // :182-183
-                    const u32x4 r = philox4x32_10(gid, tick, 0u, TAG_RESET_ENV, d.k0, d.k1);
-                    map_id = (int)__umulhi(r.x, (uint32_t)d.n_maps);
-                }
+                if (io.inj_map != nullptr && MODE == 0) map_id = io.inj_map[env];
+                else if (d.sample_maps) map_id = pr::reset_map_id(gid, tick, d.k0, d.k1, d.n_maps);
                 load_map(map_id);
-                // constraint window (:185-191), float64 like the reference
-                const u32x4 rw = philox4x32_10(gid, tick, 1u, TAG_RESET_ENV, d.k0, d.k1);
-                const double cw = d.cw_env ? d.cw_env[env] : d.cw;
-                const double sx = u53(rw.x, rw.y) * (1.0 - cw);
-                const double sy = u53(rw.z, rw.w) * (1.0 - cw);
-                const int xlb = (int)(S::XS * sx), xub = (int)(S::XS * (sx + cw));
-                const int ylb = (int)(S::YS * sy), yub = (int)(S::YS * (sy + cw));
-                // random_opponents (:177-181): this episode has n_create <= E evaders; the slots above are not created and count as gone.
-                // An injected position with x < 0 marks a slot that is not created.
-                const bool inj = io.inj_pos != nullptr && MODE == 0;
+                const pr::Window win = pr::reset_window(gid, tick, d.k0, d.k1, d.cw_env ? d.cw_env[env] : d.cw, S::XS, S::YS);
+                const bool inj = io.inj_pos != nullptr && MODE == 0;   // (an injected position with x < 0 marks an evader slot that is not created)
                 int n_create = E;
-                if constexpr (S::LIVE) {  // the pending counts take effect (clamped: the caller's array is not trusted with LDS indices)
-                    np = min(max(uniform_ptr(pending + 2 * env)[0], 1), P);
-                    ne = min(max(uniform_ptr(pending + 2 * env)[1], 0), E);
-                    n_create = ne;
+                if constexpr (S::LIVE) {  // the pending counts take effect
+                    const pr::Counts live = pr::clamp_pending(uniform_ptr(pending + 2 * env)[0], uniform_ptr(pending + 2 * env)[1], P, E);
+                    np = live.np, ne = n_create = live.ne;
                 }
-                if (d.max_opponents > 0 && !inj) {
-                    const u32x4 r3 = philox4x32_10(gid, tick, 2u, TAG_RESET_ENV, d.k0, d.k1);
-                    n_create = min(1 + (int)__umulhi(r3.x, (uint32_t)(d.max_opponents - 1)), S::LIVE ? ne : E);
-                }
+                if (d.max_opponents > 0 && !inj) n_create = pr::reset_n_create(gid, tick, d.k0, d.k1, d.max_opponents, S::LIVE ? ne : E);
                 group_sync();
                 for (int a = tid; a < A; a += NT) {  // create_agents, agent_utils.py:12-28
                     int x = 0, y = 0;
@@ -476,13 +453,10 @@
                         x = min(max(x, 0), S::XS - 1);
                         y = min(max(y, 0), S::YS - 1);
                     } else {
-                        // feasible_position: rejection sampling (agent_utils.py:37-47); bounded
-                        for (uint32_t att = 0; att < 1024u; ++att) {
-                            // (LIVE: the agent's index in the live layout, evader i = agent np + i)
-                            const uint32_t aidx = S::LIVE && a >= P ? (uint32_t)(np + a - P) : (uint32_t)a;
-                            const u32x4 r = philox4x32_10(gid, tick, aidx, TAG_RESET_POS | (att << 8), d.k0, d.k1);
-                            x = xlb + (int)__umulhi(r.x, (uint32_t)(xub - xlb));
-                            y = ylb + (int)__umulhi(r.y, (uint32_t)(yub - ylb));
+                        for (uint32_t att = 0; att < 1024u; ++att) {   // bounded, like the oracle's
+                            const uint32_t aidx = S::LIVE ? pr::live_agent_index(a, P, np) : (uint32_t)a;
+                            const pr::Cell c = pr::reset_cell(gid, tick, aidx, att, d.k0, d.k1, win);
+                            x = c.x, y = c.y;
                             if ((cell[(x + PAD) * GW + y + PAD] & 0xFFu) != 1u) break;
                         }
                     }

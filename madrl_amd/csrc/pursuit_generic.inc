@@ -4,7 +4,7 @@
 //   pursuit_to_kernel<NT, LIVE>  (TO = true): the two-buffer step of madrl_pursuit_step_to -- the step's rows go to io.obs, the cells an
 //                            in-place step leaves alone come from obs_prev (see write_obs)
 // It is included rather than called because a __device__ function between the kernel and its body changes the code the compiler
-// emits for pursuit_kernel<NT> (its passes see the body on its own before inlining it), and that kernel's code stays as it is.
+// emits for pursuit_kernel<NT> (its passes see the body on its own before inlining it).  The environment's rules are pursuit_rules.hpp's.
 // In scope: NT, LIVE, TO, d (PursuitDev), io (PursuitIO), mode, pending (int32 [n_envs][2] or nullptr), obs_prev (TO; nullptr otherwise).
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x;
@@ -277,10 +277,7 @@
                         act = io.actions[env * d.P + a];
                     } else if (io.inj_eact != nullptr) {
                         act = io.inj_eact[env * d.E + k];
-                    } else {
-                        const u32x4 r = philox4x32_10(gid, tick, (uint32_t)k, TAG_EVADER_ACT, d.k0, d.k1);
-                        act = (int)__umulhi(r.x, 5u);  // RandomPolicy.act, Controllers.py:15-16
-                    }
+                    } else act = pr::evader_action(gid, tick, (uint32_t)k, d.k0, d.k1);
                 } else {
                     // evader control (:215-224): action k moves the k-th agent of the evader layer (`for i, a in enumerate(actions):
                     // agent_layer.move_agent(i, a)`, :229-230; the caller passes one action per env.agents entry = n_pursuers of
@@ -290,10 +287,7 @@
                         act = k < d.P ? io.actions[env * d.P + k] : 4;
                     } else if (io.inj_eact != nullptr) {
                         act = io.inj_eact[env * d.P + a];
-                    } else {
-                        const u32x4 r = philox4x32_10(gid, tick, (uint32_t)a, TAG_PURSUER_ACT, d.k0, d.k1);
-                        act = (int)__umulhi(r.x, 5u);
-                    }
+                    } else act = pr::pursuer_action(gid, tick, (uint32_t)a, d.k0, d.k1);
                 }
                 // DiscreteAgent.step, DiscreteAgent.py:69-97
                 const bool term = (s_term[a >> 5] >> (a & 31)) & 1u;
@@ -359,9 +353,7 @@
                 }
                 const int sur = g_cr[(s_ax[p] + pad) * GW + s_ay[p] + pad];
                 const double catchr = d.catchr_env ? d.catchr_env[env] : d.catchr;
-                double r = catchr * (double)s_kpre[p];
-                r += d.term_pursuit * (sur ? 1.0 : 0.0);
-                r += d.urgency;
+                const double r = pr::pursuer_reward(catchr, s_kpre[p], d.term_pursuit, sur, d.urgency);
                 if (d.reward_global) s_rew[p] = r;
                 else io.rew[env * d.P + p] = (float)r;
             }
@@ -374,8 +366,7 @@
             }
             tick += 1;
             tstep += 1;
-            if (n_alive == 0) done_bits |= 1u;                               // :383-389
-            if (d.max_steps > 0 && tstep >= d.max_steps) done_bits |= 2u;
+            done_bits = pr::done_bits(n_alive == 0, d.max_steps, tstep);
             const uint32_t overflow = s_misc[3] ? 0x80u : 0u;                // a cell's count left the byte range: results void
             if (tid == 0) {
                 io.done[env] = (uint8_t)(done_bits | overflow);
@@ -397,12 +388,8 @@
             if (tid == 0) s_misc[3] = 0u;                            // a new episode: the overflow mark goes
             for (int w = tid; w < d.ngw; w += nthr) s_gone[w] = 0u;  // :175-176
             for (int w = tid; w < d.ntw; w += nthr) s_term[w] = 0u;  // fresh agents
-            if (io.inj_map != nullptr && mode == 0) {
-                map_id = io.inj_map[env];
-            } else if (d.sample_maps) {  // :182-183
-                const u32x4 r = philox4x32_10(gid, tick, 0u, TAG_RESET_ENV, d.k0, d.k1);
-                map_id = (int)__umulhi(r.x, (uint32_t)d.n_maps);
-            }
+            if (io.inj_map != nullptr && mode == 0) map_id = io.inj_map[env];
+            else if (d.sample_maps) map_id = pr::reset_map_id(gid, tick, d.k0, d.k1, d.n_maps);
             {
                 const uint32_t *mt = reinterpret_cast<const uint32_t *>(d.maps + (int64_t)map_id * d.map_stride);
                 const uint32_t *ct = reinterpret_cast<const uint32_t *>(d.cnt_tmpl);
@@ -414,26 +401,14 @@
                 }
                 cached_map = map_id;
             }
-            // constraint window (:185-191), float64 like the reference
-            const u32x4 rw = philox4x32_10(gid, tick, 1u, TAG_RESET_ENV, d.k0, d.k1);
-            const double cw = d.cw_env ? d.cw_env[env] : d.cw;
-            const double sx = u53(rw.x, rw.y) * (1.0 - cw);
-            const double sy = u53(rw.z, rw.w) * (1.0 - cw);
-            const int xlb = (int)(d.xs * sx), xub = (int)(d.xs * (sx + cw));
-            const int ylb = (int)(d.ys * sy), yub = (int)(d.ys * (sy + cw));
-            // random_opponents (train_pursuit, :177-181): this episode has n_create <= E evaders; the slots above are not
-            // created and count as gone.  An injected position with x < 0 marks a slot that is not created.
-            const bool inj = io.inj_pos != nullptr && mode == 0;
+            const pr::Window win = pr::reset_window(gid, tick, d.k0, d.k1, d.cw_env ? d.cw_env[env] : d.cw, d.xs, d.ys);
+            const bool inj = io.inj_pos != nullptr && mode == 0;   // (an injected position with x < 0 marks an evader slot that is not created)
             int n_create = d.E;
-            if constexpr (LIVE) {  // the pending counts take effect (clamped: the caller's array is not trusted with LDS indices)
-                np = min(max(pending[2 * env], 1), d.P);
-                ne = min(max(pending[2 * env + 1], 0), d.E);
-                n_create = ne;
+            if constexpr (LIVE) {  // the pending counts take effect
+                const pr::Counts live = pr::clamp_pending(pending[2 * env], pending[2 * env + 1], d.P, d.E);
+                np = live.np, ne = n_create = live.ne;
             }
-            if (d.max_opponents > 0 && !inj) {
-                const u32x4 r3 = philox4x32_10(gid, tick, 2u, TAG_RESET_ENV, d.k0, d.k1);
-                n_create = min(1 + (int)__umulhi(r3.x, (uint32_t)(d.max_opponents - 1)), LIVE ? ne : d.E);
-            }
+            if (d.max_opponents > 0 && !inj) n_create = pr::reset_n_create(gid, tick, d.k0, d.k1, d.max_opponents, LIVE ? ne : d.E);
             __syncthreads();
             for (int a = tid; a < d.A; a += nthr) {  // create_agents, agent_utils.py:12-28
                 int x = 0, y = 0;
@@ -453,13 +428,10 @@
                     x = io.inj_pos[(env * d.A + a) * 2];
                     y = io.inj_pos[(env * d.A + a) * 2 + 1];
                 } else {
-                    // feasible_position: rejection sampling (agent_utils.py:37-47); bounded
-                    for (uint32_t att = 0; att < 1024u; ++att) {
-                        // (LIVE: the agent's index in the live layout, evader i = agent np + i)
-                        const uint32_t aidx = LIVE && a >= d.P ? (uint32_t)(np + a - d.P) : (uint32_t)a;
-                        const u32x4 r = philox4x32_10(gid, tick, aidx, TAG_RESET_POS | (att << 8), d.k0, d.k1);
-                        x = xlb + (int)__umulhi(r.x, (uint32_t)(xub - xlb));
-                        y = ylb + (int)__umulhi(r.y, (uint32_t)(yub - ylb));
+                    for (uint32_t att = 0; att < 1024u; ++att) {   // bounded, like the oracle's
+                        const uint32_t aidx = LIVE ? pr::live_agent_index(a, d.P, np) : (uint32_t)a;
+                        const pr::Cell c = pr::reset_cell(gid, tick, aidx, att, d.k0, d.k1, win);
+                        x = c.x, y = c.y;
                         if (g_map[(x + pad) * GW + y + pad] != 1) break;
                     }
                 }

@@ -1,10 +1,8 @@
 // pursuit_group.hpp -- compile-time-specialised PursuitEvade kernel for shapes with MORE THAN 64 AGENTS:
 // one workgroup of NW wavefronts = one env (BASELINE configs[4]: 32x32, 16 pursuers / 60 evaders).
 //
-// Same scheme as pursuit_wave.hpp (read that header first): one lane per agent, padded dword layers in LDS,
-// counts converted in place to their float32 observation values, float4 observation slots with non-temporal
-// stores, one coalesced dword load / store of the packed state record, prefetch one env ahead with the pipeline
-// hinge.  What changes when the agents of an env no longer fit one wavefront:
+// The scheme is pursuit_wave.hpp's (read that header first) and the environment's rules are pursuit_rules.hpp's, where calling them
+// leaves the kernels bench.py runs as they were.  What changes when the agents of an env no longer fit one wavefront:
 //   * thread t = agent t (pursuers first): the agents occupy the first NAW = ceil(A / 64) wavefronts; the
 //     observation row is dealt over ALL NW wavefronts (slot q -> thread q % (64 NW)), so a wavefront without
 //     agents still carries its share of the row;
@@ -304,8 +302,8 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
             int32_t tstep = (int32_t)__builtin_amdgcn_readlane(cur_rec, 1);
             int32_t map_id = (int32_t)__builtin_amdgcn_readlane(cur_rec, 2);
             const uint32_t xyw = (uint32_t)__shfl((int)cur_rec, (4 + (tid >> 1)) & 63);
-            const uint32_t xy = (tid & 1) ? (xyw >> 16) : (xyw & 0xFFFFu);
-            int x = (int)(xy & 0xFF), y = (int)(xy >> 8);
+            const pr::Cell at = pr::unpack_xy(xyw, tid & 1);
+            int x = at.x, y = at.y;
             if (!isAgent()) x = y = 0;  // threads past the last agent keep a harmless in-map cell
             uint64_t gone = (uint32_t)__builtin_amdgcn_readlane(cur_rec, S::OFF_GONE / 4);  // (uint32_t): readlane returns int, bit 31 must not sign-extend
             if constexpr (S::NGW > 1) gone |= (uint64_t)(uint32_t)__builtin_amdgcn_readlane(cur_rec, S::OFF_GONE / 4 + 1) << 32;
@@ -364,10 +362,9 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                 group_sync();
                 int kpre = 0;
                 if (isP()) {
-                    const int dxm = (x > 0) ? GW : 0, dxp = (x < S::XS - 1) ? GW : 0;
-                    const int dym = (y > 0) ? 1 : 0, dyp = (y < S::YS - 1) ? 1 : 0;
+                    const pr::Clip4 n = pr::clipped_neighbours<GW, S::XS, S::YS>(x, y);
                     const uint32_t *ec = &L[2 * GSZ];
-                    kpre = (int)(ec[cell - dxm] + ec[cell + dxp] + ec[cell + dyp] + ec[cell - dym]);
+                    kpre = (int)(ec[cell - n.dxm] + ec[cell + n.dxp] + ec[cell + n.dyp] + ec[cell - n.dym]);
                 }
                 group_sync();
                 if (e_alive) atomicSub(&layer[cell], 1u);
@@ -383,15 +380,14 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                     const u32x4 r = philox4x32_10(gid, tick, (uint32_t)kidx, TAG_EVADER_ACT, k0, k1);
                     if (!isP()) act = (int)__umulhi(r.x, 5u);
                 }
-                const int dcell = (act == 0 ? -GW : 0) + (act == 1 ? GW : 0) + (act == 2 ? 1 : 0) + (act == 3 ? -1 : 0);
+                const int dcell = pr::move_dcell<GW>(act);
                 const bool tflag = (term >> lane) & 1ull;
                 const bool in_building = L[cell] != 0u;
                 const bool target_free = L[cell + dcell] == 0u;
                 const bool newterm = alive && !tflag && in_building;
                 if (alive && !tflag && !in_building && target_free) {
                     cell += dcell;
-                    x += (act == 1) - (act == 0);
-                    y += (act == 2) - (act == 3);
+                    x += pr::move_dx(act), y += pr::move_dy(act);
                 }
                 term |= __ballot(newterm);
                 if (alive) atomicAdd(&layer[cell], 1u);
@@ -400,14 +396,8 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                 bool caught = false;
                 if (e_alive) {
                     const uint32_t *pc = &L[GSZ];
-                    if (d.surround) {
-                        const uint32_t n0 = pc[cell - GW], n1 = pc[cell + GW], n2 = pc[cell + 1], n3 = pc[cell - 1];
-                        const int cnt = (int)(n0 - 1u < SENT - 1u) + (int)(n1 - 1u < SENT - 1u) +
-                                        (int)(n2 - 1u < SENT - 1u) + (int)(n3 - 1u < SENT - 1u);
-                        caught = cnt == (int)need_tab[x * S::YS + y];
-                    } else {
-                        caught = (int)pc[cell] >= d.n_catch;
-                    }
+                    if (d.surround) caught = pr::cells_with_pursuers(pc[cell - GW], pc[cell + GW], pc[cell + 1], pc[cell - 1], SENT) == (int)need_tab[x * S::YS + y];  // :523-540
+                    else caught = (int)pc[cell] >= d.n_catch;
                     if (caught) atomicAdd(&layer[cell], CAUGHT);
                 }
                 const uint64_t caught_mask = evader_mask(caught);  // contains the barrier for the CAUGHT marks
@@ -417,18 +407,11 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                 if (isLP()) {
                     const uint32_t *ec = &L[2 * GSZ];
                     bool sur;
-                    if (d.surround) {
-                        const uint32_t n0 = ec[cell - GW], n1 = ec[cell + GW], n2 = ec[cell + 1], n3 = ec[cell - 1];
-                        sur = ((n0 != SENT) & (n0 >= CAUGHT)) | ((n1 != SENT) & (n1 >= CAUGHT)) |
-                              ((n2 != SENT) & (n2 >= CAUGHT)) | ((n3 != SENT) & (n3 >= CAUGHT));
-                    } else {
-                        sur = ec[cell] >= CAUGHT;
-                    }
+                    if (d.surround) sur = pr::caught_beside(ec[cell - GW], ec[cell + GW], ec[cell + 1], ec[cell - 1], SENT, CAUGHT);
+                    else sur = ec[cell] >= CAUGHT;
                     double catchr = d.catchr;
                     if constexpr (INJECT) { if (d.catchr_env != nullptr) catchr = sload_f64(d.catchr_env, env); }
-                    r = catchr * (double)kpre;
-                    r += d.term_pursuit * (sur ? 1.0 : 0.0);
-                    r += d.urgency;
+                    r = pr::pursuer_reward(catchr, kpre, d.term_pursuit, sur, d.urgency);
                 }
                 if (d.reward_global && wv == 0) {
                     double all[P];
@@ -476,21 +459,13 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                         map_id = (int)__umulhi(rm.x, (uint32_t)ka->d.n_maps);
                     }
                     load_map(map_id);
-                    const u32x4 rw = philox4x32_10(gid, tick, 1u, TAG_RESET_ENV, k0, k1);
-                    const double sx = u53(rw.x, rw.y) * (1.0 - cw);
-                    const double sy = u53(rw.z, rw.w) * (1.0 - cw);
-                    const int xlb = (int)(S::XS * sx), xub = (int)(S::XS * (sx + cw));
-                    const int ylb = (int)(S::YS * sy), yub = (int)(S::YS * (sy + cw));
+                    const pr::Window win = pr::reset_window(gid, tick, k0, k1, cw, S::XS, S::YS);
                     int n_create = E;
-                    if constexpr (S::LIVE) {  // the pending counts take effect, clamped as in the wave kernel
-                        np = min(max(pending_count(env, 0), 1), P);
-                        ne = min(max(pending_count(env, 1), 0), E);
-                        n_create = ne;
+                    if constexpr (S::LIVE) {  // the pending counts take effect
+                        const pr::Counts live = pr::clamp_pending(pending_count(env, 0), pending_count(env, 1), P, E);
+                        np = live.np, ne = n_create = live.ne;
                     }
-                    if (max_opponents > 0 && !inj_pos) {
-                        const u32x4 r3 = philox4x32_10(gid, tick, 2u, TAG_RESET_ENV, k0, k1);
-                        n_create = min(1 + (int)__umulhi(r3.x, (uint32_t)(max_opponents - 1)), S::LIVE ? ne : E);
-                    }
+                    if (max_opponents > 0 && !inj_pos) n_create = pr::reset_n_create(gid, tick, k0, k1, max_opponents, S::LIVE ? ne : E);
                     bool exists = false;
                     if (isAgent()) {
                         if constexpr (S::LIVE) exists = isLP() || (!isP() && eslot < n_create);
@@ -501,11 +476,9 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                             if (!isP() && x < 0) exists = false;
                         } else {
                             for (uint32_t att = 0; att < 1024u; ++att) {
-                                // (LIVE: the agent's index in the live layout, evader i = agent np + i)
                                 const uint32_t aidx = S::LIVE ? (uint32_t)(isP() ? tid : np + eslot) : (uint32_t)tid;
-                                const u32x4 rp = philox4x32_10(gid, tick, aidx, TAG_RESET_POS | (att << 8), k0, k1);
-                                x = xlb + (int)__umulhi(rp.x, (uint32_t)(xub - xlb));
-                                y = ylb + (int)__umulhi(rp.y, (uint32_t)(yub - ylb));
+                                const pr::Cell c = pr::reset_cell(gid, tick, aidx, att, k0, k1, win);
+                                x = c.x, y = c.y;
                                 if (L[(x + PAD) * GW + y + PAD] == 0u) break;
                             }
                         }

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "pursuit_rules.hpp"
 #include "pursuit_zm16.hpp"
 
 namespace madrl {
@@ -435,7 +436,7 @@ constexpr int FILL_FIRST = 56, FILL_BATCH = 16;
 // S::LIVE (LShape) = per-env agent counts: the env's live (np, ne) come from its record (NOT_HERE slots);
 // pursuer lanes >= np do not move, are not counted, write no observation row (their stores stay issued, exec-masked, so that
 // VM_PER_ENV holds) and a 0 reward; evader slots >= ne are gone; a reset takes (np, ne) from the caller's pending counts and
-// numbers its draws in the live layout (evader i is agent np + i), so that the env is bit for bit env n of a fixed (np, ne) batch.
+// numbers its draws in the live layout (pursuit_rules.hpp).
 template <class S, int MODE, bool INJECT, bool CTRL = false>
 __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const WaveDev d, const WaveIO io) {
     static_assert(!CTRL || (S::E >= S::P && (MODE == 0 || INJECT)), "evader control: n_evaders >= n_pursuers, flexible instantiation");
@@ -568,8 +569,8 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
             int32_t tstep = (int32_t)__builtin_amdgcn_readlane(cur_rec, 1);
             int32_t map_id = (int32_t)__builtin_amdgcn_readlane(cur_rec, 2);
             const uint32_t xyw = (uint32_t)__shfl((int)cur_rec, 4 + (lane >> 1));
-            const uint32_t xy = (lane & 1) ? (xyw >> 16) : (xyw & 0xFFFFu);
-            int x = (int)(xy & 0xFF), y = (int)(xy >> 8);
+            const pr::Cell at = pr::unpack_xy(xyw, lane & 1);
+            int x = at.x, y = at.y;
             uint64_t gone = (uint32_t)__builtin_amdgcn_readlane(cur_rec, S::OFF_GONE / 4);  // (uint32_t): readlane returns int, bit 31 must not sign-extend
             if constexpr (S::NGW > 1) gone |= (uint64_t)(uint32_t)__builtin_amdgcn_readlane(cur_rec, S::OFF_GONE / 4 + 1) << 32;
             uint64_t term = (uint32_t)__builtin_amdgcn_readlane(cur_rec, S::OFF_TERM / 4);
@@ -617,10 +618,9 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                 wave_sync();
                 int kpre = 0;
                 if (isP()) {  // np.clip keeps a border pursuer on its own cell (:374-380)
-                    const int dxm = (x > 0) ? GW : 0, dxp = (x < S::XS - 1) ? GW : 0;
-                    const int dym = (y > 0) ? 1 : 0, dyp = (y < S::YS - 1) ? 1 : 0;
+                    const pr::Clip4 n = pr::clipped_neighbours<GW, S::XS, S::YS>(x, y);
                     const uint32_t *ec = &L[2 * GSZ];
-                    kpre = (int)(ec[cell - dxm] + ec[cell + dxp] + ec[cell + dyp] + ec[cell - dym]);
+                    kpre = (int)(ec[cell - n.dxm] + ec[cell + n.dxp] + ec[cell + n.dyp] + ec[cell - n.dym]);
                 }
                 wave_sync();
                 if (e_alive) atomicSub(&layer[cell], 1u);
@@ -636,7 +636,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                     injected = io.inj_eact != nullptr;
                     int pact;
                     if (injected) pact = isP() ? io.inj_eact[env * P + lane] : 4;
-                    else pact = (int)__umulhi(philox4x32_10(gid, tick, (uint32_t)lane, TAG_PURSUER_ACT, k0, k1).x, 5u);
+                    else pact = pr::pursuer_action(gid, tick, (uint32_t)lane, k0, k1);
                     act = isP() ? pact : (kidx < P ? from_k : 4);
                     injected = true;   // (nothing below draws evader moves)
                 } else if constexpr (INJECT) {
@@ -652,15 +652,14 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                     if (!isP()) act = (int)__umulhi(r.x, 5u);  // RandomPolicy.act, Controllers.py:15-16
                 }
                 // DiscreteAgent.step, DiscreteAgent.py:69-97
-                const int dcell = (act == 0 ? -GW : 0) + (act == 1 ? GW : 0) + (act == 2 ? 1 : 0) + (act == 3 ? -1 : 0);
+                const int dcell = pr::move_dcell<GW>(act);
                 const bool tflag = (term >> lane) & 1ull;
                 const bool in_building = L[cell] != 0u;          // layer 0 is +0.0f only on free in-map cells
                 const bool target_free = L[cell + dcell] == 0u;  // building or outside the map otherwise
                 const bool newterm = alive && !tflag && in_building;
                 if (alive && !tflag && !in_building && target_free) {
                     cell += dcell;
-                    x += (act == 1) - (act == 0);
-                    y += (act == 2) - (act == 3);
+                    x += pr::move_dx(act), y += pr::move_dy(act);
                 }
                 term |= __ballot(newterm);
                 if (alive) atomicAdd(&layer[cell], 1u);  // :244-246
@@ -669,14 +668,8 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                 bool caught = false;
                 if (e_alive) {
                     const uint32_t *pc = &L[GSZ];
-                    if (d.surround) {
-                        const uint32_t n0 = pc[cell - GW], n1 = pc[cell + GW], n2 = pc[cell + 1], n3 = pc[cell - 1];
-                        const int cnt = (int)(n0 - 1u < SENT - 1u) + (int)(n1 - 1u < SENT - 1u) +
-                                        (int)(n2 - 1u < SENT - 1u) + (int)(n3 - 1u < SENT - 1u);
-                        caught = cnt == (int)need_tab[x * S::YS + y];  // need_to_surround :523-540
-                    } else {
-                        caught = (int)pc[cell] >= d.n_catch;  // :498
-                    }
+                    if (d.surround) caught = pr::cells_with_pursuers(pc[cell - GW], pc[cell + GW], pc[cell + 1], pc[cell - 1], SENT) == (int)need_tab[x * S::YS + y];  // :523-540
+                    else caught = (int)pc[cell] >= d.n_catch;  // :498
                     if (caught) atomicAdd(&layer[cell], CAUGHT);
                 }
                 const uint64_t caught_mask = __ballot(caught) >> P;
@@ -687,18 +680,11 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                 if (isLP()) {
                     const uint32_t *ec = &L[2 * GSZ];
                     bool sur;
-                    if (d.surround) {  // a caught evader on one of my four neighbour cells (:489-495)
-                        const uint32_t n0 = ec[cell - GW], n1 = ec[cell + GW], n2 = ec[cell + 1], n3 = ec[cell - 1];
-                        sur = ((n0 != SENT) & (n0 >= CAUGHT)) | ((n1 != SENT) & (n1 >= CAUGHT)) |
-                              ((n2 != SENT) & (n2 >= CAUGHT)) | ((n3 != SENT) & (n3 >= CAUGHT));
-                    } else {
-                        sur = ec[cell] >= CAUGHT;  // :503-506
-                    }
+                    if (d.surround) sur = pr::caught_beside(ec[cell - GW], ec[cell + GW], ec[cell + 1], ec[cell - 1], SENT, CAUGHT);
+                    else sur = ec[cell] >= CAUGHT;  // :503-506
                     double catchr = d.catchr;
                     if constexpr (INJECT) { if (d.catchr_env != nullptr) catchr = sload_f64(d.catchr_env, env); }
-                    r = catchr * (double)kpre;
-                    r += d.term_pursuit * (sur ? 1.0 : 0.0);
-                    r += d.urgency;
+                    r = pr::pursuer_reward(catchr, kpre, d.term_pursuit, sur, d.urgency);
                 }
                 if (d.reward_global) {  // [rewards.mean()] * n_pursuers, numpy summation order
                     double all[P];
@@ -752,23 +738,13 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                         map_id = (int)__umulhi(rm.x, (uint32_t)ka->d.n_maps);
                     }
                     load_map(map_id);
-                    const u32x4 rw = philox4x32_10(gid, tick, 1u, TAG_RESET_ENV, k0, k1);
-                    const double sx = u53(rw.x, rw.y) * (1.0 - cw);  // :185-191, float64
-                    const double sy = u53(rw.z, rw.w) * (1.0 - cw);
-                    const int xlb = (int)(S::XS * sx), xub = (int)(S::XS * (sx + cw));
-                    const int ylb = (int)(S::YS * sy), yub = (int)(S::YS * (sy + cw));
-                    // random_opponents (train_pursuit, :177-181): n_create <= E evaders this episode, the slots above are not
-                    // created and count as gone; an injected position with x < 0 marks a slot that is not created
-                    int n_create = E;
-                    if constexpr (S::LIVE) {  // the pending counts take effect (clamped: the caller's array is not trusted with lanes)
-                        np = min(max(pending_count(env, 0), 1), P);
-                        ne = min(max(pending_count(env, 1), 0), E);
-                        n_create = ne;
+                    const pr::Window win = pr::reset_window(gid, tick, k0, k1, cw, S::XS, S::YS);
+                    int n_create = E;   // (an injected position with x < 0 marks an evader slot that is not created)
+                    if constexpr (S::LIVE) {  // the pending counts take effect
+                        const pr::Counts live = pr::clamp_pending(pending_count(env, 0), pending_count(env, 1), P, E);
+                        np = live.np, ne = n_create = live.ne;
                     }
-                    if (max_opponents > 0 && !inj_pos) {
-                        const u32x4 r3 = philox4x32_10(gid, tick, 2u, TAG_RESET_ENV, k0, k1);
-                        n_create = min(1 + (int)__umulhi(r3.x, (uint32_t)(max_opponents - 1)), S::LIVE ? ne : E);
-                    }
+                    if (max_opponents > 0 && !inj_pos) n_create = pr::reset_n_create(gid, tick, k0, k1, max_opponents, S::LIVE ? ne : E);
                     bool exists = false;
                     if (isAgent()) {  // create_agents / feasible_position, agent_utils.py:12-47
                         if constexpr (S::LIVE) exists = isLP() || (!isP() && eslot < n_create);
@@ -779,11 +755,10 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                             if (!isP() && x < 0) exists = false;
                         } else {
                             for (uint32_t att = 0; att < 1024u; ++att) {
-                                // (LIVE: the agent's index in the live layout, evader i = agent np + i)
                                 const uint32_t aidx = S::LIVE ? (uint32_t)(isP() ? lane : np + eslot) : (uint32_t)lane;
                                 const u32x4 rp = philox4x32_10(gid, tick, aidx, TAG_RESET_POS | (att << 8), k0, k1);
-                                x = xlb + (int)__umulhi(rp.x, (uint32_t)(xub - xlb));
-                                y = ylb + (int)__umulhi(rp.y, (uint32_t)(yub - ylb));
+                                x = win.xlb + (int)__umulhi(rp.x, (uint32_t)(win.xub - win.xlb));   // (pr::reset_cell's text: the helper
+                                y = win.ylb + (int)__umulhi(rp.y, (uint32_t)(win.yub - win.ylb));   // changes the headline step kernel)
                                 // building cells hold fl32(1/norm) != 0; window cells are inside the map
                                 if (L[(x + PAD) * GW + y + PAD] == 0u) break;
                             }

@@ -2,7 +2,7 @@
 pursuit_crowd_specializations.def) against the generic kernel the same shapes ran on before.
 
     python scripts/crowd_time.py --mode {crowd,generic} [--shape {cnn,cnn48,surround24,colocate20,wide24}] [--envs 1024] [--warmup 200] [--steps 200]
-                                 [--live P E]
+                                 [--live P E] [--to SLOTS]
 
   cnn         the authors' CNN launch line (runners/old/rllab/pursuit_cnn.sh:1): 100 v 300, obs_range 21, (R, R, 4) rows, --surround
               --sample_maps, local reward, on a ten-map 128 x 128 pool.  Their map_pool128.npy is not in their tree: the pool is
@@ -15,6 +15,9 @@ pursuit_crowd_specializations.def) against the generic kernel the same shapes ra
 --live P E: the batch is built with per_env_counts=True (the shape's counts are then a capacity) and every env runs P pursuers and E evaders:
 --mode crowd is then the live crowd kernel (the XLC lines of pursuit_live_specializations.def), --mode generic pursuit_live_kernel, and the
 bytes are those of the live rows.
+
+--to SLOTS: the two-buffer step, step_into(obs_out=) round a ring of SLOTS observation buffers (pursuit_crowd_to_kernel where the shape has
+an XC line in pursuit_to_specializations.def, pursuit_to_kernel otherwise and with --mode generic); the JSON line names the kernel kind.
 
 sample_maps as listed, max_steps=500, auto_reset=True; one launch per step through step_into.  Prints one JSON line: the HIP-event time per
 step, the kernel that ran, the algorithmic bytes per env-step (bench.algorithmic_bytes_per_env_step: 708 229 B at the CNN shape) and the
@@ -58,6 +61,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--live", type=int, nargs=2, metavar=("P", "E"), default=None)
+    ap.add_argument("--to", type=int, default=0, metavar="SLOTS")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -77,18 +81,27 @@ def main():
     acts = [torch.randint(0, 5, (N, P), device=dev, dtype=torch.int32, generator=gen) for _ in range(8)]
     rew = torch.zeros((N, P), dtype=torch.float32, device=dev)
     done = torch.zeros(N, dtype=torch.uint8, device=dev)
+    ring = [env.obs_buffer] + [torch.zeros_like(env.obs_buffer) for _ in range(a.to - 1)] if a.to else None
+
+    def step(i):
+        if ring is None:
+            env.step_into(acts[i % 8], rew, done)
+        else:
+            env.step_into(acts[i % 8], rew, done, obs_out=ring[(i + 1) % len(ring)])
+
     for i in range(a.warmup):
-        env.step_into(acts[i % 8], rew, done)
+        step(i)
     torch.cuda.synchronize()
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record()
     for i in range(a.steps):
-        env.step_into(acts[i % 8], rew, done)
+        step(i)
     t1.record()
     torch.cuda.synchronize()
     us = 1e3 * t0.elapsed_time(t1) / a.steps
     nbytes = algorithmic_bytes_per_env_step(a.live[0] if a.live else P, kw["n_evaders"], env.obs_dim, env.record_bytes)
-    print(json.dumps(dict(mode=a.mode, shape=a.shape, envs=N, **(dict(live=a.live) if a.live else {}), kernel_kind=env.kernel_kind, us_per_step=round(us, 2),
+    print(json.dumps(dict(mode=a.mode, shape=a.shape, envs=N, **(dict(live=a.live) if a.live else {}), kernel_kind=env.kernel_kind,
+                          **(dict(step_to_kernel=env.step_to_kernel_kind, slots=a.to) if a.to else {}), us_per_step=round(us, 2),
                           algorithmic_bytes_per_env_step=nbytes, share_of_8e12=round(nbytes * N / (us * 1e-6) / 8.0e12, 4))))
 
 

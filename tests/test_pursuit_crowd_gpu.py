@@ -153,6 +153,41 @@ def test_crowd_kernel_free_running_vs_oracle_and_generic(case):
         assert n_done > 0
 
 
+def test_all_reset_rules_together_free_running_vs_oracle():
+    """every reset rule at once on the smallest crowd shape (XC(24, 24, 20, 300, 9, 1, 1)): the episode's map drawn from a pool of three,
+    random_opponents, a constraint window inside the map, the fused auto-reset -- 9 envs on 3 workgroups, max_steps 7, 40 steps"""
+    from madrl_amd.maps import synthetic_map_pool
+    from oracle import pursuit as po
+    maps = list(synthetic_map_pool(3, 24, 24, seed=1))
+    kw = dict(SURROUND_24, sample_maps=True, random_opponents=True, max_opponents=250, constraint_window=0.5)
+    N, T, H = 9, 40, 7
+    env = _mk(maps, N, seed=3, env_id_base=7, max_steps=H, auto_reset=True, kernel="wave", **kw)
+    env.set_launch(max_blocks=3)   # a workgroup walks three envs
+    assert env.kernel_kind == "wave"
+    orc = po.PursuitOracle(maps, n_envs=N, seed=3, env_id_base=7, **kw)
+    assert np.array_equal(env.reset().reshape(orc.obs.shape).cpu().numpy(), orc.reset()), "reset obs"
+    _cmp_oracle_state(env, orc, "after reset")
+    assert len(set(orc.get_state()["map_id"].tolist())) >= 2
+    rng = np.random.RandomState(5)
+    tstep = np.zeros(N, np.int64)
+    for t in range(T):
+        act = rng.randint(5, size=(N, env.n_pursuers))
+        obs, rew, done, info = env.step(torch.as_tensor(act, device=DEV))
+        _oobs, orew, odone, orem = orc.step(act)
+        tstep += 1
+        bits = odone.astype(np.uint8) | ((tstep >= H).astype(np.uint8) << 1)
+        assert np.array_equal(info["done_bits"].cpu().numpy(), bits), "step %d done bits" % t
+        assert np.array_equal(info["removed"].cpu().numpy(), orem), "step %d removed" % t
+        assert np.array_equal(rew.cpu().numpy(), orew.astype(np.float32)), "step %d rewards" % t
+        mask = (bits != 0).astype(np.uint8)
+        if mask.any():
+            orc.reset(mask=mask)
+            tstep[mask != 0] = 0
+        got = obs.reshape(orc.obs.shape).cpu().numpy()
+        assert np.array_equal(got, orc.obs), "step %d obs: %d cells differ" % (t, int((got != orc.obs).sum()))
+        _cmp_oracle_state(env, orc, "step %d" % t)
+
+
 def test_every_env_of_a_1024_env_cnn_batch_matches_the_oracle():
     from oracle import pursuit as po
     maps, N = _maps("pool128"), 1024

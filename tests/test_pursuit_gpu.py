@@ -230,6 +230,28 @@ def _free_run(maps, kw, kernel, N, T, expect_catches, want_kind=None, H=25, max_
     assert n_lone_done > 0 or not expect_lone_done
 
 
+# Every reset rule at once -- the episode's map drawn from a pool, random_opponents, a constraint window inside the map, the fused
+# auto-reset -- on a small committed shape of the one-wavefront kernel (X(6, 6, 5, 4, 5, 1): the smallest whose half-size window is not a
+# single row or cell) and on the smallest of the multi-wavefront kernel (XG(16, 16, 20, 50, 5, 1, 2)), and on the generic kernel at both: 9 envs on 3 workgroups, max_steps 7, 40 steps = five resets per env.
+# max_opponents 6 at 4 evader slots / 45 at 50: the evader count is clamped in some episodes and not in others.
+ALL_RESET_RULES = {
+    "5v4": ("synthetic6", dict(n_pursuers=5, n_evaders=4, obs_range=5, n_catch=2, surround=True, flatten=True, reward_mech="local",
+                               sample_maps=True, random_opponents=True, max_opponents=6, constraint_window=0.5)),
+    "20v50": ("pool16", dict(n_pursuers=20, n_evaders=50, obs_range=5, n_catch=1, surround=False, flatten=True, reward_mech="global",
+                             sample_maps=True, random_opponents=True, max_opponents=45, constraint_window=0.5, catchr=0.1)),
+}
+
+
+@pytest.mark.parametrize("case", sorted(ALL_RESET_RULES))
+@pytest.mark.parametrize("kernel", ["generic", "auto"])
+def test_all_reset_rules_together_free_running_vs_oracle(case, kernel):
+    from madrl_amd.maps import synthetic_map_pool
+    mname, kw = ALL_RESET_RULES[case]
+    maps = list(synthetic_map_pool(3, 6, 6, seed=1)) if mname == "synthetic6" else _maps(mname)
+    assert len(maps) >= 2
+    _free_run(maps, dict(kw), kernel, 9, 40, expect_catches=False, want_kind="wave" if kernel == "auto" else "generic", H=7, max_blocks=3)
+
+
 @pytest.mark.parametrize("start", ["nothing_known", "known_zero"])
 @pytest.mark.parametrize("case", sorted(LIMIT_SHAPES), ids=sorted(LIMIT_SHAPES))
 def test_limit_shapes_keep_and_store_cells_of_a_buffer_that_is_not_zero(case, start):
