@@ -215,7 +215,8 @@ __global__ __launch_bounds__(256) void multiwalker_policy_kernel(const float *__
     const double head = 0.9 * (0 - s[0]) - 1.5 * s[1];
     hip0 -= head; hip1 -= head;
     knee0 -= 15.0 * s[3]; knee1 -= 15.0 * s[3];
-    auto clip = [](double v) { return (float)fmax(-1.0, fmin(1.0, 0.5 * v)); };
+    // np.clip (:81) hands a NaN on; fmin / fmax would turn it into 1.0
+    auto clip = [](double v) { v *= 0.5; return (float)(v < -1.0 ? -1.0 : v > 1.0 ? 1.0 : v); };
     float *a = actions + 4 * row;
     a[0] = clip(hip0); a[1] = clip(knee0); a[2] = clip(hip1); a[3] = clip(knee1);
 }

@@ -73,7 +73,7 @@ class PursuitHeuristicPolicy(_DevicePolicy):
             assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == n_rows and out.device == obs.device
             act = out
         else:
-            if self._act is None or self._act.numel() != n_rows or self._act.device != obs.device:
+            if self._act is None or self._act.shape != obs.shape[:2] or self._act.device != obs.device:
                 self._act = torch.empty(obs.shape[:2], dtype=torch.int32, device=obs.device)
             act = self._act
         if self._tick is None or self._tick.device != obs.device:
@@ -101,7 +101,7 @@ class WaterworldHeuristicPolicy(_DevicePolicy):
         if self._cs is None or self._cs.device != obs.device or self._cs.shape[0] != K:
             ang = np.linspace(0., 2. * np.pi, K + 1)[:-1]  # waterworld.py:27-29
             self._cs = torch.as_tensor(np.c_[np.cos(ang), np.sin(ang)].copy(), dtype=torch.float64, device=obs.device)
-        if self._act is None or self._act.numel() != 2 * n_rows or self._act.device != obs.device:
+        if self._act is None or self._act.shape[:-1] != obs.shape[:-1] or self._act.device != obs.device:
             self._act = torch.empty(tuple(obs.shape[:-1]) + (2,), dtype=torch.float32, device=obs.device)
         _lib.check(_lib.lib().madrl_heuristic_waterworld(_lib.ptr(obs), n_rows, D, _lib.ptr(self._cs), _lib.ptr(self._act),
                                                          _lib.current_stream(obs.device)))
@@ -118,7 +118,7 @@ class MultiWalkerHeuristicPolicy(_DevicePolicy):
         obs = obs.contiguous()
         D = obs.shape[-1]
         n_rows = obs.numel() // D
-        if self._act is None or self._act.numel() != 4 * n_rows or self._act.device != obs.device:
+        if self._act is None or self._act.shape[:-1] != obs.shape[:-1] or self._act.device != obs.device:
             self._act = torch.empty(tuple(obs.shape[:-1]) + (4,), dtype=torch.float32, device=obs.device)
         _lib.check(_lib.lib().madrl_heuristic_multiwalker(_lib.ptr(obs), n_rows, D, _lib.ptr(self._act), _lib.current_stream(obs.device)))
         return self._act, None

@@ -1,6 +1,6 @@
 """NumPy restatement of the reference's hand-written policies, vectorised over rows.  TEST INFRASTRUCTURE ONLY.
-Pinned by tests/test_oracle_heuristics.py against tests/golden/heuristics.npz (outputs of the unmodified reference
-classes, oracle/make_golden_heuristics.py).  Reference: /root/reference/heuristics/{pursuit,waterworld,multi_walker}.py."""
+Pinned by tests/test_oracle_heuristics.py against tests/golden/heuristics.npz and heuristics_edges.npz (outputs of the unmodified
+reference classes, oracle/make_golden_heuristics.py).  Reference: /root/reference/heuristics/{pursuit,waterworld,multi_walker}.py."""
 import math
 
 import numpy as np
@@ -36,9 +36,28 @@ def pursuit_actions(win):
     return out
 
 
-def waterworld_actions(obs):
-    """obs [B, D] -> float64 [B, 2], every row normalised on its own (the reference is called with B = 1; its
-    np.linalg.norm over the whole batch, waterworld.py:46, is then the row norm)"""
+def pursuit_edge_windows(ev, seed):
+    """evader counts uint8 [B, R, R] -> windows float32 [B, R, R, 4] with the counts in channel 2 and seeded clutter in the channels the
+    policy must not look at (0 walls, 1 pursuer counts, 3): tests/golden/heuristics_edges.npz stores the evader channel alone, the
+    generator (oracle/make_golden_heuristics.py) and the tests both rebuild the windows here"""
+    rng = np.random.RandomState(seed)
+    B, R = ev.shape[0], ev.shape[1]
+    win = np.zeros((B, R, R, 4), np.float32)
+    win[..., 0] = rng.rand(B, R, R) < 0.2
+    win[..., 1] = (rng.rand(B, R, R) < 0.3) * rng.randint(1, 4, (B, R, R))
+    win[..., 2] = ev
+    win[..., 3] = rng.rand(B, R, R) < 0.5
+    return win
+
+
+def pursuit_flatten_rows(win):
+    """windows [B, R, R, 4] -> the rows of PursuitEvade(flatten=True): [ch][x][y] of channels 0..2, then the agent id"""
+    B = win.shape[0]
+    return np.concatenate([np.transpose(win[..., :3], (0, 3, 1, 2)).reshape(B, -1), np.full((B, 1), 0.25, np.float32)], axis=1)
+
+
+def waterworld_raw(obs):
+    """obs [B, D] -> float64 [B, 2]: the action before it is normalised (waterworld.py:26-47)"""
     obs = np.asarray(obs, np.float64)
     K = obs.shape[1] // 7                                    # :26
     ang = np.linspace(0., 2. * np.pi, K + 1)[:-1]
@@ -47,7 +66,13 @@ def waterworld_actions(obs):
     oa, ev, po, pu = -s(0), s(1), -s(3), s(5) / 2            # :31-41
     ev[obs[:, 7 * K] > 0] *= 1.5                             # :43-44
     po[obs[:, 7 * K + 1] > 0] *= 1.5
-    act = oa + ev + po + pu
+    return oa + ev + po + pu
+
+
+def waterworld_actions(obs):
+    """obs [B, D] -> float64 [B, 2], every row normalised on its own (the reference is called with B = 1; its
+    np.linalg.norm over the whole batch, waterworld.py:46, is then the row norm)"""
+    act = waterworld_raw(obs)
     n = np.sqrt((act ** 2).sum(axis=1, keepdims=True))
     return np.where(n > 0, act / np.where(n > 0, n, 1.0), 0.0)
 
