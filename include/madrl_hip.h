@@ -193,6 +193,26 @@ int madrl_pursuit_step_to(madrl_pursuit *h, const int32_t *actions_dev, const in
                           int32_t *removed_dev, void *stream);
 int madrl_pursuit_step_to_kernel_kind(madrl_pursuit *h, int32_t *out);
 
+/* madrl_pursuit_step_to over HALF-PRECISION observation slots: both buffers hold IEEE binary16 in the layout step_to uses,
+ * n_envs * P * obs_dim elements of 2 bytes.  After the call an element madrl_pursuit_step_to would STORE holds the round-to-nearest-even
+ * binary16 of that float32 value (gradual underflow, overflow to infinity: what a float32 -> float16 tensor conversion gives); an element
+ * step_to would CARRY OVER from obs_prev (channel-1 / 2 cells outside the map, skipped cells, whole rows of absent observers) holds the 16
+ * bits at the same place of obs_prev_dev, unchanged -- a raw copy, no re-rounding.  Both passes of a fused auto-reset count (the second sees
+ * the first one's halves in obs_next_dev).  obs_prev_dev is not written; rew / done / removed, the flag plane and the state records are
+ * those of madrl_pursuit_step, bit for bit.
+ *   A NULL pointer, a buffer that is not 16-byte aligned, buffers that overlap: MADRL_EINVAL -- equal pointers too: there is no in-place
+ *   half step.
+ *   What the fast path knows about a buffer ("known zero" = all bits of the element zero, in either format) describes obs_next_dev AS A
+ *   BINARY16 BUFFER after the call.  The handle records the element format with the address and reuses its knowledge only when both
+ *   match: the same address read in the other format is an unknown buffer.  madrl_pursuit_declare_obs_zero keeps meaning float32; a half
+ *   ring starts from "nothing known" and learns.
+ * The one-wavefront (X / XL) shapes of madrl_amd/csrc/pursuit_to_specializations.def have a half two-buffer kernel; every other handle
+ * -- multi-wavefront, crowd, control_evaders -- runs this call on the generic kernel (madrl_pursuit_step_to_f16_kernel_kind). */
+int madrl_pursuit_step_to_f16(madrl_pursuit *h, const int32_t *actions_dev, const int32_t *inj_evader_actions_dev,
+                              const uint16_t *obs_prev_dev, uint16_t *obs_next_dev, float *rew_dev, uint8_t *done_dev,
+                              int32_t *removed_dev, void *stream);
+int madrl_pursuit_step_to_f16_kernel_kind(madrl_pursuit *h, int32_t *out);   /* MADRL_KERNEL_WAVE / MADRL_KERNEL_GENERIC */
+
 /* One batch stepped as n_shards independent sub-batches, each a handle of its own (created with env_id_base advanced by its offset)
  * on its own HIP stream: ONE host call issues every launch.  Env instances never interact (the reference's own parallelism is N
  * pickled env copies in sampler workers, runners/rurllab.py:259), so nothing orders sub-batch A's step t + 1 against sub-batch

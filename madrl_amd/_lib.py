@@ -158,6 +158,8 @@ SIGNATURES = {
     "madrl_heuristic_waterworld": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
     "madrl_heuristic_multiwalker": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, _vp]),
     "madrl_rollout_gae": (C.c_int, [_vp] * 3 + [C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double] + [_vp] * 3),
+    "madrl_pursuit_step_to_f16": (C.c_int, [_vp] * 9),
+    "madrl_pursuit_step_to_f16_kernel_kind": (C.c_int, [_vp, _vp]),
 }
 
 
@@ -191,6 +193,16 @@ def ptr(t):
         return None
     assert t.is_contiguous(), "tensor passed across the C ABI must be contiguous"
     return C.c_void_p(t.data_ptr())
+
+
+def require_float32(t, what):
+    """The native consumers of observation rows (the device chase policy, the wrappers' epilogue kernels) read float32 through the raw
+    pointer: any other element type -- the float16 rows of BatchedPursuitEvade(obs_dtype=torch.float16) -- would be read, or written,
+    past the end of the buffer.  Refused here, before a pointer is taken."""
+    if t.dtype is not torch.float32:
+        raise TypeError("%s reads float32 observations through the C ABI, got %s (a half-precision PursuitEvade, obs_dtype=torch.float16, "
+                        "needs a torch policy and no wrapper; convert with .float() first if a copy is acceptable)" % (what, t.dtype))
+    return t
 
 
 def current_stream(device):

@@ -31,7 +31,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
          "-Wno-pass-failed"]   # (`#pragma unroll` on loops whose bounds are only known in the specialised instantiations: the generic ones stay rolled)
 # per-source additions.  multiwalker: the SLP vectorizer pairs the solver's scalar float math into packed-fp32 instructions, which
 # need every loop constant replicated into register pairs -- the 180-sweep loop then runs out of VGPRs (AGPR copies, scratch)
-EXTRA_FLAGS = {"multiwalker_c": ["-fno-slp-vectorize"]}   # file-name prefix -> flags (the capacity classes multiwalker_c4 / _c8 / _c10.hip)
+# pursuit_to_f16_live: the default scalar register allocator leaves the kernel a private segment that nothing touches (see the file's head)
+EXTRA_FLAGS = {"multiwalker_c": ["-fno-slp-vectorize"],   # file-name prefix -> flags (the capacity classes multiwalker_c4 / _c8 / _c10.hip)
+               "pursuit_to_f16_live": ["-mllvm", "-sgpr-regalloc=basic"]}
 
 
 def pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True):

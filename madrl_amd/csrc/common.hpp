@@ -94,6 +94,11 @@ __device__ __forceinline__ __attribute__((address_space(1))) T *uniform_ptr(T *p
     return (__attribute__((address_space(1))) T *)(((uint64_t)hi << 32) | lo);  // global address space: global_*, not flat_*, instructions
 }
 
+// The IEEE binary16 of a float32 value, round to nearest even with gradual underflow and overflow to infinity (v_cvt_f16_f32 under the
+// default rounding mode: what torch.Tensor.to(torch.float16) gives) -- the half-precision observation slots of madrl_pursuit_step_to_f16.
+// (Not the packed conversion v_cvt_pkrtz_f16_f32: that one rounds toward zero, 0.3f -> 0x34CC instead of 0x34CD.)
+__device__ __forceinline__ uint16_t half_bits(float v) { return __builtin_bit_cast(uint16_t, (_Float16)v); }
+
 // Register-pressure control.  The compiler hoists every loop-invariant lane compare (lane < P, lane == k, ...)
 // out of the env loop as an SGPR-pair mask and, with ~100 uniform values already live there, spills them to
 // VGPR lanes: each use then costs two v_readlane_b32 (VALU issue slots, the resource these kernels are bound by).

@@ -36,6 +36,7 @@ namespace {
 
 using namespace madrl;
 
+enum { OBS_F32 = 0, OBS_F16 = 1 };   // the element format of an observation buffer (launch(), madrl_pursuit::zmask_fmt)
 constexpr int MAX_CELL_COUNT = 253;  // byte grids: the agents of one layer on ONE cell must stay < PAD_MAP (checked where they are counted)
 constexpr int NOT_HERE = 0xFF;       // position byte of a slot that does not exist (per-env agent counts; no coordinate is 255)
 constexpr int MAX_COUNT = 1023;      // agents per layer.  The authors' largest launch line runs 100 pursuers / 300 evaders
@@ -110,6 +111,7 @@ template <int NT>
 __global__ void pursuit_kernel(const PursuitDev d, const PursuitIO io, const int mode) {
     constexpr bool LIVE = false;
     constexpr bool TO = false;
+    constexpr bool H16 = false;
     const int32_t *const pending = nullptr;
     [[maybe_unused]] const float *const obs_prev = nullptr;
 #include "pursuit_generic.inc"
@@ -119,6 +121,7 @@ template <int NT>
 __global__ void pursuit_live_kernel(const PursuitDev d, const PursuitIO io, const int mode, const int32_t *pending) {
     constexpr bool LIVE = true;
     constexpr bool TO = false;
+    constexpr bool H16 = false;
     [[maybe_unused]] const float *const obs_prev = nullptr;
 #include "pursuit_generic.inc"
 }
@@ -129,7 +132,20 @@ template <int NT, bool LIVE_>
 __global__ void pursuit_to_kernel(const PursuitDev d, const PursuitIO io, [[maybe_unused]] const int32_t *pending, const float *const obs_prev) {
     constexpr bool LIVE = LIVE_;
     constexpr bool TO = true;
+    constexpr bool H16 = false;
     const int mode = 1;
+#include "pursuit_generic.inc"
+}
+
+// The same over binary16 observation buffers (madrl_pursuit_step_to_f16): io.obs and obs_prev16 point at 2-byte elements (io.obs is the
+// half pointer, cast: PursuitIO does not grow), every shape and mode -- evader control and the handles whose fast kernel has no half form.
+template <int NT, bool LIVE_>
+__global__ void pursuit_to_f16_kernel(const PursuitDev d, const PursuitIO io, [[maybe_unused]] const int32_t *pending, const uint16_t *const obs_prev16) {
+    constexpr bool LIVE = LIVE_;
+    constexpr bool TO = true;
+    constexpr bool H16 = true;
+    const int mode = 1;
+    const float *const obs_prev = reinterpret_cast<const float *>(obs_prev16);   // (write_obs reads it as the 2-byte elements it holds)
 #include "pursuit_generic.inc"
 }
 
@@ -274,6 +290,7 @@ struct madrl_pursuit {
                                     // (madrl_pursuit_state_bytes), not a library allocation
     const void *zmask_obs = nullptr; // the observation buffer the masks describe; another buffer, a generic-kernel launch,
                                     // set_state or madrl_pursuit_invalidate_obs resets them to "nothing known"
+    int zmask_fmt = OBS_F32;   // ... and the element format it was read in: the same address in the other format is an unknown buffer
     uint64_t step_count = 0;  // step launches so far (parity of the walk direction, see launch())
     int walk_mode = 0;        // 0 auto (alternate above ~375 MB per launch), 1 always alternate, 2 always forward; fixed at create
     void *wtables = nullptr;  // the wave / group kernels' device allocation (build_wave_tables)
@@ -400,6 +417,8 @@ constexpr FastEntry LIVE_TABLE[] = {
 
 // The two-buffer step kernels (madrl_pursuit_step_to, pursuit_to.hip and pursuit_to_group.hip): reached through the fixed line of the same shape and NW, for a handle
 // with per-env agent counts through its live line.  A handle without an entry here runs step_to on the generic kernel.
+// launch_wave_f16: the binary16 form (madrl_pursuit_step_to_f16, pursuit_to_f16.hip) -- the X / XL lines have one; the other lines run the
+// half step on the generic kernel.
 using WaveToLaunch = void (*)(const pw::WaveDev &, const pw::WaveIO &, int64_t blocks, hipStream_t s);
 using CrowdToLaunch = void (*)(const pc::CrowdDev &, const pc::CrowdIO &, const int32_t *pending, const float *obs_prev, int64_t blocks, hipStream_t s);
 struct ToEntry {
@@ -408,14 +427,15 @@ struct ToEntry {
     bool live;
     WaveToLaunch launch_wave;    // one of the two is set
     CrowdToLaunch launch_crowd;
+    WaveToLaunch launch_wave_f16;   // or nullptr
     constexpr bool crowd() const { return launch_crowd != nullptr; }
 };
-#define X(XS, YS, NP, NE, R, FL) ToEntry{{XS, YS, NP, NE, R, FL}, 1, false, pw::wave_to_launch<pw::TShape<XS, YS, NP, NE, R, FL>>, nullptr},
-#define XL(XS, YS, NP, NE, R, FL) ToEntry{{XS, YS, NP, NE, R, FL}, 1, true, pw::wave_to_launch<pw::TLShape<XS, YS, NP, NE, R, FL>>, nullptr},
-#define XC(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, false, nullptr, pc::crowd_to_launch<pc::CShape<XS, YS, NP, NE, R, FL, NW>>},
-#define XLC(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, true, nullptr, pc::crowd_to_launch<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>},
-#define XG(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, false, pw::group_to_launch<pw::TGShape<XS, YS, NP, NE, R, FL, NW>>, nullptr},
-#define XLG(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, true, pw::group_to_launch<pw::TLGShape<XS, YS, NP, NE, R, FL, NW>>, nullptr},
+#define X(XS, YS, NP, NE, R, FL) ToEntry{{XS, YS, NP, NE, R, FL}, 1, false, pw::wave_to_launch<pw::TShape<XS, YS, NP, NE, R, FL>>, nullptr, pw::wave_to_f16_launch<pw::THShape<XS, YS, NP, NE, R, FL>>},
+#define XL(XS, YS, NP, NE, R, FL) ToEntry{{XS, YS, NP, NE, R, FL}, 1, true, pw::wave_to_launch<pw::TLShape<XS, YS, NP, NE, R, FL>>, nullptr, pw::wave_to_f16_launch<pw::TLHShape<XS, YS, NP, NE, R, FL>>},
+#define XC(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, false, nullptr, pc::crowd_to_launch<pc::CShape<XS, YS, NP, NE, R, FL, NW>>, nullptr},
+#define XLC(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, true, nullptr, pc::crowd_to_launch<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>, nullptr},
+#define XG(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, false, pw::group_to_launch<pw::TGShape<XS, YS, NP, NE, R, FL, NW>>, nullptr, nullptr},
+#define XLG(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, true, pw::group_to_launch<pw::TLGShape<XS, YS, NP, NE, R, FL, NW>>, nullptr, nullptr},
 constexpr ToEntry TO_TABLE[] = {
 #include "pursuit_to_specializations.def"
 #if __has_include("pursuit_to_specializations.local.def")
@@ -561,26 +581,31 @@ Dev dev_now(Dev d, const PursuitDev &now) {
 }
 
 // the two-buffer fast kernel a step_to of this handle launches, or nullptr: the generic kernel (evader control and shapes without a
-// line in pursuit_to_specializations.def)
-const ToEntry *to_of(const madrl_pursuit *h) {
+// line in pursuit_to_specializations.def).  fmt OBS_F16 (madrl_pursuit_step_to_f16): the lines whose kernel has a half form.
+const ToEntry *to_of(const madrl_pursuit *h, int fmt = OBS_F32) {
     if (!use_wave(h) || !h->dev.train_pursuit) return nullptr;
-    return find_to(h->fast, h->pending != nullptr);
+    const ToEntry *t = find_to(h->fast, h->pending != nullptr);
+    return (t && fmt == OBS_F16 && !t->launch_wave_f16) ? nullptr : t;
 }
 
 // mode 0: reset, 1: step.  obs_prev == nullptr: in place, io.obs is read and written.  Otherwise madrl_pursuit_step_to: the step's rows go to
-// io.obs and the kept cells come from obs_prev.
-int launch(madrl_pursuit *h, const PursuitIO &io, int mode, const float *obs_prev, void *stream) {
+// io.obs and the kept cells come from obs_prev.  fmt: the element format of both buffers -- OBS_F16 (two buffers only): io.obs and
+// obs_prev point at binary16 elements, cast.
+int launch(madrl_pursuit *h, const PursuitIO &io, int mode, const float *obs_prev, void *stream, int fmt = OBS_F32) {
     hipStream_t s = (hipStream_t)stream;
-    const ToEntry *t = obs_prev ? to_of(h) : nullptr;
+    const ToEntry *t = obs_prev ? to_of(h, fmt) : nullptr;
     if (obs_prev ? t != nullptr : use_wave(h)) {
         const FastEntry *f = fast_of(h);   // (the launcher; the geometry is the fixed line's, h->fast)
         int64_t blocks = h->max_blocks > 0 ? h->max_blocks : h->fast->resident;   // persistent workgroups, as many as are resident
         if (blocks > h->dev.n_envs) blocks = h->dev.n_envs;
         // The masks describe the buffer the kept cells are read from; another one has unknown contents: every cell "not known to be zero".
         // After this launch they describe the buffer it wrote (two buffers: obs_prev is an unknown buffer from here on).
-        if (h->zmask_obs != (obs_prev ? (const void *)obs_prev : (const void *)io.obs))
+        // "Known zero" is "all bits zero" in either format, but the masks are per element: the same address read in the other format is an
+        // unknown buffer too.
+        if (h->zmask_obs != (obs_prev ? (const void *)obs_prev : (const void *)io.obs) || h->zmask_fmt != fmt)
             MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0xFF, zmask_len(h->fast, h->dev.n_envs), s));
         h->zmask_obs = io.obs;
+        h->zmask_fmt = fmt;
         if (f->crowd()) {
             const pc::CrowdDev cd = dev_now(h->cdev, h->dev);
             if (t) t->launch_crowd(cd, io_of<pc::CrowdIO>(io), h->pending, obs_prev, blocks, s);
@@ -602,7 +627,7 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, const float *obs_pre
                 if (alternate) wd.reverse = (int32_t)(h->step_count++ & 1);
             }
             wd.pending = h->pending;
-            if (t) t->launch_wave(wd, w, blocks, s);
+            if (t) (fmt == OBS_F16 ? t->launch_wave_f16 : t->launch_wave)(wd, w, blocks, s);
             else f->launch_wave(wd, w, mode, blocks, s);
         }
         MADRL_HIP_TRY(hipGetLastError());
@@ -614,7 +639,10 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, const float *obs_pre
     const dim3 grid((unsigned)blocks), block((unsigned)h->threads);
     const int rc = with_nt(h->nt, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        if (obs_prev && h->pending) hipLaunchKernelGGL((pursuit_to_kernel<NT, true>), grid, block, h->lds_bytes, s, h->dev, io, h->pending, obs_prev);
+        const uint16_t *const prev16 = reinterpret_cast<const uint16_t *>(obs_prev);
+        if (obs_prev && fmt == OBS_F16 && h->pending) hipLaunchKernelGGL((pursuit_to_f16_kernel<NT, true>), grid, block, h->lds_bytes, s, h->dev, io, h->pending, prev16);
+        else if (obs_prev && fmt == OBS_F16) hipLaunchKernelGGL((pursuit_to_f16_kernel<NT, false>), grid, block, h->lds_bytes, s, h->dev, io, h->pending, prev16);
+        else if (obs_prev && h->pending) hipLaunchKernelGGL((pursuit_to_kernel<NT, true>), grid, block, h->lds_bytes, s, h->dev, io, h->pending, obs_prev);
         else if (obs_prev) hipLaunchKernelGGL((pursuit_to_kernel<NT, false>), grid, block, h->lds_bytes, s, h->dev, io, h->pending, obs_prev);
         else if (h->pending) hipLaunchKernelGGL(pursuit_live_kernel<NT>, grid, block, h->lds_bytes, s, h->dev, io, mode, h->pending);
         else hipLaunchKernelGGL(pursuit_kernel<NT>, grid, block, h->lds_bytes, s, h->dev, io, mode);
@@ -806,6 +834,8 @@ int madrl_pursuit_set_launch(madrl_pursuit *h, int32_t threads, int64_t max_bloc
                 (void)hipFuncSetAttribute((const void *)pursuit_live_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
                 (void)hipFuncSetAttribute((const void *)pursuit_to_kernel<NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
                 (void)hipFuncSetAttribute((const void *)pursuit_to_kernel<NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+                (void)hipFuncSetAttribute((const void *)pursuit_to_f16_kernel<NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+                (void)hipFuncSetAttribute((const void *)pursuit_to_f16_kernel<NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
             });
     }
     return MADRL_OK;
@@ -868,6 +898,25 @@ int madrl_pursuit_step_to(madrl_pursuit *h, const int32_t *actions_dev, const in
 int madrl_pursuit_step_to_kernel_kind(madrl_pursuit *h, int32_t *out) {
     if (!h || !out) return fail(MADRL_EINVAL, "NULL argument");
     *out = to_of(h) ? MADRL_KERNEL_WAVE : MADRL_KERNEL_GENERIC;
+    return MADRL_OK;
+}
+
+int madrl_pursuit_step_to_f16(madrl_pursuit *h, const int32_t *actions_dev, const int32_t *inj_evader_actions_dev, const uint16_t *obs_prev_dev,
+                              uint16_t *obs_next_dev, float *rew_dev, uint8_t *done_dev, int32_t *removed_dev, void *stream) {
+    if (!h || !actions_dev || !obs_prev_dev || !obs_next_dev || !rew_dev || !done_dev || !removed_dev)
+        return fail(MADRL_EINVAL, "step_to_f16: NULL argument");
+    const uint64_t bytes = 2ull * (uint64_t)h->dev.n_envs * (uint64_t)h->dev.P * (uint64_t)h->dev.D;
+    const uint64_t a = (uint64_t)obs_prev_dev, b = (uint64_t)obs_next_dev;
+    if (a < b + bytes && b < a + bytes) return fail(MADRL_EINVAL, "step_to_f16: obs_prev and obs_next overlap (there is no in-place half step; two buffers must be disjoint)");
+    if ((a | b) & 15u) return fail(MADRL_EINVAL, "step_to_f16: observation buffers must be 16-byte aligned");
+    // (the half pointers travel in the float fields of the launch structures, cast: no structure grows)
+    return launch(h, step_io(actions_dev, inj_evader_actions_dev, reinterpret_cast<float *>(obs_next_dev), rew_dev, done_dev, removed_dev), 1,
+                  reinterpret_cast<const float *>(obs_prev_dev), stream, OBS_F16);
+}
+
+int madrl_pursuit_step_to_f16_kernel_kind(madrl_pursuit *h, int32_t *out) {
+    if (!h || !out) return fail(MADRL_EINVAL, "NULL argument");
+    *out = to_of(h, OBS_F16) ? MADRL_KERNEL_WAVE : MADRL_KERNEL_GENERIC;
     return MADRL_OK;
 }
 
@@ -940,6 +989,7 @@ int madrl_pursuit_declare_obs_zero(madrl_pursuit *h, const float *obs_dev, void 
     if (h->zmask) {   // every cell of that buffer is known to hold +0.0f: no stale cell can need protecting
         MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0, zmask_len(h->fast, h->dev.n_envs), (hipStream_t)stream));
         h->zmask_obs = obs_dev;
+        h->zmask_fmt = OBS_F32;
     }
     return MADRL_OK;
 }

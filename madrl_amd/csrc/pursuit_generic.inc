@@ -3,9 +3,12 @@
 //   pursuit_live_kernel<NT>  (LIVE = true): per-env agent counts
 //   pursuit_to_kernel<NT, LIVE>  (TO = true): the two-buffer step of madrl_pursuit_step_to -- the step's rows go to io.obs, the cells an
 //                            in-place step leaves alone come from obs_prev (see write_obs)
+//   pursuit_to_f16_kernel<NT, LIVE>  (TO and H16 = true): the same over binary16 buffers (madrl_pursuit_step_to_f16) -- io.obs and obs_prev
+//                            point at 2-byte elements, a stored value is the round-to-nearest-even half of the float32 one, a kept
+//                            element is its 16 bits copied
 // It is included rather than called because a __device__ function between the kernel and its body changes the code the compiler
 // emits for pursuit_kernel<NT> (its passes see the body on its own before inlining it).  The environment's rules are pursuit_rules.hpp's.
-// In scope: NT, LIVE, TO, d (PursuitDev), io (PursuitIO), mode, pending (int32 [n_envs][2] or nullptr), obs_prev (TO; nullptr otherwise).
+// In scope: NT, LIVE, TO, H16, d (PursuitDev), io (PursuitIO), mode, pending (int32 [n_envs][2] or nullptr), obs_prev (TO; nullptr otherwise).
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x;
     const int nthr = blockDim.x;
@@ -114,6 +117,63 @@
                 const int DV = d.D >> 2, NQ = d.P * DV;
                 int p = tid / DV, f = tid - p * DV;
                 const int dp = nthr / DV, df = nthr - dp * DV;
+                if constexpr (H16) {
+                    // binary16 buffers: the slot is the same four elements, 8 bytes.  Two buffers: one whole non-temporal store per slot, the
+                    // kept halves from the previous buffer's word.  In place (the second pass of a fused auto-reset): a slot without kept
+                    // elements is one store, any other slot plain 2-byte stores of the elements that are written.
+                    typedef uint16_t v4h __attribute__((ext_vector_type(4)));
+                    uint16_t *orow16 = reinterpret_cast<uint16_t *>(io.obs) + env * (int64_t)d.P * d.D;
+                    const uint16_t *prow16 = src ? reinterpret_cast<const uint16_t *>(src) + env * (int64_t)d.P * d.D : nullptr;
+                    for (int q = tid; q < NQ; q += nthr) {
+                        uint16_t *o = orow16 + 4 * (int64_t)q;
+                        if (p >= n_rows) {  // rows of absent observers: copied whole as 16-bit data (in place: they keep their contents)
+                            if (prow16 == nullptr) break;
+                            __builtin_nontemporal_store(*reinterpret_cast<const v4h *>(prow16 + 4 * (int64_t)q), reinterpret_cast<v4h *>(o));
+                        } else {
+                            const int base = (obx[p] - obs_off + pad) * GW + (oby[p] - obs_off + pad);
+                            v4h v;
+                            bool store[4];
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                const uint32_t c = s_code[4 * f + k];
+                                const uint32_t kind = c >> 24;
+                                store[k] = true;
+                                float val = 0.0f;
+                                if (kind == K_GRID) {
+                                    const uint32_t g = g_map[base + (int)(c & 0xFFFFFFu)];
+                                    store[k] = g != PAD_CNT;
+                                    val = s_vtab[g];
+                                } else if (kind == K_ID) {
+                                    val = (float)((double)p / (double)(LIVE ? np : d.P));
+                                } else if (kind == K_FILL) {
+                                    val = d.fill32;
+                                } else {
+                                    store[k] = false;
+                                }
+                                v[k] = half_bits(val);
+                            }
+                            const bool whole = store[0] & store[1] & store[2] & store[3];
+                            if (prow16 != nullptr) {
+                                if (!whole) {
+                                    const v4h old = *reinterpret_cast<const v4h *>(prow16 + 4 * (int64_t)q);
+#pragma unroll
+                                    for (int k = 0; k < 4; ++k)
+                                        if (!store[k]) v[k] = old[k];
+                                }
+                                __builtin_nontemporal_store(v, reinterpret_cast<v4h *>(o));
+                            } else if (whole) {
+                                __builtin_nontemporal_store(v, reinterpret_cast<v4h *>(o));
+                            } else {
+#pragma unroll
+                                for (int k = 0; k < 4; ++k)
+                                    if (store[k]) o[k] = v[k];
+                            }
+                        }
+                        f += df; p += dp;
+                        if (f >= DV) { f -= DV; ++p; }
+                    }
+                    return;
+                }
                 for (int q = tid; q < NQ; q += nthr) {
                     if constexpr (TO) {
                         if (prow != nullptr && p >= n_rows) {  // rows of absent observers: copied whole
@@ -178,6 +238,39 @@
                 return;
             }
             // dword path (rows that are not whole float4s: even obs_range with flatten)
+            if constexpr (H16) {
+                // binary16 buffers: 2-byte elements.  Two buffers: every element of all P rows, the step's value or the previous buffer's
+                // 16 bits; in place: the elements the pass writes
+                uint16_t *orow16 = reinterpret_cast<uint16_t *>(io.obs) + env * (int64_t)d.P * d.D;
+                const uint16_t *prow16 = src ? reinterpret_cast<const uint16_t *>(src) + env * (int64_t)d.P * d.D : nullptr;
+                for (int p = 0; p < (prow16 ? d.P : n_rows); ++p) {
+                    const int base = p < n_rows ? (obx[p] - obs_off + pad) * GW + (oby[p] - obs_off + pad) : 0;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        const int r = tid + t * nthr;
+                        if (r >= d.D) continue;
+                        const uint32_t kind = code[t] >> 24;
+                        bool store = false;
+                        float val = 0.0f;
+                        if (p < n_rows) {
+                            if (kind == K_GRID) {
+                                const uint32_t g = g_map[base + (int)(code[t] & 0xFFFFFFu)];
+                                store = g != PAD_CNT;
+                                val = s_vtab[g];
+                            } else if (kind == K_ID) {
+                                store = true;
+                                val = (float)((double)p / (double)(LIVE ? np : d.P));
+                            } else if (kind == K_FILL) {
+                                store = true;
+                                val = d.fill32;
+                            }
+                        }
+                        if (store) orow16[p * d.D + r] = half_bits(val);
+                        else if (prow16 != nullptr) orow16[p * d.D + r] = prow16[p * d.D + r];
+                    }
+                }
+                return;
+            }
             if constexpr (TO) {
                 if (prow != nullptr) {  // every element of all P rows: the step's value, or the previous buffer's
                     for (int p = 0; p < d.P; ++p) {

@@ -145,7 +145,9 @@ struct Shape {
     static_assert(NS <= 8, "stale-zero mask: one bit per slot in each byte of the lane's mask dword");
     static constexpr bool LIVE = false;
     static constexpr bool TO = false;
-    static constexpr bool TABLED = false;                        // (pursuit_group.hpp: slot constants from an LDS table; never here)
+    static constexpr bool H16 = false;                           // (THShape / TLHShape: binary16 observation buffers)
+    static constexpr bool LEAN_REGS = false;                     // loop constants worked out again at their uses (see THShape)
+    static constexpr bool TABLED = false;                       // (pursuit_group.hpp: slot constants from an LDS table; never here)
     static constexpr int X_TAB = 0;
 };
 
@@ -172,6 +174,30 @@ struct TShape : Shape<XS_, YS_, P_, E_, R_, FLATTEN_> {
 template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
 struct TLShape : LShape<XS_, YS_, P_, E_, R_, FLATTEN_> {
     static constexpr bool TO = true;
+};
+// The two-buffer step over binary16 buffers (madrl_pursuit_step_to_f16): io.obs and io.obs_prev point at 2-byte elements (cast: WaveIO does
+// not grow), so the env's rows are P * D * 2 bytes and a slot -- the same four elements -- is 8 bytes at (64 s + lane) * 8.  Part 1 of the
+// pass is the float32 kernel's; part 2 loads the old slot as one 8-byte word, converts the four values (half_bits: round to nearest even),
+// takes the kept halves from the old word and stores the slot as ONE non-temporal 8-byte store, 512 B per instruction and wavefront.  The
+// second pass of a fused auto-reset is a load-blend-store of whole slots of io.obs itself (half_slot_in_place below): the in-place pass's
+// masked stores are float32 geometry and cannot be reached from these shapes.
+// LEAN_REGS has nothing to do with the storage format: it is a register-pressure trait these two shapes set.  At the 96 VGPRs of five
+// wavefronts per SIMD the TLHShape kernel spilled three loop constants of the shared kernel text; with the trait the mask index of fetch_zm
+// and the two lane indices of the record store are worked out again at their uses and the global reward reads lane k by two ds_bpermute at
+// a constant address instead of __shfl (which keeps `lane & 64` live across the env loop).  No existing shape sets it: their code is the
+// parent's.  Instantiated in pursuit_to_f16.hip (THShape) and
+// pursuit_to_f16_live.hip (TLHShape).
+template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
+struct THShape : Shape<XS_, YS_, P_, E_, R_, FLATTEN_> {
+    static constexpr bool TO = true;
+    static constexpr bool H16 = true;
+    static constexpr bool LEAN_REGS = true;
+};
+template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
+struct TLHShape : LShape<XS_, YS_, P_, E_, R_, FLATTEN_> {
+    static constexpr bool TO = true;
+    static constexpr bool H16 = true;
+    static constexpr bool LEAN_REGS = true;
 };
 
 __device__ __forceinline__ double pairwise8(const double *r) {
@@ -249,9 +275,12 @@ __device__ __forceinline__ void static_for(F &&f) {
 // One observation slot: the four elements under their own lane masks as plain (L2-merged) dword stores, then the float4 under its
 // mask as one non-temporal store.  Each mask is the result of one v_cmp (inactive lanes compare to 0, so a mask never enables a lane
 // that exec had off) and goes into exec with one s_mov: 7 scalar instructions per slot, no mask algebra on the scalar unit.
-template <int OFF>
+// H16: the caller's shape holds binary16 buffers -- refused here, wherever the call stands: the offsets below (a float4 at voff = lane * 16,
+// elements 4 bytes apart, slots 1 KiB apart) are float32 geometry and would run past the end of a half buffer.
+template <int OFF, bool H16 = false>
 __device__ __forceinline__ void store_slot_masked(const void *base, uint32_t voff, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3,
                                                   v4f_t val, uint64_t m0, uint64_t m1, uint64_t m2, uint64_t m3, uint64_t m_nt) {
+    static_assert(!H16, "store_slot_masked is float32 geometry: an H16 shape runs its in-place pass through half_slot_in_place");
     uint64_t sv;
     asm volatile("s_mov_b64 %0, exec\n\t"
                  "s_mov_b64 exec, %1\n\tglobal_store_dword %6, %7, %12 offset:%13\n\t"
@@ -286,6 +315,27 @@ template <int N>
 __device__ __forceinline__ void prefetch_wait(uint32_t &r0, uint32_t &r1, uint32_t &r2) {
     static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
     asm volatile("s_waitcnt vmcnt(%3)" : "+v"(r0), "+v"(r1), "+v"(r2) : "n"(N) : "memory");
+}
+
+// One observation slot of a binary16 buffer, in place (the second pass of a fused auto-reset in the THShape / TLHShape kernels): `row` is
+// the env's rows, `slot` the lane's 8-byte slot in them, v0..v3 the four cells as float32 bits (SENT outside the map: written as zero), keep4
+// the cells that must stay untouched, one flag per byte.  A slot with such a cell is loaded -- from L2 (an agent-scope load: the word was
+// stored by this lane earlier in the kernel, non-temporal) -- and keeps those halves; every valid slot leaves as one whole 8-byte store.
+template <class RowPtr>
+__device__ __forceinline__ void half_slot_in_place(RowPtr row, uint32_t slot, bool valid, uint32_t keep4, uint32_t v0, uint32_t v1, uint32_t v2,
+                                                   uint32_t v3) {
+    typedef __attribute__((address_space(1))) uint64_t gu64_t;
+    if (!valid) return;
+    auto hb = [](uint32_t v) -> uint64_t { return half_bits(__uint_as_float((uint32_t)max((int)v, 0))); };
+    uint64_t w = hb(v0) | (hb(v1) << 16) | (hb(v2) << 32) | (hb(v3) << 48);
+    gu64_t *const at = reinterpret_cast<gu64_t *>(row) + slot;
+    if (keep4 != 0u) {
+        const uint64_t old = __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint64_t k = ((keep4 & 0x00000001u) ? 0x000000000000FFFFull : 0ull) | ((keep4 & 0x00000100u) ? 0x00000000FFFF0000ull : 0ull) |
+                           ((keep4 & 0x00010000u) ? 0x0000FFFF00000000ull : 0ull) | ((keep4 & 0x01000000u) ? 0xFFFF000000000000ull : 0ull);
+        w = (w & ~k) | (old & k);
+    }
+    *at = w;
 }
 
 // w[lane LN] = v for a wave-uniform v: one v_writelane_b32, no lane mask, no compare
@@ -442,6 +492,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
     static_assert(!CTRL || (S::E >= S::P && (MODE == 0 || INJECT)), "evader control: n_evaders >= n_pursuers, flexible instantiation");
     static_assert(!CTRL || !S::LIVE, "evader control has no per-env agent counts");
     static_assert(!S::TO || (MODE == 1 && INJECT && !CTRL), "the two-buffer step: the flexible step kernel only");
+    static_assert(!S::H16 || S::TO, "binary16 buffers: the two-buffer step only");
     constexpr int P = S::P, E = S::E, A = S::A, GW = S::GW, PAD = S::PAD, GSZ = S::GSZ, NS = S::NS;
     __shared__ __attribute__((aligned(16))) uint32_t L[S::LDS_DWORDS];
     const int lane = threadIdx.x;
@@ -528,7 +579,11 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
         if constexpr (MODE == 1) return isP() ? uniform_ptr(io.actions + env * P)[ulane] : 4;
         else return 4;
     };
-    auto fetch_zm = [&](int64_t env) -> uint32_t { return uniform_ptr(d.zmask + zm_env(env) * S::ZMW)[zm_lane]; };
+    auto fetch_zm = [&](int64_t env) -> uint32_t {
+        // (S::LEAN_REGS: the lane's index worked out again at each use -- one loop constant fewer in kernels that sit at their register limit)
+        if constexpr (S::LEAN_REGS) return uniform_ptr(d.zmask + zm_env(env) * S::ZMW)[S::ZM16 ? ((uint32_t)fresh(lane) & 31u) : (uint32_t)fresh(lane)];
+        else return uniform_ptr(d.zmask + zm_env(env) * S::ZMW)[zm_lane];
+    };
     wave_sync();
 #if MADRL_PW_EXP & 8
     if (d.n_envs > 0) { if (s_cst[0][0] + s_cst[NS - 1][3] + s_rel3[0] + s_src[NS - 1] + (int)cur_rec == 0x12345) io.rew[0] = 1.f; return; }
@@ -689,7 +744,16 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                 if (d.reward_global) {  // [rewards.mean()] * n_pursuers, numpy summation order
                     double all[P];
 #pragma unroll
-                    for (int k = 0; k < P; ++k) all[k] = __shfl(r, k);
+                    for (int k = 0; k < P; ++k) {
+                        if constexpr (S::LEAN_REGS) {   // lane k's value by its constant byte address: __shfl keeps `lane & 64` as a loop constant
+                            const uint64_t rb = __builtin_bit_cast(uint64_t, r);
+                            const uint32_t rl = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * k, (int)(uint32_t)rb);
+                            const uint32_t rh = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * k, (int)(uint32_t)(rb >> 32));
+                            all[k] = __builtin_bit_cast(double, ((uint64_t)rh << 32) | rl);
+                        } else {
+                            all[k] = __shfl(r, k);
+                        }
+                    }
                     if constexpr (S::LIVE) r = isLP() ? np_sum_first<P>(all, np) / (double)np : 0.0;
                     else r = np_sum_regs<P>(all) / (double)P;
                 }
@@ -816,15 +880,23 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                     // scalar address only 5 wait states later; the compiler cannot see the stores inside the asm blocks below
                     asm volatile("s_nop 4" : "+s"(orow_u));
                     const uint32_t voff = ulane * 16u;
+                    // (orow_u and voff are float32 geometry and feed store_slot_masked alone, which an S::H16 kernel cannot reach -- see the
+                    // static_assert in it: in those kernels they are values nothing dereferences)
                     // (the two-buffer pass: both rows as global pointers of their own, its loads and stores are the compiler's)
-                    [[maybe_unused]] const auto prow_g = uniform_ptr(S::TO ? io.obs_prev + env * (int64_t)(P * S::D) : io.obs);
-                    [[maybe_unused]] const auto orow_g = uniform_ptr(io.obs + env * (int64_t)(P * S::D));
+                    // (binary16 buffers, S::H16: the rows hold half as many bytes -- P * D / 2 of the pointers' float-sized units)
+                    [[maybe_unused]] const auto prow_g = uniform_ptr(S::TO ? io.obs_prev + env * (int64_t)(P * S::D / (S::H16 ? 2 : 1)) : io.obs);
+                    [[maybe_unused]] const auto orow_g = uniform_ptr(io.obs + env * (int64_t)(P * S::D / (S::H16 ? 2 : 1)));
                     const char *Lb = reinterpret_cast<const char *>(L);
                     auto cell_at = [&](int off) -> uint32_t { return *reinterpret_cast<const uint32_t *>(Lb + off); };
                     uint32_t acc = 0u;  // the new mask, slot by slot
+                    if constexpr (S::H16) {
+                        // the second pass of a fused auto-reset reads back the slots the first pass stored (half_slot_in_place): they have
+                        // all been acknowledged first
+                        if (pass == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    }
                     // the two-buffer pass (S::TO, the step's pass): per slot the elements that come from the previous buffer (one flag per byte)
                     // and the new mask bits
-                    [[maybe_unused]] uint32_t to_need[S::TO ? NS : 1], to_bits[S::TO ? NS : 1];
+                    [[maybe_unused]] uint32_t to_need[S::TO ? NS : 1], to_bits[S::TO && !S::H16 ? NS : 1];
                     static_for<0, NS>([&](auto sc) {
                         constexpr int s = decltype(sc)::value;
                         const int base = __builtin_amdgcn_ds_bpermute(s_src[s], origin);
@@ -846,7 +918,12 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                                 const bool in_row = (64 * (s + 1) <= S::NQ) ? true : (fresh(lane) + 64 * s < S::NQ);
                                 const uint32_t need4 = in_row ? (row_live ? dirty : 0x01010101u) : 0u;
                                 to_need[s] = need4;
-                                to_bits[s] = ~need4 & ~out4 & nz4;
+                                if constexpr (S::H16) {   // the new mask bits of all slots in ONE register, slot s at bit s of each byte (as in acc)
+                                    if constexpr (s == 0) to_bits[0] = ~need4 & ~out4 & nz4;
+                                    else to_bits[0] |= (~need4 & ~out4 & nz4) << s;
+                                } else {
+                                    to_bits[s] = ~need4 & ~out4 & nz4;
+                                }
                                 return;
                             }
                         }
@@ -896,30 +973,39 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                                          : "+s"(sburn) : : "scc");
                         }
 #endif
-                        const void *sb = orow_u + 4096 * (s / 4);
-                        // dirty: element k is stored iff it is inside the map, i.e. v_k != SENT, i.e. v_k < lim (unsigned); other lanes: lim = 0.
-                        // (fresh(): kept as a value, or the compiler splits `v_k < select` back into two lane masks and an s_and_b64)
-                        const uint32_t lim = (uint32_t)fresh((st - 1u < 0x01010101u) ? (int)SENT : 0);
-                        // One non-temporal float4 unless a cell must stay untouched; nothing if all four are outside and known zero.
-                        // Outside cells (SENT = -1 as an integer) are written as the +0.0f they already hold.
-                        // Whole 64-byte chunks: a slot that lies ENTIRELY outside the map and whose cells are known to hold zero normally
-                        // stores nothing -- but when another slot of its aligned group of four lanes is written, it is written too (as the
-                        // zeros it already holds), so that the group's 64 bytes leave the CU as one full chunk instead of a partial one the
-                        // memory side has to merge.  Round 4, mask equilibrium, 65 536 envs: 80.0 -> 71.6 us per launch (groups of two:
-                        // 74.0, of eight: 75.8; scripts/zmask_drift.py).  (The two-wavefront kernel, whose 32 x 32 map leaves far fewer cells outside, loses
-                        // with the same rule -- 86.5 against 80.4 us per 32 768-env launch -- and does not apply it.)
-                        // The group of four lanes is a DPP quad: a clean lane stores iff a clean lane of its quad has a cell inside the map.
-                        const uint32_t grp = quad_or(st == 0u ? (out4 ^ 0x01010101u) : 0u);
-                        const uint32_t nt = (uint32_t)fresh(st == 0u ? (int)grp : 0);
-                        const v4f_t val = {__uint_as_float((uint32_t)max((int)v0, 0)), __uint_as_float((uint32_t)max((int)v1, 0)),
-                                           __uint_as_float((uint32_t)max((int)v2, 0)), __uint_as_float((uint32_t)max((int)v3, 0))};
-                        // An outside cell with a non-zero stale value: leave it alone (Q2), store the inside cells one by one.  Plain
-                        // (L2-cached) stores: partial lines must merge in L2 -- nontemporal partial writes cost a read-modify-write
-                        // at the memory side (3x slower).  They are issued BEFORE the non-temporal store of the slot's other lanes: the
-                        // line is then in L2 when the streaming store arrives and leaves as one write (the other order: 175 us, not 77).
-                        store_slot_masked<1024 * (s % 4)>(sb, voff, v0, v1, v2, v3, val, __builtin_amdgcn_ballot_w64(v0 < lim),
-                                                          __builtin_amdgcn_ballot_w64(v1 < lim), __builtin_amdgcn_ballot_w64(v2 < lim),
-                                                          __builtin_amdgcn_ballot_w64(v3 < lim), __builtin_amdgcn_ballot_w64(nt != 0u));
+                        if constexpr (S::H16) {
+                            // binary16 buffer: the slot is 8 bytes of io.obs.  Whole slots, load-blend-store: a slot with a cell that must
+                            // stay untouched reads the first pass's word back (the same lane stored it, and it has been waited for) and
+                            // keeps those halves; outside cells known to be zero are written as the zero bits they hold.
+                            half_slot_in_place(orow_g, 64u * s + ulane, valid, clean ? 0u : dirty, v0, v1, v2, v3);
+                        } else {
+                            // (float32 geometry from here on: orow_u + 4096 (s / 4), voff = lane * 16.  The `if constexpr` keeps it out of an H16
+                            // kernel; store_slot_masked<.., S::H16> refuses to compile for one should this ever be restructured)
+                            const void *sb = orow_u + 4096 * (s / 4);
+                            // dirty: element k is stored iff it is inside the map, i.e. v_k != SENT, i.e. v_k < lim (unsigned); other lanes: lim = 0.
+                            // (fresh(): kept as a value, or the compiler splits `v_k < select` back into two lane masks and an s_and_b64)
+                            const uint32_t lim = (uint32_t)fresh((st - 1u < 0x01010101u) ? (int)SENT : 0);
+                            // One non-temporal float4 unless a cell must stay untouched; nothing if all four are outside and known zero.
+                            // Outside cells (SENT = -1 as an integer) are written as the +0.0f they already hold.
+                            // Whole 64-byte chunks: a slot that lies ENTIRELY outside the map and whose cells are known to hold zero normally
+                            // stores nothing -- but when another slot of its aligned group of four lanes is written, it is written too (as the
+                            // zeros it already holds), so that the group's 64 bytes leave the CU as one full chunk instead of a partial one the
+                            // memory side has to merge.  Round 4, mask equilibrium, 65 536 envs: 80.0 -> 71.6 us per launch (groups of two:
+                            // 74.0, of eight: 75.8; scripts/zmask_drift.py).  (The two-wavefront kernel, whose 32 x 32 map leaves far fewer cells outside, loses
+                            // with the same rule -- 86.5 against 80.4 us per 32 768-env launch -- and does not apply it.)
+                            // The group of four lanes is a DPP quad: a clean lane stores iff a clean lane of its quad has a cell inside the map.
+                            const uint32_t grp = quad_or(st == 0u ? (out4 ^ 0x01010101u) : 0u);
+                            const uint32_t nt = (uint32_t)fresh(st == 0u ? (int)grp : 0);
+                            const v4f_t val = {__uint_as_float((uint32_t)max((int)v0, 0)), __uint_as_float((uint32_t)max((int)v1, 0)),
+                                               __uint_as_float((uint32_t)max((int)v2, 0)), __uint_as_float((uint32_t)max((int)v3, 0))};
+                            // An outside cell with a non-zero stale value: leave it alone (Q2), store the inside cells one by one.  Plain
+                            // (L2-cached) stores: partial lines must merge in L2 -- nontemporal partial writes cost a read-modify-write
+                            // at the memory side (3x slower).  They are issued BEFORE the non-temporal store of the slot's other lanes: the
+                            // line is then in L2 when the streaming store arrives and leaves as one write (the other order: 175 us, not 77).
+                            store_slot_masked<1024 * (s % 4), S::H16>(sb, voff, v0, v1, v2, v3, val, __builtin_amdgcn_ballot_w64(v0 < lim),
+                                                              __builtin_amdgcn_ballot_w64(v1 < lim), __builtin_amdgcn_ballot_w64(v2 < lim),
+                                                              __builtin_amdgcn_ballot_w64(v3 < lim), __builtin_amdgcn_ballot_w64(nt != 0u));
+                        }
                     });
                     if constexpr (S::TO) {
                         if (pass == 0) {
@@ -931,7 +1017,12 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                             typedef __attribute__((address_space(1))) v4u_t gv4u_t;
                             typedef __attribute__((address_space(1))) v4f_t gv4f_t;
                             constexpr int TG = NS <= 5 ? NS : 4;
-                            auto emit = [&](auto sc, const v4u_t oldv) {
+                            // (binary16 buffers: the old slot is one 8-byte word, two halves per dword)
+                            typedef uint32_t v2u_t __attribute__((ext_vector_type(2)));
+                            typedef __attribute__((address_space(1))) v2u_t gv2u_t;
+                            using old_t = std::conditional_t<S::H16, uint64_t, v4u_t>;
+                            using gold_t = std::conditional_t<S::H16, __attribute__((address_space(1))) uint64_t, gv4u_t>;
+                            auto emit = [&](auto sc, const old_t oldv) {
                                 constexpr int s = decltype(sc)::value;
                                 const int base = __builtin_amdgcn_ds_bpermute(s_src[s], origin);
                                 const uint32_t need4 = to_need[s];
@@ -939,17 +1030,33 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                                 uint32_t w1 = (uint32_t)max((int)cell_at(base + s_cst[s][1]), 0);
                                 uint32_t w2 = (uint32_t)max((int)cell_at(base + s_cst[s][2]), 0);
                                 uint32_t w3 = (uint32_t)max((int)cell_at((int)__umul24((uint32_t)base, (uint32_t)s_rel3[s]) + s_cst[s][3]), 0);
-                                if (need4 & 0x00000001u) w0 = oldv.x;
-                                if (need4 & 0x00000100u) w1 = oldv.y;
-                                if (need4 & 0x00010000u) w2 = oldv.z;
-                                if (need4 & 0x01000000u) w3 = oldv.w;
-                                const uint32_t oldnz = (oldv.x != 0u ? 0x00000001u : 0u) | (oldv.y != 0u ? 0x00000100u : 0u) |
-                                                       (oldv.z != 0u ? 0x00010000u : 0u) | (oldv.w != 0u ? 0x01000000u : 0u);
-                                acc = (acc << 1) | to_bits[s] | (need4 & oldnz);   // the mask bit of a kept cell: "the loaded value is non-zero"
-                                const bool in_row = (64 * (s + 1) <= S::NQ) ? true : (fresh(lane) + 64 * s < S::NQ);
-                                if (in_row) {
-                                    const v4f_t wv = {__uint_as_float(w0), __uint_as_float(w1), __uint_as_float(w2), __uint_as_float(w3)};
-                                    __builtin_nontemporal_store(wv, reinterpret_cast<gv4f_t *>(orow_g) + (64u * s + ulane));
+                                if constexpr (S::H16) {
+                                    const bool in_row = (64 * (s + 1) <= S::NQ) ? true : (fresh(lane) + 64 * s < S::NQ);
+                                    // converted and packed; the kept halves come from the old word, 16 bits as they are
+                                    const uint32_t oldx = (uint32_t)oldv, oldy = (uint32_t)(oldv >> 32);
+                                    uint32_t lo = (uint32_t)half_bits(__uint_as_float(w0)) | ((uint32_t)half_bits(__uint_as_float(w1)) << 16);
+                                    uint32_t hi = (uint32_t)half_bits(__uint_as_float(w2)) | ((uint32_t)half_bits(__uint_as_float(w3)) << 16);
+                                    const uint32_t klo = ((need4 & 0x00000001u) ? 0x0000FFFFu : 0u) | ((need4 & 0x00000100u) ? 0xFFFF0000u : 0u);
+                                    const uint32_t khi = ((need4 & 0x00010000u) ? 0x0000FFFFu : 0u) | ((need4 & 0x01000000u) ? 0xFFFF0000u : 0u);
+                                    lo = (lo & ~klo) | (oldx & klo);
+                                    hi = (hi & ~khi) | (oldy & khi);
+                                    const uint32_t oldnz = ((oldx & 0xFFFFu) != 0u ? 0x00000001u : 0u) | ((oldx >> 16) != 0u ? 0x00000100u : 0u) |
+                                                           ((oldy & 0xFFFFu) != 0u ? 0x00010000u : 0u) | ((oldy >> 16) != 0u ? 0x01000000u : 0u);
+                                    acc = (acc << 1) | ((to_bits[0] >> s) & 0x01010101u) | (need4 & oldnz);   // per half: "the loaded 16 bits are non-zero"
+                                    if (in_row) __builtin_nontemporal_store(v2u_t{lo, hi}, reinterpret_cast<gv2u_t *>(orow_g) + (64u * s + ulane));
+                                } else {
+                                    if (need4 & 0x00000001u) w0 = oldv.x;
+                                    if (need4 & 0x00000100u) w1 = oldv.y;
+                                    if (need4 & 0x00010000u) w2 = oldv.z;
+                                    if (need4 & 0x01000000u) w3 = oldv.w;
+                                    const uint32_t oldnz = (oldv.x != 0u ? 0x00000001u : 0u) | (oldv.y != 0u ? 0x00000100u : 0u) |
+                                                           (oldv.z != 0u ? 0x00010000u : 0u) | (oldv.w != 0u ? 0x01000000u : 0u);
+                                    acc = (acc << 1) | to_bits[s] | (need4 & oldnz);   // the mask bit of a kept cell: "the loaded value is non-zero"
+                                    const bool in_row = (64 * (s + 1) <= S::NQ) ? true : (fresh(lane) + 64 * s < S::NQ);
+                                    if (in_row) {
+                                        const v4f_t wv = {__uint_as_float(w0), __uint_as_float(w1), __uint_as_float(w2), __uint_as_float(w3)};
+                                        __builtin_nontemporal_store(wv, reinterpret_cast<gv4f_t *>(orow_g) + (64u * s + ulane));
+                                    }
                                 }
                             };
                             static_for<0, (NS + TG - 1) / TG>([&](auto gc) {
@@ -958,15 +1065,15 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
 #pragma unroll
                                 for (int s = g0; s < g1; ++s) any |= to_need[s];
                                 if (__builtin_amdgcn_ballot_w64(any != 0u) != 0ull) {
-                                    v4u_t old[TG];
+                                    old_t old[TG];
 #pragma unroll
                                     for (int s = g0; s < g1; ++s) {
-                                        old[s - g0] = v4u_t{0u, 0u, 0u, 0u};
-                                        if (to_need[s] != 0u) old[s - g0] = reinterpret_cast<const gv4u_t *>(prow_g)[64u * s + ulane];
+                                        old[s - g0] = old_t{};
+                                        if (to_need[s] != 0u) old[s - g0] = reinterpret_cast<const gold_t *>(prow_g)[64u * s + ulane];
                                     }
                                     static_for<g0, g1>([&](auto sc) { emit(sc, old[decltype(sc)::value - g0]); });
                                 } else {
-                                    static_for<g0, g1>([&](auto sc) { emit(sc, v4u_t{0u, 0u, 0u, 0u}); });
+                                    static_for<g0, g1>([&](auto sc) { emit(sc, old_t{}); });
                                 }
                             });
                         }
@@ -995,8 +1102,13 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                 if constexpr (S::LIVE) {
                     if (!(isP() ? isLP() : eslot < ne)) myxy = NOT_HERE | (NOT_HERE << 8);
                 }
-                const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(rec_src0, myxy);
-                const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(rec_src1, myxy);
+                // (S::LEAN_REGS: worked out again, like the mask index in fetch_zm -- two loop constants fewer)
+                [[maybe_unused]] auto src_of = [&](auto kc) -> int {
+                    if constexpr (S::LEAN_REGS) return ((fresh(lane) >= 4 ? 2 * (fresh(lane) - 4) : 0) + decltype(kc)::value) * 4;
+                    else return decltype(kc)::value ? rec_src1 : rec_src0;
+                };
+                const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src_of(std::integral_constant<int, 0>{}), myxy);
+                const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src_of(std::integral_constant<int, 1>{}), myxy);
                 uint32_t w = (lo & 0xFFFFu) | (hi << 16);
                 // the uniform header / bit-set dwords go in with v_writelane (one VALU op each, no lane mask)
                 put_lane<0>(w, tick);
@@ -1044,6 +1156,9 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
 // pursuit_to_specializations.def in pursuit_to.hip)
 template <class S>
 void wave_to_launch(const WaveDev &d, const WaveIO &io, int64_t blocks, hipStream_t s);
+// ... and of a THShape / TLHShape: binary16 buffers, io.obs and io.obs_prev are the half pointers, cast (pursuit_to_f16.hip, pursuit_to_f16_live.hip)
+template <class S>
+void wave_to_f16_launch(const WaveDev &d, const WaveIO &io, int64_t blocks, hipStream_t s);
 
 }  // namespace pw
 }  // namespace madrl

@@ -64,7 +64,7 @@ class PursuitHeuristicPolicy(_DevicePolicy):
         self._act = None
 
     def sample_actions(self, obs, deterministic=True, out=None):
-        obs = obs.contiguous()
+        obs = _lib.require_float32(obs, "PursuitHeuristicPolicy").contiguous()
         R = self.R
         n_rows = obs.shape[0] * obs.shape[1]
         if self._table is None or self._table.device != obs.device:

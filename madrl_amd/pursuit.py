@@ -7,7 +7,7 @@ Two classes:
   vectorised env.  Same constructor kwargs / defaults, same `agents`, `reward_mech`,
   `reset()`, `step()`, `seed()`, `is_terminal`, `set_param_values()`,
   `update_curriculum()`, pickling by constructor arguments; tensors instead of lists:
-      reset()        -> obs  float32 [N, P, D]            (D = 3R^2(+1) or (R,R,4))
+      reset()        -> obs  float32 [N, P, D]            (D = 3R^2(+1) or (R,R,4); float16 with obs_dtype=torch.float16)
       step(actions)  -> obs, rew float32 [N, P], done bool [N], {'removed': int32 [N], ...}
 * `PursuitEvade(map_pool, **reference_kwargs)` -- N == 1 drop-in with the reference's
   exact return types (list of per-agent ndarrays, ndarray / list rewards, bool, dict), for
@@ -54,12 +54,21 @@ class PursuitAgent(Agent):
 class BatchedPursuitEvade(AbstractMAEnv):
 
     def __init__(self, map_pool, n_envs=1, device="cuda:0", seed=0, env_id_base=0, max_steps=0,
-                 auto_reset=False, threads=0, max_blocks=0, kernel="auto", per_env_counts=False, **kwargs):
+                 auto_reset=False, threads=0, max_blocks=0, kernel="auto", per_env_counts=False, obs_dtype=torch.float32, **kwargs):
+        """obs_dtype: torch.float32, or torch.float16 -- half-precision observation slots: every observation tensor of the env is float16,
+        each element the round-to-nearest-even half of the float32 value (kept cells: their 16 bits carried over), at half the bytes.
+        step() then ping-pongs between two internal buffers through madrl_pursuit_step_to_f16 (the returned view holds until the next
+        step, as documented); step_to / step_into(obs_out=) take float16 destinations."""
+        if obs_dtype not in (torch.float32, torch.float16):
+            raise ValueError("obs_dtype must be torch.float32 or torch.float16, got %r" % (obs_dtype,))
+        self.obs_dtype = obs_dtype
         self._ctor = dict(map_pool=map_pool, n_envs=n_envs, device=str(device), seed=seed,
                           env_id_base=env_id_base, max_steps=max_steps, auto_reset=auto_reset,
                           threads=threads, max_blocks=max_blocks, kernel=kernel, kwargs=dict(kwargs))
         if per_env_counts:   # (only when set: the pickles of fixed-shape batches stay what they were)
             self._ctor["per_env_counts"] = True
+        if obs_dtype is not torch.float32:   # (likewise)
+            self._ctor["obs_dtype"] = obs_dtype
         self._kernel = kernel
         # per-env agent counts: n_pursuers / n_evaders are a capacity, each env runs its own live counts (set_agent_counts)
         self.per_env_counts = bool(per_env_counts)
@@ -143,7 +152,11 @@ class BatchedPursuitEvade(AbstractMAEnv):
             dev = self.device
             self._state = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
             # IN/OUT observation buffer == the reference's persistent local_obs (Q2)
-            self._obs = torch.zeros((N, P, D), dtype=torch.float32, device=dev)
+            self._obs = torch.zeros((N, P, D), dtype=self.obs_dtype, device=dev)
+            # half-precision slots: step() goes from the current buffer into the other one of this pair (there is no in-place half step);
+            # reset() runs the float32 reset kernel on a private widened copy (_obs32, allocated at the first reset)
+            self._half_pair = (self._obs, torch.zeros_like(self._obs)) if self._half else None
+            self._obs32 = None
             self._rew = torch.zeros((N, P), dtype=torch.float32, device=dev)
             self._done = torch.zeros(N, dtype=torch.uint8, device=dev)
             self._removed = torch.zeros(N, dtype=torch.int32, device=dev)
@@ -162,7 +175,7 @@ class BatchedPursuitEvade(AbstractMAEnv):
                                           dev_index, _lib.ptr(self._state), C.byref(h)))
         self._handle = h
         self._handle_key = self._create_key()
-        if getattr(self, "_obs_is_fresh", False):   # nothing has written the buffer yet: tell the fast path (no cell "unknown" at the start)
+        if getattr(self, "_obs_is_fresh", False) and not self._half:   # nothing has written the buffer yet: tell the fast path (no cell "unknown" at the start)
             _lib.check(L.madrl_pursuit_declare_obs_zero(h, _lib.ptr(self._obs), _lib.current_stream(self.device)))
         self.handle_generation = getattr(self, "handle_generation", 0) + 1   # how many times the native handle was (re-)created
         if self.per_env_counts:   # pending counts [N, 2]: kept across re-created handles of the same capacity, at the capacity otherwise
@@ -269,6 +282,10 @@ class BatchedPursuitEvade(AbstractMAEnv):
     def _stream(self):
         return _lib.current_stream(self.device)
 
+    @property
+    def _half(self):
+        return self.obs_dtype is torch.float16
+
     def _obs_view(self):
         if self.flatten:
             return self._obs
@@ -319,8 +336,19 @@ class BatchedPursuitEvade(AbstractMAEnv):
         if mask is not None and getattr(self, "_needs_reset", False):
             raise RuntimeError("the agent counts changed (update_curriculum / set_param_values): the whole batch must be reset() once")
         self._check_obs_untouched()
-        _lib.check(_lib.lib().madrl_pursuit_reset(self._handle, _lib.ptr(mask), _lib.ptr(pos), _lib.ptr(mid),
-                                                  _lib.ptr(self._obs), self._stream()))
+        if self._half:
+            # not a hot path: the current half buffer widened to a private float32 one, the reset kernel on that, and back.  half -> float ->
+            # half is the identity for the cells the reset keeps.  (The library then knows the float32 buffer: the next half step starts
+            # from "nothing known", as every half ring does.)
+            if self._obs32 is None:
+                self._obs32 = torch.empty(self._obs.shape, dtype=torch.float32, device=self.device)
+            self._obs32.copy_(self._obs)
+            _lib.check(_lib.lib().madrl_pursuit_reset(self._handle, _lib.ptr(mask), _lib.ptr(pos), _lib.ptr(mid),
+                                                      _lib.ptr(self._obs32), self._stream()))
+            self._obs.copy_(self._obs32)
+        else:
+            _lib.check(_lib.lib().madrl_pursuit_reset(self._handle, _lib.ptr(mask), _lib.ptr(pos), _lib.ptr(mid),
+                                                      _lib.ptr(self._obs), self._stream()))
         self._was_reset, self._needs_reset, self._obs_is_fresh = True, False, False
         self._obs_version = self._version_of_obs()
         return self._obs_view()
@@ -365,6 +393,12 @@ class BatchedPursuitEvade(AbstractMAEnv):
             act = self._i32(actions, (N, P), "actions")
         # evader control (train_pursuit=False): the opponents are the pursuers, one injected action per pursuer
         eact = self._i32(evader_actions, (N, E if self.train_pursuit else P), "evader_actions")
+        if self._half:   # into the other internal buffer
+            rew = self._rew if rew_out is None else rew_out
+            dn = self._done if done_out is None else done_out
+            assert rew.dtype == torch.float32 and rew.numel() == N * P and dn.dtype == torch.uint8 and dn.numel() == N
+            self._launch_step_to(act, eact, self._half_next(), rew, dn)
+            return self._step_result(rew, dn)
         self._check_obs_untouched()
         self._obs_is_fresh = False
         rew = self._rew if rew_out is None else rew_out
@@ -380,12 +414,21 @@ class BatchedPursuitEvade(AbstractMAEnv):
         N, P, D = self.n_envs, int(self.n_pursuers), self.obs_dim
         if type(obs_out) is not torch.Tensor:
             raise TypeError("obs_out must be a torch.Tensor, got %s" % type(obs_out).__name__)
-        if obs_out.dtype is not torch.float32 or obs_out.device != self.device or not obs_out.is_contiguous() or obs_out.numel() != N * P * D:
-            raise ValueError("obs_out must be a contiguous float32 tensor of %d elements on %s (got %s, %s, %s, contiguous=%s)"
-                             % (N * P * D, self.device, tuple(obs_out.shape), obs_out.dtype, obs_out.device, obs_out.is_contiguous()))
+        if obs_out.dtype is not self.obs_dtype or obs_out.device != self.device or not obs_out.is_contiguous() or obs_out.numel() != N * P * D:
+            raise ValueError("obs_out must be a contiguous %s tensor of %d elements on %s (got %s, %s, %s, contiguous=%s)"
+                             % (str(self.obs_dtype).replace("torch.", ""), N * P * D, self.device, tuple(obs_out.shape), obs_out.dtype,
+                                obs_out.device, obs_out.is_contiguous()))
         if obs_out.data_ptr() == self._obs.data_ptr():
+            if self._half:
+                raise ValueError("obs_out is the env's current observation buffer: there is no in-place half-precision step (step() "
+                                 "goes to the env's other internal buffer)")
             return None
         return obs_out.view(N, P, D)
+
+    def _half_next(self):
+        """the internal half buffer a step() writes: the one of the pair that is not the current buffer"""
+        a, b = self._half_pair
+        return b if self._obs.data_ptr() == a.data_ptr() else a
 
     def _launch_step_to(self, act, eact, dest, rew, dn):
         """madrl_pursuit_step_to from the current observation buffer into `dest`, which becomes the current buffer: obs_buffer, the views
@@ -393,8 +436,9 @@ class BatchedPursuitEvade(AbstractMAEnv):
         the buffer (include/madrl_hip.h).  The previous buffer is left as it was and belongs to the caller again."""
         self._check_obs_untouched()   # (an in-place edit of the buffer the kept cells are read from)
         self._obs_is_fresh = False
-        _lib.check(_lib.lib().madrl_pursuit_step_to(self._handle, _lib.ptr(act), _lib.ptr(eact), _lib.ptr(self._obs), _lib.ptr(dest),
-                                                    _lib.ptr(rew), _lib.ptr(dn), _lib.ptr(self._removed), self._stream()))
+        step_to = _lib.lib().madrl_pursuit_step_to_f16 if self._half else _lib.lib().madrl_pursuit_step_to
+        _lib.check(step_to(self._handle, _lib.ptr(act), _lib.ptr(eact), _lib.ptr(self._obs), _lib.ptr(dest),
+                           _lib.ptr(rew), _lib.ptr(dn), _lib.ptr(self._removed), self._stream()))
         self._obs = dest
         self._obs_version = self._version_of_obs()
 
@@ -430,7 +474,8 @@ class BatchedPursuitEvade(AbstractMAEnv):
         """'wave' | 'generic': the kernel a step_to of this env launches ('wave': the two-buffer instantiation of its fast kernel -- one
         wavefront per env, a group of wavefronts or the crowd kernel)"""
         out = C.c_int32()
-        _lib.check(_lib.lib().madrl_pursuit_step_to_kernel_kind(self._handle, C.byref(out)))
+        kind = _lib.lib().madrl_pursuit_step_to_f16_kernel_kind if self._half else _lib.lib().madrl_pursuit_step_to_kernel_kind
+        _lib.check(kind(self._handle, C.byref(out)))
         return {_lib.KERNEL_GENERIC: "generic", _lib.KERNEL_WAVE: "wave"}[out.value]
 
     def step_into(self, actions, rew_out, done_out, obs_out=None):
@@ -444,6 +489,8 @@ class BatchedPursuitEvade(AbstractMAEnv):
         assert actions.dtype == torch.int32 and actions.is_contiguous() and actions.numel() == N * P
         assert rew_out.dtype == torch.float32 and rew_out.numel() == N * P and done_out.dtype == torch.uint8 and done_out.numel() == N
         dest = self._obs_destination(obs_out) if obs_out is not None else None
+        if dest is None and self._half:
+            dest = self._half_next()
         if dest is not None:
             self._launch_step_to(actions, None, dest, rew_out, done_out)
             return self._obs_view()
@@ -723,6 +770,8 @@ class PursuitEvade(SingleEnvDelegate, AbstractMAEnv):
     (the reference's default is an unseeded RandomPolicy, Controllers.py:11)."""
 
     def __init__(self, map_pool, device="cuda:0", **kwargs):
+        if "obs_dtype" in kwargs:   # (this class hands out float64 ndarrays, like the reference)
+            raise TypeError("PursuitEvade returns the reference's float64 observation lists; obs_dtype is BatchedPursuitEvade's")
         self._evader_controller = kwargs.pop("evader_controller", None)
         if not kwargs.get("train_pursuit", True):  # the opponents are the pursuers then (:220-224)
             self._evader_controller = kwargs.pop("pursuer_controller", None)

@@ -17,7 +17,7 @@ from . import _lib
 class Trajectory(object):
     """time-major tensors of one collect() call: actions [T,N,A(,adim)], rewards float32 [T,N,A],
     dones uint8 [T,N] (bit0 terminal, bit1 time limit; PursuitEvade / MultiWalker: bit 7 = a capacity overflow mark, no episode boundary),
-    values float32 [T+1,N,A] or None, observations float32 [T,N,A,D] or None (the observation each action was chosen from),
+    values float32 [T+1,N,A] or None, observations [T,N,A,D] in the env's observation dtype or None (the observation each action was chosen from),
     last_observation float32 [N,A,D] or None (the observation after the last step: observations[0] of the next collect()),
     returns / advantages float32 [T,N,A]."""
 
@@ -98,7 +98,7 @@ class RolloutCollector(object):
         b["advantages"] = torch.empty_like(b["returns"]) if val is not None else None
         b["observations"] = b["last_observation"] = None
         if self.store_observations and self._slots:   # [T + 1] slots: the step kernel of step t writes slot t + 1
-            self._obs_slots = torch.empty((T + 1,) + tuple(obs.shape), dtype=torch.float32, device=dev)
+            self._obs_slots = torch.empty((T + 1,) + tuple(obs.shape), dtype=obs.dtype, device=dev)   # (float16 over a half-precision PursuitEvade)
             b["observations"], b["last_observation"] = self._obs_slots[:T], self._obs_slots[T]
             # The env gets its destinations through a second handle on the same memory with an in-place-operation counter of its own
             # (`.data`): the copy into slot 0 below must not look to BatchedPursuitEvade like an edit of its current buffer, slot T
@@ -106,7 +106,7 @@ class RolloutCollector(object):
             # Trajectory.last_observation by the caller is therefore not noticed by the env: call env.invalidate_obs() after one.
             self._env_slots = self._obs_slots.data
         elif self.store_observations:
-            b["observations"] = torch.empty((T,) + tuple(obs.shape), dtype=torch.float32, device=dev)
+            b["observations"] = torch.empty((T,) + tuple(obs.shape), dtype=obs.dtype, device=dev)
         return b
 
     def _act(self, obs):

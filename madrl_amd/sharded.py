@@ -124,7 +124,8 @@ class StreamSharded(object):
 
     def _native_pursuit(self):
         from .pursuit import BatchedPursuitEvade
-        return all(type(e) is BatchedPursuitEvade for e in self.envs)
+        # (madrl_pursuit_step_sharded writes float32 rows in place: sub-batches with half-precision observations step one by one)
+        return all(type(e) is BatchedPursuitEvade and e.obs_dtype is torch.float32 for e in self.envs)
 
     def _step_pursuit_native(self, parts, fork, join):
         """PursuitEvade sub-batches: ONE call of the C ABI forks, launches every sub-batch on its stream and joins

@@ -141,7 +141,7 @@ class ObservationBuffer(_Wrapper):
         return out
 
     def _push(self, obs, reset_mask, active_mask=None):
-        obs = obs.contiguous()
+        obs = _lib.require_float32(obs, "ObservationBuffer").contiguous()
         if self._buf is None:
             self._buf = torch.zeros(tuple(obs.shape) + (self._buffer_size,), dtype=torch.float32, device=obs.device)  # :150
         n = obs.numel()
@@ -211,7 +211,7 @@ class StandardizedEnv(_Wrapper):
         """mask (uint8 [N], a partial reset): the envs outside it keep their statistics and their standardised rows, as under the fused form"""
         if not self._enable_obsnorm:
             return obs
-        obs = obs.contiguous()
+        obs = _lib.require_float32(obs, "StandardizedEnv").contiguous()
         if self._obs_mean is None:  # :229-230
             self._obs_mean = torch.zeros(obs.shape, dtype=torch.float64, device=obs.device)
             self._obs_var = torch.ones(obs.shape, dtype=torch.float64, device=obs.device)
