@@ -70,9 +70,12 @@ struct MwDev {
     uint32_t *spare_state; // [n_envs] records like `state`
     float *spare_obs;      // [n_envs][W][D]: the observation MultiWalkerEnv.reset returns for that episode
     uint32_t *ready_step;  // [n_envs] 0: the spare is stale / consumed, SPARE_BUSY: being prepared, else the step() call that finished it
-    uint32_t *dirty_list;  // [2][n_envs] envs whose spare is stale: list (step_id & 1) is rebuilt by step() call step_id, which appends to the other
+    uint32_t *dirty_list;  // [2][n_envs] envs whose spare is stale: list (*step_count & 1) is rebuilt by that step() call, which appends to the other
     uint32_t *n_dirty;     // [2]
-    uint32_t step_id;      // this step() call (starts at 1; reset calls carry the last one)
+    // The step() calls so far (the first one counts 1; a reset reads the last one's).  ON THE DEVICE, advanced by mw_begin_step_kernel: a value
+    // passed with the launch is frozen in a captured hipGraph, and every replay of an odd number of steps would then start with the parity its
+    // predecessor ended on -- emptying the list that one had just appended to and rebuilding spares marked ready.
+    uint32_t *step_count;
     int32_t spare_blocks;  // leading blocks of a step launch that work on spares
 };
 struct MwIO {
@@ -184,7 +187,7 @@ struct GroupPar {
 // the launch copies the spare over the live record and hands out its observation; the env goes on a list, and the NEXT step() call
 // rebuilds the listed spares in the leading blocks of its own launch (16 per wavefront).  Only an env whose spare is not ready (two
 // episodes ending within two steps) takes the second launch: reset + trailing step for the envs marked `pending`, which is also what
-// reset(mask) runs.  A spare finished by the current call is never taken (ready_step == step_id): which order the hardware runs the
+// reset(mask) runs.  A spare finished by the current call is never taken (ready_step == the call's number): which order the hardware runs the
 // blocks in must not decide which path an env takes.
 constexpr uint32_t SPARE_BUSY = 0xFFFFFFFFu;
 
@@ -227,7 +230,8 @@ void mw_step_kernel(const MwDev d, const MwIO io, const int mode, const int pend
     uint32_t *s_done = reinterpret_cast<uint32_t *>(s_rew + mw::MAX_WALKERS);
     constexpr int RW_OFF = (4 * mw::MAX_WALKERS + 4 + 7) / 8 * 8 < 32 ? 32 : (4 * mw::MAX_WALKERS + 4 + 7) / 8 * 8;   // env_observe's doubles, after the two above
     const int W = M.W;
-    const uint32_t cur = d.step_id & 1u, nxt = cur ^ 1u;
+    const uint32_t step_id = *d.step_count;   // (no launch that reads it writes it: mw_begin_step_kernel runs ahead of them)
+    const uint32_t cur = step_id & 1u, nxt = cur ^ 1u;
     const bool spare = mode == 0 && (int)blockIdx.x < d.spare_blocks;
     int64_t env = ((int64_t)blockIdx.x - (mode == 0 && !spare ? d.spare_blocks : 0)) * EPW + g;
     bool active;
@@ -337,13 +341,13 @@ void mw_step_kernel(const MwDev d, const MwIO io, const int mode, const int pend
                 // the spare must hold THIS record's next episode: a caller that restored or teacher-forced the live records through
                 // state_buffer (Hot::episode included) leaves spares built for another episode behind -- those take the second launch
                 const uint32_t sp_episode = reinterpret_cast<const mw::Hot *>(d.spare_state + env * (int64_t)d.world_dw)->episode;
-                take = (rs != 0 && rs != SPARE_BUSY && rs != d.step_id && sp_episode == Wd.episode + 1u) ? 1u : 2u;   // 1: the spare is ready, 2: the second launch
+                take = (rs != 0 && rs != SPARE_BUSY && rs != step_id && sp_episode == Wd.episode + 1u) ? 1u : 2u;   // 1: the spare is ready, 2: the second launch
             }
             d.pending[env] = take == 2 ? 1 : 0;
             *s_done |= take << 8;
         } else {
             Wd.t = 0;   // the reset's trailing step does not count (:357)
-            if (spare) d.ready_step[env] = d.step_id;
+            if (spare) d.ready_step[env] = step_id;
             else d.pending[env] = 0;
         }
     }
@@ -374,12 +378,17 @@ void mw_step_kernel(const MwDev d, const MwIO io, const int mode, const int pend
     if (PH == PH_TOI) MW_TSTAMP(1, 5);
 }
 
-// first thing in a step() call: the list the call's own launch will append to starts empty
-__global__ void mw_begin_step_kernel(const MwDev d) { if (threadIdx.x == 0 && blockIdx.x == 0) d.n_dirty[(d.step_id & 1u) ^ 1u] = 0; }
-__global__ void mw_init_spares_kernel(const MwDev d) {   // every spare is stale: all envs on the list of the first step() call (step_id 1)
+// first thing in a step() call of an auto-reset env: the call gets its number, and (spares in use) the list its own launch will append to starts empty
+__global__ void mw_begin_step_kernel(const MwDev d, const int use_spares) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const uint32_t id = *d.step_count + 1u;
+    *d.step_count = id;
+    if (use_spares) d.n_dirty[(id & 1u) ^ 1u] = 0;
+}
+__global__ void mw_init_spares_kernel(const MwDev d) {   // every spare is stale: all envs on the list of the first step() call (number 1)
     const int64_t env = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (env < d.n_envs) { d.ready_step[env] = 0; d.dirty_list[d.n_envs + env] = (uint32_t)env; }
-    if (env == 0) { d.n_dirty[0] = 0; d.n_dirty[1] = (uint32_t)d.n_envs; }
+    if (env == 0) { d.n_dirty[0] = 0; d.n_dirty[1] = (uint32_t)d.n_envs; *d.step_count = 0; }
 }
 
 __global__ void mw_get_bodies_kernel(const MwDev d, float *bodies, uint8_t *flags, float *terrain) {
@@ -457,7 +466,6 @@ struct MwHandle {
     MwDev dev;
     int device;
     int64_t max_blocks;
-    uint32_t step_id;
     int use_spares, fused;
     void *model_dev;
     int NB, NT;
@@ -490,12 +498,10 @@ void mw_launch_step(const MwHandle *h, const MwDev &d, const MwIO &io, int mode,
 void mw_launch_all(MwHandle *h, const MwIO &io, int mode, hipStream_t s) {
     MwDev d = h->dev;
     d.spare_blocks = 0;
-    d.step_id = h->step_id;
     if (mode == 1) {   // MultiWalkerEnv.step
-        d.step_id = ++h->step_id;
-        if (h->cfg.auto_reset && h->use_spares) {
-            hipLaunchKernelGGL(mw_begin_step_kernel, dim3(1), dim3(64), 0, s, d);
-            d.spare_blocks = (int32_t)((d.n_envs + EPW - 1) / EPW);   // room for every spare (a common horizon ends all episodes at once); mostly a handful do something
+        if (h->cfg.auto_reset) {   // (without auto-reset no spare is ever built and nothing looks at the call's number)
+            hipLaunchKernelGGL(mw_begin_step_kernel, dim3(1), dim3(64), 0, s, d, h->use_spares);
+            if (h->use_spares) d.spare_blocks = (int32_t)((d.n_envs + EPW - 1) / EPW);   // room for every spare (a common horizon ends all episodes at once); mostly a handful do something
         }
         mw_launch_step(h, d, io, 0, 0, s);
         if (!h->cfg.auto_reset) return;
@@ -529,7 +535,7 @@ int k_state_bytes(const madrl_multiwalker_config *cfg, int64_t n_envs, uint64_t 
     memset(&M, 0, sizeof(M));
     mw::build_model(M, cfg->n_walkers);
     // per env: the world record, then the step's Scratch (manifolds + schedule handed from launch to launch); one byte per env; then the
-    // spares: a second record per env, its observation, three dwords per env (state, two lists), the lists' lengths
+    // spares: a second record per env, its observation, three dwords per env (state, two lists), four dwords: the lists' lengths, the step() counter, one unused
     const uint64_t rec = (uint64_t)(align_up(sizeof(mw::World), 16) + mw_scratch_bytes(M));
     const uint64_t od = (uint64_t)cfg->n_walkers * (uint64_t)(mw::OBS_DIM - 1 + (cfg->one_hot ? mw::MAX_AGENTS_ID : 1));
     *out_bytes = rec * (uint64_t)n_envs + align_up((uint64_t)n_envs, 16) + rec * (uint64_t)n_envs + align_up(od * 4 * (uint64_t)n_envs, 16) + 12 * (uint64_t)n_envs + 16;
@@ -585,9 +591,9 @@ int k_create(const madrl_multiwalker_config *cfg, int64_t n_envs, int32_t device
         d.ready_step = (uint32_t *)p; p += 4 * (size_t)n_envs;
         d.dirty_list = (uint32_t *)p; p += 8 * (size_t)n_envs;
         d.n_dirty = (uint32_t *)p;
+        d.step_count = d.n_dirty + 2;   // (the third of the four dwords behind the lists)
     }
     d.cold_q = (int32_t)(align_up(offsetof(mw::Cold, slot) + (size_t)M.n_slots * sizeof(mw::Slot), 16) / 16);
-    h->step_id = 0;
     h->use_spares = 1;
     h->fused = 0;
     d.ty_bytes = (int32_t)align_up((size_t)M.NT * 4, 16);
