@@ -3,9 +3,36 @@ import glob
 import os
 
 import numpy as np
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def bits(t):
+    """a float32 tensor as int32: a comparison in every bit, which also holds for NaN and tells -0.0 from +0.0"""
+    t = t.contiguous()
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+def same_bits(a, b):
+    return torch.equal(bits(a), bits(b))
+
+
+def i32(a):
+    return np.ascontiguousarray(a, np.float32).view(np.int32)
+
+
+def raw(a):
+    """the bits of a numpy array, whatever its type (float32 -> uint32, the saved mask int64 / uint64 -> uint64, tick int32 / uint32 -> uint32)"""
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
+
+
+def slots(cap, tri):
+    """the slots (at the capacity) of the particles of a live triple, in the live class order"""
+    (A, B, _C), (a, b, c) = cap, tri
+    return np.r_[np.arange(a), A + np.arange(b), A + B + np.arange(c)]
 
 
 def pursuit_golden_files():

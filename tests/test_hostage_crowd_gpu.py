@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import raw, same_bits
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL = 1e-5
@@ -25,21 +27,10 @@ def _mk(*args, n_envs, crowd=True, **kw):
     return BatchedContinuousHostageWorld(*args, n_envs=n_envs, device=DEV, crowd=crowd, **kw)
 
 
-def _bits(t):
-    t = t.contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def _raw(a):
-    """the bits of a numpy array, whatever its type (float32 -> int32, the saved mask int64 / uint64 -> uint64, tick int32 / uint32 -> uint32)"""
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
-
-
 def _assert_state_equal(env, orc, where):
     gst, ost = env.get_state(), orc.get_state()
     for k in STATE_KEYS:
-        assert np.array_equal(_raw(gst[k].cpu().numpy()), _raw(ost[k])), "state %s, %s" % (k, where)
+        assert np.array_equal(raw(gst[k].cpu().numpy()), raw(ost[k])), "state %s, %s" % (k, where)
 
 
 @pytest.mark.parametrize("path", FILES, ids=gid)
@@ -212,18 +203,18 @@ def test_crowd_equals_the_one_wavefront_kernel(case):
     kw = dict(kw, seed=5, env_id_base=9, max_steps=15, auto_reset=True, action_scale=0.03, bad_speed=0.03)
     a, b = _mk(*args, n_envs=N, crowd=True, **kw), _mk(*args, n_envs=N, crowd=False, **kw)
     assert (a.kernel_kind, b.kernel_kind) == ("crowd", "wave")
-    assert torch.equal(_bits(a.reset()), _bits(b.reset()))
+    assert same_bits(a.reset(), b.reset())
     g = torch.Generator(device="cpu").manual_seed(3)
     for t in range(40):
         act = (torch.rand((N, args[0], 2), generator=g) * 2 - 1).to(DEV)
         oa, ra, da, ia = a.step(act)
         ob, rb, db, ib = b.step(act)
-        assert torch.equal(_bits(oa), _bits(ob)), "obs step %d" % t
-        assert torch.equal(_bits(ra), _bits(rb)) and torch.equal(da, db), "rewards / done step %d" % t
+        assert same_bits(oa, ob), "obs step %d" % t
+        assert same_bits(ra, rb) and torch.equal(da, db), "rewards / done step %d" % t
         assert torch.equal(ia["ho_saved"], ib["ho_saved"]) and torch.equal(ia["cr_encs"], ib["cr_encs"]), "info step %d" % t
         sa, sb = a.get_state(), b.get_state()
         for k in sa:
-            assert torch.equal(_bits(sa[k]), _bits(sb[k])), "state %s step %d" % (k, t)
+            assert same_bits(sa[k], sb[k]), "state %s step %d" % (k, t)
 
 
 def test_contact_tests_at_the_threshold_match_the_sqrt_formulation():
@@ -311,7 +302,7 @@ def test_crowd_env_interface():
     orc.set_state(pos=pos, vel=vel, key=key, bomb=bomb, saved=saved, flags=flags, t=t, tick=tick.view(np.uint32))
     st = env.get_state()
     for k, v in (("pos", pos), ("vel", vel), ("key", key), ("bomb", bomb), ("saved", saved), ("flags", flags), ("t", t), ("tick", tick)):
-        assert np.array_equal(_raw(st[k].cpu().numpy()), _raw(v)), k
+        assert np.array_equal(raw(st[k].cpu().numpy()), raw(v)), k
     obs, rew, done, info = env.step(act)
     oobs, orew, odone, oinfo = orc.step(act)
     assert np.array_equal(obs.cpu().numpy(), oobs) and np.array_equal(rew.cpu().numpy(), orew) and np.array_equal(done.cpu().numpy(), odone != 0)
@@ -362,15 +353,15 @@ def test_stream_sharded_halves_equal_the_whole_batch():
     full = mk(N, 40, DEV)
     sh = StreamSharded(mk, N, n_streams=2, env_id_base=40, device=DEV)
     assert [e.kernel_kind for e in sh.envs] == ["crowd", "crowd"]
-    assert torch.equal(_bits(full.reset()), _bits(torch.cat(sh.reset())))
+    assert same_bits(full.reset(), torch.cat(sh.reset()))
     g = torch.Generator(device="cpu").manual_seed(1)
     dones = 0
     for t in range(20):
         a = (torch.rand((N, args[0], 2), generator=g) * 2 - 1).to(DEV)
         o, r, d, _ = full.step(a)
         parts = sh.step(a)
-        assert torch.equal(_bits(o), _bits(torch.cat([p[0] for p in parts]))), t
-        assert torch.equal(_bits(r), _bits(torch.cat([p[1] for p in parts]))) and torch.equal(d, torch.cat([p[2] for p in parts])), t
+        assert same_bits(o, torch.cat([p[0] for p in parts])), t
+        assert same_bits(r, torch.cat([p[1] for p in parts])) and torch.equal(d, torch.cat([p[2] for p in parts])), t
         dones += int(d.sum())
     assert dones >= N
 
@@ -392,10 +383,10 @@ def test_rollout_collector_over_a_crowd_env(graph):
         traj = col.collect()
         torch.cuda.synchronize()
         for t in range(H):
-            assert torch.equal(_bits(traj.observations[t]), _bits(obs)), (it, t)
+            assert same_bits(traj.observations[t], obs), (it, t)
             act = policy(obs)
-            assert torch.equal(_bits(traj.actions[t]), _bits(act)), (it, t)
+            assert same_bits(traj.actions[t], act), (it, t)
             obs, rew, done, _info = env.step(act)
-            assert torch.equal(_bits(traj.rewards[t]), _bits(rew)) and torch.equal(traj.dones[t] != 0, done), (it, t)
-        assert torch.equal(_bits(traj.last_observation), _bits(obs)), it
+            assert same_bits(traj.rewards[t], rew) and torch.equal(traj.dones[t] != 0, done), (it, t)
+        assert same_bits(traj.last_observation, obs), it
     assert int((traj.dones != 0).sum()) >= N   # max_steps=5: episodes ended and restarted inside the horizon

@@ -12,13 +12,16 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import bits, i32, raw, same_bits, slots
+from live_twins import (HOSTAGE_EVENTS as EVENTS, LiveTwins, all_h, assert_collector_equals_stepping_by_hand, assert_obs_out_leaves_no_nan,
+                        hostage, lockstep)
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL = 1e-5
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED, BASE = 77, 500
 STATE_KEYS = ("key", "bomb", "saved", "flags", "t", "tick")
-EVENTS = ("saves", "criminal_hits", "gate_openings", "bombings", "all_saved", "time_limit")
 
 # test_hostage_crowd_gpu.py::BEYOND["62_particles"] as a capacity
 CAP_62 = ((12, 20, 30), 2, dict(n_sensors=16, action_scale=0.03, bad_speed=0.03))
@@ -33,160 +36,41 @@ def _mk(*args, n_envs, crowd=True, **kw):
     return BatchedContinuousHostageWorld(*args, n_envs=n_envs, device=DEV, crowd=crowd, **kw)
 
 
-def _bits(t):
-    t = t.contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def _i32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
-
-
-def _raw(a):
-    """the bits of a numpy array, whatever its type (the saved mask int64 / uint64 -> uint64, tick int32 / uint32 -> uint32)"""
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
-
-
 def _np(t):
     return t.cpu().numpy()
 
 
-def _slots(cap, tri):
-    """the slots (at the capacity) of the particles of a live triple, in the live class order"""
-    (R, H, _C), (r, h, c) = cap, tri
-    return np.r_[np.arange(r), R + np.arange(h), R + H + np.arange(c)]
+def _run(cap, coop, kw, triples, N, H, **more):
+    return LiveTwins(hostage(cap, coop, kw, SEED, BASE, "crowd", _mk), triples, N, H, **more)
 
 
-def _all_h(h):
-    return np.uint64(2 ** int(h) - 1)
-
-
-class LiveRun(object):
-    """a per-env-counts batch and its oracle twins; `cur[n]` is the index of the triple env n runs, `pend[n]` of the one it takes next.
-    The protocol of test_waterworld_live_counts_gpu.py::LiveRun; `ev[q]` tallies, from the oracle's outputs alone, what happened among
-    the envs that ran triple q."""
-
-    def __init__(self, cap, coop, kw, triples, N, H, deal=None, auto_reset=True):
-        from oracle import hostage as ho
-        self.cap, self.coop, self.kw, self.triples, self.N, self.H = tuple(cap), coop, kw, [tuple(t) for t in triples], N, H
-        self.env = _mk(*cap, coop, 1, n_envs=N, per_env_counts=True, seed=SEED, env_id_base=BASE, max_steps=H, auto_reset=auto_reset, **kw)
-        assert self.env.kernel_kind == "crowd"
-        self.twins = [ho.HostageOracle(*tri, coop, 1, n_envs=N, seed=SEED, env_id_base=BASE, max_steps=H, dtype=np.float32, **kw)
-                      for tri in self.triples]
-        self.started = False   # live counts start at the capacity; the first reset deals the triples
-        self.cur = np.full(N, -1)
-        self.pend = self.cur.copy()
-        self.set_pending(np.arange(N) % len(self.triples) if deal is None else deal)
-        self.ev = [dict.fromkeys(EVENTS, 0) for _ in self.triples]
-        self.resets = 0
-
-    def set_pending(self, idx, mask=None):
-        idx = np.broadcast_to(np.asarray(idx), (self.N,))
-        tri = np.asarray(self.triples)[idx]
-        self.env.set_particle_counts(tri[:, 0], tri[:, 1], tri[:, 2], mask=mask)
-        self.pend = np.where(np.ones(self.N, bool) if mask is None else np.asarray(mask, bool), idx, self.pend)
-
-    def _reset_twins(self, env_mask, own_done=False):
-        """the envs of env_mask take their pending triple: such an env's new twin gets the env's tick and resets it (its key is the env's
-        already: every twin had its first reset at tick 0).  own_done: every twin also resets the envs its own step ended (they run along)"""
-        new = np.where(env_mask, self.pend, self.cur)
-        ticks = [o.get_state()["tick"] for o in self.twins]
-        for q, o in enumerate(self.twins):
-            m_in = env_mask & (new == q)
-            tk = ticks[q].copy()
-            for n in np.nonzero(m_in & (self.cur != q))[0]:
-                tk[n] = ticks[self.cur[n]][n]
-            o.set_state(tick=tk)
-            m = m_in | (o.done.astype(bool) if own_done else False)
-            if m.any():
-                o.reset(mask=m.astype(np.uint8))
-        self.cur = new
-
-    def reset(self, mask=None):
-        m = np.ones(self.N, bool) if mask is None else np.asarray(mask, bool)
-        if not self.started:
-            assert mask is None   # the first reset: every env leaves the capacity for its dealt triple; all ticks are 0
-            self.started, self.cur = True, self.pend.copy()
-            for o in self.twins:
-                o.reset()
-        else:
-            self._reset_twins(m)
-        self.obs = _np(self.env.reset(mask=None if mask is None else m.astype(np.uint8)))
-        self.check("reset")
-
-    def stage(self):
-        """Random actions never open the gate: every twin is staged with stage() of test_hostage_crowd_gpu.py on its own triple, and the
-        live batch through set_state(counts=, pos=, vel=, saved=, flags=), each env's rows from its twin, scattered into slots; the slots
-        that hold no particle are given values that would matter if they were kept"""
-        from test_hostage_crowd_gpu import stage
-        N, NPc = self.N, sum(self.cap)
-        rng = np.random.RandomState(9)
-        pos, vel = rng.uniform(0, 1, (N, NPc, 2)).astype(np.float32), rng.uniform(-.03, .03, (N, NPc, 2)).astype(np.float32)
-        saved, flags = np.zeros(N, np.uint64), np.zeros(N, np.uint8)
-        for q, (o, tri) in enumerate(zip(self.twins, self.triples)):
-            st = o.get_state()
-            sg = stage(st, tri + (self.coop,))
-            o.set_state(**sg)
-            idx, s = np.nonzero(self.cur == q)[0], _slots(self.cap, tri)
-            pos[np.ix_(idx, s)], vel[np.ix_(idx, s)] = sg["pos"][idx], st["vel"][idx]
-            saved[idx], flags[idx] = sg["saved"][idx], sg["flags"][idx]
-        full = np.uint64(2 ** 64 - 1)   # bits at or above an env's hostage count: set_state(counts=) clears them
-        hh = np.asarray(self.triples)[self.cur][:, 1]
-        junk = np.array([full & ~_all_h(h) for h in hh], np.uint64)
-        self.env.set_state(counts=np.asarray(self.triples)[self.cur], pos=pos, vel=vel, saved=saved | junk, flags=flags)
-        self.check("staged", obs=False)
-
-    def step(self, act, tag):
-        gate0 = [o.get_state()["flags"] & 1 for o in self.twins]
-        obs, rew, done, info = self.env.step(act)
-        rew, done = _np(rew), _np(done)
-        saves, hits = _np(info["ho_saved"]), _np(info["cr_encs"])
-        for q, (o, (r, h, _c)) in enumerate(zip(self.twins, self.triples)):
-            o.step(act[:, :r])
-            idx = self.cur == q
-            assert np.array_equal(done[idx], o.done[idx].astype(bool)), "done %s" % tag
-            assert np.array_equal(saves[idx], o.info[idx, 0]) and np.array_equal(hits[idx], o.info[idx, 1]), "info %s" % tag
-            assert np.array_equal(_i32(rew[idx, :r]), _i32(o.rew[idx])), "rewards %s: %s" % (tag, np.abs(rew[idx, :r] - o.rew[idx]).max())
-            assert not _i32(rew[idx, r:]).any(), "rewards of absent rescuers %s" % tag
-            mid, ev, d, all_h = o.get_state(), self.ev[q], idx & (o.done != 0), _all_h(h)   # the tallies of free_run_oracle, per triple
-            ev["saves"] += int(o.info[idx, 0].sum()); ev["criminal_hits"] += int(o.info[idx, 1].sum())
-            ev["gate_openings"] += int(((mid["flags"] & 1) & ~gate0[q] & 1)[idx].sum())
-            ev["bombings"] += int((d & ((mid["flags"] & 2) != 0)).sum())
-            ev["all_saved"] += int((d & ((mid["saved"] & all_h) == all_h)).sum())
-            ev["time_limit"] += int((d & (mid["t"] >= self.H) & ((mid["flags"] & 2) == 0) & ((mid["saved"] & all_h) != all_h)).sum())
-        self.resets += int(done.sum())
-        self._reset_twins(done, own_done=True)
-        self.obs = _np(obs)
-        self.check(tag)
-        return done
-
-    def check(self, tag, obs=True):
-        st = {k: _np(v) for k, v in self.env.get_state().items()}
-        pending, live = self.env.particle_counts()
-        assert np.array_equal(_np(live), np.asarray(self.triples)[self.cur]), "live counts %s" % tag
-        assert np.array_equal(_np(pending), np.asarray(self.triples)[self.pend]), "pending counts %s" % tag
-        assert np.array_equal(st["counts"], _np(live))
-        for q, (o, tri) in enumerate(zip(self.twins, self.triples)):
-            idx, r = self.cur == q, tri[0]
-            if not idx.any():
-                continue
-            if obs:
-                assert np.array_equal(_i32(self.obs[idx, :r]), _i32(o.obs[idx])), "obs %s: %g" % (tag, np.abs(self.obs[idx, :r] - o.obs[idx]).max())
-                assert not _i32(self.obs[idx, r:]).any(), "rows of absent rescuers are not +0.0, %s" % tag
-            ost, s = o.get_state(), _slots(self.cap, tri)
-            gone = np.setdiff1d(np.arange(sum(self.cap)), s)
-            assert np.array_equal(_i32(st["pos"][idx][:, s]), _i32(ost["pos"][idx])), "pos %s" % tag
-            assert np.array_equal(_i32(st["vel"][idx][:, s]), _i32(ost["vel"][idx])), "vel %s" % tag
-            assert (st["pos"][idx][:, gone] == -1.0).all() and not _i32(st["vel"][idx][:, gone]).any(), "absent slots %s" % tag
-            for k in STATE_KEYS:
-                assert np.array_equal(_raw(st[k][idx]), _raw(ost[k][idx])), "state %s, %s" % (k, tag)
+def _stage(run, coop):
+    """Random actions never open the gate: every twin is staged with stage() of test_hostage_crowd_gpu.py on its own triple, and the
+    live batch through set_state(counts=, pos=, vel=, saved=, flags=), each env's rows from its twin, scattered into slots; the slots
+    that hold no particle are given values that would matter if they were kept"""
+    from test_hostage_crowd_gpu import stage
+    N, NPc = run.N, sum(run.cap)
+    rng = np.random.RandomState(9)
+    pos, vel = rng.uniform(0, 1, (N, NPc, 2)).astype(np.float32), rng.uniform(-.03, .03, (N, NPc, 2)).astype(np.float32)
+    saved, flags = np.zeros(N, np.uint64), np.zeros(N, np.uint8)
+    for q, (o, tri) in enumerate(zip(run.twins, run.triples)):
+        st = o.get_state()
+        sg = stage(st, tri + (coop,))
+        o.set_state(**sg)
+        idx, s = np.nonzero(run.cur == q)[0], slots(run.cap, tri)
+        pos[np.ix_(idx, s)], vel[np.ix_(idx, s)] = sg["pos"][idx], st["vel"][idx]
+        saved[idx], flags[idx] = sg["saved"][idx], sg["flags"][idx]
+    full = np.uint64(2 ** 64 - 1)   # bits at or above an env's hostage count: set_state(counts=) clears them
+    hh = np.asarray(run.triples)[run.cur][:, 1]
+    junk = np.array([full & ~all_h(h) for h in hh], np.uint64)
+    run.env.set_state(counts=np.asarray(run.triples)[run.cur], pos=pos, vel=vel, saved=saved | junk, flags=flags)
+    run.check("staged", obs=False)
 
 
 def _free_run(cap, coop, kw, triples, N, T, H):
-    run = LiveRun(cap, coop, kw, triples, N, H)
+    run = _run(cap, coop, kw, triples, N, H)
     run.reset()
-    run.stage()
+    _stage(run, coop)
     rng = np.random.RandomState(1)
     for t in range(T):
         run.step(rng.uniform(-1, 1, size=(N, cap[0], 2)).astype(np.float32), "step %d" % t)
@@ -201,7 +85,7 @@ def _every_event_per_triple(run):
 
 
 def _every_event_somewhere(run):
-    total = {k: sum(ev[k] for ev in run.ev) for k in EVENTS}
+    total = {k: run.total(k) for k in EVENTS}
     assert all(v > 0 for v in total.values()), total
 
 
@@ -239,7 +123,7 @@ def test_counts_change_at_a_reset_not_before():
     one growing change set mid-episode: the set of changed envs is the set of envs whose own episode has ended, step by step"""
     (cap, coop, kw), N, H = CAP_62, 20, 9
     tri = TRI_62[:3] + [(1, 1, 1)]
-    run = LiveRun(cap, coop, kw, tri, N, H, deal=np.arange(N) % 2)   # (12, 20, 30) and (11, 19, 29)
+    run = _run(cap, coop, kw, tri, N, H, deal=np.arange(N) % 2)   # (12, 20, 30) and (11, 19, 29)
     run.reset()
     rng = np.random.RandomState(2)
     act = lambda: rng.uniform(-1, 1, size=(N, cap[0], 2)).astype(np.float32)
@@ -250,7 +134,7 @@ def test_counts_change_at_a_reset_not_before():
     run.step(act(), "after the stagger")
     ages = _np(run.env.get_state()["t"])
     assert set(ages[young]) == {2} and set(ages[~young]) == {5}
-    run.stage()                                 # by env index modulo 5: an all-saved termination, a gate opening, a bombing, a save, nothing
+    _stage(run, coop)                                 # by env index modulo 5: an all-saved termination, a gate opening, a bombing, a save, nothing
     # one shrinking change and one growing change, on all envs in the middle of their episodes
     old = run.cur.copy()
     run.set_pending(np.where(old == 0, 2, 0))   # (12, 20, 30) -> (5, 3, 20), (11, 19, 29) -> (12, 20, 30)
@@ -261,12 +145,12 @@ def test_counts_change_at_a_reset_not_before():
         done = run.step(act(), "changing %d" % t)   # (check(): live == the twin each env is compared with, pending as set)
         assert np.array_equal(run.cur != old, switched | done), "an env changes when its own episode ends, not before"
         shrunk = done & (old == 0)
-        assert not _i32(run.obs[shrunk, 5:]).any()  # the reset pass zeroes the rows between the new and the old rescuer count
+        assert not i32(run.obs[shrunk, 5:]).any()  # the reset pass zeroes the rows between the new and the old rescuer count
         if t == 0:   # only a staged env can end this early (ages 3 and 6 of 9), and not one whose gate stays closed
             assert done.any() and not done[np.isin(np.arange(N) % 5, (1, 4))].any()
         switched |= done
     assert switched.all() and np.array_equal(run.cur, run.pend)
-    ended = {k: sum(ev[k] for ev in run.ev) for k in EVENTS}
+    ended = {k: run.total(k) for k in EVENTS}
     assert ended["bombings"] > 0 and ended["all_saved"] > 0 and ended["time_limit"] > 0, ended
     # reset(mask=) applies the pending counts to the masked envs only
     before = run.cur.copy()
@@ -296,7 +180,7 @@ def test_teacher_forcing_through_the_slotted_layout(name):
     ckw = dict(kw, n_good=cap[0], n_hostages=cap[1], n_bad=cap[2])
     env = _mk(n_envs=T, per_env_counts=True, **ckw)
     orc = ho.HostageOracle(n_envs=T, sensors=g["sensors"], dtype=np.float32, **kw)
-    s, NPc = _slots(cap, tri), sum(cap)
+    s, NPc = slots(cap, tri), sum(cap)
     gone = np.setdiff1d(np.arange(NPc), s)
     rng = np.random.RandomState(5)
 
@@ -326,12 +210,12 @@ def test_teacher_forcing_through_the_slotted_layout(name):
     obs, rew = _np(obs), _np(rew)
     live = g["is_reset_step"] == 0
     # the kernel IS the float32 oracle of the live shape
-    assert np.array_equal(_i32(obs[:, :r]), _i32(oobs)) and not _i32(obs[:, r:]).any()
-    assert np.array_equal(_i32(rew[live, :r]), _i32(orew[live])) and not _i32(rew[:, r:]).any()
-    assert np.array_equal(_i32(st["pos"][:, s]), _i32(ost["pos"])) and np.array_equal(_i32(st["vel"][:, s]), _i32(ost["vel"]))
-    assert (st["pos"][:, gone] == -1).all() and not _i32(st["vel"][:, gone]).any()
+    assert np.array_equal(i32(obs[:, :r]), i32(oobs)) and not i32(obs[:, r:]).any()
+    assert np.array_equal(i32(rew[live, :r]), i32(orew[live])) and not i32(rew[:, r:]).any()
+    assert np.array_equal(i32(st["pos"][:, s]), i32(ost["pos"])) and np.array_equal(i32(st["vel"][:, s]), i32(ost["vel"]))
+    assert (st["pos"][:, gone] == -1).all() and not i32(st["vel"][:, gone]).any()
     for k in STATE_KEYS:
-        assert np.array_equal(_raw(st[k]), _raw(ost[k])), k
+        assert np.array_equal(raw(st[k]), raw(ost[k])), k
     # ... and within 1e-5 of the recording, in the reference's float64, wherever that oracle is: every step of these files
     err = np.abs(obs[:, :r] - g["obs"]).reshape(T, -1).max(1)
     oerr = np.abs(oobs - g["obs"]).reshape(T, -1).max(1)
@@ -351,10 +235,10 @@ def test_teacher_forcing_through_the_slotted_layout(name):
     for t in range(5):
         o1, r1, d1, i1 = first.step(a)
         o2, r2, d2, i2 = second.step(a)
-        assert torch.equal(_bits(o1), _bits(o2)) and torch.equal(_bits(r1), _bits(r2)) and torch.equal(i1["cr_encs"], i2["cr_encs"])
+        assert same_bits(o1, o2) and same_bits(r1, r2) and torch.equal(i1["cr_encs"], i2["cr_encs"])
         s1, s2 = first.get_state(), second.get_state()
         for k in s1:
-            assert torch.equal(_bits(s1[k]), _bits(s2[k])), (k, t)
+            assert same_bits(s1[k], s2[k]), (k, t)
     assert (_np(s1["counts"]) == tri).all() and (s1["t"] == st1["t"] + 5).all()
 
 
@@ -362,19 +246,7 @@ def test_live_kernel_at_the_capacity_equals_the_fixed_shape_kernel():
     args, N = (12, 24, 25, 2, 1), 65
     kw = dict(n_sensors=16, seed=5, env_id_base=9, max_steps=15, auto_reset=True, action_scale=0.03, bad_speed=0.03)
     a, b = _mk(*args, n_envs=N, per_env_counts=True, **kw), _mk(*args, n_envs=N, **kw)
-    assert torch.equal(_bits(a.reset()), _bits(b.reset()))
-    g = torch.Generator(device="cpu").manual_seed(3)
-    for t in range(40):
-        act = (torch.rand((N, 12, 2), generator=g) * 2 - 1).to(DEV)
-        oa, ra, da, ia = a.step(act)
-        ob, rb, db, ib = b.step(act)
-        assert torch.equal(_bits(oa), _bits(ob)), "obs step %d" % t
-        assert torch.equal(_bits(ra), _bits(rb)) and torch.equal(da, db), "rewards / done step %d" % t
-        assert torch.equal(ia["ho_saved"], ib["ho_saved"]) and torch.equal(ia["cr_encs"], ib["cr_encs"]), "info step %d" % t
-        sa, sb = a.get_state(), b.get_state()
-        assert set(sa) - set(sb) == {"counts"}
-        for k in sb:
-            assert torch.equal(_bits(sa[k]), _bits(sb[k])), "state %s step %d" % (k, t)
+    assert len(list(lockstep(a, b, (N, 12, 2), 40, ("ho_saved", "cr_encs")))) == 40
 
 
 def _mixed(N=9, **kw):
@@ -431,9 +303,9 @@ def test_interface_errors_and_counts_across_a_new_handle():
 def test_is_terminal_uses_each_envs_live_hostage_count():
     """a mixed batch without auto_reset, staged: the envs of kind 0 end by "all saved" at their own hostage count"""
     (cap, coop, kw), N = CAP_62, 20
-    run = LiveRun(cap, coop, kw, TRI_62, N, H=50, auto_reset=False)
+    run = _run(cap, coop, kw, TRI_62, N, H=50, auto_reset=False)
     run.reset()
-    run.stage()
+    _stage(run, coop)
     assert not _np(run.env.is_terminal).any()
     act = np.random.RandomState(3).uniform(-1, 1, size=(N, cap[0], 2)).astype(np.float32)
     _obs, _rew, done, _info = run.env.step(act)
@@ -441,7 +313,7 @@ def test_is_terminal_uses_each_envs_live_hostage_count():
     for q, (o, (r, h, _c)) in enumerate(zip(run.twins, run.triples)):
         o.step(act[:, :r])
         st, idx = o.get_state(), run.cur == q
-        all_saved = (st["saved"] & _all_h(h)) == _all_h(h)
+        all_saved = (st["saved"] & all_h(h)) == all_h(h)
         want[idx] = (((st["flags"] & 2) != 0) | all_saved | (st["t"] >= 50))[idx]
         by_all_saved[idx] = all_saved[idx]
     assert np.array_equal(_np(run.env.is_terminal), want) and np.array_equal(_np(done), want)
@@ -451,45 +323,20 @@ def test_is_terminal_uses_each_envs_live_hostage_count():
 
 
 def test_obs_out_leaves_no_nan_in_an_uninitialised_destination():
-    env = _mixed()
-    env.reset()
-    dst = torch.empty(9 * 33 * env.obs_dim, device=DEV).fill_(float("nan"))
-    act = torch.rand((9, 33, 2), device=DEV) * 2 - 1
-    for t in range(6):   # (max_steps=5: the last step goes through the reset pass)
-        obs, rew, _done, _info = env.step(act, obs_out=dst)
-        assert obs.data_ptr() == dst.data_ptr() and not torch.isnan(dst).any()
-        absent = ~env.live_agents()
-        assert absent.any() and not _bits(obs[absent]).any() and not _bits(rew[absent]).any() and (obs[~absent].abs().amax(dim=1) > 0).all()
-        dst.fill_(float("nan"))
+    assert_obs_out_leaves_no_nan(_mixed(), steps=6)   # (max_steps=5: the last step goes through the reset pass)
 
 
 def test_rollout_collector_and_standardized_env_over_a_mixed_batch():
-    from madrl_amd.rollout import RolloutCollector
     from madrl_amd.wrappers import StandardizedEnv
-    H = 8
     # the policy of test_hostage_crowd_gpu.py::test_rollout_collector_over_a_crowd_env: a fixed function of the observation
     policy = lambda obs: torch.tanh(torch.stack([obs[..., :7].sum(-1) * 20.0 - 0.3, obs[..., 21:28].sum(-1) * 20.0 + 0.2], -1))
-    col = RolloutCollector(_mixed(), policy, horizon=H, store_observations=True)
-    assert col._slots
-    env = _mixed()
-    obs = env.reset()
-    for it in range(2):
-        traj = col.collect()
-        torch.cuda.synchronize()
-        for t in range(H):
-            assert torch.equal(_bits(traj.observations[t]), _bits(obs)), (it, t)
-            act = policy(obs)
-            assert torch.equal(_bits(traj.actions[t]), _bits(act)), (it, t)
-            obs, rew, done, _info = env.step(act)
-            assert torch.equal(_bits(traj.rewards[t]), _bits(rew)) and torch.equal(traj.dones[t] != 0, done), (it, t)
-        assert torch.equal(_bits(traj.last_observation), _bits(obs)), it
-    assert not torch.isnan(traj.observations).any() and int((traj.dones != 0).sum()) >= 9
+    assert_collector_equals_stepping_by_hand(_mixed, lambda: policy, H=8, min_dones=9)
     # StandardizedEnv takes its epilogue kernels over the capacity-shaped rows: scaling alone is the raw step times the scale, and the
     # rows of absent rescuers standardise to exactly 0 (mean 0, value 0)
     raw, scaled, normed = _mixed(), StandardizedEnv(_mixed(), scale_reward=2.0), StandardizedEnv(_mixed(), enable_obsnorm=True, enable_rewnorm=True)
     assert not scaled._fused and not normed._fused
     o0 = raw.reset()
-    assert torch.equal(_bits(scaled.reset()), _bits(o0))
+    assert same_bits(scaled.reset(), o0)
     on = normed.reset()
     g = torch.Generator(device="cpu").manual_seed(2)
     for t in range(7):
@@ -497,6 +344,6 @@ def test_rollout_collector_and_standardized_env_over_a_mixed_batch():
         o0, r0, d0, _ = raw.step(a)
         o1, r1, d1, _ = scaled.step(a)
         on, rn, dn, _ = normed.step(a)
-        assert torch.equal(_bits(o1), _bits(o0)) and torch.equal(_bits(r1), _bits(r0 * 2)) and torch.equal(d1, d0) and torch.equal(dn, d0), t
+        assert same_bits(o1, o0) and same_bits(r1, r0 * 2) and torch.equal(d1, d0) and torch.equal(dn, d0), t
         absent = ~raw.live_agents()
-        assert torch.isfinite(on).all() and torch.isfinite(rn).all() and not _bits(on[absent]).any() and not _bits(rn[absent]).any(), t
+        assert torch.isfinite(on).all() and torch.isfinite(rn).all() and not bits(on[absent]).any() and not bits(rn[absent]).any(), t

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from live_pursuit import assert_live_equals_fixed, assert_pending_counts_history, counts_tensor
 from test_pursuit_crowd_gpu import CNN, SURROUND_24, FREE_RUNS, _maps
 
 pytestmark = pytest.mark.gpu
@@ -49,21 +50,6 @@ def _oracle(cap, n, p, e, **kw):
     return po.PursuitOracle(_maps(CAPS[cap][0]), n_envs=n, **dict(CAPS[cap][1], n_pursuers=p, n_evaders=e, **kw))
 
 
-def _state_equal(cap, fix, p, e):
-    a, b = cap.get_state(), fix.get_state()
-    assert torch.equal(a["pos_p"][:, :p], b["pos_p"]) and bool((a["pos_p"][:, p:] == -1).all())
-    assert torch.equal(a["term_p"][:, :p], b["term_p"]) and not bool(a["term_p"][:, p:].any())
-    assert torch.equal(a["pos_e"][:, :e], b["pos_e"]) and bool((a["pos_e"][:, e:] == -1).all())
-    assert torch.equal(a["gone"][:, :e], b["gone"]) and bool(a["gone"][:, e:].all())
-    assert torch.equal(a["term_e"][:, :e], b["term_e"])
-    for k in ("map_id", "tick", "t"):
-        assert torch.equal(a[k], b[k]), k
-
-
-def _counts(blocks, per):
-    return torch.tensor([c for c in blocks for _ in range(per)], dtype=torch.int32, device=DEV)
-
-
 @pytest.mark.parametrize("cap", sorted(LISTED))
 def test_listed_capacities_run_the_live_crowd_kernel(cap):
     mname, kw = LISTED[cap]
@@ -87,26 +73,8 @@ def test_live_counts_match_a_fixed_shape_batch(cap, which, kernel):
     env = _env(cap, N, kernel, per_env_counts=True, **kw)
     fix = _env(cap, N, "auto", n_pursuers=p, n_evaders=e, **kw)
     assert env.kernel_kind == kernel
-    env.set_agent_counts(p, e)
-    obs_c, obs_f = env.reset(), fix.reset()
-    assert torch.equal(obs_c[:, :p], obs_f) and not bool(obs_c[:, p:].any())
-    _state_equal(env, fix, p, e)
-    rng = np.random.RandomState(which)
-    T = CAPS[cap][3]
-    for it in range(T):
-        act = torch.as_tensor(rng.randint(5, size=(N, P)), device=DEV, dtype=torch.int32)
-        obs_c, rew_c, done_c, info_c = env.step(act)
-        obs_f, rew_f, done_f, info_f = fix.step(act[:, :p].contiguous())
-        assert torch.equal(obs_c[:, :p], obs_f), it
-        assert not bool(obs_c[:, p:].any()), it   # rows >= p never written (the buffer started as zeros)
-        assert torch.equal(rew_c[:, :p], rew_f) and not bool(rew_c[:, p:].any()), it
-        assert torch.equal(info_c["done_bits"], info_f["done_bits"]) and torch.equal(info_c["removed"], info_f["removed"]), it
-        assert torch.equal(env._flags, fix._flags), it   # done / truncated / count_overflow flag plane
-        if it % 20 == 19 or it == T - 1:
-            _state_equal(env, fix, p, e)
+    assert_live_equals_fixed(env, fix, p, e, P, CAPS[cap][3], np.random.RandomState(which), state_every=20, last_too=True)
     assert env.kernel_kind == kernel
-    pend, live = env.agent_counts()
-    assert bool((live == torch.tensor([p, e], device=DEV, dtype=torch.int32)).all()) and torch.equal(pend, live)
 
 
 # name: capacity, extra config, envs per block, blocks, blocks with removed > 0, blocks with episodes ended by catches.
@@ -135,7 +103,7 @@ def test_mixed_batch_matches_the_oracle_per_block(case, kernel):
     N = B * len(blocks)
     env = _env(cap, N, kernel, per_env_counts=True, seed=3, env_id_base=7, max_steps=H, auto_reset=True, **extra)
     assert env.kernel_kind == kernel
-    counts = _counts(blocks, B)
+    counts = counts_tensor(blocks, B)
     env.set_agent_counts(counts[:, 0], counts[:, 1])
     obs = env.reset().cpu().numpy().reshape(N, P, -1)
     orcs = [_oracle(cap, B, p, e, seed=3, env_id_base=7 + j * B, **extra) for j, (p, e) in enumerate(blocks)]
@@ -186,58 +154,7 @@ def test_pending_counts_take_effect_at_each_envs_own_reset(cap):
     P = CAPS[cap][1]["n_pursuers"]
     N = B * len(blocks)
     envs = [_env(cap, N, k, per_env_counts=True, seed=3, max_steps=25, auto_reset=True) for k in ("wave", "generic")]
-    counts = _counts(blocks, B)
-    for env in envs:
-        env.set_agent_counts(counts[:, 0], counts[:, 1])
-        env.reset()
-    rng = np.random.RandomState(1)
-    k = torch.arange(P, device=DEV)[None, :]
-
-    def step_both(it):
-        act = torch.as_tensor(rng.randint(5, size=(N, P)), device=DEV)
-        out = [env.step(act) for env in envs]
-        (ow, rw, dw, iw), (og, rg, dg, ig) = out
-        assert torch.equal(ow, og) and torch.equal(rw, rg) and torch.equal(iw["done_bits"], ig["done_bits"]), it
-        assert torch.equal(iw["removed"], ig["removed"]) and torch.equal(envs[0]._flags, envs[1]._flags), it
-        return iw, (ow, og)
-
-    for it in range(7):
-        step_both(it)
-    schedule = [counts.flip(0).contiguous(), counts.contiguous()]   # the floor block goes to full capacity and back, the full block down
-    live = counts
-    for phase, new in enumerate(schedule):
-        for env in envs:
-            env.set_agent_counts(new[:, 0], new[:, 1])
-        switched = torch.zeros(N, dtype=torch.bool, device=DEV)
-        for it in range(30):
-            info, obs = step_both((phase, it))
-            switched |= info["done_bits"] != 0
-            for env in envs:
-                pend, lv = env.agent_counts()
-                assert torch.equal(pend, new)
-                assert torch.equal(lv, torch.where(switched[:, None], new, live)), (phase, it)
-                st = env.get_state()
-                ghost = k >= lv[:, :1]
-                assert bool((st["pos_p"][ghost] == -1).all()) and bool((st["pos_p"][~ghost] >= 0).all())
-                assert torch.equal(env.live_agents(), ~ghost)
-        assert bool(switched.all())   # max_steps 25: every env has reset
-        live = new
-        if phase == 0:   # an in-place edit of the returned tensor: channel 3 of the rows is no longer known to hold +0.0
-            for o in obs:
-                o.view(N, P, -1)[:, :, ::7] += 0.5
-    # an explicit reset(mask=) takes the pending counts of the masked envs only
-    new = torch.tensor([[5, 9]], dtype=torch.int32, device=DEV).repeat(N, 1)
-    mask = torch.arange(N, device=DEV) % 2 == 1
-    outs = []
-    for env in envs:
-        env.set_agent_counts(new[:, 0], new[:, 1])
-        outs.append(env.reset(mask=mask))
-        assert torch.equal(env.agent_counts()[1], torch.where(mask[:, None], new, live))
-    assert torch.equal(outs[0], outs[1])
-    for it in range(5):
-        step_both(("after reset", it))
-    for env in envs:
-        assert env.kernel_kind == ("wave" if env is envs[0] else "generic")
+    assert_pending_counts_history(envs, counts_tensor(blocks, B), P)
 
 
 @pytest.mark.parametrize("masked", [True, False])
@@ -294,7 +211,7 @@ def test_state_pickle_and_kernel_switch_round_trips(cap):
     P = CAPS[cap][1]["n_pursuers"]
     N = B * len(blocks)
     env = _env(cap, N, "auto", per_env_counts=True, seed=4, max_steps=20, auto_reset=True)
-    counts = _counts(blocks, B)
+    counts = counts_tensor(blocks, B)
     env.set_agent_counts(counts[:, 0], counts[:, 1])
     env.reset()
     rng = np.random.RandomState(4)
@@ -331,7 +248,7 @@ def test_stream_sharded_sub_batches_give_the_results_of_one_launch():
     blocks = COUNTS[cap]
     kw = dict(CAPS[cap][1], per_env_counts=True, seed=9, max_steps=8, auto_reset=True)
     maps = _maps(CAPS[cap][0])
-    counts = _counts(blocks, N // len(blocks))
+    counts = counts_tensor(blocks, N // len(blocks))
     envs = [_mk(maps, N, "wave", max_blocks=b, **kw) for b in (0, 1, 7)]
     sh = StreamSharded(lambda n_envs, env_id_base, device: _mk(maps, n_envs, "wave", env_id_base=env_id_base, **kw), N, n_streams=2, device=DEV)
     for e in envs:

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from live_pursuit import assert_live_equals_fixed, counts_tensor
+
 DEV = "cuda:0"
 CAP = dict(n_pursuers=8, n_evaders=30, obs_range=7)
 
@@ -23,17 +25,6 @@ def _env(n, kernel, **kw):
     args = dict(CAP)
     args.update(kw)
     return BatchedPursuitEvade(_maps(), n_envs=n, device=DEV, kernel=kernel, **args)
-
-
-def _state_equal(cap, fix, p, e):
-    a, b = cap.get_state(), fix.get_state()
-    assert torch.equal(a["pos_p"][:, :p], b["pos_p"]) and bool((a["pos_p"][:, p:] == -1).all())
-    assert torch.equal(a["term_p"][:, :p], b["term_p"]) and not bool(a["term_p"][:, p:].any())
-    assert torch.equal(a["pos_e"][:, :e], b["pos_e"]) and bool((a["pos_e"][:, e:] == -1).all())
-    assert torch.equal(a["gone"][:, :e], b["gone"]) and bool(a["gone"][:, e:].all())
-    assert torch.equal(a["term_e"][:, :e], b["term_e"])
-    for k in ("map_id", "tick", "t"):
-        assert torch.equal(a[k], b[k]), k
 
 
 VARIANTS = {
@@ -54,24 +45,8 @@ def test_live_counts_match_a_fixed_shape_batch(variant, kernel):
     cap = _env(N, kernel, per_env_counts=True, **kw)
     fix = _env(N, "auto", **dict(kw, n_pursuers=p, n_evaders=e))
     assert cap.kernel_kind == kernel
-    cap.set_agent_counts(p, e)
-    obs_c, obs_f = cap.reset(), fix.reset()
-    assert torch.equal(obs_c[:, :p], obs_f) and not bool(obs_c[:, p:].any())
-    _state_equal(cap, fix, p, e)
-    rng = np.random.RandomState(3)
-    for it in range(200):
-        act = torch.as_tensor(rng.randint(5, size=(N, 8)), device=DEV, dtype=torch.int32)
-        obs_c, rew_c, done_c, info_c = cap.step(act)
-        obs_f, rew_f, done_f, info_f = fix.step(act[:, :p].contiguous())
-        assert torch.equal(obs_c[:, :p], obs_f), it
-        assert not bool(obs_c[:, p:].any()), it   # row 7 never written (the buffer started as zeros)
-        assert torch.equal(rew_c[:, :p], rew_f) and not bool(rew_c[:, p:].any()), it
-        assert torch.equal(info_c["done_bits"], info_f["done_bits"]) and torch.equal(info_c["removed"], info_f["removed"]), it
-        if it % 50 == 49:
-            _state_equal(cap, fix, p, e)
+    assert_live_equals_fixed(cap, fix, p, e, 8, 200, np.random.RandomState(3), state_every=50)
     assert cap.kernel_kind == kernel
-    pend, live = cap.agent_counts()
-    assert bool((live == torch.tensor([p, e], device=DEV, dtype=torch.int32)).all()) and torch.equal(pend, live)
 
 
 BLOCKS = ((8, 30), (7, 29), (6, 28), (4, 26))
@@ -79,7 +54,7 @@ BLOCKS = ((8, 30), (7, 29), (6, 28), (4, 26))
 
 def _mixed(kernel, B, **kw):
     cap = _env(B * len(BLOCKS), kernel, per_env_counts=True, seed=5, **kw)
-    counts = torch.tensor([c for c in BLOCKS for _ in range(B)], dtype=torch.int32, device=DEV)
+    counts = counts_tensor(BLOCKS, B)
     cap.set_agent_counts(counts[:, 0], counts[:, 1])
     return cap, counts
 

@@ -3,6 +3,8 @@ trajectory as the collector that copies the observations after every step, and n
 import pytest
 import torch
 
+from helpers import same_bits
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -35,13 +37,9 @@ def _waterworld_policy(row_id_base=0):
 WORLDS = {"pursuit": (_pursuit, _pursuit_policy), "waterworld": (_waterworld, _waterworld_policy)}
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
-
-
 def _check(a, b, what):
     for k in KEYS:
-        assert torch.equal(_bits(getattr(a, k)), _bits(getattr(b, k))), (what, k)
+        assert same_bits(getattr(a, k), getattr(b, k)), (what, k)
 
 
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
@@ -57,9 +55,9 @@ def test_same_trajectory_as_the_copying_collector(world, graph):
         a, b = slots.collect(), copying.collect()
         _check(a, b, (world, it))
         assert a.observations.shape[0] == T and a.last_observation.shape == a.observations.shape[1:]
-        assert torch.equal(_bits(a.last_observation), _bits(b.last_observation)), (world, it)
+        assert same_bits(a.last_observation, b.last_observation), (world, it)
         if last is not None:   # the first observation of this horizon is the last one of the previous horizon
-            assert torch.equal(_bits(last), _bits(a.observations[0])), (world, it)
+            assert same_bits(last, a.observations[0]), (world, it)
         last = a.last_observation.clone()
     assert int((a.dones != 0).sum()) >= N   # max_steps=5: episodes ended and restarted inside the horizon
     if graph:
@@ -80,8 +78,8 @@ def test_sharded_collector_equals_the_one_batch_collector():
             parts = col.collect()
             torch.cuda.synchronize()
             for k in KEYS:
-                assert torch.equal(_bits(getattr(a, k)), _bits(torch.cat([getattr(p, k) for p in parts], dim=1))), (it, k)
-            assert torch.equal(_bits(a.last_observation), _bits(torch.cat([p.last_observation for p in parts], dim=0))), it
+                assert same_bits(getattr(a, k), torch.cat([getattr(p, k) for p in parts], dim=1)), (it, k)
+            assert same_bits(a.last_observation, torch.cat([p.last_observation for p in parts], dim=0)), it
 
 
 def test_a_plain_step_follows_the_collector():
@@ -93,7 +91,7 @@ def test_a_plain_step_follows_the_collector():
     assert env.obs_buffer.data_ptr() == a.last_observation.data_ptr()
     act = torch.full((N, 8), 2, dtype=torch.int32, device=DEV)
     ra, rb = env.step(act), twin.step(act)
-    assert torch.equal(_bits(ra[0]), _bits(rb[0])) and torch.equal(_bits(ra[1]), _bits(rb[1]))
+    assert same_bits(ra[0], rb[0]) and same_bits(ra[1], rb[1])
 
 
 @pytest.mark.parametrize("world", sorted(WORLDS))

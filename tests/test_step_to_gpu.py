@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import same_bits
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -55,14 +57,6 @@ def _mk(cfg, n=N_ENVS, **kw):
     return env
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
 class Twins(object):
     """`ref` steps in place; `env` steps through `ring`, whose first slot is its own buffer"""
 
@@ -84,15 +78,15 @@ class Twins(object):
                 c = torch.tensor(counts, dtype=torch.int32, device=DEV)
                 e.set_agent_counts(c[:, 0], c[:, 1])
         a, b = self.ref.reset(), self.env.reset()
-        assert _same(a, b)
+        assert same_bits(a, b)
 
     def actions(self):
         return torch.randint(0, 5, (N_ENVS, self.n_act), generator=self.gen).to(torch.int32).to(DEV)
 
     def check_results(self, ra, rb, what):
         (oa, rwa, da, ia), (ob, rwb, db, ib) = ra, rb
-        assert _same(oa, ob), (what, "observations")
-        assert _same(rwa, rwb), (what, "rewards")
+        assert same_bits(oa, ob), (what, "observations")
+        assert same_bits(rwa, rwb), (what, "rewards")
         assert torch.equal(da, db), (what, "done")
         for k in ("done_bits", "removed", "truncated", "count_overflow"):
             assert torch.equal(ia[k], ib[k]), (what, k)
@@ -105,14 +99,14 @@ class Twins(object):
         rb = self.env.step_to(act, self.ring[nxt])
         self.check_results(ra, rb, what)
         assert rb[0].data_ptr() == self.ring[nxt].data_ptr() and self.env.obs_buffer.data_ptr() == self.ring[nxt].data_ptr()
-        assert _same(self.ring[nxt], self.ref.obs_buffer), (what, "slot")
-        assert _same(self.ring[self.at], prev_before), (what, "the previous slot was written")
+        assert same_bits(self.ring[nxt], self.ref.obs_buffer), (what, "slot")
+        assert same_bits(self.ring[self.at], prev_before), (what, "the previous slot was written")
         self.at = nxt
 
     def in_place(self, what):
         act = self.actions()
         self.check_results(self.ref.step(act), self.env.step(act), what)
-        assert _same(self.ring[self.at], self.ref.obs_buffer), (what, "slot")
+        assert same_bits(self.ring[self.at], self.ref.obs_buffer), (what, "slot")
 
     def check_state(self):
         a, b = self.ref.get_state(), self.env.get_state()
@@ -207,13 +201,13 @@ def test_argument_checks():
     # obs_out that IS the current buffer behaves as step()
     ra, rb = tw.ref.step(act), env.step_to(act, env.obs_buffer)
     tw.check_results(ra, rb, "same buffer")
-    assert env.obs_buffer.data_ptr() == cur.data_ptr() and _same(cur, tw.ref.obs_buffer)
+    assert env.obs_buffer.data_ptr() == cur.data_ptr() and same_bits(cur, tw.ref.obs_buffer)
     # ... and step_into(obs_out=) is step_to()
     act = tw.actions()
     ra = tw.ref.step(act)
     rew_slot, dn_slot = torch.zeros_like(rew), torch.zeros_like(dn)
     o = env.step_into(act, rew_slot, dn_slot, obs_out=other)
-    assert o.data_ptr() == other.data_ptr() and _same(other, tw.ref.obs_buffer) and _same(rew_slot, ra[1]) and torch.equal(dn_slot, ra[3]["done_bits"])
+    assert o.data_ptr() == other.data_ptr() and same_bits(other, tw.ref.obs_buffer) and same_bits(rew_slot, ra[1]) and torch.equal(dn_slot, ra[3]["done_bits"])
 
 
 def _other_envs():
@@ -233,7 +227,7 @@ def test_obs_out_on_the_other_envs(world):
     mk, adim = _other_envs()[world]
     ref, env = mk(), mk()
     a, b = ref.reset(), env.reset()
-    assert _same(a, b)
+    assert same_bits(a, b)
     ring = [torch.full_like(a, 101.0), torch.full_like(a, 102.0)]
     gen = torch.Generator(device="cpu").manual_seed(9)
     for k in range(20):
@@ -241,7 +235,7 @@ def test_obs_out_on_the_other_envs(world):
         slot = ring[k % 2]
         ra, rb = ref.step(act), env.step(act, obs_out=slot.view(-1))   # (any contiguous tensor of the right size)
         assert rb[0].data_ptr() == slot.data_ptr() and rb[0].shape == ra[0].shape
-        assert _same(slot, ra[0]) and _same(ra[1], rb[1]) and torch.equal(ra[2], rb[2]), k
+        assert same_bits(slot, ra[0]) and same_bits(ra[1], rb[1]) and torch.equal(ra[2], rb[2]), k
     with pytest.raises(ValueError):
         env.step(act, obs_out=torch.zeros(a.numel() + 1, dtype=torch.float32, device=DEV))
     with pytest.raises(ValueError):

@@ -10,6 +10,8 @@ twin."""
 import pytest
 import torch
 
+from helpers import same_bits
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -66,14 +68,6 @@ def _mk(name, max_blocks=2, walk=None):
     return env
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
 class Twins(object):
     """`ref` steps in place; `env` steps through `ring`, whose first slot is its own buffer"""
 
@@ -95,7 +89,7 @@ class Twins(object):
                 c = torch.tensor(self.counts, dtype=torch.int32, device=DEV)
                 e.set_agent_counts(c[:, 0], c[:, 1])
         a, b = self.ref.reset(), self.env.reset()
-        assert _same(a, b)
+        assert same_bits(a, b)
 
     def actions(self):
         act = torch.randint(0, 5, (N_ENVS, self.P), generator=self.gen).to(torch.int32).to(DEV)
@@ -104,8 +98,8 @@ class Twins(object):
 
     def check_results(self, ra, rb, what):
         (oa, rwa, da, ia), (ob, rwb, db, ib) = ra, rb
-        assert _same(oa, ob), (what, "observations")
-        assert _same(rwa, rwb), (what, "rewards")
+        assert same_bits(oa, ob), (what, "observations")
+        assert same_bits(rwa, rwb), (what, "rewards")
         assert torch.equal(da, db), (what, "done")
         for k in ("done_bits", "removed", "truncated", "count_overflow"):
             assert torch.equal(ia[k], ib[k]), (what, k)
@@ -118,14 +112,14 @@ class Twins(object):
         rb = self.env.step_to(act, self.ring[nxt], evader_actions=eact)
         self.check_results(ra, rb, what)
         assert rb[0].data_ptr() == self.ring[nxt].data_ptr() and self.env.obs_buffer.data_ptr() == self.ring[nxt].data_ptr()
-        assert _same(self.ring[nxt], self.ref.obs_buffer), (what, "slot")
-        assert _same(self.ring[self.at], prev_before), (what, "the previous slot was written")
+        assert same_bits(self.ring[nxt], self.ref.obs_buffer), (what, "slot")
+        assert same_bits(self.ring[self.at], prev_before), (what, "the previous slot was written")
         self.at = nxt
 
     def in_place(self, what):
         act, eact = self.actions()
         self.check_results(self.ref.step(act, evader_actions=eact), self.env.step(act, evader_actions=eact), what)
-        assert _same(self.ring[self.at], self.ref.obs_buffer), (what, "slot")
+        assert same_bits(self.ring[self.at], self.ref.obs_buffer), (what, "slot")
 
     def check_state(self):
         a, b = self.ref.get_state(), self.env.get_state()

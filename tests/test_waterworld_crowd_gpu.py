@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import same_bits
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL = 1e-5  # BASELINE.json north_star: "within 1e-5 for Waterworld ... float32 state"
@@ -22,11 +24,6 @@ gid = lambda p: os.path.basename(p)[:-4]
 def _mk(n_envs, crowd=True, **kw):
     from madrl_amd.waterworld import BatchedMAWaterWorld
     return BatchedMAWaterWorld(n_envs=n_envs, device=DEV, crowd=crowd, **kw)
-
-
-def _bits(t):
-    t = t.contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
 
 
 @pytest.mark.parametrize("path", FILES, ids=gid)
@@ -137,18 +134,18 @@ def test_crowd_equals_the_one_wavefront_kernel(kw, N):
     a = _mk(N, crowd=True, seed=5, env_id_base=9, max_steps=15, auto_reset=True, **kw)
     b = _mk(N, crowd=False, seed=5, env_id_base=9, max_steps=15, auto_reset=True, **kw)
     assert (a.kernel_kind, b.kernel_kind) == ("crowd", "wave")
-    assert torch.equal(_bits(a.reset()), _bits(b.reset()))
+    assert same_bits(a.reset(), b.reset())
     g = torch.Generator(device="cpu").manual_seed(3)
     for t in range(40):
         act = (torch.rand((N, kw["n_pursuers"], 2), generator=g) * 2 - 1).to(DEV)
         oa, ra, da, ia = a.step(act)
         ob, rb, db, ib = b.step(act)
-        assert torch.equal(_bits(oa), _bits(ob)), "obs step %d" % t
-        assert torch.equal(_bits(ra), _bits(rb)) and torch.equal(da, db), "rewards / done step %d" % t
+        assert same_bits(oa, ob), "obs step %d" % t
+        assert same_bits(ra, rb) and torch.equal(da, db), "rewards / done step %d" % t
         assert torch.equal(ia["evcatches"], ib["evcatches"]) and torch.equal(ia["pocatches"], ib["pocatches"]), "info step %d" % t
         sa, sb = a.get_state(), b.get_state()
         for k in sa:
-            assert torch.equal(_bits(sa[k]), _bits(sb[k])), "state %s step %d" % (k, t)
+            assert same_bits(sa[k], sb[k]), "state %s step %d" % (k, t)
 
 
 def test_crowd_env_interface():
@@ -208,13 +205,13 @@ def test_standardized_env_over_a_crowd_env_takes_the_epilogue_kernels():
     assert not auto._fused and not plain._fused and auto.unwrapped._std is None
     with pytest.raises(ValueError, match="fused=True"):
         StandardizedEnv(mk(), fused=True, **cfg)
-    assert torch.equal(_bits(auto.reset()), _bits(plain.reset()))
+    assert same_bits(auto.reset(), plain.reset())
     g = torch.Generator(device="cpu").manual_seed(2)
     for t in range(10):
         a = (torch.rand((N, 13, 2), generator=g) * 2 - 1).to(DEV)
         oa, ra, da, _ = auto.step(a)
         op, rp, dp, _ = plain.step(a)
-        assert torch.equal(_bits(oa), _bits(op)) and torch.equal(_bits(ra), _bits(rp)) and torch.equal(da, dp), t
+        assert same_bits(oa, op) and same_bits(ra, rp) and torch.equal(da, dp), t
     assert torch.isfinite(oa).all() and not torch.equal(oa, auto.unwrapped._obs)   # standardised, not the raw rows
 
 
@@ -234,11 +231,11 @@ def test_rollout_collector_over_a_crowd_env(graph):
         traj = col.collect()
         torch.cuda.synchronize()
         for t in range(H):
-            assert torch.equal(_bits(traj.observations[t]), _bits(obs)), (it, t)
+            assert same_bits(traj.observations[t], obs), (it, t)
             act = pol(obs)
             act = act[0] if isinstance(act, tuple) else act
-            assert torch.equal(_bits(traj.actions[t]), _bits(act)), (it, t)
+            assert same_bits(traj.actions[t], act), (it, t)
             obs, rew, done, _info = env.step(act)
-            assert torch.equal(_bits(traj.rewards[t]), _bits(rew)) and torch.equal(traj.dones[t] != 0, done), (it, t)
-        assert torch.equal(_bits(traj.last_observation), _bits(obs)), it
+            assert same_bits(traj.rewards[t], rew) and torch.equal(traj.dones[t] != 0, done), (it, t)
+        assert same_bits(traj.last_observation, obs), it
     assert int((traj.dones != 0).sum()) >= N   # max_steps=5: episodes ended and restarted inside the horizon

@@ -3,12 +3,16 @@ ww_crowd_kernel_live, csrc/waterworld_crowd.hip).  The definition of right: an e
 fixed-shape (p, e, po) batch with the same seed and env_id_base + n computes.  So every test runs free against float32 oracle twins, one
 twin of N envs per distinct triple, env n against env n of its triple's twin; nothing is copied across, and every output and the state
 are compared in every bit at every step.  Host-facing layouts stay at the capacity, slotted by class."""
+import functools
 import os
 import pickle
 
 import numpy as np
 import pytest
 import torch
+
+from helpers import bits, i32, same_bits, slots
+from live_twins import LiveTwins, assert_collector_equals_stepping_by_hand, assert_obs_out_leaves_no_nan, lockstep, waterworld
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -26,132 +30,30 @@ def _mk(n_envs, crowd=True, **kw):
     return BatchedMAWaterWorld(n_envs=n_envs, device=DEV, crowd=crowd, **kw)
 
 
-def _bits(t):
-    t = t.contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def _i32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
-
-
-def _slots(cap, tri):
-    """the slots (at the capacity) of the particles of a live triple, in the live class order"""
-    (P, E, _PO), (p, e, po) = cap, tri
-    return np.r_[np.arange(p), P + np.arange(e), P + E + np.arange(po)]
-
-
-class LiveRun(object):
-    """a per-env-counts batch and its oracle twins; `cur[n]` is the index of the triple env n runs, `pend[n]` of the one it takes next"""
-
-    def __init__(self, kw, triples, N, H, deal=None, **env_kw):
-        from oracle import waterworld as ww
-        self.kw, self.triples, self.N = kw, list(triples), N
-        self.cap = (kw["n_pursuers"], kw["n_evaders"], kw["n_poison"])
-        self.env = _mk(N, per_env_counts=True, seed=SEED, env_id_base=BASE, max_steps=H, auto_reset=True, **dict(kw, **env_kw))
-        assert self.env.kernel_kind == "crowd"
-        self.twins = [ww.WaterworldOracle(n_envs=N, seed=SEED, env_id_base=BASE, max_steps=H, dtype=np.float32,
-                                          **dict(kw, n_pursuers=p, n_evaders=e, n_poison=po)) for p, e, po in self.triples]
-        self.started = False   # live counts start at the capacity; the first reset deals the triples
-        self.cur = np.full(N, -1)
-        self.pend = self.cur.copy()
-        self.set_pending(np.arange(N) % len(self.triples) if deal is None else deal)
-        self.evc = self.poc = self.resets = 0
-
-    def set_pending(self, idx, mask=None):
-        idx = np.broadcast_to(np.asarray(idx), (self.N,))
-        tri = np.asarray(self.triples)[idx]
-        self.env.set_particle_counts(tri[:, 0], tri[:, 1], tri[:, 2], mask=mask)
-        self.pend = np.where(np.ones(self.N, bool) if mask is None else np.asarray(mask, bool), idx, self.pend)
-
-    def _reset_twins(self, env_mask, own_done=False):
-        """the envs of env_mask take their pending triple: such an env's new twin gets the env's tick and resets it.  own_done: every twin also
-        resets the envs its own step ended (they run along)"""
-        new = np.where(env_mask, self.pend, self.cur)
-        ticks = [o.get_state()["tick"] for o in self.twins]
-        for q, o in enumerate(self.twins):
-            m_in = env_mask & (new == q)
-            tk = ticks[q].copy()
-            for n in np.nonzero(m_in & (self.cur != q))[0]:
-                tk[n] = ticks[self.cur[n]][n]
-            o.set_state(tick=tk)
-            m = m_in | (o.done.astype(bool) if own_done else False)
-            if m.any():
-                o.reset(mask=m.astype(np.uint8))
-        self.cur = new
-
-    def reset(self, mask=None):
-        m = np.ones(self.N, bool) if mask is None else np.asarray(mask, bool)
-        if not self.started:
-            assert mask is None   # the first reset: every env leaves the capacity for its dealt triple; all ticks are 0
-            self.started, self.cur = True, self.pend.copy()
-            for o in self.twins:
-                o.reset()
-        else:
-            self._reset_twins(m)
-        obs = self.env.reset(mask=None if mask is None else m.astype(np.uint8))
-        self.check(obs, "reset")
-
-    def step(self, act, tag):
-        obs, rew, done, info = self.env.step(act)
-        rew, done = rew.cpu().numpy(), done.cpu().numpy()
-        evc, poc = info["evcatches"].cpu().numpy(), info["pocatches"].cpu().numpy()
-        for q, (o, (p, _e, _po)) in enumerate(zip(self.twins, self.triples)):
-            o.step(act[:, :p])
-            idx = self.cur == q
-            assert np.array_equal(done[idx], o.done[idx].astype(bool)), "done %s" % tag
-            assert np.array_equal(evc[idx], o.info[idx, 0]) and np.array_equal(poc[idx], o.info[idx, 1]), "info %s" % tag
-            assert np.array_equal(_i32(rew[idx, :p]), _i32(o.rew[idx])), "rewards %s" % tag
-            assert not _i32(rew[idx, p:]).any(), "rewards of absent pursuers %s" % tag
-            self.evc += int(o.info[idx, 0].sum()); self.poc += int(o.info[idx, 1].sum())
-        self.resets += int(done.sum())
-        self._reset_twins(done, own_done=True)
-        self.check(obs, tag)
-        return done
-
-    def check(self, obs, tag):
-        obs = obs.cpu().numpy()
-        st = {k: v.cpu().numpy() for k, v in self.env.get_state().items()}
-        pending, live = self.env.particle_counts()
-        assert np.array_equal(live.cpu().numpy(), np.asarray(self.triples)[self.cur]), "live counts %s" % tag
-        assert np.array_equal(pending.cpu().numpy(), np.asarray(self.triples)[self.pend]), "pending counts %s" % tag
-        assert np.array_equal(st["counts"], live.cpu().numpy())
-        for q, (o, tri) in enumerate(zip(self.twins, self.triples)):
-            idx, p = self.cur == q, tri[0]
-            if not idx.any():
-                continue
-            assert np.array_equal(_i32(obs[idx, :p]), _i32(o.obs[idx])), "obs %s: %g" % (tag, np.abs(obs[idx, :p] - o.obs[idx]).max())
-            assert not _i32(obs[idx, p:]).any(), "rows of absent pursuers are not +0.0, %s" % tag
-            ost, s = o.get_state(), _slots(self.cap, tri)
-            gone = np.setdiff1d(np.arange(sum(self.cap)), s)
-            assert np.array_equal(_i32(st["pos"][idx][:, s]), _i32(ost["pos"][idx])), "pos %s" % tag
-            assert np.array_equal(_i32(st["vel"][idx][:, s]), _i32(ost["vel"][idx])), "vel %s" % tag
-            assert (st["pos"][idx][:, gone] == -1.0).all() and not _i32(st["vel"][idx][:, gone]).any(), "absent slots %s" % tag
-            assert np.array_equal(_i32(st["obst"][idx]), _i32(ost["obst"][idx])), "obst %s" % tag
-            assert np.array_equal(st["t"][idx], ost["t"][idx]), "t %s" % tag
-            assert np.array_equal(st["tick"][idx].view(np.uint32), ost["tick"][idx]), "tick %s" % tag
+def _run(kw, triples, N, H, **more):
+    return LiveTwins(waterworld(kw, SEED, BASE, "crowd", functools.partial(_mk, per_env_counts=True)), triples, N, H, **more)
 
 
 def _free_run(kw, triples, N, T, H, **env_kw):
-    run = LiveRun(kw, triples, N, H, **env_kw)
+    run = _run(kw, triples, N, H, **env_kw)
     run.reset()
     rng = np.random.RandomState(1)
     for t in range(T):
         run.step(rng.uniform(-1, 1, size=(N, kw["n_pursuers"], 2)).astype(np.float32), "step %d" % t)
-    print("%d evader catches, %d poison catches, %d time-limit resets" % (run.evc, run.poc, run.resets))
+    print("%d evader catches, %d poison catches, %d time-limit resets" % (run.total("evc"), run.total("poc"), run.resets))
     return run
 
 
 def test_first_shape_past_a_wavefront():
     run = _free_run(CAP_63, TRI_63, N=65, T=40, H=13)
-    assert run.evc > 0 and run.poc > 0 and run.resets > 0
+    assert run.total("evc") > 0 and run.total("poc") > 0 and run.resets > 0
 
 
 def test_chunk_boundaries_that_differ_per_env():
     """WE and WP (64-bit words per collision row) change from env to env inside one launch"""
     kw = dict(n_pursuers=65, n_evaders=65, n_poison=129, n_coop=2, n_sensors=30, ev_speed=0.04, action_scale=0.03)
     run = _free_run(kw, [(65, 65, 129), (64, 64, 128), (33, 1, 65), (1, 64, 1)], N=16, T=30, H=10)
-    assert run.evc + run.poc > 0 and run.resets > 0
+    assert run.total("evc") + run.total("poc") > 0 and run.resets > 0
 
 
 def test_rows_longer_than_a_wavefront():
@@ -172,7 +74,7 @@ def test_variants(kw, triples):
 
 def test_counts_change_at_a_reset_not_before():
     N, H = 12, 9
-    run = LiveRun(CAP_63, TRI_63, N, H, deal=np.arange(N) % 2)   # (13, 25, 25) and (12, 24, 24)
+    run = _run(CAP_63, TRI_63, N, H, deal=np.arange(N) % 2)   # (13, 25, 25) and (12, 24, 24)
     run.reset()
     rng = np.random.RandomState(2)
     act = lambda: rng.uniform(-1, 1, size=(N, 13, 2)).astype(np.float32)
@@ -217,7 +119,7 @@ def test_teacher_forcing_through_the_slotted_layout():
     ckw = dict(kw, n_pursuers=cap[0], n_evaders=cap[1], n_poison=cap[2])
     env = _mk(T, per_env_counts=True, **ckw)
     orc = ww.WaterworldOracle(n_envs=T, dtype=np.float32, sensors=g["sensors"], **kw)
-    s, NPc = _slots(cap, tri), sum(cap)
+    s, NPc = slots(cap, tri), sum(cap)
     rng = np.random.RandomState(5)
 
     def slotted(a, fill):   # absent slots hold values that would matter if they were read
@@ -253,10 +155,10 @@ def test_teacher_forcing_through_the_slotted_layout():
         worst, oworst = max(worst, max(errs)), max(oworst, max(oerrs))
     print("worst error kernel %.3g, float32 oracle %.3g" % (worst, oworst))
     assert oworst <= TOL and worst <= TOL
-    assert np.array_equal(_i32(obs[:, :20]), _i32(oobs)) and not _i32(obs[:, 20:]).any()
-    assert np.array_equal(_i32(rew[live, :20]), _i32(orew[live])) and not _i32(rew[:, 20:]).any()
-    assert np.array_equal(_i32(pos1[:, s]), _i32(ost["pos"])) and np.array_equal(_i32(vel1[:, s]), _i32(ost["vel"]))
-    assert (pos1[:, gone] == -1).all() and not _i32(vel1[:, gone]).any()
+    assert np.array_equal(i32(obs[:, :20]), i32(oobs)) and not i32(obs[:, 20:]).any()
+    assert np.array_equal(i32(rew[live, :20]), i32(orew[live])) and not i32(rew[:, 20:]).any()
+    assert np.array_equal(i32(pos1[:, s]), i32(ost["pos"])) and np.array_equal(i32(vel1[:, s]), i32(ost["vel"]))
+    assert (pos1[:, gone] == -1).all() and not i32(vel1[:, gone]).any()
     # get_state -> set_state on a second env object, which continues identically (free-running: the same seed and env ids)
     first, second = env, _mk(T, per_env_counts=True, **ckw)
     second.set_state(**st)
@@ -264,10 +166,10 @@ def test_teacher_forcing_through_the_slotted_layout():
     for t in range(5):
         o1, r1, d1, i1 = first.step(a)
         o2, r2, d2, i2 = second.step(a)
-        assert torch.equal(_bits(o1), _bits(o2)) and torch.equal(_bits(r1), _bits(r2)) and torch.equal(i1["evcatches"], i2["evcatches"])
+        assert same_bits(o1, o2) and same_bits(r1, r2) and torch.equal(i1["evcatches"], i2["evcatches"])
         s1, s2 = first.get_state(), second.get_state()
         for k in s1:
-            assert torch.equal(_bits(s1[k]), _bits(s2[k])), (k, t)
+            assert same_bits(s1[k], s2[k]), (k, t)
     assert (s1["counts"].cpu().numpy() == tri).all() and (s1["t"] == st["t"] + 5).all()
 
 
@@ -275,19 +177,7 @@ def test_live_kernel_at_the_capacity_equals_the_fixed_shape_kernel():
     kw, N = dict(n_pursuers=12, n_evaders=25, n_poison=25, n_coop=3, n_sensors=16, radius=0.03), 65
     a = _mk(N, per_env_counts=True, seed=5, env_id_base=9, max_steps=15, auto_reset=True, **kw)
     b = _mk(N, seed=5, env_id_base=9, max_steps=15, auto_reset=True, **kw)
-    assert torch.equal(_bits(a.reset()), _bits(b.reset()))
-    g = torch.Generator(device="cpu").manual_seed(3)
-    for t in range(40):
-        act = (torch.rand((N, 12, 2), generator=g) * 2 - 1).to(DEV)
-        oa, ra, da, ia = a.step(act)
-        ob, rb, db, ib = b.step(act)
-        assert torch.equal(_bits(oa), _bits(ob)), "obs step %d" % t
-        assert torch.equal(_bits(ra), _bits(rb)) and torch.equal(da, db), "rewards / done step %d" % t
-        assert torch.equal(ia["evcatches"], ib["evcatches"]) and torch.equal(ia["pocatches"], ib["pocatches"]), "info step %d" % t
-        sa, sb = a.get_state(), b.get_state()
-        assert set(sa) - set(sb) == {"counts"}
-        for k in sb:
-            assert torch.equal(_bits(sa[k]), _bits(sb[k])), "state %s step %d" % (k, t)
+    assert len(list(lockstep(a, b, (N, 12, 2), 40, ("evcatches", "pocatches")))) == 40
 
 
 def _mixed(N=8, **kw):
@@ -333,43 +223,19 @@ def test_interface_errors_and_counts_across_a_new_handle():
 
 
 def test_obs_out_leaves_no_nan_in_an_uninitialised_destination():
-    env = _mixed()
-    env.reset()
-    dst = torch.empty(8 * 13 * env.obs_dim, device=DEV).fill_(float("nan"))
-    act = torch.rand((8, 13, 2), device=DEV) * 2 - 1
-    obs, rew, _done, _info = env.step(act, obs_out=dst)
-    assert obs.data_ptr() == dst.data_ptr() and not torch.isnan(dst).any()
-    absent = ~env.live_agents()
-    assert absent.any() and not _bits(obs[absent]).any() and not _bits(rew[absent]).any() and (obs[~absent].abs().amax(dim=1) > 0).all()
+    assert_obs_out_leaves_no_nan(_mixed())
 
 
 def test_rollout_collector_and_standardized_env_over_a_mixed_batch():
     from madrl_amd.heuristics import WaterworldHeuristicPolicy
-    from madrl_amd.rollout import RolloutCollector
     from madrl_amd.wrappers import StandardizedEnv
-    H = 8
-    col = RolloutCollector(_mixed(), WaterworldHeuristicPolicy(), horizon=H, store_observations=True)
-    assert col._slots
-    env, pol = _mixed(), WaterworldHeuristicPolicy()
-    obs = env.reset()
-    for it in range(2):
-        traj = col.collect()
-        torch.cuda.synchronize()
-        for t in range(H):
-            assert torch.equal(_bits(traj.observations[t]), _bits(obs)), (it, t)
-            act = pol(obs)
-            act = act[0] if isinstance(act, tuple) else act
-            assert torch.equal(_bits(traj.actions[t]), _bits(act)), (it, t)
-            obs, rew, done, _info = env.step(act)
-            assert torch.equal(_bits(traj.rewards[t]), _bits(rew)) and torch.equal(traj.dones[t] != 0, done), (it, t)
-        assert torch.equal(_bits(traj.last_observation), _bits(obs)), it
-    assert not torch.isnan(traj.observations).any() and int((traj.dones != 0).sum()) >= 8
+    assert_collector_equals_stepping_by_hand(_mixed, WaterworldHeuristicPolicy, H=8, min_dones=8)
     # StandardizedEnv takes its epilogue kernels over the capacity-shaped rows: scaling alone is the raw step times the scale, and the
     # rows of absent pursuers standardise to exactly 0 (mean 0, value 0)
     raw, scaled, normed = _mixed(), StandardizedEnv(_mixed(), scale_reward=2.0), StandardizedEnv(_mixed(), enable_obsnorm=True, enable_rewnorm=True)
     assert not scaled._fused and not normed._fused
     o0 = raw.reset()
-    assert torch.equal(_bits(scaled.reset()), _bits(o0))
+    assert same_bits(scaled.reset(), o0)
     on = normed.reset()
     absent = ~raw.live_agents()
     g = torch.Generator(device="cpu").manual_seed(2)
@@ -378,6 +244,6 @@ def test_rollout_collector_and_standardized_env_over_a_mixed_batch():
         o0, r0, d0, _ = raw.step(a)
         o1, r1, d1, _ = scaled.step(a)
         on, rn, dn, _ = normed.step(a)
-        assert torch.equal(_bits(o1), _bits(o0)) and torch.equal(_bits(r1), _bits(r0 * 2)) and torch.equal(d1, d0) and torch.equal(dn, d0), t
+        assert same_bits(o1, o0) and same_bits(r1, r0 * 2) and torch.equal(d1, d0) and torch.equal(dn, d0), t
         absent = ~raw.live_agents()
-        assert torch.isfinite(on).all() and torch.isfinite(rn).all() and not _bits(on[absent]).any() and not _bits(rn[absent]).any(), t
+        assert torch.isfinite(on).all() and torch.isfinite(rn).all() and not bits(on[absent]).any() and not bits(rn[absent]).any(), t

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import bits, same_bits
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL = 1e-5   # TOL of tests/test_waterworld_gpu.py
@@ -28,15 +30,6 @@ def _mk(n_envs, crowd=False, **kw):
     r = np.asarray(kw.get("sensor_range", 0.2), dtype=np.float64).reshape(-1)
     assert env._ranged == bool((r != r[0]).any()) and np.array_equal(env.sensor_range, np.ones(env.n_pursuers) * kw.get("sensor_range", 0.2))
     return env
-
-
-def _bits(t):
-    t = t.contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 def _cycle(values, n):
@@ -119,9 +112,9 @@ def _row_identity(shape, crowd, N=13, T=60, H=20, max_blocks=3):
         st = ranged.get_state()
         for v, tw, o, idx in zip(values, twins, tobs, rows):
             for k, s in tw.get_state().items():
-                assert _same_bits(st[k], s), "state %s, twin %g, %s" % (k, v, tag)
-            assert _same_bits(obs[:, idx], o[:, idx]), "rows of range %g, %s: %g" % (v, tag, (obs[:, idx] - o[:, idx]).abs().max())
-        return int((_bits(obs[:, others]) != _bits(tobs[values.index(ranges[0])][:, others])).any(dim=-1).sum())
+                assert same_bits(st[k], s), "state %s, twin %g, %s" % (k, v, tag)
+            assert same_bits(obs[:, idx], o[:, idx]), "rows of range %g, %s: %g" % (v, tag, (obs[:, idx] - o[:, idx]).abs().max())
+        return int((bits(obs[:, others]) != bits(tobs[values.index(ranges[0])][:, others])).any(dim=-1).sum())
 
     differ = check(ranged.reset(), [t.reset() for t in twins], "reset")
     g = torch.Generator(device="cpu").manual_seed(6)
@@ -132,7 +125,7 @@ def _row_identity(shape, crowd, N=13, T=60, H=20, max_blocks=3):
         tobs = []
         for v, tw in zip(values, twins):
             o, r, d, i = tw.step(act)
-            assert _same_bits(rew, r) and torch.equal(done, d), "rewards / done, twin %g, step %d" % (v, t)
+            assert same_bits(rew, r) and torch.equal(done, d), "rewards / done, twin %g, step %d" % (v, t)
             assert torch.equal(info["evcatches"], i["evcatches"]) and torch.equal(info["pocatches"], i["pocatches"]), "info, twin %g, step %d" % (v, t)
             tobs.append(o)
         differ += check(obs, tobs, "step %d" % t)
@@ -160,21 +153,21 @@ def test_rows_are_those_of_uniform_twins_crowd(shape):
     assert len(crowd) == 60
     if shape == "7_9_9_k12":   # a shape both families take: the two ranged kernels agree in every bit
         wave = _row_identity(shape, False)
-        assert all(_same_bits(a, b) for a, b in zip(wave, crowd))
+        assert all(same_bits(a, b) for a, b in zip(wave, crowd))
 
 
 # ------------------------------------------------------------------ switching
 def _run_same(a, b, N, Np, T, seed=3):
-    assert _same_bits(a.reset(), b.reset())
+    assert same_bits(a.reset(), b.reset())
     g = torch.Generator(device="cpu").manual_seed(seed)
     for t in range(T):
         act = (torch.rand((N, Np, 2), generator=g) * 2 - 1).to(DEV)
         oa, ra, da, ia = a.step(act)
         ob, rb, db, ib = b.step(act)
-        assert _same_bits(oa, ob) and _same_bits(ra, rb) and torch.equal(da, db), "step %d" % t
+        assert same_bits(oa, ob) and same_bits(ra, rb) and torch.equal(da, db), "step %d" % t
         assert torch.equal(ia["evcatches"], ib["evcatches"]) and torch.equal(ia["pocatches"], ib["pocatches"]), "info step %d" % t
         sa, sb = a.get_state(), b.get_state()
-        assert all(_same_bits(sa[k], sb[k]) for k in sb), "state step %d" % t
+        assert all(same_bits(sa[k], sb[k]) for k in sb), "state step %d" % t
 
 
 def test_an_all_equal_array_is_the_float():
@@ -203,19 +196,19 @@ def test_null_returns_the_handle_to_the_uniform_range(crowd):
     for t in range(6):
         x = act()
         (oa, ra, da, _), (ou, ru, du, _) = a.step(x), u.step(x)
-        assert _same_bits(ra, ru) and torch.equal(da, du) and _same_bits(oa[:, 0], ou[:, 0]) and _same_bits(oa[:, 3], ou[:, 3])
-        differed += int(not _same_bits(oa, ou))
+        assert same_bits(ra, ru) and torch.equal(da, du) and same_bits(oa[:, 0], ou[:, 0]) and same_bits(oa[:, 3], ou[:, 3])
+        differed += int(not same_bits(oa, ou))
     assert differed >= 3   # the ranges were in force
     _lib.check(L.madrl_waterworld_set_sensor_ranges(a._handle, None))
     for t in range(12):
         x = act()
         (oa, ra, da, _), (ou, ru, du, _) = a.step(x), u.step(x)
-        assert _same_bits(oa, ou) and _same_bits(ra, ru) and torch.equal(da, du), "after NULL, step %d" % t
-    assert _same_bits(a.reset(), u.reset())
+        assert same_bits(oa, ou) and same_bits(ra, ru) and torch.equal(da, du), "after NULL, step %d" % t
+    assert same_bits(a.reset(), u.reset())
     r = np.ascontiguousarray(ranges)   # ... and bound again (the handle's table is reused)
     _lib.check(L.madrl_waterworld_set_sensor_ranges(a._handle, r.ctypes.data_as(C.c_void_p)))
     x = act()
-    assert not _same_bits(a.step(x)[0][:, 4], u.step(x)[0][:, 4])
+    assert not same_bits(a.step(x)[0][:, 4], u.step(x)[0][:, 4])
 
 
 # ------------------------------------------------------------------ refusals in C
@@ -281,8 +274,8 @@ def test_ranges_survive_seed_and_a_pickle_round_trip(crowd):
     assert env._ranged and env.kernel_kind == fresh.kernel_kind
     uniform = _mk(8, crowd=crowd, sensor_range=float(RANGES5[0]), seed=23, **dict(SHAPES["5_10_10_k30"][0], max_steps=6, auto_reset=True))
     first = env.reset()
-    assert _same_bits(first[:, 0], uniform.reset()[:, 0]) and not _same_bits(first, uniform._obs)   # the ranges are in force on the new handle
-    assert _same_bits(first, fresh.reset())             # (both have been reset once: the ticks stay in step)
+    assert same_bits(first[:, 0], uniform.reset()[:, 0]) and not same_bits(first, uniform._obs)   # the ranges are in force on the new handle
+    assert same_bits(first, fresh.reset())             # (both have been reset once: the ticks stay in step)
     _run_same(env, fresh, 8, 5, 8)
     again = pickle.loads(pickle.dumps(env))             # the constructor arguments: the array travels
     assert again._ranged and np.array_equal(again.sensor_range, RANGES5) and again.kernel_kind == env.kernel_kind
@@ -304,8 +297,8 @@ def test_masked_reset_leaves_the_other_envs_rows_alone():
     m = torch.arange(9, device=DEV) % 3 == 1
     after = env.reset(mask=m)
     t1 = env.get_state()["t"]
-    assert _same_bits(after[~m], before[~m]) and torch.equal(t1[~m], t0[~m])
-    assert (t1[m] == 1).all() and not _same_bits(after[m], before[m])
+    assert same_bits(after[~m], before[~m]) and torch.equal(t1[~m], t0[~m])
+    assert (t1[m] == 1).all() and not same_bits(after[m], before[m])
 
 
 def test_obs_out_leaves_no_nan_in_an_uninitialised_destination():
@@ -329,13 +322,13 @@ def test_standardized_env_runs_its_epilogue_kernels():
     assert not auto._fused and not unfused._fused
     with pytest.raises(ValueError, match="fused=True"):
         StandardizedEnv(_ranged5(seed=7), fused=True, **kws)
-    assert _same_bits(auto.reset(), unfused.reset())
+    assert same_bits(auto.reset(), unfused.reset())
     g = torch.Generator(device="cpu").manual_seed(2)
     for t in range(8):
         a = (torch.rand((8, 5, 2), generator=g) * 2 - 1).to(DEV)
         o1, r1, d1, _ = auto.step(a)
         o2, r2, d2, _ = unfused.step(a)
-        assert _same_bits(o1, o2) and _same_bits(r1, r2) and torch.equal(d1, d2), t
+        assert same_bits(o1, o2) and same_bits(r1, r2) and torch.equal(d1, d2), t
     assert torch.isfinite(o1).all() and torch.isfinite(r1).all()
 
 
@@ -350,11 +343,11 @@ def test_rollout_collector_over_a_ranged_batch_equals_stepping_by_hand():
         traj = col.collect()
         torch.cuda.synchronize()
         for t in range(H):
-            assert _same_bits(traj.observations[t], obs), (it, t)
+            assert same_bits(traj.observations[t], obs), (it, t)
             act = pol(obs)
             act = act[0] if isinstance(act, tuple) else act
-            assert _same_bits(traj.actions[t], act), (it, t)
+            assert same_bits(traj.actions[t], act), (it, t)
             obs, rew, done, _info = env.step(act)
-            assert _same_bits(traj.rewards[t], rew) and torch.equal(traj.dones[t] != 0, done), (it, t)
-        assert _same_bits(traj.last_observation, obs), it
+            assert same_bits(traj.rewards[t], rew) and torch.equal(traj.dones[t] != 0, done), (it, t)
+        assert same_bits(traj.last_observation, obs), it
     assert not torch.isnan(traj.observations).any() and int((traj.dones != 0).sum()) >= 8

@@ -10,6 +10,9 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import i32, same_bits, slots
+from live_twins import LiveTwins, assert_collector_equals_stepping_by_hand, assert_obs_out_leaves_no_nan, lockstep, waterworld
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL = 1e-5
@@ -29,135 +32,31 @@ def _mk(n_envs, per_env_counts="wave", **kw):
     return env
 
 
-def _bits(t):
-    t = t.contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def _i32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
-
-
-def _slots(cap, tri):
-    """the slots (at the capacity) that hold the particles of a live triple, in the live class order"""
-    (P, E, _PO), (p, e, po) = cap, tri
-    return np.r_[np.arange(p), P + np.arange(e), P + E + np.arange(po)]
-
-
-class Twins(object):
-    """a per-env-counts batch on the one-wavefront kernel and one oracle twin per triple; `cur[n]`: the triple env n runs, `pend[n]`: the one
-    its next reset takes"""
-
-    def __init__(self, kw, triples, N, H, deal=None, max_blocks=0):
-        from oracle import waterworld as ww
-        self.kw, self.triples, self.N = kw, np.asarray(triples), N
-        self.cap = (kw["n_pursuers"], kw["n_evaders"], kw["n_poison"])
-        self.env = _mk(N, seed=SEED, env_id_base=BASE, max_steps=H, auto_reset=True, **kw)
-        assert self.env.kernel_kind == "wave" and self.env.per_env_counts
-        if max_blocks:
-            self.env.set_launch(max_blocks)   # one wavefront then walks envs of different triples one after the other
-        self.twins = [ww.WaterworldOracle(n_envs=N, seed=SEED, env_id_base=BASE, max_steps=H, dtype=np.float32,
-                                          **dict(kw, n_pursuers=p, n_evaders=e, n_poison=po)) for p, e, po in triples]
-        self.started = False
-        self.cur = np.full(N, -1)
-        self.pend = self.cur.copy()
-        self.set_pending(np.arange(N) % len(triples) if deal is None else deal)
-        self.evc = self.poc = self.resets = 0
-
-    def set_pending(self, idx, mask=None):
-        idx = np.broadcast_to(np.asarray(idx), (self.N,))
-        tri = self.triples[idx]
-        self.env.set_particle_counts(tri[:, 0], tri[:, 1], tri[:, 2], mask=mask)
-        self.pend = np.where(np.ones(self.N, bool) if mask is None else np.asarray(mask, bool), idx, self.pend)
-
-    def _twins_reset(self, env_mask, own_done=False):
-        """the envs of env_mask take their pending triple: the twin an env moves to gets the env's tick first and then resets it.  own_done:
-        every twin also resets the envs its own step ended (its envs that no batch env is compared with run along)"""
-        new = np.where(env_mask, self.pend, self.cur)
-        ticks = [o.get_state()["tick"] for o in self.twins]
-        for q, o in enumerate(self.twins):
-            arrive = env_mask & (new == q)
-            tk = ticks[q].copy()
-            for n in np.nonzero(arrive & (self.cur != q))[0]:
-                tk[n] = ticks[self.cur[n]][n]
-            o.set_state(tick=tk)
-            m = arrive | (o.done.astype(bool) if own_done else False)
-            if m.any():
-                o.reset(mask=m.astype(np.uint8))
-        self.cur = new
-
-    def reset(self, mask=None):
-        m = np.ones(self.N, bool) if mask is None else np.asarray(mask, bool)
-        if not self.started:
-            assert mask is None   # the first reset deals the triples; every tick is 0
-            self.started, self.cur = True, self.pend.copy()
-            for o in self.twins:
-                o.reset()
-        else:
-            self._twins_reset(m)
-        self.check(self.env.reset(mask=None if mask is None else m.astype(np.uint8)), "reset")
-
-    def step(self, act, tag):
-        obs, rew, done, info = self.env.step(act)
-        rew, done = rew.cpu().numpy(), done.cpu().numpy()
-        evc, poc = info["evcatches"].cpu().numpy(), info["pocatches"].cpu().numpy()
-        for q, (o, (p, _e, _po)) in enumerate(zip(self.twins, self.triples)):
-            o.step(act[:, :p])
-            idx = self.cur == q
-            assert np.array_equal(done[idx], o.done[idx].astype(bool)), "done %s" % tag
-            assert np.array_equal(evc[idx], o.info[idx, 0]) and np.array_equal(poc[idx], o.info[idx, 1]), "catch counts %s" % tag
-            assert np.array_equal(_i32(rew[idx, :p]), _i32(o.rew[idx])), "rewards %s" % tag
-            assert not _i32(rew[idx, p:]).any(), "rewards of absent pursuers %s" % tag
-            self.evc += int(o.info[idx, 0].sum()); self.poc += int(o.info[idx, 1].sum())
-        self.resets += int(done.sum())
-        self._twins_reset(done, own_done=True)
-        self.check(obs, tag)
-        return done
-
-    def check(self, obs, tag):
-        obs = obs.cpu().numpy()
-        st = {k: v.cpu().numpy() for k, v in self.env.get_state().items()}
-        pending, live = (c.cpu().numpy() for c in self.env.particle_counts())
-        assert np.array_equal(live, self.triples[self.cur]), "live counts %s" % tag
-        assert np.array_equal(pending, self.triples[self.pend]), "pending counts %s" % tag
-        assert np.array_equal(st["counts"], live)
-        for q, (o, tri) in enumerate(zip(self.twins, self.triples)):
-            idx, p = self.cur == q, tri[0]
-            if not idx.any():
-                continue
-            assert np.array_equal(_i32(obs[idx, :p]), _i32(o.obs[idx])), "obs %s: %g" % (tag, np.abs(obs[idx, :p] - o.obs[idx]).max())
-            assert not _i32(obs[idx, p:]).any(), "rows of absent pursuers are not +0.0, %s" % tag
-            ost, s = o.get_state(), _slots(self.cap, tri)
-            gone = np.setdiff1d(np.arange(sum(self.cap)), s)
-            assert np.array_equal(_i32(st["pos"][idx][:, s]), _i32(ost["pos"][idx])), "pos %s" % tag
-            assert np.array_equal(_i32(st["vel"][idx][:, s]), _i32(ost["vel"][idx])), "vel %s" % tag
-            assert (st["pos"][idx][:, gone] == -1.0).all() and not _i32(st["vel"][idx][:, gone]).any(), "absent slots %s" % tag
-            assert np.array_equal(_i32(st["obst"][idx]), _i32(ost["obst"][idx])), "obst %s" % tag
-            assert np.array_equal(st["t"][idx], ost["t"][idx]), "t %s" % tag
-            assert np.array_equal(st["tick"][idx].view(np.uint32), ost["tick"][idx]), "tick %s" % tag
+def _run(kw, triples, N, H, **more):
+    return LiveTwins(waterworld(kw, SEED, BASE, "wave", _mk), triples, N, H, **more)
 
 
 def _free_run(kw, triples, N, T, H, max_blocks=0):
-    run = Twins(kw, triples, N, H, max_blocks=max_blocks)
+    run = _run(kw, triples, N, H, max_blocks=max_blocks)
     run.reset()
     rng = np.random.RandomState(1)
     for t in range(T):
         run.step(rng.uniform(-1, 1, size=(N, kw["n_pursuers"], 2)).astype(np.float32), "step %d" % t)
-    print("%d evader catches, %d poison catches, %d time-limit resets" % (run.evc, run.poc, run.resets))
+    print("%d evader catches, %d poison catches, %d time-limit resets" % (run.total("evc"), run.total("poc"), run.resets))
     return run
 
 
 def test_reference_shape_as_capacity_one_wavefront_walks_mixed_envs():
     """13 envs on 3 wavefronts: a wavefront's consecutive envs have different triples -- the prefetch with capacity strides, per-env LDS contents"""
     run = _free_run(CAP_C3, TRI_C3, N=13, T=40, H=12, max_blocks=3)
-    assert run.evc > 0 and run.poc > 0 and run.resets >= 3 * 13
+    assert run.total("evc") > 0 and run.total("poc") > 0 and run.resets >= 3 * 13
 
 
 def test_both_limits_of_a_wavefront_at_once():
     """62 particles and 32 pursuers: a record of 252 dwords (4 in every lane), the action row on all 64 lanes"""
     kw = dict(n_pursuers=32, n_evaders=15, n_poison=15, n_coop=2, n_sensors=4, radius=0.03, ev_speed=0.03, action_scale=0.03)
     run = _free_run(kw, [(32, 15, 15), (32, 1, 1), (1, 15, 15), (17, 8, 9)], N=9, T=30, H=8, max_blocks=2)
-    assert run.evc + run.poc > 0 and run.resets > 0
+    assert run.total("evc") + run.total("poc") > 0 and run.resets > 0
 
 
 def test_number_of_sensing_passes_differs_per_env():
@@ -178,7 +77,7 @@ def test_variants(kw, triples):
 
 def test_counts_change_at_a_reset_not_before():
     N, H = 12, 9
-    run = Twins(CAP_C3, TRI_C3, N, H, deal=np.arange(N) % 2, max_blocks=5)   # (5, 10, 10) and (4, 9, 9)
+    run = _run(CAP_C3, TRI_C3, N, H, deal=np.arange(N) % 2, max_blocks=5)   # (5, 10, 10) and (4, 9, 9)
     run.reset()
     rng = np.random.RandomState(2)
     act = lambda: rng.uniform(-1, 1, size=(N, 5, 2)).astype(np.float32)
@@ -222,7 +121,7 @@ def test_teacher_forcing_through_the_slotted_layout():
     assert (kw["n_pursuers"], kw["n_evaders"], kw["n_poison"]) == tri
     env = _mk(T, **dict(kw, n_pursuers=cap[0], n_evaders=cap[1], n_poison=cap[2]))
     orc = ww.WaterworldOracle(n_envs=T, dtype=np.float32, sensors=g["sensors"], **kw)
-    s, NPc, p = _slots(cap, tri), sum(cap), tri[0]
+    s, NPc, p = slots(cap, tri), sum(cap), tri[0]
     gone = np.setdiff1d(np.arange(NPc), s)
     rng = np.random.RandomState(5)
 
@@ -256,31 +155,13 @@ def test_teacher_forcing_through_the_slotted_layout():
         worst, oworst = max(worst, max(errs)), max(oworst, max(oerrs))
     print("worst error kernel %.3g, float32 oracle %.3g; %d catches" % (worst, oworst, int(np.nansum(g["evc"][live]) + np.nansum(g["poc"][live]))))
     assert oworst <= TOL and worst <= TOL
-    assert np.array_equal(_i32(obs[:, :p]), _i32(oobs)) and not _i32(obs[:, p:]).any()
-    assert np.array_equal(_i32(rew[live, :p]), _i32(orew[live])) and not _i32(rew[:, p:]).any()
-    assert np.array_equal(_i32(pos1[:, s]), _i32(ost["pos"])) and np.array_equal(_i32(vel1[:, s]), _i32(ost["vel"]))
-    assert (pos1[:, gone] == -1).all() and not _i32(vel1[:, gone]).any()
+    assert np.array_equal(i32(obs[:, :p]), i32(oobs)) and not i32(obs[:, p:]).any()
+    assert np.array_equal(i32(rew[live, :p]), i32(orew[live])) and not i32(rew[:, p:]).any()
+    assert np.array_equal(i32(pos1[:, s]), i32(ost["pos"])) and np.array_equal(i32(vel1[:, s]), i32(ost["vel"]))
+    assert (pos1[:, gone] == -1).all() and not i32(vel1[:, gone]).any()
 
 
-def _same(a, b, N, Np, T, counts=False):
-    """two batches stepped with the same actions: outputs and state equal in every bit"""
-    assert torch.equal(_bits(a.reset()), _bits(b.reset()))
-    g = torch.Generator(device="cpu").manual_seed(3)
-    for t in range(T):
-        act = (torch.rand((N, Np, 2), generator=g) * 2 - 1).to(DEV)
-        oa, ra, da, ia = a.step(act)
-        ob, rb, db, ib = b.step(act)
-        assert torch.equal(_bits(oa), _bits(ob)), "obs step %d" % t
-        assert torch.equal(_bits(ra), _bits(rb)) and torch.equal(da, db), "rewards / done step %d" % t
-        assert torch.equal(ia["evcatches"], ib["evcatches"]) and torch.equal(ia["pocatches"], ib["pocatches"]), "info step %d" % t
-        sa, sb = a.get_state(), b.get_state()
-        assert set(sa) - set(sb) == (set() if counts else {"counts"})
-        for k in sb:
-            assert torch.equal(_bits(sa[k]), _bits(sb[k])), "state %s step %d" % (k, t)
-        if counts:
-            for ca, cb in zip(a.particle_counts(), b.particle_counts()):
-                assert torch.equal(ca, cb), "counts step %d" % t
-        yield t
+CATCHES = ("evcatches", "pocatches")
 
 
 @pytest.mark.parametrize("kw", [dict(CAP_C3), dict(n_pursuers=12, n_evaders=25, n_poison=25, n_coop=3, n_sensors=16, radius=0.03)],
@@ -290,7 +171,7 @@ def test_live_kernel_at_the_capacity_equals_the_fixed_shape_kernel(kw):
     a = _mk(N, seed=5, env_id_base=9, max_steps=15, auto_reset=True, **kw)
     b = _mk(N, per_env_counts=False, seed=5, env_id_base=9, max_steps=15, auto_reset=True, **kw)
     assert b.kernel_kind == "wave" and not b.per_env_counts
-    assert len(list(_same(a, b, N, kw["n_pursuers"], 40))) == 40
+    assert len(list(lockstep(a, b, (N, kw["n_pursuers"], 2), 40, CATCHES))) == 40
 
 
 def test_live_kernel_equals_the_crowd_live_kernel_on_mixed_triples():
@@ -303,7 +184,7 @@ def test_live_kernel_equals_the_crowd_live_kernel_on_mixed_triples():
     deal = tri[np.arange(N) % 5]
     for e in (a, b):
         e.set_particle_counts(deal[:, 0], deal[:, 1], deal[:, 2])
-    for t in _same(a, b, N, 12, 30, counts=True):
+    for t in lockstep(a, b, (N, 12, 2), 30, CATCHES, counts=True):
         if t == 12:   # a count change in the middle of the episodes: taken at each env's next time limit
             deal = tri[(np.arange(N) + 2) % 5]
             for e in (a, b):
@@ -389,43 +270,20 @@ def test_standardized_env_runs_its_epilogue_kernels():
     kws = dict(scale_reward=2.0, enable_obsnorm=True, enable_rewnorm=True)
     auto, unfused = StandardizedEnv(_mixed(), **kws), StandardizedEnv(_mixed(), fused=False, **kws)
     assert not auto._fused and not unfused._fused
-    assert torch.equal(_bits(auto.reset()), _bits(unfused.reset()))
+    assert same_bits(auto.reset(), unfused.reset())
     g = torch.Generator(device="cpu").manual_seed(2)
     for t in range(7):
         a = (torch.rand((8, 5, 2), generator=g) * 2 - 1).to(DEV)
         o1, r1, d1, _ = auto.step(a)
         o2, r2, d2, _ = unfused.step(a)
-        assert torch.equal(_bits(o1), _bits(o2)) and torch.equal(_bits(r1), _bits(r2)) and torch.equal(d1, d2), t
+        assert same_bits(o1, o2) and same_bits(r1, r2) and torch.equal(d1, d2), t
     assert torch.isfinite(o1).all() and torch.isfinite(r1).all()
 
 
 def test_obs_out_leaves_no_nan_in_an_uninitialised_destination():
-    env = _mixed()
-    env.reset()
-    dst = torch.empty(8 * 5 * env.obs_dim, device=DEV).fill_(float("nan"))
-    act = torch.rand((8, 5, 2), device=DEV) * 2 - 1
-    obs, rew, _done, _info = env.step(act, obs_out=dst)
-    assert obs.data_ptr() == dst.data_ptr() and not torch.isnan(dst).any()
-    absent = ~env.live_agents()
-    assert absent.any() and not _bits(obs[absent]).any() and not _bits(rew[absent]).any() and (obs[~absent].abs().amax(dim=1) > 0).all()
+    assert_obs_out_leaves_no_nan(_mixed())
 
 
 def test_rollout_collector_over_a_mixed_batch_equals_stepping_by_hand():
     from madrl_amd.heuristics import WaterworldHeuristicPolicy
-    from madrl_amd.rollout import RolloutCollector
-    H = 8
-    col = RolloutCollector(_mixed(), WaterworldHeuristicPolicy(), horizon=H, store_observations=True)
-    env, pol = _mixed(), WaterworldHeuristicPolicy()
-    obs = env.reset()
-    for it in range(2):
-        traj = col.collect()
-        torch.cuda.synchronize()
-        for t in range(H):
-            assert torch.equal(_bits(traj.observations[t]), _bits(obs)), (it, t)
-            act = pol(obs)
-            act = act[0] if isinstance(act, tuple) else act
-            assert torch.equal(_bits(traj.actions[t]), _bits(act)), (it, t)
-            obs, rew, done, _info = env.step(act)
-            assert torch.equal(_bits(traj.rewards[t]), _bits(rew)) and torch.equal(traj.dones[t] != 0, done), (it, t)
-        assert torch.equal(_bits(traj.last_observation), _bits(obs)), it
-    assert not torch.isnan(traj.observations).any() and int((traj.dones != 0).sum()) >= 8
+    assert_collector_equals_stepping_by_hand(_mixed, WaterworldHeuristicPolicy, H=8, min_dones=8)
