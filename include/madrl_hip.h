@@ -206,8 +206,11 @@ int madrl_pursuit_step_to_kernel_kind(madrl_pursuit *h, int32_t *out);
  *   BINARY16 BUFFER after the call.  The handle records the element format with the address and reuses its knowledge only when both
  *   match: the same address read in the other format is an unknown buffer.  madrl_pursuit_declare_obs_zero keeps meaning float32; a half
  *   ring starts from "nothing known" and learns.
- * The one-wavefront (X / XL) shapes of madrl_amd/csrc/pursuit_to_specializations.def have a half two-buffer kernel; every other handle
- * -- multi-wavefront, crowd, control_evaders -- runs this call on the generic kernel (madrl_pursuit_step_to_f16_kernel_kind). */
+ * The one-wavefront (X / XL) shapes of madrl_amd/csrc/pursuit_to_specializations.def have a half two-buffer kernel, and so have the
+ * multi-wavefront shapes listed in madrl_amd/csrc/pursuit_to_f16_group_specializations.def (HG lines; HLG: with per-env agent counts) --
+ * the authors' 32 x 32 training shapes, 30 v 50 and 30 v 30, among them, BASELINE configs[4] (32, 32, 16, 60, 7, 1) not.  Every other
+ * handle -- unlisted multi-wavefront shapes, crowd, control_evaders, a handle forced to MADRL_KERNEL_GENERIC -- runs this call on the
+ * generic kernel, with the same values (madrl_pursuit_step_to_f16_kernel_kind). */
 int madrl_pursuit_step_to_f16(madrl_pursuit *h, const int32_t *actions_dev, const int32_t *inj_evader_actions_dev,
                               const uint16_t *obs_prev_dev, uint16_t *obs_next_dev, float *rew_dev, uint8_t *done_dev,
                               int32_t *removed_dev, void *stream);

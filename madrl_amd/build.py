@@ -7,6 +7,7 @@
     python -m madrl_amd.build --pursuit-live-crowd-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN # ... and per-env agent counts on it
     python -m madrl_amd.build --pursuit-to-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN   # the two-buffer step (step_to) on this shape's fast kernel
     python -m madrl_amd.build --pursuit-to-group-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN [LIVE] # ... of a multi-wavefront shape (LIVE 1: with per-env agent counts)
+    python -m madrl_amd.build --pursuit-to-group-f16-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN [LIVE] # the half-precision step_to (obs_dtype=torch.float16) of a multi-wavefront shape
     python -m madrl_amd.build --waterworld-shape N_PURSUERS N_EVADERS N_POISON N_SENSORS [OBS_DIM]
 
 The fast paths (one wavefront -- or a group of wavefronts -- per env, everything about the shape a compile-time constant) exist for the
@@ -245,6 +246,35 @@ def add_pursuit_to_group_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten
     return _append_local("pursuit_to_specializations.def", line + "   // added by madrl_amd.build") or added
 
 
+def pursuit_to_group_f16_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True, live=False):
+    """-> (half line, fixed line) that give the half-precision step_to() (obs_dtype=torch.float16) of a multi-wavefront shape its fast
+    kernel: HG(..., NW) -- live: HLG(..., NW), the handles with per-env agent counts -- over an XG(..., NW) shape, or (None, why not): the
+    half kernels of a one-wavefront shape come with its --pursuit-to-shape line, the crowd kernel has no half form, and a shape without a
+    fast path has nothing to stand on.  Pure: nothing is written."""
+    kind, nw = pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
+    args = "%d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)))
+    if kind == "XG":
+        return "%s(%s, %d)" % ("HLG" if live else "HG", args, nw), "XG(%s, %d)" % (args, nw)
+    if kind == "X":
+        return None, "its fast path is the one-wavefront kernel (X), whose half kernel comes with its two-buffer line: use --pursuit-to-shape"
+    if pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)[0] is not None:
+        return None, "no multi-wavefront fast path (%s); the crowd kernel takes this shape, and it has no half form" % nw
+    return None, nw
+
+
+def add_pursuit_to_group_f16_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten, live=0):
+    """the half-precision step_to() of this multi-wavefront shape on the binary16 instantiation of the group kernel: the HG (live: HLG)
+    line in the local half list, the XG line it stands on in the local fixed list if it is missing, and with `live` the XLG line of the
+    live list"""
+    line, fixed = pursuit_to_group_f16_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, live=bool(live))
+    if line is None:
+        raise ValueError("no half-precision multi-wavefront kernel for this PursuitEvade shape: %s (the half step_to runs on the generic kernel)" % fixed)
+    added = _append_local("pursuit_specializations.def", fixed + "   // added by madrl_amd.build")
+    if live:
+        added = _append_local("pursuit_live_specializations.def", "XLG" + fixed[2:] + "   // added by madrl_amd.build") or added
+    return _append_local("pursuit_to_f16_group_specializations.def", line + "   // added by madrl_amd.build") or added
+
+
 def add_waterworld_shape(n_pursuers, n_evaders, n_poison, n_sensors, obs_dim=None):
     if obs_dim is None:
         obs_dim = n_sensors * 7 + 2 + 1          # speed features and the agent id (the reference's defaults)
@@ -323,6 +353,7 @@ if __name__ == "__main__":
                              ("--pursuit-live-crowd-shape", add_pursuit_live_crowd_shape, 6, 6),
                              ("--pursuit-to-shape", add_pursuit_to_shape, 6, 6),
                              ("--pursuit-to-group-shape", add_pursuit_to_group_shape, 6, 7),
+                             ("--pursuit-to-group-f16-shape", add_pursuit_to_group_f16_shape, 6, 7),
                              ("--waterworld-shape", add_waterworld_shape, 4, 5)):
         while flag in argv:
             i = argv.index(flag)

@@ -417,8 +417,8 @@ constexpr FastEntry LIVE_TABLE[] = {
 
 // The two-buffer step kernels (madrl_pursuit_step_to, pursuit_to.hip and pursuit_to_group.hip): reached through the fixed line of the same shape and NW, for a handle
 // with per-env agent counts through its live line.  A handle without an entry here runs step_to on the generic kernel.
-// launch_wave_f16: the binary16 form (madrl_pursuit_step_to_f16, pursuit_to_f16.hip) -- the X / XL lines have one; the other lines run the
-// half step on the generic kernel.
+// launch_wave_f16: the binary16 form (madrl_pursuit_step_to_f16, pursuit_to_f16.hip) -- the X / XL lines have one; the half kernels of the
+// multi-wavefront family are listed in TO_F16_GROUP_TABLE below, and every other handle runs the half step on the generic kernel.
 using WaveToLaunch = void (*)(const pw::WaveDev &, const pw::WaveIO &, int64_t blocks, hipStream_t s);
 using CrowdToLaunch = void (*)(const pc::CrowdDev &, const pc::CrowdIO &, const int32_t *pending, const float *obs_prev, int64_t blocks, hipStream_t s);
 struct ToEntry {
@@ -468,6 +468,39 @@ const ToEntry *find_to(const FastEntry *f, bool live) {
 }
 
 constexpr bool same_line(const FastEntry &a, const FastEntry &b) { return a.key == b.key && a.crowd() == b.crowd() && a.g.nw == b.g.nw; }
+
+// The half-precision two-buffer step kernels of the multi-wavefront family (madrl_pursuit_step_to_f16, pursuit_to_group_f16.hip and
+// pursuit_to_group_f16_live.hip): a list of its own, pursuit_to_f16_group_specializations.def.  Only launch_wave_f16 is set: a half line
+// stands on the XG line of its shape (HLG: and on its XLG line), not on a float32 two-buffer line.
+#define HG(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, false, nullptr, nullptr, pw::group_to_f16_launch<pw::THGShape<XS, YS, NP, NE, R, FL, NW>>},
+#define HLG(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, true, nullptr, nullptr, pw::group_to_f16_launch<pw::TLHGShape<XS, YS, NP, NE, R, FL, NW>>},
+constexpr ToEntry TO_F16_GROUP_TABLE[] = {
+#include "pursuit_to_f16_group_specializations.def"
+#if __has_include("pursuit_to_f16_group_specializations.local.def")
+#include "pursuit_to_f16_group_specializations.local.def"
+#endif
+};
+#undef HG
+#undef HLG
+
+// A half line without its fixed line (a live one: without its live line) would compile a kernel that no handle can use.
+constexpr bool to_f16_group_lines_have_their_lines() {
+    for (const ToEntry &t : TO_F16_GROUP_TABLE) {
+        bool fixed = false, live = !t.live;
+        for (const FastEntry &f : FAST_TABLE) fixed = fixed || (f.key == t.key && !f.crowd() && f.g.nw == t.nw && t.nw > 1);
+        for (const FastEntry &l : LIVE_TABLE) live = live || (l.key == t.key && !l.crowd() && l.g.nw == t.nw);
+        if (!fixed || !live) return false;
+    }
+    return true;
+}
+static_assert(to_f16_group_lines_have_their_lines(), "a line of pursuit_to_f16_group_specializations.def needs the XG line of its shape with the same NW in pursuit_specializations.def, an HLG line also the XLG line in pursuit_live_specializations.def");
+
+// the half two-buffer group kernel that stands on the fast line `f` (live: the per-env-count instantiation)
+const ToEntry *find_to_f16_group(const FastEntry *f, bool live) {
+    for (const ToEntry &t : TO_F16_GROUP_TABLE)
+        if (f && !f->crowd() && t.key == f->key && t.nw == f->g.nw && t.live == live) return &t;
+    return nullptr;
+}
 
 // A live line without its fixed line would compile a kernel that no handle can use.
 constexpr bool live_lines_have_fixed_lines(bool crowd) {
@@ -581,11 +614,13 @@ Dev dev_now(Dev d, const PursuitDev &now) {
 }
 
 // the two-buffer fast kernel a step_to of this handle launches, or nullptr: the generic kernel (evader control and shapes without a
-// line in pursuit_to_specializations.def).  fmt OBS_F16 (madrl_pursuit_step_to_f16): the lines whose kernel has a half form.
+// line in pursuit_to_specializations.def).  fmt OBS_F16 (madrl_pursuit_step_to_f16): the lines whose kernel has a half form -- the X / XL
+// lines of that list, and for a handle on an XG line the HG / HLG lines of pursuit_to_f16_group_specializations.def.
 const ToEntry *to_of(const madrl_pursuit *h, int fmt = OBS_F32) {
     if (!use_wave(h) || !h->dev.train_pursuit) return nullptr;
     const ToEntry *t = find_to(h->fast, h->pending != nullptr);
-    return (t && fmt == OBS_F16 && !t->launch_wave_f16) ? nullptr : t;
+    if (fmt != OBS_F16) return t;
+    return (t && t->launch_wave_f16) ? t : find_to_f16_group(h->fast, h->pending != nullptr);
 }
 
 // mode 0: reset, 1: step.  obs_prev == nullptr: in place, io.obs is read and written.  Otherwise madrl_pursuit_step_to: the step's rows go to

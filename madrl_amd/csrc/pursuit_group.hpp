@@ -30,6 +30,12 @@
 // agents span wavefronts, so the live (np, ne) are counted from the record that EVERY wavefront holds whole (dword k in lane k), not from
 // a ballot of the agent lanes: all NW wavefronts agree on them without a barrier.  Rows k >= np are not stored (their store branches stay,
 // taken by no lane), and their stale-zero mask bits are kept.
+//
+// TWO BUFFERS (TGShape / TLGShape, madrl_pursuit_step_to) and HALF-PRECISION SLOTS (THGShape / TLHGShape, madrl_pursuit_step_to_f16; the
+// HG / HLG lines of pursuit_to_f16_group_specializations.def): see the comments at those shapes below.  A half shape differs from its
+// float32 two-buffer twin in the row pass only -- 8-byte slots, converted values, kept halves carried over as bits, a load-blend-store
+// second pass -- and in the S::LEAN_REGS form of the global reward's sum; dynamics, rewards, done bits, records and the masks'
+// equilibrium are the shared kernel text.
 #pragma once
 
 #include "pursuit_wave.hpp"
@@ -90,6 +96,8 @@ struct GShape {
     static_assert(!TABLED || 3 * GSZ + 2 + P < 32768, "TABLED: dword offsets of the layers must fit 15 bits");
     static constexpr bool LIVE = false;
     static constexpr bool TO = false;
+    static constexpr bool H16 = false;                           // (THGShape / TLHGShape: binary16 observation buffers)
+    static constexpr bool LEAN_REGS = false;                     // register-pressure measures no float32 shape takes (see THGShape)
 };
 
 // Per-env agent counts on the group kernel: the same geometry with P and E as a capacity (see LShape in pursuit_wave.hpp).
@@ -112,11 +120,38 @@ template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_, int NW_>
 struct TLGShape : LGShape<XS_, YS_, P_, E_, R_, FLATTEN_, NW_> {
     static constexpr bool TO = true;
 };
+// The two-buffer step over binary16 buffers on the group kernel (madrl_pursuit_step_to_f16; the contract is THShape's in pursuit_wave.hpp):
+// io.obs and io.obs_prev point at 2-byte elements (cast: WaveDev / WaveIO do not grow), an env's rows are P * D * 2 bytes, and a slot -- the
+// same four elements, thread tid keeps slot q = tid + NT s -- is 8 bytes at q * 8.  The stale-zero mask words, the TABLED slot table and
+// the batch sizes keep their meaning.  Part 1 of the two-buffer pass (need_of) is the float32 kernel's; part 2 loads an old slot as one
+// 8-byte word (lanes that keep nothing load nothing), converts the four new values (half_bits: round to nearest even; SENT / outside and
+// known zero becomes +0.0), carries the kept halves over as the 16 bits they are -- their mask bit: "the loaded half is non-zero by its
+// bits" -- and stores the slot as ONE non-temporal 8-byte store.  The old values of a batch cost two registers per slot instead of four.
+// The second pass of a fused auto-reset is a load-blend-store of whole 8-byte slots of io.obs (half_slot_in_place, pursuit_wave.hpp): the
+// thread that wrote a slot in pass 0 reads it back, after its stores have been acknowledged, with an agent-scope load; the float32
+// in-place stores are float32 geometry and refuse to compile for these shapes (float32_slots_only below).
+// Only the flexible step kernel <S, 1, true> is instantiated (group_to_f16_launch; pursuit_to_group_f16.hip the HG lines,
+// pursuit_to_group_f16_live.hip the HLG lines of pursuit_to_f16_group_specializations.def).
+template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_, int NW_>
+struct THGShape : GShape<XS_, YS_, P_, E_, R_, FLATTEN_, NW_> {
+    static constexpr bool TO = true;
+    static constexpr bool H16 = true;
+    static constexpr bool LEAN_REGS = true;
+};
+template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_, int NW_>
+struct TLHGShape : LGShape<XS_, YS_, P_, E_, R_, FLATTEN_, NW_> {
+    static constexpr bool TO = true;
+    static constexpr bool H16 = true;
+    static constexpr bool LEAN_REGS = true;
+};
 // slots of the two-buffer pass whose old float4s are in flight together: all loads of a batch are issued before its first store (vmcnt
 // retires in order: a wait for a load is a wait for every store issued before it).  Four registers per slot and lane; the live forms
 // of the long-row shapes compile to the 128 registers of their occupancy with no room to spare (eight slots spill 76 - 80 registers).
 // Measured at the authors' 30 v 50 shape, 16 384 envs, one launch per step round a ring of nine buffers: batches of 2 slots 311 us per
-// launch, of 3 slots 295, of 4 slots 281 (profiles/r11_step_to_group): the waits bind, not the loads
+// launch, of 3 slots 295, of 4 slots 281 (profiles/r11_step_to_group): the waits bind, not the loads.
+// The binary16 forms (THGShape / TLHGShape) keep these sizes: their old values are two registers per slot, but the unrolled body of a
+// larger batch does not fit either -- at the authors' shapes batches of 5 / 6 / 8 slots compile to 13 / 17 / 55 VGPR spills (fixed) and
+// 27 / 27 / 61 (live), batches of 4 to 105 and 108 registers without one.
 #ifndef MADRL_PG_TO_BATCH
 #define MADRL_PG_TO_BATCH 4    // long rows (the rolled loop)
 #endif
@@ -128,6 +163,11 @@ struct TLGShape : LGShape<XS_, YS_, P_, E_, R_, FLATTEN_, NW_> {
 // pursuit_to_specializations.def
 template <class S>
 void group_to_launch(const WaveDev &d, const WaveIO &io, int64_t blocks, hipStream_t s);
+
+// ... and of a THGShape / TLHGShape kernel (binary16 buffers: io.obs and io.obs_prev are the half pointers, cast): explicitly instantiated
+// in pursuit_to_group_f16.hip (HG lines) and pursuit_to_group_f16_live.hip (HLG lines of pursuit_to_f16_group_specializations.def)
+template <class S>
+void group_to_f16_launch(const WaveDev &d, const WaveIO &io, int64_t blocks, hipStream_t s);
 
 // host launcher of an LGShape kernel: explicitly instantiated in pursuit_live_group.hip, one per XLG line, so that these kernels
 // compile in a translation unit of their own
@@ -141,10 +181,97 @@ __device__ __forceinline__ void group_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The global reward under S::LEAN_REGS: the sums of pursuit_wave.hpp over the lanes of wavefront 0 (lane k = pursuer k) instead of over an
+// array of P doubles.  The same additions in the same order, but the values are fetched eight lanes at a time and the scheduler cannot
+// gather all P of them -- 2 P registers -- before the first addition: at 46 and 64 pursuers the float32 kernels spill there.
+// lane k's value by its constant byte address (two ds_bpermute; __shfl would keep `lane & 64` as a loop constant)
+__device__ __forceinline__ double lane_val(double v, int k) {
+    const uint64_t b = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * k, (int)(uint32_t)b);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * k, (int)(uint32_t)(b >> 32));
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+// np_sum_regs over lanes 0 .. P - 1
+template <int P>
+__device__ __forceinline__ double np_sum_lanes(double v) {
+    if constexpr (P < 8) {
+        double res = 0.0;
+#pragma unroll
+        for (int i = 0; i < P; ++i) res += lane_val(v, i);
+        return res;
+    } else {
+        double r[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r[k] = lane_val(v, k);
+        constexpr int LIM = P - (P % 8);
+#pragma unroll
+        for (int i = 8; i < LIM; i += 8) {
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) r[k] += lane_val(v, i + k);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        double res = pairwise8(r);
+#pragma unroll
+        for (int i = LIM; i < P; ++i) res += lane_val(v, i);
+        return res;
+    }
+}
+// np_sum_first over lanes 0 .. n - 1 (n <= P, wave-uniform): a block of eight below lim = n - n % 8 goes into the eight partial sums, the
+// block at lim is kept and its first n % 8 values are added one by one after the pairwise step, as np_sum_first does
+template <int P>
+__device__ __forceinline__ double np_sum_first_lanes(double v, int n) {
+    double res = 0.0;
+    if (n < 8) {
+#pragma unroll
+        for (int i = 0; i < (P < 8 ? P : 7); ++i)
+            if (i < n) res += lane_val(v, i);
+        return res;
+    }
+    if constexpr (P >= 8) {
+        double r[8], t[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            r[k] = lane_val(v, k);
+            t[k] = 0.0;
+        }
+        const int lim = n - (n % 8);
+#pragma unroll
+        for (int i = 8; i < P; i += 8) {
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if (i + k < P) {
+                    const double a = lane_val(v, i + k);
+                    if (i < lim) r[k] += a;    // (then i + 8 <= lim <= P: a whole block)
+                    if (i == lim) t[k] = a;
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        res = pairwise8(r);
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (k < n - lim) res += t[k];
+    }
+    return res;
+}
+
+// Stands where a row pass addresses float4 slots (16 bytes at q * 16, elements 4 bytes apart): float32 geometry, which would run past the
+// end of a binary16 buffer.  H16: the caller's shape holds binary16 buffers -- refused here, wherever the call stands (as
+// store_slot_masked does in pursuit_wave.hpp): an H16 shape runs its in-place pass through half_slot_in_place.
+template <bool H16>
+__device__ __forceinline__ constexpr void float32_slots_only() {
+    static_assert(!H16, "float32 geometry: an H16 shape runs its in-place pass through half_slot_in_place");
+}
+
 template <class S, int MODE, bool INJECT>
 __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S::OCC))) void pursuit_group_kernel(const WaveDev d, const WaveIO io) {
     constexpr int P = S::P, E = S::E, A = S::A, GW = S::GW, PAD = S::PAD, GSZ = S::GSZ, NS = S::NS, NT = S::NT;
     static_assert(!S::TO || (MODE == 1 && INJECT), "the two-buffer step: the flexible step kernel only");
+    static_assert(!S::H16 || S::TO, "binary16 buffers: the two-buffer step only");
+    // an env's rows in the float-sized units of io.obs / io.obs_prev (binary16 buffers, S::H16: half as many bytes)
+    constexpr int64_t ROW = P * S::D / (S::H16 ? 2 : 1);
     __shared__ __attribute__((aligned(16))) uint32_t L[S::LDS_DWORDS];
     const int tid = threadIdx.x;            // = agent index for tid < A
     const int lane = tid & 63;
@@ -414,11 +541,16 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                     r = pr::pursuer_reward(catchr, kpre, d.term_pursuit, sur, d.urgency);
                 }
                 if (d.reward_global && wv == 0) {
+                    if constexpr (S::LEAN_REGS) {   // the same sums over the lanes, eight at a time (np_sum_lanes above)
+                        if constexpr (S::LIVE) r = isLP() ? np_sum_first_lanes<P>(r, np) / (double)np : 0.0;
+                        else r = np_sum_lanes<P>(r) / (double)P;
+                    } else {
                     double all[P];
 #pragma unroll
                     for (int k = 0; k < P; ++k) all[k] = __shfl(r, k);
                     if constexpr (S::LIVE) r = isLP() ? np_sum_first<P>(all, np) / (double)np : 0.0;
                     else r = np_sum_regs<P>(all) / (double)P;
+                    }
                 }
                 tick += 1;
                 tstep += 1;
@@ -516,8 +648,13 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                         in_place = false;
                         typedef float v4f __attribute__((ext_vector_type(4)));
                         typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-                        v4f *orow = reinterpret_cast<v4f *>(io.obs + env * (int64_t)(P * S::D));
-                        const v4u *prow = reinterpret_cast<const v4u *>(io.obs_prev + env * (int64_t)(P * S::D));
+                        typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+                        // a slot in memory: a float4 -- binary16 buffers: four halves in one 8-byte word, two per dword
+                        using old_t = std::conditional_t<S::H16, v2u, v4u>;
+                        using slot_t = std::conditional_t<S::H16, v2u, v4f>;
+                        slot_t *orow = reinterpret_cast<slot_t *>(io.obs + env * ROW);
+                        const old_t *prow = reinterpret_cast<const old_t *>(io.obs_prev + env * ROW);
+                        const old_t no_old = {};   // (zeros)
                         uint32_t acc[MW];
 #pragma unroll
                         for (int w = 0; w < MW; ++w) acc[w] = 0u;
@@ -533,7 +670,7 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                         // one slot: the kept elements from `oldv` (zeros in a lane that loaded nothing: it keeps nothing), the others from the
                         // layers -- outside cells known to be zero as +0.0 -- and the slot's new mask bits: a stored element as in the in-place
                         // pass, a kept one "the loaded value is non-zero"
-                        auto emit = [&](auto wc, int sh, int q, bool valid, bool row_live, const v4u oldv, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3) {
+                        auto emit = [&](auto wc, int sh, int q, bool valid, bool row_live, const old_t oldv, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3) {
                             constexpr int w = decltype(wc)::value;
                             const uint32_t top = __builtin_amdgcn_perm(v1, v0, 0x0C0C0703u) | __builtin_amdgcn_perm(v3, v2, 0x07030C0Cu);
                             const uint32_t out4 = (top >> 7) & 0x01010101u;
@@ -541,6 +678,22 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                             const uint32_t old4 = (zm[w] >> sh) & 0x01010101u;
                             if constexpr (!S::LIVE) row_live = true;
                             const uint32_t need4 = row_live ? (out4 & old4) : 0x01010101u;
+                            if constexpr (S::H16) {
+                                // per half: "the loaded 16 bits are non-zero"
+                                const uint32_t oldnz = ((oldv.x & 0xFFFFu) != 0u ? 0x00000001u : 0u) | ((oldv.x >> 16) != 0u ? 0x00000100u : 0u) |
+                                                       ((oldv.y & 0xFFFFu) != 0u ? 0x00010000u : 0u) | ((oldv.y >> 16) != 0u ? 0x01000000u : 0u);
+                                acc[w] = (acc[w] << 1) | (row_live ? (~out4 & nz4) : 0u) | (need4 & (valid ? oldnz : old4));
+                                if (valid) {
+                                    // converted and packed; the kept halves come from the old word, 16 bits as they are
+                                    auto hb = [](uint32_t v) -> uint32_t { return half_bits(__uint_as_float((uint32_t)max((int)v, 0))); };
+                                    uint32_t lo = hb(v0) | (hb(v1) << 16), hi = hb(v2) | (hb(v3) << 16);
+                                    const uint32_t klo = ((need4 & 0x00000001u) ? 0x0000FFFFu : 0u) | ((need4 & 0x00000100u) ? 0xFFFF0000u : 0u);
+                                    const uint32_t khi = ((need4 & 0x00010000u) ? 0x0000FFFFu : 0u) | ((need4 & 0x01000000u) ? 0xFFFF0000u : 0u);
+                                    lo = (lo & ~klo) | (oldv.x & klo);
+                                    hi = (hi & ~khi) | (oldv.y & khi);
+                                    __builtin_nontemporal_store(v2u{lo, hi}, &orow[q]);
+                                }
+                            } else {
                             const uint32_t oldnz = (oldv.x != 0u ? 0x00000001u : 0u) | (oldv.y != 0u ? 0x00000100u : 0u) |
                                                    (oldv.z != 0u ? 0x00010000u : 0u) | (oldv.w != 0u ? 0x01000000u : 0u);
                             // (a thread past the end of the rows stores and loads nothing: its bits stay what the in-place pass makes them)
@@ -554,6 +707,7 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                                 if (need4 & 0x01000000u) w3 = oldv.w;
                                 const v4f val = {__uint_as_float(w0), __uint_as_float(w1), __uint_as_float(w2), __uint_as_float(w3)};
                                 __builtin_nontemporal_store(val, &orow[q]);
+                            }
                             }
                         };
                         // Batches of slots.  Part 1: which lanes keep an element of which slot (the values are read from LDS again in part 2:
@@ -598,7 +752,7 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                                             advance(bq, bf, bp);
                                         }
                                     }
-                                    auto stores = [&](const v4u (&old)[nb]) {
+                                    auto stores = [&](const old_t (&old)[nb]) {
 #pragma unroll
                                         for (int j = 0; j < nb; ++j) {
                                             const bool valid = q < S::NQ;
@@ -609,9 +763,9 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                                             advance(q, fq, pq);
                                         }
                                     };
-                                    v4u old[nb];
+                                    old_t old[nb];
 #pragma unroll
-                                    for (int j = 0; j < nb; ++j) old[j] = v4u{0u, 0u, 0u, 0u};
+                                    for (int j = 0; j < nb; ++j) old[j] = no_old;
                                     if (__builtin_amdgcn_ballot_w64(any != 0u) != 0ull) {
 #pragma unroll
                                         for (int j = 0; j < nb; ++j)
@@ -650,7 +804,7 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                                     need[s - g0] = valid_of(sc) ? need_of(std::integral_constant<int, 0>{}, NS - 1 - s, s_org[s] - S::X_ORG < np, v0, v1, v2, v3) : 0u;
                                     any |= need[s - g0];
                                 });
-                                auto stores = [&](const v4u (&old)[TG]) {
+                                auto stores = [&](const old_t (&old)[TG]) {
                                     static_for<g0, g1>([&](auto sc) {
                                         constexpr int s = decltype(sc)::value;
                                         uint32_t v0, v1, v2, v3;
@@ -658,9 +812,9 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                                         emit(std::integral_constant<int, 0>{}, NS - 1 - s, tid + NT * s, valid_of(sc), s_org[s] - S::X_ORG < np, old[s - g0], v0, v1, v2, v3);
                                     });
                                 };
-                                v4u old[TG];
+                                old_t old[TG];
 #pragma unroll
-                                for (int j = 0; j < TG; ++j) old[j] = v4u{0u, 0u, 0u, 0u};
+                                for (int j = 0; j < TG; ++j) old[j] = no_old;
                                 if (__builtin_amdgcn_ballot_w64(any != 0u) != 0ull) {
                                     static_for<g0, g1>([&](auto sc) {
                                         constexpr int s = decltype(sc)::value;
@@ -678,7 +832,11 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                 }
                 if (in_place) {
                     typedef float v4f __attribute__((ext_vector_type(4)));
-                    v4f *orow = reinterpret_cast<v4f *>(io.obs + env * (int64_t)(P * S::D));
+                    v4f *orow = reinterpret_cast<v4f *>(io.obs + env * ROW);   // (binary16 buffers: the base of the env's rows, never indexed as float4s)
+                    // binary16 buffers: this is the second pass of a fused auto-reset, and it reads back the slots this thread stored in the
+                    // first (half_slot_in_place): they have all been acknowledged first
+                    [[maybe_unused]] const auto orow_h = (__attribute__((address_space(1))) float *)(io.obs + env * ROW);
+                    if constexpr (S::H16) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     uint32_t acc[MW];
 #pragma unroll
                     for (int w = 0; w < MW; ++w) acc[w] = 0u;
@@ -698,6 +856,13 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                         } else {
                             acc[w] = (acc[w] << 1) | (dirty | (~out4 & nz4));
                         }
+                        if constexpr (S::H16) {
+                            // binary16 buffer: the slot is 8 bytes of io.obs.  Whole slots, load-blend-store: a slot with a cell that must stay
+                            // untouched reads the first pass's word back and keeps those halves; outside cells known to be zero are written as
+                            // the zero bits they hold.  (Rows of absent pursuers, LIVE: `valid` is false, nothing is loaded or stored.)
+                            half_slot_in_place(orow_h, (uint32_t)q, valid, dirty, v0, v1, v2, v3);
+                        } else {
+                        float32_slots_only<S::H16>();   // (refuses to compile for an H16 shape should this ever be restructured)
                         if (valid) {
                             if (dirty == 0u) {
                                 if (out4 != 0x01010101u) {
@@ -712,6 +877,7 @@ __global__ __launch_bounds__(S::NT) __attribute__((amdgpu_waves_per_eu(S::OCC, S
                                 if (v2 != SENT) o[2] = __uint_as_float(v2);
                                 if (v3 != SENT) o[3] = __uint_as_float(v3);
                             }
+                        }
                         }
                     };
                     if constexpr (S::TABLED) {

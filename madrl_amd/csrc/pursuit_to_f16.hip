@@ -1,7 +1,9 @@
 // pursuit_to_f16.hip -- the half-precision two-buffer step kernels of madrl_pursuit_step_to_f16: the flexible step kernel of the
 // one-wavefront family over a THShape (pursuit_wave.hpp), one for every X line of pursuit_to_specializations.def (the XL lines, over a
-// TLHShape: pursuit_to_f16_live.hip, which is compiled with another scalar register allocator).  The
-// XG / XLG (multi-wavefront) and XC / XLC (crowd) lines have no half form: their handles run the half step on the generic kernel
+// TLHShape: pursuit_to_f16_live.hip, which is compiled with another scalar register allocator).  The half kernels of the multi-wavefront
+// family have a list of their own, pursuit_to_f16_group_specializations.def (HG / HLG lines over a THGShape / TLHGShape of
+// pursuit_group.hpp: pursuit_to_group_f16.hip, pursuit_to_group_f16_live.hip).  The XC / XLC (crowd) lines and the multi-wavefront
+// shapes not listed there have no half form: their handles run the half step on the generic kernel
 // (pursuit_to_f16_kernel, pursuit.hip).  A translation unit of its own, compiled side by side with pursuit.hip, whose TO_TABLE reaches these
 // kernels through wave_to_f16_launch<S>.
 #include "common.hpp"

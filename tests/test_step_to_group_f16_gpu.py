@@ -1,0 +1,330 @@
+"""Half-precision observation slots on the multi-wavefront family: madrl_pursuit_step_to_f16 / BatchedPursuitEvade(obs_dtype=torch.float16)
+of a handle on an HG / HLG line of csrc/pursuit_to_f16_group_specializations.def (pursuit_group_kernel over a THGShape / TLHGShape,
+pursuit_group.hpp).
+
+The yardstick is that of tests/test_step_to_f16_gpu.py, whose Ring and bit comparisons are used here: a float32 twin with the same seed
+steps through a float32 ring of three, the half env through a half ring of three; after every hop the half slot equals the float32
+slot's `.to(torch.float16)` in every bit, and rewards, done bits, removed counts and, at the end, the state records are equal.  All slots
+of a ring are carved from one tensor with 4 KiB guard bands, filled with a byte no result holds and checked after every hop; slots and
+first buffers are pre-filled with 7.0.  Every case asserts that the half env reports its fast kernel: before the half group kernels
+existed these handles ran the half step on the generic kernel."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from test_step_to_f16_gpu import DEV, F16, F32, Ring, _as_half_bits, _b16, _same16
+
+pytestmark = pytest.mark.gpu
+
+N_ENVS, HOPS = 7, 12
+
+
+def _corridors(xs, ys):
+    """rows 0 and xs - 1 free, everything between them built over: an agent never leaves its row, so the window cells beyond it stay
+    outside the map (kept cells that survive every step and reset), and three agents on a cell are common"""
+    m = np.full((xs, ys), -1, dtype=np.int32)
+    m[0, :] = m[xs - 1, :] = 0
+    return m
+
+
+def _maps(kind, xs, ys):
+    from madrl_amd.maps import rectangle_map, synthetic_map_pool
+    return {"pool": lambda: synthetic_map_pool(3, xs, ys), "rect": lambda: [rectangle_map(xs, ys)], "corridors": lambda: [_corridors(xs, ys)]}[kind]()
+
+
+def _counts(p, e):
+    return [(p, e), (p - 1, e - 1), (15, 15), (4, 4), (1, 1), (p, 1), (12, 0)]
+
+
+AUTHORS = dict(obs_range=11, flatten=True, surround=True, sample_maps=True)
+LONG = dict(flatten=True, surround=False, n_catch=2)
+# name: (maps, map size, env kwargs, per-env counts or None, twin kwargs)
+CASES = {
+    "HG_authors_30v50": ("pool", (32, 32), dict(n_pursuers=30, n_evaders=50, **AUTHORS), None, {}),
+    "HG_authors_30v50_global": ("pool", (32, 32), dict(n_pursuers=30, n_evaders=50, reward_mech="global", **AUTHORS), None, {}),
+    "HG_authors_30v30": ("pool", (32, 32), dict(n_pursuers=30, n_evaders=30, **AUTHORS), None, {}),
+    "HG_authors_30v30_one_env_per_workgroup": ("pool", (32, 32), dict(n_pursuers=30, n_evaders=30, **AUTHORS), None, dict(max_blocks=None)),
+    "HLG_authors_30v50": ("pool", (32, 32), dict(n_pursuers=30, n_evaders=50, per_env_counts=True, **AUTHORS), _counts(30, 50), {}),
+    "HLG_authors_30v30": ("pool", (32, 32), dict(n_pursuers=30, n_evaders=30, per_env_counts=True, **AUTHORS), _counts(30, 30), {}),
+    "HLG_20v50": ("rect", (16, 16), dict(n_pursuers=20, n_evaders=50, obs_range=5, flatten=True, per_env_counts=True), _counts(20, 50), {}),
+    "HLG_20v50_global": ("rect", (16, 16), dict(n_pursuers=20, n_evaders=50, obs_range=5, flatten=True, per_env_counts=True,
+                                                reward_mech="global"), _counts(20, 50), {}),
+    # the register path, fixed shape: 448 slots on 128 threads, the last slot valid in half of them
+    "HG_register_path_64v40": ("corridors", (16, 16), dict(n_pursuers=64, n_evaders=40, obs_range=3, **LONG), None, dict(rne=True)),
+    # long rows past the authors' two mask words: a mask word of 5 slots (a remainder batch of 1), one of 7 (a remainder batch of 3), and
+    # the limit: 32 slots, four mask words, 64 pursuers (and the global reward over them)
+    "HG_13_slots_36v12": ("rect", (10, 10), dict(n_pursuers=36, n_evaders=12, obs_range=11, **LONG), None, {}),
+    "HG_23_slots_46v10": ("rect", (12, 12), dict(n_pursuers=46, n_evaders=10, obs_range=13, **LONG), None, {}),
+    "HG_32_slots_64v20": ("rect", (12, 12), dict(n_pursuers=64, n_evaders=20, obs_range=13, reward_mech="global", **LONG), None, {}),
+    "HG_36v12_evader_actions": ("rect", (10, 10), dict(n_pursuers=36, n_evaders=12, obs_range=11, **LONG), None, dict(evader_actions=True)),
+    "HG_36v12_subnormal_values": ("rect", (10, 10), dict(n_pursuers=36, n_evaders=12, obs_range=11, layer_norm=30000.0, **LONG), None,
+                                  dict(subnormal=True)),
+}
+
+# The seed of every case's twins: one for which a cell that no step ever stores still reads 7.0 after the twelve hops, on the float32 twin
+# and on the generic half kernel alike (the values do not depend on the kernel).  The live cases keep whole rows of absent pursuers and
+# the cases on 10 x 10 and 12 x 12 maps have windows wider than the map, with any seed; the corridor map of the 64 v 40 case keeps the
+# cells beyond an agent's row by construction.  The authors' fixed shapes keep a 7.0 only where a window cell lies outside the map after
+# every reset: seed 1 leaves 52 such elements in the 30-pursuer cases of tests/test_step_to_group_gpu.py, which walk the same
+# trajectories (the same maps, seed, action draws and hop count); seed 21 of tests/test_step_to_f16_gpu.py leaves none.
+SEED = 1
+
+
+def _mk(name, obs_dtype=F32, n=N_ENVS, max_blocks=2, max_steps=3, seed=SEED):
+    from madrl_amd.pursuit import BatchedPursuitEvade
+    kind, (xs, ys), kw = CASES[name][:3]
+    env = BatchedPursuitEvade(_maps(kind, xs, ys), n_envs=n, device=DEV, seed=seed, max_steps=max_steps, auto_reset=True, obs_dtype=obs_dtype, **kw)
+    if max_blocks is not None:
+        env.set_launch(max_blocks=max_blocks)   # a workgroup walks several envs: the loop-carried state is exercised
+    return env
+
+
+def _prefill(env, counts=None):
+    env.obs_buffer.fill_(7.0)
+    env.invalidate_obs()
+    if counts is not None:
+        c = torch.tensor(counts, dtype=torch.int32, device=DEV)
+        env.set_agent_counts(c[:, 0], c[:, 1])
+
+
+class Twins(object):
+    """`f`: the float32 twin and its ring; `h`: the half env and its ring"""
+
+    def __init__(self, name, half_kernel=None):
+        self.counts = CASES[name][3]
+        tkw = dict(CASES[name][4])
+        self.with_eact = tkw.pop("evader_actions", False)
+        self.want_rne, self.want_subnormal = tkw.pop("rne", False), tkw.pop("subnormal", False)
+        self.f, self.h = _mk(name, **tkw), _mk(name, obs_dtype=F16, **tkw)
+        if half_kernel is not None:
+            self.h.set_kernel(half_kernel)
+        assert self.f.obs_buffer.dtype is F32 and self.h.obs_buffer.dtype is F16
+        self.P, self.E = int(self.f.n_pursuers), int(self.f.n_evaders)
+        for e in (self.f, self.h):
+            _prefill(e, self.counts)
+        shape = tuple(self.f.obs_buffer.shape)
+        self.fr, self.hr = Ring(shape, F32), Ring(shape, F16)
+        self.at = 0
+        self.gen = torch.Generator(device="cpu").manual_seed(5)
+        a, b = self.f.reset(), self.h.reset()
+        assert b.dtype is F16 and _same16(b, a), "reset() of the half env is not the float32 twin's reset .to(float16)"
+        self.sevens_at_start = int((self.h.obs_buffer == 7.0).sum())
+        assert self.sevens_at_start == int((self.f.obs_buffer == 7.0).sum())
+        self.rne_differs = self.subnormal = False
+        self.dones = torch.zeros(N_ENVS, dtype=torch.int64, device=DEV)
+
+    def actions(self):
+        act = torch.randint(0, 5, (N_ENVS, self.P), generator=self.gen).to(torch.int32).to(DEV)
+        eact = torch.randint(0, 5, (N_ENVS, self.E), generator=self.gen).to(torch.int32).to(DEV) if self.with_eact else None
+        return act, eact
+
+    def recount(self):
+        """other pending counts, taken at each env's next fused reset (the row count of an env changes between the two passes)"""
+        c = torch.tensor(self.counts[::-1], dtype=torch.int32, device=DEV)
+        for e in (self.f, self.h):
+            e.set_agent_counts(c[:, 0], c[:, 1])
+
+    def hop(self, what):
+        act, eact = self.actions()
+        k = self.at
+        prev = self.h.obs_buffer
+        prev_before = prev.clone()
+        fo, frew, fdone, finfo = self.f.step_to(act, self.fr.slots[k], evader_actions=eact)
+        ho, hrew, hdone, hinfo = self.h.step_to(act, self.hr.slots[k], evader_actions=eact)
+        torch.cuda.synchronize()
+        assert self.hr.intact() and self.fr.intact(), (what, "a guard band was written")
+        assert ho.dtype is F16 and ho.shape == fo.shape and ho.data_ptr() == self.hr.slots[k].data_ptr() == self.h.obs_buffer.data_ptr()
+        fs, hs = self.fr.slots[k], self.hr.slots[k]
+        assert _same16(hs, fs), (what, "slot", int((_b16(hs) != _as_half_bits(fs)).sum()))
+        assert torch.equal(frew.view(torch.int32), hrew.view(torch.int32)), (what, "rewards")
+        assert torch.equal(fdone, hdone), (what, "done")
+        for key in ("done_bits", "removed", "truncated", "count_overflow"):
+            assert torch.equal(finfo[key], hinfo[key]), (what, key)
+        assert torch.equal(_b16(prev), _b16(prev_before)), (what, "obs_prev was written")
+        # positive float32 values whose half was rounded UP: truncation would have given the half below
+        self.rne_differs = self.rne_differs or bool((hs.to(F32) > fs).any())
+        bits = _b16(hs).to(torch.int32) & 0xFFFF
+        self.subnormal = self.subnormal or bool(((bits > 0) & (bits < 0x0400)).any())
+        self.dones += (finfo["done_bits"] != 0).to(torch.int64)
+        self.at = (k + 1) % 3
+        self.last_rew = hrew
+        return hs
+
+    def run(self, hops=HOPS):
+        for k in range(hops):
+            if self.counts is not None and k == hops // 2:
+                self.recount()
+            self.hop(k)
+
+    def finish(self):
+        assert bool((self.dones >= 1).all()) and int(self.dones.sum()) >= N_ENVS, "max_steps=3: every env ended an episode, the second pass of a fused auto-reset ran"
+        a, b = self.f.get_state(), self.h.get_state()
+        for key in a:
+            assert torch.equal(a[key], b[key]), key
+        if self.counts is not None:
+            assert not torch.equal(self.h.agent_counts()[1].cpu(), torch.tensor(self.counts, dtype=torch.int32)), "the changed counts were never taken"
+        for env in (self.f, self.h):
+            left = int((env.obs_buffer == 7.0).sum())
+            assert left > 0, "no kept cell still reads 7.0"
+            assert left < self.sevens_at_start, "every cell that read 7.0 after the reset still does: no kept cell was ever stored"
+        if self.want_rne:
+            assert self.rne_differs, "no element whose round-to-nearest-even and truncated halves differ occurred"
+        if self.want_subnormal:
+            assert self.subnormal, "1 / 30000 is subnormal in binary16: none seen"
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_half_group_ring_equals_the_float32_ring(name):
+    tw = Twins(name)
+    assert tw.h.kernel_kind == "wave" and tw.h.step_to_kernel_kind == "wave"
+    tw.run()
+    tw.finish()
+    assert tw.h.step_to_kernel_kind == "wave"
+
+
+def test_three_agents_on_a_cell_round_to_nearest_even():
+    """0.3f (three agents on a cell at layer_norm 10) is 0x34CD in binary16; the packed round-toward-zero conversion gives 0x34CC"""
+    assert _b16(torch.tensor([0.3], dtype=F32).to(F16)).item() == 0x34CD
+    tw = Twins("HG_register_path_64v40")
+    assert tw.h.step_to_kernel_kind == "wave"
+    saw_03 = False
+    for k in range(4):
+        saw_03 = saw_03 or bool((_b16(tw.hop(k)) == 0x34CD).any())
+    assert saw_03, "0.3 (three agents on a cell) never occurred"
+    assert tw.rne_differs
+
+
+def test_forced_generic_equals_the_half_group_kernel():
+    """set_kernel('generic') keeps forcing the generic half kernel (what these handles ran before), with the same bits as the group kernel"""
+    name = "HG_13_slots_36v12"
+    g = Twins(name, half_kernel="generic")
+    assert g.h.step_to_kernel_kind == "generic" and g.h.kernel_kind == "generic"
+    w = _mk(name, obs_dtype=F16)
+    assert w.step_to_kernel_kind == "wave"
+    _prefill(w)
+    ring = Ring(tuple(w.obs_buffer.shape), F16)
+    assert torch.equal(_b16(w.reset()), _b16(g.h.obs_buffer))
+    gen = torch.Generator(device="cpu").manual_seed(5)
+    for k in range(HOPS):
+        act = torch.randint(0, 5, (N_ENVS, g.P), generator=gen).to(torch.int32).to(DEV)   # (the draws Twins.actions makes)
+        hs = g.hop(k)
+        o, rew = w.step_to(act, ring.slots[k % 3])[:2]
+        torch.cuda.synchronize()
+        assert ring.intact()
+        assert torch.equal(_b16(o).reshape(-1), _b16(hs).reshape(-1)), k
+        assert torch.equal(rew.view(torch.int32), g.last_rew.view(torch.int32)), k
+    g.finish()
+
+
+def test_c_abi_format_switch_on_a_group_handle():
+    """madrl_pursuit_step_to and madrl_pursuit_step_to_f16 alternate on ONE handle of an HG shape, through the same address in both formats:
+    what the handle knows about a buffer in one format says nothing about the same bytes read in the other.  Every call is checked
+    against a twin on the generic kernel that is given the handle's state and fresh copies of the buffers (unknown buffers by their
+    addresses)."""
+    from madrl_amd import _lib
+    L = _lib.lib()
+    name = "HG_13_slots_36v12"
+    N, P = 6, 36
+    e1, e2 = _mk(name, n=N, max_steps=2), _mk(name, n=N, max_steps=2)
+    e2.set_kernel("generic")
+    n = N * P * e1.obs_dim
+    e1.reset(), e2.reset()
+    kind = C.c_int32()
+    assert L.madrl_pursuit_step_to_f16_kernel_kind(e1._handle, C.byref(kind)) == 0 and kind.value == _lib.KERNEL_WAVE
+    assert L.madrl_pursuit_step_to_kernel_kind(e1._handle, C.byref(kind)) == 0 and kind.value == _lib.KERNEL_WAVE
+    gen = torch.Generator().manual_seed(3)
+    stream = _lib.current_stream(e1.device)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    region = torch.zeros(4 * n + 64, dtype=torch.uint8, device=DEV)   # holds a half buffer -- and, at the same address, a float32 one
+    region[2 * n:4 * n].view(F32).fill_(7.0)   # (7.0 as float32: the second half of the float32 view)
+    as_f16, as_f32 = region[:2 * n].view(F16), region[:4 * n].view(F32)
+    hA, hC, hD = e1.obs_buffer.to(F16).reshape(-1), torch.zeros(n, dtype=F16, device=DEV), torch.zeros(n, dtype=F16, device=DEV)
+    f1 = torch.zeros(n, dtype=F32, device=DEV)
+    dones = 0
+
+    def call(prev, nxt, what):
+        """one step of e1 from `prev` into `nxt` in the format of the two, and the same step of the twin"""
+        nonlocal dones
+        fn = L.madrl_pursuit_step_to_f16 if prev.dtype is F16 else L.madrl_pursuit_step_to
+        act = torch.randint(0, 5, (N, P), generator=gen).to(torch.int32).to(DEV)
+        out = [(torch.zeros((N, P), dtype=F32, device=DEV), torch.zeros(N, dtype=torch.uint8, device=DEV), torch.zeros(N, dtype=torch.int32, device=DEV))
+               for _ in range(2)]
+        e2.set_state(e1.get_state())
+        prev2, nxt2 = prev.clone(), torch.zeros_like(nxt)
+        _lib.check(fn(e1._handle, p(act), None, p(prev), p(nxt), p(out[0][0]), p(out[0][1]), p(out[0][2]), stream))
+        _lib.check(fn(e2._handle, p(act), None, p(prev2), p(nxt2), p(out[1][0]), p(out[1][1]), p(out[1][2]), stream))
+        torch.cuda.synchronize()
+        as_int = torch.int16 if nxt.dtype is F16 else torch.int32
+        assert torch.equal(nxt.view(as_int), nxt2.view(as_int)), (what, "observations", int((nxt.view(as_int) != nxt2.view(as_int)).sum()))
+        assert torch.equal(out[0][0].view(torch.int32), out[1][0].view(torch.int32)), (what, "rewards")
+        assert torch.equal(out[0][1], out[1][1]) and torch.equal(out[0][2], out[1][2]), (what, "done / removed")
+        a, b = e1.get_state(), e2.get_state()
+        for key in a:
+            assert torch.equal(a[key], b[key]), (what, key)
+        dones += int((out[0][1] != 0).sum())
+
+    call(hA, hC, "half")
+    call(hC, as_f16, "half, into the region")          # the handle's knowledge now describes the region as a binary16 buffer
+    call(as_f32, f1, "float32, from the same address")   # element i is halves 2 i and 2 i + 1, then the 7.0s: an unknown buffer
+    assert bool((f1 == 7.0).any())                       # kept cells of the float32 view did hold non-zero values
+    call(f1, as_f32, "float32, into the region")         # ... and now as a float32 buffer
+    kept = _b16(as_f16).clone()
+    call(as_f16, hD, "half, from the same address")      # halves 2 i and 2 i + 1 are float32 element i: an unknown buffer again
+    same = (_b16(hD) == kept) & (kept != 0)
+    assert bool(same.any()), "no kept half of the float32 bytes is non-zero"
+    call(hD, hC, "half again")
+    assert dones >= N, "max_steps=2: fused auto-resets occurred"
+
+
+T, NR = 4, 14
+
+
+def _policy(obs):
+    """depends only on which cells are non-zero: the count of non-zero cells of a row mod 5"""
+    return ((obs != 0).sum(dim=-1) % 5).to(torch.int32)
+
+
+def _rollout_env():
+    env = _mk("HLG_20v50", obs_dtype=F16, n=NR, max_blocks=0, seed=9)
+    _prefill(env, [_counts(20, 50)[i % 7] for i in range(NR)])
+    assert env.step_to_kernel_kind == "wave"
+    return env
+
+
+def test_rollout_collector_keeps_half_slots_of_a_live_group_batch():
+    """RolloutCollector(store_observations=True) over a half batch on an HLG line with mixed per-env counts: the step kernel writes the
+    float16 trajectory slots, eager and as a captured graph, and the trajectories are those of stepping by hand"""
+    from madrl_amd.rollout import RolloutCollector
+    h = RolloutCollector(_rollout_env(), _policy, T, store_observations=True)
+    g = RolloutCollector(_rollout_env(), _policy, T, store_observations=True, graph=True)
+    m = _rollout_env()   # by hand, through a guarded ring
+    assert h._slots and g._slots
+    ring = Ring(tuple(m.obs_buffer.shape), F16)
+    obs, at, dones = m.reset(), 0, 0
+    for it in range(3):   # (graph: call 1 eager, call 2 captures and replays, call 3 replays)
+        want = dict(observations=[], actions=[], rewards=[], dones=[])
+        for t in range(T):
+            act = _policy(obs)
+            want["observations"].append(obs.clone())
+            want["actions"].append(act)
+            obs, rew, _done, info = m.step_to(act, ring.slots[at])
+            at = (at + 1) % 3
+            want["rewards"].append(rew.clone())
+            want["dones"].append(info["done_bits"].clone())
+        b, c = h.collect(), g.collect()
+        torch.cuda.synchronize()
+        assert ring.intact()
+        dones += int((torch.stack(want["dones"]) != 0).sum())
+        for tr in (b, c):
+            assert tr.observations.dtype is F16 and tr.last_observation.dtype is F16
+            assert torch.equal(_b16(tr.observations), _b16(torch.stack(want["observations"]))), it
+            assert torch.equal(_b16(tr.last_observation), _b16(obs)), it
+            assert torch.equal(tr.actions, torch.stack(want["actions"])), it
+            assert torch.equal(tr.rewards.view(torch.int32), torch.stack(want["rewards"]).view(torch.int32)), it
+            assert torch.equal(tr.dones, torch.stack(want["dones"])), it
+    assert g._graph is not None
+    assert dones >= NR
+    assert h._obs_slots.element_size() == 2 and g._obs_slots.element_size() == 2
+    assert bool((b.last_observation == 7.0).any()), "rows of absent pursuers travel from slot to slot"
