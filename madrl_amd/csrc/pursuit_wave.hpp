@@ -121,6 +121,10 @@ struct Shape {
     static constexpr int MWORDS = 1;                             // stale-zero mask dwords per lane
     static constexpr bool ZM16 = zm16::eligible(P, R, FLATTEN);  // the masks are kept as 16 bits per lane (pursuit_zm16.hpp)
     static constexpr int ZMW = ZM16 ? 32 : 64;                   // mask dwords per env
+    // the in-place float32 pass leaves out the float4 stores of a 64-byte chunk that would write zeros over zeros ("zeros over known
+    // zeros" in the kernel).  Sound only where the pass stores into the buffer the masks describe and every mask position it trusts is a
+    // true bit: the 16-bit form (the position a lane drops is forced to "unknown"), in place, float32 -- the two-buffer shapes switch it off
+    static constexpr bool ZSKIP = ZM16;
     static constexpr int OCC = NS <= 5 ? MADRL_PW_WAVES : (MADRL_PW_WAVES < 4 ? MADRL_PW_WAVES : 4);  // resident wavefronts per SIMD aimed at
     static constexpr int X_FILL = 3 * GSZ;                       // extras after the layers
     static constexpr int X_SKIP = 3 * GSZ + 1;
@@ -170,10 +174,12 @@ constexpr int NOT_HERE = 0xFF;   // position byte of a slot that does not exist 
 template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
 struct TShape : Shape<XS_, YS_, P_, E_, R_, FLATTEN_> {
     static constexpr bool TO = true;
+    static constexpr bool ZSKIP = false;                         // (another buffer: never skips)
 };
 template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
 struct TLShape : LShape<XS_, YS_, P_, E_, R_, FLATTEN_> {
     static constexpr bool TO = true;
+    static constexpr bool ZSKIP = false;                         // (another buffer: never skips)
 };
 // The two-buffer step over binary16 buffers (madrl_pursuit_step_to_f16): io.obs and io.obs_prev point at 2-byte elements (cast: WaveIO does
 // not grow), so the env's rows are P * D * 2 bytes and a slot -- the same four elements -- is 8 bytes at (64 s + lane) * 8.  Part 1 of the
@@ -190,12 +196,14 @@ struct TLShape : LShape<XS_, YS_, P_, E_, R_, FLATTEN_> {
 template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
 struct THShape : Shape<XS_, YS_, P_, E_, R_, FLATTEN_> {
     static constexpr bool TO = true;
+    static constexpr bool ZSKIP = false;                         // (another buffer: never skips)
     static constexpr bool H16 = true;
     static constexpr bool LEAN_REGS = true;
 };
 template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
 struct TLHShape : LShape<XS_, YS_, P_, E_, R_, FLATTEN_> {
     static constexpr bool TO = true;
+    static constexpr bool ZSKIP = false;                         // (another buffer: never skips)
     static constexpr bool H16 = true;
     static constexpr bool LEAN_REGS = true;
 };
@@ -291,6 +299,13 @@ __device__ __forceinline__ void store_slot_masked(const void *base, uint32_t vof
                  "s_mov_b64 exec, %0\n\ts_nop 0"
                  : "=&s"(sv) : "s"(m0), "s"(m1), "s"(m2), "s"(m3), "s"(m_nt), "v"(voff), "v"(v0), "v"(v1), "v"(v2), "v"(v3), "v"(val),
                    "s"(base), "n"(OFF));
+}
+// a + K for a loop constant a, computed where it stands (volatile: not hoisted out of the env loop into one more live register) in ONE instruction
+template <uint32_t K>
+__device__ __forceinline__ uint32_t add_here(uint32_t a) {
+    uint32_t r;
+    asm volatile("v_add_u32 %0, %1, %2" : "=v"(r) : "n"(K), "v"(a));
+    return r;
 }
 // OR of a lane value over its aligned group of four lanes (a DPP quad): two quad_perm moves, no scalar instruction
 __device__ __forceinline__ uint32_t quad_or(uint32_t v) {
@@ -454,6 +469,8 @@ constexpr int FILL_FIRST = 56, FILL_BATCH = 16;
 //   256 every env's stale-zero mask at the address of env & 255: the mask traffic stays in L2 (timing only, wrong results)
 //   512 no mask traffic: the masks are read at env & 255 (never written: they stay in L2) and not stored, every float4 stored whole as
 //       with 2 -- against 2 this prices the mask bytes alone (timing only, wrong results)
+//   1024 S::ZSKIP shapes: no non-temporal float4 in a chunk whose clean slots get new values that are all zero or outside the map, whatever
+//       the buffer holds -- more than "zeros over known zeros" can skip, its upper bound (timing only, wrong results)
 #ifndef MADRL_ABLATE
 #define MADRL_ABLATE 0
 #endif
@@ -493,6 +510,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
     static_assert(!CTRL || !S::LIVE, "evader control has no per-env agent counts");
     static_assert(!S::TO || (MODE == 1 && INJECT && !CTRL), "the two-buffer step: the flexible step kernel only");
     static_assert(!S::H16 || S::TO, "binary16 buffers: the two-buffer step only");
+    static_assert(!S::ZSKIP || (S::ZM16 && !S::TO && !S::H16), "zeros over known zeros: the in-place float32 pass of a 16-bit-mask shape only");
     constexpr int P = S::P, E = S::E, A = S::A, GW = S::GW, PAD = S::PAD, GSZ = S::GSZ, NS = S::NS;
     __shared__ __attribute__((aligned(16))) uint32_t L[S::LDS_DWORDS];
     const int lane = threadIdx.x;
@@ -603,7 +621,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
         uint32_t pf_rec, pf_act, pf_zm;
         if constexpr (PIPE) {
             prefetch3(pf_rec, pf_act, pf_zm, d.state + nenv * (int64_t)S::REC_BYTES, rec_off, io.actions + nenv * P, act_off,
-                      d.zmask + zm_env(nenv) * S::ZMW, zm_lane * 4u);
+                      d.zmask + zm_env(nenv) * S::ZMW, (S::ZSKIP ? ((uint32_t)fresh(lane) & 31u) : zm_lane) * 4u);   // (ZSKIP: worked out again, as S::LEAN_REGS does in fetch_zm -- the rule's values take the register)
         } else {
 #if MADRL_ABLATE & 64
             nxt_rec = cur_rec ^ (uint32_t)(fresh(lane) == 0);  // no loads in the loop: is the in-order vmcnt drain what serialises a wave?
@@ -775,6 +793,9 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
             if constexpr (!PIPE) asm volatile("" : "+v"(nxt_rec), "+v"(nxt_act), "+v"(nxt_zm));
             uint32_t zm = cur_zm;  // stale-zero mask of this env: byte k, bit (4 - s) = cell k of slot s
             if constexpr (S::ZM16) zm = zm16::unpack(fresh(lane) < 32 ? cur_zm : cur_zm >> 16, zm_keep);  // (cur_zm: as loaded, two lanes' halves)
+            // (S::ZSKIP: the position the lane's 16 bits leave out reads "unknown" -- unpack fills it with its neighbour's bit, which only
+            // `out4 & old4` may consult, never the rule that trusts a zero; pack drops the position again)
+            if constexpr (S::ZSKIP) zm |= add_here<0x01010101u>(zm_keep);
 
             // One observation pass normally.  On auto-reset two: the reference sequence is step()
             // then reset(), both write the persistent observation buffer and the cells the second
@@ -928,13 +949,13 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                             }
                         }
                         bool valid = (64 * (s + 1) <= S::NQ) ? true : (fresh(lane) + 64 * s < S::NQ);
+                        uint32_t new4 = (out4 & old4) | (~out4 & nz4);   // the slot's new mask bits
                         if constexpr (CTRL || S::LIVE) {
                             const bool row_live = (s_src[s] >> 2) < n_rows;   // rows of absent observers keep their contents -- and their flags
-                            acc = (acc << 1) | (row_live ? ((out4 & old4) | (~out4 & nz4)) : old4);
+                            new4 = row_live ? new4 : old4;
                             valid = valid && row_live;
-                        } else {
-                            acc = (acc << 1) | ((out4 & old4) | (~out4 & nz4));
                         }
+                        acc = (acc << 1) | new4;
                         bool clean = dirty == 0u;
 #if MADRL_ABLATE & 1
                         valid = d.n_envs < 0;
@@ -994,8 +1015,28 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                             // 74.0, of eight: 75.8; scripts/zmask_drift.py).  (The two-wavefront kernel, whose 32 x 32 map leaves far fewer cells outside, loses
                             // with the same rule -- 86.5 against 80.4 us per 32 768-env launch -- and does not apply it.)
                             // The group of four lanes is a DPP quad: a clean lane stores iff a clean lane of its quad has a cell inside the map.
-                            const uint32_t grp = quad_or(st == 0u ? (out4 ^ 0x01010101u) : 0u);
-                            const uint32_t nt = (uint32_t)fresh(st == 0u ? (int)grp : 0);
+                            uint32_t nt;
+                            if constexpr (S::ZSKIP) {
+                                // Zeros over known zeros: `x` = the cells of this lane's slot that are NOT "known to hold +0.0f before this
+                                // pass and holding it after": an old bit set, or a non-zero value stored now.  A clean lane without one would
+                                // overwrite sixteen bytes of zeros with zeros (its outside cells are known zeros too, or it would be dirty),
+                                // so leaving its store out is exact lane by lane; the quad decides together only to keep chunks whole: the
+                                // clean lanes of a quad store iff one of them has an x.  That implies the condition of the rule above (a clean
+                                // lane's old bits and new values sit on cells inside the map) and costs what it cost: x takes the place of
+                                // the inside flags in the same quad_or and the same single compare.  Dirty lanes, lanes past the row and
+                                // lanes in an absent observer's row (st != 0) say nothing; a dirty lane stores its inside cells one by one
+                                // whatever its quad does.
+#if MADRL_ABLATE & 1024
+                                const uint32_t x = ~out4 & nz4;
+#else
+                                const uint32_t x = old4 | new4;   // (= old4 | (~out4 & nz4): the kept bits of new4 are old bits)
+#endif
+                                const uint32_t grp = quad_or(st == 0u ? x : 0u);
+                                nt = (uint32_t)fresh(st == 0u ? (int)grp : 0);
+                            } else {
+                                const uint32_t grp = quad_or(st == 0u ? (out4 ^ 0x01010101u) : 0u);
+                                nt = (uint32_t)fresh(st == 0u ? (int)grp : 0);
+                            }
                             const v4f_t val = {__uint_as_float((uint32_t)max((int)v0, 0)), __uint_as_float((uint32_t)max((int)v1, 0)),
                                                __uint_as_float((uint32_t)max((int)v2, 0)), __uint_as_float((uint32_t)max((int)v3, 0))};
                             // An outside cell with a non-zero stale value: leave it alone (Q2), store the inside cells one by one.  Plain
@@ -1079,6 +1120,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                         }
                     }
                     zm = acc;
+                    if constexpr (S::ZSKIP) zm |= add_here<0x01010101u>(zm_keep);   // (the second pass of a fused auto-reset: as above)
                 }
                 wave_sync();
                 if (alive) layer[cell] = 0u;  // restore the count layers for the next pass / env

@@ -166,7 +166,9 @@ class BatchedPursuitEvade(AbstractMAEnv):
             self._flag_views = tuple(self._flags[:, k].view(torch.bool) for k in range(3))   # done, truncated, count_overflow
             self._shape_key = shape_key
             self._obs_is_fresh = True   # every element +0.0f, like the reference's local_obs at construction (:119-120)
-            self._obs_version = None    # (no launch has written this tensor yet: nothing to compare its version counter with)
+            # the "all zero" declared below is a statement about the tensor as allocated: an in-place edit before the first launch
+            # (`env.obs_buffer.fill_(1.0)`) must end it like any later one (_check_obs_untouched)
+            self._obs_version = self._version_of_obs()
         self.obs_dim = D
         self._destroy()
         h = C.c_void_p()
