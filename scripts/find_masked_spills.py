@@ -21,7 +21,10 @@ DEF = re.compile(r"(\S+)\s+(v\[(\d+):(\d+)\]|v(\d+))[ ,]")
 
 
 def scan(path, want=""):
-    text = open(path).read()
+    return scan_text(open(path).read(), want)
+
+
+def scan_text(text, want=""):
     out = []
     for fn in re.split(r"\n\t\.globl\t", text)[1:]:
         name = fn.split("\n", 1)[0].split()[0]

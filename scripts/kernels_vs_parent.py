@@ -14,31 +14,18 @@ import re
 import shutil
 import subprocess
 import sys
-import tempfile
 
-LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
-META = (("vgprs", "vgpr_count"), ("sgprs", "sgpr_count"), ("sgpr_spills", "sgpr_spill_count"), ("private", "private_segment_fixed_size"),
-        ("vgpr_spills", "vgpr_spill_count"), ("lds", "group_segment_fixed_size"), ("kernarg", "kernarg_segment_size"))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import isa   # noqa: E402  (the tests' reader of a library's notes)
+from isa import LLVM   # noqa: E402
 
 
 def kernels(path):
     """-> {mangled name: (tuple of instruction lines, {metadata})}"""
     out = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        name = os.path.basename(path)
-        shutil.copy(path, tmp)
-        subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", name], cwd=tmp, check=True, capture_output=True)
-        for f in sorted(os.listdir(tmp)):
-            if not f.endswith("gfx950"):
-                continue
-            co = os.path.join(tmp, f)
-            meta = {}
-            notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-            for blk in re.split(r"\n  - \.agpr_count:", notes)[1:]:
-                n = re.search(r"\.name:\s+(\S+)", blk)
-                if n:
-                    meta[n.group(1)] = {k: int(re.search(r"\.%s:\s+(\d+)" % key, blk).group(1)) for k, key in META}
-                    meta[n.group(1)]["args"] = tuple(re.findall(r"- \.offset:\s+(\d+)\s+\.size:\s+(\d+)\s+\.value_kind:\s+(\w+)", blk))
+    meta = isa.built_kernels(path)
+    with isa.code_objects(path) as cos:
+        for co in cos:
             dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", co], capture_output=True, text=True, check=True).stdout
             cur = None
             for line in dis.splitlines():
@@ -92,9 +79,9 @@ def main(argv):
             ma, mb = a[k][1], b[k][1]
             print("| `%s` | %s | %s | %s | %s | %s | %s | %s | %s |" % (
                 names[k], arrow(len(a[k][0]), len(b[k][0])), arrow(ma["vgprs"], mb["vgprs"]), arrow(ma["sgprs"], mb["sgprs"]),
-                arrow(ma["sgpr_spills"], mb["sgpr_spills"]), arrow(ma["private"], mb["private"]), arrow(ma["vgpr_spills"], mb["vgpr_spills"]),
+                arrow(ma["sgpr_spills"], mb["sgpr_spills"]), arrow(ma["scratch"], mb["scratch"]), arrow(ma["vgpr_spills"], mb["vgpr_spills"]),
                 arrow(waves(ma["vgprs"]), waves(mb["vgprs"])),
-                "the parent's" if (ma["lds"], ma["kernarg"], ma["args"]) == (mb["lds"], mb["kernarg"], mb["args"]) else "CHANGED"))
+                "the parent's" if (ma["lds"], ma["kernarg"], ma["all_args"]) == (mb["lds"], mb["kernarg"], mb["all_args"]) else "CHANGED"))
 
 
 if __name__ == "__main__":

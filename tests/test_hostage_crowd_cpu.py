@@ -120,8 +120,8 @@ def test_validation_of_the_crowd_flag():
 
 
 def test_built_library_has_the_crowd_kernels_without_a_private_segment():
-    from test_kernel_metadata import _kernels
-    ks = {n: k for n, k in _kernels().items() if "hw_crowd_kernel" in n}
+    from isa import built_kernels
+    ks = {n: k for n, k in built_kernels().items() if "hw_crowd_kernel" in n}
     assert len(ks) >= 2 and any("ILi0E" in n for n in ks) and any("ILi1E" in n for n in ks), sorted(ks)   # reset and step
     for n, k in ks.items():
         assert "hostage_kernel" not in n and "waterworld_kernel" not in n

@@ -8,8 +8,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_built_library_has_the_live_count_kernels_without_a_private_segment():
-    from test_kernel_metadata import _kernels
-    ks = _kernels()
+    from isa import built_kernels
+    ks = built_kernels()
     live = {n: k for n, k in ks.items() if "hw_crowd_kernel_live" in n}
     assert len(live) >= 2 and any("ILi0E" in n for n in live) and any("ILi1E" in n for n in live), sorted(live)   # reset and step
     for n, k in live.items():

@@ -4,7 +4,7 @@ reads its kernels')."""
 import os
 import re
 
-from test_kernel_metadata import _kernels
+from isa import built_kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -45,7 +45,7 @@ def test_header_declares_and_library_exports_the_symbol():
 
 
 def test_fused_instantiations_exist_and_fit_their_occupancy():
-    ks = _kernels()
+    ks = built_kernels()
     hostage = [n for n in ks if "hostage_kernelILi" in n]
     assert len(hostage) == 8, sorted(hostage)   # reset and step x specialised and generic x plain and fused
     for (mode, *shape), waves in _fused_waves().items():

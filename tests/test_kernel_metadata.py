@@ -8,51 +8,19 @@
 * The specialised Waterworld / hostage instantiations were tuned to an occupancy at which they do not spill (spill stores reach HBM).
 """
 import os
-import re
-import shutil
-import subprocess
-import tempfile
 
-import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SO = os.path.join(os.path.dirname(HERE), "madrl_amd", "libmadrl_hip.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
-
-
-def _kernels():
-    objdump, readelf = os.path.join(LLVM, "llvm-objdump"), os.path.join(LLVM, "llvm-readelf")
-    if not (os.path.exists(SO) and os.path.exists(objdump) and os.path.exists(readelf)):
-        pytest.skip("built library or llvm tools not available")
-    out = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        shutil.copy(SO, tmp)
-        subprocess.run([objdump, "--offloading", "libmadrl_hip.so"], cwd=tmp, check=True, capture_output=True)
-        for f in sorted(os.listdir(tmp)):
-            if not f.endswith("gfx950"):
-                continue
-            notes = subprocess.run([readelf, "--notes", os.path.join(tmp, f)], capture_output=True, text=True).stdout
-            for blk in re.split(r"\n  - \.agpr_count:", notes)[1:]:
-                name = re.search(r"\.name:\s+(\S+)", blk)
-                if not name:
-                    continue
-                args = [(int(o), int(s)) for o, s in re.findall(r"- \.offset:\s+(\d+)\s+\.size:\s+(\d+)\s+\.value_kind:\s+by_value", blk)]
-                out[name.group(1)] = dict(scratch=int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)),
-                                          vgpr_spills=int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)),
-                                          vgprs=int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)), args=args)
-    assert out, "no gfx950 kernels found in the library"
-    return out
+import isa
 
 
 def test_prefetch_kernels_never_spill():
-    ks = {n: k for n, k in _kernels().items() if "pursuit_wave_kernel" in n and "ELi1ELb0ELb0EEE" in n}   # MODE 1, INJECT false, CTRL false
+    ks = {n: k for n, k in isa.built_kernels().items() if "pursuit_wave_kernel" in n and "ELi1ELb0ELb0EEE" in n}   # MODE 1, INJECT false, CTRL false
     assert len(ks) >= 11
     for n, k in ks.items():
         assert k["scratch"] == 0 and k["vgpr_spills"] == 0, (n, k)
 
 
 def test_kernarg_views_match_the_argument_layout():
-    ks = _kernels()
+    ks = isa.built_kernels()
     checked = 0
     for n, k in ks.items():
         if any(t in n for t in ("pursuit_wave_kernel", "pursuit_group_kernel", "waterworld_kernel", "hostage_kernel")):
@@ -63,7 +31,7 @@ def test_kernarg_views_match_the_argument_layout():
 
 
 def test_specialised_particle_kernels_do_not_spill():
-    ks = _kernels()
+    ks = isa.built_kernels()
     spec = {n: k for n, k in ks.items() if ("waterworld_kernelILi" in n and "ELi0ELi0ELi0ELi0E" not in n) or
             ("hostage_kernelILi" in n and "ELi0ELi0ELi0ELi0E" not in n)}
     assert len(spec) >= 10
@@ -77,7 +45,7 @@ def test_multiwalker_launches_have_no_scratch():
     named members and value-wise selects instead of indexed local arrays (multiwalker_toi.hpp V2x5).  Besides the latency of scratch
     accesses inside GJK, a kernel with a few hundred bytes of scratch per lane made the runtime re-allocate scratch around every other
     kernel on the stream: +3 ms per step next to a policy's torch kernels."""
-    ks = {n: k for n, k in _kernels().items() if "mw_step_kernel" in n}
+    ks = {n: k for n, k in isa.built_kernels().items() if "mw_step_kernel" in n}
     # three capacity classes (mwk_c4 / _c8 / _c10: 4 / 8 / 16 lanes per env) x (collide | solve | continuous pass | the whole step in one
     # launch -- since round 6 for the sixteen-lane class too, see test_no_spill_copy_runs_under_a_narrowed_exec_mask)
     assert len(ks) == 12 and sum("mwk_c10" in n for n in ks) == 4, sorted(ks)
@@ -94,27 +62,12 @@ def test_no_spill_copy_runs_under_a_narrowed_exec_mask():
     (profiles/r05_multiwalker/rocgdb_c10_fused.txt, profiles/r06_multiwalker/c10_fused_masked_spill.txt).  Round 6 removed the values
     that were live across that join (the record is found again from the lane id after the sweeps: GroupPar::rec_again) -- this test keeps
     it that way: the three capacity classes are compiled to assembly with the build's own flags and scanned (scripts/find_masked_spills.py)."""
-    import importlib.util
-    import sys
     from concurrent.futures import ThreadPoolExecutor
-    root = os.path.dirname(HERE)
-    sys.path.insert(0, root)
     from madrl_amd import build as B
-    if not os.path.exists(B.HIPCC):
-        pytest.skip("no hipcc")
-    spec = importlib.util.spec_from_file_location("find_masked_spills", os.path.join(root, "scripts", "find_masked_spills.py"))
-    fms = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(fms)
-    with tempfile.TemporaryDirectory() as tmp:
-        def asm(c):
-            out = os.path.join(tmp, c + ".s")
-            subprocess.run([B.HIPCC] + [f for f in B.FLAGS if f != "-Wall"] + B.EXTRA_FLAGS["multiwalker_c"] +
-                           ["--cuda-device-only", "-S", os.path.join(B.CSRC, "multiwalker_%s.hip" % c), "-o", out], check=True, capture_output=True)
-            return out
-        with ThreadPoolExecutor(3) as ex:
-            files = list(ex.map(asm, ("c4", "c8", "c10")))
-        for f in files:
-            text = open(f).read()
-            assert text.count("mw_step_kernelILi7E") > 0, "the one-launch kernel is missing from " + f
-            hits = fms.scan(f)
-            assert not hits, [(h[0], h[1], h[2]) for h in hits]
+    with ThreadPoolExecutor(3) as ex:   # (a missing compiler skips the test from inside the first compile)
+        texts = list(ex.map(lambda c: isa.compile_asm(None, B.EXTRA_FLAGS["multiwalker_c"], path=os.path.join(B.CSRC, "multiwalker_%s.hip" % c)),
+                            ("c4", "c8", "c10")))
+    for c, text in zip(("c4", "c8", "c10"), texts):
+        assert text.count("mw_step_kernelILi7E") > 0, "the one-launch kernel is missing from multiwalker_%s" % c
+        hits = isa.masked_spills(text)
+        assert not hits, [(h[0], h[1], h[2]) for h in hits]

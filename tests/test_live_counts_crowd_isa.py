@@ -8,36 +8,21 @@ lines of pursuit_live_specializations.def):
 import os
 import re
 import subprocess
-import sys
-import tempfile
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import isa
+from isa import CSRC
+from madrl_amd.build import pursuit_live_crowd_lines, add_pursuit_live_crowd_shape
 
-from madrl_amd.build import pursuit_live_crowd_lines, add_pursuit_live_crowd_shape   # noqa: E402
-from test_kernel_metadata import _kernels   # noqa: E402
-from test_pursuit_crowd_build import _lds_bytes   # noqa: E402
-
-CSRC = os.path.join(ROOT, "madrl_amd", "csrc")
 CAPS = [(128, 128, 100, 300, 21, 0, 16), (48, 48, 100, 300, 21, 0, 8), (24, 24, 20, 300, 9, 1, 1), (20, 20, 260, 40, 5, 1, 2)]
-
-
-def _lines(name, kinds):
-    text = open(os.path.join(CSRC, name)).read()
-    return {kind: {tuple(int(v) for v in m.group(1).split(",")) for m in re.finditer(r"^\s*%s\(([^)]*)\)" % kind, text, re.M)}
-            for kind in kinds}
 
 
 def test_def_lists_are_consistent():
     from madrl_amd import build as B
-    live = _lines("pursuit_live_specializations.def", ("XL", "XLG", "XLC"))
-    crowd = _lines("pursuit_crowd_specializations.def", ("XC",))["XC"]
-    assert live["XLC"] == set(CAPS)
+    live = isa.def_lines("pursuit_live_specializations.def", ("XL", "XLG", "XLC"))
+    crowd = isa.def_lines("pursuit_crowd_specializations.def", ("XC",))["XC"]
+    assert set(live["XLC"]) == set(CAPS)
     for line in live["XLC"]:
         assert line in crowd, line   # same shape, same NW
         assert B.pursuit_fast_path(*line[:6])[0] is None, line   # no X / XG path: that shape keeps its kernel and its XL / XLG line
@@ -107,68 +92,41 @@ def test_live_hint_names_the_crowd_line():
     assert "XLC(64,64,80,200,11,1,2)" in msg and "--pursuit-live-crowd-shape 64 64 80 200 11 1" in msg, msg
 
 
-def _live_name(cap, mode):
-    return "_ZN5madrl2pc25pursuit_live_crowd_kernelINS0_7LCShapeI%sEELi%dEEEvNS0_8CrowdDevENS0_7CrowdIOEPKi" % (
-        "".join("Li%dE" % v for v in cap), mode)
-
-
-def _fixed_name(cap, mode):
-    return "_ZN5madrl2pc20pursuit_crowd_kernelINS0_6CShapeI%sEELi%dEEEvNS0_8CrowdDevENS0_7CrowdIOE" % ("".join("Li%dE" % v for v in cap), mode)
-
-
 def test_built_live_crowd_kernels():
     from madrl_amd import build as B
-    ks = {n: k for n, k in _kernels().items() if "pursuit_live_crowd_kernel" in n}
-    lds = _lds_bytes()
+    built = isa.built_kernels()
+    ks = {n: k for n, k in built.items() if "pursuit_live_crowd_kernel" in n}
     assert len(ks) >= 2 * len(CAPS)
     for cap in CAPS:
         for mode in (0, 1):   # reset launch, step launch
-            name = _live_name(cap, mode)
+            name = isa.crowd_kernel(cap, mode, live=True)
             assert name in ks, name
             k = ks[name]
             assert k["scratch"] == 0 and k["vgpr_spills"] == 0, (name, k)
             assert k["vgprs"] <= 512 // max(64 * cap[6] // 256, 1), (name, k)
-            assert lds[name] == B.pursuit_crowd_lds_bytes(*cap[:6]) == lds[_fixed_name(cap, mode)], (name, lds[name])   # the live form adds no LDS
+            assert k["lds"] == B.pursuit_crowd_lds_bytes(*cap[:6]) == built[isa.crowd_kernel(cap, mode)]["lds"], (name, k["lds"])   # the live form adds no LDS
             (o0, s0), (o1, _s1) = k["args"][:2]   # CrowdDev and CrowdIO by value where the fixed kernel has them; the pending counts behind
             assert o0 == 0 and o1 == (s0 + 7) // 8 * 8, (name, k["args"])
 
 
-def _compile():
-    from madrl_amd import build as B
-    if not os.path.exists(B.HIPCC):
-        pytest.skip("no hipcc")
-    tu = '#include "common.hpp"\n#include "pursuit_crowd.hpp"\nnamespace madrl { namespace pc {\n'
-    for cap in CAPS:
-        for mode in (0, 1):
-            tu += "template __global__ void pursuit_crowd_kernel<CShape<%d, %d, %d, %d, %d, %d, %d>, %d>(const CrowdDev, const CrowdIO);\n" % (cap + (mode,))
-            tu += ("template __global__ void pursuit_live_crowd_kernel<LCShape<%d, %d, %d, %d, %d, %d, %d>, %d>(const CrowdDev, const CrowdIO, "
-                   "const int32_t *);\n" % (cap + (mode,)))
-    tu += "} }\n"
-    with tempfile.TemporaryDirectory() as tmp:
-        src, out = os.path.join(tmp, "crowd_live.hip"), os.path.join(tmp, "crowd_live.s")
-        with open(src, "w") as f:
-            f.write(tu)
-        subprocess.run([B.HIPCC] + [f for f in B.FLAGS if f != "-Wall"] + ["-I", CSRC, "--cuda-device-only", "-S", src, "-o", out],
-                       check=True, capture_output=True)
-        return open(out).read()
+TU = '#include "common.hpp"\n#include "pursuit_crowd.hpp"\nnamespace madrl { namespace pc {\n'
+for _cap in CAPS:
+    for _mode in (0, 1):
+        TU += "template __global__ void pursuit_crowd_kernel<CShape<%d, %d, %d, %d, %d, %d, %d>, %d>(const CrowdDev, const CrowdIO);\n" % (_cap + (_mode,))
+        TU += ("template __global__ void pursuit_live_crowd_kernel<LCShape<%d, %d, %d, %d, %d, %d, %d>, %d>(const CrowdDev, const CrowdIO, "
+               "const int32_t *);\n" % (_cap + (_mode,)))
+TU += "} }\n"
 
 
 @pytest.fixture(scope="module")
 def asm():
-    return _compile()
-
-
-def _insts(text, name):
-    lines = text.split("\n")
-    start = next(i for i, l in enumerate(lines) if l.startswith(name + ":"))
-    end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
-    return [l.split(";")[0].strip() for l in lines[start + 1:end] if l.strip() and not l.strip().startswith((";", ".", "//"))]
+    return isa.compile_asm(TU)
 
 
 @pytest.mark.parametrize("mode", [0, 1], ids=["reset", "step"])
 @pytest.mark.parametrize("cap", CAPS, ids=lambda c: "%dx%d_%dv%d" % c[:4])
 def test_live_crowd_kernel_keeps_the_fixed_kernels_stores_and_barriers(asm, cap, mode):
-    live, fix = _insts(asm, _live_name(cap, mode)), _insts(asm, _fixed_name(cap, mode))
+    live, fix = isa.kernel_insts(asm, isa.crowd_kernel(cap, mode, live=True)), isa.kernel_insts(asm, isa.crowd_kernel(cap, mode))
     nt4 = lambda k: sum(1 for i in k if i.startswith("global_store_dwordx4") and re.search(r"\bnt\b", i))
     bar = lambda k: sum(1 for i in k if i.startswith("s_barrier"))
     print(cap, mode, "non-temporal float4 stores", nt4(live), nt4(fix), "barriers", bar(live), bar(fix))

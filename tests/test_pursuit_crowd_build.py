@@ -1,11 +1,10 @@
 """CPU tests (-m "not gpu") of the PursuitEvade crowd kernel's build side: which shapes madrl_amd.build.pursuit_crowd_path accepts and how a
 shape is added, and invariants of the BUILT gfx950 kernels (one per XC line and mode, no private segment, LDS inside a workgroup's 160 KiB)."""
 import os
-import re
 
 import pytest
 
-from test_kernel_metadata import SO, LLVM, _kernels
+import isa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEF = os.path.join(ROOT, "madrl_amd", "csrc", "pursuit_crowd_specializations.def")
@@ -15,12 +14,7 @@ COMMITTED = {(128, 128, 100, 300, 21, 0): 16,   # the authors' CNN launch line (
 
 
 def _lines():
-    out = []
-    for line in open(DEF):
-        m = re.match(r"\s*XC\(([^)]*)\)", line)
-        if m:
-            out.append(tuple(int(x) for x in m.group(1).split(",")))
-    return out
+    return isa.def_lines("pursuit_crowd_specializations.def", ("XC",))["XC"]
 
 
 def test_which_shapes_can_have_a_crowd_kernel_and_how_they_are_added(tmp_path, monkeypatch):
@@ -57,39 +51,18 @@ def test_which_shapes_can_have_a_crowd_kernel_and_how_they_are_added(tmp_path, m
         assert "pursuit_crowd_specializations.local.def" in open(os.path.join(ROOT, "madrl_amd", "csrc", src)).read()
 
 
-def _lds_bytes():
-    """kernel name -> .group_segment_fixed_size of the built library's gfx950 code objects"""
-    import shutil
-    import subprocess
-    import tempfile
-    out = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        shutil.copy(SO, tmp)
-        subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", "libmadrl_hip.so"], cwd=tmp, check=True, capture_output=True)
-        for f in sorted(os.listdir(tmp)):
-            if not f.endswith("gfx950"):
-                continue
-            notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", os.path.join(tmp, f)], capture_output=True, text=True).stdout
-            for blk in re.split(r"\n  - \.agpr_count:", notes)[1:]:
-                name = re.search(r"\.name:\s+(\S+)", blk)
-                if name:
-                    out[name.group(1)] = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", blk).group(1))
-    return out
-
-
 def test_built_crowd_kernels():
     from madrl_amd import build as b
-    ks = {n: k for n, k in _kernels().items() if "pursuit_crowd_kernel" in n}
-    lds = _lds_bytes()
+    ks = {n: k for n, k in isa.built_kernels().items() if "pursuit_crowd_kernel" in n}
     lines = _lines()
     assert len(lines) >= 5 and len(ks) >= 2 * len(lines)
     for v in lines:
         for mode in (0, 1):   # reset launch, step launch
-            name = "_ZN5madrl2pc20pursuit_crowd_kernelINS0_6CShapeILi%dELi%dELi%dELi%dELi%dELi%dELi%dEEELi%dEEEvNS0_8CrowdDevENS0_7CrowdIOE" % (v + (mode,))
+            name = isa.crowd_kernel(v, mode)
             assert name in ks, name
             k = ks[name]
             assert k["scratch"] == 0, (name, k)   # no private segment: a spill store of these store-bound kernels would reach HBM
             assert k["vgprs"] <= 512 // max(64 * v[6] // 256, 1), (name, k)   # the workgroup's wavefronts fit the SIMDs' register files
-            assert lds[name] <= 163840 and lds[name] == b.pursuit_crowd_lds_bytes(*v[:6]), (name, lds[name])
+            assert k["lds"] <= 163840 and k["lds"] == b.pursuit_crowd_lds_bytes(*v[:6]), (name, k["lds"])
             (o0, s0), (o1, _s1) = k["args"][:2]   # two by-value arguments: CrowdDev, then CrowdIO
             assert o0 == 0 and o1 == (s0 + 7) // 8 * 8, (name, k["args"])

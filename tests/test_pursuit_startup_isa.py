@@ -10,21 +10,15 @@ instantiation and two multi-wavefront ones for gfx950 with the build's own flags
     per-env-counts instantiations (LGShape), whose second batch is the first env's record, action and masks;
   * all three: no scratch, no VGPR spills, and not more VGPRs than the kernels had with the serial fills.
 """
-import os
 import re
-import subprocess
-import sys
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import isa
 
-# kernel -> VGPRs of the build before the staged start-up (the headline's 96 is also its budget at five wavefronts per SIMD)
+# kernel -> (instantiation, VGPRs of the build before the staged start-up; the headline's 96 is also its budget at five wavefronts per SIMD)
 KERNELS = {
-    "wave": ("pursuit_wave_kernel<Shape<16, 16, 8, 30, 7, 1>, 1, false, false>", 96),
+    "wave": ("pursuit_wave_kernel<Shape<16, 16, 8, 30, 7, 1>, 1, false, false>", isa.HEADLINE_VGPRS),
     "group_c5": ("pursuit_group_kernel<GShape<32, 32, 16, 60, 7, 1, 2>, 1, false>", 115),
     "group_authors": ("pursuit_group_kernel<GShape<32, 32, 30, 50, 11, 1, 4>, 1, false>", 113),
 }
@@ -34,11 +28,11 @@ LIVE_KERNELS = {
     "live_authors": "pursuit_group_kernel<LGShape<32, 32, 30, 50, 11, 1, 4>, 1, false>",
 }
 MANGLED = {
-    "live_20v50": "_ZN5madrl2pw20pursuit_group_kernelINS0_7LGShapeILi16ELi16ELi20ELi50ELi5ELi1ELi2EEELi1ELb0EEEvNS0_7WaveDevENS0_6WaveIOE",
-    "live_authors": "_ZN5madrl2pw20pursuit_group_kernelINS0_7LGShapeILi32ELi32ELi30ELi50ELi11ELi1ELi4EEELi1ELb0EEEvNS0_7WaveDevENS0_6WaveIOE",
-    "wave": "_ZN5madrl2pw19pursuit_wave_kernelINS0_5ShapeILi16ELi16ELi8ELi30ELi7ELi1EEELi1ELb0ELb0EEEvNS0_7WaveDevENS0_6WaveIOE",
-    "group_c5": "_ZN5madrl2pw20pursuit_group_kernelINS0_6GShapeILi32ELi32ELi16ELi60ELi7ELi1ELi2EEELi1ELb0EEEvNS0_7WaveDevENS0_6WaveIOE",
-    "group_authors": "_ZN5madrl2pw20pursuit_group_kernelINS0_6GShapeILi32ELi32ELi30ELi50ELi11ELi1ELi4EEELi1ELb0EEEvNS0_7WaveDevENS0_6WaveIOE",
+    "live_20v50": isa.group_kernel("LGShape", (16, 16, 20, 50, 5, 1, 2)),
+    "live_authors": isa.group_kernel("LGShape", (32, 32, 30, 50, 11, 1, 4)),
+    "wave": isa.HEADLINE,
+    "group_c5": isa.group_kernel("GShape", (32, 32, 16, 60, 7, 1, 2)),
+    "group_authors": isa.group_kernel("GShape", (32, 32, 30, 50, 11, 1, 4)),
 }
 
 TU = """#include "common.hpp"
@@ -52,51 +46,11 @@ namespace madrl { namespace pw {
 
 @pytest.fixture(scope="module")
 def asm_text():
-    from madrl_amd import build as B
-    if not os.path.exists(B.HIPCC):
-        pytest.skip("no hipcc")
-    with tempfile.TemporaryDirectory() as tmp:
-        src, out = os.path.join(tmp, "startup.hip"), os.path.join(tmp, "startup.s")
-        with open(src, "w") as f:
-            f.write(TU)
-        subprocess.run([B.HIPCC] + [f for f in B.FLAGS if f != "-Wall"] + ["-I", B.CSRC, "--cuda-device-only", "-S", src, "-o", out],
-                       check=True, capture_output=True)
-        return open(out).read()
-
-
-def _blocks(text, name):
-    """the basic blocks of a kernel in layout order: (label, annotation text, instructions)"""
-    lines = text.split("\n")
-    start = next(i for i, l in enumerate(lines) if l.startswith(MANGLED[name] + ":"))
-    end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
-    blocks, cur = [], None
-    for l in lines[start + 1:end]:
-        m = re.match(r"^(?:\.L(BB\d+_\d+):|; %bb\.\d+:)", l)
-        if m:
-            cur = dict(name=m.group(1), notes=l, insts=[], open=True)
-            blocks.append(cur)
-        elif cur is not None:
-            t = l.strip()
-            if t.startswith(";") and cur["open"]:
-                cur["notes"] += " " + t
-            elif t and not t.startswith((";", ".")):
-                cur["open"] = False
-                cur["insts"].append(t.split(";")[0].strip())
-    return blocks
+    return isa.compile_asm(TU)
 
 
 def _before_env_loop(text, name):
-    """-> (blocks before the env loop, names of the loop headers among them).  The env loop is the outermost loop (Depth=1 header) that
-    holds global stores; every block of it is annotated with its header, so 'before' = not in that loop and laid out before its header."""
-    blocks = _blocks(text, name)
-    in_loop = lambda b, h: b["name"] == h or ("Header=%s " % h) in b["notes"] + " " or ("Parent Loop %s " % h) in b["notes"] + " "
-    heads = [b["name"] for b in blocks if "Loop Header: Depth=1" in b["notes"]]
-    env = [h for h in heads if any(i.startswith("global_store") for b in blocks if in_loop(b, h) for i in b["insts"])]
-    assert len(env) == 1, "expected one top-level loop with global stores (the env loop), found %r" % env
-    at = next(i for i, b in enumerate(blocks) if b["name"] == env[0])
-    pre = [b for b in blocks[:at] if not in_loop(b, env[0])]
-    assert pre, "no code before the env loop?"
-    return pre, [b["name"] for b in pre if "Loop Header" in b["notes"]]
+    return isa.before_env_loop(isa.blocks(isa.kernel_body(text, MANGLED[name])))
 
 
 def _events(pre):
@@ -131,11 +85,7 @@ def test_group_startup_is_at_most_two_batches(asm_text, name):
 
 @pytest.mark.parametrize("name", sorted(KERNELS))
 def test_startup_register_budget(asm_text, name):
-    meta = asm_text[asm_text.index("amdhsa.kernels:"):]
-    entries = [e for e in re.split(r"\n  - (?=\.)", meta) if re.search(r"\.name:\s+%s\n" % re.escape(MANGLED[name]), e)]   # one list item per kernel
-    assert len(entries) == 1
-    entry = entries[0]
-    get = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, entry).group(1))
-    assert get("private_segment_fixed_size") == 0
-    assert get("vgpr_spill_count") == 0
-    assert get("vgpr_count") <= KERNELS[name][1], "%d VGPRs, %d before" % (get("vgpr_count"), KERNELS[name][1])
+    meta = isa.kernel_meta(asm_text, MANGLED[name])
+    assert meta["private_segment_fixed_size"] == 0
+    assert meta["vgpr_spill_count"] == 0
+    assert meta["vgpr_count"] <= KERNELS[name][1], "%d VGPRs, %d before" % (meta["vgpr_count"], KERNELS[name][1])

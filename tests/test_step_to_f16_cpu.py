@@ -3,30 +3,27 @@ two-buffer kernels beside the float32 ones, and the obs_dtype argument of Batche
 import ctypes as C
 import inspect
 import os
-import re
 
 import pytest
 import torch
 
-from test_kernel_metadata import SO, _kernels
+import isa
+from isa import SO
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, "..", "madrl_amd", "csrc")
 
 
 def _to_lines():
     """the X / XL lines of pursuit_to_specializations.def: (live, (xs, ys, p, e, r, flatten))"""
-    out = []
-    for m in re.finditer(r"^\s*(XL?)\(([^)]*)\)", open(os.path.join(CSRC, "pursuit_to_specializations.def")).read(), re.M):
-        out.append((m.group(1) == "XL", tuple(int(v) for v in m.group(2).split(","))))
+    lines = isa.def_lines("pursuit_to_specializations.def", ("X", "XL"))
+    out = [(False, v) for v in lines["X"]] + [(True, v) for v in lines["XL"]]
     assert len(out) >= 5 and any(live for live, _ in out), "the list has X and XL lines"
     return out
 
 
 def _wave_name(shape_type, args):
     """the mangled name of pursuit_wave_kernel<pw::SHAPE<args>, 1, true, false>"""
-    return ("_ZN5madrl2pw19pursuit_wave_kernelINS0_%d%sI%sEELi1ELb1ELb0EEEvNS0_7WaveDevENS0_6WaveIOE"
-            % (len(shape_type), shape_type, "".join("Li%dE" % v for v in args)))
+    return isa.wave_kernel(shape_type, args, inject=True)
 
 
 def test_the_library_exports_both_symbols():
@@ -43,20 +40,11 @@ def test_the_library_exports_both_symbols():
     assert header.index("int madrl_pursuit_step_to(") < header.index("int madrl_pursuit_step_to_f16(") < header.index("int madrl_pursuit_step_sharded(")
 
 
-_KS = {}
-
-
-def _all_kernels():
-    if not _KS:
-        _KS.update(_kernels())
-    return _KS
-
-
 @pytest.mark.parametrize("live,args", _to_lines(), ids=lambda v: "-".join(str(x) for x in v) if isinstance(v, tuple) else ("XL" if v else "X"))
 def test_every_one_wavefront_line_has_its_half_kernel(live, args):
     """(The XL kernels are compiled in a translation unit of their own, pursuit_to_f16_live.hip, with the basic scalar register allocator:
     the default one leaves them a 20-byte private segment that no instruction touches.)"""
-    ks = _all_kernels()
+    ks = isa.built_kernels()
     half = ks.get(_wave_name("TLHShape" if live else "THShape", args))
     f32 = ks.get(_wave_name("TLShape" if live else "TShape", args))
     assert f32 is not None, ("the float32 two-buffer kernel is gone", live, args)
@@ -68,7 +56,7 @@ def test_every_one_wavefront_line_has_its_half_kernel(live, args):
 
 
 def test_the_generic_half_kernels_take_the_float32_kernels_arguments():
-    ks = _kernels()
+    ks = isa.built_kernels()
     half = {n: k for n, k in ks.items() if "pursuit_to_f16_kernel" in n}
     f32 = {n: k for n, k in ks.items() if "pursuit_to_kernel" in n}
     assert len(half) == 16 and len(f32) == 16   # NT 1..8, with and without per-env agent counts

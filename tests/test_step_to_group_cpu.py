@@ -8,19 +8,12 @@ import os
 import re
 import subprocess
 import sys
-import tempfile
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, HERE, os.path.join(ROOT, "scripts")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import isa
+from isa import CSRC, ROOT
 
-import test_live_counts_group_isa as group_isa   # noqa: E402  (_body, _meta, _env_loop)
-
-CSRC = os.path.join(ROOT, "madrl_amd", "csrc")
 CAPS = [(32, 32, 16, 60, 7, 1, 2), (32, 32, 30, 50, 11, 1, 4), (16, 16, 20, 50, 5, 1, 2)]
 IN_PLACE = {"TGShape": "GShape", "TLGShape": "LGShape"}
 REQUIRED = {
@@ -29,20 +22,13 @@ REQUIRED = {
 }
 
 
-def _lines(name):
-    out = {}
-    for m in re.finditer(r"^\s*(X[A-Z]*)\(([^)]*)\)", open(os.path.join(CSRC, name)).read(), re.M):
-        out.setdefault(m.group(1), []).append(tuple(int(v) for v in m.group(2).split(",")))
-    return out
-
-
 def test_committed_group_lines_stand_on_their_fast_lines():
-    to = _lines("pursuit_to_specializations.def")
+    to = isa.def_lines("pursuit_to_specializations.def")
     for kind, shapes in REQUIRED.items():
         for s in shapes:
             assert s in to.get(kind, []), (kind, s)
-    fixed = _lines("pursuit_specializations.def").get("XG", [])
-    live = _lines("pursuit_live_specializations.def").get("XLG", [])
+    fixed = isa.def_lines("pursuit_specializations.def", ("XG",))["XG"]
+    live = isa.def_lines("pursuit_live_specializations.def", ("XLG",))["XLG"]
     for s in to.get("XG", []) + to.get("XLG", []):
         assert s in fixed, s          # (the same NW: the tuple holds it)
     for s in to.get("XLG", []):
@@ -90,62 +76,37 @@ def test_build_refuses_a_shape_without_a_group_fast_path(shape, reason):
 
 
 # ------------------------------------------------------------------ emitted code
-def _compile():
-    from madrl_amd import build as B
-    if not os.path.exists(B.HIPCC):
-        pytest.skip("no hipcc")
-    tu = '#include "common.hpp"\n#include "pursuit_group.hpp"\nnamespace madrl { namespace pw {\n'
-    for kind in ("GShape", "TGShape", "LGShape", "TLGShape"):
-        for cap in CAPS:
-            tu += "template __global__ void pursuit_group_kernel<%s<%d, %d, %d, %d, %d, %d, %d>, 1, true>(const WaveDev, const WaveIO);\n" % (
-                (kind,) + cap)
-    tu += "} }\n"
-    with tempfile.TemporaryDirectory() as tmp:
-        src, out = os.path.join(tmp, "group_to.hip"), os.path.join(tmp, "group_to.s")
-        with open(src, "w") as f:
-            f.write(tu)
-        subprocess.run([B.HIPCC] + [f for f in B.FLAGS if f != "-Wall"] + ["-I", CSRC, "--cuda-device-only", "-S", src, "-o", out],
-                       check=True, capture_output=True)
-        import find_masked_spills
-        masked = find_masked_spills.scan(out, "TGShape") + find_masked_spills.scan(out, "TLGShape")
-        text = open(out).read()
-    return text, masked
+TU = isa.group_tu([(kind, cap) for kind in ("GShape", "TGShape", "LGShape", "TLGShape") for cap in CAPS], inject=True)
 
 
 @pytest.fixture(scope="module")
 def asm():
-    return _compile()
-
-
-def _mangled(kind, cap):
-    return "_ZN5madrl2pw20pursuit_group_kernelINS0_%d%sI%sEELi1ELb1EEEvNS0_7WaveDevENS0_6WaveIOE" % (
-        len(kind), kind, "".join("Li%dE" % v for v in cap))
+    return isa.compile_asm(TU)
 
 
 KERNELS = [(kind, cap) for kind in ("TGShape", "TLGShape") for cap in CAPS]
 _id = lambda v: v if isinstance(v, str) else "%dv%d" % (v[2], v[3])
+_mangled = lambda kind, cap: isa.group_kernel(kind, cap, inject=True)
 
 
 @pytest.mark.parametrize("kind,cap", KERNELS, ids=_id)
 def test_two_buffer_group_kernel_no_scratch(asm, kind, cap):
-    meta = group_isa._meta(asm[0], _mangled(kind, cap))
-    assert re.search(r"\.private_segment_fixed_size:\s+0\b", meta), meta
-    assert re.search(r"\.vgpr_spill_count:\s+0\b", meta), meta
+    meta = isa.kernel_meta(asm, _mangled(kind, cap))
+    assert meta["private_segment_fixed_size"] == 0 and meta["vgpr_spill_count"] == 0, meta
 
 
 def test_two_buffer_group_kernels_have_no_masked_spills(asm):
-    assert asm[1] == []
+    assert isa.masked_spills(asm, "TGShape") + isa.masked_spills(asm, "TLGShape") == []
 
 
 @pytest.mark.parametrize("kind,cap", KERNELS, ids=_id)
 def test_two_buffer_group_kernel_adds_no_barrier_and_loads_float4s(asm, kind, cap):
-    to = group_isa._body(asm[0], _mangled(kind, cap))
-    ip = group_isa._body(asm[0], _mangled(IN_PLACE[kind], cap))
-    barriers = lambda body: sum(1 for l in body if l.strip().startswith("s_barrier"))
+    to, ip = _mangled(kind, cap), _mangled(IN_PLACE[kind], cap)
+    barriers = lambda name: sum(1 for i in isa.kernel_insts(asm, name) if i.startswith("s_barrier"))
     assert barriers(to) == barriers(ip) and barriers(ip) > 0, (barriers(to), barriers(ip))
-    loop = group_isa._env_loop(to)
+    loop, ip_loop = isa.store_env_loop(asm, to), isa.store_env_loop(asm, ip)
     assert any(i.startswith("global_load_dwordx4") for i in loop)
-    assert not any(i.startswith("global_load_dwordx4") for i in group_isa._env_loop(ip))   # (the in-place pass loads no float4: the check above sees the new loads)
+    assert not any(i.startswith("global_load_dwordx4") for i in ip_loop)   # (the in-place pass loads no float4: the check above sees the new loads)
     # whole stores only: the two-buffer kernel adds non-temporal float4 stores, and no dword store, to the in-place kernel's
     dword = lambda l: sum(1 for i in l if re.match(r"global_store_dword\s", i))
-    assert dword(loop) == dword(group_isa._env_loop(ip))
+    assert dword(loop) == dword(ip_loop)

@@ -6,20 +6,12 @@ import os
 import re
 import subprocess
 import sys
-import tempfile
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, HERE, os.path.join(ROOT, "scripts")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import isa
+from isa import CSRC, ROOT
 
-import test_kernel_metadata as built          # noqa: E402  (_kernels)
-import test_live_counts_group_isa as group_isa   # noqa: E402  (_body, _meta)
-
-CSRC = os.path.join(ROOT, "madrl_amd", "csrc")
 DEF = "pursuit_to_f16_group_specializations.def"
 REQUIRED = {
     "HG": [(32, 32, 30, 50, 11, 1, 4), (32, 32, 30, 30, 11, 1, 4), (10, 10, 36, 12, 11, 1, 4), (12, 12, 46, 10, 13, 1, 4),
@@ -31,16 +23,7 @@ IN_PLACE = {"THGShape": "GShape", "TLHGShape": "LGShape"}
 FLOAT32 = {"THGShape": "TGShape", "TLHGShape": "TLGShape"}
 
 
-def _lines(name):
-    out = {}
-    for m in re.finditer(r"^\s*([XH][A-Z]*)\(([^)]*)\)", open(os.path.join(CSRC, name)).read(), re.M):
-        out.setdefault(m.group(1), []).append(tuple(int(v) for v in m.group(2).split(",")))
-    return out
-
-
-def _mangled(kind, cap):
-    return "_ZN5madrl2pw20pursuit_group_kernelINS0_%d%sI%sEELi1ELb1EEEvNS0_7WaveDevENS0_6WaveIOE" % (
-        len(kind), kind, "".join("Li%dE" % v for v in cap))
+_mangled = lambda kind, cap: isa.group_kernel(kind, cap, inject=True)
 
 
 KERNELS = [(SHAPE[kind], cap) for kind in ("HG", "HLG") for cap in REQUIRED[kind]]
@@ -49,13 +32,13 @@ _id = lambda v: v if isinstance(v, str) else "%dv%d" % (v[2], v[3])
 
 # ------------------------------------------------------------------ the list
 def test_committed_half_lines_stand_on_their_fast_lines():
-    half = _lines(DEF)
+    half = isa.def_lines(DEF)
     assert set(half) == {"HG", "HLG"}, sorted(half)
     for kind, shapes in REQUIRED.items():
         for s in shapes:
             assert s in half[kind], (kind, s)
-    fixed = _lines("pursuit_specializations.def").get("XG", [])
-    live = _lines("pursuit_live_specializations.def").get("XLG", [])
+    fixed = isa.def_lines("pursuit_specializations.def", ("XG",))["XG"]
+    live = isa.def_lines("pursuit_live_specializations.def", ("XLG",))["XLG"]
     for s in half["HG"] + half["HLG"]:
         assert s in fixed, s          # (the same NW: the tuple holds it)
     for s in half["HLG"]:
@@ -64,7 +47,7 @@ def test_committed_half_lines_stand_on_their_fast_lines():
     # listing it goes together with that test
     assert not any(s[:6] == (32, 32, 16, 60, 7, 1) for s in half["HG"] + half["HLG"])
     # the two-buffer list keeps its six kinds: the half lines have a file of their own
-    assert not any(k.startswith("H") for k in _lines("pursuit_to_specializations.def"))
+    assert not any(k.startswith("H") for k in isa.def_lines("pursuit_to_specializations.def"))
 
 
 def test_every_includer_defines_both_kinds():
@@ -79,7 +62,7 @@ def test_every_includer_defines_both_kinds():
 # ------------------------------------------------------------------ the built library
 @pytest.fixture(scope="module")
 def lib_kernels():
-    return built._kernels()
+    return isa.built_kernels()
 
 
 @pytest.mark.parametrize("kind,cap", KERNELS, ids=_id)
@@ -101,54 +84,33 @@ def test_the_lines_with_a_float32_two_buffer_kernel_are_compared(lib_kernels):
 
 
 # ------------------------------------------------------------------ emitted code
-def _compile():
-    from madrl_amd import build as B
-    if not os.path.exists(B.HIPCC):
-        pytest.skip("no hipcc")
-    tu = '#include "common.hpp"\n#include "pursuit_group.hpp"\nnamespace madrl { namespace pw {\n'
-    for kind, cap in KERNELS:
-        for k in (kind, IN_PLACE[kind]):
-            tu += "template __global__ void pursuit_group_kernel<%s<%d, %d, %d, %d, %d, %d, %d>, 1, true>(const WaveDev, const WaveIO);\n" % ((k,) + cap)
-    tu += "} }\n"
-    with tempfile.TemporaryDirectory() as tmp:
-        src, out = os.path.join(tmp, "group_to_f16.hip"), os.path.join(tmp, "group_to_f16.s")
-        with open(src, "w") as f:
-            f.write(tu)
-        subprocess.run([B.HIPCC] + [f for f in B.FLAGS if f != "-Wall"] + ["-I", CSRC, "--cuda-device-only", "-S", src, "-o", out],
-                       check=True, capture_output=True)
-        import find_masked_spills
-        masked = find_masked_spills.scan(out, "THGShape") + find_masked_spills.scan(out, "TLHGShape")
-        text = open(out).read()
-    return text, masked
+TU = isa.group_tu([(k, cap) for kind, cap in KERNELS for k in (kind, IN_PLACE[kind])], inject=True)
 
 
 @pytest.fixture(scope="module")
 def asm():
-    return _compile()
+    return isa.compile_asm(TU)
 
 
 @pytest.mark.parametrize("kind,cap", KERNELS, ids=_id)
 def test_half_group_kernel_no_scratch(asm, kind, cap):
-    meta = group_isa._meta(asm[0], _mangled(kind, cap))
-    assert re.search(r"\.private_segment_fixed_size:\s+0\b", meta), meta
-    assert re.search(r"\.vgpr_spill_count:\s+0\b", meta), meta
+    meta = isa.kernel_meta(asm, _mangled(kind, cap))
+    assert meta["private_segment_fixed_size"] == 0 and meta["vgpr_spill_count"] == 0, meta
 
 
 def test_half_group_kernels_have_no_masked_spills(asm):
-    assert asm[1] == []
+    assert isa.masked_spills(asm, "THGShape") + isa.masked_spills(asm, "TLHGShape") == []
 
 
 @pytest.mark.parametrize("kind,cap", KERNELS, ids=_id)
 def test_half_group_kernel_adds_no_barrier_and_moves_whole_8_byte_slots(asm, kind, cap):
-    to = group_isa._body(asm[0], _mangled(kind, cap))
-    ip = group_isa._body(asm[0], _mangled(IN_PLACE[kind], cap))
-    barriers = lambda body: sum(1 for l in body if l.strip().startswith("s_barrier"))
-    assert barriers(to) == barriers(ip) and barriers(ip) > 0, (barriers(to), barriers(ip))
-    inst = [l.strip().split(";")[0].strip() for l in to]
+    inst, ip = isa.kernel_insts(asm, _mangled(kind, cap)), isa.kernel_insts(asm, _mangled(IN_PLACE[kind], cap))
+    barriers = lambda insts: sum(1 for i in insts if i.startswith("s_barrier"))
+    assert barriers(inst) == barriers(ip) and barriers(ip) > 0, (barriers(inst), barriers(ip))
     # a slot is 8 bytes: it is loaded and stored as one word, the two-buffer pass's stores non-temporal; nothing float4-sized is left
     assert any(re.match(r"global_load_dwordx2\s", i) for i in inst)
     assert any(re.match(r"global_store_dwordx2\s", i) and i.endswith(" nt") for i in inst)
-    assert any(re.match(r"global_store_dwordx4\s", i) and i.endswith(" nt") for i in (l.strip().split(";")[0].strip() for l in ip))
+    assert any(re.match(r"global_store_dwordx4\s", i) and i.endswith(" nt") for i in ip)
     assert not any(re.match(r"global_store_dwordx4\s", i) for i in inst), "a float4 store in a kernel over binary16 buffers"
 
 

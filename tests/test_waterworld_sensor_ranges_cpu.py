@@ -17,8 +17,8 @@ TOL = 1e-12   # the float64 oracle against the reference: the tolerance tests/te
 
 
 def test_built_library_has_the_ranged_kernels_without_a_private_segment():
-    from test_kernel_metadata import _kernels
-    ks = _kernels()
+    from isa import built_kernels
+    ks = built_kernels()
     for family in ("waterworld_kernel_ranges", "ww_crowd_kernel_ranges"):
         ranged = {n: k for n, k in ks.items() if family in n}
         assert len(ranged) >= 2 and any("rangesILi0E" in n for n in ranged) and any("rangesILi1E" in n for n in ranged), (family, sorted(ranged))   # reset and step

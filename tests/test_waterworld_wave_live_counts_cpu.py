@@ -8,8 +8,8 @@ import pytest
 
 
 def test_built_library_has_the_one_wavefront_live_kernels():
-    from test_kernel_metadata import _kernels
-    ks = _kernels()
+    from isa import built_kernels
+    ks = built_kernels()
     live = {n: k for n, k in ks.items() if "waterworld_kernel_live" in n}
     assert len(live) == 2 and any("liveILi0E" in n for n in live) and any("liveILi1E" in n for n in live), sorted(live)   # reset and step
     for n, k in live.items():
