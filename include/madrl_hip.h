@@ -137,6 +137,31 @@ int madrl_pursuit_set_launch(madrl_pursuit *h, int32_t threads, int64_t max_bloc
  * the memory-side cache), 1 = always alternate, 2 = always forward.  Results do not depend on it. */
 int madrl_pursuit_set_walk(madrl_pursuit *h, int32_t mode);
 
+/* The one-wavefront shapes listed in madrl_amd/csrc/pursuit_fixed_specializations.def have a second step kernel with the launch constants
+ * compiled in.  A madrl_pursuit_step takes it, launch by launch, when all of this holds: surround catch, local reward, control_evaders 0,
+ * n_maps 1 without sample_maps, max_opponents 0, no per-env agent counts, no per-env curriculum arrays, no injected evader actions,
+ * a walk that does not alternate.  Every other launch -- resets, step_to, step_to_f16 -- runs on the shape's plain kernel; the two share
+ * the record and what is known about the observation buffer, and compute the same values.  MADRL_PURSUIT_FIXED=0 in the environment
+ * keeps the handles created while it is set on the plain kernel.
+ * madrl_pursuit_last_step_entry: which kernel the handle's last step launch (step, step_to, step_to_f16, step_sharded) ran on.
+ * madrl_pursuit_fixed_choice: 1 / 0, whether a launch described by launch_bits of a handle of this configuration and batch size takes
+ * the fixed-constants kernel; host only, no device is touched. */
+#define MADRL_STEP_ENTRY_NONE 0      /* no step launch yet */
+#define MADRL_STEP_ENTRY_GENERIC 1
+#define MADRL_STEP_ENTRY_WAVE 2      /* the plain fast kernel of the line */
+#define MADRL_STEP_ENTRY_FIXED 3     /* its fixed-constants kernel */
+int madrl_pursuit_last_step_entry(const madrl_pursuit *h, int32_t *out);
+#define MADRL_LAUNCH_PER_ENV_COUNTS 1u      /* madrl_pursuit_set_agent_counts is in force */
+#define MADRL_LAUNCH_CURRICULUM_ARRAYS 2u   /* per-env constraint_window / catchr arrays are bound */
+#define MADRL_LAUNCH_INJECTED_ACTIONS 4u    /* inj_evader_actions_dev != NULL */
+#define MADRL_LAUNCH_WALK_ALTERNATE 8u      /* madrl_pursuit_set_walk(h, 1) */
+#define MADRL_LAUNCH_WALK_FORWARD 16u       /* madrl_pursuit_set_walk(h, 2); neither: automatic */
+#define MADRL_LAUNCH_STEP_TO 32u            /* madrl_pursuit_step_to */
+#define MADRL_LAUNCH_HALF 64u               /* madrl_pursuit_step_to_f16 */
+#define MADRL_LAUNCH_RESET 128u             /* madrl_pursuit_reset */
+#define MADRL_LAUNCH_KERNEL_GENERIC 256u    /* madrl_pursuit_set_kernel(h, MADRL_KERNEL_GENERIC) */
+int madrl_pursuit_fixed_choice(const madrl_pursuit_config *cfg, int64_t n_envs, uint32_t launch_bits, int32_t *out);
+
 /* Replaces PursuitEvade.reset (pursuit_evade.py:173-207) for every env with mask[n] != 0
  * (mask_dev NULL = all).
  *   inj_pos_dev  int32 [n_envs][P+E][2] or NULL: positions used instead of the rejection

@@ -160,6 +160,8 @@ SIGNATURES = {
     "madrl_rollout_gae": (C.c_int, [_vp] * 3 + [C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double] + [_vp] * 3),
     "madrl_pursuit_step_to_f16": (C.c_int, [_vp] * 9),
     "madrl_pursuit_step_to_f16_kernel_kind": (C.c_int, [_vp, _vp]),
+    "madrl_pursuit_last_step_entry": (C.c_int, [_vp, _vp]),
+    "madrl_pursuit_fixed_choice": (C.c_int, [_vp, C.c_int64, C.c_uint32, _vp]),
 }
 
 

@@ -266,6 +266,7 @@ __global__ void pursuit_live_counts_kernel(const PursuitDev d, int32_t *pos_p, i
 // =================================================================== host side / C ABI
 namespace {
 struct FastEntry;  // one compiled specialisation: a line of the *_specializations.def lists (below)
+struct FixedEntry;
 }
 
 struct madrl_pursuit {
@@ -282,6 +283,9 @@ struct madrl_pursuit {
     // (pursuit_crowd.hpp: cdev; it shares the generic kernel's tables)
     const FastEntry *fast = nullptr;
     const FastEntry *fast_live = nullptr;  // the live-count instantiation of `fast` (pursuit_live_specializations.def), if compiled
+    const FixedEntry *fixed = nullptr;     // the fixed-constants step kernel of `fast` (pursuit_fixed_specializations.def), if compiled and not
+                                           // switched off (MADRL_PURSUIT_FIXED=0 at create); taken launch by launch (fixed_contract)
+    int last_step_entry = MADRL_STEP_ENTRY_NONE;   // which kernel the last step launch ran on (madrl_pursuit_last_step_entry)
     madrl::pw::WaveDev wdev{};
     madrl::pc::CrowdDev cdev{};
     void *zmask = nullptr;          // what the fast path remembers about the observation buffer (zmask_len): the stale-zero masks,
@@ -414,6 +418,60 @@ constexpr FastEntry LIVE_TABLE[] = {
 #undef XL
 #undef XLG
 #undef XLC
+
+// The step kernels with their launch constants folded in (pw::FShape, pursuit_fixed.hip): reached through the X line of the same shape,
+// launch by launch, when the launch meets the FShape contract (fixed_contract below); the masks and the record are the X line's.
+using WaveFixedLaunch = void (*)(const pw::WaveDev &, const pw::WaveIO &, int64_t blocks, hipStream_t s);
+struct FixedEntry {
+    ShapeKey key;
+    WaveFixedLaunch launch;
+};
+#define XF(XS, YS, NP, NE, R, FL) FixedEntry{{XS, YS, NP, NE, R, FL}, pw::wave_fixed_launch<pw::FShape<XS, YS, NP, NE, R, FL>>},
+constexpr FixedEntry FIXED_TABLE[] = {
+#include "pursuit_fixed_specializations.def"
+#if __has_include("pursuit_fixed_specializations.local.def")
+#include "pursuit_fixed_specializations.local.def"
+#endif
+};
+#undef XF
+constexpr bool fixed_lines_have_their_lines() {
+    for (const FixedEntry &x : FIXED_TABLE) {
+        bool found = false;
+        for (const FastEntry &f : FAST_TABLE) found = found || (f.key == x.key && !f.crowd() && f.g.nw == 1);
+        if (!found) return false;
+    }
+    return true;
+}
+static_assert(fixed_lines_have_their_lines(), "an XF line of pursuit_fixed_specializations.def needs the X line of its shape in pursuit_specializations.def");
+
+// the fixed-constants entry of the one-wavefront line `f`, or nullptr
+const FixedEntry *find_fixed(const FastEntry *f) {
+    for (const FixedEntry &x : FIXED_TABLE)
+        if (f && !f->crowd() && f->g.nw == 1 && f->key == x.key) return &x;
+    return nullptr;
+}
+// MADRL_PURSUIT_FIXED=0 in the environment keeps every handle created from then on off the fixed-constants kernels (A/B runs, twin tests)
+bool fixed_enabled() {
+    const char *v = getenv("MADRL_PURSUIT_FIXED");
+    return !(v && v[0] == '0' && v[1] == 0);
+}
+// What of a launch decides between the two kernels of a line, and the FShape contract (pursuit_wave.hpp) over it and the handle's
+// constants: pure, so that madrl_pursuit_fixed_choice answers without a device exactly what launch() does.
+struct LaunchAsk {
+    bool step;        // mode 1 (resets run on the plain kernel)
+    bool two_buffer;  // step_to / step_to_f16
+    bool pending;     // per-env agent counts
+    bool inj_eact;    // injected evader actions
+    bool alternate;   // the walk alternates its direction (set_walk, or automatic above the threshold)
+};
+bool walk_alternates(const PursuitDev &d, int walk_mode) {
+    if (walk_mode != 0) return walk_mode == 1;
+    return (double)d.n_envs * (4.0 * d.P * d.D + 2.0 * d.rec_bytes) > 375e6;
+}
+bool fixed_contract(const PursuitDev &d, const LaunchAsk &a) {
+    return a.step && !a.two_buffer && !a.pending && !a.inj_eact && !a.alternate && d.surround && !d.reward_global && d.train_pursuit &&
+           d.n_maps == 1 && !d.sample_maps && d.max_opponents == 0 && d.cw_env == nullptr && d.catchr_env == nullptr;
+}
 
 // The two-buffer step kernels (madrl_pursuit_step_to, pursuit_to.hip and pursuit_to_group.hip): reached through the fixed line of the same shape and NW, for a handle
 // with per-env agent counts through its live line.  A handle without an entry here runs step_to on the generic kernel.
@@ -641,6 +699,7 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, const float *obs_pre
             MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0xFF, zmask_len(h->fast, h->dev.n_envs), s));
         h->zmask_obs = io.obs;
         h->zmask_fmt = fmt;
+        if (mode == 1) h->last_step_entry = MADRL_STEP_ENTRY_WAVE;
         if (f->crowd()) {
             const pc::CrowdDev cd = dev_now(h->cdev, h->dev);
             if (t) t->launch_crowd(cd, io_of<pc::CrowdIO>(io), h->pending, obs_prev, blocks, s);
@@ -656,18 +715,20 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, const float *obs_pre
             // (98 304: 4.7e8, 131 072: 4.5e8); alternating holds 6.4-6.7e8 from 81 920 to 131 072 but costs 6 % below.  Hence
             // the switch at ~375 MB of rows + records per launch.  Env results do not depend on the processing order.
             pw::WaveDev wd = dev_now(h->wdev, h->dev);
-            if (mode == 1) {
-                bool alternate = (double)h->dev.n_envs * (4.0 * h->dev.P * h->dev.D + 2.0 * h->dev.rec_bytes) > 375e6;
-                if (h->walk_mode != 0) alternate = h->walk_mode == 1;
-                if (alternate) wd.reverse = (int32_t)(h->step_count++ & 1);
-            }
+            const bool alternate = mode == 1 && walk_alternates(h->dev, h->walk_mode);
+            if (alternate) wd.reverse = (int32_t)(h->step_count++ & 1);
             wd.pending = h->pending;
+            // the fixed-constants kernel of the line, when this launch meets its contract (the same masks and record: interchangeable)
+            const bool fixed = h->fixed && fixed_contract(h->dev, LaunchAsk{mode == 1, obs_prev != nullptr, h->pending != nullptr, io.inj_eact != nullptr, alternate});
+            if (fixed) h->last_step_entry = MADRL_STEP_ENTRY_FIXED;
             if (t) (fmt == OBS_F16 ? t->launch_wave_f16 : t->launch_wave)(wd, w, blocks, s);
+            else if (fixed) h->fixed->launch(wd, w, blocks, s);
             else f->launch_wave(wd, w, mode, blocks, s);
         }
         MADRL_HIP_TRY(hipGetLastError());
         return MADRL_OK;
     }
+    if (mode == 1) h->last_step_entry = MADRL_STEP_ENTRY_GENERIC;
     h->zmask_obs = nullptr;  // the generic kernel does not maintain the fast path's stale-zero masks
     int64_t blocks = h->dev.n_envs;
     if (h->max_blocks > 0 && blocks > h->max_blocks) blocks = h->max_blocks;
@@ -829,6 +890,7 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
         h->fast = nullptr;
     }
     h->fast_live = find_live(h->fast);
+    h->fixed = fixed_enabled() ? find_fixed(h->fast) : nullptr;
 
     rc = madrl_pursuit_set_launch(h.get(), 0, 0);
     if (rc) return rc;
@@ -837,6 +899,30 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
         hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess)
         return fail(MADRL_EHIP, "create: hipEventCreateWithFlags failed");
     *out = h.release();
+    return MADRL_OK;
+}
+
+int madrl_pursuit_last_step_entry(const madrl_pursuit *h, int32_t *out) {
+    if (!h || !out) return fail(MADRL_EINVAL, "last_step_entry: NULL argument");
+    *out = h->last_step_entry;
+    return MADRL_OK;
+}
+
+int madrl_pursuit_fixed_choice(const madrl_pursuit_config *cfg, int64_t n_envs, uint32_t launch_bits, int32_t *out) {
+    if (!out) return fail(MADRL_EINVAL, "fixed_choice: out is NULL");
+    const int rc = validate(cfg);
+    if (rc) return rc;
+    if (n_envs < 1 || launch_bits >= 2u * MADRL_LAUNCH_KERNEL_GENERIC) return fail(MADRL_EINVAL, "fixed_choice: n_envs < 1 or unknown launch bits");
+    PursuitDev d;
+    layout(cfg, &d);
+    d.n_envs = n_envs;
+    static const double some = 0.0;   // (per-env curriculum arrays: bound or not is all the contract asks)
+    if (launch_bits & MADRL_LAUNCH_CURRICULUM_ARRAYS) d.cw_env = d.catchr_env = &some;
+    const int walk = (launch_bits & MADRL_LAUNCH_WALK_ALTERNATE) ? 1 : (launch_bits & MADRL_LAUNCH_WALK_FORWARD) ? 2 : 0;
+    const LaunchAsk a{!(launch_bits & MADRL_LAUNCH_RESET), (launch_bits & (MADRL_LAUNCH_STEP_TO | MADRL_LAUNCH_HALF)) != 0,
+                      (launch_bits & MADRL_LAUNCH_PER_ENV_COUNTS) != 0, (launch_bits & MADRL_LAUNCH_INJECTED_ACTIONS) != 0, walk_alternates(d, walk)};
+    const bool fixed = !(launch_bits & MADRL_LAUNCH_KERNEL_GENERIC) && fixed_enabled() && find_fixed(find_fast(cfg)) && fixed_contract(d, a);
+    *out = fixed ? 1 : 0;
     return MADRL_OK;
 }
 

@@ -98,6 +98,20 @@ struct KArgs {
     WaveDev d;
     WaveIO io;
 };
+// The launch flags of WaveDev as the env loop reads them: the launch's values, or for an S::FIXED shape the constants of its contract
+// (FShape) -- the branches on them, the code behind the untaken sides and the SGPRs that held the flags leave that kernel.
+// MADRL_PW_FOLD=1 (a profiling aid like MADRL_ABLATE, scripts/variants.sh: never the shipped library) folds these three flags in EVERY
+// kernel of this file: the cheapest stand-in for the FShape kernel in the benchmarked form (profiles/r23_fixed/pricing.txt).
+#ifndef MADRL_PW_FOLD
+#define MADRL_PW_FOLD 0
+#endif
+template <class S>
+struct Launch {
+    static constexpr bool FOLD = S::FIXED || MADRL_PW_FOLD;
+    static __device__ __forceinline__ bool surround(const WaveDev &d) { if constexpr (FOLD) return true; else return d.surround; }
+    static __device__ __forceinline__ bool reward_global(const WaveDev &d) { if constexpr (FOLD) return false; else return d.reward_global; }
+    static __device__ __forceinline__ bool reverse(const WaveDev &d) { if constexpr (FOLD) return false; else return d.reverse; }
+};
 typedef const __attribute__((address_space(4))) KArgs *KArgsPtr;
 __device__ __forceinline__ KArgsPtr cold_args() { return kernargs<KArgs>(); }
 // pending count k (0 pursuers, 1 evaders) of an env (LShape kernels, resets only): a scalar load, like sload_f64
@@ -153,6 +167,7 @@ struct Shape {
     static constexpr bool LEAN_REGS = false;                     // loop constants worked out again at their uses (see THShape)
     static constexpr bool TABLED = false;                       // (pursuit_group.hpp: slot constants from an LDS table; never here)
     static constexpr int X_TAB = 0;
+    static constexpr bool FIXED = false;                         // (FShape: the launch flags are compile-time constants)
 };
 
 // Per-env agent counts (madrl_pursuit_set_agent_counts): the same geometry, with P and E as a CAPACITY.  An env runs LIVE p <= P
@@ -164,6 +179,20 @@ struct LShape : Shape<XS_, YS_, P_, E_, R_, FLATTEN_> {
     static constexpr bool LIVE = true;
 };
 constexpr int NOT_HERE = 0xFF;   // position byte of a slot that does not exist (live-count records)
+
+// The step kernel specialised on its LAUNCH CONSTANTS as well: the same geometry, and every launch flag the env loop of the plain kernel
+// tests per env is a constant of the shape (the accessors of `Launch` above).  The contract -- launch() in pursuit.hip takes this
+// kernel only for a step launch that meets all of it, and the plain kernel of the same shape otherwise; both share record and masks,
+// so they are interchangeable launch by launch:
+//   surround catch, local reward, train_pursuit (no evader control), ONE map and no sample_maps (map_id is 0: the map staged with the
+//   tables is the map of every env, load_map leaves the loop), forward walk, no per-env curriculum arrays (catchr_env == cw_env ==
+//   nullptr), max_opponents == 0, no pending counts, no injected evader actions, in place, float32.
+// max_steps, auto_reset, catchr, cw, urgency, term_pursuit and n_catch stay run-time values.  Only <FShape, 1, false, false> is
+// instantiated (pursuit_fixed.hip, the XF lines of pursuit_fixed_specializations.def); resets run on the plain kernel.
+template <int XS_, int YS_, int P_, int E_, int R_, int FLATTEN_>
+struct FShape : Shape<XS_, YS_, P_, E_, R_, FLATTEN_> {
+    static constexpr bool FIXED = true;
+};
 
 // The two-buffer step (madrl_pursuit_step_to): the step's observation pass stores every valid float4 of the env's rows to io.obs, whole
 // and non-temporal; the cells the in-place pass leaves alone come from the same place of io.obs_prev -- loaded only in the slots whose
@@ -511,6 +540,8 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
     static_assert(!S::TO || (MODE == 1 && INJECT && !CTRL), "the two-buffer step: the flexible step kernel only");
     static_assert(!S::H16 || S::TO, "binary16 buffers: the two-buffer step only");
     static_assert(!S::ZSKIP || (S::ZM16 && !S::TO && !S::H16), "zeros over known zeros: the in-place float32 pass of a 16-bit-mask shape only");
+    static_assert(!S::FIXED || (MODE == 1 && !INJECT && !CTRL && !S::LIVE && !S::TO), "launch constants folded in: the plain in-place step kernel only");
+    using LC = Launch<S>;
     constexpr int P = S::P, E = S::E, A = S::A, GW = S::GW, PAD = S::PAD, GSZ = S::GSZ, NS = S::NS;
     __shared__ __attribute__((aligned(16))) uint32_t L[S::LDS_DWORDS];
     const int lane = threadIdx.x;
@@ -529,9 +560,16 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
     // thing.  With a map pool the first env may reload (load_map below).  (Shapes whose tables do not fit FILL_FIRST registers
     // beside their slot constants stage the rest in further batches.)
     using F = Fill<S, 64>;
-    const int n_envs = (int)d.n_envs, stride = (int)gridDim.x;  // env indices are 32-bit (the C ABI caps n_envs below 2^31); only byte offsets are 64-bit
+    const int n_envs = (int)d.n_envs;  // env indices are 32-bit (the C ABI caps n_envs below 2^31); only byte offsets are 64-bit
+    int stride = (int)gridDim.x;
+    // (FIXED: a value made here, held in an SGPR the flags left -- as a plain kernel argument the plain kernel loads it again at the top
+    // of every env iteration and waits for it before it can form the next env's prefetch addresses)
+    if constexpr (S::FIXED) asm volatile("" : "+s"(stride));
+    uint64_t urgency_bits = __builtin_bit_cast(uint64_t, d.urgency);   // (FIXED: likewise -- the plain kernel loads it in every env's reward block)
+    if constexpr (S::FIXED) asm volatile("" : "+s"(urgency_bits));
+    const double urgency = __builtin_bit_cast(double, urgency_bits);
     if (n_envs <= 0) return;
-    auto phys = [&](int e) -> int64_t { return (int64_t)(d.reverse ? n_envs - 1 - e : e); };
+    auto phys = [&](int e) -> int64_t { return (int64_t)(LC::reverse(d) ? n_envs - 1 - e : e); };
     // the env whose mask words an env reads and writes: its own
     auto zm_env = [](int64_t env) -> int64_t { return (MADRL_ABLATE & (256 | 512)) ? (env & 255) : env; };
     // the dword of an env's masks a lane loads: its own -- or, 16 bits per lane, the one it shares with lane +- 32
@@ -640,7 +678,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
             // -------------------------------------------------------- unpack the record
             uint32_t tick = __builtin_amdgcn_readlane(cur_rec, 0);
             int32_t tstep = (int32_t)__builtin_amdgcn_readlane(cur_rec, 1);
-            int32_t map_id = (int32_t)__builtin_amdgcn_readlane(cur_rec, 2);
+            int32_t map_id = S::FIXED ? 0 : (int32_t)__builtin_amdgcn_readlane(cur_rec, 2);   // (FIXED: one map)
             const uint32_t xyw = (uint32_t)__shfl((int)cur_rec, 4 + (lane >> 1));
             const pr::Cell at = pr::unpack_xy(xyw, lane & 1);
             int x = at.x, y = at.y;
@@ -649,7 +687,9 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
             uint64_t term = (uint32_t)__builtin_amdgcn_readlane(cur_rec, S::OFF_TERM / 4);
             if constexpr (S::NTW > 1) term |= (uint64_t)(uint32_t)__builtin_amdgcn_readlane(cur_rec, S::OFF_TERM / 4 + 1) << 32;
             const uint32_t gid = d.gid_base + (uint32_t)env;
-            const uint32_t k0 = fresh_s(d.k0), k1 = fresh_s(d.k1);  // round keys recomputed on the SALU, not kept live
+            // round keys recomputed on the SALU, not kept live (FIXED too: holding the twenty keys takes more SGPRs than the flags left -- 8
+            // scalars parked in VGPR lanes and read back in the evader draw; holding k0's ten alone: 2)
+            const uint32_t k0 = fresh_s(d.k0), k1 = fresh_s(d.k1);
             int np = P, ne = E;  // live pursuers / evader slots (LIVE; the capacity otherwise)
             if constexpr (S::LIVE) {
                 const bool here = x != NOT_HERE;
@@ -682,7 +722,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                 cached_map = mid;
                 wave_sync();
             };
-            load_map(map_id);
+            if constexpr (!S::FIXED) load_map(map_id);
 
             if constexpr (MODE == 1) {
                 const bool e_alive = alive && !isP();
@@ -741,7 +781,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                 bool caught = false;
                 if (e_alive) {
                     const uint32_t *pc = &L[GSZ];
-                    if (d.surround) caught = pr::cells_with_pursuers(pc[cell - GW], pc[cell + GW], pc[cell + 1], pc[cell - 1], SENT) == (int)need_tab[x * S::YS + y];  // :523-540
+                    if (LC::surround(d)) caught = pr::cells_with_pursuers(pc[cell - GW], pc[cell + GW], pc[cell + 1], pc[cell - 1], SENT) == (int)need_tab[x * S::YS + y];  // :523-540
                     else caught = (int)pc[cell] >= d.n_catch;  // :498
                     if (caught) atomicAdd(&layer[cell], CAUGHT);
                 }
@@ -753,13 +793,13 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                 if (isLP()) {
                     const uint32_t *ec = &L[2 * GSZ];
                     bool sur;
-                    if (d.surround) sur = pr::caught_beside(ec[cell - GW], ec[cell + GW], ec[cell + 1], ec[cell - 1], SENT, CAUGHT);
+                    if (LC::surround(d)) sur = pr::caught_beside(ec[cell - GW], ec[cell + GW], ec[cell + 1], ec[cell - 1], SENT, CAUGHT);
                     else sur = ec[cell] >= CAUGHT;  // :503-506
                     double catchr = d.catchr;
                     if constexpr (INJECT) { if (d.catchr_env != nullptr) catchr = sload_f64(d.catchr_env, env); }
-                    r = pr::pursuer_reward(catchr, kpre, d.term_pursuit, sur, d.urgency);
+                    r = pr::pursuer_reward(catchr, kpre, d.term_pursuit, sur, urgency);
                 }
-                if (d.reward_global) {  // [rewards.mean()] * n_pursuers, numpy summation order
+                if (LC::reward_global(d)) {  // [rewards.mean()] * n_pursuers, numpy summation order
                     double all[P];
 #pragma unroll
                     for (int k = 0; k < P; ++k) {
@@ -809,8 +849,14 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                     gone = 0ull;
                     term = 0ull;
                     const KArgsPtr ka = cold_args();
-                    const double cw = ka->d.cw_env != nullptr ? sload_f64(ka->d.cw_env, env) : ka->d.cw;
-                    const int max_opponents = ka->d.max_opponents;
+                    double cw;
+                    if constexpr (S::FIXED) cw = ka->d.cw;
+                    else cw = ka->d.cw_env != nullptr ? sload_f64(ka->d.cw_env, env) : ka->d.cw;
+                    const int max_opponents = S::FIXED ? 0 : ka->d.max_opponents;
+                    // (FIXED: the draws below see their inputs as values made HERE, so that their lane-uniform first Philox rounds cannot
+                    // be hoisted out of the branch into every env's straight-line code -- 1 env in 500 resets)
+                    uint32_t rgid = gid, rk0 = k0, rk1 = k1;
+                    if constexpr (S::FIXED) asm volatile("" : "+s"(rgid), "+s"(tick), "+s"(rk0), "+s"(rk1));
                     bool inj_map = false, inj_pos = false;
                     if constexpr (MODE == 0) {
                         inj_map = io.inj_map != nullptr;
@@ -818,18 +864,18 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                     }
                     if (inj_map) {
                         map_id = __builtin_amdgcn_readfirstlane(io.inj_map[env]);
-                    } else if (ka->d.sample_maps) {  // :182-183
-                        const u32x4 rm = philox4x32_10(gid, tick, 0u, TAG_RESET_ENV, k0, k1);
+                    } else if (!S::FIXED && ka->d.sample_maps) {  // :182-183
+                        const u32x4 rm = philox4x32_10(rgid, tick, 0u, TAG_RESET_ENV, rk0, rk1);
                         map_id = (int)__umulhi(rm.x, (uint32_t)ka->d.n_maps);
                     }
-                    load_map(map_id);
-                    const pr::Window win = pr::reset_window(gid, tick, k0, k1, cw, S::XS, S::YS);
+                    if constexpr (!S::FIXED) load_map(map_id);
+                    const pr::Window win = pr::reset_window(rgid, tick, rk0, rk1, cw, S::XS, S::YS);
                     int n_create = E;   // (an injected position with x < 0 marks an evader slot that is not created)
                     if constexpr (S::LIVE) {  // the pending counts take effect
                         const pr::Counts live = pr::clamp_pending(pending_count(env, 0), pending_count(env, 1), P, E);
                         np = live.np, ne = n_create = live.ne;
                     }
-                    if (max_opponents > 0 && !inj_pos) n_create = pr::reset_n_create(gid, tick, k0, k1, max_opponents, S::LIVE ? ne : E);
+                    if (max_opponents > 0 && !inj_pos) n_create = pr::reset_n_create(rgid, tick, rk0, rk1, max_opponents, S::LIVE ? ne : E);
                     bool exists = false;
                     if (isAgent()) {  // create_agents / feasible_position, agent_utils.py:12-47
                         if constexpr (S::LIVE) exists = isLP() || (!isP() && eslot < n_create);
@@ -841,7 +887,7 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                         } else {
                             for (uint32_t att = 0; att < 1024u; ++att) {
                                 const uint32_t aidx = S::LIVE ? (uint32_t)(isP() ? lane : np + eslot) : (uint32_t)lane;
-                                const u32x4 rp = philox4x32_10(gid, tick, aidx, TAG_RESET_POS | (att << 8), k0, k1);
+                                const u32x4 rp = philox4x32_10(rgid, tick, aidx, TAG_RESET_POS | (att << 8), rk0, rk1);
                                 x = win.xlb + (int)__umulhi(rp.x, (uint32_t)(win.xub - win.xlb));   // (pr::reset_cell's text: the helper
                                 y = win.ylb + (int)__umulhi(rp.y, (uint32_t)(win.yub - win.ylb));   // changes the headline step kernel)
                                 // building cells hold fl32(1/norm) != 0; window cells are inside the map
@@ -1134,7 +1180,8 @@ __global__ __launch_bounds__(64) MADRL_PW_OCC void pursuit_wave_kernel(const Wav
                 if (fresh(lane) == 0) {
                     io.done[env] = (uint8_t)done_bits;
                     io.removed[env] = n_removed;
-                    cold_args()->d.flags[env] = done_flag_word(done_bits);   // (the pointer is not kept in SGPRs across the env loop)
+                    if constexpr (S::FIXED) d.flags[env] = done_flag_word(done_bits);
+                    else cold_args()->d.flags[env] = done_flag_word(done_bits);   // (the pointer is not kept in SGPRs across the env loop)
                 }
             }
             // ---------------------------------------------------------- registers -> state record
@@ -1201,6 +1248,10 @@ void wave_to_launch(const WaveDev &d, const WaveIO &io, int64_t blocks, hipStrea
 // ... and of a THShape / TLHShape: binary16 buffers, io.obs and io.obs_prev are the half pointers, cast (pursuit_to_f16.hip, pursuit_to_f16_live.hip)
 template <class S>
 void wave_to_f16_launch(const WaveDev &d, const WaveIO &io, int64_t blocks, hipStream_t s);
+// ... and the fixed-constants step kernel <S, 1, false> of an FShape (defined and instantiated for every XF line of
+// pursuit_fixed_specializations.def in pursuit_fixed.hip)
+template <class S>
+void wave_fixed_launch(const WaveDev &d, const WaveIO &io, int64_t blocks, hipStream_t s);
 
 }  // namespace pw
 }  // namespace madrl

@@ -260,6 +260,15 @@ class BatchedPursuitEvade(AbstractMAEnv):
         _lib.check(_lib.lib().madrl_pursuit_kernel_kind(self._handle, C.byref(out)))
         return {_lib.KERNEL_GENERIC: "generic", _lib.KERNEL_WAVE: "wave"}[out.value]
 
+    @property
+    def last_step_entry(self):
+        """'none' | 'generic' | 'wave' | 'fixed': the kernel the last step launch ran on -- 'fixed' is the one-wavefront kernel with its
+        launch constants compiled in (csrc/pursuit_fixed_specializations.def), taken launch by launch when the launch meets its contract
+        (include/madrl_hip.h, madrl_pursuit_last_step_entry); MADRL_PURSUIT_FIXED=0 in the environment at creation keeps a handle off it"""
+        out = C.c_int32()
+        _lib.check(_lib.lib().madrl_pursuit_last_step_entry(self._handle, C.byref(out)))
+        return ("none", "generic", "wave", "fixed")[out.value]
+
     def set_walk(self, mode):
         """'auto' | 'alternate' | 'forward': the order in which successive launches of the fast path walk the env range (a
         memory-side cache matter for large batches; results do not depend on it)"""
