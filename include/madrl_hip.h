@@ -663,6 +663,14 @@ int madrl_rollout_gae(const float *rew, const uint8_t *done, const float *values
 int madrl_heuristic_pursuit(const float *obs, int64_t n_rows, int32_t obs_range, int64_t row_stride, int32_t cell_stride,
                             int32_t ch_offset, const uint8_t *table_dev, uint64_t seed, int64_t row_id_base,
                             uint32_t tick, uint32_t *tick_dev, int32_t *actions, void *stream);
+/* The same over binary16 observation rows (madrl_pursuit_step_to_f16, BatchedPursuitEvade(obs_dtype=torch.float16)): obs_f16
+ * points at 2-byte elements, and row_stride, cell_stride and ch_offset count such elements.  A cell holds an evader iff its
+ * 16 bits are not +-0 ((bits & 0x7FFF) != 0: -0.0 is empty, a subnormal and NaN are evaders), which is what v != 0.0f says
+ * of the widened value: the actions are those madrl_heuristic_pursuit gives on the rows converted to float32, the drawn
+ * ones included.  Rows need 2-byte alignment only.  Same arguments otherwise, same counter words, same checks. */
+int madrl_heuristic_pursuit_f16(const void *obs_f16, int64_t n_rows, int32_t obs_range, int64_t row_stride, int32_t cell_stride,
+                                int32_t ch_offset, const uint8_t *table_dev, uint64_t seed, int64_t row_id_base,
+                                uint32_t tick, uint32_t *tick_dev, int32_t *actions, void *stream);
 /* WaterworldHeuristicPolicy.sample_actions, every row normalised on its own; cos_sin_dev float64 [K][2] with
  * K = obs_dim / 7 (np.linspace(0, 2 pi, K + 1)[:-1]); actions float32 [n_rows][2] */
 int madrl_heuristic_waterworld(const float *obs, int64_t n_rows, int32_t obs_dim, const double *cos_sin_dev,

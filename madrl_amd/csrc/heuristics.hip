@@ -69,6 +69,17 @@ __device__ __forceinline__ void policy_retire(uint32_t *tick_dev) {
     }
 }
 
+// "this cell holds an evader".  float32: v != 0.0f.  binary16 rows (BatchedPursuitEvade(obs_dtype=torch.float16)) are read as their 16 bits and
+// never converted: not +-0 says what v != 0.0f says of the widened value -- -0.0 is empty, the smallest subnormal and NaN are evaders
+__device__ __forceinline__ bool occupied(float v) { return v != 0.0f; }
+__device__ __forceinline__ bool occupied(uint16_t h) { return (h & 0x7FFFu) != 0u; }
+
+// the packed key of window cell k: (distance^2 from the centre cell << 16) | k -- the minimum is the nearest evader, the first in row-major order among equals
+__device__ __forceinline__ uint32_t cell_key(int k, int R, int c) {
+    const int i = k / R, j = k - i * R;
+    return ((uint32_t)((i - c) * (i - c) + (j - c) * (j - c)) << 16) | (uint32_t)k;
+}
+
 __global__ __launch_bounds__(256) void pursuit_policy_kernel(const float *__restrict__ obs, int64_t n_rows, int R, int64_t row_stride,
                                                              int cell_stride, int ch_offset, const uint8_t *__restrict__ table,
                                                              uint32_t k0, uint32_t k1, int64_t row_id_base, uint32_t tick,
@@ -86,11 +97,35 @@ __global__ __launch_bounds__(256) void pursuit_policy_kernel(const float *__rest
             for (int q = 0; q < 4; ++q) v[q] = kb + 16 * q < cells ? o[(int64_t)(kb + 16 * q) * cell_stride] : 0.0f;
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                if (v[q] != 0.0f) {
-                    const int k = kb + 16 * q, i = k / R, j = k - i * R;
-                    const uint32_t d2 = (uint32_t)((i - c) * (i - c) + (j - c) * (j - c));
-                    key = min(key, (d2 << 16) | (uint32_t)k);
-                }
+                if (occupied(v[q])) key = min(key, cell_key(kb + 16 * q, R, c));
+        }
+        key = min_row16(key);
+        if (sub == 0) policy_emit(key, row, table, k0, k1, row_id_base, tk, actions);
+    }
+    policy_retire(tick_dev);
+}
+
+// The same over binary16 rows (four 2-byte loads per lane in flight); strides and offsets count 2-byte elements.  A kernel of its own beside
+// the float32 one, not one body for both: with the float32 loop moved into a shared function template the float32 kernel's registers and
+// instruction order changed, and that kernel's emitted code is pinned.  What decides an action is shared: occupied, cell_key, min_row16, policy_*.
+__global__ __launch_bounds__(256) void pursuit_policy_f16_kernel(const uint16_t *__restrict__ obs, int64_t n_rows, int R, int64_t row_stride,
+                                                                 int cell_stride, int ch_offset, const uint8_t *__restrict__ table,
+                                                                 uint32_t k0, uint32_t k1, int64_t row_id_base, uint32_t tick,
+                                                                 uint32_t *tick_dev, int32_t *__restrict__ actions) {
+    const int sub = threadIdx.x & 15;
+    const int c = R / 2;
+    const int cells = R * R;
+    const uint32_t tk = policy_tick(tick, tick_dev);
+    for (int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); row < n_rows; row += (int64_t)gridDim.x * 16) {
+        uint32_t key = 0xFFFFFFFFu;
+        const uint16_t *o = obs + row * row_stride + ch_offset;
+        for (int kb = sub; kb < cells; kb += 64) {
+            uint16_t v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = kb + 16 * q < cells ? o[(int64_t)(kb + 16 * q) * cell_stride] : (uint16_t)0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (occupied(v[q])) key = min(key, cell_key(kb + 16 * q, R, c));
         }
         key = min_row16(key);
         if (sub == 0) policy_emit(key, row, table, k0, k1, row_id_base, tk, actions);
@@ -105,6 +140,11 @@ __global__ __launch_bounds__(256) void pursuit_policy_kernel(const float *__rest
 // with U = 2, 4, 8 and 4 or 8 blocks per CU alike (38.4 only with U = 2 and 4 blocks) -- not latency: the rows' 196 useful bytes at a
 // 592-byte stride touch 168 MB of 128-byte lines (PMC FETCH_SIZE), i.e. 5.9 TB/s; what is left is the reference's row layout.
 struct __attribute__((packed, aligned(4))) f4u { float v[4]; };
+// Binary16 flatten rows: the channel is 2 * R * R consecutive bytes and lane s takes the same four cells in ONE 8-byte load.  Rows are
+// 6 R^2 + 2 bytes apart -- 4-byte aligned for odd R, 2-byte aligned for even R -- and the step back to the final four cells lands on a 2-byte
+// boundary when the cell count is odd (byte 90 of the channel at R = 7), so the load is declared 2-byte aligned; gfx950 takes such a
+// global_load_dwordx2 as it stands (DESIGN.md section 5 has what the emitted code shows)
+struct __attribute__((packed, aligned(2))) h4u { uint16_t v[4]; };
 
 template <int U>
 __global__ __launch_bounds__(256) void pursuit_policy_rows_kernel(const float *__restrict__ obs, int64_t n_rows, int R, int64_t row_stride,
@@ -117,10 +157,7 @@ __global__ __launch_bounds__(256) void pursuit_policy_rows_kernel(const float *_
     const int base = min(4 * sub, cells - 4);
     uint32_t keyq[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int k = base + q, i = k / R, j = k - i * R;
-        keyq[q] = ((uint32_t)((i - c) * (i - c) + (j - c) * (j - c)) << 16) | (uint32_t)k;
-    }
+    for (int q = 0; q < 4; ++q) keyq[q] = cell_key(base + q, R, c);
     const int64_t stride = (int64_t)gridDim.x * 16;
     const float *o = obs + ch_offset + base;
     for (int64_t row0 = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); row0 < n_rows; row0 += U * stride) {
@@ -135,7 +172,43 @@ __global__ __launch_bounds__(256) void pursuit_policy_rows_kernel(const float *_
         for (int u = 0; u < U; ++u) {
             uint32_t k = 0xFFFFFFFFu;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) k = min(k, v[u].v[q] != 0.0f ? keyq[q] : 0xFFFFFFFFu);
+            for (int q = 0; q < 4; ++q) k = min(k, occupied(v[u].v[q]) ? keyq[q] : 0xFFFFFFFFu);
+            k = min_row16(k);
+            mine = sub == u ? k : mine;   // lane u of the group finishes row u
+        }
+        const int64_t my_row = row0 + sub * stride;
+        if (sub < U && my_row < n_rows) policy_emit(mine, my_row, table, k0, k1, row_id_base, tk, actions);
+    }
+    policy_retire(tick_dev);
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void pursuit_policy_rows_f16_kernel(const uint16_t *__restrict__ obs, int64_t n_rows, int R,
+                                                                      int64_t row_stride, int ch_offset, const uint8_t *__restrict__ table,
+                                                                      uint32_t k0, uint32_t k1, int64_t row_id_base, uint32_t tick,
+                                                                      uint32_t *tick_dev, int32_t *__restrict__ actions) {
+    const int sub = threadIdx.x & 15;
+    const int c = R / 2, cells = R * R;
+    const uint32_t tk = policy_tick(tick, tick_dev);
+    const int base = min(4 * sub, cells - 4);
+    uint32_t keyq[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) keyq[q] = cell_key(base + q, R, c);
+    const int64_t stride = (int64_t)gridDim.x * 16;
+    const uint16_t *o = obs + ch_offset + base;
+    for (int64_t row0 = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); row0 < n_rows; row0 += U * stride) {
+        h4u v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {   // all U loads in flight before the first comparison
+            const int64_t r = row0 + u * stride;
+            v[u] = *reinterpret_cast<const h4u *>(o + (r < n_rows ? r : row0) * row_stride);
+        }
+        uint32_t mine = 0xFFFFFFFFu;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            uint32_t k = 0xFFFFFFFFu;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) k = min(k, occupied(v[u].v[q]) ? keyq[q] : 0xFFFFFFFFu);
             k = min_row16(k);
             mine = sub == u ? k : mine;   // lane u of the group finishes row u
         }
@@ -221,6 +294,37 @@ __global__ __launch_bounds__(256) void multiwalker_policy_kernel(const float *__
     a[0] = clip(hip0); a[1] = clip(knee0); a[2] = clip(hip1); a[3] = clip(knee1);
 }
 
+// (a build with -DMADRL_POLICY_F16_ROWS=0 sends half flatten rows to the generic half kernel: the variant scripts/rollout_f16_time.py times)
+#ifndef MADRL_POLICY_F16_ROWS
+#define MADRL_POLICY_F16_ROWS 1
+#endif
+
+// one dispatch rule for both element types (T: float, or uint16_t for binary16 rows)
+template <typename T>
+int launch_pursuit_policy(const T *obs, int64_t n_rows, int32_t obs_range, int64_t row_stride, int32_t cell_stride, int32_t ch_offset,
+                          const uint8_t *table_dev, uint64_t seed, int64_t row_id_base, uint32_t tick, uint32_t *tick_dev, int32_t *actions,
+                          void *stream) {
+    constexpr bool F16 = sizeof(T) == 2;
+    const int cells = obs_range * obs_range;
+    if (cell_stride == 1 && cells >= 4 && cells <= 64 && (!F16 || MADRL_POLICY_F16_ROWS)) {
+        constexpr int U = 2;
+        int64_t blocks = (n_rows + 16 * U - 1) / (16 * U);
+        if (blocks > 256 * 8) blocks = 256 * 8;   // 8 four-wavefront blocks per CU: every wavefront resident at once
+        auto kernel = [] { if constexpr (F16) return pursuit_policy_rows_f16_kernel<U>; else return pursuit_policy_rows_kernel<U>; }();
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, obs, n_rows, (int)obs_range,
+                           row_stride, (int)ch_offset, table_dev, (uint32_t)seed, (uint32_t)(seed >> 32), row_id_base, tick, tick_dev, actions);
+    } else {
+        int64_t blocks = (n_rows + 15) / 16;
+        if (blocks > 256 * 16) blocks = 256 * 16;   // 16 four-wavefront blocks per CU: two rounds of resident wavefronts
+        auto kernel = [] { if constexpr (F16) return pursuit_policy_f16_kernel; else return pursuit_policy_kernel; }();
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, obs, n_rows,
+                           (int)obs_range, row_stride, (int)cell_stride, (int)ch_offset, table_dev, (uint32_t)seed, (uint32_t)(seed >> 32),
+                           row_id_base, tick, tick_dev, actions);
+    }
+    MADRL_HIP_TRY(hipGetLastError());
+    return MADRL_OK;
+}
+
 }  // namespace
 }  // namespace madrl
 
@@ -232,22 +336,15 @@ int madrl_heuristic_pursuit(const float *obs, int64_t n_rows, int32_t obs_range,
                             int32_t ch_offset, const uint8_t *table_dev, uint64_t seed, int64_t row_id_base, uint32_t tick,
                             uint32_t *tick_dev, int32_t *actions, void *stream) {
     if (!obs || !table_dev || !actions || n_rows < 1 || obs_range < 1 || obs_range > 255) return fail(MADRL_EINVAL, "heuristic_pursuit: bad argument");
-    const int cells = obs_range * obs_range;
-    if (cell_stride == 1 && cells >= 4 && cells <= 64) {
-        constexpr int U = 2;
-        int64_t blocks = (n_rows + 16 * U - 1) / (16 * U);
-        if (blocks > 256 * 8) blocks = 256 * 8;   // 8 four-wavefront blocks per CU: every wavefront resident at once
-        hipLaunchKernelGGL(pursuit_policy_rows_kernel<U>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, obs, n_rows, (int)obs_range,
-                           row_stride, (int)ch_offset, table_dev, (uint32_t)seed, (uint32_t)(seed >> 32), row_id_base, tick, tick_dev, actions);
-    } else {
-        int64_t blocks = (n_rows + 15) / 16;
-        if (blocks > 256 * 16) blocks = 256 * 16;   // 16 four-wavefront blocks per CU: two rounds of resident wavefronts
-        hipLaunchKernelGGL(pursuit_policy_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, obs, n_rows,
-                           (int)obs_range, row_stride, (int)cell_stride, (int)ch_offset, table_dev, (uint32_t)seed, (uint32_t)(seed >> 32),
-                           row_id_base, tick, tick_dev, actions);
-    }
-    MADRL_HIP_TRY(hipGetLastError());
-    return MADRL_OK;
+    return launch_pursuit_policy(obs, n_rows, obs_range, row_stride, cell_stride, ch_offset, table_dev, seed, row_id_base, tick, tick_dev, actions, stream);
+}
+
+int madrl_heuristic_pursuit_f16(const void *obs_f16, int64_t n_rows, int32_t obs_range, int64_t row_stride, int32_t cell_stride,
+                                int32_t ch_offset, const uint8_t *table_dev, uint64_t seed, int64_t row_id_base, uint32_t tick,
+                                uint32_t *tick_dev, int32_t *actions, void *stream) {
+    if (!obs_f16 || !table_dev || !actions || n_rows < 1 || obs_range < 1 || obs_range > 255) return fail(MADRL_EINVAL, "heuristic_pursuit_f16: bad argument");
+    return launch_pursuit_policy(static_cast<const uint16_t *>(obs_f16), n_rows, obs_range, row_stride, cell_stride, ch_offset, table_dev, seed,
+                                 row_id_base, tick, tick_dev, actions, stream);
 }
 
 int madrl_heuristic_waterworld(const float *obs, int64_t n_rows, int32_t obs_dim, const double *cos_sin_dev, float *actions, void *stream) {

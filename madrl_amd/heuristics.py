@@ -50,13 +50,19 @@ class _DevicePolicy(object):
 
 
 class PursuitHeuristicPolicy(_DevicePolicy):
-    """obs: flatten rows [N, P, 3*R*R+1] or windows [N, P, R, R, 4] of BatchedPursuitEvade -> int32 [N, P]"""
+    """obs: flatten rows [N, P, 3*R*R+1] or windows [N, P, R, R, 4] of BatchedPursuitEvade -> int32 [N, P]
+
+    obs_dtype: torch.float32, or torch.float16 for the rows of BatchedPursuitEvade(obs_dtype=torch.float16).  A policy reads exactly its own
+    element type (any other is a TypeError before a pointer is taken) and gives the actions of the float32 policy on the widened rows."""
 
     def __call__(self, obs, out=None):
         """out: optional contiguous int32 destination of the actions (e.g. a slot of a trajectory tensor): no copy afterwards"""
         return self.sample_actions(obs, out=out)[0]
 
-    def __init__(self, obs_range, flatten=True, seed=0, row_id_base=0):
+    def __init__(self, obs_range, flatten=True, seed=0, row_id_base=0, obs_dtype=torch.float32):
+        if obs_dtype not in (torch.float32, torch.float16):
+            raise ValueError("obs_dtype must be torch.float32 or torch.float16, got %r" % (obs_dtype,))
+        self.obs_dtype = obs_dtype
         self.R, self.flatten, self.seed, self.row_id_base = int(obs_range), bool(flatten), int(seed), int(row_id_base)
         self._tick = None  # [draw counter, workgroup counts ...] on the device: every launch advances the counter itself (a host counter would be frozen into a captured hipGraph)
         self._table_host = pursuit_decision_table(self.R)
@@ -64,7 +70,15 @@ class PursuitHeuristicPolicy(_DevicePolicy):
         self._act = None
 
     def sample_actions(self, obs, deterministic=True, out=None):
-        obs = _lib.require_float32(obs, "PursuitHeuristicPolicy").contiguous()
+        if self.obs_dtype is torch.float32:
+            obs = _lib.require_float32(obs, "PursuitHeuristicPolicy").contiguous()
+            launch = "madrl_heuristic_pursuit"
+        else:
+            if not isinstance(obs, torch.Tensor) or obs.dtype is not torch.float16:
+                raise TypeError("PursuitHeuristicPolicy(obs_dtype=torch.float16) reads float16 observations through the C ABI, got %s (the rows of a "
+                                "float32 PursuitEvade take a policy with obs_dtype=torch.float32)" % getattr(obs, "dtype", type(obs).__name__))
+            obs = obs.contiguous()
+            launch = "madrl_heuristic_pursuit_f16"
         R = self.R
         n_rows = obs.shape[0] * obs.shape[1]
         if self._table is None or self._table.device != obs.device:
@@ -80,9 +94,9 @@ class PursuitHeuristicPolicy(_DevicePolicy):
             self._tick = torch.zeros(_lib.POLICY_COUNTER_WORDS, dtype=torch.int32, device=obs.device)
         row_stride = obs.numel() // n_rows
         cell_stride, ch_off = (1, 2 * R * R) if self.flatten else (4, 2)
-        _lib.check(_lib.lib().madrl_heuristic_pursuit(_lib.ptr(obs), n_rows, R, row_stride, cell_stride, ch_off, _lib.ptr(self._table),
-                                                      self.seed, self.row_id_base, 0, _lib.ptr(self._tick), _lib.ptr(act),
-                                                      _lib.current_stream(obs.device)))
+        _lib.check(getattr(_lib.lib(), launch)(_lib.ptr(obs), n_rows, R, row_stride, cell_stride, ch_off, _lib.ptr(self._table),
+                                               self.seed, self.row_id_base, 0, _lib.ptr(self._tick), _lib.ptr(act),
+                                               _lib.current_stream(obs.device)))
         return act, None
 
 
