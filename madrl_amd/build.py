@@ -18,6 +18,7 @@ csrc/*_specializations.local.def (git-ignored, included after the committed list
 -ffp-contract=off: reward arithmetic and the reset window are float64 expressions that must
 round step by step like NumPy does in the reference; an FMA contraction would change bits.
 """
+import collections
 import os
 import re
 import subprocess
@@ -123,33 +124,47 @@ def _append_local(def_name, line):
     return True
 
 
-def add_pursuit_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
-    kind, nw = pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten)
+def _add(*pairs):
+    """append each (list file, line) to the local companion of that list unless the lists hold the line already -> whether anything was added"""
+    return any([_append_local(name, line + "   // added by madrl_amd.build") for name, line in pairs])
+
+
+class _Shape(collections.namedtuple("_Shape", "kind nw args why_wave why_crowd")):
+    """a shape, classified once (_classify).  kind, nw: the family that takes it -- "X" (nw None), "XG" or, for a shape without an X / XG fast
+    path, "XC", with its NW -- or None; args: the numbers of its line, that NW included; why_wave / why_crowd: what pursuit_fast_path /
+    pursuit_crowd_path refuse it for, or None"""
+    def line(self, macro):
+        return "%s(%s)" % (macro, self.args)
+
+
+def _classify(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True):
+    (kind, nw), (ckind, cnw) = (f(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id) for f in (pursuit_fast_path, pursuit_crowd_path))
+    why_wave, why_crowd = nw if kind is None else None, cnw if ckind is None else None
     if kind is None:
-        raise ValueError("no fast path for this PursuitEvade shape: %s (it runs on the generic kernel)" % nw)
-    args = "%d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)))
-    return _append_local("pursuit_specializations.def", "X(%s)   // added by madrl_amd.build" % args if kind == "X" else
-                         "XG(%s, %d)   // added by madrl_amd.build" % (args, nw))
+        kind, nw = ckind, None if ckind is None else cnw
+    args = "%d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten))) + ("" if nw is None else ", %d" % nw)
+    return _Shape(kind, nw, args, why_wave, why_crowd)
+
+
+def add_pursuit_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
+    c = _classify(xs, ys, n_pursuers, n_evaders, obs_range, flatten)
+    if c.why_wave is not None:
+        raise ValueError("no fast path for this PursuitEvade shape: %s (it runs on the generic kernel)" % c.why_wave)
+    return _add(("pursuit_specializations.def", c.line(c.kind)))
 
 
 def add_pursuit_crowd_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
-    kind, nw = pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten)
+    kind, nw = pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten)   # (also for a shape that has an X / XG fast path)
     if kind is None:
         raise ValueError("no crowd kernel for this PursuitEvade shape: %s (it runs on the generic kernel)" % nw)
-    return _append_local("pursuit_crowd_specializations.def", "XC(%d, %d, %d, %d, %d, %d, %d)   // added by madrl_amd.build"
-                         % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)), nw))
+    return _add(("pursuit_crowd_specializations.def", "XC(%d, %d, %d, %d, %d, %d, %d)" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)), nw)))
 
 
 def pursuit_live_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True):
     """-> (live line, fixed line) that give a per-env-counts capacity its fast path: XL(...) over an X(...) shape, XLG(..., NW) over an
     XG(..., NW) shape -- or None when the capacity has no fast path at all (pursuit_fast_path says why).  Pure: nothing is written."""
-    kind, nw = pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
-    if kind is None:
-        return None
-    args = "%d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)))
-    if kind == "X":
-        return "XL(%s)" % args, "X(%s)" % args
-    return "XLG(%s, %d)" % (args, nw), "XG(%s, %d)" % (args, nw)
+    c = _classify(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
+    return (c.line("XL" + c.kind[1:]), c.line(c.kind)) if c.kind in ("X", "XG") else None
 
 
 def add_pursuit_live_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
@@ -158,23 +173,16 @@ def add_pursuit_live_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
     lines = pursuit_live_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten)
     if lines is None:
         raise ValueError("no fast path for this PursuitEvade capacity: %s (per-env agent counts run on the generic kernel)"
-                         % pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten)[1])
-    live, fixed = lines
-    added_fixed = _append_local("pursuit_specializations.def", fixed + "   // added by madrl_amd.build")
-    return _append_local("pursuit_live_specializations.def", live + "   // added by madrl_amd.build") or added_fixed
+                         % _classify(xs, ys, n_pursuers, n_evaders, obs_range, flatten).why_wave)
+    return _add(("pursuit_specializations.def", lines[1]), ("pursuit_live_specializations.def", lines[0]))
 
 
 def pursuit_live_crowd_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True):
     """-> (live line, fixed line) that give a per-env-counts capacity above 64 pursuers or evaders the crowd kernel: XLC(..., NW) over an
     XC(..., NW) shape -- or None when the crowd kernel cannot take the capacity (pursuit_crowd_path says why) or when it has an X / XG
     fast path (pursuit_live_lines forms its lines).  Pure: nothing is written."""
-    if pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)[0] is not None:
-        return None
-    kind, nw = pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
-    if kind is None:
-        return None
-    args = "%d, %d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)), nw)
-    return "XLC(%s)" % args, "XC(%s)" % args
+    c = _classify(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
+    return (c.line("XLC"), c.line("XC")) if c.kind == "XC" else None
 
 
 def add_pursuit_live_crowd_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
@@ -182,30 +190,24 @@ def add_pursuit_live_crowd_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatt
     local crowd list if it is missing"""
     lines = pursuit_live_crowd_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten)
     if lines is None:
-        if pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten)[0] is not None:
+        c = _classify(xs, ys, n_pursuers, n_evaders, obs_range, flatten)
+        if c.kind is not None:
             raise ValueError("this PursuitEvade capacity has a one-wavefront / multi-wavefront fast path: use --pursuit-live-shape")
-        raise ValueError("no crowd kernel for this PursuitEvade capacity: %s (per-env agent counts run on the generic kernel)"
-                         % pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten)[1])
-    live, fixed = lines
-    added_fixed = _append_local("pursuit_crowd_specializations.def", fixed + "   // added by madrl_amd.build")
-    return _append_local("pursuit_live_specializations.def", live + "   // added by madrl_amd.build") or added_fixed
+        raise ValueError("no crowd kernel for this PursuitEvade capacity: %s (per-env agent counts run on the generic kernel)" % c.why_crowd)
+    return _add(("pursuit_crowd_specializations.def", lines[1]), ("pursuit_live_specializations.def", lines[0]))
 
 
 def pursuit_to_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True):
     """-> (two-buffer line, fixed line) that give step_to() of a shape its fast kernel: X(...) over an X(...) shape, XC(..., NW) over an
     XC(..., NW) shape -- or (None, why not): the lines of a multi-wavefront (XG) shape are formed by pursuit_to_group_lines, and a shape
     without an X / XC fast path has nothing to stand on.  Pure: nothing is written."""
-    kind, nw = pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
-    args = "%d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)))
-    if kind == "X":
-        return "X(%s)" % args, "X(%s)" % args
-    if kind == "XG":
+    c = _classify(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
+    if c.kind == "XG":
         return None, ("its fast path is the multi-wavefront kernel (XG, %d wavefronts), whose two-buffer line --pursuit-to-group-shape adds: "
-                      "use that option" % nw)
-    ckind, cnw = pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
-    if ckind is None:
-        return None, "the shape has no X / XC fast path (one wavefront: %s; crowd kernel: %s)" % (nw, cnw)
-    return "XC(%s, %d)" % (args, cnw), "XC(%s, %d)" % (args, cnw)
+                      "use that option" % c.nw)
+    if c.kind is None:
+        return None, "the shape has no X / XC fast path (one wavefront: %s; crowd kernel: %s)" % (c.why_wave, c.why_crowd)
+    return c.line(c.kind), c.line(c.kind)
 
 
 def add_pursuit_to_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
@@ -214,24 +216,26 @@ def add_pursuit_to_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten):
     line, fixed = pursuit_to_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten)
     if line is None:
         raise ValueError("no two-buffer fast kernel for this PursuitEvade shape: %s (step_to runs on the generic kernel)" % fixed)
-    added_fixed = _append_local("pursuit_specializations.def" if fixed.startswith("X(") else "pursuit_crowd_specializations.def",
-                                fixed + "   // added by madrl_amd.build")
-    return _append_local("pursuit_to_specializations.def", line + "   // added by madrl_amd.build") or added_fixed
+    return _add(("pursuit_specializations.def" if fixed.startswith("X(") else "pursuit_crowd_specializations.def", fixed),
+                ("pursuit_to_specializations.def", line))
+
+
+def _group_lines(shape, include_id, macro, x_why, xc_why):
+    """-> (line under `macro`, XG line) of a multi-wavefront shape, or (None, why not): an X shape x_why, an XC shape xc_why after the
+    refusal of pursuit_fast_path, any other shape that refusal alone"""
+    c = _classify(*shape, include_id=include_id)
+    if c.kind == "XG":
+        return c.line(macro), c.line("XG")
+    return None, x_why if c.kind == "X" else "no multi-wavefront fast path (%s); %s" % (c.why_wave, xc_why) if c.kind == "XC" else c.why_wave
 
 
 def pursuit_to_group_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True, live=False):
     """-> (two-buffer line, fixed line) that give step_to() of a multi-wavefront shape its fast kernel: XG(..., NW) -- live: XLG(..., NW),
     the handles with per-env agent counts -- over an XG(..., NW) shape, or (None, why not): a one-wavefront or crowd shape has its lines
     from pursuit_to_lines, and a shape without a fast path has nothing to stand on.  Pure: nothing is written."""
-    kind, nw = pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
-    args = "%d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)))
-    if kind == "XG":
-        return "%s(%s, %d)" % ("XLG" if live else "XG", args, nw), "XG(%s, %d)" % (args, nw)
-    if kind == "X":
-        return None, "its fast path is the one-wavefront kernel (X): use --pursuit-to-shape"
-    if pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)[0] is not None:
-        return None, "no multi-wavefront fast path (%s); the crowd kernel takes this shape: use --pursuit-to-shape" % nw
-    return None, nw
+    return _group_lines((xs, ys, n_pursuers, n_evaders, obs_range, flatten), include_id, "XLG" if live else "XG",
+                        "its fast path is the one-wavefront kernel (X): use --pursuit-to-shape",
+                        "the crowd kernel takes this shape: use --pursuit-to-shape")
 
 
 def add_pursuit_to_group_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten, live=0):
@@ -240,10 +244,8 @@ def add_pursuit_to_group_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten
     line, fixed = pursuit_to_group_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, live=bool(live))
     if line is None:
         raise ValueError("no two-buffer multi-wavefront kernel for this PursuitEvade shape: %s (step_to runs on the generic kernel)" % fixed)
-    added = _append_local("pursuit_specializations.def", fixed + "   // added by madrl_amd.build")
-    if live:
-        added = _append_local("pursuit_live_specializations.def", line + "   // added by madrl_amd.build") or added
-    return _append_local("pursuit_to_specializations.def", line + "   // added by madrl_amd.build") or added
+    return _add(("pursuit_specializations.def", fixed), *([("pursuit_live_specializations.def", line)] if live else []),
+                ("pursuit_to_specializations.def", line))
 
 
 def pursuit_to_group_f16_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id=True, live=False):
@@ -251,15 +253,9 @@ def pursuit_to_group_f16_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten
     kernel: HG(..., NW) -- live: HLG(..., NW), the handles with per-env agent counts -- over an XG(..., NW) shape, or (None, why not): the
     half kernels of a one-wavefront shape come with its --pursuit-to-shape line, the crowd kernel has no half form, and a shape without a
     fast path has nothing to stand on.  Pure: nothing is written."""
-    kind, nw = pursuit_fast_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)
-    args = "%d, %d, %d, %d, %d, %d" % (xs, ys, n_pursuers, n_evaders, obs_range, int(bool(flatten)))
-    if kind == "XG":
-        return "%s(%s, %d)" % ("HLG" if live else "HG", args, nw), "XG(%s, %d)" % (args, nw)
-    if kind == "X":
-        return None, "its fast path is the one-wavefront kernel (X), whose half kernel comes with its two-buffer line: use --pursuit-to-shape"
-    if pursuit_crowd_path(xs, ys, n_pursuers, n_evaders, obs_range, flatten, include_id)[0] is not None:
-        return None, "no multi-wavefront fast path (%s); the crowd kernel takes this shape, and it has no half form" % nw
-    return None, nw
+    return _group_lines((xs, ys, n_pursuers, n_evaders, obs_range, flatten), include_id, "HLG" if live else "HG",
+                        "its fast path is the one-wavefront kernel (X), whose half kernel comes with its two-buffer line: use --pursuit-to-shape",
+                        "the crowd kernel takes this shape, and it has no half form")
 
 
 def add_pursuit_to_group_f16_shape(xs, ys, n_pursuers, n_evaders, obs_range, flatten, live=0):
@@ -269,10 +265,8 @@ def add_pursuit_to_group_f16_shape(xs, ys, n_pursuers, n_evaders, obs_range, fla
     line, fixed = pursuit_to_group_f16_lines(xs, ys, n_pursuers, n_evaders, obs_range, flatten, live=bool(live))
     if line is None:
         raise ValueError("no half-precision multi-wavefront kernel for this PursuitEvade shape: %s (the half step_to runs on the generic kernel)" % fixed)
-    added = _append_local("pursuit_specializations.def", fixed + "   // added by madrl_amd.build")
-    if live:
-        added = _append_local("pursuit_live_specializations.def", "XLG" + fixed[2:] + "   // added by madrl_amd.build") or added
-    return _append_local("pursuit_to_f16_group_specializations.def", line + "   // added by madrl_amd.build") or added
+    return _add(("pursuit_specializations.def", fixed), *([("pursuit_live_specializations.def", "XLG" + fixed[2:])] if live else []),
+                ("pursuit_to_f16_group_specializations.def", line))
 
 
 def add_waterworld_shape(n_pursuers, n_evaders, n_poison, n_sensors, obs_dim=None):

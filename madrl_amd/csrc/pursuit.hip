@@ -265,8 +265,7 @@ __global__ void pursuit_live_counts_kernel(const PursuitDev d, int32_t *pos_p, i
 
 // =================================================================== host side / C ABI
 namespace {
-struct FastEntry;  // one compiled specialisation: a line of the *_specializations.def lists (below)
-struct FixedEntry;
+struct Line;  // one line of the specialisation lists with every kernel compiled for it (below)
 }
 
 struct madrl_pursuit {
@@ -278,13 +277,11 @@ struct madrl_pursuit {
     int64_t max_blocks = 0;
     size_t lds_bytes = 0;
     void *tables = nullptr;  // one device allocation holding maps | cnt_tmpl | vtab | codes
-    // the fast path: the compile-time specialised kernel of this shape (find_fast), when there is one and the configuration is eligible
-    // for it -- one wavefront per env or a group of them (pursuit_wave.hpp, pursuit_group.hpp: wdev, wtables) or the crowd kernel
-    // (pursuit_crowd.hpp: cdev; it shares the generic kernel's tables)
-    const FastEntry *fast = nullptr;
-    const FastEntry *fast_live = nullptr;  // the live-count instantiation of `fast` (pursuit_live_specializations.def), if compiled
-    const FixedEntry *fixed = nullptr;     // the fixed-constants step kernel of `fast` (pursuit_fixed_specializations.def), if compiled and not
-                                           // switched off (MADRL_PURSUIT_FIXED=0 at create); taken launch by launch (fixed_contract)
+    // the fast path: the line of this shape (find_line), when there is one and the configuration is eligible for it -- one wavefront per
+    // env or a group of them (pursuit_wave.hpp, pursuit_group.hpp: wdev, wtables) or the crowd kernel (pursuit_crowd.hpp: cdev; it shares
+    // the generic kernel's tables).  Which of the line's kernels a launch runs: runs_fast() and takes_fixed() below
+    const Line *line = nullptr;
+    bool fixed_on = false;   // the line's fixed-constants step kernel is not switched off (MADRL_PURSUIT_FIXED=0 at create)
     int last_step_entry = MADRL_STEP_ENTRY_NONE;   // which kernel the last step launch ran on (madrl_pursuit_last_step_entry)
     madrl::pw::WaveDev wdev{};
     madrl::pc::CrowdDev cdev{};
@@ -326,16 +323,33 @@ ShapeKey key_of(const madrl_pursuit_config *c) { return {c->xs, c->ys, c->n_purs
 
 using WaveLaunch = void (*)(const pw::WaveDev &, const pw::WaveIO &, int mode, int64_t blocks, hipStream_t s);
 using CrowdLaunch = void (*)(const pc::CrowdDev &, const pc::CrowdIO &, const int32_t *pending, int mode, int64_t blocks, hipStream_t s);
+using WaveFixedLaunch = void (*)(const pw::WaveDev &, const pw::WaveIO &, int64_t blocks, hipStream_t s);
+using WaveToLaunch = void (*)(const pw::WaveDev &, const pw::WaveIO &, int64_t blocks, hipStream_t s);
+using CrowdToLaunch = void (*)(const pc::CrowdDev &, const pc::CrowdIO &, const int32_t *pending, const float *obs_prev, int64_t blocks, hipStream_t s);
 
-struct FastEntry {
+// The kernels of one line in one count mode, by role; nullptr: no list gives the line that role.  A wave / group line has wave
+// launchers, a crowd line crowd ones (and no half form).
+struct Kernels {
+    WaveLaunch wave;            // in place: reset and step (mode)
+    CrowdLaunch crowd;
+    WaveToLaunch wave_to;       // two buffers (madrl_pursuit_step_to)
+    CrowdToLaunch crowd_to;
+    WaveToLaunch wave_to_f16;   // two buffers of binary16 elements (madrl_pursuit_step_to_f16)
+    constexpr bool has(bool two_buffer, int fmt) const {
+        return !two_buffer ? (wave || crowd) : fmt == OBS_F16 ? wave_to_f16 != nullptr : (wave_to || crowd_to);
+    }
+};
+
+// One X / XG / XC line of pursuit_specializations.def / pursuit_crowd_specializations.def with what the other four lists compile for it.
+struct Line {
     ShapeKey key;
+    bool crowd;      // the family: the crowd kernel, or one wavefront / a group of them per env
     WaveGeom g;      // the compiled geometry (pursuit_tables.hpp).  g.nw, wavefronts per env: 1 = pursuit_wave_kernel, > 1 = pursuit_group_kernel; the
                      // crowd kernel's workgroup.  g.mwords: 1 = one bit per float4 slot in each byte, up to 8 slots per lane; the row-loop kernel: NS / 8
     int mask_bytes;  // per env, of `zmask`
     int resident;    // workgroups of one launch: exactly the resident capacity of the 256 CUs
-    WaveLaunch launch_wave;    // the family: one of the two is set
-    CrowdLaunch launch_crowd;
-    constexpr bool crowd() const { return launch_crowd != nullptr; }
+    Kernels k[2];    // [0] the configuration's counts, [1] per-env agent counts (madrl_pursuit_set_agent_counts)
+    WaveFixedLaunch fixed;   // the step with its launch constants folded in (pw::FShape), taken launch by launch: takes_fixed()
 };
 
 template <class S>
@@ -367,28 +381,27 @@ void group_launch(const pw::WaveDev &d, const pw::WaveIO &io, int mode, int64_t 
 
 // resident: 4 SIMDs of S::OCC wavefronts (the occupancy the kernel's registers are allocated for) on each CU
 template <class S, int NW>
-constexpr FastEntry wave_entry(WaveLaunch launch) {
+constexpr Line wave_entry(WaveLaunch launch) {
     constexpr WaveGeom g{NW, S::GSZ, S::GW, S::PAD, S::X_ID, S::X_SKIP, S::MWORDS, S::D, S::REC_BYTES, S::OFF_GONE, S::OFF_TERM};
     static_assert(g == wave_geom(S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN, NW), "wave_geom() of pursuit_tables.hpp is not this kernel's geometry");
-    return FastEntry{{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN}, g, 256 * NW * S::MWORDS, 256 * 4 * S::OCC / NW, launch, nullptr};
+    return Line{{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN}, false, g, 256 * NW * S::MWORDS, 256 * 4 * S::OCC / NW, {{launch}}, nullptr};
 }
 
 // resident: what the LDS of a workgroup and 24 wavefronts per CU allow (at most 85 registers per lane; a 16-wavefront workgroup may use
 // 128 and is alone on its CU anyway)
 template <class S>
-constexpr FastEntry crowd_entry(CrowdLaunch launch) {
+constexpr Line crowd_entry(CrowdLaunch launch) {
     constexpr int by_lds = 160 * 1024 / (S::LDS_DWORDS * 4), by_waves = 24 / S::NW > 0 ? 24 / S::NW : 1;
-    return FastEntry{{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN}, WaveGeom{S::NW, S::GSZ, 0, 0, 0, 0, 0, S::D, S::REC_BYTES, S::OFF_GONE, S::OFF_TERM},
-                     4, 256 * (by_lds < by_waves ? by_lds : by_waves), nullptr, launch};
+    return Line{{S::XS, S::YS, S::P, S::E, S::R, S::FLATTEN}, true, WaveGeom{S::NW, S::GSZ, 0, 0, 0, 0, 0, S::D, S::REC_BYTES, S::OFF_GONE, S::OFF_TERM},
+                4, 256 * (by_lds < by_waves ? by_lds : by_waves), {{nullptr, launch}}, nullptr};
 }
 
-// The fixed-shape kernels: the X / XG lines, then the XC lines -- a shape that has an X / XG line keeps the kernel of that line.  The
-// *.local.def lists are the lines added on this machine by `python -m madrl_amd.build --pursuit-shape / --pursuit-crowd-shape ...`
-// (git-ignored).
+// The lines: the X / XG lines, then the XC lines -- a shape that has an X / XG line keeps the kernel of that line.  The *.local.def lists
+// are the lines added on this machine by `python -m madrl_amd.build --pursuit-shape / --pursuit-crowd-shape ...` (git-ignored).
 #define X(XS, YS, NP, NE, R, FL) wave_entry<pw::Shape<XS, YS, NP, NE, R, FL>, 1>(wave_launch<pw::Shape<XS, YS, NP, NE, R, FL>>),
 #define XG(XS, YS, NP, NE, R, FL, NW) wave_entry<pw::GShape<XS, YS, NP, NE, R, FL, NW>, NW>(group_launch<pw::GShape<XS, YS, NP, NE, R, FL, NW>>),
 #define XC(XS, YS, NP, NE, R, FL, NW) crowd_entry<pc::CShape<XS, YS, NP, NE, R, FL, NW>>(pc::crowd_launch<pc::CShape<XS, YS, NP, NE, R, FL, NW>>),
-constexpr FastEntry FAST_TABLE[] = {
+constexpr Line BASE_LINES[] = {
 #include "pursuit_specializations.def"
 #if __has_include("pursuit_specializations.local.def")
 #include "pursuit_specializations.local.def"
@@ -402,54 +415,125 @@ constexpr FastEntry FAST_TABLE[] = {
 #undef XG
 #undef XC
 
-// Their live-count instantiations (per-env agent counts), reached through the fixed line of the same shape and NW (find_live): same
-// geometry, same tables.  (wave_launch of an LShape: no evader-control instantiations, madrl_pursuit_set_agent_counts refuses
-// control_evaders; the XLG and XLC kernels are compiled in pursuit_live_group.hip and pursuit_live_crowd.hip.)  The .local.def list:
-// `python -m madrl_amd.build --pursuit-live-shape / --pursuit-live-crowd-shape ...`, which appends the fixed line too.
-#define XL(XS, YS, NP, NE, R, FL) wave_entry<pw::LShape<XS, YS, NP, NE, R, FL>, 1>(wave_launch<pw::LShape<XS, YS, NP, NE, R, FL>>),
-#define XLG(XS, YS, NP, NE, R, FL, NW) wave_entry<pw::LGShape<XS, YS, NP, NE, R, FL, NW>, NW>(pw::live_group_launch<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>),
-#define XLC(XS, YS, NP, NE, R, FL, NW) crowd_entry<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>(pc::live_crowd_launch<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>),
-constexpr FastEntry LIVE_TABLE[] = {
+// The lines with the kernels of the other four lists attached, each to the first line of its key, family and NW.  A line of those lists
+// that finds no line to stand on would compile a kernel that no handle can use: its list is noted in `orphans`, which stops the compile.
+enum Orphan : unsigned { LIVE_WAVE = 1, LIVE_CROWD = 2, LIVE_GEOMETRY = 4, FIXED_LIST = 8, TO_LIST = 16, TO_F16_GROUP_LIST = 32 };
+struct LineTable {
+    Line line[sizeof(BASE_LINES) / sizeof(BASE_LINES[0])];
+    unsigned orphans;
+
+    constexpr Line *stand(const ShapeKey &key, bool crowd, int nw) {
+        for (Line &b : line)
+            if (b.key == key && b.crowd == crowd && b.g.nw == nw) return &b;
+        return nullptr;
+    }
+    // the roles of `add` go to count mode `live` of line `b` (the first line of a list that names a role keeps it); no line: an orphan
+    constexpr void attach(Line *b, bool live, const Kernels &add, Orphan list) {
+        if (!b) { orphans |= list; return; }
+        Kernels &k = b->k[live];
+        if (!k.wave) k.wave = add.wave;
+        if (!k.crowd) k.crowd = add.crowd;
+        if (!k.wave_to) k.wave_to = add.wave_to;
+        if (!k.crowd_to) k.crowd_to = add.crowd_to;
+        if (!k.wave_to_f16) k.wave_to_f16 = add.wave_to_f16;
+    }
+    // a per-env-count instantiation (wave_entry / crowd_entry of an LShape / LGShape / LCShape): it is launched with the tables, masks and
+    // block count of the line it stands on, so its compiled geometry must be that line's
+    constexpr void attach_live(const Line &l) {
+        Line *b = stand(l.key, l.crowd, l.g.nw);
+        if (b && !(b->g == l.g && b->mask_bytes == l.mask_bytes)) orphans |= LIVE_GEOMETRY;
+        attach(b, true, l.k[0], l.crowd ? LIVE_CROWD : LIVE_WAVE);
+    }
+    constexpr void attach_fixed(const ShapeKey &key, WaveFixedLaunch launch) {
+        Line *b = stand(key, false, 1);
+        if (!b) orphans |= FIXED_LIST;
+        else if (!b->fixed) b->fixed = launch;
+    }
+    // a half line of the multi-wavefront family stands on the XG line of its shape, a live one (HLG) also on its XLG line
+    constexpr void attach_half_group(const ShapeKey &key, int nw, bool live, WaveToLaunch launch) {
+        Line *b = nw > 1 ? stand(key, false, nw) : nullptr;
+        attach(b && (!live || b->k[1].wave) ? b : nullptr, live, Kernels{nullptr, nullptr, nullptr, nullptr, launch}, TO_F16_GROUP_LIST);
+    }
+};
+
+constexpr LineTable resolve_lines() {
+    LineTable t{};
+    for (size_t i = 0; i < sizeof(BASE_LINES) / sizeof(BASE_LINES[0]); ++i) t.line[i] = BASE_LINES[i];
+    // Per-env agent counts: same geometry, same tables.  (wave_launch of an LShape: no evader-control instantiations,
+    // madrl_pursuit_set_agent_counts refuses control_evaders; the XLG and XLC kernels are compiled in pursuit_live_group.hip and
+    // pursuit_live_crowd.hip.)  The .local.def list: `python -m madrl_amd.build --pursuit-live-shape / --pursuit-live-crowd-shape ...`,
+    // which appends the fixed line too.
+#define XL(XS, YS, NP, NE, R, FL) t.attach_live(wave_entry<pw::LShape<XS, YS, NP, NE, R, FL>, 1>(wave_launch<pw::LShape<XS, YS, NP, NE, R, FL>>));
+#define XLG(XS, YS, NP, NE, R, FL, NW) t.attach_live(wave_entry<pw::LGShape<XS, YS, NP, NE, R, FL, NW>, NW>(pw::live_group_launch<pw::LGShape<XS, YS, NP, NE, R, FL, NW>>));
+#define XLC(XS, YS, NP, NE, R, FL, NW) t.attach_live(crowd_entry<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>(pc::live_crowd_launch<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>));
 #include "pursuit_live_specializations.def"
 #if __has_include("pursuit_live_specializations.local.def")
 #include "pursuit_live_specializations.local.def"
 #endif
-};
 #undef XL
 #undef XLG
 #undef XLC
-
-// The step kernels with their launch constants folded in (pw::FShape, pursuit_fixed.hip): reached through the X line of the same shape,
-// launch by launch, when the launch meets the FShape contract (fixed_contract below); the masks and the record are the X line's.
-using WaveFixedLaunch = void (*)(const pw::WaveDev &, const pw::WaveIO &, int64_t blocks, hipStream_t s);
-struct FixedEntry {
-    ShapeKey key;
-    WaveFixedLaunch launch;
-};
-#define XF(XS, YS, NP, NE, R, FL) FixedEntry{{XS, YS, NP, NE, R, FL}, pw::wave_fixed_launch<pw::FShape<XS, YS, NP, NE, R, FL>>},
-constexpr FixedEntry FIXED_TABLE[] = {
+    // The step kernels with their launch constants folded in (pw::FShape, pursuit_fixed.hip), of one-wavefront lines: the masks and the
+    // record are the X line's.
+#define XF(XS, YS, NP, NE, R, FL) t.attach_fixed({XS, YS, NP, NE, R, FL}, pw::wave_fixed_launch<pw::FShape<XS, YS, NP, NE, R, FL>>);
 #include "pursuit_fixed_specializations.def"
 #if __has_include("pursuit_fixed_specializations.local.def")
 #include "pursuit_fixed_specializations.local.def"
 #endif
-};
 #undef XF
-constexpr bool fixed_lines_have_their_lines() {
-    for (const FixedEntry &x : FIXED_TABLE) {
-        bool found = false;
-        for (const FastEntry &f : FAST_TABLE) found = found || (f.key == x.key && !f.crowd() && f.g.nw == 1);
-        if (!found) return false;
-    }
-    return true;
+    // The two-buffer step kernels (pursuit_to.hip, pursuit_to_group.hip); an XL / XLG / XLC line is used by handles whose capacity also
+    // has its line in the live list.  The X / XL lines come with their binary16 form (pursuit_to_f16.hip).
+#define TO(XS, YS, NP, NE, R, FL, CROWD, NW, LIVE, ...) t.attach(t.stand({XS, YS, NP, NE, R, FL}, CROWD, NW), LIVE, Kernels{nullptr, nullptr, __VA_ARGS__}, TO_LIST);
+#define X(XS, YS, NP, NE, R, FL) TO(XS, YS, NP, NE, R, FL, false, 1, false, pw::wave_to_launch<pw::TShape<XS, YS, NP, NE, R, FL>>, nullptr, pw::wave_to_f16_launch<pw::THShape<XS, YS, NP, NE, R, FL>>)
+#define XL(XS, YS, NP, NE, R, FL) TO(XS, YS, NP, NE, R, FL, false, 1, true, pw::wave_to_launch<pw::TLShape<XS, YS, NP, NE, R, FL>>, nullptr, pw::wave_to_f16_launch<pw::TLHShape<XS, YS, NP, NE, R, FL>>)
+#define XC(XS, YS, NP, NE, R, FL, NW) TO(XS, YS, NP, NE, R, FL, true, NW, false, nullptr, pc::crowd_to_launch<pc::CShape<XS, YS, NP, NE, R, FL, NW>>, nullptr)
+#define XLC(XS, YS, NP, NE, R, FL, NW) TO(XS, YS, NP, NE, R, FL, true, NW, true, nullptr, pc::crowd_to_launch<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>, nullptr)
+#define XG(XS, YS, NP, NE, R, FL, NW) TO(XS, YS, NP, NE, R, FL, false, NW, false, pw::group_to_launch<pw::TGShape<XS, YS, NP, NE, R, FL, NW>>, nullptr, nullptr)
+#define XLG(XS, YS, NP, NE, R, FL, NW) TO(XS, YS, NP, NE, R, FL, false, NW, true, pw::group_to_launch<pw::TLGShape<XS, YS, NP, NE, R, FL, NW>>, nullptr, nullptr)
+#include "pursuit_to_specializations.def"
+#if __has_include("pursuit_to_specializations.local.def")
+#include "pursuit_to_specializations.local.def"
+#endif
+#undef X
+#undef XL
+#undef XC
+#undef XLC
+#undef XG
+#undef XLG
+#undef TO
+    // The half-precision two-buffer step kernels of the multi-wavefront family (pursuit_to_group_f16.hip, pursuit_to_group_f16_live.hip):
+    // a list of its own; a half line does not need a float32 two-buffer line.
+#define HG(XS, YS, NP, NE, R, FL, NW) t.attach_half_group({XS, YS, NP, NE, R, FL}, NW, false, pw::group_to_f16_launch<pw::THGShape<XS, YS, NP, NE, R, FL, NW>>);
+#define HLG(XS, YS, NP, NE, R, FL, NW) t.attach_half_group({XS, YS, NP, NE, R, FL}, NW, true, pw::group_to_f16_launch<pw::TLHGShape<XS, YS, NP, NE, R, FL, NW>>);
+#include "pursuit_to_f16_group_specializations.def"
+#if __has_include("pursuit_to_f16_group_specializations.local.def")
+#include "pursuit_to_f16_group_specializations.local.def"
+#endif
+#undef HG
+#undef HLG
+    return t;
 }
-static_assert(fixed_lines_have_their_lines(), "an XF line of pursuit_fixed_specializations.def needs the X line of its shape in pursuit_specializations.def");
+constexpr LineTable LINES = resolve_lines();
+static_assert(!(LINES.orphans & LIVE_WAVE), "an XL / XLG line needs the X / XG line of the same capacity with the same NW");
+static_assert(!(LINES.orphans & LIVE_CROWD), "an XLC line needs the XC line of the same capacity with the same NW");
+static_assert(!(LINES.orphans & LIVE_GEOMETRY), "an XL / XLG / XLC kernel's compiled geometry or mask bytes are not those of the X / XG / XC line it is launched with");
+static_assert(!(LINES.orphans & FIXED_LIST), "an XF line of pursuit_fixed_specializations.def needs the X line of its shape in pursuit_specializations.def");
+static_assert(!(LINES.orphans & TO_LIST), "a line of pursuit_to_specializations.def needs the X line (X / XL), the XG line with the same NW (XG / XLG) or the XC line with the same NW (XC / XLC) of its shape");
+static_assert(!(LINES.orphans & TO_F16_GROUP_LIST), "a line of pursuit_to_f16_group_specializations.def needs the XG line of its shape with the same NW in pursuit_specializations.def, an HLG line also the XLG line in pursuit_live_specializations.def");
 
-// the fixed-constants entry of the one-wavefront line `f`, or nullptr
-const FixedEntry *find_fixed(const FastEntry *f) {
-    for (const FixedEntry &x : FIXED_TABLE)
-        if (f && !f->crowd() && f->g.nw == 1 && f->key == x.key) return &x;
+// The line a configuration runs on, by the configuration alone (madrl_pursuit_state_bytes sizes the caller's buffer by it): the first of
+// its shape.  A flatten row without the id is not a whole number of float4; evader control has the one-wavefront kernel or the generic one.
+// A line that madrl_pursuit_create then finds not eligible leaves the handle on the generic kernel, not on a later line.
+const Line *find_line(const madrl_pursuit_config *c) {
+    if (c->flatten && !c->include_id) return nullptr;
+    const ShapeKey k = key_of(c);
+    for (const Line &e : LINES.line) {
+        if (c->control_evaders && (e.g.nw > 1 || e.crowd)) continue;
+        if (e.key == k) return &e;
+    }
     return nullptr;
 }
+
 // MADRL_PURSUIT_FIXED=0 in the environment keeps every handle created from then on off the fixed-constants kernels (A/B runs, twin tests)
 bool fixed_enabled() {
     const char *v = getenv("MADRL_PURSUIT_FIXED");
@@ -472,125 +556,8 @@ bool fixed_contract(const PursuitDev &d, const LaunchAsk &a) {
     return a.step && !a.two_buffer && !a.pending && !a.inj_eact && !a.alternate && d.surround && !d.reward_global && d.train_pursuit &&
            d.n_maps == 1 && !d.sample_maps && d.max_opponents == 0 && d.cw_env == nullptr && d.catchr_env == nullptr;
 }
-
-// The two-buffer step kernels (madrl_pursuit_step_to, pursuit_to.hip and pursuit_to_group.hip): reached through the fixed line of the same shape and NW, for a handle
-// with per-env agent counts through its live line.  A handle without an entry here runs step_to on the generic kernel.
-// launch_wave_f16: the binary16 form (madrl_pursuit_step_to_f16, pursuit_to_f16.hip) -- the X / XL lines have one; the half kernels of the
-// multi-wavefront family are listed in TO_F16_GROUP_TABLE below, and every other handle runs the half step on the generic kernel.
-using WaveToLaunch = void (*)(const pw::WaveDev &, const pw::WaveIO &, int64_t blocks, hipStream_t s);
-using CrowdToLaunch = void (*)(const pc::CrowdDev &, const pc::CrowdIO &, const int32_t *pending, const float *obs_prev, int64_t blocks, hipStream_t s);
-struct ToEntry {
-    ShapeKey key;
-    int nw;
-    bool live;
-    WaveToLaunch launch_wave;    // one of the two is set
-    CrowdToLaunch launch_crowd;
-    WaveToLaunch launch_wave_f16;   // or nullptr
-    constexpr bool crowd() const { return launch_crowd != nullptr; }
-};
-#define X(XS, YS, NP, NE, R, FL) ToEntry{{XS, YS, NP, NE, R, FL}, 1, false, pw::wave_to_launch<pw::TShape<XS, YS, NP, NE, R, FL>>, nullptr, pw::wave_to_f16_launch<pw::THShape<XS, YS, NP, NE, R, FL>>},
-#define XL(XS, YS, NP, NE, R, FL) ToEntry{{XS, YS, NP, NE, R, FL}, 1, true, pw::wave_to_launch<pw::TLShape<XS, YS, NP, NE, R, FL>>, nullptr, pw::wave_to_f16_launch<pw::TLHShape<XS, YS, NP, NE, R, FL>>},
-#define XC(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, false, nullptr, pc::crowd_to_launch<pc::CShape<XS, YS, NP, NE, R, FL, NW>>, nullptr},
-#define XLC(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, true, nullptr, pc::crowd_to_launch<pc::LCShape<XS, YS, NP, NE, R, FL, NW>>, nullptr},
-#define XG(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, false, pw::group_to_launch<pw::TGShape<XS, YS, NP, NE, R, FL, NW>>, nullptr, nullptr},
-#define XLG(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, true, pw::group_to_launch<pw::TLGShape<XS, YS, NP, NE, R, FL, NW>>, nullptr, nullptr},
-constexpr ToEntry TO_TABLE[] = {
-#include "pursuit_to_specializations.def"
-#if __has_include("pursuit_to_specializations.local.def")
-#include "pursuit_to_specializations.local.def"
-#endif
-};
-#undef X
-#undef XL
-#undef XC
-#undef XLC
-#undef XG
-#undef XLG
-
-// A two-buffer line without its fixed line would compile a kernel that no handle can use.
-constexpr bool to_lines_have_fixed_lines() {
-    for (const ToEntry &t : TO_TABLE) {
-        bool found = false;
-        for (const FastEntry &f : FAST_TABLE) found = found || (f.key == t.key && f.crowd() == t.crowd() && f.g.nw == t.nw);
-        if (!found) return false;
-    }
-    return true;
-}
-static_assert(to_lines_have_fixed_lines(), "a line of pursuit_to_specializations.def needs the X line (X / XL), the XG line with the same NW (XG / XLG) or the XC line with the same NW (XC / XLC) of its shape");
-
-// the two-buffer kernel that stands on the fast line `f` (live: the per-env-count instantiation)
-const ToEntry *find_to(const FastEntry *f, bool live) {
-    for (const ToEntry &t : TO_TABLE)
-        if (f && t.key == f->key && t.crowd() == f->crowd() && t.nw == f->g.nw && t.live == live) return &t;
-    return nullptr;
-}
-
-constexpr bool same_line(const FastEntry &a, const FastEntry &b) { return a.key == b.key && a.crowd() == b.crowd() && a.g.nw == b.g.nw; }
-
-// The half-precision two-buffer step kernels of the multi-wavefront family (madrl_pursuit_step_to_f16, pursuit_to_group_f16.hip and
-// pursuit_to_group_f16_live.hip): a list of its own, pursuit_to_f16_group_specializations.def.  Only launch_wave_f16 is set: a half line
-// stands on the XG line of its shape (HLG: and on its XLG line), not on a float32 two-buffer line.
-#define HG(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, false, nullptr, nullptr, pw::group_to_f16_launch<pw::THGShape<XS, YS, NP, NE, R, FL, NW>>},
-#define HLG(XS, YS, NP, NE, R, FL, NW) ToEntry{{XS, YS, NP, NE, R, FL}, NW, true, nullptr, nullptr, pw::group_to_f16_launch<pw::TLHGShape<XS, YS, NP, NE, R, FL, NW>>},
-constexpr ToEntry TO_F16_GROUP_TABLE[] = {
-#include "pursuit_to_f16_group_specializations.def"
-#if __has_include("pursuit_to_f16_group_specializations.local.def")
-#include "pursuit_to_f16_group_specializations.local.def"
-#endif
-};
-#undef HG
-#undef HLG
-
-// A half line without its fixed line (a live one: without its live line) would compile a kernel that no handle can use.
-constexpr bool to_f16_group_lines_have_their_lines() {
-    for (const ToEntry &t : TO_F16_GROUP_TABLE) {
-        bool fixed = false, live = !t.live;
-        for (const FastEntry &f : FAST_TABLE) fixed = fixed || (f.key == t.key && !f.crowd() && f.g.nw == t.nw && t.nw > 1);
-        for (const FastEntry &l : LIVE_TABLE) live = live || (l.key == t.key && !l.crowd() && l.g.nw == t.nw);
-        if (!fixed || !live) return false;
-    }
-    return true;
-}
-static_assert(to_f16_group_lines_have_their_lines(), "a line of pursuit_to_f16_group_specializations.def needs the XG line of its shape with the same NW in pursuit_specializations.def, an HLG line also the XLG line in pursuit_live_specializations.def");
-
-// the half two-buffer group kernel that stands on the fast line `f` (live: the per-env-count instantiation)
-const ToEntry *find_to_f16_group(const FastEntry *f, bool live) {
-    for (const ToEntry &t : TO_F16_GROUP_TABLE)
-        if (f && !f->crowd() && t.key == f->key && t.nw == f->g.nw && t.live == live) return &t;
-    return nullptr;
-}
-
-// A live line without its fixed line would compile a kernel that no handle can use.
-constexpr bool live_lines_have_fixed_lines(bool crowd) {
-    for (const FastEntry &l : LIVE_TABLE) {
-        bool found = l.crowd() != crowd;
-        for (const FastEntry &f : FAST_TABLE) found = found || same_line(f, l);
-        if (!found) return false;
-    }
-    return true;
-}
-static_assert(live_lines_have_fixed_lines(false), "an XL / XLG line needs the X / XG line of the same capacity with the same NW");
-static_assert(live_lines_have_fixed_lines(true), "an XLC line needs the XC line of the same capacity with the same NW");
-
-// The line a configuration runs on, by the configuration alone (madrl_pursuit_state_bytes sizes the caller's buffer by it): the first of
-// its shape.  A flatten row without the id is not a whole number of float4; evader control has the one-wavefront kernel or the generic one.
-// A line that madrl_pursuit_create then finds not eligible leaves the handle on the generic kernel, not on a later line.
-const FastEntry *find_fast(const madrl_pursuit_config *c) {
-    if (c->flatten && !c->include_id) return nullptr;
-    const ShapeKey k = key_of(c);
-    for (const FastEntry &e : FAST_TABLE) {
-        if (c->control_evaders && (e.g.nw > 1 || e.crowd())) continue;
-        if (e.key == k) return &e;
-    }
-    return nullptr;
-}
-
-// the live-count instantiation of the fixed-shape entry `f` the handle uses
-const FastEntry *find_live(const FastEntry *f) {
-    for (const FastEntry &e : LIVE_TABLE)
-        if (f && same_line(e, *f)) return &e;
-    return nullptr;
-}
+// a fast launch on line `l` runs the line's fixed-constants kernel (on: MADRL_PURSUIT_FIXED as read at create)
+bool takes_fixed(const Line *l, bool on, const PursuitDev &d, const LaunchAsk &a) { return on && l && l->fixed && fixed_contract(d, a); }
 
 int validate(const madrl_pursuit_config *c) {
     if (!c) return fail(MADRL_EINVAL, "config is NULL");
@@ -641,13 +608,23 @@ int with_nt(int nt, F &&fn) {
     }
 }
 
-// the fast path this handle can use in its current mode (per-env agent counts: the live-count instantiation)
-const FastEntry *fast_of(const madrl_pursuit *h) { return h->pending ? h->fast_live : h->fast; }
-bool has_wave(const madrl_pursuit *h) { return fast_of(h) != nullptr; }
-bool use_wave(const madrl_pursuit *h) { return has_wave(h) && h->kernel_kind != MADRL_KERNEL_GENERIC; }
+// The kernels of this handle's line in count mode `live` (per-env agent counts: the live-count instantiations), when it has a fast path
+// there at all: a line, and that line's in-place kernel.
+const Kernels *fast_kernels(const madrl_pursuit *h, bool live) {
+    return h->line && h->line->k[live].has(false, OBS_F32) ? &h->line->k[live] : nullptr;
+}
+// Which launch runs a kernel of the line -- every other one runs the generic kernel: in place, a handle with a fast path in its count mode
+// that is not switched to the generic kernel; with two buffers it also needs the line's two-buffer kernel of that mode and element format
+// (shapes without a line in pursuit_to_specializations.def have none; a half form have the X / XL lines of that list and the HG / HLG
+// lines of pursuit_to_f16_group_specializations.def), and evader control runs in place only.
+bool runs_fast(const madrl_pursuit *h, bool two_buffer = false, int fmt = OBS_F32) {
+    const Kernels *k = fast_kernels(h, h->pending != nullptr);
+    if (!k || h->kernel_kind == MADRL_KERNEL_GENERIC) return false;
+    return !two_buffer || (h->dev.train_pursuit && k->has(true, fmt));
+}
 
 // bytes of what the fast path of line `f` remembers about the observation buffer (behind the records in the caller's state buffer)
-size_t zmask_len(const FastEntry *f, int64_t n_envs) { return f ? (size_t)n_envs * (size_t)f->mask_bytes : 0; }
+size_t zmask_len(const Line *f, int64_t n_envs) { return f ? (size_t)n_envs * (size_t)f->mask_bytes : 0; }
 
 template <class IO>
 IO io_of(const PursuitIO &io) {
@@ -671,43 +648,34 @@ Dev dev_now(Dev d, const PursuitDev &now) {
     return d;
 }
 
-// the two-buffer fast kernel a step_to of this handle launches, or nullptr: the generic kernel (evader control and shapes without a
-// line in pursuit_to_specializations.def).  fmt OBS_F16 (madrl_pursuit_step_to_f16): the lines whose kernel has a half form -- the X / XL
-// lines of that list, and for a handle on an XG line the HG / HLG lines of pursuit_to_f16_group_specializations.def.
-const ToEntry *to_of(const madrl_pursuit *h, int fmt = OBS_F32) {
-    if (!use_wave(h) || !h->dev.train_pursuit) return nullptr;
-    const ToEntry *t = find_to(h->fast, h->pending != nullptr);
-    if (fmt != OBS_F16) return t;
-    return (t && t->launch_wave_f16) ? t : find_to_f16_group(h->fast, h->pending != nullptr);
-}
-
 // mode 0: reset, 1: step.  obs_prev == nullptr: in place, io.obs is read and written.  Otherwise madrl_pursuit_step_to: the step's rows go to
 // io.obs and the kept cells come from obs_prev.  fmt: the element format of both buffers -- OBS_F16 (two buffers only): io.obs and
 // obs_prev point at binary16 elements, cast.
 int launch(madrl_pursuit *h, const PursuitIO &io, int mode, const float *obs_prev, void *stream, int fmt = OBS_F32) {
     hipStream_t s = (hipStream_t)stream;
-    const ToEntry *t = obs_prev ? to_of(h, fmt) : nullptr;
-    if (obs_prev ? t != nullptr : use_wave(h)) {
-        const FastEntry *f = fast_of(h);   // (the launcher; the geometry is the fixed line's, h->fast)
-        int64_t blocks = h->max_blocks > 0 ? h->max_blocks : h->fast->resident;   // persistent workgroups, as many as are resident
+    const bool to = obs_prev != nullptr;   // two buffers
+    if (runs_fast(h, to, fmt)) {
+        const Line *l = h->line;
+        const Kernels &k = l->k[h->pending != nullptr];
+        int64_t blocks = h->max_blocks > 0 ? h->max_blocks : l->resident;   // persistent workgroups, as many as are resident
         if (blocks > h->dev.n_envs) blocks = h->dev.n_envs;
         // The masks describe the buffer the kept cells are read from; another one has unknown contents: every cell "not known to be zero".
         // After this launch they describe the buffer it wrote (two buffers: obs_prev is an unknown buffer from here on).
         // "Known zero" is "all bits zero" in either format, but the masks are per element: the same address read in the other format is an
         // unknown buffer too.
         if (h->zmask_obs != (obs_prev ? (const void *)obs_prev : (const void *)io.obs) || h->zmask_fmt != fmt)
-            MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0xFF, zmask_len(h->fast, h->dev.n_envs), s));
+            MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0xFF, zmask_len(l, h->dev.n_envs), s));
         h->zmask_obs = io.obs;
         h->zmask_fmt = fmt;
         if (mode == 1) h->last_step_entry = MADRL_STEP_ENTRY_WAVE;
-        if (f->crowd()) {
+        if (l->crowd) {
             const pc::CrowdDev cd = dev_now(h->cdev, h->dev);
-            if (t) t->launch_crowd(cd, io_of<pc::CrowdIO>(io), h->pending, obs_prev, blocks, s);
-            else f->launch_crowd(cd, io_of<pc::CrowdIO>(io), h->pending, mode, blocks, s);
+            if (to) k.crowd_to(cd, io_of<pc::CrowdIO>(io), h->pending, obs_prev, blocks, s);
+            else k.crowd(cd, io_of<pc::CrowdIO>(io), h->pending, mode, blocks, s);
         } else {
             pw::WaveIO w = io_of<pw::WaveIO>(io);
-            w.flex = (t || io.inj_eact != nullptr || h->dev.catchr_env != nullptr) ? 1 : 0;
-            w.control_evaders = (t || h->dev.train_pursuit) ? 0 : 1;   // (in place only: to_of)
+            w.flex = (to || io.inj_eact != nullptr || h->dev.catchr_env != nullptr) ? 1 : 0;
+            w.control_evaders = (to || h->dev.train_pursuit) ? 0 : 1;   // (in place only: runs_fast)
             w.obs_prev = obs_prev;
             // Large batches: successive step launches walk the env range in opposite directions, so the rows written last by
             // one step are the first ones touched by the next while they are still in the 256 MB memory-side cache.  Measured
@@ -719,11 +687,11 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, const float *obs_pre
             if (alternate) wd.reverse = (int32_t)(h->step_count++ & 1);
             wd.pending = h->pending;
             // the fixed-constants kernel of the line, when this launch meets its contract (the same masks and record: interchangeable)
-            const bool fixed = h->fixed && fixed_contract(h->dev, LaunchAsk{mode == 1, obs_prev != nullptr, h->pending != nullptr, io.inj_eact != nullptr, alternate});
+            const bool fixed = takes_fixed(l, h->fixed_on, h->dev, LaunchAsk{mode == 1, to, h->pending != nullptr, io.inj_eact != nullptr, alternate});
             if (fixed) h->last_step_entry = MADRL_STEP_ENTRY_FIXED;
-            if (t) (fmt == OBS_F16 ? t->launch_wave_f16 : t->launch_wave)(wd, w, blocks, s);
-            else if (fixed) h->fixed->launch(wd, w, blocks, s);
-            else f->launch_wave(wd, w, mode, blocks, s);
+            if (to) (fmt == OBS_F16 ? k.wave_to_f16 : k.wave_to)(wd, w, blocks, s);
+            else if (fixed) l->fixed(wd, w, blocks, s);
+            else k.wave(wd, w, mode, blocks, s);
         }
         MADRL_HIP_TRY(hipGetLastError());
         return MADRL_OK;
@@ -749,12 +717,12 @@ int launch(madrl_pursuit *h, const PursuitIO &io, int mode, const float *obs_pre
 }
 
 // caller-owned state buffer = [n_envs packed records][pad to 256 B][what the configuration's fast path remembers about the observation
-// buffer (FastEntry::mask_bytes per env): stale-zero masks, 256 B per wavefront and mask word, or the crowd kernel's one word][flag plane,
+// buffer (Line::mask_bytes per env): stale-zero masks, 256 B per wavefront and mask word, or the crowd kernel's one word][flag plane,
 // one dword per env].  The one-wavefront kernels of a pw::Shape with ZM16 (pursuit_zm16.hpp: 16 mask bits per lane) read and write only the
 // first n_envs * 128 bytes of the mask region, [n_envs][32] dwords; the region keeps its 256 B per env -- sizes and offsets are part of the
 // ABI -- and the memsets below (0xFF = nothing known, 0 = known zero: the same polarity in both forms) keep covering all of it.
 uint64_t zmask_offset(int rec_bytes, int64_t n_envs) { return align_up((uint64_t)rec_bytes * (uint64_t)n_envs, 256); }
-uint64_t flags_offset(const madrl_pursuit_config *cfg, int rec_bytes, int64_t n_envs) { return zmask_offset(rec_bytes, n_envs) + zmask_len(find_fast(cfg), n_envs); }
+uint64_t flags_offset(const madrl_pursuit_config *cfg, int rec_bytes, int64_t n_envs) { return zmask_offset(rec_bytes, n_envs) + zmask_len(find_line(cfg), n_envs); }
 
 // the launch constants WaveDev and CrowdDev share with the generic kernel's
 template <class Dev>
@@ -857,11 +825,11 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
     d.codes = reinterpret_cast<const uint32_t *>(tb + gt.codes);
 
     // ---- the fast path of this shape, if the configuration is eligible for its line
-    h->fast = find_fast(cfg);
+    h->line = find_line(cfg);
     void *const zmask = (uint8_t *)state_dev + zmask_offset(d.rec_bytes, n_envs);  // caller-owned, like the records
-    if (h->fast && !h->fast->crowd()) {
+    if (h->line && !h->line->crowd) {
         // one wavefront or a group of them per env: its own tables (pursuit_wave.hpp)
-        const WaveTables wt = build_wave_tables(cfg, d, h->fast->g, n_envs, map_pool_host);
+        const WaveTables wt = build_wave_tables(cfg, d, h->line->g, n_envs, map_pool_host);
         if (wt.eligible) {
             const size_t wbytes = wt.host.size() * sizeof(uint32_t);
             e = hipMalloc(&h->wtables, wbytes);
@@ -876,9 +844,9 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
             w.slot_tab = w.fmaps + wt.w_slots;
             w.zmask = reinterpret_cast<uint32_t *>(zmask);
         } else {
-            h->fast = nullptr;
+            h->line = nullptr;
         }
-    } else if (h->fast && h->fast->g.GSZ == d.GSZ && same_record(h->fast->g, d)) {
+    } else if (h->line && h->line->g.GSZ == d.GSZ && same_record(h->line->g, d)) {
         // the crowd kernel: the generic kernel's tables and record, when the compiled geometry is this configuration's
         h->zmask = zmask;
         pc::CrowdDev &c = h->cdev;
@@ -887,10 +855,9 @@ int madrl_pursuit_create(const madrl_pursuit_config *cfg, const int8_t *map_pool
         c.maps = d.maps;
         c.ch3 = reinterpret_cast<const uint32_t *>(zmask);
     } else {
-        h->fast = nullptr;
+        h->line = nullptr;
     }
-    h->fast_live = find_live(h->fast);
-    h->fixed = fixed_enabled() ? find_fixed(h->fast) : nullptr;
+    h->fixed_on = fixed_enabled();
 
     rc = madrl_pursuit_set_launch(h.get(), 0, 0);
     if (rc) return rc;
@@ -921,7 +888,7 @@ int madrl_pursuit_fixed_choice(const madrl_pursuit_config *cfg, int64_t n_envs, 
     const int walk = (launch_bits & MADRL_LAUNCH_WALK_ALTERNATE) ? 1 : (launch_bits & MADRL_LAUNCH_WALK_FORWARD) ? 2 : 0;
     const LaunchAsk a{!(launch_bits & MADRL_LAUNCH_RESET), (launch_bits & (MADRL_LAUNCH_STEP_TO | MADRL_LAUNCH_HALF)) != 0,
                       (launch_bits & MADRL_LAUNCH_PER_ENV_COUNTS) != 0, (launch_bits & MADRL_LAUNCH_INJECTED_ACTIONS) != 0, walk_alternates(d, walk)};
-    const bool fixed = !(launch_bits & MADRL_LAUNCH_KERNEL_GENERIC) && fixed_enabled() && find_fixed(find_fast(cfg)) && fixed_contract(d, a);
+    const bool fixed = !(launch_bits & MADRL_LAUNCH_KERNEL_GENERIC) && takes_fixed(find_line(cfg), fixed_enabled(), d, a);
     *out = fixed ? 1 : 0;
     return MADRL_OK;
 }
@@ -968,10 +935,10 @@ int madrl_pursuit_set_kernel(madrl_pursuit *h, int32_t kind) {
     if (!h) return fail(MADRL_EINVAL, "handle is NULL");
     if (kind != MADRL_KERNEL_AUTO && kind != MADRL_KERNEL_GENERIC && kind != MADRL_KERNEL_WAVE)
         return fail(MADRL_EINVAL, "unknown kernel kind %d", kind);
-    if (kind == MADRL_KERNEL_WAVE && h->pending && !h->fast_live)
+    if (kind == MADRL_KERNEL_WAVE && h->pending && !fast_kernels(h, true))
         return fail(MADRL_EINVAL, "per-env agent counts: no live-count specialisation was compiled for this capacity "
                     "(see madrl_amd/csrc/pursuit_live_specializations.def)");
-    if (kind == MADRL_KERNEL_WAVE && !h->fast)
+    if (kind == MADRL_KERNEL_WAVE && !fast_kernels(h, false))
         return fail(MADRL_EINVAL, "no one-wavefront-per-env specialisation was compiled for this configuration "
                     "(see madrl_amd/csrc/pursuit_specializations.def)");
     h->kernel_kind = kind;
@@ -980,7 +947,7 @@ int madrl_pursuit_set_kernel(madrl_pursuit *h, int32_t kind) {
 
 int madrl_pursuit_kernel_kind(const madrl_pursuit *h, int32_t *out_kind) {
     if (!h || !out_kind) return fail(MADRL_EINVAL, "NULL argument");
-    *out_kind = use_wave(h) ? MADRL_KERNEL_WAVE : MADRL_KERNEL_GENERIC;
+    *out_kind = runs_fast(h) ? MADRL_KERNEL_WAVE : MADRL_KERNEL_GENERIC;
     return MADRL_OK;
 }
 
@@ -1018,7 +985,7 @@ int madrl_pursuit_step_to(madrl_pursuit *h, const int32_t *actions_dev, const in
 
 int madrl_pursuit_step_to_kernel_kind(madrl_pursuit *h, int32_t *out) {
     if (!h || !out) return fail(MADRL_EINVAL, "NULL argument");
-    *out = to_of(h) ? MADRL_KERNEL_WAVE : MADRL_KERNEL_GENERIC;
+    *out = runs_fast(h, true) ? MADRL_KERNEL_WAVE : MADRL_KERNEL_GENERIC;
     return MADRL_OK;
 }
 
@@ -1037,7 +1004,7 @@ int madrl_pursuit_step_to_f16(madrl_pursuit *h, const int32_t *actions_dev, cons
 
 int madrl_pursuit_step_to_f16_kernel_kind(madrl_pursuit *h, int32_t *out) {
     if (!h || !out) return fail(MADRL_EINVAL, "NULL argument");
-    *out = to_of(h, OBS_F16) ? MADRL_KERNEL_WAVE : MADRL_KERNEL_GENERIC;
+    *out = runs_fast(h, true, OBS_F16) ? MADRL_KERNEL_WAVE : MADRL_KERNEL_GENERIC;
     return MADRL_OK;
 }
 
@@ -1108,7 +1075,7 @@ int madrl_pursuit_invalidate_obs(madrl_pursuit *h) {
 int madrl_pursuit_declare_obs_zero(madrl_pursuit *h, const float *obs_dev, void *stream) {
     if (!h || !obs_dev) return fail(MADRL_EINVAL, "declare_obs_zero: NULL argument");
     if (h->zmask) {   // every cell of that buffer is known to hold +0.0f: no stale cell can need protecting
-        MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0, zmask_len(h->fast, h->dev.n_envs), (hipStream_t)stream));
+        MADRL_HIP_TRY(hipMemsetAsync(h->zmask, 0, zmask_len(h->line, h->dev.n_envs), (hipStream_t)stream));
         h->zmask_obs = obs_dev;
         h->zmask_fmt = OBS_F32;
     }
@@ -1134,7 +1101,7 @@ int madrl_pursuit_set_agent_counts(madrl_pursuit *h, const int32_t *pending_dev)
     if (!h) return fail(MADRL_EINVAL, "handle is NULL");
     if (pending_dev && !h->dev.train_pursuit)
         return fail(MADRL_EINVAL, "per-env agent counts with control_evaders=1 (train_pursuit=False) are not supported");
-    if (pending_dev && h->kernel_kind == MADRL_KERNEL_WAVE && !h->fast_live)
+    if (pending_dev && h->kernel_kind == MADRL_KERNEL_WAVE && !fast_kernels(h, true))
         return fail(MADRL_EINVAL, "per-env agent counts: kernel WAVE was requested and no live-count specialisation was compiled for this "
                     "capacity (see madrl_amd/csrc/pursuit_live_specializations.def)");
     h->pending = pending_dev;

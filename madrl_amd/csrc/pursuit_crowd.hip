@@ -1,6 +1,6 @@
 // pursuit_crowd.hip -- the instantiations of the crowd kernel (pursuit_crowd_kernel<CShape<...>, MODE>, the XC lines of
 // pursuit_crowd_specializations.def).  A translation unit of their own: the build compiles it side by side with pursuit.hip, whose
-// FAST_TABLE reaches these kernels through crowd_launch<S>.
+// table of lines reaches these kernels through crowd_launch<S>.
 #include "common.hpp"
 #include "pursuit_crowd.hpp"
 

@@ -231,7 +231,7 @@ __global__ __launch_bounds__(S::NT) void pursuit_crowd_to_kernel(const CrowdDev 
 }
 
 // host side: launches the instantiation of shape S (defined and instantiated for every XC line in pursuit_crowd.hip; `pending` is not
-// used: one signature for both launchers, FastEntry in pursuit.hip)
+// used: one signature for both launchers, Kernels in pursuit.hip)
 template <class S>
 void crowd_launch(const CrowdDev &d, const CrowdIO &io, const int32_t *pending, int mode, int64_t blocks, hipStream_t s);
 // ... of an LCShape (for every XLC line in pursuit_live_crowd.hip)

@@ -1,6 +1,6 @@
 // pursuit_fixed.hip -- the one-wavefront step kernels with their launch constants folded in: pursuit_wave_kernel<FShape<...>, 1, false, false>
 // for the XF lines of pursuit_fixed_specializations.def.  A translation unit of its own: the build compiles it side by side with pursuit.hip,
-// whose FIXED_TABLE reaches these kernels through wave_fixed_launch<S>.
+// whose table of lines reaches these kernels through wave_fixed_launch<S>.
 #include "common.hpp"
 #include "pursuit_wave.hpp"
 

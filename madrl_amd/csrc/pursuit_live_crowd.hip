@@ -1,6 +1,6 @@
 // pursuit_live_crowd.hip -- the per-env agent-count instantiations of the crowd kernel (pursuit_live_crowd_kernel<LCShape<...>, MODE>, the XLC
 // lines of pursuit_live_specializations.def).  A translation unit of their own: the build compiles it side by side with pursuit.hip, whose
-// LIVE_TABLE reaches these kernels through live_crowd_launch<S>.
+// table of lines reaches these kernels through live_crowd_launch<S>.
 #include "common.hpp"
 #include "pursuit_crowd.hpp"
 

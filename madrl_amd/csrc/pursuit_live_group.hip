@@ -1,6 +1,6 @@
 // pursuit_live_group.hip -- the per-env agent-count instantiations of the group kernel (pursuit_group_kernel<LGShape<...>>, the XLG lines
 // of pursuit_live_specializations.def).  A translation unit of their own: the build compiles it side by side with pursuit.hip, whose
-// LIVE_TABLE reaches these kernels through live_group_launch<S>.
+// table of lines reaches these kernels through live_group_launch<S>.
 #include "common.hpp"
 #include "pursuit_group.hpp"
 

@@ -1,6 +1,6 @@
 // pursuit_to.hip -- the two-buffer step kernels of madrl_pursuit_step_to (the lines of pursuit_to_specializations.def): the flexible step
 // kernel of the one-wavefront family over a TShape / TLShape, and pursuit_crowd_to_kernel over a CShape / LCShape (the XG / XLG lines, the
-// multi-wavefront family, are compiled in pursuit_to_group.hip).  A translation unit of its own: the build compiles it side by side with pursuit.hip, whose TO_TABLE reaches these kernels through wave_to_launch<S> and
+// multi-wavefront family, are compiled in pursuit_to_group.hip).  A translation unit of its own: the build compiles it side by side with pursuit.hip, whose table of lines reaches these kernels through wave_to_launch<S> and
 // crowd_to_launch<S>.
 #include "common.hpp"
 #include "pursuit_wave.hpp"

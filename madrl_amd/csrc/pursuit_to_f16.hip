@@ -4,7 +4,7 @@
 // family have a list of their own, pursuit_to_f16_group_specializations.def (HG / HLG lines over a THGShape / TLHGShape of
 // pursuit_group.hpp: pursuit_to_group_f16.hip, pursuit_to_group_f16_live.hip).  The XC / XLC (crowd) lines and the multi-wavefront
 // shapes not listed there have no half form: their handles run the half step on the generic kernel
-// (pursuit_to_f16_kernel, pursuit.hip).  A translation unit of its own, compiled side by side with pursuit.hip, whose TO_TABLE reaches these
+// (pursuit_to_f16_kernel, pursuit.hip).  A translation unit of its own, compiled side by side with pursuit.hip, whose table of lines reaches these
 // kernels through wave_to_f16_launch<S>.
 #include "common.hpp"
 #include "pursuit_wave.hpp"

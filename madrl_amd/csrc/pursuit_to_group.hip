@@ -1,7 +1,7 @@
 // pursuit_to_group.hip -- the two-buffer step kernels of the multi-wavefront family (the XG / XLG lines of pursuit_to_specializations.def):
 // the flexible step kernel pursuit_group_kernel<S, 1, true> over a TGShape / TLGShape.  A translation unit of its own rather than a part of
 // pursuit_to.hip: the long-row kernels are the slowest of the two-buffer list to compile, and the build compiles its objects side by side.
-// pursuit.hip's TO_TABLE reaches these kernels through group_to_launch<S>.
+// pursuit.hip's table of lines reaches these kernels through group_to_launch<S>.
 #include "common.hpp"
 #include "pursuit_group.hpp"
 

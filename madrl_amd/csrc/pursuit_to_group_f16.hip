@@ -2,7 +2,7 @@
 // flexible step kernel pursuit_group_kernel<S, 1, true> over a THGShape (pursuit_group.hpp), one for every HG line of
 // pursuit_to_f16_group_specializations.def (the HLG lines, over a TLHGShape: pursuit_to_group_f16_live.hip).  A translation unit of its
 // own: the long-row kernels are the slowest of the list to compile, and the build compiles its objects side by side.
-// pursuit.hip's TO_F16_GROUP_TABLE reaches these kernels through group_to_f16_launch<S>.
+// pursuit.hip's table of lines reaches these kernels through group_to_f16_launch<S>.
 #include "common.hpp"
 #include "pursuit_group.hpp"
 

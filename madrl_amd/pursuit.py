@@ -210,41 +210,30 @@ class BatchedPursuitEvade(AbstractMAEnv):
         shape = (self.xs, self.ys, int(self.n_pursuers), int(self.n_evaders), int(self.obs_range), int(bool(self.flatten)))
         if shape in BatchedPursuitEvade._hinted or self.kernel_kind != "generic" or not self.train_pursuit and shape[2] + shape[3] > 64:
             return
-        if self.per_env_counts:   # a capacity without a live-count instantiation
-            lines = _build.pursuit_live_lines(*shape, include_id=bool(self.include_id))
+        xs, ys, P, E, R = shape[:5]
+        args, inc = " ".join(str(v) for v in shape), bool(self.include_id)
+        msg = None
+        if self.per_env_counts:   # a capacity without a live-count instantiation; more than 64 of a kind: the crowd kernel's
+            lines, crowd = _build.pursuit_live_lines(*shape, include_id=inc), _build.pursuit_live_crowd_lines(*shape, include_id=inc)
             if lines is not None:
-                import warnings
-                BatchedPursuitEvade._hinted.add(shape)
-                warnings.warn("PursuitEvade per-env agent counts at capacity %d v %d (%dx%d, obs_range %d) run on the generic kernel; the line "
-                              "%s in madrl_amd/csrc/pursuit_live_specializations.def (and a rebuild: `python -m madrl_amd.build "
-                              "--pursuit-live-shape %s`) gives them the %s kernel"
-                              % (shape[2], shape[3], shape[0], shape[1], shape[4], lines[0].replace(" ", ""), " ".join(str(v) for v in shape),
-                                 "one-wavefront" if lines[0].startswith("XL(") else "multi-wavefront"), stacklevel=3)
-                return
-            lines = _build.pursuit_live_crowd_lines(*shape, include_id=bool(self.include_id))
-            if lines is not None:   # more than 64 of a kind: the crowd kernel's live-count instantiation
-                import warnings
-                BatchedPursuitEvade._hinted.add(shape)
-                warnings.warn("PursuitEvade per-env agent counts at capacity %d v %d (%dx%d, obs_range %d) run on the generic kernel; the line "
-                              "%s in madrl_amd/csrc/pursuit_live_specializations.def (and a rebuild: `python -m madrl_amd.build "
-                              "--pursuit-live-crowd-shape %s`) gives them the crowd kernel"
-                              % (shape[2], shape[3], shape[0], shape[1], shape[4], lines[0].replace(" ", ""), " ".join(str(v) for v in shape)),
-                              stacklevel=3)
-            return
-        kind, _ = _build.pursuit_fast_path(*shape, include_id=bool(self.include_id))
-        if kind is None and self.train_pursuit and _build.pursuit_crowd_path(*shape, include_id=bool(self.include_id))[0] is not None:
-            import warnings   # more than 64 of a kind: only the crowd kernel can take the shape
-            BatchedPursuitEvade._hinted.add(shape)
-            warnings.warn("PursuitEvade %dx%d, %d v %d, obs_range %d runs on the generic kernel; `python -m madrl_amd.build --pursuit-crowd-shape "
-                          "%s` compiles the crowd kernel for this shape (results are identical, a step takes less time)"
-                          % (shape[0], shape[1], shape[2], shape[3], shape[4], " ".join(str(v) for v in shape)), stacklevel=3)
-            return
-        if kind is not None:
+                msg = ("PursuitEvade per-env agent counts at capacity %d v %d (%dx%d, obs_range %d) run on the generic kernel; the line "
+                       "%s in madrl_amd/csrc/pursuit_live_specializations.def (and a rebuild: `python -m madrl_amd.build "
+                       "--pursuit-live-shape %s`) gives them the %s kernel"
+                       % (P, E, xs, ys, R, lines[0].replace(" ", ""), args, "one-wavefront" if lines[0].startswith("XL(") else "multi-wavefront"))
+            elif crowd is not None:
+                msg = ("PursuitEvade per-env agent counts at capacity %d v %d (%dx%d, obs_range %d) run on the generic kernel; the line "
+                       "%s in madrl_amd/csrc/pursuit_live_specializations.def (and a rebuild: `python -m madrl_amd.build "
+                       "--pursuit-live-crowd-shape %s`) gives them the crowd kernel" % (P, E, xs, ys, R, crowd[0].replace(" ", ""), args))
+        elif _build.pursuit_fast_path(*shape, include_id=inc)[0] is not None:
+            msg = ("PursuitEvade %dx%d, %d v %d, obs_range %d runs on the generic kernel; `python -m madrl_amd.build --pursuit-shape %s` "
+                   "compiles the specialised kernel for this shape (results are identical, a step takes about half the time)" % (xs, ys, P, E, R, args))
+        elif self.train_pursuit and _build.pursuit_crowd_path(*shape, include_id=inc)[0] is not None:   # more than 64 of a kind
+            msg = ("PursuitEvade %dx%d, %d v %d, obs_range %d runs on the generic kernel; `python -m madrl_amd.build --pursuit-crowd-shape "
+                   "%s` compiles the crowd kernel for this shape (results are identical, a step takes less time)" % (xs, ys, P, E, R, args))
+        if msg is not None:
             import warnings
             BatchedPursuitEvade._hinted.add(shape)
-            warnings.warn("PursuitEvade %dx%d, %d v %d, obs_range %d runs on the generic kernel; `python -m madrl_amd.build --pursuit-shape %s` "
-                          "compiles the specialised kernel for this shape (results are identical, a step takes about half the time)"
-                          % (shape[0], shape[1], shape[2], shape[3], shape[4], " ".join(str(v) for v in shape)), stacklevel=3)
+            warnings.warn(msg, stacklevel=3)
 
     def set_kernel(self, kind):
         """'auto' | 'generic' | 'wave'.  'wave' is the compile-time specialised kernel of the shape: one wavefront per env, a group of

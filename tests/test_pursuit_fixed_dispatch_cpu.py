@@ -1,6 +1,6 @@
 """CPU test (-m "not gpu"): which step launches take the Pursuit kernel with its launch constants folded in (pw::FShape, the XF lines of
 csrc/pursuit_fixed_specializations.def).  madrl_pursuit_fixed_choice is the host's own decision -- launch() in pursuit.hip calls the same
-two functions (find_fixed, fixed_contract) -- answered without a device: every XF line in the contract's form takes the fixed kernel,
+function (takes_fixed: the line's XF kernel, fixed_contract) -- answered without a device: every XF line in the contract's form takes the fixed kernel,
 and each clause of the contract flipped ALONE sends the launch to the plain kernel of the line."""
 import ctypes as C
 import os
