@@ -10,8 +10,9 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def bits(t):
-    """a float32 tensor as int32: a comparison in every bit, which also holds for NaN and tells -0.0 from +0.0"""
-    t = t.contiguous()
+    """a float32 tensor (or numpy array, which an oracle returns: as a CPU tensor) as int32: a comparison in every bit, which also holds
+    for NaN and tells -0.0 from +0.0"""
+    t = (t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))).contiguous()
     return t.view(torch.int32) if t.dtype == torch.float32 else t
 
 

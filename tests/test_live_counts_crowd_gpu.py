@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from live_pursuit import assert_live_equals_fixed, assert_pending_counts_history, counts_tensor
-from test_pursuit_crowd_gpu import CNN, SURROUND_24, FREE_RUNS, _maps
+from pursuit_cases import CNN, FREE_RUNS, SURROUND_24, named_maps as _maps
 
 pytestmark = pytest.mark.gpu
 

@@ -6,37 +6,16 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import pursuit_golden_files, golden_id
+from pursuit_cases import CNN, FREE_RUNS, SURROUND_24, golden as _golden, named_maps as _maps
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-CNN = dict(n_pursuers=100, n_evaders=300, obs_range=21, n_catch=2, surround=True, flatten=False, reward_mech="local")
 
 
 def _mk(maps, n_envs, **kw):
     from madrl_amd.pursuit import BatchedPursuitEvade
     return BatchedPursuitEvade(maps, n_envs=n_envs, device=DEV, **kw)
-
-
-def _golden(name):
-    files = pursuit_golden_files()
-    return np.load(files[[golden_id(p) for p in files].index(name)])
-
-
-def _maps(name):
-    from madrl_amd.maps import rectangle_map, resize
-    if name == "rect128":
-        return [rectangle_map(128, 128)]
-    if name == "pool128":   # ten 128 x 128 maps: resize(8, map_pool16) -- the authors' map_pool128.npy is not in their tree
-        return list(resize(8, _golden("pursuit_pool16_sample_maps")["maps"]))
-    if name == "rect48":
-        return [rectangle_map(48, 48)]
-    if name == "open24":
-        return [np.zeros((24, 24), np.int32)]
-    if name == "open20":
-        return [np.zeros((20, 20), np.int32)]
-    raise KeyError(name)
 
 
 STATE_KEYS = ("pos_p", "pos_e", "gone", "term_p", "term_e", "map_id", "tick", "t")
@@ -85,20 +64,6 @@ def test_crowd_kernel_replays_the_reference_goldens(name):
                 assert np.array_equal(st["pos_p"][n].cpu().numpy(), g["pos_p"][t]), tag + ": pursuer positions"
                 assert np.array_equal(st["pos_e"][n].cpu().numpy(), g["pos_e"][t]), tag + ": evader positions"
                 assert np.array_equal(st["gone"][n].cpu().numpy(), g["gone_e"][t]), tag + ": evaders_gone"
-
-
-SURROUND_24 = dict(n_pursuers=20, n_evaders=300, obs_range=9, n_catch=2, surround=True, flatten=True, reward_mech="local")
-FREE_RUNS = {
-    # name: (maps, config, envs, steps, max_steps, removed > 0, episodes ended by catches > 0)
-    "cnn_rect128": ("rect128", CNN, 64, 60, 25, False, False),       # random pursuers surround nobody on 128 x 128: rows, moves, resets
-    "cnn_pool128_sample_maps": ("pool128", dict(CNN, sample_maps=True), 64, 60, 25, False, False),
-    "cnn_rows_48x48": ("rect48", CNN, 64, 60, 25, True, False),
-    "surround_20v300": ("open24", SURROUND_24, 128, 60, 25, True, False),
-    "colocate_global_260v40": ("open20", dict(n_pursuers=260, n_evaders=40, obs_range=5, n_catch=2, surround=False, flatten=True,
-                                              reward_mech="global", catchr=0.1, urgency_reward=-0.05), 128, 120, 100, True, True),
-    "surround_20v300_random_opponents": ("open24", dict(SURROUND_24, random_opponents=True, max_opponents=250), 128, 60, 25, True, False),
-    "cnn_rows_48x48_constraint_window": ("rect48", dict(CNN, constraint_window=0.5), 64, 60, 25, True, False),
-}
 
 
 @pytest.mark.parametrize("case", sorted(FREE_RUNS), ids=sorted(FREE_RUNS))

@@ -9,180 +9,62 @@ All slots of a ring are carved from ONE tensor with guard bands of 4 KiB between
 and checked after every step: a store past the end of a slot -- a float32-sized address in the half kernel -- fails a test here instead of
 faulting.  Slots and the envs' first buffers are pre-filled with 7.0 (exact in binary16), so every kept cell is visible."""
 import ctypes as C
+import functools
 import pickle
 
-import numpy as np
 import pytest
 import torch
 
+from step_to_twins import DEV, F16, F32, Case, HalfTwins, agents, b16, make_env, prefill, rollout_env, same16
+from step_to_twins import nonzero_count_policy as _policy
+
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-GUARD, GUARD_BYTE = 4096, 0xA5
-F16, F32 = torch.float16, torch.float32
-
-
-def _maps(xs, ys):
-    from madrl_amd.maps import rectangle_map
-    return [rectangle_map(xs, ys)] if min(xs, ys) >= 16 else [np.zeros((xs, ys), np.int32)]
-
-
-def _shape(xs, ys, p, e, r, fl, **kw):
-    return dict(map=(xs, ys), n_pursuers=p, n_evaders=e, obs_range=r, flatten=bool(fl), **kw)
-
-
-def _mk(cfg, n, seed=21, max_steps=3, max_blocks=2, **kw):
-    from madrl_amd.pursuit import BatchedPursuitEvade
-    cfg = dict(cfg)
-    xs, ys = cfg.pop("map")
-    env = BatchedPursuitEvade(_maps(xs, ys), n_envs=n, device=DEV, seed=seed, max_steps=max_steps, auto_reset=True, **dict(cfg, **kw))
-    env.set_launch(max_blocks=max_blocks)   # a workgroup (wavefront) walks several envs
-    return env
-
-
-def _b16(t):
-    return t.contiguous().view(torch.int16)
-
-
-def _as_half_bits(t):
-    """the bits the half twin must hold where the float32 twin holds t"""
-    return _b16(t.to(F16)) if t.dtype is F32 else _b16(t)
-
-
-def _same16(half, ref):
-    assert half.dtype is F16
-    return torch.equal(_b16(half).reshape(-1), _as_half_bits(ref).reshape(-1))
-
-
-class Ring(object):
-    """n slots of `shape` carved from one byte tensor: [guard][slot 0][guard][slot 1] ... [guard]"""
-
-    def __init__(self, shape, dtype, n=3):
-        nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        stride = (nbytes + 15) // 16 * 16 + GUARD
-        self.raw = torch.full((GUARD + n * stride,), GUARD_BYTE, dtype=torch.uint8, device=DEV)
-        self.is_guard = torch.ones(self.raw.numel(), dtype=torch.bool, device=DEV)
-        self.slots = []
-        for k in range(n):
-            off = GUARD + k * stride
-            self.slots.append(self.raw[off:off + nbytes].view(dtype).view(shape))
-            self.is_guard[off:off + nbytes] = False
-            assert self.slots[-1].data_ptr() % 16 == 0
-        for s in self.slots:
-            s.fill_(7.0)
-
-    def intact(self):
-        return bool((self.raw[self.is_guard] == GUARD_BYTE).all())
-
-
-class Twins(object):
-    """`f`: the float32 twin and its ring; `h`: the half env and its ring"""
-
-    def __init__(self, cfg, n, counts=None, seed=21, **kw):
-        self.n = n
-        self.f, self.h = _mk(cfg, n, seed=seed, **kw), _mk(cfg, n, seed=seed, obs_dtype=F16, **kw)
-        assert self.f.obs_buffer.dtype is F32 and self.h.obs_buffer.dtype is F16
-        self.P = int(self.f.n_pursuers)
-        for e in (self.f, self.h):
-            e.obs_buffer.fill_(7.0)
-            e.invalidate_obs()
-            if counts is not None:
-                c = torch.tensor(counts, dtype=torch.int32, device=DEV)
-                e.set_agent_counts(c[:, 0], c[:, 1])
-        shape = tuple(self.f.obs_buffer.shape)
-        self.fr, self.hr = Ring(shape, F32), Ring(shape, F16)
-        self.at = 0
-        self.gen = torch.Generator(device="cpu").manual_seed(5)
-        a, b = self.f.reset(), self.h.reset()
-        assert b.dtype is F16 and b.shape == a.shape
-        assert _same16(b, a), "reset() of the half env is not the float32 twin's reset .to(float16)"
-        self.sevens_at_start = int((self.h.obs_buffer == 7.0).sum())
-        self.rne_differs = False   # an element whose round-to-nearest-even and truncated halves differ was seen
-        self.dones = 0
-
-    def actions(self):
-        return torch.randint(0, 5, (self.n, self.P), generator=self.gen).to(torch.int32).to(DEV)
-
-    def hop(self, what, act=None):
-        act = self.actions() if act is None else act
-        k = self.at
-        prev = self.h.obs_buffer
-        prev_before = prev.clone()
-        (fo, frew, fdone, finfo), (ho, hrew, hdone, hinfo) = self.f.step_to(act, self.fr.slots[k]), self.h.step_to(act, self.hr.slots[k])
-        torch.cuda.synchronize()
-        assert self.hr.intact() and self.fr.intact(), (what, "a guard band was written")
-        assert ho.dtype is F16 and ho.shape == fo.shape and ho.data_ptr() == self.hr.slots[k].data_ptr() == self.h.obs_buffer.data_ptr()
-        fs, hs = self.fr.slots[k], self.hr.slots[k]
-        assert _same16(hs, fs), (what, "slot", int((_b16(hs) != _as_half_bits(fs)).sum()))
-        assert torch.equal(frew.view(torch.int32), hrew.view(torch.int32)), (what, "rewards")
-        assert torch.equal(fdone, hdone), (what, "done")
-        for key in ("done_bits", "removed", "truncated", "count_overflow"):
-            assert torch.equal(finfo[key], hinfo[key]), (what, key)
-        assert torch.equal(_b16(prev), _b16(prev_before)), (what, "obs_prev was written")
-        # positive float32 values whose half was rounded UP: truncation would have given the half below
-        self.rne_differs = self.rne_differs or bool((hs.to(F32) > fs).any())
-        self.dones += int((finfo["done_bits"] != 0).sum())
-        self.at = (k + 1) % 3
-        return hs
-
-    def finish(self):
-        a, b = self.f.get_state(), self.h.get_state()
-        for key in a:
-            assert torch.equal(a[key], b[key]), key
-        left = int((self.h.obs_buffer == 7.0).sum())
-        assert left > 0, "no kept cell still reads 7.0"
-        assert left < self.sevens_at_start, "every cell that read 7.0 after the reset still does: no kept cell was ever stored"
-
-
-# name: (configuration, envs, env kwargs, per-env counts, steps, kernel kind).  The steps (and seeds) are few enough that some never-stored
-# cell is left at the end: on a 3 x 3 window every cell has been inside the map once after a handful of steps and resets.
+X_2V2 = Case("rect16", (10, 10), agents(2, 2, 3, 1), None, {})
+X_8V30 = Case("rect16", (16, 16), agents(8, 30, 7, 1), None, {})
+X_8V30_SURROUND = Case("rect16", (16, 16), agents(8, 30, 7, 1, surround=True, n_catch=2), None, {})
+# Every case: seed 21 unless it names one, max_steps 3, two workgroups (make_env's defaults).  The steps (and seeds) are few enough that
+# some never-stored cell is left at the end: on a 3 x 3 window every cell has been inside the map once after a handful of steps and resets.
 COUNTS = [(8, 30), (7, 29), (3, 5), (1, 1)]
 RING_CASES = {
-    "X_smallest": (_shape(10, 10, 2, 2, 3, 1), 5, dict(seed=23), None, 5, "wave"),
-    "X_window_wider_than_map": (_shape(6, 6, 3, 5, 11, 0), 5, {}, None, 12, "wave"),
-    "XL_live_counts": (_shape(16, 16, 8, 30, 7, 1), 8, dict(per_env_counts=True), [COUNTS[i % 4] for i in range(8)], 12, "wave"),
-    "generic_evader_control": (_shape(16, 16, 8, 12, 7, 1, train_pursuit=False), 5, {}, None, 8, "generic"),
-    "generic_2_byte_path": (_shape(12, 12, 3, 4, 4, 1), 5, {}, None, 12, "generic"),
-    "XG_runs_generic": (_shape(32, 32, 16, 60, 7, 1), 4, {}, None, 8, "generic"),
-    "XC_runs_generic": (_shape(24, 24, 20, 300, 9, 1, surround=True, n_catch=2), 4, {}, None, 8, "generic"),
-    "X_subnormal_values": (_shape(10, 10, 2, 2, 3, 1, layer_norm=30000.0), 5, dict(seed=23), None, 5, "wave"),
+    "X_smallest": X_2V2._replace(twin=dict(seed=23), n=5, steps=5, kind="wave"),
+    "X_window_wider_than_map": Case("rect16", (6, 6), agents(3, 5, 11, 0), None, {}, n=5, steps=12, kind="wave"),
+    "XL_live_counts": Case("rect16", (16, 16), agents(8, 30, 7, 1, per_env_counts=True), [COUNTS[i % 4] for i in range(8)], {},
+                           n=8, steps=12, kind="wave"),
+    "generic_evader_control": Case("rect16", (16, 16), agents(8, 12, 7, 1, train_pursuit=False), None, {}, n=5, steps=8, kind="generic"),
+    "generic_2_byte_path": Case("rect16", (12, 12), agents(3, 4, 4, 1), None, {}, n=5, steps=12, kind="generic"),
+    "XG_runs_generic": Case("rect16", (32, 32), agents(16, 60, 7, 1), None, {}, n=4, steps=8, kind="generic"),
+    "XC_runs_generic": Case("rect16", (24, 24), agents(20, 300, 9, 1, surround=True, n_catch=2), None, {}, n=4, steps=8, kind="generic"),
+    "X_subnormal_values": Case("rect16", (10, 10), agents(2, 2, 3, 1, layer_norm=30000.0), None, dict(seed=23), n=5, steps=5, kind="wave"),
 }
 
 
 @pytest.mark.parametrize("name", sorted(RING_CASES))
 def test_half_ring_equals_the_float32_ring(name):
-    cfg, n, kw, counts, steps, kind = RING_CASES[name]
-    tw = Twins(cfg, n, counts=counts, **kw)
-    assert tw.h.step_to_kernel_kind == kind
+    case = RING_CASES[name]
+    tw = HalfTwins(case)
+    assert tw.h.step_to_kernel_kind == case.kind
     if name in ("XG_runs_generic", "XC_runs_generic"):
         assert tw.f.step_to_kernel_kind == "wave"   # (the float32 form of the same handle has its fast kernel)
-    for k in range(steps):
-        if counts is not None and k == steps // 2:   # other pending counts, taken at each env's next fused reset
-            c = torch.tensor(counts[::-1], dtype=torch.int32, device=DEV)
-            for e in (tw.f, tw.h):
-                e.set_agent_counts(c[:, 0], c[:, 1])
-        tw.hop((name, k))
-    assert tw.dones >= n, "max_steps=3: every env ended an episode, the second pass of a fused auto-reset ran"
-    if counts is not None:
-        assert not torch.equal(tw.h.agent_counts()[1].cpu(), torch.tensor(counts, dtype=torch.int32)), "the changed counts were never taken"
+    tw.run(case.steps)   # (half way: other pending counts, taken at each env's next fused reset)
     if name == "X_subnormal_values":
-        sub = _b16(tw.h.obs_buffer).to(torch.int32) & 0xFFFF
+        sub = b16(tw.h.obs_buffer).to(torch.int32) & 0xFFFF
         assert bool(((sub > 0) & (sub < 0x0400)).any()), "1 / 30000 is subnormal in binary16: none seen"
-    tw.finish()
+    tw.finish()   # (max_steps=3: every env ended an episode; the changed counts were taken)
 
 
 def test_consecutive_envs_of_a_wavefront_and_round_to_nearest_even():
     """X(16,16,8,30,7,1): 130 envs on 3 workgroups, auto_reset with max_steps=12, 40 steps -- a wavefront's consecutive envs, the second
     pass of a fused auto-reset on the half buffer, and elements whose round-to-nearest-even and truncated halves differ (three agents on a
     cell at layer_norm 10: 0.3f is 0x34CD in binary16, the packed round-toward-zero conversion gives 0x34CC)"""
-    assert _b16(torch.tensor([0.3], dtype=F32).to(F16)).item() == 0x34CD
-    tw = Twins(_shape(16, 16, 8, 30, 7, 1, surround=True, n_catch=2), 130, max_steps=12, max_blocks=3)
+    assert b16(torch.tensor([0.3], dtype=F32).to(F16)).item() == 0x34CD
+    tw = HalfTwins(X_8V30_SURROUND, n=130, max_steps=12, max_blocks=3)
     assert tw.h.step_to_kernel_kind == "wave"
     saw_03 = False
     for k in range(40):
         hs = tw.hop(k)
-        saw_03 = saw_03 or bool((_b16(hs) == 0x34CD).any())
-    assert tw.dones >= 2 * 130
+        saw_03 = saw_03 or bool((b16(hs) == 0x34CD).any())
+    assert int(tw.dones.sum()) >= 2 * 130
     assert tw.rne_differs, "no element whose round-to-nearest-even and truncated halves differ occurred"
     assert saw_03, "0.3 (three agents on a cell) never occurred"
     tw.finish()
@@ -192,30 +74,29 @@ def test_step_ping_pong_in_place_edit_and_pickle():
     """step() of a half env ping-pongs between two internal buffers and gives what the ring gives; an in-place edit of the returned tensor
     (to a value exact in binary16) is noticed and persists in the kept cells as on a float32 twin that steps in place; a pickle keeps
     the dtype"""
-    cfg = _shape(6, 6, 3, 5, 11, 0)   # every row has kept cells
-    tw = Twins(cfg, 5)
-    pp, ip = _mk(cfg, 5, obs_dtype=F16), _mk(cfg, 5)   # half step() / float32 step() in place
+    case = RING_CASES["X_window_wider_than_map"]   # every row has kept cells
+    tw = HalfTwins(case)
+    pp, ip = make_env(case, F16, n=5), make_env(case, n=5)   # half step() / float32 step() in place
     for e in (pp, ip):
-        e.obs_buffer.fill_(7.0)
-        e.invalidate_obs()
+        prefill(e)
         e.reset()
     seen = set()
     for k in range(6):
-        act = tw.actions()
+        act = tw.actions()[0]
         hs = tw.hop(k, act)
         o = pp.step(act)[0]
         assert o.dtype is F16 and o.shape == (5, 3, 11, 11, 4) and o.data_ptr() == pp.obs_buffer.data_ptr()
-        assert torch.equal(_b16(o).reshape(-1), _b16(hs).reshape(-1)), k
-        assert _same16(o, ip.step(act)[0]), k
+        assert torch.equal(b16(o).reshape(-1), b16(hs).reshape(-1)), k
+        assert same16(o, ip.step(act)[0]), k
         seen.add(o.data_ptr())
     assert len(seen) == 2
     for k in range(4):   # the edit: every element 5.0, through the returned tensors
-        act = tw.actions()
+        act = tw.actions()[0]
         if k == 0:
             pp.obs_buffer.view(-1)[:] = 5.0
             ip.obs_buffer.view(-1)[:] = 5.0
         o, r = pp.step(act)[0], ip.step(act)[0]
-        assert _same16(o, r), ("after the edit", k)
+        assert same16(o, r), ("after the edit", k)
         assert bool((o == 5.0).any()) and not bool((o == 5.0).all())
     clone = pickle.loads(pickle.dumps(pp))
     assert clone.obs_dtype is F16 and clone.reset().dtype is F16 and clone.step_to_kernel_kind == "wave"
@@ -223,8 +104,7 @@ def test_step_ping_pong_in_place_edit_and_pickle():
 
 
 def test_mismatched_destination_dtypes_raise():
-    cfg = _shape(10, 10, 2, 2, 3, 1)
-    h, f = _mk(cfg, 5, obs_dtype=F16), _mk(cfg, 5)
+    h, f = make_env(X_2V2, F16, n=5), make_env(X_2V2, n=5)
     h.reset(), f.reset()
     act = torch.zeros((5, 2), dtype=torch.int32, device=DEV)
     shape = tuple(f.obs_buffer.shape)
@@ -238,15 +118,14 @@ def test_mismatched_destination_dtypes_raise():
     with pytest.raises(ValueError):   # there is no in-place half step
         h.step_to(act, h.obs_buffer)
     o = h.step_into(act, rew, dn, obs_out=torch.zeros(shape, dtype=F16, device=DEV))
-    assert o.dtype is F16 and _same16(o, f.step_into(act, rew, dn, obs_out=torch.zeros(shape, dtype=F32, device=DEV)))
+    assert o.dtype is F16 and same16(o, f.step_into(act, rew, dn, obs_out=torch.zeros(shape, dtype=F32, device=DEV)))
 
 
 def test_c_abi_argument_checks_and_format_switch():
     from madrl_amd import _lib
     L = _lib.lib()
-    cfg = _shape(16, 16, 8, 30, 7, 1)
     N, P = 6, 8
-    e1 = _mk(cfg, N, max_steps=0)
+    e1 = make_env(X_8V30, n=N, max_steps=0)
     D = e1.obs_dim
     n = N * P * D
     e1.reset()
@@ -281,7 +160,7 @@ def test_c_abi_argument_checks_and_format_switch():
     got, want = torch.zeros(n, dtype=F32, device=DEV), torch.zeros(n, dtype=F32, device=DEV)
     g_rew, w_rew = torch.zeros_like(rew), torch.zeros_like(rew)
     _lib.check(L.madrl_pursuit_step_to(e1._handle, p(act), None, p(as_f32), p(got), p(g_rew), p(dn), p(rem), stream))
-    e2 = _mk(cfg, N, max_steps=0)
+    e2 = make_env(X_8V30, n=N, max_steps=0)
     e2.reset()
     e2.set_state(st)
     _lib.check(L.madrl_pursuit_step_to(e2._handle, p(act), None, p(as_f32.clone()), p(want), p(w_rew), p(dn), p(rem), stream))
@@ -294,13 +173,7 @@ def test_c_abi_argument_checks_and_format_switch():
 T, NR = 6, 32
 
 
-def _rollout_env(**kw):
-    return _mk(_shape(16, 16, 8, 30, 7, 1, surround=True, n_catch=2), NR, seed=9, max_steps=5, max_blocks=0, **kw)
-
-
-def _policy(obs):
-    """depends only on which cells are non-zero: the count of non-zero cells of a row mod 5"""
-    return ((obs != 0).sum(dim=-1) % 5).to(torch.int32)
+_rollout_env = functools.partial(rollout_env, X_8V30_SURROUND, n=NR, max_steps=5)
 
 
 def test_rollout_collector_keeps_half_slots():
@@ -315,8 +188,8 @@ def test_rollout_collector_keeps_half_slots():
         for tr in (b, c):
             assert tr.observations.dtype is F16 and tr.last_observation.dtype is F16
             assert tr.observations.shape == a.observations.shape
-            assert _same16(tr.observations, a.observations), it
-            assert _same16(tr.last_observation, a.last_observation), it
+            assert same16(tr.observations, a.observations), it
+            assert same16(tr.last_observation, a.last_observation), it
             for key in ("actions", "rewards", "dones", "returns"):
                 x, y = getattr(a, key), getattr(tr, key)
                 assert x.dtype == y.dtype and torch.equal(x.view(torch.uint8), y.view(torch.uint8)), (it, key)
@@ -347,14 +220,13 @@ def test_stream_sharded_half_envs_step_one_by_one():
     from madrl_amd.sharded import StreamSharded
 
     def make(dtype):
-        return lambda n_envs, env_id_base, device: _mk(_shape(16, 16, 8, 30, 7, 1, surround=True, n_catch=2), n_envs, seed=9, max_steps=5,
-                                                       max_blocks=0, env_id_base=env_id_base, obs_dtype=dtype)
+        return lambda n_envs, env_id_base, device: rollout_env(X_8V30_SURROUND, dtype, n=n_envs, max_steps=5, env_id_base=env_id_base)
 
     f, h = StreamSharded(make(F32), NR, n_streams=2, device=DEV), StreamSharded(make(F16), NR, n_streams=2, device=DEV)
     assert f._native_pursuit() and not h._native_pursuit()
     cat = lambda parts: torch.cat(list(parts), dim=0)
     a, b = cat(f.reset()), cat(h.reset())
-    assert b.dtype is F16 and _same16(b, a)
+    assert b.dtype is F16 and same16(b, a)
     gen = torch.Generator(device="cpu").manual_seed(5)
     for k in range(7):
         act = torch.randint(0, 5, (NR, 8), generator=gen).to(torch.int32).to(DEV)
@@ -362,7 +234,7 @@ def test_stream_sharded_half_envs_step_one_by_one():
         torch.cuda.synchronize()
         assert h._nat is None, "the half batch took the one-call float32 path"
         oa, ob = cat([r[0] for r in ra]), cat([r[0] for r in rb])   # (one (obs, rew, done, info) per sub-batch)
-        assert ob.dtype is F16 and _same16(ob, oa), k
+        assert ob.dtype is F16 and same16(ob, oa), k
         assert torch.equal(cat([r[1] for r in ra]).view(torch.int32), cat([r[1] for r in rb]).view(torch.int32)), k
     fc = ShardedRolloutCollector(StreamSharded(make(F32), NR, n_streams=2, device=DEV), [_policy, _policy], T, store_observations=True)
     hc = ShardedRolloutCollector(StreamSharded(make(F16), NR, n_streams=2, device=DEV), [_policy, _policy], T, store_observations=True)
@@ -370,5 +242,5 @@ def test_stream_sharded_half_envs_step_one_by_one():
         pa, pb = fc.collect(), hc.collect()
         torch.cuda.synchronize()
         for x, y in zip(pa, pb):
-            assert y.observations.dtype is F16 and _same16(y.observations, x.observations), it
+            assert y.observations.dtype is F16 and same16(y.observations, x.observations), it
             assert torch.equal(x.actions, y.actions) and torch.equal(x.rewards.view(torch.int32), y.rewards.view(torch.int32)), it

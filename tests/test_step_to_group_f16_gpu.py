@@ -2,36 +2,23 @@
 of a handle on an HG / HLG line of csrc/pursuit_to_f16_group_specializations.def (pursuit_group_kernel over a THGShape / TLHGShape,
 pursuit_group.hpp).
 
-The yardstick is that of tests/test_step_to_f16_gpu.py, whose Ring and bit comparisons are used here: a float32 twin with the same seed
-steps through a float32 ring of three, the half env through a half ring of three; after every hop the half slot equals the float32
-slot's `.to(torch.float16)` in every bit, and rewards, done bits, removed counts and, at the end, the state records are equal.  All slots
+The yardstick is that of tests/test_step_to_f16_gpu.py, over the same harness (tests/step_to_twins.py: HalfTwins, Ring): a float32 twin
+with the same seed steps through a float32 ring of three, the half env through a half ring of three; after every hop the half slot
+equals the float32 slot's `.to(torch.float16)` in every bit, and rewards, done bits, removed counts and, at the end, the state records are equal.  All slots
 of a ring are carved from one tensor with 4 KiB guard bands, filled with a byte no result holds and checked after every hop; slots and
 first buffers are pre-filled with 7.0.  Every case asserts that the half env reports its fast kernel: before the half group kernels
 existed these handles ran the half step on the generic kernel."""
 import ctypes as C
 
-import numpy as np
 import pytest
 import torch
 
-from test_step_to_f16_gpu import DEV, F16, F32, Ring, _as_half_bits, _b16, _same16
+from step_to_twins import DEV, F16, F32, Case, HalfTwins, Ring, b16, make_env, prefill, rollout_env
+from step_to_twins import nonzero_count_policy as _policy
 
 pytestmark = pytest.mark.gpu
 
 N_ENVS, HOPS = 7, 12
-
-
-def _corridors(xs, ys):
-    """rows 0 and xs - 1 free, everything between them built over: an agent never leaves its row, so the window cells beyond it stay
-    outside the map (kept cells that survive every step and reset), and three agents on a cell are common"""
-    m = np.full((xs, ys), -1, dtype=np.int32)
-    m[0, :] = m[xs - 1, :] = 0
-    return m
-
-
-def _maps(kind, xs, ys):
-    from madrl_amd.maps import rectangle_map, synthetic_map_pool
-    return {"pool": lambda: synthetic_map_pool(3, xs, ys), "rect": lambda: [rectangle_map(xs, ys)], "corridors": lambda: [_corridors(xs, ys)]}[kind]()
 
 
 def _counts(p, e):
@@ -40,26 +27,25 @@ def _counts(p, e):
 
 AUTHORS = dict(obs_range=11, flatten=True, surround=True, sample_maps=True)
 LONG = dict(flatten=True, surround=False, n_catch=2)
-# name: (maps, map size, env kwargs, per-env counts or None, twin kwargs)
 CASES = {
-    "HG_authors_30v50": ("pool", (32, 32), dict(n_pursuers=30, n_evaders=50, **AUTHORS), None, {}),
-    "HG_authors_30v50_global": ("pool", (32, 32), dict(n_pursuers=30, n_evaders=50, reward_mech="global", **AUTHORS), None, {}),
-    "HG_authors_30v30": ("pool", (32, 32), dict(n_pursuers=30, n_evaders=30, **AUTHORS), None, {}),
-    "HG_authors_30v30_one_env_per_workgroup": ("pool", (32, 32), dict(n_pursuers=30, n_evaders=30, **AUTHORS), None, dict(max_blocks=None)),
-    "HLG_authors_30v50": ("pool", (32, 32), dict(n_pursuers=30, n_evaders=50, per_env_counts=True, **AUTHORS), _counts(30, 50), {}),
-    "HLG_authors_30v30": ("pool", (32, 32), dict(n_pursuers=30, n_evaders=30, per_env_counts=True, **AUTHORS), _counts(30, 30), {}),
-    "HLG_20v50": ("rect", (16, 16), dict(n_pursuers=20, n_evaders=50, obs_range=5, flatten=True, per_env_counts=True), _counts(20, 50), {}),
-    "HLG_20v50_global": ("rect", (16, 16), dict(n_pursuers=20, n_evaders=50, obs_range=5, flatten=True, per_env_counts=True,
+    "HG_authors_30v50": Case("pool", (32, 32), dict(n_pursuers=30, n_evaders=50, **AUTHORS), None, {}),
+    "HG_authors_30v50_global": Case("pool", (32, 32), dict(n_pursuers=30, n_evaders=50, reward_mech="global", **AUTHORS), None, {}),
+    "HG_authors_30v30": Case("pool", (32, 32), dict(n_pursuers=30, n_evaders=30, **AUTHORS), None, {}),
+    "HG_authors_30v30_one_env_per_workgroup": Case("pool", (32, 32), dict(n_pursuers=30, n_evaders=30, **AUTHORS), None, dict(max_blocks=None)),
+    "HLG_authors_30v50": Case("pool", (32, 32), dict(n_pursuers=30, n_evaders=50, per_env_counts=True, **AUTHORS), _counts(30, 50), {}),
+    "HLG_authors_30v30": Case("pool", (32, 32), dict(n_pursuers=30, n_evaders=30, per_env_counts=True, **AUTHORS), _counts(30, 30), {}),
+    "HLG_20v50": Case("rect", (16, 16), dict(n_pursuers=20, n_evaders=50, obs_range=5, flatten=True, per_env_counts=True), _counts(20, 50), {}),
+    "HLG_20v50_global": Case("rect", (16, 16), dict(n_pursuers=20, n_evaders=50, obs_range=5, flatten=True, per_env_counts=True,
                                                 reward_mech="global"), _counts(20, 50), {}),
     # the register path, fixed shape: 448 slots on 128 threads, the last slot valid in half of them
-    "HG_register_path_64v40": ("corridors", (16, 16), dict(n_pursuers=64, n_evaders=40, obs_range=3, **LONG), None, dict(rne=True)),
+    "HG_register_path_64v40": Case("corridors", (16, 16), dict(n_pursuers=64, n_evaders=40, obs_range=3, **LONG), None, dict(rne=True)),
     # long rows past the authors' two mask words: a mask word of 5 slots (a remainder batch of 1), one of 7 (a remainder batch of 3), and
     # the limit: 32 slots, four mask words, 64 pursuers (and the global reward over them)
-    "HG_13_slots_36v12": ("rect", (10, 10), dict(n_pursuers=36, n_evaders=12, obs_range=11, **LONG), None, {}),
-    "HG_23_slots_46v10": ("rect", (12, 12), dict(n_pursuers=46, n_evaders=10, obs_range=13, **LONG), None, {}),
-    "HG_32_slots_64v20": ("rect", (12, 12), dict(n_pursuers=64, n_evaders=20, obs_range=13, reward_mech="global", **LONG), None, {}),
-    "HG_36v12_evader_actions": ("rect", (10, 10), dict(n_pursuers=36, n_evaders=12, obs_range=11, **LONG), None, dict(evader_actions=True)),
-    "HG_36v12_subnormal_values": ("rect", (10, 10), dict(n_pursuers=36, n_evaders=12, obs_range=11, layer_norm=30000.0, **LONG), None,
+    "HG_13_slots_36v12": Case("rect", (10, 10), dict(n_pursuers=36, n_evaders=12, obs_range=11, **LONG), None, {}),
+    "HG_23_slots_46v10": Case("rect", (12, 12), dict(n_pursuers=46, n_evaders=10, obs_range=13, **LONG), None, {}),
+    "HG_32_slots_64v20": Case("rect", (12, 12), dict(n_pursuers=64, n_evaders=20, obs_range=13, reward_mech="global", **LONG), None, {}),
+    "HG_36v12_evader_actions": Case("rect", (10, 10), dict(n_pursuers=36, n_evaders=12, obs_range=11, **LONG), None, dict(evader_actions=True)),
+    "HG_36v12_subnormal_values": Case("rect", (10, 10), dict(n_pursuers=36, n_evaders=12, obs_range=11, layer_norm=30000.0, **LONG), None,
                                   dict(subnormal=True)),
 }
 
@@ -72,126 +58,27 @@ CASES = {
 SEED = 1
 
 
-def _mk(name, obs_dtype=F32, n=N_ENVS, max_blocks=2, max_steps=3, seed=SEED):
-    from madrl_amd.pursuit import BatchedPursuitEvade
-    kind, (xs, ys), kw = CASES[name][:3]
-    env = BatchedPursuitEvade(_maps(kind, xs, ys), n_envs=n, device=DEV, seed=seed, max_steps=max_steps, auto_reset=True, obs_dtype=obs_dtype, **kw)
-    if max_blocks is not None:
-        env.set_launch(max_blocks=max_blocks)   # a workgroup walks several envs: the loop-carried state is exercised
-    return env
-
-
-def _prefill(env, counts=None):
-    env.obs_buffer.fill_(7.0)
-    env.invalidate_obs()
-    if counts is not None:
-        c = torch.tensor(counts, dtype=torch.int32, device=DEV)
-        env.set_agent_counts(c[:, 0], c[:, 1])
-
-
-class Twins(object):
-    """`f`: the float32 twin and its ring; `h`: the half env and its ring"""
-
-    def __init__(self, name, half_kernel=None):
-        self.counts = CASES[name][3]
-        tkw = dict(CASES[name][4])
-        self.with_eact = tkw.pop("evader_actions", False)
-        self.want_rne, self.want_subnormal = tkw.pop("rne", False), tkw.pop("subnormal", False)
-        self.f, self.h = _mk(name, **tkw), _mk(name, obs_dtype=F16, **tkw)
-        if half_kernel is not None:
-            self.h.set_kernel(half_kernel)
-        assert self.f.obs_buffer.dtype is F32 and self.h.obs_buffer.dtype is F16
-        self.P, self.E = int(self.f.n_pursuers), int(self.f.n_evaders)
-        for e in (self.f, self.h):
-            _prefill(e, self.counts)
-        shape = tuple(self.f.obs_buffer.shape)
-        self.fr, self.hr = Ring(shape, F32), Ring(shape, F16)
-        self.at = 0
-        self.gen = torch.Generator(device="cpu").manual_seed(5)
-        a, b = self.f.reset(), self.h.reset()
-        assert b.dtype is F16 and _same16(b, a), "reset() of the half env is not the float32 twin's reset .to(float16)"
-        self.sevens_at_start = int((self.h.obs_buffer == 7.0).sum())
-        assert self.sevens_at_start == int((self.f.obs_buffer == 7.0).sum())
-        self.rne_differs = self.subnormal = False
-        self.dones = torch.zeros(N_ENVS, dtype=torch.int64, device=DEV)
-
-    def actions(self):
-        act = torch.randint(0, 5, (N_ENVS, self.P), generator=self.gen).to(torch.int32).to(DEV)
-        eact = torch.randint(0, 5, (N_ENVS, self.E), generator=self.gen).to(torch.int32).to(DEV) if self.with_eact else None
-        return act, eact
-
-    def recount(self):
-        """other pending counts, taken at each env's next fused reset (the row count of an env changes between the two passes)"""
-        c = torch.tensor(self.counts[::-1], dtype=torch.int32, device=DEV)
-        for e in (self.f, self.h):
-            e.set_agent_counts(c[:, 0], c[:, 1])
-
-    def hop(self, what):
-        act, eact = self.actions()
-        k = self.at
-        prev = self.h.obs_buffer
-        prev_before = prev.clone()
-        fo, frew, fdone, finfo = self.f.step_to(act, self.fr.slots[k], evader_actions=eact)
-        ho, hrew, hdone, hinfo = self.h.step_to(act, self.hr.slots[k], evader_actions=eact)
-        torch.cuda.synchronize()
-        assert self.hr.intact() and self.fr.intact(), (what, "a guard band was written")
-        assert ho.dtype is F16 and ho.shape == fo.shape and ho.data_ptr() == self.hr.slots[k].data_ptr() == self.h.obs_buffer.data_ptr()
-        fs, hs = self.fr.slots[k], self.hr.slots[k]
-        assert _same16(hs, fs), (what, "slot", int((_b16(hs) != _as_half_bits(fs)).sum()))
-        assert torch.equal(frew.view(torch.int32), hrew.view(torch.int32)), (what, "rewards")
-        assert torch.equal(fdone, hdone), (what, "done")
-        for key in ("done_bits", "removed", "truncated", "count_overflow"):
-            assert torch.equal(finfo[key], hinfo[key]), (what, key)
-        assert torch.equal(_b16(prev), _b16(prev_before)), (what, "obs_prev was written")
-        # positive float32 values whose half was rounded UP: truncation would have given the half below
-        self.rne_differs = self.rne_differs or bool((hs.to(F32) > fs).any())
-        bits = _b16(hs).to(torch.int32) & 0xFFFF
-        self.subnormal = self.subnormal or bool(((bits > 0) & (bits < 0x0400)).any())
-        self.dones += (finfo["done_bits"] != 0).to(torch.int64)
-        self.at = (k + 1) % 3
-        self.last_rew = hrew
-        return hs
-
-    def run(self, hops=HOPS):
-        for k in range(hops):
-            if self.counts is not None and k == hops // 2:
-                self.recount()
-            self.hop(k)
-
-    def finish(self):
-        assert bool((self.dones >= 1).all()) and int(self.dones.sum()) >= N_ENVS, "max_steps=3: every env ended an episode, the second pass of a fused auto-reset ran"
-        a, b = self.f.get_state(), self.h.get_state()
-        for key in a:
-            assert torch.equal(a[key], b[key]), key
-        if self.counts is not None:
-            assert not torch.equal(self.h.agent_counts()[1].cpu(), torch.tensor(self.counts, dtype=torch.int32)), "the changed counts were never taken"
-        for env in (self.f, self.h):
-            left = int((env.obs_buffer == 7.0).sum())
-            assert left > 0, "no kept cell still reads 7.0"
-            assert left < self.sevens_at_start, "every cell that read 7.0 after the reset still does: no kept cell was ever stored"
-        if self.want_rne:
-            assert self.rne_differs, "no element whose round-to-nearest-even and truncated halves differ occurred"
-        if self.want_subnormal:
-            assert self.subnormal, "1 / 30000 is subnormal in binary16: none seen"
+def _twins(name, **kw):
+    return HalfTwins(CASES[name], n=N_ENVS, seed=SEED, **kw)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_half_group_ring_equals_the_float32_ring(name):
-    tw = Twins(name)
+    tw = _twins(name)
     assert tw.h.kernel_kind == "wave" and tw.h.step_to_kernel_kind == "wave"
-    tw.run()
+    tw.run(HOPS)
     tw.finish()
     assert tw.h.step_to_kernel_kind == "wave"
 
 
 def test_three_agents_on_a_cell_round_to_nearest_even():
     """0.3f (three agents on a cell at layer_norm 10) is 0x34CD in binary16; the packed round-toward-zero conversion gives 0x34CC"""
-    assert _b16(torch.tensor([0.3], dtype=F32).to(F16)).item() == 0x34CD
-    tw = Twins("HG_register_path_64v40")
+    assert b16(torch.tensor([0.3], dtype=F32).to(F16)).item() == 0x34CD
+    tw = _twins("HG_register_path_64v40")
     assert tw.h.step_to_kernel_kind == "wave"
     saw_03 = False
     for k in range(4):
-        saw_03 = saw_03 or bool((_b16(tw.hop(k)) == 0x34CD).any())
+        saw_03 = saw_03 or bool((b16(tw.hop(k)) == 0x34CD).any())
     assert saw_03, "0.3 (three agents on a cell) never occurred"
     assert tw.rne_differs
 
@@ -199,21 +86,21 @@ def test_three_agents_on_a_cell_round_to_nearest_even():
 def test_forced_generic_equals_the_half_group_kernel():
     """set_kernel('generic') keeps forcing the generic half kernel (what these handles ran before), with the same bits as the group kernel"""
     name = "HG_13_slots_36v12"
-    g = Twins(name, half_kernel="generic")
+    g = _twins(name, half_kernel="generic")
     assert g.h.step_to_kernel_kind == "generic" and g.h.kernel_kind == "generic"
-    w = _mk(name, obs_dtype=F16)
+    w = make_env(CASES[name], F16, n=N_ENVS, seed=SEED)
     assert w.step_to_kernel_kind == "wave"
-    _prefill(w)
+    prefill(w)
     ring = Ring(tuple(w.obs_buffer.shape), F16)
-    assert torch.equal(_b16(w.reset()), _b16(g.h.obs_buffer))
+    assert torch.equal(b16(w.reset()), b16(g.h.obs_buffer))
     gen = torch.Generator(device="cpu").manual_seed(5)
     for k in range(HOPS):
-        act = torch.randint(0, 5, (N_ENVS, g.P), generator=gen).to(torch.int32).to(DEV)   # (the draws Twins.actions makes)
+        act = torch.randint(0, 5, (N_ENVS, g.P), generator=gen).to(torch.int32).to(DEV)   # (the draws HalfTwins.actions makes)
         hs = g.hop(k)
         o, rew = w.step_to(act, ring.slots[k % 3])[:2]
         torch.cuda.synchronize()
         assert ring.intact()
-        assert torch.equal(_b16(o).reshape(-1), _b16(hs).reshape(-1)), k
+        assert torch.equal(b16(o).reshape(-1), b16(hs).reshape(-1)), k
         assert torch.equal(rew.view(torch.int32), g.last_rew.view(torch.int32)), k
     g.finish()
 
@@ -227,7 +114,7 @@ def test_c_abi_format_switch_on_a_group_handle():
     L = _lib.lib()
     name = "HG_13_slots_36v12"
     N, P = 6, 36
-    e1, e2 = _mk(name, n=N, max_steps=2), _mk(name, n=N, max_steps=2)
+    e1, e2 = make_env(CASES[name], n=N, seed=SEED, max_steps=2), make_env(CASES[name], n=N, seed=SEED, max_steps=2)
     e2.set_kernel("generic")
     n = N * P * e1.obs_dim
     e1.reset(), e2.reset()
@@ -270,9 +157,9 @@ def test_c_abi_format_switch_on_a_group_handle():
     call(as_f32, f1, "float32, from the same address")   # element i is halves 2 i and 2 i + 1, then the 7.0s: an unknown buffer
     assert bool((f1 == 7.0).any())                       # kept cells of the float32 view did hold non-zero values
     call(f1, as_f32, "float32, into the region")         # ... and now as a float32 buffer
-    kept = _b16(as_f16).clone()
+    kept = b16(as_f16).clone()
     call(as_f16, hD, "half, from the same address")      # halves 2 i and 2 i + 1 are float32 element i: an unknown buffer again
-    same = (_b16(hD) == kept) & (kept != 0)
+    same = (b16(hD) == kept) & (kept != 0)
     assert bool(same.any()), "no kept half of the float32 bytes is non-zero"
     call(hD, hC, "half again")
     assert dones >= N, "max_steps=2: fused auto-resets occurred"
@@ -281,14 +168,8 @@ def test_c_abi_format_switch_on_a_group_handle():
 T, NR = 4, 14
 
 
-def _policy(obs):
-    """depends only on which cells are non-zero: the count of non-zero cells of a row mod 5"""
-    return ((obs != 0).sum(dim=-1) % 5).to(torch.int32)
-
-
 def _rollout_env():
-    env = _mk("HLG_20v50", obs_dtype=F16, n=NR, max_blocks=0, seed=9)
-    _prefill(env, [_counts(20, 50)[i % 7] for i in range(NR)])
+    env = rollout_env(CASES["HLG_20v50"], F16, counts=[_counts(20, 50)[i % 7] for i in range(NR)], n=NR)
     assert env.step_to_kernel_kind == "wave"
     return env
 
@@ -319,8 +200,8 @@ def test_rollout_collector_keeps_half_slots_of_a_live_group_batch():
         dones += int((torch.stack(want["dones"]) != 0).sum())
         for tr in (b, c):
             assert tr.observations.dtype is F16 and tr.last_observation.dtype is F16
-            assert torch.equal(_b16(tr.observations), _b16(torch.stack(want["observations"]))), it
-            assert torch.equal(_b16(tr.last_observation), _b16(obs)), it
+            assert torch.equal(b16(tr.observations), b16(torch.stack(want["observations"]))), it
+            assert torch.equal(b16(tr.last_observation), b16(obs)), it
             assert torch.equal(tr.actions, torch.stack(want["actions"])), it
             assert torch.equal(tr.rewards.view(torch.int32), torch.stack(want["rewards"]).view(torch.int32)), it
             assert torch.equal(tr.dones, torch.stack(want["dones"])), it

@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+import helpers
+from helpers import same_bits
 from live_pursuit import assert_live_equals_fixed
 
 pytestmark = pytest.mark.gpu
@@ -63,12 +65,14 @@ def _stagger(env):
     env.set_state(dict(t=AGES))   # (clocks alone: what the fast path knows about the buffer stays)
 
 
-def _bits(t):
-    return (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)).reshape(-1).view(np.int32)
+def _vs_oracle(t, a):
+    """a tensor of the env's and the oracle's array of the same elements, both for same_bits / _differ"""
+    return t.detach().cpu().reshape(a.shape), a
 
 
-def same_bits(a, b):
-    return np.array_equal(_bits(a), _bits(b))
+def _differ(a, b):
+    """in how many elements two buffers differ in some bit (the figure of a failure's message)"""
+    return int((helpers.bits(a) != helpers.bits(b)).sum())
 
 
 class OracleRun(object):
@@ -78,7 +82,7 @@ class OracleRun(object):
         self.env, self.orc = _env(name, **kw), _oracle(name, **kw)
         self.P = SHAPES[name][1]
         obs, oobs = self.env.reset(), self.orc.reset()
-        assert same_bits(obs, oobs), "reset obs"
+        assert same_bits(*_vs_oracle(obs, oobs)), "reset obs"
         _stagger(self.env)
         self.tstep = AGES.astype(np.int64).copy()
         self.rng = np.random.RandomState(5)
@@ -99,8 +103,8 @@ class OracleRun(object):
             self.orc.reset(mask=mask)
             self.tstep[mask != 0] = 0
             self.n_resets += int(mask.sum())
-        got, want = _bits(self.env.obs_buffer), _bits(self.orc.obs)
-        assert np.array_equal(got, want), "step %d obs: %d elements differ" % (t, int((got != want).sum()))
+        got, want = _vs_oracle(self.env.obs_buffer, self.orc.obs)
+        assert same_bits(got, want), "step %d obs: %d elements differ" % (t, _differ(got, want))
         return obs
 
 
@@ -134,8 +138,8 @@ def _twin_run(make, P, edit_at=None):
         assert buf._version != version
         act = torch.randint(0, 5, (N, P), generator=g, dtype=torch.int32).to(DEV)
         (oa, ra, da, ia), (ob, rb, db, ib) = a.step(act), b.step(act)
-        got, want = _bits(a.obs_buffer), _bits(b.obs_buffer)
-        assert np.array_equal(got, want), "step %d: %d elements differ from the twin that never skips" % (t, int((got != want).sum()))
+        got, want = a.obs_buffer, b.obs_buffer
+        assert same_bits(got, want), "step %d: %d elements differ from the twin that never skips" % (t, _differ(got, want))
         assert torch.equal(ra, rb) and torch.equal(ia["done_bits"], ib["done_bits"]) and torch.equal(ia["removed"], ib["removed"]), t
     return a, b
 
@@ -178,8 +182,8 @@ def test_two_alternating_buffers_through_the_c_abi(name):
             _lib.check(L.madrl_pursuit_step(e._handle, _lib.ptr(act), None, _lib.ptr(bufs[id(e)][t % 2]), _lib.ptr(e._rew), _lib.ptr(e._done),
                                             _lib.ptr(e._removed), stream))
         for k in range(2):
-            got, want = _bits(bufs[id(a)][k]), _bits(bufs[id(b)][k])
-            assert np.array_equal(got, want), "call %d, buffer %d: %d elements differ" % (t, k, int((got != want).sum()))
+            got, want = bufs[id(a)][k], bufs[id(b)][k]
+            assert same_bits(got, want), "call %d, buffer %d: %d elements differ" % (t, k, _differ(got, want))
         assert torch.equal(a._rew, b._rew) and torch.equal(a._done, b._done), t
 
 
