@@ -682,6 +682,38 @@ int madrl_heuristic_multiwalker(const float *obs, int64_t n_rows, int32_t obs_di
  * against the published known-answer vectors. */
 void madrl_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
+/* ------------------------------------------------------------------------------------------
+ * Half-precision observation rows of the particle worlds (appended; the ABI version stays 7 and no struct grew).
+ *
+ * madrl_waterworld_reset / _step and madrl_hostage_reset / _step with a binary16 destination: obs_dev points at
+ * N * agents * obs_dim 2-byte elements and needs 2-byte alignment only (slot t of a [T + 1][N][agents][obs_dim] tensor with
+ * an odd N * agents * obs_dim starts on an odd element).  Every element a launch stores holds the round-to-nearest-even
+ * binary16 of the float32 value the float32 entry stores there -- subnormal halves kept, overflow to infinity, what
+ * torch.Tensor.to(torch.float16) gives -- and rows of envs outside a reset mask keep their 16 bits.  Nothing is written
+ * outside the N * agents * obs_dim elements.  Rewards, done bytes, info counters and the state record are the float32
+ * entries', bit for bit; every other argument is theirs.
+ * They run on the fixed-shape one-wavefront kernels alone (the shapes of csrc/waterworld_specializations.def and the hostage
+ * world's 3 / 10 / 5 with 30 sensors on specialised instantiations, any other shape on a generic one) and check the handle
+ * at every call.  MADRL_EINVAL, each with its own message:
+ *   obs_dev is NULL                      (the half rows have no other destination)
+ *   the handle has cfg.crowd = 1         (the crowd kernels have no half rows)
+ *   per-env particle counts are bound    (madrl_*_set_particle_counts)
+ *   per-pursuer sensor ranges are bound  (madrl_waterworld_set_sensor_ranges)
+ *   a StandardizedEnv is bound           (madrl_*_set_standardize)
+ * The set_* calls themselves are what they were: a handle may be driven through the float32 entries with any of them bound
+ * and through the half entries once they are unbound again. */
+int madrl_waterworld_reset_f16(madrl_waterworld *h, const uint8_t *mask_dev, uint16_t *obs_dev, void *stream);
+int madrl_waterworld_step_f16(madrl_waterworld *h, const float *actions_dev, const float *inj_respawn_dev,
+                              uint16_t *obs_dev, float *rew_dev, uint8_t *done_dev, int32_t *info_dev, void *stream);
+int madrl_hostage_reset_f16(madrl_hostage *h, const uint8_t *mask_dev, uint16_t *obs_dev, void *stream);
+int madrl_hostage_step_f16(madrl_hostage *h, const float *actions_dev, const float *inj_respawn_dev, uint16_t *obs_dev,
+                           float *rew_dev, uint8_t *done_dev, int32_t *info_dev, void *stream);
+/* madrl_heuristic_waterworld over binary16 rows (2-byte alignment): every value is widened exactly and the float32 policy's
+ * arithmetic runs from there -- the actions madrl_heuristic_waterworld gives on the rows converted to float32, bit for bit.
+ * Same arguments otherwise, same checks. */
+int madrl_heuristic_waterworld_f16(const uint16_t *obs, int64_t n_rows, int32_t obs_dim, const double *cos_sin_dev,
+                                   float *actions, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,11 @@ SIGNATURES = {
     "madrl_pursuit_step_to_f16_kernel_kind": (C.c_int, [_vp, _vp]),
     "madrl_pursuit_last_step_entry": (C.c_int, [_vp, _vp]),
     "madrl_pursuit_fixed_choice": (C.c_int, [_vp, C.c_int64, C.c_uint32, _vp]),
+    "madrl_waterworld_reset_f16": (C.c_int, [_vp] * 4),
+    "madrl_waterworld_step_f16": (C.c_int, [_vp] * 8),
+    "madrl_hostage_reset_f16": (C.c_int, [_vp] * 4),
+    "madrl_hostage_step_f16": (C.c_int, [_vp] * 8),
+    "madrl_heuristic_waterworld_f16": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
 }
 
 
@@ -199,12 +204,14 @@ def ptr(t):
 
 
 def require_float32(t, what):
-    """The native consumers of observation rows (the device chase policy, the wrappers' epilogue kernels) read float32 through the raw
-    pointer: any other element type -- the float16 rows of BatchedPursuitEvade(obs_dtype=torch.float16) -- would be read, or written,
-    past the end of the buffer.  Refused here, before a pointer is taken."""
+    """The native consumers of observation rows (the float32 device policies, the wrappers' epilogue kernels) read float32 through the raw
+    pointer: any other element type -- the float16 rows of an env built with obs_dtype=torch.float16 (BatchedPursuitEvade,
+    BatchedMAWaterWorld, BatchedContinuousHostageWorld) -- would be read, or written, past the end of the buffer.  Refused here, before a
+    pointer is taken."""
     if t.dtype is not torch.float32:
-        raise TypeError("%s reads float32 observations through the C ABI, got %s (a half-precision PursuitEvade, obs_dtype=torch.float16, "
-                        "needs a torch policy and no wrapper; convert with .float() first if a copy is acceptable)" % (what, t.dtype))
+        raise TypeError("%s reads float32 observations through the C ABI, got %s (a half-precision env, obs_dtype=torch.float16, needs a "
+                        "policy of its own element type and no normalising wrapper; convert with .float() first if a copy is acceptable)"
+                        % (what, t.dtype))
     return t
 
 
@@ -214,11 +221,11 @@ def current_stream(device):
 
 def obs_destination(obs_out, like):
     """`obs_out=` of the envs' step(): a caller's tensor a step kernel writes its observations to (a trajectory slot) instead of the env's own
-    buffer `like` -- checked (float32, contiguous, same device and size) and viewed in that buffer's shape"""
+    buffer `like` -- checked (the buffer's element type, contiguous, same device and size) and viewed in that buffer's shape"""
     if type(obs_out) is not torch.Tensor:
         raise TypeError("obs_out must be a torch.Tensor, got %s" % type(obs_out).__name__)
-    if obs_out.dtype is not torch.float32 or obs_out.device != like.device or not obs_out.is_contiguous() or obs_out.numel() != like.numel():
-        raise ValueError("obs_out must be a contiguous float32 tensor of %d elements on %s (got %s, %s, %s, contiguous=%s)"
-                         % (like.numel(), like.device, tuple(obs_out.shape), obs_out.dtype, obs_out.device, obs_out.is_contiguous()))
+    if obs_out.dtype is not like.dtype or obs_out.device != like.device or not obs_out.is_contiguous() or obs_out.numel() != like.numel():
+        raise ValueError("obs_out must be a contiguous %s tensor of %d elements on %s (got %s, %s, %s, contiguous=%s)"
+                         % (str(like.dtype).replace("torch.", ""), like.numel(), like.device, tuple(obs_out.shape), obs_out.dtype, obs_out.device,
+                            obs_out.is_contiguous()))
     return obs_out.view(like.shape)
-

@@ -387,4 +387,20 @@ int particle_step(H *h, const float *actions_dev, const float *inj_respawn_dev, 
     return launch(h, io, 1, stream);
 }
 
+// The half-precision entries (madrl_*_reset_f16 / madrl_*_step_f16) run the fixed-shape one-wavefront kernel alone and have no other
+// output for the rows than `obs`: checked at every call, since the set_* calls of a handle know nothing of the entry that comes next.
+template <class H>
+int particle_half_ok(const H *h, const void *obs_dev, const char *what) {
+    if (!h) return fail(MADRL_EINVAL, "%s: handle is NULL", what);
+    if (!obs_dev) return fail(MADRL_EINVAL, "%s: obs is NULL (the half rows have no other destination)", what);
+    if (h->cfg.crowd) return fail(MADRL_EINVAL, "%s: the crowd kernel (cfg.crowd = 1) has no half-precision rows; they run on the one-wavefront kernel", what);
+    if (h->live != nullptr)
+        return fail(MADRL_EINVAL, "%s: per-env particle counts are bound (set_particle_counts), and the live-count kernel has no half-precision rows; unbind them first (set_particle_counts(NULL, NULL))", what);
+    if (h->ranged)
+        return fail(MADRL_EINVAL, "%s: per-pursuer sensor ranges are bound (set_sensor_ranges), and the ranged kernel has no half-precision rows; unbind them first (set_sensor_ranges(NULL))", what);
+    if (h->std_bound)
+        return fail(MADRL_EINVAL, "%s: a fused StandardizedEnv is bound (set_standardize), and it has no half-precision rows; unbind it first (set_standardize(NULL))", what);
+    return MADRL_OK;
+}
+
 }  // namespace madrl

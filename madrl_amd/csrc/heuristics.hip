@@ -254,6 +254,45 @@ __global__ __launch_bounds__(256) void waterworld_policy_kernel(const float *__r
     }
 }
 
+// The same over binary16 rows (BatchedMAWaterWorld(obs_dtype=torch.float16)): every value is loaded as its 16 bits, widened exactly (each
+// binary16 is a float32) and from there on the float32 kernel's float64 arithmetic runs in its order -- the actions of the float32 policy on
+// the widened rows, bit for bit.  A kernel of its own beside the float32 one for the reason given at pursuit_policy_f16_kernel: that
+// kernel's emitted code is pinned.
+__device__ __forceinline__ float widen(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+
+__global__ __launch_bounds__(256) void waterworld_policy_f16_kernel(const uint16_t *__restrict__ obs, int64_t n_rows, int D,
+                                                                    const double *__restrict__ cs, float *__restrict__ actions) {
+    const int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3;
+    const int sub = threadIdx.x & 7;
+    const int K = D / 7;
+    double ax[4] = {0, 0, 0, 0}, ay[4] = {0, 0, 0, 0};
+    const uint16_t *o = obs + (row < n_rows ? row : 0) * (int64_t)D;
+    for (int k = sub; k < K; k += 8) {
+        const double cx = cs[2 * k], sy = cs[2 * k + 1];
+        const double v0 = widen(o[k]), v1 = widen(o[K + k]), v3 = widen(o[3 * K + k]), v5 = widen(o[5 * K + k]);
+        ax[0] += v0 * cx; ay[0] += v0 * sy;
+        ax[1] += v1 * cx; ay[1] += v1 * sy;
+        ax[2] += v3 * cx; ay[2] += v3 * sy;
+        ax[3] += v5 * cx; ay[3] += v5 * sy;
+    }
+#pragma unroll
+    for (int m = 1; m < 8; m <<= 1)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            ax[q] += __shfl_xor(ax[q], m, 8);
+            ay[q] += __shfl_xor(ay[q], m, 8);
+        }
+    if (row < n_rows && sub == 0) {
+        const double fe = widen(o[7 * K]) > 0.0f ? 1.5 : 1.0, fp = widen(o[7 * K + 1]) > 0.0f ? 1.5 : 1.0;
+        double x = -ax[0] + ax[1] * fe - ax[2] * fp + ax[3] / 2;
+        double y = -ay[0] + ay[1] * fe - ay[2] * fp + ay[3] / 2;
+        const double n = sqrt(x * x + y * y);
+        if (n > 0) { x /= n; y /= n; } else { x = 0; y = 0; }
+        actions[2 * row] = (float)x;
+        actions[2 * row + 1] = (float)y;
+    }
+}
+
 // ---- MultiWalkerHeuristicPolicy.sample_actions (multi_walker.py:16-86), one row per thread.  The gait state machine is
 // re-initialised on every call in the reference (:23-25: state = STAY_ON_ONE_LEG, moving_leg = 0), so the policy is a
 // pure function of the observation; `if target:` treats a 0.0 target as unset (:60-67).
@@ -351,6 +390,15 @@ int madrl_heuristic_waterworld(const float *obs, int64_t n_rows, int32_t obs_dim
     if (!obs || !cos_sin_dev || !actions || n_rows < 1 || obs_dim < 9) return fail(MADRL_EINVAL, "heuristic_waterworld: bad argument");
     const int64_t threads = n_rows * 8;
     hipLaunchKernelGGL(waterworld_policy_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, obs, n_rows,
+                       (int)obs_dim, cos_sin_dev, actions);
+    MADRL_HIP_TRY(hipGetLastError());
+    return MADRL_OK;
+}
+
+int madrl_heuristic_waterworld_f16(const uint16_t *obs, int64_t n_rows, int32_t obs_dim, const double *cos_sin_dev, float *actions, void *stream) {
+    if (!obs || !cos_sin_dev || !actions || n_rows < 1 || obs_dim < 9) return fail(MADRL_EINVAL, "heuristic_waterworld_f16: bad argument");
+    const int64_t threads = n_rows * 8;
+    hipLaunchKernelGGL(waterworld_policy_f16_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, obs, n_rows,
                        (int)obs_dim, cos_sin_dev, actions);
     MADRL_HIP_TRY(hipGetLastError());
     return MADRL_OK;

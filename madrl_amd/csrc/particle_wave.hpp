@@ -147,6 +147,29 @@ __device__ __forceinline__ void store_record(const uint32_t *SU, int64_t env, in
     }
 }
 
+// ---- half-precision rows (waterworld_kernel_f16, hostage_kernel_f16).  The env's staged float32 rows O[n_out] (16-byte aligned in LDS) leave
+// as binary16: element e of the destination holds half_bits(O[e]) (common.hpp: round to nearest even, subnormals kept -- never the packed
+// round-toward-zero conversion).  Eight values per lane: two 16-byte LDS reads, eight conversions, ONE 16-byte store; the n_out % 8 values
+// behind them leave in 2-byte stores.  The destination is 2-byte aligned and no more (slot t of a [T + 1, N, A, D] half tensor with odd
+// N * A * D starts on an odd element): the 16-byte store is declared so, and gfx950 under HSA runs global accesses in unaligned mode -- what
+// the float32 rows' 16-byte stores rely on for their 4-byte-aligned base.  Nothing is written outside orow[0 .. n_out - 1]: a chunk ends at
+// 8 * (n_out / 8) at the latest, the tail below n_out.
+__device__ __forceinline__ void store_rows_half(const float *O, __attribute__((address_space(1))) uint16_t *orow, uint32_t n_out, uint32_t ulane) {
+    typedef float f4a __attribute__((ext_vector_type(4), aligned(16)));
+    typedef uint32_t u4h __attribute__((ext_vector_type(4), aligned(2)));
+    const uint32_t n8 = n_out / 8u;
+    for (uint32_t e = ulane; e < n8; e += 64u) {
+        const f4a a = *reinterpret_cast<const f4a *>(O + 8 * e), b = *reinterpret_cast<const f4a *>(O + 8 * e + 4);
+        u4h w;
+        w.x = (uint32_t)half_bits(a.x) | ((uint32_t)half_bits(a.y) << 16);
+        w.y = (uint32_t)half_bits(a.z) | ((uint32_t)half_bits(a.w) << 16);
+        w.z = (uint32_t)half_bits(b.x) | ((uint32_t)half_bits(b.y) << 16);
+        w.w = (uint32_t)half_bits(b.z) | ((uint32_t)half_bits(b.w) << 16);
+        *reinterpret_cast<__attribute__((address_space(1))) u4h *>(orow + 8 * e) = w;
+    }
+    for (uint32_t e = 8u * n8 + ulane; e < n_out; e += 64u) orow[e] = half_bits(O[e]);
+}
+
 // ---- phase A.  act_lane: the action row spread over the lanes (WaveRecord::act); agent(): the lane's agent index, 0 for a lane that is
 // no agent (a callable: the kernels evaluate the lane predicate in it once per use).  -> the lane's scaled action (a0, a1) and its control penalty: its own under the local reward, and under the global one
 // (actions**2).sum() over the agents, summed row-major in that order, not as a tree.

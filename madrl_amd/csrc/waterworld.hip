@@ -30,11 +30,10 @@
 // instantiations as they were) and waterworld_kernel_live<MODE> (per-env particle counts within the handle's capacity,
 // madrl_waterworld_set_particle_counts on a handle with cfg.crowd = 0: the generic body, the count arrays as a third argument) and
 // waterworld_kernel_ranges<MODE> (a sensor range per pursuer, madrl_waterworld_set_sensor_ranges: the generic body, the ranges behind
-// the sensor table).
+// the sensor table).  waterworld_kernel_f16 (waterworld_f16.hip) is the fourth: the fixed-shape entry with half-precision observation rows.
 // Arithmetic is float32 (north_star tolerance 1e-5 against the float64 reference); every
 // expression keeps the statement order of the reference's step() so that a float32 CPU restatement agrees bit for bit.
-#include "waterworld_dev.hpp"   // WwDev, WwIO, the RNG tags: shared with waterworld_crowd.hip
-#include "particle_wave.hpp"    // the device code this kernel shares with hostage_kernel (hostage.hip)
+#include "waterworld_wave.hpp"   // WwDev, WwIO, the views of the kernel-argument segment, the occupancy rule: shared with waterworld_f16.hip
 
 #include <math.h>
 #include <string.h>
@@ -42,34 +41,6 @@
 namespace {
 
 using namespace madrl;
-
-// The launch parameters as read from the kernel-argument segment (kernargs(), common.hpp) at the phase that needs them.
-struct WwKArgs {
-    WwDev d;
-    WwIO io;
-};
-// ... and of waterworld_kernel_live, whose third argument follows the two (all three are 8-byte aligned)
-struct WwKArgsLive {
-    WwDev d;
-    WwIO io;
-    ParticleCounts cn;
-};
-static_assert(sizeof(WwKArgs) % 8 == 0 && sizeof(WwKArgsLive) == sizeof(WwKArgs) + sizeof(ParticleCounts), "the third argument follows the two without padding");
-
-// Profiling aid (scripts/variants.sh, never the shipped library): 1 no sensing loop, 2 no observation store, 4 no collisions
-#ifndef MADRL_WW_ABLATE
-#define MADRL_WW_ABLATE 0
-#endif
-
-// Resident wavefronts per SIMD the SPECIALISED kernel's registers are allocated for (the generic one is left to the compiler).
-// Measured at BASELINE C3, 32 768 envs: 4 waves (104 VGPRs) 77 us, 5 waves (86) 60.4 us, 6 waves (80, no scratch) 57.2 us, 7 waves
-// (72 + 32 B of scratch) 57.4 us.
-#ifndef MADRL_WW_WAVES
-#define MADRL_WW_WAVES 6
-#endif
-// (the fused-wrapper variant holds float64 statistics: one wave fewer, or it spills)
-#define MADRL_WW_OCC_N (TNp > 0 ? (FUSED ? MADRL_WW_WAVES - 1 : MADRL_WW_WAVES) - (TNp > 6 ? 1 : 0) : 0)  // (> 6 pursuers: two words per collision matrix, more live pass state)
-#define MADRL_WW_OCC __attribute__((amdgpu_waves_per_eu(MADRL_WW_OCC_N > 0 ? MADRL_WW_OCC_N : 1, MADRL_WW_OCC_N > 0 ? MADRL_WW_OCC_N : 8)))
 
 // MODE 0: reset(mask)   MODE 1: step (+ fused auto-reset)
 // TNp..TK > 0: the particle / sensor counts are compile-time constants (loops unroll, the index divisions fold); 0: generic.
@@ -79,7 +50,9 @@ template <int MODE, int TNp, int TNe, int TNpo, int TK, bool FUSED = false, int 
 __global__ __launch_bounds__(64) MADRL_WW_OCC void waterworld_kernel(const WwDev d, const WwIO io) {
 #define MADRL_WW_BODY_LIVE 0
 #define MADRL_WW_BODY_RANGES 0
+#define MADRL_WW_BODY_HALF 0
 #include "waterworld_wave_body.inc"
+#undef MADRL_WW_BODY_HALF
 #undef MADRL_WW_BODY_RANGES
 #undef MADRL_WW_BODY_LIVE
 }
@@ -92,7 +65,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void
     constexpr bool FUSED = false;
 #define MADRL_WW_BODY_LIVE 1
 #define MADRL_WW_BODY_RANGES 0
+#define MADRL_WW_BODY_HALF 0
 #include "waterworld_wave_body.inc"
+#undef MADRL_WW_BODY_HALF
 #undef MADRL_WW_BODY_RANGES
 #undef MADRL_WW_BODY_LIVE
 }
@@ -106,7 +81,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void
     constexpr bool FUSED = false;
 #define MADRL_WW_BODY_LIVE 0
 #define MADRL_WW_BODY_RANGES 1
+#define MADRL_WW_BODY_HALF 0
 #include "waterworld_wave_body.inc"
+#undef MADRL_WW_BODY_HALF
 #undef MADRL_WW_BODY_RANGES
 #undef MADRL_WW_BODY_LIVE
 }
@@ -237,6 +214,11 @@ int ww_launch(const madrl_waterworld *h, const WwIO &io, int mode, void *stream)
     return MADRL_OK;
 }
 
+// the half-precision entries: waterworld_kernel_f16 (waterworld_f16.hip) on the handle's shape, the half pointer in io.obs
+int ww_launch_f16(const madrl_waterworld *h, const WwIO &io, int mode, void *stream) {
+    return ww_f16_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, stream);
+}
+
 __global__ void ww_state_copy_kernel(const WwDev d, float *pos, float *vel, float *obst, int32_t *t, uint32_t *tick,
                                      const int to_state) {
     const int64_t env = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -341,6 +323,19 @@ int madrl_waterworld_reset(madrl_waterworld *h, const uint8_t *mask_dev, float *
 int madrl_waterworld_step(madrl_waterworld *h, const float *actions_dev, const float *inj_respawn_dev, float *obs_dev,
                           float *rew_dev, uint8_t *done_dev, int32_t *info_dev, void *stream) {
     return particle_step(h, actions_dev, inj_respawn_dev, obs_dev, rew_dev, done_dev, info_dev, stream, ww_launch);
+}
+
+int madrl_waterworld_reset_f16(madrl_waterworld *h, const uint8_t *mask_dev, uint16_t *obs_dev, void *stream) {
+    const int rc = particle_half_ok(h, obs_dev, "madrl_waterworld_reset_f16");
+    if (rc) return rc;
+    return particle_reset(h, mask_dev, reinterpret_cast<float *>(obs_dev), stream, ww_launch_f16);
+}
+
+int madrl_waterworld_step_f16(madrl_waterworld *h, const float *actions_dev, const float *inj_respawn_dev, uint16_t *obs_dev,
+                              float *rew_dev, uint8_t *done_dev, int32_t *info_dev, void *stream) {
+    const int rc = particle_half_ok(h, obs_dev, "madrl_waterworld_step_f16");
+    if (rc) return rc;
+    return particle_step(h, actions_dev, inj_respawn_dev, reinterpret_cast<float *>(obs_dev), rew_dev, done_dev, info_dev, stream, ww_launch_f16);
 }
 
 int madrl_waterworld_get_state(madrl_waterworld *h, float *pos, float *vel, float *obst, int32_t *t, uint32_t *tick,

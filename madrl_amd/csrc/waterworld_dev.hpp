@@ -1,9 +1,9 @@
 // waterworld_dev.hpp -- the launch arguments of the Waterworld kernels, shared by waterworld.hip (handle, validation, layout, dispatch,
-// the one-wavefront kernel) and waterworld_crowd.hip (the multi-wavefront kernel).
+// the one-wavefront kernel), waterworld_f16.hip (its half-precision entry) and waterworld_crowd.hip (the multi-wavefront kernel).
 //
 // The structs stay in the unnamed namespace: they are part of the mangled names of waterworld_kernel<...>, which must not change.
-// Each translation unit therefore has its own (identical) copy of the types, and the one function that crosses the two files,
-// ww_crowd_launch below, takes them as untyped pointers.
+// Each translation unit therefore has its own (identical) copy of the types, and the functions that cross the files,
+// ww_crowd_launch and ww_f16_launch below, take them as untyped pointers.
 #pragma once
 
 #include "common.hpp"
@@ -50,6 +50,9 @@ namespace madrl {
 // ranged: the per-pursuer sensor ranges of madrl_waterworld_set_sensor_ranges lie behind dev's sensor table and lds_bytes has room for them.
 int ww_crowd_launch(const void *dev, const void *io, int mode, int64_t max_blocks, size_t lds_bytes, const int32_t *pending, int32_t *live,
                     bool ranged, void *stream);
+// waterworld_f16.hip: waterworld_kernel_f16 on dev's shape (a line of waterworld_specializations.def: its specialised instantiation), io.obs
+// holding the binary16 destination.  The caller has checked the handle: no crowd, counts, ranges or StandardizedEnv (particle_half_ok).
+int ww_f16_launch(const void *dev, const void *io, int mode, int64_t max_blocks, size_t lds_bytes, void *stream);
 // the dynamic LDS of one ww_crowd_kernel workgroup
 size_t ww_crowd_lds_bytes(int n_pursuers, int n_evaders, int n_poison, int n_sensors, int rec_dw);
 

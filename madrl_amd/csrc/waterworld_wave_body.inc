@@ -2,6 +2,8 @@
 // (waterworld.hip), included inside both __global__ entries like waterworld_crowd_body.inc: the fixed-shape entry keeps its two arguments,
 // its name and its code.  In scope: MODE, TNp .. TD, FUSED, d (WwDev), io (WwIO) and the macro MADRL_WW_BODY_LIVE (0 / 1); the live entry's third
 // argument (ParticleCounts) is read through kernargs<WwKArgsLive>().  MADRL_WW_BODY_RANGES (0 / 1): the ranged entry, see RNG below.
+// MADRL_WW_BODY_HALF (0 / 1): waterworld_kernel_f16 (waterworld_f16.hip) -- io.obs is a binary16 destination and the staged rows leave through
+// store_rows_half (particle_wave.hpp); nothing else differs.  Never with LIVE, RANGES or FUSED.
 // LIVE: d.Np / d.Ne / d.Npo are a CAPACITY (Pc, Ec, POc) and every env runs its own counts.  Whatever a caller sees stays at the capacity,
 // slotted by class: the record, the rows of inj_resp, the action / reward / observation rows (stride Pc).  The env's counts travel with the
 // record prefetch (WaveCounts); the slotted record is packed to the live counts on its way into LDS and scattered back on its way out
@@ -442,6 +444,12 @@
                         do_init = true;
                     }
                 }
+#if MADRL_WW_BODY_HALF
+                if (pass == npass - 1) {  // half rows: the binary16 of every staged value (the host refuses a NULL destination and a bound wrapper)
+                    const int n_out = Np * D;
+                    store_rows_half(O, uniform_ptr(reinterpret_cast<uint16_t *>(IOA.obs) + env * (int64_t)n_out), (uint32_t)n_out, ulane);
+                }
+#else
                 if (pass == npass - 1) {
                     float *const obs_p = IOA.obs;
                     const int n_out = (LIVE ? Pc : Np) * D;  // (LIVE: the capacity's rows, those of absent pursuers zero-filled in O)
@@ -462,6 +470,7 @@
                     // (hostage.hip hands the helper a copy of *IOA.st and says why; this kernel keeps the reference)
                     if (FUSED) std_obs_row(*IOA.st, O, env * (int64_t)(Np * D), Np * D, lane);
                 }
+#endif
                 wave_sync();
             }
             // ---------------------------------------------------------- LDS -> record

@@ -101,14 +101,29 @@ class PursuitHeuristicPolicy(_DevicePolicy):
 
 
 class WaterworldHeuristicPolicy(_DevicePolicy):
-    """obs float32 [N, Np, D] of BatchedMAWaterWorld -> float32 [N, Np, 2]"""
+    """obs [N, Np, D] of BatchedMAWaterWorld -> float32 [N, Np, 2]
 
-    def __init__(self):
+    obs_dtype: torch.float32, or torch.float16 for the rows of BatchedMAWaterWorld(obs_dtype=torch.float16).  A policy reads exactly its own
+    element type (any other is a TypeError before a pointer is taken: the kernel would read past the end of a narrower buffer) and gives
+    the actions of the float32 policy on the widened rows, bit for bit."""
+
+    def __init__(self, obs_dtype=torch.float32):
+        if obs_dtype not in (torch.float32, torch.float16):
+            raise ValueError("obs_dtype must be torch.float32 or torch.float16, got %r" % (obs_dtype,))
+        self.obs_dtype = obs_dtype
         self._cs = None
         self._act = None
 
     def sample_actions(self, obs, deterministic=True):
-        obs = obs.contiguous()
+        if self.obs_dtype is torch.float32:
+            obs = _lib.require_float32(obs, "WaterworldHeuristicPolicy").contiguous()
+            launch = "madrl_heuristic_waterworld"
+        else:
+            if not isinstance(obs, torch.Tensor) or obs.dtype is not torch.float16:
+                raise TypeError("WaterworldHeuristicPolicy(obs_dtype=torch.float16) reads float16 observations through the C ABI, got %s (the rows of "
+                                "a float32 Waterworld take a policy with obs_dtype=torch.float32)" % getattr(obs, "dtype", type(obs).__name__))
+            obs = obs.contiguous()
+            launch = "madrl_heuristic_waterworld_f16"
         D = obs.shape[-1]
         K = D // 7
         n_rows = obs.numel() // D
@@ -117,8 +132,8 @@ class WaterworldHeuristicPolicy(_DevicePolicy):
             self._cs = torch.as_tensor(np.c_[np.cos(ang), np.sin(ang)].copy(), dtype=torch.float64, device=obs.device)
         if self._act is None or self._act.shape[:-1] != obs.shape[:-1] or self._act.device != obs.device:
             self._act = torch.empty(tuple(obs.shape[:-1]) + (2,), dtype=torch.float32, device=obs.device)
-        _lib.check(_lib.lib().madrl_heuristic_waterworld(_lib.ptr(obs), n_rows, D, _lib.ptr(self._cs), _lib.ptr(self._act),
-                                                         _lib.current_stream(obs.device)))
+        _lib.check(getattr(_lib.lib(), launch)(_lib.ptr(obs), n_rows, D, _lib.ptr(self._cs), _lib.ptr(self._act),
+                                               _lib.current_stream(obs.device)))
         return self._act, None
 
 
@@ -129,7 +144,7 @@ class MultiWalkerHeuristicPolicy(_DevicePolicy):
         self._act = None
 
     def sample_actions(self, obs, deterministic=True):
-        obs = obs.contiguous()
+        obs = _lib.require_float32(obs, "MultiWalkerHeuristicPolicy").contiguous()
         D = obs.shape[-1]
         n_rows = obs.numel() // D
         if self._act is None or self._act.shape[:-1] != obs.shape[:-1] or self._act.device != obs.device:

@@ -48,7 +48,7 @@ class BatchedContinuousHostageWorld(BatchedParticleWorld):
                  sensor_range=0.2, action_scale=0.01, save_reward=5., hit_reward=-1., encounter_reward=0.01, not_saved_reward=-3,
                  bomb_reward=-5., bomb_radius=0.05, key_radius=0.0075, control_penalty=-.1, reward_mech='global', addid=True,
                  n_envs=1, device="cuda:0", seed=0, env_id_base=0, max_steps=0, auto_reset=False, max_blocks=0, crowd=False,
-                 per_env_counts=False, **kwargs):
+                 per_env_counts=False, obs_dtype=torch.float32, **kwargs):
         """crowd=True: the multi-wavefront kernel (csrc/hostage_crowd.hip) -- up to 128 rescuers, 64 hostages and 1 023 particles per env,
         any sensor count up to 256; the same results bit for bit on a shape both kernels take.  Without it an env holds at most 61 particles
         and 32 rescuers.
@@ -56,10 +56,17 @@ class BatchedContinuousHostageWorld(BatchedParticleWorld):
         (set_particle_counts), taken at its next reset; all tensors keep the capacity's shapes, slotted by class (rescuer i at i, hostage m
         at n_good + m, criminal m at n_good + n_hostages + m; bit m of the saved mask is hostage m).  A pickle keeps the constructor
         arguments only: the counts of the copy are back at the capacity.  per_env_counts="wave" (Waterworld's one-wavefront form) is a
-        ValueError here: hostage_kernel has no live counts."""
+        ValueError here: hostage_kernel has no live counts.
+        obs_dtype=torch.float16: every observation tensor the env hands out or accepts (reset(), reset(mask=), step(), step(respawn=),
+        step_on_stream(), step(obs_out=)) is float16 and holds, element for element, the round-to-nearest-even half of what the float32 env
+        holds (torch's .to(torch.float16): subnormals kept); rewards, done, info and the state are the float32 env's, bit for bit.  It runs
+        on the one-wavefront kernel alone (specialised for 3 / 10 / 5 with 30 sensors): with crowd=True or per_env_counts it is a
+        ValueError, it has no fused StandardizedEnv (fused_standardize is False; a StandardizedEnv without enable_obsnorm passes the rows
+        through, one with it and ObservationBuffer raise TypeError), and any other dtype is a ValueError."""
         self._ctor = dict(locals())
         self._ctor.pop("self"); self._ctor.pop("kwargs"); self._ctor.pop("__class__", None)
         self._flags(crowd, per_env_counts)
+        self._half(obs_dtype)
         self.n_good, self.n_hostages, self.n_bad = n_good, n_hostages, n_bad
         self.n_coop_save, self.n_coop_avoid, self.radius, self.key_loc = n_coop_save, n_coop_avoid, radius, key_loc
         self.key_radius, self.bad_speed, self.n_sensors = key_radius, bad_speed, n_sensors

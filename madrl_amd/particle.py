@@ -11,7 +11,7 @@ from . import _lib
 from .base import AbstractMAEnv, SingleEnvDelegate
 
 _CALLS = ("obs_dim", "state_bytes", "create", "destroy", "set_launch", "kernel_kind", "set_particle_counts", "set_standardize", "reset", "step",
-          "get_state", "set_state")
+          "get_state", "set_state", "reset_f16", "step_f16")
 _API = {}   # C symbol prefix -> the world's functions under their short names (filled by setup(): nothing is kept on the instance)
 
 
@@ -35,8 +35,12 @@ class BatchedParticleWorld(AbstractMAEnv):
     per_env_counts=True (which `_flags()` takes from the constructor, with crowd=True): the `_COUNTS` attributes are a capacity and every env
     runs its own counts, taken at its next reset (set_particle_counts of the world, with its own keyword names); all tensors keep the
     capacity's shapes, slotted by class.  per_env_counts="wave" (without crowd=True) is the same on the one-wavefront kernel, for a world
-    whose one-wavefront kernel has a live-count entry (`_WAVE_LIVE`)."""
+    whose one-wavefront kernel has a live-count entry (`_WAVE_LIVE`).
+    obs_dtype=torch.float16 (which `_half()` takes from the constructor): every observation tensor the env hands out or accepts is float16
+    -- the round-to-nearest-even half of what the float32 env holds there; rewards, done, info and the state are the float32 env's.  It
+    runs on the fixed-shape one-wavefront kernels alone (madrl_*_reset_f16 / madrl_*_step_f16)."""
     per_env_counts = False
+    obs_dtype = torch.float32
     _WAVE_LIVE = False  # the world's one-wavefront kernel takes per-env counts (per_env_counts="wave")
     _SYM = None         # prefix of the C symbols: "madrl_waterworld"
     _COUNTS = None      # names of the attributes that hold the particle counts, the agents' first: ("n_pursuers", "n_evaders", "n_poison")
@@ -67,6 +71,26 @@ class BatchedParticleWorld(AbstractMAEnv):
                              + (" (or ask for the one-wavefront kernel's form with per_env_counts=\"wave\")" if self._WAVE_LIVE else ""))
         self._crowd, self.per_env_counts = bool(crowd), bool(per_env_counts)
 
+    def _half(self, obs_dtype, ranged=False):
+        """the observation dtype of a constructor, after `_flags()` and before a device is touched: only a set one travels in `_ctor`"""
+        if obs_dtype is torch.float32:   # (the class attribute says so: nothing is added to the instance either)
+            self._ctor.pop("obs_dtype")
+            return
+        if obs_dtype is not torch.float16:
+            raise ValueError("obs_dtype must be torch.float32 or torch.float16, got %r" % (obs_dtype,))
+        elif self._crowd:
+            raise ValueError("obs_dtype=torch.float16 runs on the one-wavefront kernel: the crowd kernel (crowd=True) has no half-precision rows")
+        elif self.per_env_counts:
+            raise ValueError("obs_dtype=torch.float16 runs on the fixed-shape kernel: the live-count kernels (per_env_counts) have no half-precision rows")
+        elif ranged:
+            raise ValueError("obs_dtype=torch.float16 runs on the fixed-shape kernel: the ranged kernel (a sensor_range whose elements differ) has "
+                             "no half-precision rows (pass a float, or an array of equal elements)")
+        self.obs_dtype = obs_dtype
+
+    @property
+    def _f16(self):
+        return self.obs_dtype is torch.float16
+
     def setup(self):
         c = _api(self._SYM)
         if self.device.type != "cuda":
@@ -78,9 +102,9 @@ class BatchedParticleWorld(AbstractMAEnv):
         counts = [getattr(self, k) for k in self._COUNTS]
         N, Na, D, dev = self.n_envs, counts[0], dim.value, self.device
         self.n_particles = sum(counts)
-        if getattr(self, "_shape_key", None) != (N, Na, D, nbytes.value):
+        if getattr(self, "_shape_key", None) != (N, Na, D, nbytes.value) or self._obs.dtype is not self.obs_dtype:
             self._state = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
-            self._obs = torch.zeros((N, Na, D), dtype=torch.float32, device=dev)
+            self._obs = torch.zeros((N, Na, D), dtype=self.obs_dtype, device=dev)
             self._rew = torch.zeros((N, Na), dtype=torch.float32, device=dev)
             self._done = torch.zeros(N, dtype=torch.uint8, device=dev)
             self._info = torch.zeros((N, 2), dtype=torch.int32, device=dev)
@@ -132,8 +156,8 @@ class BatchedParticleWorld(AbstractMAEnv):
 
     @property
     def fused_standardize(self):
-        """whether bind_standardize() works on this env (StandardizedEnv asks): the crowd and live-count kernels have no fused form"""
-        return not self._crowd and not self.per_env_counts
+        """whether bind_standardize() works on this env (StandardizedEnv asks): the crowd, live-count and half-precision kernels have no fused form"""
+        return not self._crowd and not self.per_env_counts and not self._f16
 
     def set_launch(self, max_blocks=0):
         self._max_blocks = int(max_blocks)
@@ -174,6 +198,9 @@ class BatchedParticleWorld(AbstractMAEnv):
         if mask is not None:
             mask = torch.as_tensor(mask, device=self.device).reshape(self.n_envs).to(torch.uint8).contiguous()
         std = getattr(self, "_std", None)
+        if self._f16:   # (a half env binds no StandardizedEnv)
+            _lib.check(_API[self._SYM].reset_f16(self._handle, _lib.ptr(mask), _lib.ptr(self._obs), _lib.current_stream(self.device)))
+            return self._obs
         _lib.check(_API[self._SYM].reset(self._handle, _lib.ptr(mask), None if std else _lib.ptr(self._obs), _lib.current_stream(self.device)))
         return std["obs_out"] if std else self._obs
 
@@ -190,6 +217,9 @@ class BatchedParticleWorld(AbstractMAEnv):
         if self.per_env_counts:
             raise _lib.MadrlError("bind_standardize: the live-count kernel (per_env_counts=\"wave\") has no fused StandardizedEnv; "
                                   "StandardizedEnv(env) or StandardizedEnv(env, fused=False) runs the epilogue kernels over it")
+        if self._f16:
+            raise _lib.MadrlError("bind_standardize: the half-precision kernel (obs_dtype=torch.float16) has no fused StandardizedEnv; "
+                                  "StandardizedEnv(env) without enable_obsnorm passes its rows through")
         N, Na, D, dev = self.n_envs, getattr(self, self._COUNTS[0]), self.obs_dim, self.device
         self._std_kwargs = dict(scale_reward=scale_reward, enable_obsnorm=enable_obsnorm, enable_rewnorm=enable_rewnorm,
                                 obs_alpha=obs_alpha, rew_alpha=rew_alpha, eps=eps)
@@ -216,9 +246,10 @@ class BatchedParticleWorld(AbstractMAEnv):
         """waterworld.py:220-436, hostage.py:228-430.  action: float [N, n_agents, 2] (or anything that reshapes to it).
         respawn: optional float [N, rows, 4] injected respawn outcomes (parity hook; rows: every particle in Waterworld, the criminals in
         the hostage world).
-        obs_out: optional contiguous float32 destination of N * n_agents * obs_dim elements on the env's device (e.g. a slot of a trajectory
-        tensor) the kernel writes the observations to instead of the env's own buffer; its [N, n_agents, D] view is returned.  Refused while
-        a fused StandardizedEnv is bound: the observation tensor the kernel writes then belongs to the wrapper."""
+        obs_out: optional contiguous destination of N * n_agents * obs_dim elements of the env's obs_dtype on the env's device (e.g. a slot
+        of a trajectory tensor) the kernel writes the observations to instead of the env's own buffer; its [N, n_agents, D] view is returned.
+        A float16 destination needs 2-byte alignment only.  Refused while a fused StandardizedEnv is bound: the observation tensor the
+        kernel writes then belongs to the wrapper."""
         N, Na = self.n_envs, getattr(self, self._COUNTS[0])
         if not self._conforming(action):
             a = torch.as_tensor(action, device=self.device)
@@ -250,8 +281,9 @@ class BatchedParticleWorld(AbstractMAEnv):
             if std:
                 raise ValueError("obs_out: a fused StandardizedEnv is bound to this env, the kernel's observation output belongs to the wrapper")
             obs = _lib.obs_destination(obs_out, self._obs)
-        _lib.check(_API[self._SYM].step(self._handle, _lib.ptr(a), _lib.ptr(r), None if std else _lib.ptr(obs), _lib.ptr(self._rew),
-                                _lib.ptr(self._done), _lib.ptr(self._info), stream_ptr))
+        step = _API[self._SYM].step_f16 if self._f16 else _API[self._SYM].step
+        _lib.check(step(self._handle, _lib.ptr(a), _lib.ptr(r), None if std else _lib.ptr(obs), _lib.ptr(self._rew),
+                        _lib.ptr(self._done), _lib.ptr(self._info), stream_ptr))
         # `done` is a bool VIEW of the byte the kernel wrote (0 / 1): no torch kernel runs after the launch
         info = {self._INFO_KEYS[0]: self._info[:, 0], self._INFO_KEYS[1]: self._info[:, 1], "done_bits": self._done}
         if std:  # fused StandardizedEnv: standardised observations and scaled / normalised rewards straight from the kernel
@@ -351,6 +383,9 @@ class ParticleWorld(SingleEnvDelegate, AbstractMAEnv):
 
     def __init__(self, *args, **kwargs):
         kwargs.pop("n_envs", None)
+        if kwargs.get("obs_dtype", torch.float32) is not torch.float32:   # the drop-in returns the reference's types: float64 arrays
+            raise ValueError("%s returns the reference's float64 observations; obs_dtype=%r is for the batched engine (%s)"
+                             % (type(self).__name__, kwargs["obs_dtype"], self._BATCHED.__name__))
         self._env = self._BATCHED(*args, n_envs=1, **kwargs)
 
     @property

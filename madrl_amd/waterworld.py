@@ -50,7 +50,7 @@ class BatchedMAWaterWorld(BatchedParticleWorld):
                  sensor_range=0.2, action_scale=0.01, poison_reward=-1., food_reward=1., encounter_reward=.05,
                  control_penalty=-.5, reward_mech='local', addid=True, speed_features=True,
                  n_envs=1, device="cuda:0", seed=0, env_id_base=0, max_steps=0, auto_reset=False, max_blocks=0,
-                 crowd=False, per_env_counts=False, **kwargs):
+                 crowd=False, per_env_counts=False, obs_dtype=torch.float32, **kwargs):
         """crowd=True: the multi-wavefront kernel (csrc/waterworld_crowd.hip) -- up to 128 pursuers and 1 023 particles per env, any
         sensor count; same results bit for bit on a shape both kernels take.  The default keeps the one-wavefront kernel and its limits
         (62 particles, 32 pursuers).
@@ -68,7 +68,15 @@ class BatchedMAWaterWorld(BatchedParticleWorld):
         runs on the ranged kernels (madrl_waterworld_set_sensor_ranges; crowd=True or not): observation row i is bit for bit row i of a
         batch with sensor_range=sensor_range[i], everything else is unchanged.  Such a batch runs the generic one-wavefront kernel whatever
         its shape, has no fused StandardizedEnv (the wrapper runs its epilogue kernels) and does not combine with per_env_counts
-        (ValueError).  An all-equal array is the float."""
+        (ValueError).  An all-equal array is the float.
+        obs_dtype=torch.float16: every observation tensor the env hands out or accepts (reset(), reset(mask=), step(), step(respawn=),
+        step_on_stream(), step(obs_out=)) is float16 and holds, element for element, the round-to-nearest-even half of what the float32 env
+        holds (torch's .to(torch.float16): subnormals kept); rewards, done, info and the state are the float32 env's, bit for bit.  Half the
+        bytes per stored row -- a rollout's observation slots (RolloutCollector(store_observations=True)) are allocated in this dtype, and
+        WaterworldHeuristicPolicy(obs_dtype=torch.float16) reads them.  It runs on the fixed-shape one-wavefront kernel alone (specialised
+        for the shapes of csrc/waterworld_specializations.def): with crowd=True, per_env_counts or differing ranges it is a ValueError, it
+        has no fused StandardizedEnv (fused_standardize is False; a StandardizedEnv without enable_obsnorm passes the rows through, one with
+        it and ObservationBuffer raise TypeError), and any other dtype is a ValueError."""
         # like the reference, unknown kwargs are swallowed (waterworld.py:81,:483 passes obs_loc=None)
         self._ctor = dict(locals())
         self._ctor.pop("self"); self._ctor.pop("kwargs"); self._ctor.pop("__class__", None)
@@ -83,6 +91,7 @@ class BatchedMAWaterWorld(BatchedParticleWorld):
             if self.per_env_counts:
                 raise ValueError("per-pursuer sensor ranges do not combine with per_env_counts: the live-count kernels take one range "
                                  "(pass a float, or an array of equal elements)")
+        self._half(obs_dtype, self._ranged)
         self.action_scale, self.poison_reward, self.food_reward = action_scale, poison_reward, food_reward
         self.control_penalty, self.encounter_reward = control_penalty, encounter_reward
         self.n_obstacles = 1
