@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MADRL_ABI_VERSION 7
+#define MADRL_ABI_VERSION 8
 
 #define MADRL_OK 0
 #define MADRL_EINVAL (-1)   /* bad argument / unsupported configuration */
@@ -713,6 +713,22 @@ int madrl_hostage_step_f16(madrl_hostage *h, const float *actions_dev, const flo
  * Same arguments otherwise, same checks. */
 int madrl_heuristic_waterworld_f16(const uint16_t *obs, int64_t n_rows, int32_t obs_dim, const double *cos_sin_dev,
                                    float *actions, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Which kernel family a Waterworld handle's last reset / step launch ran on (appended at ABI 8; no struct grew).
+ * Host code only: the launchers record the family in the handle, no device is touched.  madrl_waterworld_reset / _step and
+ * madrl_waterworld_reset_f16 / _step_f16 report alike: SPECIALISED for a fixed-shape launch of a shape listed in
+ * csrc/waterworld_specializations.def (or its local companion), GENERIC for any other fixed-shape launch of the
+ * one-wavefront kernel, LIVE / RANGED for the one-wavefront entries of madrl_waterworld_set_particle_counts /
+ * madrl_waterworld_set_sensor_ranges, CROWD for every launch of a cfg.crowd = 1 handle.  A launch that was refused
+ * (MADRL_EINVAL) leaves the value as it was.  The hostage world has no such call. */
+#define MADRL_WW_LAUNCH_NONE 0          /* no reset / step launch yet */
+#define MADRL_WW_LAUNCH_GENERIC 1
+#define MADRL_WW_LAUNCH_SPECIALISED 2
+#define MADRL_WW_LAUNCH_LIVE 3
+#define MADRL_WW_LAUNCH_RANGED 4
+#define MADRL_WW_LAUNCH_CROWD 5
+int madrl_waterworld_last_launch_kernel(const madrl_waterworld *h, int32_t *out);
 
 #ifdef __cplusplus
 }

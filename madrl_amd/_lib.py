@@ -15,7 +15,7 @@ import torch  # noqa: F401  (must precede CDLL, see above)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("MADRL_HIP_LIB") or os.path.join(_HERE, "libmadrl_hip.so")  # override: profiling variants only
-ABI_VERSION = 7
+ABI_VERSION = 8
 POLICY_COUNTER_WORDS = 32 * 65   # MADRL_POLICY_COUNTER_WORDS of include/madrl_hip.h
 
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_WAVE = 0, 1, 2
@@ -168,6 +168,7 @@ SIGNATURES = {
     "madrl_hostage_reset_f16": (C.c_int, [_vp] * 4),
     "madrl_hostage_step_f16": (C.c_int, [_vp] * 8),
     "madrl_heuristic_waterworld_f16": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
+    "madrl_waterworld_last_launch_kernel": (C.c_int, [_vp, _vp]),
 }
 
 

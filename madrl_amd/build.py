@@ -8,7 +8,7 @@
     python -m madrl_amd.build --pursuit-to-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN   # the two-buffer step (step_to) on this shape's fast kernel
     python -m madrl_amd.build --pursuit-to-group-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN [LIVE] # ... of a multi-wavefront shape (LIVE 1: with per-env agent counts)
     python -m madrl_amd.build --pursuit-to-group-f16-shape XS YS N_PURSUERS N_EVADERS OBS_RANGE FLATTEN [LIVE] # the half-precision step_to (obs_dtype=torch.float16) of a multi-wavefront shape
-    python -m madrl_amd.build --waterworld-shape N_PURSUERS N_EVADERS N_POISON N_SENSORS [OBS_DIM]
+    python -m madrl_amd.build --waterworld-shape N_PURSUERS N_EVADERS N_POISON N_SENSORS [OBS_DIM]   # refused when it cannot be built (waterworld_shape_refusal)
 
 The fast paths (one wavefront -- or a group of wavefronts -- per env, everything about the shape a compile-time constant) exist for the
 shapes listed in csrc/*_specializations.def: the BASELINE configurations, the reference's own runner / script defaults, the test shapes.
@@ -269,12 +269,57 @@ def add_pursuit_to_group_f16_shape(xs, ys, n_pursuers, n_evaders, obs_range, fla
                 ("pursuit_to_f16_group_specializations.def", line))
 
 
+def waterworld_wave_lds_bytes(n_pursuers, n_evaders, n_poison, n_sensors, obs_dim):
+    """the static LDS of a specialised one-wavefront Waterworld kernel (SPEC_BYTES, waterworld_wave_body.inc: wave_lds_bytes(4 * NP + 4, ...) of
+    particle_wave.hpp): the record | the staged rows [n_pursuers + 1][obs_dim] | the sensor vectors, each a whole number of 16 bytes, then the
+    reach masks, the collision bytes and the flags; the generic kernel's dynamic LDS (ww_lds_bytes) is the same number"""
+    P, E, PO, K, D = int(n_pursuers), int(n_evaders), int(n_poison), int(n_sensors), int(obs_dim)
+    up4 = lambda v: (v + 3) // 4 * 4
+    return ((up4(4 * (P + E + PO) + 4) + up4((P + 1) * D) + up4(2 * K)) * 4 + 8 * P + P * (E + PO) + 2 * E + PO + 15) // 16 * 16
+
+
+def waterworld_shape_refusal(n_pursuers, n_evaders, n_poison, n_sensors, obs_dim):
+    """why a line X(n_pursuers, n_evaders, n_poison, n_sensors, obs_dim) cannot be built or would never run, or None: what ww_validate
+    (waterworld.hip), ww_obs_dim_of, particle_create (common.hpp) and the static_asserts of waterworld_wave_body.inc say, evaluated here so
+    that such a shape is refused before it breaks the build"""
+    P, E, PO, K, D = int(n_pursuers), int(n_evaders), int(n_poison), int(n_sensors), int(obs_dim)
+    if min(P, E, PO) < 1 or P + E + PO > 62 or 2 * P > 64 or not 1 <= K <= 256:
+        return "no Waterworld kernel for this shape at all (madrl_waterworld_create refuses it)"
+    widths = [K * nfeat + 2 + addid for nfeat in (4, 7) for addid in (0, 1)]
+    if D not in widths:
+        return ("OBS_DIM %d is no row width of %d sensors: %d / %d without speed features (without / with the agent id), %d / %d with them; "
+                "no configuration would ever take the line" % ((D, K) + tuple(widths)))
+    lds = waterworld_wave_lds_bytes(P, E, PO, K, D)
+    if lds > 64 * 1024:
+        return ("the shape needs %d bytes of LDS per workgroup, a Waterworld handle may use 65 536 (madrl_waterworld_create refuses it): "
+                "fewer sensors or fewer pursuers" % lds)
+    return None
+
+
 def add_waterworld_shape(n_pursuers, n_evaders, n_poison, n_sensors, obs_dim=None):
     if obs_dim is None:
         obs_dim = n_sensors * 7 + 2 + 1          # speed features and the agent id (the reference's defaults)
-    if n_pursuers + n_evaders + n_poison > 62 or 2 * n_pursuers > 64 or not 1 <= n_sensors <= 256:
-        raise ValueError("no Waterworld kernel for this shape at all (madrl_waterworld_create refuses it)")
+    why = waterworld_shape_refusal(n_pursuers, n_evaders, n_poison, n_sensors, obs_dim)
+    if why is not None:   # before anything is written: a line that cannot compile would break every later build
+        raise ValueError("no specialised Waterworld kernel for this shape: " + why)
     return _append_local("waterworld_specializations.def", "X(%d, %d, %d, %d, %d)   // added by madrl_amd.build" % (n_pursuers, n_evaders, n_poison, n_sensors, obs_dim))
+
+
+def waterworld_line_of(n_pursuers, n_evaders, n_poison=10, n_sensors=30, speed_features=True, addid=True):
+    """the dispatch key of ww_launch (waterworld.hip) restated: (Np, Ne, Npo, K, ww_obs_dim_of) of a configuration, compared with every
+    line of the lists -> the lines that match it (the host takes the last one; a list without duplicates has at most one)"""
+    key = (int(n_pursuers), int(n_evaders), int(n_poison), int(n_sensors),
+           int(n_sensors) * (7 if speed_features else 4) + 2 + (1 if addid else 0))
+    return [line for line in waterworld_lines() if line == key]
+
+
+def waterworld_lines():
+    """the X(...) argument tuples of csrc/waterworld_specializations.def and of its .local.def companion, in file order, duplicates kept"""
+    out = []
+    for path in (os.path.join(CSRC, "waterworld_specializations.def"), os.path.join(CSRC, "waterworld_specializations.local.def")):
+        if os.path.exists(path):
+            out += [tuple(int(v) for v in m.group(1).split(",")) for m in re.finditer(r"^\s*X\(([^)]*)\)", open(path).read(), re.M)]
+    return out
 
 
 def specialised_shapes(def_name):

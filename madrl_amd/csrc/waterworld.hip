@@ -94,7 +94,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void
 
 }  // namespace
 // =================================================================== host side / C ABI
-struct madrl_waterworld : ParticleHandle<madrl_waterworld_config, WwDev> {};
+struct madrl_waterworld : ParticleHandle<madrl_waterworld_config, WwDev> {
+    mutable int32_t last_launch = MADRL_WW_LAUNCH_NONE;  // the kernel family of the last reset / step launch (madrl_waterworld_last_launch_kernel)
+};
 
 namespace {
 
@@ -180,7 +182,11 @@ const WwSpec WW_SPECS[] = {
 int ww_launch(const madrl_waterworld *h, const WwIO &io, int mode, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     const WwDev &d = h->dev;
-    if (h->cfg.crowd) return ww_crowd_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, h->pending, h->live, h->ranged, stream);
+    if (h->cfg.crowd) {
+        const int rc = ww_crowd_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, h->pending, h->live, h->ranged, stream);
+        if (rc == MADRL_OK) h->last_launch = MADRL_WW_LAUNCH_CROWD;
+        return rc;
+    }
     const dim3 g = particle_grid(h->max_blocks, d.n_envs), b(64);
     const bool fused = io.st != nullptr;
     if (h->live != nullptr) {  // per-env particle counts: the generic body at the capacity's LDS bytes, whatever the shape
@@ -189,6 +195,7 @@ int ww_launch(const madrl_waterworld *h, const WwIO &io, int mode, void *stream)
         if (mode == 0) hipLaunchKernelGGL(waterworld_kernel_live<0>, g, b, h->lds_bytes, s, h->dev, io, cn);
         else hipLaunchKernelGGL(waterworld_kernel_live<1>, g, b, h->lds_bytes, s, h->dev, io, cn);
         MADRL_HIP_TRY(hipGetLastError());
+        h->last_launch = MADRL_WW_LAUNCH_LIVE;
         return MADRL_OK;
     }
     if (h->ranged) {  // per-pursuer sensor ranges: the generic body with the ranges in LDS, whatever the shape
@@ -196,6 +203,7 @@ int ww_launch(const madrl_waterworld *h, const WwIO &io, int mode, void *stream)
         if (mode == 0) hipLaunchKernelGGL(waterworld_kernel_ranges<0>, g, b, h->lds_bytes, s, h->dev, io);
         else hipLaunchKernelGGL(waterworld_kernel_ranges<1>, g, b, h->lds_bytes, s, h->dev, io);
         MADRL_HIP_TRY(hipGetLastError());
+        h->last_launch = MADRL_WW_LAUNCH_RANGED;
         return MADRL_OK;
     }
     const WwSpec *spec = nullptr;
@@ -211,12 +219,16 @@ int ww_launch(const madrl_waterworld *h, const WwIO &io, int mode, void *stream)
         else hipLaunchKernelGGL((waterworld_kernel<1, 0, 0, 0, 0, false>), g, b, h->lds_bytes, s, h->dev, io);
     }
     MADRL_HIP_TRY(hipGetLastError());
+    h->last_launch = spec ? MADRL_WW_LAUNCH_SPECIALISED : MADRL_WW_LAUNCH_GENERIC;
     return MADRL_OK;
 }
 
 // the half-precision entries: waterworld_kernel_f16 (waterworld_f16.hip) on the handle's shape, the half pointer in io.obs
 int ww_launch_f16(const madrl_waterworld *h, const WwIO &io, int mode, void *stream) {
-    return ww_f16_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, stream);
+    int specialised = 0;
+    const int rc = ww_f16_launch(&h->dev, &io, mode, h->max_blocks, h->lds_bytes, stream, &specialised);
+    if (rc == MADRL_OK) h->last_launch = specialised ? MADRL_WW_LAUNCH_SPECIALISED : MADRL_WW_LAUNCH_GENERIC;
+    return rc;
 }
 
 __global__ void ww_state_copy_kernel(const WwDev d, float *pos, float *vel, float *obst, int32_t *t, uint32_t *tick,
@@ -267,6 +279,12 @@ int madrl_waterworld_create(const madrl_waterworld_config *cfg, const double *se
 }
 
 int madrl_waterworld_kernel_kind(madrl_waterworld *h, int32_t *out) { return particle_kernel_kind(h, out); }
+
+int madrl_waterworld_last_launch_kernel(const madrl_waterworld *h, int32_t *out) {
+    if (!h || !out) return fail(MADRL_EINVAL, "last_launch_kernel: NULL argument");
+    *out = h->last_launch;
+    return MADRL_OK;
+}
 
 void madrl_waterworld_destroy(madrl_waterworld *h) { particle_destroy(h); }
 

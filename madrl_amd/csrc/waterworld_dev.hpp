@@ -52,7 +52,8 @@ int ww_crowd_launch(const void *dev, const void *io, int mode, int64_t max_block
                     bool ranged, void *stream);
 // waterworld_f16.hip: waterworld_kernel_f16 on dev's shape (a line of waterworld_specializations.def: its specialised instantiation), io.obs
 // holding the binary16 destination.  The caller has checked the handle: no crowd, counts, ranges or StandardizedEnv (particle_half_ok).
-int ww_f16_launch(const void *dev, const void *io, int mode, int64_t max_blocks, size_t lds_bytes, void *stream);
+// *specialised: 1 / 0, whether the launch took a line's instantiation (madrl_waterworld_last_launch_kernel), written once it is enqueued.
+int ww_f16_launch(const void *dev, const void *io, int mode, int64_t max_blocks, size_t lds_bytes, void *stream, int *specialised);
 // the dynamic LDS of one ww_crowd_kernel workgroup
 size_t ww_crowd_lds_bytes(int n_pursuers, int n_evaders, int n_poison, int n_sensors, int rec_dw);
 

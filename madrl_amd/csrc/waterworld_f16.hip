@@ -58,7 +58,7 @@ const WwSpecF16 WW_SPECS_F16[] = {
 
 namespace madrl {
 
-int ww_f16_launch(const void *dev, const void *io_, int mode, int64_t max_blocks, size_t lds_bytes, void *stream) {
+int ww_f16_launch(const void *dev, const void *io_, int mode, int64_t max_blocks, size_t lds_bytes, void *stream, int *specialised) {
     hipStream_t s = (hipStream_t)stream;
     const WwDev &d = *static_cast<const WwDev *>(dev);
     const WwIO &io = *static_cast<const WwIO *>(io_);
@@ -70,6 +70,7 @@ int ww_f16_launch(const void *dev, const void *io_, int mode, int64_t max_blocks
     else if (mode == 0) hipLaunchKernelGGL((waterworld_kernel_f16<0, 0, 0, 0, 0>), g, b, lds_bytes, s, d, io);
     else hipLaunchKernelGGL((waterworld_kernel_f16<1, 0, 0, 0, 0>), g, b, lds_bytes, s, d, io);
     MADRL_HIP_TRY(hipGetLastError());
+    *specialised = spec != nullptr;
     return MADRL_OK;
 }
 

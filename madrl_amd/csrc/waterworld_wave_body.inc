@@ -16,6 +16,8 @@
     // registers, hoists out of the env loop per access pattern and -- at 5 waves per SIMD -- spills.
     constexpr int SPEC_BYTES = TNp > 0 ? (int)wave_lds_bytes(4 * (TNp + TNe + TNpo) + 4, TNp, TD, TK, TNe, TNpo) : 16;
     static_assert(TNp == 0 || TD > 0, "a specialised shape fixes the observation width too");
+    static_assert(SPEC_BYTES <= 64 * 1024, "this line of waterworld_specializations.def (or of its .local.def companion) needs more than 64 KiB of static LDS: "
+                                           "madrl_waterworld_create refuses such a shape; `python -m madrl_amd.build --waterworld-shape` checks a shape before it lists it");
     extern __shared__ __attribute__((aligned(16))) float smem_dyn[];
     __shared__ __attribute__((aligned(16))) float smem_static[SPEC_BYTES / 4];
     float *const smem = TNp > 0 ? smem_static : smem_dyn;

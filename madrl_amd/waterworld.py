@@ -160,6 +160,18 @@ class BatchedMAWaterWorld(BatchedParticleWorld):
                       "--waterworld-shape %d %d %d %d %d` compiles the specialised kernel for this shape (results are identical, a step takes about half the "
                       "time)" % (shape + shape), stacklevel=3)
 
+    _LAUNCH_KERNELS = ("none", "generic", "specialised", "live", "ranged", "crowd")
+
+    @property
+    def last_launch_kernel(self):
+        """the kernel family the handle's last reset / step launch ran on (include/madrl_hip.h, madrl_waterworld_last_launch_kernel): "none"
+        before the first launch of a handle, "specialised" for a fixed-shape launch of a shape in csrc/waterworld_specializations.def,
+        "generic" for any other fixed-shape one-wavefront launch, "live" / "ranged" for the per-env-count and per-pursuer-range entries,
+        "crowd" with crowd=True.  float32 and float16 rows report alike."""
+        out = C.c_int32()
+        _lib.check(_lib.lib().madrl_waterworld_last_launch_kernel(self._handle, C.byref(out)))
+        return self._LAUNCH_KERNELS[out.value]
+
     def get_param_values(self):
         return self.__dict__
 

@@ -24,7 +24,7 @@ def test_the_header_declares_the_half_call_next_to_the_float32_one():
     assert [" ".join(a.split()) for a in decl.split(",")] == [
         "const void *obs_f16", "int64_t n_rows", "int32_t obs_range", "int64_t row_stride", "int32_t cell_stride", "int32_t ch_offset",
         "const uint8_t *table_dev", "uint64_t seed", "int64_t row_id_base", "uint32_t tick", "uint32_t *tick_dev", "int32_t *actions", "void *stream"]
-    assert re.search(r"#define MADRL_ABI_VERSION\s+7\b", header)
+    assert re.search(r"#define MADRL_ABI_VERSION\s+8\b", header)
 
 
 def test_the_library_exports_it_and_the_binding_knows_13_arguments():
@@ -33,7 +33,7 @@ def test_the_library_exports_it_and_the_binding_knows_13_arguments():
     assert hasattr(L, "madrl_heuristic_pursuit_f16")
     res, args = _lib.SIGNATURES["madrl_heuristic_pursuit_f16"]
     assert res is C.c_int and len(args) == 13 and args == _ARGS == _lib.SIGNATURES["madrl_heuristic_pursuit"][1]
-    assert L.madrl_abi_version() == 7 == _lib.ABI_VERSION
+    assert L.madrl_abi_version() == 8 == _lib.ABI_VERSION
 
 
 def test_argument_checks_are_those_of_the_float32_call():

@@ -28,9 +28,9 @@ def test_signatures_and_abi_version():
     from madrl_amd import _lib
     assert "madrl_pursuit_step_to" in _lib.SIGNATURES and len(_lib.SIGNATURES["madrl_pursuit_step_to"][1]) == 9
     assert "madrl_pursuit_step_to_kernel_kind" in _lib.SIGNATURES and len(_lib.SIGNATURES["madrl_pursuit_step_to_kernel_kind"][1]) == 2
-    assert _lib.ABI_VERSION == 7
+    assert _lib.ABI_VERSION == 8
     if os.path.exists(_lib.SO_PATH):
-        assert _lib.lib().madrl_abi_version() == 7
+        assert _lib.lib().madrl_abi_version() == 8
     header = open(os.path.join(ROOT, "include", "madrl_hip.h")).read()
     assert re.search(r"int\s+madrl_pursuit_step_to\s*\(", header) and re.search(r"int\s+madrl_pursuit_step_to_kernel_kind\s*\(", header)
 

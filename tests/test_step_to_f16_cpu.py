@@ -35,7 +35,7 @@ def test_the_library_exports_both_symbols():
     from madrl_amd import _lib
     assert _lib.SIGNATURES["madrl_pursuit_step_to_f16"] == (C.c_int, [C.c_void_p] * 9)
     assert _lib.SIGNATURES["madrl_pursuit_step_to_f16_kernel_kind"] == (C.c_int, [C.c_void_p] * 2)
-    assert L.madrl_abi_version() == 7 == _lib.ABI_VERSION
+    assert L.madrl_abi_version() == 8 == _lib.ABI_VERSION
     header = open(os.path.join(HERE, "..", "include", "madrl_hip.h")).read()
     assert header.index("int madrl_pursuit_step_to(") < header.index("int madrl_pursuit_step_to_f16(") < header.index("int madrl_pursuit_step_sharded(")
 

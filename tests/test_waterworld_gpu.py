@@ -8,9 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+from waterworld_parity import DEV, TOL, vs_f32_oracle
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-TOL = 1e-5  # BASELINE.json north_star: "within 1e-5 for Waterworld ... float32 state"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILES = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "waterworld_*.npz")))
 gid = lambda p: os.path.basename(p)[:-4]
@@ -75,47 +75,9 @@ CASES = {
 LIMITS = dict(n_pursuers=20, n_evaders=22, n_poison=20, n_sensors=70, obstacle_loc=None, reward_mech="global")
 
 
-def _vs_f32_oracle(case, teacher_forced, N=256, T=60, H=20):
-    """Seeded rollout with auto-reset against the float32 oracle: same statement order, their own Philox on both sides.
-    teacher_forced: the kernel takes the oracle's state at the start of every step (a divergence cannot compound: the comparison of each
-    step stands on its own, tolerance 1e-5 as north_star asks).  Otherwise NOTHING is ever copied across: 60 steps, resets, respawns and
-    random obstacles included, must stay identical in every bit of every output and of the state -- one flipped `<=` would show."""
-    from oracle import waterworld as ww
-    kw = CASES[case] if isinstance(case, str) else case
-    env = _mk(N, seed=77, env_id_base=500, max_steps=H, auto_reset=True, **kw)
-    orc = ww.WaterworldOracle(n_envs=N, seed=77, env_id_base=500, max_steps=H, dtype=np.float32, **kw)
-    obs = env.reset()
-    oobs = orc.reset()
-    tol = TOL if teacher_forced else 0.0
-    assert np.abs(obs.cpu().numpy() - oobs).max() <= tol
-    rng = np.random.RandomState(1)
-    exact = total = 0
-    catches = 0
-    for t in range(T):
-        if teacher_forced:
-            st = orc.get_state()
-            env.set_state(pos=st["pos"], vel=st["vel"], obst=st["obst"], t=st["t"], tick=st["tick"].view(np.int32))
-        act = rng.uniform(-1, 1, size=(N, kw["n_pursuers"], 2)).astype(np.float32)
-        obs, rew, done, info = env.step(act)
-        oobs, orew, odone, oinfo = orc.step(act)
-        assert np.array_equal(done.cpu().numpy(), odone.astype(bool)), "done step %d" % t
-        assert np.array_equal(info["evcatches"].cpu().numpy(), oinfo[:, 0]), "evcatches step %d" % t
-        assert np.array_equal(info["pocatches"].cpu().numpy(), oinfo[:, 1]), "pocatches step %d" % t
-        assert np.abs(rew.cpu().numpy() - orew).max() <= tol, "rewards step %d" % t
-        catches += int(oinfo.sum())
-        if odone.any():
-            orc.reset(mask=odone)
-        got = obs.cpu().numpy()
-        assert np.abs(got - orc.obs).max() <= tol, "obs step %d: %g" % (t, np.abs(got - orc.obs).max())
-        gst = env.get_state()
-        ost = orc.get_state()
-        assert np.abs(gst["pos"].cpu().numpy() - ost["pos"]).max() <= tol
-        assert np.abs(gst["vel"].cpu().numpy() - ost["vel"]).max() <= tol
-        assert np.array_equal(gst["t"].cpu().numpy(), ost["t"])
-        assert np.array_equal(gst["tick"].cpu().numpy().view(np.uint32), ost["tick"])
-        exact += int(np.array_equal(got, orc.obs)); total += 1
-    assert catches > 0, "no catches"
-    print("bit-identical observation batches: %d / %d" % (exact, total))
+def _vs_f32_oracle(case, teacher_forced, **run):
+    """waterworld_parity.vs_f32_oracle (shared with test_waterworld_specialised_gpu.py) on a case of CASES or on constructor arguments"""
+    return vs_f32_oracle(CASES[case] if isinstance(case, str) else case, teacher_forced, **run)
 
 
 @pytest.mark.parametrize("case", sorted(CASES), ids=sorted(CASES))
@@ -160,16 +122,30 @@ def test_drawn_configurations_free_running_vs_f32_oracle(i):
         del CASES["drawn_%d" % i]
 
 
-@pytest.mark.parametrize("shape", ["c3_bitrows", "generic"])
+# shape -> (constructor arguments, the kernel family that takes them, whether the crafted pairs are the LAST of their classes)
+THRESHOLD_SHAPES = {
+    "c3_bitrows": (dict(n_pursuers=5, n_evaders=10, n_coop=1), "specialised", False),
+    "generic": (dict(n_pursuers=3, n_evaders=10, n_coop=1, n_poison=5, n_sensors=12), "generic", False),
+    # test lines of waterworld_specializations.def: four words per ballot matrix (pursuer 7 x evader 29 is bit 239: word 3 of col_ev) and
+    # the byte matrices of a specialised kernel (WE = 5)
+    "words4": (dict(n_pursuers=8, n_evaders=30, n_coop=1, n_poison=16, n_sensors=8), "specialised", True),
+    "spec_bytes": (dict(n_pursuers=10, n_evaders=30, n_coop=1, n_poison=16, n_sensors=6), "specialised", True),
+}
+
+
+@pytest.mark.parametrize("shape", ["c3_bitrows", "generic", "words4", "spec_bytes"])
 def test_contact_tests_at_the_threshold_match_the_sqrt_formulation(shape):
     """The kernel tests `dx*dx + dy*dy <= sq_threshold(thr)` where the reference (and the float32 oracle) test `sqrt(...) <= thr`.
     The two must give the same truth value for EVERY input: crafted states put an evader / a poison at the contact distance of a
-    pursuer, and an evader at the rebound distance of the obstacle, within +-8 ulps of the threshold along 256 directions."""
+    pursuer, and an evader at the rebound distance of the obstacle, within +-8 ulps of the threshold along 256 directions.
+    words4 / spec_bytes: the touching pursuers are the last two, the evader and the poison the last of their classes -- the highest bits
+    of the ballot words, the last bytes of the byte matrices."""
     from oracle import waterworld as ww
-    kw = dict(n_pursuers=5, n_evaders=10, n_coop=1) if shape == "c3_bitrows" else dict(n_pursuers=3, n_evaders=10, n_coop=1, n_poison=5, n_sensors=12)
+    kw, family, last = THRESHOLD_SHAPES[shape]
     Np, Ne = kw["n_pursuers"], kw["n_evaders"]
     Npo = kw.get("n_poison", 10)
     NP = Np + Ne + Npo
+    pu_ev, pu_po, ev_hit, po_hit = (Np - 1, Np - 2, Np + Ne - 1, Np + Ne + Npo - 1) if last else (0, 1, Np, Np + Ne)
     N = 17 * 256
     env = _mk(N, seed=3, max_steps=1000, auto_reset=False, **kw)
     orc = ww.WaterworldOracle(n_envs=N, seed=3, max_steps=1000, dtype=np.float32, **kw)
@@ -183,11 +159,15 @@ def test_contact_tests_at_the_threshold_match_the_sqrt_formulation(shape):
         d = (thr.view(np.int32) + k.astype(np.int32)).view(np.float32)     # thr moved by k ulps
         return np.stack([center[:, 0] + d * np.cos(th).astype(np.float32), center[:, 1] + d * np.sin(th).astype(np.float32)], -1).astype(np.float32)
     pos = np.zeros((N, NP, 2), np.float32)
-    far = np.linspace(0.02, 0.12, NP).astype(np.float32)
-    pos[:, :, 0] = 0.9; pos[:, :, 1] = far[None, :] * 4 + 0.3               # everything parked away from everything else
-    pos[:, 0] = (0.30, 0.12); pos[:, 1] = (0.62, 0.12)
-    pos[:, Np] = at_distance(pos[:, 0], r_pu + r_ev, k, th)                # evader 0 at contact distance of pursuer 0
-    pos[:, Np + Ne] = at_distance(pos[:, 1], r_pu + r_po, k, th)           # poison 0 at contact distance of pursuer 1
+    if last:   # 54 / 56 particles: the pursuers parked at the left wall, the evaders and poison at the right one, nobody near the obstacle
+        pos[:, :Np, 0] = 0.05; pos[:, :Np, 1] = np.linspace(0.3, 0.7, Np).astype(np.float32)[None, :]
+        pos[:, Np:, 0] = 0.95; pos[:, Np:, 1] = np.linspace(0.05, 0.95, NP - Np).astype(np.float32)[None, :]
+    else:
+        far = np.linspace(0.02, 0.12, NP).astype(np.float32)
+        pos[:, :, 0] = 0.9; pos[:, :, 1] = far[None, :] * 4 + 0.3           # everything parked away from everything else
+    pos[:, pu_ev] = (0.30, 0.12); pos[:, pu_po] = (0.62, 0.12)
+    pos[:, ev_hit] = at_distance(pos[:, pu_ev], r_pu + r_ev, k, th)        # an evader at contact distance of a pursuer
+    pos[:, po_hit] = at_distance(pos[:, pu_po], r_pu + r_po, k, th)        # a poison at contact distance of another pursuer
     obst = np.tile(np.float32([0.5, 0.7]), (N, 1))
     pos[:, Np + 1] = at_distance(obst, r_ev + r_ob, k, th)                 # evader 1 at rebound distance of the obstacle
     vel = np.zeros((N, NP, 2), np.float32)
@@ -197,6 +177,7 @@ def test_contact_tests_at_the_threshold_match_the_sqrt_formulation(shape):
         e.set_state(pos=pos, vel=vel, obst=obst, t=st["t"], tick=np.asarray(st["tick"]).view(np.int32))
     act = np.zeros((N, Np, 2), np.float32)
     obs, rew, done, info = env.step(act)
+    assert env.last_launch_kernel == family
     oobs, orew, odone, oinfo = orc.step(act)
     assert np.array_equal(info["evcatches"].cpu().numpy(), oinfo[:, 0])
     assert np.array_equal(info["pocatches"].cpu().numpy(), oinfo[:, 1])

@@ -32,7 +32,7 @@ def test_set_sensor_ranges_is_declared_and_exported():
     from madrl_amd import _lib
     header = open(os.path.join(ROOT, "include", "madrl_hip.h")).read()
     assert re.search(r"int madrl_waterworld_set_sensor_ranges\(madrl_waterworld \*h, const double \*ranges_host\);", header)
-    assert re.search(r"#define MADRL_ABI_VERSION 7\b", header)
+    assert re.search(r"#define MADRL_ABI_VERSION 8\b", header)
     assert len(_lib.SIGNATURES["madrl_waterworld_set_sensor_ranges"][1]) == 2
     fn = _lib.lib().madrl_waterworld_set_sensor_ranges
     assert len(fn.argtypes) == 2
