@@ -1,5 +1,14 @@
 """Env API mirror of madrl_environments/__init__.py:9-119 (Agent, AbstractMAEnv)."""
 import numpy as np
+import torch
+
+
+def done_bytes(done, info):
+    """The done bytes of a batched step (uint8 [N]: bit 0 terminal, bit 1 time limit, bit 7 overflow mark, as `Trajectory` documents):
+    info['done_bits'] where the env gives them, else its bool `done` as bytes."""
+    if isinstance(info, dict) and "done_bits" in info:
+        return info["done_bits"]
+    return done.to(torch.uint8).contiguous()
 
 
 def stack_dict_list(dict_list):
@@ -49,6 +58,21 @@ class AbstractMAEnv(object):
 
     def step(self, actions):
         raise NotImplementedError()
+
+    # The batched envs' sampler entry (RolloutCollector calls nothing else to step an env).
+    takes_obs_out = False   # whether step_into honours `obs_out` right now (a class attribute or a property)
+
+    def step_into(self, actions, rew_out, done_out, obs_out=None):
+        """step() for a sampler loop: rewards go to `rew_out` (float32 [N, A]) and the done bytes (`done_bytes`) to `done_out` (uint8 [N]),
+        both contiguous tensors on the env's device, e.g. slot t of a trajectory; returns the observation tensor the next action is chosen
+        from.  actions: anything step() accepts.  obs_out (only where `takes_obs_out`): the step writes its observations there, and the
+        returned tensor is a view of it.  This default is step() plus the two copies; an env whose kernel takes destinations overrides it."""
+        if obs_out is not None:
+            raise ValueError("%s.step_into has no observation destination (takes_obs_out is False)" % type(self).__name__)
+        obs, rew, done, info = self.step(actions)
+        rew_out.copy_(rew)
+        done_out.copy_(done_bytes(done, info))
+        return obs
 
     @property
     def is_terminal(self):

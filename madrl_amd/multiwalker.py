@@ -161,18 +161,25 @@ class BatchedMultiWalkerEnv(AbstractMAEnv):
         terminate_on_fall off exceeds them after a few hundred steps.
         rew_out float32 [N, W] / done_out uint8 [N]: optional destinations the kernel writes instead of the env's buffers.
         obs_out: the same for the observations (contiguous float32, N * W * obs_dim elements); its [N, W, D] view is returned."""
+        rew = self._rew if rew_out is None else rew_out
+        dn = self._done if done_out is None else done_out
+        obs = self.step_into(actions, rew, dn, obs_out)
+        return obs, rew, (dn & 1).bool(), {"done_bits": dn, "truncated": (dn & 2).bool(), "overflow": (dn & 128).bool()}
+
+    takes_obs_out = True
+
+    def step_into(self, actions, rew_out, done_out, obs_out=None):
+        """AbstractMAEnv.step_into as the launch of step() alone: its checks and the kernel, none of the three bool tensors of its result"""
         N, W = self.n_envs, int(self.n_walkers)
         a = torch.as_tensor(actions, device=self.device)
         if a.numel() != N * W * 4:
             raise AssertionError("actions have %d elements, expected %d" % (a.numel(), N * W * 4))  # :360-361
         a = a.reshape(N, W, 4).to(torch.float32).contiguous()
-        rew = self._rew if rew_out is None else rew_out
-        dn = self._done if done_out is None else done_out
-        assert rew.dtype == torch.float32 and rew.numel() == N * W and dn.dtype == torch.uint8 and dn.numel() == N
+        assert rew_out.dtype == torch.float32 and rew_out.numel() == N * W and done_out.dtype == torch.uint8 and done_out.numel() == N
         obs = self._obs if obs_out is None else _lib.obs_destination(obs_out, self._obs)
-        _lib.check(_lib.lib().madrl_multiwalker_step(self._handle, _lib.ptr(a), _lib.ptr(obs), _lib.ptr(rew),
-                                                     _lib.ptr(dn), _lib.current_stream(self.device)))
-        return obs, rew, (dn & 1).bool(), {"done_bits": dn, "truncated": (dn & 2).bool(), "overflow": (dn & 128).bool()}
+        _lib.check(_lib.lib().madrl_multiwalker_step(self._handle, _lib.ptr(a), _lib.ptr(obs), _lib.ptr(rew_out),
+                                                     _lib.ptr(done_out), _lib.current_stream(self.device)))
+        return obs
 
     def bodies(self):
         N, W, dev = self.n_envs, int(self.n_walkers), self.device

@@ -250,16 +250,33 @@ class BatchedParticleWorld(AbstractMAEnv):
         of a trajectory tensor) the kernel writes the observations to instead of the env's own buffer; its [N, n_agents, D] view is returned.
         A float16 destination needs 2-byte alignment only.  Refused while a fused StandardizedEnv is bound: the observation tensor the
         kernel writes then belongs to the wrapper."""
-        N, Na = self.n_envs, getattr(self, self._COUNTS[0])
-        if not self._conforming(action):
-            a = torch.as_tensor(action, device=self.device)
-            if a.numel() != N * Na * 2:
-                raise AssertionError("action has %d elements, expected %d" % (a.numel(), N * Na * 2))  # waterworld.py:227, hostage.py:234
-            action = a.reshape(N, Na, 2).to(torch.float32).contiguous()
         r = None
         if respawn is not None:
-            r = torch.as_tensor(respawn, device=self.device).reshape(N, getattr(self, self._INJECT), 4).to(torch.float32).contiguous()
-        return self._launch_step(action, r, _lib.current_stream(self.device), obs_out)
+            r = torch.as_tensor(respawn, device=self.device).reshape(self.n_envs, getattr(self, self._INJECT), 4).to(torch.float32).contiguous()
+        return self._launch_step(self._actions(action), r, _lib.current_stream(self.device), obs_out)
+
+    @property
+    def takes_obs_out(self):
+        return self._std is None
+
+    def step_into(self, actions, rew_out, done_out, obs_out=None):
+        """AbstractMAEnv.step_into: the kernel writes rewards and done bytes into the caller's tensors (the C ABI takes any device pointer).
+        While a fused StandardizedEnv is bound the rewards it hands out are the wrapper's: step() and the two copies then."""
+        if self._std is not None:
+            return super().step_into(actions, rew_out, done_out, obs_out)
+        N, Na = self.n_envs, getattr(self, self._COUNTS[0])
+        assert rew_out.dtype == torch.float32 and rew_out.numel() == N * Na and done_out.dtype == torch.uint8 and done_out.numel() == N
+        return self._launch_step(self._actions(actions), None, _lib.current_stream(self.device), obs_out, rew_out, done_out)[0]
+
+    def _actions(self, action):
+        """step()'s action argument as the float32 [N, n_agents, 2] tensor the kernel reads"""
+        if self._conforming(action):
+            return action
+        N, Na = self.n_envs, getattr(self, self._COUNTS[0])
+        a = torch.as_tensor(action, device=self.device)
+        if a.numel() != N * Na * 2:
+            raise AssertionError("action has %d elements, expected %d" % (a.numel(), N * Na * 2))  # waterworld.py:227, hostage.py:234
+        return a.reshape(N, Na, 2).to(torch.float32).contiguous()
 
     def _conforming(self, a):
         """an action tensor the kernel can read as it is (float32, contiguous, on the device, N * n_agents * 2 elements): no torch kernel needed"""
@@ -274,21 +291,22 @@ class BatchedParticleWorld(AbstractMAEnv):
             return None
         return self._launch_step(action, None, C.c_void_p(stream.cuda_stream))
 
-    def _launch_step(self, a, r, stream_ptr, obs_out=None):
+    def _launch_step(self, a, r, stream_ptr, obs_out=None, rew=None, done=None):
+        """rew / done: where the kernel writes rewards and done bytes (None: the env's own buffers)"""
         std = getattr(self, "_std", None)
-        obs = self._obs
+        obs, rew, done = self._obs, self._rew if rew is None else rew, self._done if done is None else done
         if obs_out is not None:
             if std:
                 raise ValueError("obs_out: a fused StandardizedEnv is bound to this env, the kernel's observation output belongs to the wrapper")
             obs = _lib.obs_destination(obs_out, self._obs)
         step = _API[self._SYM].step_f16 if self._f16 else _API[self._SYM].step
-        _lib.check(step(self._handle, _lib.ptr(a), _lib.ptr(r), None if std else _lib.ptr(obs), _lib.ptr(self._rew),
-                        _lib.ptr(self._done), _lib.ptr(self._info), stream_ptr))
+        _lib.check(step(self._handle, _lib.ptr(a), _lib.ptr(r), None if std else _lib.ptr(obs), _lib.ptr(rew),
+                        _lib.ptr(done), _lib.ptr(self._info), stream_ptr))
         # `done` is a bool VIEW of the byte the kernel wrote (0 / 1): no torch kernel runs after the launch
-        info = {self._INFO_KEYS[0]: self._info[:, 0], self._INFO_KEYS[1]: self._info[:, 1], "done_bits": self._done}
+        info = {self._INFO_KEYS[0]: self._info[:, 0], self._INFO_KEYS[1]: self._info[:, 1], "done_bits": done}
         if std:  # fused StandardizedEnv: standardised observations and scaled / normalised rewards straight from the kernel
-            return std["obs_out"], std["rew_out"], self._done.view(torch.bool), info
-        return obs, self._rew, self._done.view(torch.bool), info
+            return std["obs_out"], std["rew_out"], done.view(torch.bool), info
+        return obs, rew, done.view(torch.bool), info
 
     # ------------------------------------------------------------------ per-env particle counts (per_env_counts=True)
     def _require_counts(self, what):

@@ -383,7 +383,14 @@ class BatchedPursuitEvade(AbstractMAEnv):
         [N, E], entry k drives the k-th remaining evader (scripted evader_controller).
         rew_out float32 [N, P] / done_out uint8 [N]: optional contiguous destinations (e.g. a slot of a trajectory tensor) the
         kernel writes instead of the env's own buffers -- the C ABI takes any device pointer, no copy afterwards."""
-        N, P, E = self.n_envs, int(self.n_pursuers), int(self.n_evaders)
+        rew, dn = self._step(actions, evader_actions, rew_out, done_out, None)
+        return self._step_result(rew, dn)
+
+    def _step(self, actions, evader_actions, rew_out, done_out, dest):
+        """What step(), step_to() and step_into() share: the checks, the conversions and the launch -- into `dest` (which becomes the
+        current buffer), or with dest=None the plain step: in place, a half-precision env into the other buffer of its pair.  Returns the
+        reward and done-byte tensors the kernel wrote (the env's own where none were given)."""
+        N, P = self.n_envs, int(self.n_pursuers)
         if getattr(self, "_needs_reset", False):
             raise RuntimeError("update_curriculum / set_param_values changed the agent counts: the running episodes cannot continue "
                                "(the reference applies new counts at the next reset(), pursuit_evade.py:173-199) -- call reset() first")
@@ -392,22 +399,21 @@ class BatchedPursuitEvade(AbstractMAEnv):
         else:
             act = self._i32(actions, (N, P), "actions")
         # evader control (train_pursuit=False): the opponents are the pursuers, one injected action per pursuer
-        eact = self._i32(evader_actions, (N, E if self.train_pursuit else P), "evader_actions")
-        if self._half:   # into the other internal buffer
-            rew = self._rew if rew_out is None else rew_out
-            dn = self._done if done_out is None else done_out
-            assert rew.dtype == torch.float32 and rew.numel() == N * P and dn.dtype == torch.uint8 and dn.numel() == N
-            self._launch_step_to(act, eact, self._half_next(), rew, dn)
-            return self._step_result(rew, dn)
-        self._check_obs_untouched()
-        self._obs_is_fresh = False
+        eact = self._i32(evader_actions, (N, int(self.n_evaders) if self.train_pursuit else P), "evader_actions")
         rew = self._rew if rew_out is None else rew_out
         dn = self._done if done_out is None else done_out
         assert rew.dtype == torch.float32 and rew.numel() == N * P and dn.dtype == torch.uint8 and dn.numel() == N
+        if dest is None and self._half:
+            dest = self._half_next()
+        if dest is not None:
+            self._launch_step_to(act, eact, dest, rew, dn)
+            return rew, dn
+        self._check_obs_untouched()
+        self._obs_is_fresh = False
         _lib.check(_lib.lib().madrl_pursuit_step(self._handle, _lib.ptr(act), _lib.ptr(eact), _lib.ptr(self._obs),
                                                  _lib.ptr(rew), _lib.ptr(dn), _lib.ptr(self._removed),
                                                  self._stream()))
-        return self._step_result(rew, dn)
+        return rew, dn
 
     def _obs_destination(self, obs_out):
         """obs_out of step_to / step_into as the flat [N, P, D] tensor the env adopts, or None when it IS the current buffer (a plain step)"""
@@ -452,21 +458,7 @@ class BatchedPursuitEvade(AbstractMAEnv):
         The one-wavefront, multi-wavefront and crowd shapes of csrc/pursuit_to_specializations.def have two-buffer fast kernels (with
         per-env agent counts: the XL / XLG / XLC lines); every other handle (train_pursuit=False included) runs this call on the generic
         kernel (step_to_kernel_kind)."""
-        N, P, E = self.n_envs, int(self.n_pursuers), int(self.n_evaders)
-        dest = self._obs_destination(obs_out)
-        if dest is None:
-            return self.step(actions, evader_actions=evader_actions, rew_out=rew_out, done_out=done_out)
-        if getattr(self, "_needs_reset", False):
-            raise RuntimeError("update_curriculum / set_param_values changed the agent counts -- call reset() first")
-        if type(actions) is torch.Tensor and actions.dtype is torch.int32 and actions.shape == (N, P) and actions.device == self.device and actions.is_contiguous():
-            act = actions
-        else:
-            act = self._i32(actions, (N, P), "actions")
-        eact = self._i32(evader_actions, (N, E if self.train_pursuit else P), "evader_actions")
-        rew = self._rew if rew_out is None else rew_out
-        dn = self._done if done_out is None else done_out
-        assert rew.dtype == torch.float32 and rew.numel() == N * P and dn.dtype == torch.uint8 and dn.numel() == N
-        self._launch_step_to(act, eact, dest, rew, dn)
+        rew, dn = self._step(actions, evader_actions, rew_out, done_out, self._obs_destination(obs_out))
         return self._step_result(rew, dn)
 
     @property
@@ -478,26 +470,13 @@ class BatchedPursuitEvade(AbstractMAEnv):
         _lib.check(kind(self._handle, C.byref(out)))
         return {_lib.KERNEL_GENERIC: "generic", _lib.KERNEL_WAVE: "wave"}[out.value]
 
+    takes_obs_out = True
+
     def step_into(self, actions, rew_out, done_out, obs_out=None):
-        """The launch of step() alone, for a sampler loop that keeps everything on the device: rewards and done bits go to the given
-        trajectory slots, the observation view is returned, and none of the small torch kernels that build step()'s `done` / `info`
-        tensors run (six launches of ~5 us each: a third of a 65 536-env rollout step, profiles/r05_rollout).  actions: int32 [N, P]
-        contiguous on the env's device.  obs_out: the observations go there, as in step_to()."""
-        N, P = self.n_envs, int(self.n_pursuers)
-        if getattr(self, "_needs_reset", False):
-            raise RuntimeError("update_curriculum / set_param_values changed the agent counts -- call reset() first")
-        assert actions.dtype == torch.int32 and actions.is_contiguous() and actions.numel() == N * P
-        assert rew_out.dtype == torch.float32 and rew_out.numel() == N * P and done_out.dtype == torch.uint8 and done_out.numel() == N
-        dest = self._obs_destination(obs_out) if obs_out is not None else None
-        if dest is None and self._half:
-            dest = self._half_next()
-        if dest is not None:
-            self._launch_step_to(actions, None, dest, rew_out, done_out)
-            return self._obs_view()
-        self._check_obs_untouched()
-        self._obs_is_fresh = False
-        _lib.check(_lib.lib().madrl_pursuit_step(self._handle, _lib.ptr(actions), None, _lib.ptr(self._obs), _lib.ptr(rew_out), _lib.ptr(done_out),
-                                                 _lib.ptr(self._removed), self._stream()))
+        """AbstractMAEnv.step_into as the launch of step() alone, for a sampler loop that keeps everything on the device: rewards and done
+        bits go to the given trajectory slots, the observation view is returned, and nothing of step()'s result is built.  actions: as
+        in step() (the sampler's own int32 [N, P] tensor is read as it is).  obs_out: the observations go there, as in step_to()."""
+        self._step(actions, None, rew_out, done_out, None if obs_out is None else self._obs_destination(obs_out))
         return self._obs_view()
 
     def _step_result(self, rew, dn):

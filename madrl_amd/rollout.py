@@ -8,6 +8,8 @@ discounted-return / GAE post-processing those samplers apply (runners/rurllab.py
 The env must be an `auto_reset` batched env (episode boundaries are the done flags; the observation
 returned by a done step already belongs to the next episode) or be shorter-lived than the horizon.
 """
+import inspect
+
 import numpy as np
 import torch
 
@@ -58,8 +60,9 @@ class RolloutCollector(object):
     env copies alive between iterations."""
 
     def __init__(self, env, policy, horizon, discount=0.99, gae_lambda=1.0, store_observations=False, graph=False, obs_slots=None):
-        """store_observations=True over an env whose step takes an observation destination (BatchedPursuitEvade.step_into / step_to,
-        `obs_out=` of the Waterworld, hostage and MultiWalker steps): the step kernel of step t writes slot t + 1 of a [T + 1]-slot
+        """env: a batched env; it is stepped through AbstractMAEnv.step_into alone.
+        store_observations=True over an env whose step_into takes an observation destination (`env.takes_obs_out`: BatchedPursuitEvade,
+        the Waterworld and hostage worlds, MultiWalker): the step kernel of step t writes slot t + 1 of a [T + 1]-slot
         observation tensor itself -- observations = slots 0 .. T-1, last_observation = slot T -- and the only observation-sized copy of a
         horizon is the one that brings the previous horizon's last observation to slot 0.  Other envs (wrappers such as ObservationBuffer
         or StandardizedEnv, a Waterworld or hostage world with a fused StandardizedEnv bound) keep the copy per step.  obs_slots: None = as described,
@@ -73,14 +76,8 @@ class RolloutCollector(object):
         self._obs = None
         self._buf = None
         self._use_graph, self._graph, self._calls = bool(graph), None, 0
-        import inspect
-        self._direct = "rew_out" in inspect.signature(env.step).parameters   # envs whose step() can write into caller buffers
-        self._into = hasattr(env, "step_into")                               # ... and that offer the launch alone (no done / info tensors built)
-        # ... and whose step kernel can write its observations into a trajectory slot (store_observations)
-        self._slots = False
-        if store_observations and (obs_slots is None or obs_slots) and getattr(env, "_std", None) is None:
-            self._slots = ("obs_out" in inspect.signature(env.step_into).parameters if self._into
-                           else "obs_out" in inspect.signature(env.step).parameters)
+        # the env's step kernel writes its observations into a trajectory slot (AbstractMAEnv.step_into, takes_obs_out)
+        self._slots = bool(store_observations and obs_slots is not False and env.takes_obs_out)
         if obs_slots and store_observations and not self._slots:
             raise ValueError("obs_slots=True: %s has no observation destination (obs_out=) in its step" % type(env).__name__)
         try:
@@ -159,30 +156,12 @@ class RolloutCollector(object):
             # buffer stays valid across the horizon boundary) into slot 1 -- slot 0 holds the same values
             if t == 0:
                 b["observations"][0].copy_(obs)
-            nxt = self._env_slots[t + 1]
         elif b["observations"] is not None:
             b["observations"][t].copy_(obs)
         if val is not None:
             b["values"][t].copy_(val)
-        if self._slots and self._into and act.dtype == torch.int32 and act.is_contiguous():
-            obs = env.step_into(act, b["rewards"][t], b["dones"][t], obs_out=nxt)
-        elif self._slots and self._into:   # (PursuitEvade with actions that need a conversion)
-            obs = env.step_to(act, nxt, rew_out=b["rewards"][t], done_out=b["dones"][t])[0]
-        elif self._slots and self._direct:
-            obs = env.step(act, rew_out=b["rewards"][t], done_out=b["dones"][t], obs_out=nxt)[0]
-        elif self._slots:
-            obs, rew, done, info = env.step(act, obs_out=nxt)
-            b["rewards"][t].copy_(rew)
-            b["dones"][t].copy_(info["done_bits"] if isinstance(info, dict) and "done_bits" in info else done.to(torch.uint8))
-        elif self._into and act.dtype == torch.int32 and act.is_contiguous():
-            obs = env.step_into(act, b["rewards"][t], b["dones"][t])
-        elif self._direct:   # the step kernel writes rewards / done bits straight into their trajectory slot
-            obs, rew, done, info = env.step(act, rew_out=b["rewards"][t], done_out=b["dones"][t])
-        else:
-            obs, rew, done, info = env.step(act)
-            b["rewards"][t].copy_(rew)
-            b["dones"][t].copy_(info["done_bits"] if isinstance(info, dict) and "done_bits" in info else done.to(torch.uint8))
-        self._obs = obs
+        # rewards and done bytes go to their trajectory slot, written by the step kernel itself where the env's takes destinations
+        self._obs = env.step_into(act, b["rewards"][t], b["dones"][t], obs_out=self._env_slots[t + 1] if self._slots else None)
 
     def _finish(self):
         obs, b = self._obs, self._buf

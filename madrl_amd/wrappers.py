@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .base import AbstractMAEnv, Agent, SingleEnvDelegate
+from .base import AbstractMAEnv, Agent, SingleEnvDelegate, done_bytes
 from .spaces import Box
 
 
@@ -114,11 +114,6 @@ class _Wrapper(AbstractMAEnv):
     def set_param_values(self, lut):
         self._unwrapped.set_param_values(lut)
 
-    def _done_u8(self, done, info):
-        if isinstance(info, dict) and "done_bits" in info:
-            return info["done_bits"]
-        return done.to(torch.uint8).contiguous()
-
 
 class ObservationBuffer(_Wrapper):
     """:143-201 -- keeps the last `buffer_size` observations of every agent, newest last:
@@ -161,7 +156,7 @@ class ObservationBuffer(_Wrapper):
 
     def _step_b(self, action, **kw):
         obs, rew, done, info = self._inner_step(action, **kw)
-        reset_mask = self._done_u8(done, info) if getattr(self._unwrapped, "auto_reset", False) else None
+        reset_mask = done_bytes(done, info) if getattr(self._unwrapped, "auto_reset", False) else None
         return self._push(obs, reset_mask), rew, done, info
 
 
@@ -294,7 +289,7 @@ class DiagnosticsWrapper(_Wrapper):
         obs, rew, done, info = self._inner_step(*args, **kw)
         rew_c = rew.contiguous()
         _lib.check(_lib.lib().madrl_wrap_diagnostics(
-            _lib.ptr(rew_c), _lib.ptr(self._done_u8(done, info)), _lib.ptr(self._ep_reward), _lib.ptr(self._ep_len),
+            _lib.ptr(rew_c), _lib.ptr(done_bytes(done, info)), _lib.ptr(self._ep_reward), _lib.ptr(self._ep_len),
             _lib.ptr(self._disc_ret), _lib.ptr(self._disc_pow), self.n_envs, self._A, float(self._discount), int(self._max_traj_len),
             _lib.ptr(self._out_reward), _lib.ptr(self._out_disc), _lib.ptr(self._out_len), _lib.ptr(self._out_fin), _stream(self)))
         to_log = {"finished": self._out_fin.bool(), "global/episode_reward_agents": self._out_reward,

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from madrl_amd.base import AbstractMAEnv
 from oracle import heuristics_oracle as ho
 from oracle import rollout_oracle as ro
 from oracle import wrappers_oracle as wo
@@ -121,8 +122,9 @@ def test_gae_every_column_beyond_the_grid_cap(T, N, A, use_values):
 
 
 # ---------------------------------------------------------------- b. ... through RolloutCollector
-class _SeededEnv(object):
-    """a batched env that plays seeded observation / reward / done tensors back (cf. ReplayEnv of tests/test_wrappers_gpu.py)"""
+class _SeededEnv(AbstractMAEnv):
+    """a batched env that plays seeded observation / reward / done tensors back (cf. ReplayEnv of tests/test_wrappers_gpu.py); the
+    collector steps it through the step_into it inherits"""
 
     def __init__(self, n_envs, n_agents, n_steps, seed):
         rng = np.random.RandomState(seed)
