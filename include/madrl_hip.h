@@ -554,8 +554,9 @@ int madrl_multiwalker_create(const madrl_multiwalker_config *cfg, int64_t n_envs
                              madrl_multiwalker **out);
 void madrl_multiwalker_destroy(madrl_multiwalker *h);
 /* How a step is issued.  fused: 0 (default) = three launches per b2World::Step (collide | solve | continuous pass + observe), 1 = one
- * launch (9 and 10 walkers always take three: the one-launch kernel is not built for the sixteen-lane class, multiwalker_impl.hpp).  use_spares: 1 (default) = an env whose episode ends takes the next episode prepared ahead of time, 0 = every auto-reset
- * runs the reset + trailing step in a second pass.  Results do not depend on either (tests/test_multiwalker_gpu.py). */
+ * launch, in every capacity class (tests/test_multiwalker_gpu.py runs it at 3, 8, 9 and 10 walkers).  use_spares: 1 (default) = an env whose
+ * episode ends takes the next episode prepared ahead of time, 0 = every auto-reset runs the reset + trailing step in a second pass.
+ * Results do not depend on either (tests/test_multiwalker_gpu.py). */
 int madrl_multiwalker_set_mode(madrl_multiwalker *h, int32_t fused, int32_t use_spares);
 int madrl_multiwalker_dims(const madrl_multiwalker *h, int32_t *n_bodies, int32_t *n_terrain);
 /* The kernels exist in three capacity classes -- room for 4 / 8 / 10 walkers, an env spread over 4 / 8 / 16 lanes of a wavefront (16 / 8 / 4

@@ -2271,7 +2271,7 @@ MW_HD_INLINE void step_solve(const Model &M, Hot &Wd, const ColdView &Cd, Scratc
     MW_TSTAMP(0, 3);
     // From here on the record is addressed through pointers found again from the lane id (par.cold_again / pool_again: the identity
     // everywhere but in the one-launch kernel of the sixteen-lane class): no per-lane pointer is then live across the sweeps above, which
-    // is where hipcc 7.2 parked them under a narrowed exec mask (multiwalker_impl.hpp, HAVE_FUSED).
+    // is where hipcc 7.2 parked them under a narrowed exec mask (multiwalker_impl.hpp, "the one-launch form and hipcc 7.2").
     const ColdView CdW = par.cold_again(Cd);
     Manifold *const MPW = par.pool_again(MP);
     MP_ = MPW;

@@ -1,6 +1,8 @@
 // multiwalker_impl.hpp -- batched MultiWalkerEnv for MI355X (gfx950 / CDNA4), float32: the kernels and the host side of ONE capacity
 // class.  Included by multiwalker_c4.hip / _c8.hip / _c10.hip, which set MW_CAPW (walkers the class has room for) and MW_NLANES (lanes
-// per env); multiwalker.hip holds the C ABI and picks the class by n_walkers.
+// per env); multiwalker.hip holds the C ABI, checks its arguments and picks the class by n_walkers.  The host side here is the class's handle
+// (MwHandle, derived from multiwalker_class.hpp's madrl_multiwalker) and the three functions of its MwClass entry; where things lie in the
+// caller's state buffer is multiwalker_layout.hpp's mw_layout and nobody else's.
 //
 // SIXTEEN ENVS PER WAVEFRONT, FOUR LANES PER ENV (up to four walkers; eight envs of eight lanes for 5 .. 8 walkers, four envs of sixteen
 // lanes for 9 and 10 -- the reference's curriculum, lessons/multiwalker/env.yaml:1-27).  A b2World::Step of this env is a long chain of
@@ -25,6 +27,7 @@
 #if defined(MADRL_MW_TIMING)
 // measurement build (scripts/variants.sh, never the shipped library): s_memtime stamps of a wavefront's first lane and a few per-env
 // counters, per block, for the solver launch (p = 0) and the continuous-pass launch (p = 1); read back by madrl_multiwalker_debug_read
+// (multiwalker_c4.hip, the one unit the recipe compiles with the macro)
 #define MW_DBG_BLOCKS 4096
 static __device__ unsigned long long g_mw_stamp[2][MW_DBG_BLOCKS][8];
 static __device__ int g_mw_val[2][MW_DBG_BLOCKS][16][4];
@@ -40,7 +43,9 @@ static __device__ unsigned long long g_mw_acc[MW_DBG_BLOCKS][8];
 #endif
 #define MW_LDS __attribute__((address_space(3)))   // mw::step_solve: its working copies of manifolds past the registers are in LDS
 #include "multiwalker_core.hpp"
+#include "multiwalker_layout.hpp"
 
+#include <memory>
 #include <new>
 #include <stdio.h>
 #include <stdlib.h>
@@ -120,7 +125,7 @@ constexpr int NL = mw::SOLVE_LANES;
 constexpr int HOT_BYTES = (int)((sizeof(mw::Hot) + 15) / 16 * 16);
 constexpr int SCR_HDR_BYTES = (int)((offsetof(mw::Scratch, m) + 15) / 16 * 16);              // Scratch without the pool
 static_assert(offsetof(mw::Scratch, m) % 16 == 0, "the manifold pool follows the header at a 16-byte boundary");
-constexpr int SOLVE_HDR_BYTES = (int)((offsetof(mw::Scratch, m_bA) + 15) / 16 * 16);         // the part of Scratch the solver and the continuous pass work on
+using mw::SOLVE_HDR_BYTES;                                                                   // the part of Scratch the solver and the continuous pass work on
 constexpr int TOI_WORK_BYTES = (int)((sizeof(mw::ToiWork) + 15) / 16 * 16);
 constexpr int TOI_LANE_BYTES = (mw::EDGE_SLOTS_HULL * 5 + 15) / 16 * 16;   // time-of-impact cache of a walker's body: 4 + 1 bytes per contact slot
 
@@ -131,7 +136,7 @@ struct GroupPar {
     static constexpr int MREG = MREG_;
     int l;
     // Wave-uniform values from which a lane finds its env's record again with nothing but its lane id (sixteen-lane class: no per-lane
-    // pointer has to stay live across the solver's sweeps, see HAVE_FUSED below): the records (live or spare), the list that maps a
+    // pointer has to stay live across the solver's sweeps, see "the one-launch form and hipcc 7.2" below): the records (live or spare), the list that maps a
     // spare slot to its env (or nullptr), the first env of this wavefront, the record stride and where the manifold pool starts in it
     const uint32_t *rec_base;
     const uint32_t *slot_env;
@@ -209,7 +214,6 @@ constexpr uint32_t SPARE_BUSY = 0xFFFFFFFFu;
 // every class is then clean under scripts/find_masked_spills.py -- tests/test_kernel_metadata.py compiles the three classes and runs that
 // scan, so a later change that brings such a copy back fails the CPU suite -- and matches the CPU build byte for byte in every lane
 // (tests/test_multiwalker_gpu.py, the "fused" cases at 3, 8, 9 and 10 walkers).
-constexpr bool HAVE_FUSED = true;
 template <int PH>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_of(PH), waves_of(PH))))
 void mw_step_kernel(const MwDev d, const MwIO io, const int mode, const int pending_only) {
@@ -391,27 +395,9 @@ __global__ void mw_init_spares_kernel(const MwDev d) {   // every spare is stale
     if (env == 0) { d.n_dirty[0] = 0; d.n_dirty[1] = (uint32_t)d.n_envs; *d.step_count = 0; }
 }
 
-__global__ void mw_get_bodies_kernel(const MwDev d, float *bodies, uint8_t *flags, float *terrain) {
-    const int64_t env = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (env >= d.n_envs) return;
-    const mw::World *wr = reinterpret_cast<const mw::World *>(d.state + env * (int64_t)d.world_dw);
-    const mw::Hot *w = &wr->h;
-    const int NB = d.model->NB, W = d.model->W, NT = d.model->NT;
-    if (bodies)
-        for (int b = 0; b < NB; ++b) {
-            float *p = bodies + (env * NB + b) * 6;
-            p[0] = w->b[b].c.x; p[1] = w->b[b].c.y; p[2] = w->b[b].a; p[3] = w->b[b].v.x; p[4] = w->b[b].v.y; p[5] = w->b[b].w;
-        }
-    if (flags) {
-        uint8_t *f = flags + env * (1 + 3 * W);
-        f[0] = w->game_over;
-        for (int k = 0; k < W; ++k) { f[1 + k] = w->fallen[k]; f[1 + W + 2 * k] = w->ground[k][0]; f[1 + W + 2 * k + 1] = w->ground[k][1]; }
-    }
-    if (terrain) for (int i = 0; i < NT; ++i) terrain[env * NT + i] = wr->c.ty[i];
-}
-
-// unpacked state (checkpoint / teacher-forcing hook); any pointer may be NULL
-__global__ void mw_get_state_kernel(const MwDev d, float *bodies, float *joints, float *aux, uint8_t *flags, float *terrain) {
+// unpacked state (inspection, checkpoint / teacher-forcing hook); any pointer may be NULL.  A flags row is game_over, fallen[W], ground[W][2]
+// and, with_overflow (1: get_state, 0: get_bodies), the sticky overflow byte: [N][1 + 3W + with_overflow]
+__global__ void mw_get_state_kernel(const MwDev d, float *bodies, float *joints, float *aux, uint8_t *flags, const int with_overflow, float *terrain) {
     const int64_t env = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (env >= d.n_envs) return;
     const mw::World *wr = reinterpret_cast<const mw::World *>(d.state + env * (int64_t)d.world_dw);
@@ -435,10 +421,10 @@ __global__ void mw_get_state_kernel(const MwDev d, float *bodies, float *joints,
             p[4] = wr->c.sleep_time[b]; p[5] = w->awake.test(b) ? 1.0f : 0.0f;
         }
     if (flags) {
-        uint8_t *f = flags + env * (2 + 3 * W);
+        uint8_t *f = flags + env * (1 + 3 * W + with_overflow);
         f[0] = w->game_over;
         for (int k = 0; k < W; ++k) { f[1 + k] = w->fallen[k]; f[1 + W + 2 * k] = w->ground[k][0]; f[1 + W + 2 * k + 1] = w->ground[k][1]; }
-        f[1 + 3 * W] = w->overflow;
+        if (with_overflow) f[1 + 3 * W] = w->overflow;
     }
     if (terrain) for (int i = 0; i < NT; ++i) terrain[env * NT + i] = wr->c.ty[i];
 }
@@ -461,118 +447,96 @@ __global__ void mw_set_state_kernel(const MwDev d, const float *bodies, const fl
         }
 }
 
-struct MwHandle {
-    madrl_multiwalker_config cfg;
-    MwDev dev;
-    int device;
-    int64_t max_blocks;
-    int use_spares, fused;
-    void *model_dev;
-    int NB, NT;
+// the handle of this class; multiwalker.hip has checked the arguments of every call that arrives here
+struct MwHandle final : madrl_multiwalker {
+    madrl_multiwalker_config cfg{};
+    MwDev dev{};
+    void *model_dev = nullptr;
+    ~MwHandle() override { if (model_dev) (void)hipFree(model_dev); }   // the one place that frees: destroy, and every error path of k_create
+
+    // THE launch sequence of an API call.  is_step: MultiWalkerEnv.step -- begin-step (auto-reset only: without it no spare is ever built and
+    // nothing looks at the call's number), the step with the spares to rebuild in its leading blocks, then the second pass for the envs
+    // without a ready spare; else reset + trailing step of the envs io.mask selects.  A b2World::Step is one launch or three (set_mode).
+    int launch(const MwIO &io, bool is_step, void *stream) {
+        const hipStream_t s = (hipStream_t)stream;
+        MwDev d = dev;
+        d.spare_blocks = 0;
+        const int32_t env_blocks = (int32_t)((d.n_envs + EPW - 1) / EPW);   // every group of EPW envs gets its own wavefront
+        const auto world_step = [&](int mode, int pending_only) {
+            const dim3 blocks((unsigned)(env_blocks + d.spare_blocks));
+            if (fused) {
+                hipLaunchKernelGGL(mw_step_kernel<PH_ALL>, blocks, dim3(64), (size_t)EPW * d.lds_stride[0], s, d, io, mode, pending_only);
+            } else {
+                hipLaunchKernelGGL(mw_step_kernel<PH_COLLIDE>, blocks, dim3(64), (size_t)EPW * d.lds_stride[1], s, d, io, mode, pending_only);
+                hipLaunchKernelGGL(mw_step_kernel<PH_SOLVE>, blocks, dim3(64), (size_t)EPW * d.lds_stride[2], s, d, io, mode, pending_only);
+                hipLaunchKernelGGL(mw_step_kernel<PH_TOI>, blocks, dim3(64), (size_t)EPW * d.lds_stride[3], s, d, io, mode, pending_only);
+            }
+        };
+        if (!is_step) {
+            world_step(1, 0);
+        } else if (!cfg.auto_reset) {
+            world_step(0, 0);
+        } else {
+            hipLaunchKernelGGL(mw_begin_step_kernel, dim3(1), dim3(64), 0, s, d, use_spares);
+            if (use_spares) d.spare_blocks = env_blocks;   // room for every spare (a common horizon ends all episodes at once); mostly a handful do something
+            world_step(0, 0);
+            d.spare_blocks = 0;
+            world_step(1, 1);
+        }
+        MADRL_HIP_TRY(hipGetLastError());
+        return MADRL_OK;
+    }
+    int reset(const uint8_t *mask, const double *terrain, const double *push, float *obs, void *stream) override {
+        MwIO io{};
+        io.mask = mask;
+        io.inj_terrain = terrain;
+        io.inj_push = push;
+        io.obs = obs;
+        return launch(io, false, stream);
+    }
+    int step(const float *actions, float *obs, float *rew, uint8_t *done, void *stream) override {
+        MwIO io{};
+        io.actions = actions;
+        io.obs = obs;
+        io.rew = rew;
+        io.done = done;
+        return launch(io, true, stream);
+    }
+    int get_state(float *bodies, float *joints, float *aux, uint8_t *flags, int with_overflow, float *terrain, void *stream) override {
+        hipLaunchKernelGGL(mw_get_state_kernel, dim3((unsigned)((dev.n_envs + 63) / 64)), dim3(64), 0, (hipStream_t)stream, dev, bodies, joints, aux,
+                           flags, with_overflow, terrain);
+        MADRL_HIP_TRY(hipGetLastError());
+        return MADRL_OK;
+    }
+    int set_state(const float *bodies, const float *joints, void *stream) override {
+        hipLaunchKernelGGL(mw_set_state_kernel, dim3((unsigned)((dev.n_envs + 63) / 64)), dim3(64), 0, (hipStream_t)stream, dev, bodies, joints);
+        MADRL_HIP_TRY(hipGetLastError());
+        return MADRL_OK;
+    }
 };
 
-size_t mw_scratch_bytes(const mw::Model &M) {   // the schedule between launches, then the manifold pool of a step (Model::max_manifolds entries)
-    return (size_t)SOLVE_HDR_BYTES + align_up((size_t)M.max_manifolds * sizeof(mw::Manifold), 16);
-}
-
-int mw_validate(const madrl_multiwalker_config *c) {
-    if (!c) return fail(MADRL_EINVAL, "config is NULL");
-    if (c->struct_size != (int32_t)sizeof(madrl_multiwalker_config))
-        return fail(MADRL_EINVAL, "madrl_multiwalker_config.struct_size=%d, library expects %d", c->struct_size,
-                    (int)sizeof(madrl_multiwalker_config));
-    if (c->n_walkers < 1 || c->n_walkers > mw::MAX_WALKERS)   // (the C ABI picked this class by n_walkers: multiwalker.hip)
-        return fail(MADRL_EINVAL, "n_walkers=%d unsupported by the %d-walker class", c->n_walkers, mw::MAX_WALKERS);
-    return MADRL_OK;
-}
-
-void mw_launch_step(const MwHandle *h, const MwDev &d, const MwIO &io, int mode, int pending_only, hipStream_t s) {
-    const unsigned blocks = (unsigned)((d.n_envs + EPW - 1) / EPW + d.spare_blocks);   // every group of EPW envs gets its own wavefront
-    if (h->fused && HAVE_FUSED) {
-        hipLaunchKernelGGL(mw_step_kernel<HAVE_FUSED ? PH_ALL : PH_COLLIDE>, dim3(blocks), dim3(64), (size_t)EPW * d.lds_stride[0], s, d, io, mode, pending_only);
-    } else {
-        hipLaunchKernelGGL(mw_step_kernel<PH_COLLIDE>, dim3(blocks), dim3(64), (size_t)EPW * d.lds_stride[1], s, d, io, mode, pending_only);
-        hipLaunchKernelGGL(mw_step_kernel<PH_SOLVE>, dim3(blocks), dim3(64), (size_t)EPW * d.lds_stride[2], s, d, io, mode, pending_only);
-        hipLaunchKernelGGL(mw_step_kernel<PH_TOI>, dim3(blocks), dim3(64), (size_t)EPW * d.lds_stride[3], s, d, io, mode, pending_only);
-    }
-}
-void mw_launch_all(MwHandle *h, const MwIO &io, int mode, hipStream_t s) {
-    MwDev d = h->dev;
-    d.spare_blocks = 0;
-    if (mode == 1) {   // MultiWalkerEnv.step
-        if (h->cfg.auto_reset) {   // (without auto-reset no spare is ever built and nothing looks at the call's number)
-            hipLaunchKernelGGL(mw_begin_step_kernel, dim3(1), dim3(64), 0, s, d, h->use_spares);
-            if (h->use_spares) d.spare_blocks = (int32_t)((d.n_envs + EPW - 1) / EPW);   // room for every spare (a common horizon ends all episodes at once); mostly a handful do something
-        }
-        mw_launch_step(h, d, io, 0, 0, s);
-        if (!h->cfg.auto_reset) return;
-        d.spare_blocks = 0;
-        mw_launch_step(h, d, io, 1, 1, s);   // envs without a ready spare
-        return;
-    }
-    mw_launch_step(h, d, io, 1, 0, s);
-}
-
-int mw_launch(MwHandle *h, const MwIO &io, int mode, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    mw_launch_all(h, io, mode, s);
-    MADRL_HIP_TRY(hipGetLastError());
-    return MADRL_OK;
-}
-
-int k_obs_dim(const madrl_multiwalker_config *cfg, int32_t *out_dim) {
-    int rc = mw_validate(cfg);
-    if (rc) return rc;
-    if (!out_dim) return fail(MADRL_EINVAL, "out_dim is NULL");
-    *out_dim = mw::OBS_DIM - 1 + (cfg->one_hot ? mw::MAX_AGENTS_ID : 1);
-    return MADRL_OK;
-}
-
-int k_state_bytes(const madrl_multiwalker_config *cfg, int64_t n_envs, uint64_t *out_bytes) {
-    int rc = mw_validate(cfg);
-    if (rc) return rc;
-    if (n_envs < 1 || !out_bytes) return fail(MADRL_EINVAL, "n_envs must be >= 1 and out_bytes non-NULL");
+uint64_t k_state_bytes(const madrl_multiwalker_config *cfg, int64_t n_envs) {
     mw::Model M;
-    memset(&M, 0, sizeof(M));
-    mw::build_model(M, cfg->n_walkers);
-    // per env: the world record, then the step's Scratch (manifolds + schedule handed from launch to launch); one byte per env; then the
-    // spares: a second record per env, its observation, three dwords per env (state, two lists), four dwords: the lists' lengths, the step() counter, one unused
-    const uint64_t rec = (uint64_t)(align_up(sizeof(mw::World), 16) + mw_scratch_bytes(M));
-    const uint64_t od = (uint64_t)cfg->n_walkers * (uint64_t)(mw::OBS_DIM - 1 + (cfg->one_hot ? mw::MAX_AGENTS_ID : 1));
-    *out_bytes = rec * (uint64_t)n_envs + align_up((uint64_t)n_envs, 16) + rec * (uint64_t)n_envs + align_up(od * 4 * (uint64_t)n_envs, 16) + 12 * (uint64_t)n_envs + 16;
-    return MADRL_OK;
+    mw::host_model(M, cfg->n_walkers);
+    return mw::mw_layout(M, cfg->one_hot, n_envs).total;
 }
 
-int k_create(const madrl_multiwalker_config *cfg, int64_t n_envs, int32_t device, void *state_dev,
-                             void **out) {
-    int rc = mw_validate(cfg);
-    if (rc) return rc;
-    if (!state_dev || !out || n_envs < 1) return fail(MADRL_EINVAL, "create: NULL argument or n_envs < 1");
-    rc = check_env_ids(n_envs, cfg->env_id_base);
-    if (rc) return rc;
+int k_create(const madrl_multiwalker_config *cfg, int64_t n_envs, int32_t device, void *state_dev, madrl_multiwalker **out) {
     MADRL_HIP_TRY(hipSetDevice(device));
-    MwHandle *h = new (std::nothrow) MwHandle();
+    std::unique_ptr<MwHandle> h(new (std::nothrow) MwHandle());   // ~MwHandle frees whatever an early return leaves behind
     if (!h) return fail(MADRL_ENOMEM, "out of host memory");
     h->cfg = *cfg;
-    h->device = device;
-    h->max_blocks = 0;
     mw::Model M;
-    memset(&M, 0, sizeof(M));
-    mw::build_model(M, cfg->n_walkers);
+    mw::host_model(M, cfg->n_walkers);
     M.continuous = cfg->discrete_only ? 0 : 1;
     M.poly_rev = cfg->polygon_revision ? 1 : 0;
 #ifdef MADRL_EXPERIMENTS   // measurement builds only (scripts/variants.sh): the production library takes nothing from the process environment
     if (const char *e = getenv("MADRL_MW_TOI")) M.continuous = atoi(e);  // 0 = no continuous pass, 2 = candidates only
 #endif
-    h->NB = M.NB; h->NT = M.NT;
     hipError_t e = hipMalloc(&h->model_dev, sizeof(M));
     if (e == hipSuccess) e = hipMemcpy(h->model_dev, &M, sizeof(M), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (h->model_dev) (void)hipFree(h->model_dev);
-        delete h;
-        return fail(MADRL_EHIP, "model upload failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(MADRL_EHIP, "model upload failed: %s", hipGetErrorString(e));
     MwDev &d = h->dev;
-    memset(&d, 0, sizeof(d));
     d.cfg.n_walkers = cfg->n_walkers; d.cfg.reward_global = cfg->reward_global; d.cfg.terminate_on_fall = cfg->terminate_on_fall;
     d.cfg.one_hot = cfg->one_hot ? 1 : 0; d.cfg.max_steps = cfg->max_steps; d.cfg.auto_reset = cfg->auto_reset;
     d.cfg.position_noise = (float)cfg->position_noise; d.cfg.angle_noise = (float)cfg->angle_noise;
@@ -580,22 +544,17 @@ int k_create(const madrl_multiwalker_config *cfg, int64_t n_envs, int32_t device
     d.cfg.drop_reward = (float)cfg->drop_reward;
     d.cfg.k0 = (uint32_t)cfg->seed; d.cfg.k1 = (uint32_t)(cfg->seed >> 32);
     d.gid_base = (uint32_t)cfg->env_id_base;
-    d.scratch_bytes = (int32_t)mw_scratch_bytes(M);
-    d.scratch_off_dw = (int32_t)(align_up(sizeof(mw::World), 16) / 4);
-    d.world_dw = d.scratch_off_dw + d.scratch_bytes / 4;
-    d.pending = (uint8_t *)state_dev + (size_t)d.world_dw * 4 * (size_t)n_envs;
-    {
-        unsigned char *p = d.pending + align_up((size_t)n_envs, 16);
-        d.spare_state = (uint32_t *)p; p += (size_t)d.world_dw * 4 * (size_t)n_envs;
-        d.spare_obs = (float *)p; p += align_up((size_t)cfg->n_walkers * (size_t)mw::obs_dim_of(d.cfg) * 4 * (size_t)n_envs, 16);
-        d.ready_step = (uint32_t *)p; p += 4 * (size_t)n_envs;
-        d.dirty_list = (uint32_t *)p; p += 8 * (size_t)n_envs;
-        d.n_dirty = (uint32_t *)p;
-        d.step_count = d.n_dirty + 2;   // (the third of the four dwords behind the lists)
-    }
-    d.cold_q = (int32_t)(align_up(offsetof(mw::Cold, slot) + (size_t)M.n_slots * sizeof(mw::Slot), 16) / 16);
-    h->use_spares = 1;
-    h->fused = 0;
+    const mw::MwLayout L = mw::mw_layout(M, cfg->one_hot, n_envs);
+    unsigned char *const buf = (unsigned char *)state_dev;
+    d.world_dw = L.world_dw; d.scratch_off_dw = L.scratch_off_dw; d.scratch_bytes = L.scratch_bytes; d.cold_q = L.cold_q;
+    d.state = (uint32_t *)(buf + L.records);
+    d.pending = buf + L.pending;
+    d.spare_state = (uint32_t *)(buf + L.spare_state);
+    d.spare_obs = (float *)(buf + L.spare_obs);
+    d.ready_step = (uint32_t *)(buf + L.ready_step);
+    d.dirty_list = (uint32_t *)(buf + L.dirty_list);
+    d.n_dirty = (uint32_t *)(buf + L.n_dirty);
+    d.step_count = (uint32_t *)(buf + L.step_count);
     d.ty_bytes = (int32_t)align_up((size_t)M.NT * 4, 16);
     d.toi_lane0_bytes = (int32_t)align_up((size_t)(M.slot_cap[0] > mw::EDGE_SLOTS_HULL ? M.slot_cap[0] : mw::EDGE_SLOTS_HULL) * 5, 16);
     {
@@ -616,144 +575,22 @@ int k_create(const madrl_multiwalker_config *cfg, int64_t n_envs, int32_t device
     }
     d.n_envs = n_envs;
     d.model = (const mw::Model *)h->model_dev;
-    d.state = (uint32_t *)state_dev;
 #ifdef MADRL_EXPERIMENTS
     if (getenv("MADRL_MW_VERBOSE")) fprintf(stderr, "multiwalker: LDS per env %d (one launch) | %d %d %d (collide, solve, continuous pass)\n", d.lds_stride[0], d.lds_stride[1], d.lds_stride[2], d.lds_stride[3]);
 #endif
     hipLaunchKernelGGL(mw_init_spares_kernel, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, 0, d);
-    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) { (void)hipFree(h->model_dev); delete h; return fail(MADRL_EHIP, "state buffer too small or not device memory"); }
-    *out = h;
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail(MADRL_EHIP, "state buffer too small or not device memory");
+    h->cap_walkers = mw::MAX_WALKERS; h->lanes = NL;
+    h->n_bodies = M.NB; h->n_terrain = M.NT;
+    h->stride_bytes = d.world_dw * 4; h->world_bytes = (int32_t)sizeof(mw::World);
+    *out = h.release();
     return MADRL_OK;
 }
-
-void k_destroy(MwHandle *h) {
-    if (!h) return;
-    if (h->model_dev) (void)hipFree(h->model_dev);
-    delete h;
-}
-
-int k_set_mode(MwHandle *h, int32_t fused, int32_t use_spares) {
-    if (!h || (fused & ~1) || (use_spares & ~1)) return fail(MADRL_EINVAL, "set_mode: handle is NULL or a flag is not 0 / 1");
-    h->fused = fused;
-    h->use_spares = use_spares;
-    return MADRL_OK;
-}
-
-#if defined(MADRL_MW_TIMING)
-int k_debug_read(unsigned long long *stamps_host, int *vals_host) {   // [2][4096][8], [2][4096][16][4]
-    MADRL_HIP_TRY(hipDeviceSynchronize());
-    MADRL_HIP_TRY(hipMemcpyFromSymbol(stamps_host, HIP_SYMBOL(g_mw_stamp), sizeof(g_mw_stamp)));
-    MADRL_HIP_TRY(hipMemcpyFromSymbol(vals_host, HIP_SYMBOL(g_mw_val), sizeof(g_mw_val)));
-    return MADRL_OK;
-}
-int k_debug_read_acc(unsigned long long *acc_host, int reset) {   // [4096][8]; reset != 0: zero the accumulators afterwards
-    MADRL_HIP_TRY(hipDeviceSynchronize());
-    MADRL_HIP_TRY(hipMemcpyFromSymbol(acc_host, HIP_SYMBOL(g_mw_acc), sizeof(g_mw_acc)));
-    if (reset) { static unsigned long long zero[MW_DBG_BLOCKS][8]; MADRL_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_mw_acc), zero, sizeof(zero))); }
-    return MADRL_OK;
-}
-#endif
-
-int k_dims(const MwHandle *h, int32_t *n_bodies, int32_t *n_terrain) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    if (n_bodies) *n_bodies = h->NB;
-    if (n_terrain) *n_terrain = h->NT;
-    return MADRL_OK;
-}
-
-int k_record_bytes(const MwHandle *h, int32_t *stride_bytes, int32_t *world_bytes) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    if (stride_bytes) *stride_bytes = h->dev.world_dw * 4;
-    if (world_bytes) *world_bytes = (int32_t)sizeof(mw::World);
-    return MADRL_OK;
-}
-
-int k_reset(MwHandle *h, const uint8_t *mask_dev, float *obs_dev, void *stream) {
-    if (!h || !obs_dev) return fail(MADRL_EINVAL, "reset: handle/obs is NULL");
-    MwIO io;
-    memset(&io, 0, sizeof(io));
-    io.mask = mask_dev;
-    io.obs = obs_dev;
-    return mw_launch(h, io, 0, stream);
-}
-
-int k_reset_with(MwHandle *h, const uint8_t *mask_dev, const double *terrain_dev, const double *push_dev,
-                                 float *obs_dev, void *stream) {
-    if (!h || !obs_dev) return fail(MADRL_EINVAL, "reset: handle/obs is NULL");
-    MwIO io;
-    memset(&io, 0, sizeof(io));
-    io.mask = mask_dev;
-    io.inj_terrain = terrain_dev;
-    io.inj_push = push_dev;
-    io.obs = obs_dev;
-    return mw_launch(h, io, 0, stream);
-}
-
-int k_get_state(MwHandle *h, float *bodies_dev, float *joints_dev, float *aux_dev, uint8_t *flags_dev,
-                                float *terrain_dev, void *stream) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    const unsigned blocks = (unsigned)((h->dev.n_envs + 63) / 64);
-    hipLaunchKernelGGL(mw_get_state_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream, h->dev, bodies_dev, joints_dev, aux_dev,
-                       flags_dev, terrain_dev);
-    MADRL_HIP_TRY(hipGetLastError());
-    return MADRL_OK;
-}
-
-int k_set_state(MwHandle *h, const float *bodies_dev, const float *joints_dev, void *stream) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    const unsigned blocks = (unsigned)((h->dev.n_envs + 63) / 64);
-    hipLaunchKernelGGL(mw_set_state_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream, h->dev, bodies_dev, joints_dev);
-    MADRL_HIP_TRY(hipGetLastError());
-    return MADRL_OK;
-}
-
-int k_step(MwHandle *h, const float *actions_dev, float *obs_dev, float *rew_dev,
-                           uint8_t *done_dev, void *stream) {
-    if (!h || !actions_dev || !obs_dev || !rew_dev || !done_dev) return fail(MADRL_EINVAL, "step: NULL argument");
-    MwIO io;
-    memset(&io, 0, sizeof(io));
-    io.actions = actions_dev;
-    io.obs = obs_dev;
-    io.rew = rew_dev;
-    io.done = done_dev;
-    return mw_launch(h, io, 1, stream);
-}
-
-int k_get_bodies(MwHandle *h, float *bodies_dev, uint8_t *flags_dev, float *terrain_dev,
-                                 void *stream) {
-    if (!h) return fail(MADRL_EINVAL, "handle is NULL");
-    const unsigned blocks = (unsigned)((h->dev.n_envs + 63) / 64);
-    hipLaunchKernelGGL(mw_get_bodies_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream, h->dev, bodies_dev, flags_dev,
-                       terrain_dev);
-    MADRL_HIP_TRY(hipGetLastError());
-    return MADRL_OK;
-}
-
-// the handle crosses the class boundary as void *
-int a_create(const madrl_multiwalker_config *cfg, int64_t n_envs, int32_t device, void *state_dev, void **out) { return k_create(cfg, n_envs, device, state_dev, out); }
-void a_destroy(void *h) { k_destroy((MwHandle *)h); }
-int a_set_mode(void *h, int32_t fused, int32_t use_spares) { return k_set_mode((MwHandle *)h, fused, use_spares); }
-int a_dims(const void *h, int32_t *nb, int32_t *nt) { return k_dims((const MwHandle *)h, nb, nt); }
-int a_record_bytes(const void *h, int32_t *stride, int32_t *world) { return k_record_bytes((const MwHandle *)h, stride, world); }
-int a_reset(void *h, const uint8_t *mask, float *obs, void *stream) { return k_reset((MwHandle *)h, mask, obs, stream); }
-int a_reset_with(void *h, const uint8_t *mask, const double *terrain, const double *push, float *obs, void *stream) { return k_reset_with((MwHandle *)h, mask, terrain, push, obs, stream); }
-int a_get_state(void *h, float *bodies, float *joints, float *aux, uint8_t *flags, float *terrain, void *stream) { return k_get_state((MwHandle *)h, bodies, joints, aux, flags, terrain, stream); }
-int a_set_state(void *h, const float *bodies, const float *joints, void *stream) { return k_set_state((MwHandle *)h, bodies, joints, stream); }
-int a_step(void *h, const float *actions, float *obs, float *rew, uint8_t *done, void *stream) { return k_step((MwHandle *)h, actions, obs, rew, done, stream); }
-int a_get_bodies(void *h, float *bodies, uint8_t *flags, float *terrain, void *stream) { return k_get_bodies((MwHandle *)h, bodies, flags, terrain, stream); }
 
 }  // namespace MW_KNS
 using namespace MW_KNS;
 
 #if !defined(__HIP_DEVICE_COMPILE__)   // (a table of host functions: nothing for the device pass, which would emit any const global)
-extern const madrl::MwClassApi MW_CAT_(madrl_mw_class_c, MW_CAPW);
-const madrl::MwClassApi MW_CAT_(madrl_mw_class_c, MW_CAPW) = {
-    mw::MAX_WALKERS, NL, k_obs_dim, k_state_bytes, a_create, a_destroy, a_set_mode, a_dims, a_record_bytes, a_reset, a_reset_with, a_get_state,
-    a_set_state, a_step, a_get_bodies,
-#if defined(MADRL_MW_TIMING)
-    k_debug_read, k_debug_read_acc,
-#else
-    nullptr, nullptr,
-#endif
-};
+extern const madrl::MwClass MW_CAT_(madrl_mw_class_c, MW_CAPW);
+const madrl::MwClass MW_CAT_(madrl_mw_class_c, MW_CAPW) = {mw::MAX_WALKERS, NL, mw::host_obs_dim, k_state_bytes, k_create};
 #endif

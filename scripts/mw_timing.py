@@ -1,5 +1,6 @@
-"""Where a MultiWalker step's time goes, per wavefront (measurement build: SRC=multiwalker MACRO=MADRL_MW_TIMING EXTRA=-fno-slp-vectorize
-scripts/variants.sh 1; run with MADRL_HIP_LIB=scripts/_variants/libmadrl_hip.multiwalker.1.so).  s_memtime stamps of every wavefront of the
+"""Where a MultiWalker step's time goes, per wavefront (measurement build: SRC=multiwalker_c4 MACRO=MADRL_MW_TIMING EXTRA=-fno-slp-vectorize
+scripts/variants.sh 1 -- the four-walker class alone, which then defines madrl_multiwalker_debug_read / _debug_read_acc; run with
+MADRL_HIP_LIB=scripts/_variants/libmadrl_hip.multiwalker_c4.1.so).  s_memtime stamps of every wavefront of the
 solver launch and of the continuous-pass launch of ONE step in rollout steady state, with the per-env counters that explain them
 (longest lane list, position iterations, continuous-pass events)."""
 import ctypes as C

@@ -107,8 +107,8 @@ def _mk(W, N, **kw):
 
 
 def _spare_tail(env):
-    """(ready_step [N], dirty_list [2, N], the four dwords behind them) from the end of the env's state tensor, as k_state_bytes / k_create lay
-    it out -- after checking that layout against madrl_multiwalker_state_bytes"""
+    """(ready_step [N], dirty_list [2, N], the four dwords behind them) from the end of the env's state tensor, as mw_layout (madrl_amd/csrc/multiwalker_layout.hpp)
+    lays it out -- after checking that layout against madrl_multiwalker_state_bytes"""
     from madrl_amd import _lib
     N, W = env.n_envs, int(env.n_walkers)
     up16 = lambda x: (x + 15) // 16 * 16
